@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: factorize GFLOP/s (fp64) of the MI355X engine.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one complete numerical factorization (spllt_factor -> spllt_wait,
 reference timing window drivers/spllt_omp.F90:185-192) of the workload, with
 `val` already resident in HBM and L left device-resident.  GFLOP/s = F_sym / t
 with F_sym the reference's own symbolic flop count
 (src/spllt_analyse_mod.F90:1007-1023).  Prints ONE JSON line on rank 0.
+
+A plain single-GPU run sets up, warms up, times the K steps and prints the line
+(`roofline` and `cpu_baseline` null).  --full adds everything else: drop-in
+variant, accuracy check against the CPU oracle, roofline and per-launch profile,
+timeline, CPU baseline, DGEMM reference, two handles in flight, the small and the
+other BASELINE configurations.  --dump-outputs DIR writes the factor of the last
+timed step (a fixed sample of it) as DIR/L.npy.
 """
 import argparse
 import json
@@ -44,8 +51,32 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--profile-out", default=None, help="write the per-launch timing table here")
-    return ap.parse_args()
+    ap.add_argument("--profile-out", default=None, help="write the per-launch timing table here (needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: check, roofline, CPU baseline and the other configurations")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the factor computed by the last timed step to DIR/L.npy (single GPU)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.profile_out and not args.full:
+        ap.error("--profile-out needs --full (the per-launch table is part of the profile)")
+    return args
+
+
+# entries of L that --dump-outputs writes at most: 32 MiB of float64
+DUMP_ENTRIES = 1 << 22
+
+
+def dump_outputs(out_dir, f):
+    """What a caller of the timed path receives: the factor L (the whole arena, float64).  An arena
+    of more than DUMP_ENTRIES entries is sampled at fixed positions (seed 0, sorted), so the same
+    arguments dump the same entries on every run and every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    L = f.get_factor()
+    if L.size > DUMP_ENTRIES:
+        L = L[np.sort(np.random.default_rng(0).integers(0, L.size, DUMP_ENTRIES))]
+    np.save(os.path.join(out_dir, "L.npy"), np.ascontiguousarray(L, dtype=np.float64))
 
 
 def build_workload(args):
@@ -261,6 +292,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if world > 1 and args.dump_outputs:
+        sys.exit("bench.py: --dump-outputs needs a single-GPU run")
     import torch
     import torch.distributed as dist
     if world > 1:
@@ -316,6 +349,37 @@ def main():
     t_total = time.perf_counter() - t0
     ms_per_step = t_total / args.steps * 1e3
     value = flops / (t_total / args.steps) / 1e9
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, f)
+    out = {
+        "metric": "factorize GFLOP/s (fp64)", "value": round(value, 2), "unit": "GFLOP/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": name, "stand_in_for": "SuiteSparse ND/nd24k" if "nd24k" in name else None,
+                   "n": n, "nnz_lower": int(si["nnz_a"]), "nb": nb, "nnz_L": int(si["nnz_l"]),
+                   "flops_sym": flops, "nnodes": int(si["nnodes"]), "ordering": si["ordering"] + ("/geometric-nd" if order is not None else ""),
+                   "parallelism": "1 GPU, level-batched stream DAG (chain / bulk / far streams, zone pipeline)"},
+        "roofline": None, "cpu_baseline": None,
+        "detail": {"device_ms_per_step": round(float(np.mean(dev_ms)), 3),
+                   "host_submit_ms_per_step": round(float(np.mean(sub_ms)), 3), "analyse_s": round(t_analyse, 2),
+                   "launches": f.times()["launches"],
+                   "engine_flags": int(os.environ.get("SPLLT_ENGINE_FLAGS", "0")), "nemin": args.nemin},
+    }
+    if args.full:
+        out["roofline"], out["cpu_baseline"], more = full_measurements(args, A, n, ptr, row, val, order, nb, name,
+                                                                       f, dval, flops, value)
+        out["detail"].update(more)
+    print(json.dumps(out))
+
+
+def full_measurements(args, A, n, ptr, row, val, order, nb, name, f, dval, flops, value):
+    """--full: everything beside the headline, measured after the timed steps with the same handle
+    (closed here before the other configurations run).  Returns the line's `roofline` and
+    `cpu_baseline` and what it adds to `detail`."""
+    import torch
+    from spllt_amd import api
 
     # drop-in variant (H2D of val + D2H of L), reported separately, never `value`
     t0 = time.perf_counter()
@@ -470,27 +534,14 @@ def main():
         for other in ("poisson3d_128", "serena_like") + (() if os.environ.get("SPLLT_NO_FLAN") else ("flan_like",)):
             if other != args.config:
                 extra.append(run_extra_config(other))
-    out = {
-        "metric": "factorize GFLOP/s (fp64)", "value": round(value, 2), "unit": "GFLOP/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": name, "stand_in_for": "SuiteSparse ND/nd24k" if "nd24k" in name else None,
-                   "n": n, "nnz_lower": int(si["nnz_a"]), "nb": nb, "nnz_L": int(si["nnz_l"]),
-                   "flops_sym": flops, "nnodes": int(si["nnodes"]), "ordering": si["ordering"] + ("/geometric-nd" if order is not None else ""),
-                   "parallelism": "1 GPU, level-batched stream DAG (chain / bulk / far streams, zone pipeline)"},
-        "roofline": roof, "cpu_baseline": cpu,
-        "detail": {"device_ms_per_step": round(float(np.mean(dev_ms)), 3),
-                   "host_submit_ms_per_step": round(float(np.mean(sub_ms)), 3), "analyse_s": round(t_analyse, 2),
-                   "dropin_factor_s": round(t_h2d, 4), "L_d2h_s": round(t_d2h, 4), "L_d2h_warm_s": round(t_d2h_warm, 4),
-                   "L_d2h_warm_GBps": round(L.nbytes / max(t_d2h_warm, 1e-9) / 1e9, 2),
-                   "device_solve_s": None if t_solve is None else round(t_solve, 5),
-                   "launches": nlaunch, "kernel_table": table, "timeline": level_done, "check": check,
-                   "engine_flags": int(os.environ.get("SPLLT_ENGINE_FLAGS", "0")), "nemin": args.nemin,
-                   "dgemm_reference": dgemm_ref, "two_handles_in_flight": two_handles, "configs": extra,
-                   "small_configs": small},
-    }
-    print(json.dumps(out))
+
+    detail = {"dropin_factor_s": round(t_h2d, 4), "L_d2h_s": round(t_d2h, 4), "L_d2h_warm_s": round(t_d2h_warm, 4),
+              "L_d2h_warm_GBps": round(L.nbytes / max(t_d2h_warm, 1e-9) / 1e9, 2),
+              "device_solve_s": None if t_solve is None else round(t_solve, 5),
+              "launches": nlaunch, "kernel_table": table, "timeline": level_done, "check": check,
+              "dgemm_reference": dgemm_ref, "two_handles_in_flight": two_handles, "configs": extra,
+              "small_configs": small}
+    return roof, cpu, detail
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ mkdir -p $OUT
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg timeout -k 10 300 python bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-check ${BENCH_ARGS} > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { tail -3 $OUT/ab_$i.err; exit 1; }
+  env $cfg timeout -k 10 300 python bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-check ${BENCH_ARGS} > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { tail -3 $OUT/ab_$i.err; exit 1; }
   python - "$cfg" $OUT/ab_$i.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ for r in $(seq 1 $R); do
   for v in A B; do
     lib=$2; [ $v = B ] && lib=$3
     cp $lib spllt_amd/libspllt_hip.so
-    timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-check --no-extra-configs ${BENCH_ARGS} --profile-out $OUT/table_$v.txt > $OUT/b_$v.json 2> $OUT/b_$v.err || { tail -3 $OUT/b_$v.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-check --no-extra-configs ${BENCH_ARGS} --profile-out $OUT/table_$v.txt > $OUT/b_$v.json 2> $OUT/b_$v.err || { tail -3 $OUT/b_$v.err; exit 1; }
     python - $v $lib $OUT/b_$v.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[3]).read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 # (the library destroys its pooled CU-masked streams at exit only when asked: rocprofv3 crashes on live ones)
 cd /tmp
-B="--steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extra-configs $ARGS"
+B="--full --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extra-configs $ARGS"
 FAILED=0
 # a pass whose process aborts at exit (round 2: SIGSEGV in __cxa_finalize with pooled CU-masked
 # streams still alive when the runtime unloaded) still leaves its CSVs behind: say so, loudly

@@ -19,11 +19,11 @@ timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 rc=$?; echo "smoke rc=$rc" | tee -a $OUT/status_$TAG.txt; tail -2 $OUT/smoke_$TAG.log
 [ $rc -ne 0 ] && exit $rc
 echo "== bench" | tee -a $OUT/status_$TAG.txt
-timeout -k 10 600 python bench.py --steps 5 --warmup 2 --profile-out $OUT/launch_table_$TAG.txt > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 --profile-out $OUT/launch_table_$TAG.txt > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?; echo "bench rc=$rc" | tee -a $OUT/status_$TAG.txt; tail -c 1500 $OUT/bench_$TAG.json; tail -2 $OUT/bench_$TAG.err
 [ $rc -ne 0 ] && exit $rc
 if [ -n "$WITH_FLAN" ]; then
-  timeout -k 10 600 python bench.py --steps 2 --warmup 1 --config flan_like --no-cpu-baseline --no-extra-configs > $OUT/bench_flan_$TAG.json 2> $OUT/bench_flan_$TAG.err; echo "flan rc=$?"; tail -c 600 $OUT/bench_flan_$TAG.json
+  timeout -k 10 600 python bench.py --full --steps 2 --warmup 1 --config flan_like --no-cpu-baseline --no-extra-configs > $OUT/bench_flan_$TAG.json 2> $OUT/bench_flan_$TAG.err; echo "flan rc=$?"; tail -c 600 $OUT/bench_flan_$TAG.json
 fi
 [ -x bin_tmp/cumask_probe ] && ./bin_tmp/cumask_probe > $OUT/cumask_probe_$TAG.txt 2>&1
 for v in 16_4_2 32_4_2 16_2_4 16_2_2; do [ -x bin_tmp/ub_$v ] && { echo "== 128-tile BK_WM_WN=$v"; ./bin_tmp/ub_$v 8192 8192 | grep "T=128"; } ; done > $OUT/update_bench_128_variants_$TAG.txt 2>&1

@@ -1093,7 +1093,7 @@ def test_submission_deadline():
 
 
 def test_bench_contract_one_gpu():
-    """`python bench.py` on a shrunken workload: ONE JSON line with the driver's fields, the
+    """`python bench.py --full` on a shrunken workload: ONE JSON line with the driver's fields, the
     roofline object (dominant kernel, alone and inside the program) and the CPU baseline of the
     oracle on the same workload; the accuracy gate inside must pass."""
     import json
@@ -1101,7 +1101,7 @@ def test_bench_contract_one_gpu():
     import subprocess
     import sys
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                         "--scale", "0.5", "--no-extra-configs"], capture_output=True, text=True, timeout=280,
                        cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1120,6 +1120,40 @@ def test_bench_contract_one_gpu():
     assert cpu["kind"] == "port" and cpu["cores"] >= 1 and cpu["value"] > 0 and cpu["sample"]
     chk = d["detail"]["check"]
     assert chk["bwd_err"] <= 1e-14 and chk["max_relerr_L_vs_cpu"] <= 1e-12
+
+
+def test_bench_plain_run_dumps_the_factor_of_its_last_step(tmp_path):
+    """`python bench.py` without --full: ONE JSON line with the headline only (`roofline` and
+    `cpu_baseline` null, nothing of --full under `detail`, `steps` as asked), and --dump-outputs DIR
+    writes the factor of the last timed step: DIR/L.npy, float64, at most 64 MB -- an arena larger
+    than 2^22 entries sampled at sorted positions drawn with seed 0 -- equal to the same entries of
+    the factor of the same workload computed here."""
+    import json
+    import subprocess
+    import sys
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                        "--scale", "0.5", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True,
+                       timeout=280, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["metric"] == "factorize GFLOP/s (fp64)" and d["unit"] == "GFLOP/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and d["roofline"] is None and d["cpu_baseline"] is None
+    assert not {"check", "kernel_table", "configs", "small_configs"} & set(d["detail"]), d["detail"]
+    assert os.listdir(tmp_path / "out") == ["L.npy"]
+    got = np.load(tmp_path / "out" / "L.npy")
+    assert got.dtype == np.float64 and got.nbytes <= 64 * 2**20
+    A, order, cfg = matgen.build_config("nd24k_like", 0.5)
+    f, val = make_case(A, nb=cfg["nb"], nemin=32, order=order)
+    f.factor(val).wait()
+    L = f.get_factor()
+    f.close()
+    assert L.size > 2**22 and got.size == 2**22
+    ref = L[np.sort(np.random.default_rng(0).integers(0, L.size, 2**22))]
+    assert rel_err(got, ref) <= 1e-12
 
 
 @pytest.mark.parametrize("flags", [0, 2, 4096])
