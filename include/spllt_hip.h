@@ -270,6 +270,23 @@ int spllt_hip_get_factor(void *fkeep, double *out, int64_t count);
 /* device pointer of the L arena (valid until spllt_deallocate_fkeep) */
 /* (partitioned factorization: the rank's packed arena, not the global layout) */
 double *spllt_hip_device_factor(void *fkeep);
+/* ---- selected inversion (single GPU) -----------------------------------------
+ * Z = (P A P^T)^-1 on the pattern of L (P: the pivot order, "order" of spllt_hip_sym_get), computed
+ * on the device from the current factor by the Takahashi recurrences, panel by panel from the root
+ * down.  The Z arena has exactly L's layout (spllt_hip_get_factor): every position that holds L
+ * holds the entry of Z with the same (row, column) in pivot order; the never-read strict upper
+ * triangle of the diagonal tiles is unspecified.  Entries of A^-1 outside the pattern of L need
+ * solves.  A later factorization makes Z stale: the readers then return SPLLT_ERROR_PARAMETER until
+ * spllt_hip_selected_inverse runs again.  L and the solve stay usable.  No atomics: two runs on the
+ * same factor give a bit-identical Z.  A partitioned factor returns SPLLT_ERROR_UNIMPLEMENTED; too
+ * little device memory for the Z arena (L's size) returns SPLLT_ERROR_ALLOCATION.  Messages:
+ * spllt_hip_last_error. */
+int     spllt_hip_selected_inverse(void *fkeep);                       /* compute Z on the device */
+int     spllt_hip_get_inverse(void *fkeep, double *out, int64_t count); /* Z arena -> host, L's layout */
+double *spllt_hip_device_inverse(void *fkeep);                         /* device pointer of the Z arena */
+int     spllt_hip_inverse_diag(void *fkeep, double *out, int n);        /* (A^-1)_ii, user order, host */
+int     spllt_hip_log_det(void *fkeep, double *out);                    /* log det A of the last factor */
+int     spllt_hip_release_inverse(void *fkeep);                        /* free the Z arena early */
 /* timings of the last factorization, milliseconds */
 int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, double *h2d_ms,
                            int *launches);
@@ -281,7 +298,11 @@ int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, do
  * "solve_units" (SolveUnit bytes), "solve_list" (int32), "solve_tiles" (UpdTile bytes),
  * "solve_fwd" / "solve_bwd" (int64 x 4 per launch: kind, level, first, count), "solve_split"
  * (int64 x 2: launches of fwd that belong to the own branches, launches of bwd that belong
- * to the top tree).  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
+ * to the top tree); the selected-inversion program: "selinv_units" (SelinvUnit bytes),
+ * "selinv_tiles" (UpdTile bytes: unit, row tile, K slice), "selinv_launches" (int64 x 5 per
+ * launch: kind, level, first, count, flops), "selinv_rows" (SelinvRow bytes), "selinv_relpos"
+ * (int32), "selinv_diag" (int64 per pivot position: arena offset of its diagonal entry),
+ * "selinv_scratch" (int64), "selinv_flops" (double).  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
  * spllt_amd/api.py.  Returns the byte length. */
 int64_t spllt_hip_program_get(void *fkeep, const char *name, void *buf, int64_t capacity_bytes);
 /* per-launch device time (ms) of one profiled factorization; returns #launches */

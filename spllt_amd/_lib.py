@@ -58,6 +58,8 @@ HIP_SYMBOLS = [
     "spllt_hip_partition_get", "spllt_hip_solve_dev", "spllt_hip_set_chain_block", "spllt_hip_engine_stream", "spllt_hip_analyse_symbolic", "spllt_hip_profile_in_program", "spllt_hip_timeline",
     "spllt_hip_read_rb", "spllt_hip_read_mm", "spllt_hip_free_matrix", "spllt_hip_set_communicator",
     "spllt_hip_last_flag", "spllt_hip_debug", "spllt_hip_exchange_stream",
+    "spllt_hip_selected_inverse", "spllt_hip_get_inverse", "spllt_hip_device_inverse", "spllt_hip_inverse_diag",
+    "spllt_hip_log_det", "spllt_hip_release_inverse",
 ]
 
 _lib = None
@@ -183,6 +185,18 @@ def load():
     lib.spllt_hip_free_matrix.restype = None
     lib.spllt_hip_set_communicator.argtypes = [vp, vp]
     lib.spllt_hip_set_communicator.restype = C.c_int
+    lib.spllt_hip_selected_inverse.argtypes = [vp]
+    lib.spllt_hip_selected_inverse.restype = C.c_int
+    lib.spllt_hip_get_inverse.argtypes = [vp, dp, C.c_int64]
+    lib.spllt_hip_get_inverse.restype = C.c_int
+    lib.spllt_hip_device_inverse.argtypes = [vp]
+    lib.spllt_hip_device_inverse.restype = C.c_void_p
+    lib.spllt_hip_inverse_diag.argtypes = [vp, dp, C.c_int]
+    lib.spllt_hip_inverse_diag.restype = C.c_int
+    lib.spllt_hip_log_det.argtypes = [vp, dp]
+    lib.spllt_hip_log_det.restype = C.c_int
+    lib.spllt_hip_release_inverse.argtypes = [vp]
+    lib.spllt_hip_release_inverse.restype = C.c_int
     lib.spllt_hip_last_flag.argtypes = [vp]
     lib.spllt_hip_last_flag.restype = C.c_int
     _lib = lib

@@ -47,6 +47,13 @@ LAUNCH_COLS = ("kind", "level", "first", "count", "tile", "flops", "stream", "re
                "wait0", "wait1", "wait2", "wait3")
 SOLVE_UNIT_DTYPE = np.dtype([("off", "<i8"), ("dinv_off", "<i8"), ("idx_off", "<i8"), ("w", "<i4"),
                              ("nrow", "<i4"), ("pw", "<i4"), ("cb", "<i4"), ("gcol0", "<i4"), ("pad_", "<i4")])
+# selected inversion (schedule.hpp SelinvUnit / SelinvRow); "selinv_launches": int64 x 5 per launch
+SELINV_UNIT_DTYPE = np.dtype([("off", "<i8"), ("dinv_off", "<i8"), ("row_off", "<i8"), ("y_off", "<i8"),
+                              ("p_off", "<i8"), ("ld", "<i4"), ("c0", "<i4"), ("pn", "<i4"), ("dinv_ld", "<i4"),
+                              ("nR", "<i4"), ("rbase", "<i4"), ("ntile", "<i4"), ("nsplit", "<i4"),
+                              ("kslice", "<i4"), ("gcol", "<i4"), ("ncol", "<i4"), ("nb", "<i4")])
+SELINV_ROW_DTYPE = np.dtype([("cbase", "<i8"), ("ld", "<i4"), ("map", "<i4")])
+SELINV_LAUNCH_COLS = ("kind", "level", "first", "count", "flops")
 POTRF_UNIT_DTYPE = np.dtype([("off", "<i8"), ("dinv_off", "<i8"), ("ld", "<i4"), ("n", "<i4"),
                              ("gcol", "<i4"), ("flags", "<i4")])
 
@@ -197,6 +204,22 @@ class Factorization:
             return raw.view(np.int64).reshape(-1, 4)
         if name == "solve_split":
             return raw.view(np.int64)
+        if name == "selinv_units":
+            return raw.view(SELINV_UNIT_DTYPE)
+        if name == "selinv_tiles":
+            return raw.view(UPD_TILE_DTYPE)
+        if name == "selinv_rows":
+            return raw.view(SELINV_ROW_DTYPE)
+        if name == "selinv_relpos":
+            return raw.view(np.int32)
+        if name == "selinv_diag":
+            return raw.view(np.int64)
+        if name == "selinv_launches":
+            return raw.view(np.int64).reshape(-1, len(SELINV_LAUNCH_COLS))
+        if name == "selinv_scratch":
+            return int(raw.view(np.int64)[0])
+        if name == "selinv_flops":
+            return float(raw.view(np.float64)[0])
         return raw
 
     # ---- numerical phases --------------------------------------------------
@@ -246,6 +269,88 @@ class Factorization:
 
     def device_factor_ptr(self):
         return self.lib.spllt_hip_device_factor(self.fkeep)
+
+    # ---- selected inversion ---------------------------------------------------
+    def selected_inverse(self):
+        """spllt_hip_selected_inverse: Z = (P A P^T)^-1 on the pattern of L, on the device"""
+        rc = self.lib.spllt_hip_selected_inverse(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_selected_inverse", rc, self.last_error())
+        return self
+
+    def get_inverse(self, out=None):
+        """the Z arena on the host (L's layout, see get_factor)"""
+        arena = self.sym_info()["arena"]
+        if out is None:
+            out = np.zeros(max(arena, 1), dtype=np.float64)
+        assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
+        rc = self.lib.spllt_hip_get_inverse(self.fkeep, _dp(out), arena)
+        if rc < 0:
+            raise SplltError("spllt_hip_get_inverse", rc, self.last_error())
+        return out[:arena]
+
+    def device_inverse_ptr(self):
+        return self.lib.spllt_hip_device_inverse(self.fkeep)
+
+    def inverse_diag(self):
+        """(A^-1)_ii in the user's variable order"""
+        out = np.zeros(max(self.n, 1), dtype=np.float64)
+        rc = self.lib.spllt_hip_inverse_diag(self.fkeep, _dp(out), self.n)
+        if rc < 0:
+            raise SplltError("spllt_hip_inverse_diag", rc, self.last_error())
+        return out[:self.n]
+
+    def log_det(self):
+        """log det A of the last factorization (2 sum log L_jj)"""
+        v = C.c_double()
+        rc = self.lib.spllt_hip_log_det(self.fkeep, C.byref(v))
+        if rc < 0:
+            raise SplltError("spllt_hip_log_det", rc, self.last_error())
+        return v.value
+
+    def release_inverse(self):
+        rc = self.lib.spllt_hip_release_inverse(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_inverse", rc, self.last_error())
+
+    def inverse_entries(self, i, j, Z=None):
+        """(A^-1)_{ij} for 0-based user indices i, j (scalars or arrays) whose pivot pair lies in the
+        pattern of L; ValueError for a pair outside it.  Z: the host Z arena (get_inverse()) to read,
+        fetched when not given."""
+        i, j = np.broadcast_arrays(np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64))
+        if ((i < 0) | (i >= self.n) | (j < 0) | (j >= self.n)).any():
+            raise ValueError("inverse_entries: index out of range")
+        if Z is None:
+            Z = self.get_inverse()
+        pos = self._inverse_positions(i.ravel(), j.ravel())
+        return Z[pos].reshape(i.shape)
+
+    def _inverse_positions(self, i, j):
+        """arena positions of the pivot pairs of user indices (i, j): one global search over the row
+        lists, keyed by (node, row) -- the lists are sorted inside a node and the nodes follow in order"""
+        if getattr(self, "_pattern", None) is None:
+            t = {k: self.sym(k) for k in ("order", "sptr", "rptr", "rlist", "node_bcol0", "bcol_off",
+                                          "bcol_width", "bcol_r0")}
+            nn = len(t["sptr"]) - 1
+            node_of = np.repeat(np.arange(nn), np.diff(t["sptr"]))
+            keys = np.repeat(np.arange(nn, dtype=np.int64), np.diff(t["rptr"])) * (self.n + 1) + t["rlist"]
+            self._pattern = (t, node_of, keys)
+        t, node_of, keys = self._pattern
+        pi, pj = t["order"][i], t["order"][j]
+        r, c = np.maximum(pi, pj).astype(np.int64), np.minimum(pi, pj)   # (symmetric: the lower triangle holds it)
+        s = node_of[c]
+        q = s.astype(np.int64) * (self.n + 1) + r
+        e = np.searchsorted(keys, q)
+        ok = e < len(keys)
+        ok[ok] = keys[e[ok]] == q[ok]
+        if not ok.all():
+            bad = int(np.nonzero(~ok)[0][0])
+            raise ValueError(f"inverse_entries: ({int(i[bad])}, {int(j[bad])}) is not in the pattern of L")
+        lr = e - t["rptr"][s]                                  # node-local row
+        k = c - t["sptr"][s]                                   # node-local column
+        b = t["node_bcol0"][s] + k // self.options.nb
+        r0 = t["bcol_r0"][b].astype(np.int64)
+        return t["bcol_off"][b] + (lr - r0) * t["bcol_width"][b] + (k - r0)
 
     def solve(self, b, job=0):
         """spllt_solve on a copy of b (n or n x nrhs, column-major per rhs)."""

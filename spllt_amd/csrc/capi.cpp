@@ -40,6 +40,10 @@ struct Fkeep {
   long worksize = 0;
   double* xbuf = nullptr;  // multi-GPU exchange buffer (caller-owned device memory)
   bool dead = false;       // a submission never returned: the engine belongs to the stuck helper thread
+  // the selected-inversion program of spllt_hip_program_get (built once per pattern and panel layout)
+  std::shared_ptr<const Symbolic> si_S;
+  int si_pw = -1, si_cb = -1, si_rc = 0;
+  SelinvProgram si_prog;
 };
 
 std::mutex g_mu;
@@ -753,6 +757,95 @@ double* spllt_hip_device_factor(void* fkeep) {
   return (f && f->eng) ? f->eng->device_L() : nullptr;
 }
 
+// ---- selected inversion ---------------------------------------------------
+// the handle's engine with its factor finished, or an error flag (with the message in last_error)
+static int selinv_engine(Fkeep* f, const char* what) {
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  int rc = do_wait(f);
+  if (rc) return rc;
+  if (!f->eng) {
+    f->last_error = std::string(what) + ": nothing has been factorized on this handle";
+    return SPLLT_ERROR_PARAMETER;
+  }
+  if (f->eo.nranks > 1) {
+    f->last_error = std::string(what) + ": not available on a partitioned (multi-GPU) factor";
+    std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
+    return SPLLT_ERROR_UNIMPLEMENTED;
+  }
+  return 0;
+}
+
+static int selinv_fail(Fkeep* f, int rc) {
+  if (!f->eng->selinv_error().empty()) f->last_error = f->eng->selinv_error();
+  else if (f->eng->status()) f->last_error = f->eng->error();
+  return rc;
+}
+
+static int selinv_need_z(Fkeep* f, const char* what) {
+  int rc = selinv_engine(f, what);
+  if (rc) return rc;
+  if (!f->eng->inverse_valid()) {
+    f->last_error = std::string(what) + ": no selected inverse of the current factor (call spllt_hip_selected_inverse "
+                                        "after every factorization)";
+    return SPLLT_ERROR_PARAMETER;
+  }
+  return 0;
+}
+
+int spllt_hip_selected_inverse(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = selinv_engine(f, "spllt_hip_selected_inverse");
+  if (rc) return rc;
+  rc = f->eng->selected_inverse();
+  return rc ? selinv_fail(f, rc) : 0;
+}
+
+int spllt_hip_get_inverse(void* fkeep, double* out, int64_t count) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!out) return SPLLT_ERROR_PARAMETER;
+  int rc = selinv_need_z(f, "spllt_hip_get_inverse");
+  if (rc) return rc;
+  rc = f->eng->download_inverse(out, count);
+  return rc ? selinv_fail(f, rc) : 0;
+}
+
+double* spllt_hip_device_inverse(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  return (f && f->eng && !f->eng->pending()) ? f->eng->device_Z() : nullptr;
+}
+
+int spllt_hip_inverse_diag(void* fkeep, double* out, int n) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!out) return SPLLT_ERROR_PARAMETER;
+  int rc = selinv_need_z(f, "spllt_hip_inverse_diag");
+  if (rc) return rc;
+  if (n != f->S->n) {
+    f->last_error = "spllt_hip_inverse_diag: n = " + std::to_string(n) + " does not match the analysed order " +
+                    std::to_string(f->S->n);
+    return SPLLT_ERROR_PARAMETER;
+  }
+  rc = f->eng->inverse_diag(out, n);
+  return rc ? selinv_fail(f, rc) : 0;
+}
+
+int spllt_hip_log_det(void* fkeep, double* out) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!out) return SPLLT_ERROR_PARAMETER;
+  int rc = selinv_engine(f, "spllt_hip_log_det");
+  if (rc) return rc;
+  rc = f->eng->log_det(out);
+  return rc ? selinv_fail(f, rc) : 0;
+}
+
+int spllt_hip_release_inverse(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  if (!f->eng || f->dead) return 0;
+  if (f->eng->pending()) do_wait(f);
+  int rc = f->eng->release_inverse();
+  return rc ? selinv_fail(f, rc) : 0;
+}
+
 int spllt_hip_factor_times(void* fkeep, double* submit_ms, double* device_ms, double* h2d_ms, int* launches) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->eng) return SPLLT_ERROR_PARAMETER;
@@ -822,6 +915,33 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
   if (k == "gather_items") return raw(P->gather_items.data(), P->gather_items.size() * sizeof(GatherItem));
   if (k == "scratch_size") { int64_t v = P->scratch_size; return raw(&v, sizeof v); }
   if (k == "dinv_size") { int64_t v = P->dinv_size; return raw(&v, sizeof v); }
+  if (k.rfind("selinv_", 0) == 0) {
+    // the selected-inversion program (single GPU; built from the symbolic structure alone)
+    if (f->si_S != f->S || f->si_pw != P->pw || f->si_cb != P->cb) {
+      f->si_rc = build_selinv_program(*f->S, P->pw, P->cb, f->si_prog);
+      f->si_S = f->S;
+      f->si_pw = P->pw;
+      f->si_cb = P->cb;
+    }
+    if (f->si_rc) return -1;
+    const SelinvProgram& sp = f->si_prog;
+    if (k == "selinv_units") return raw(sp.units.data(), sp.units.size() * sizeof(SelinvUnit));
+    if (k == "selinv_tiles") return raw(sp.tiles.data(), sp.tiles.size() * sizeof(UpdTile));
+    if (k == "selinv_rows") return raw(sp.rows.data(), sp.rows.size() * sizeof(SelinvRow));
+    if (k == "selinv_relpos") return raw(sp.relpos.data(), sp.relpos.size() * sizeof(int));
+    if (k == "selinv_diag") return raw(sp.diag_pos.data(), sp.diag_pos.size() * sizeof(int64_t));
+    if (k == "selinv_scratch") return raw(&sp.scratch_size, sizeof(int64_t));
+    if (k == "selinv_flops") return raw(&sp.flops, sizeof(double));
+    if (k == "selinv_launches") {   // int64 x 5 per launch: kind, level, first, count, flops
+      std::vector<int64_t> v;
+      for (const SelinvLaunch& l : sp.launches) {
+        v.push_back(l.kind); v.push_back(l.level); v.push_back(l.first); v.push_back(l.count);
+        v.push_back((int64_t)l.flops);
+      }
+      return raw(v.data(), v.size() * sizeof(int64_t));
+    }
+    return -1;
+  }
   if (k.rfind("solve_", 0) == 0) {
     // the substitution program (partition-aware like the factor program)
     SolveProgram sp;

@@ -1270,6 +1270,7 @@ int Engine::continue_after_exchange() {
 int Engine::factor_async_dev(const double* val_dev, int64_t nnz) {
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
+  z_valid_ = false;
   double t0 = now_ms();
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipEventRecord(ev0_, stream_), "event");
@@ -1297,6 +1298,7 @@ int Engine::factor_async_dev(const double* val_dev, int64_t nnz) {
 int Engine::factor_async(const double* val_host, int64_t nnz) {
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
+  z_valid_ = false;
   double t0 = now_ms();
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipEventRecord(ev0_, stream_), "event");
@@ -1429,6 +1431,117 @@ int Engine::prepare_solve() {
   return 0;
 }
 
+// ---- selected inversion --------------------------------------------------------------------------
+int Engine::prepare_selinv() {
+  if (selinv_ready_) return 0;
+  const Symbolic& S = *S_;
+  if (build_selinv_program(S, prog_.pw, prog_.cb, siprog_)) {
+    si_err_ = "selected inversion: the row structure of a node is not contained in its ancestors'";
+    return -10;
+  }
+  std::vector<int> order(S.order.begin(), S.order.end());
+  TableStager tab;
+  tab.add(&d_siunits_, siprog_.units);
+  tab.add(&d_sitiles_, siprog_.tiles);
+  tab.add(&d_sirows_, siprog_.rows);
+  tab.add(&d_sirelpos_, siprog_.relpos);
+  tab.add(&d_sidiag_, siprog_.diag_pos);
+  tab.add(&d_siorder_, order);
+  // (a failure here leaves the factor and the solve usable: the engine's status is not touched)
+  hipError_t e = tab.commit(&d_selinv_tables_, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e == hipSuccess) e = dalloc((void**)&d_siout_, sizeof(double) * ((size_t)S.n + 1));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (d_selinv_tables_) { release_buffer(d_selinv_tables_); d_selinv_tables_ = nullptr; }
+    si_err_ = std::string("selected inversion: not enough device memory for the program tables (") +
+              hipGetErrorString(e) + ")";
+    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
+  }
+  selinv_ready_ = true;
+  return 0;
+}
+
+void Engine::release_buffer(void* p) {
+  for (size_t i = 0; i < owned_.size(); ++i)
+    if (owned_[i].first == p) {
+      dev_release(owned_[i].first, owned_[i].second, device_);
+      owned_.erase(owned_.begin() + (long)i);
+      return;
+    }
+}
+
+int Engine::selected_inverse() {
+  if (status_) return status_;
+  if (pending_) return -10;   // (the caller waits first)
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  si_err_.clear();
+  int rc = prepare_selinv();
+  if (rc) return rc;
+  if (!d_Z_ || !d_siscratch_) {
+    // the Z arena (L's size) and the scratch: a failure here leaves the factor usable
+    const size_t zb = sizeof(double) * (size_t)std::max<int64_t>(1, S_->arena);
+    const size_t sb = sizeof(double) * (size_t)std::max<int64_t>(1, siprog_.scratch_size);
+    hipError_t e = d_Z_ ? hipSuccess : dalloc((void**)&d_Z_, zb);
+    if (e == hipSuccess && !d_siscratch_) e = dalloc((void**)&d_siscratch_, sb);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      if (d_Z_) { release_buffer(d_Z_); d_Z_ = nullptr; }
+      si_err_ = "selected inversion: not enough device memory for the inverse arena (" + std::to_string(zb >> 20) +
+                " MiB) and its scratch (" + std::to_string(sb >> 20) + " MiB)";
+      return -1;
+    }
+  }
+  z_valid_ = false;
+  for (const SelinvLaunch& l : siprog_.launches)
+    launch_selinv(stream_, l, d_siunits_, d_sitiles_, d_sirows_, d_sirelpos_, d_L_, d_dinv_, d_Z_, d_siscratch_);
+  HIPCHK(hipGetLastError(), "selinv launch");
+  if ((rc = sync_stream(stream_, "selinv sync"))) return rc;
+  z_valid_ = true;
+  return 0;
+}
+
+int Engine::download_inverse(double* out, int64_t count) {
+  if (status_) return status_;
+  if (!z_valid_) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  return staged_d2h(out, d_Z_, sizeof(double) * (size_t)std::min<int64_t>(count, S_->arena));
+}
+
+int Engine::inverse_diag(double* out, int n) {
+  if (status_) return status_;
+  if (!z_valid_ || n != S_->n) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  launch_selinv_diag_gather(stream_, d_Z_, d_sidiag_, d_siorder_, n, d_siout_);
+  HIPCHK(hipGetLastError(), "selinv diag launch");
+  HIPCHK(hipMemcpyAsync(out, d_siout_, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, stream_), "diag D2H");
+  return sync_stream(stream_, "selinv diag sync");
+}
+
+int Engine::log_det(double* out) {
+  if (status_) return status_;
+  if (pending_) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_selinv();
+  if (rc) return rc;
+  launch_log_det(stream_, d_L_, d_sidiag_, S_->n, d_siout_ + S_->n);
+  HIPCHK(hipGetLastError(), "log det launch");
+  HIPCHK(hipMemcpyAsync(out, d_siout_ + S_->n, sizeof(double), hipMemcpyDeviceToHost, stream_), "log det D2H");
+  return sync_stream(stream_, "log det sync");
+}
+
+int Engine::release_inverse() {
+  if (status_) return status_;
+  z_valid_ = false;
+  if (d_Z_) {
+    HIPCHK(hipSetDevice(device_), "hipSetDevice");
+    if (int rc = sync_stream(stream_, "selinv release")) return rc;
+    release_buffer(d_Z_);
+    release_buffer(d_siscratch_);
+    d_Z_ = d_siscratch_ = nullptr;
+  }
+  return 0;
+}
+
 // Substitution on device vectors in pivot order (y[q * n + p], q < nrhs), in place.
 // phase -1: everything that `job` asks for; 0/1/2: the three phases of a
 // partitioned solve (schedule.hpp, SolveProgram).
@@ -1534,6 +1647,7 @@ int Engine::profile_launches(const double* val_host, int64_t nnz, std::vector<fl
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
   if (!prog_.exchanges.empty()) return -98;   // single-GPU programs only
+  z_valid_ = false;                           // (L is factored again from val)
   const Symbolic& S = *S_;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipMemcpy(d_val_, val_host, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice), "val H2D");
@@ -1577,6 +1691,7 @@ int Engine::timeline(const double* val_host, int64_t nnz, std::vector<float>& t)
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
   if (!prog_.exchanges.empty()) return -98;   // single-GPU programs only
+  z_valid_ = false;                           // (L is factored again from val)
   const Symbolic& S = *S_;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipMemcpy(d_val_, val_host, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice), "val H2D");

@@ -124,6 +124,18 @@ class Engine {
   // substitution on device vectors in pivot order; phase -1 = all, 0/1/2 = partitioned phases
   int solve_dev(double* y_dev, int nrhs, int job, int phase);
   int prepare_solve();
+  // ---- selected inversion (selinv.hip, single GPU): Z = (P A P^T)^-1 on the pattern of L, in a
+  // second arena with L's layout.  Computed from the current factor (after wait()); a later
+  // factorization marks it stale: the readers below then fail instead of returning old numbers.
+  int selected_inverse();
+  bool inverse_valid() const { return z_valid_; }
+  int download_inverse(double* out, int64_t count);   // Z arena -> host
+  int inverse_diag(double* out, int n);               // (A^-1)_ii, user variable order, host
+  int log_det(double* out);                           // 2 sum log L_jj of the current factor
+  int release_inverse();                              // give the Z arena back to the pool
+  double* device_Z() { return z_valid_ ? d_Z_ : nullptr; }
+  const SelinvProgram& selinv_program() const { return siprog_; }
+  const std::string& selinv_error() const { return si_err_; }
   double* device_L() { return d_L_; }
   hipStream_t stream() { return stream_; }
   // the stream the pending exchange is packed / unpacked on (its collective belongs there); the chain stream when none is pending
@@ -254,6 +266,23 @@ class Engine {
   int* d_rlist_ = nullptr;
   int* d_flag_ = nullptr;
   int* h_flag_ = nullptr;  // pinned
+  // selected inversion (tables uploaded once per pattern, on first use)
+  int prepare_selinv();
+  void release_buffer(void* p);
+  SelinvProgram siprog_;
+  bool selinv_ready_ = false;
+  bool z_valid_ = false;
+  std::string si_err_;
+  char* d_selinv_tables_ = nullptr;
+  SelinvUnit* d_siunits_ = nullptr;
+  UpdTile* d_sitiles_ = nullptr;
+  SelinvRow* d_sirows_ = nullptr;
+  int* d_sirelpos_ = nullptr;
+  int64_t* d_sidiag_ = nullptr;
+  int* d_siorder_ = nullptr;
+  double* d_Z_ = nullptr;
+  double* d_siscratch_ = nullptr;
+  double* d_siout_ = nullptr;      // n + 1 doubles: diag(A^-1), log det
 };
 
 }  // namespace spx

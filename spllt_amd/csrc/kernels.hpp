@@ -82,6 +82,16 @@ void launch_solve(hipStream_t st, int kind, const int* list, const UpdTile* tile
                   const int* rlist, double* y, int nr, int64_t ldy, bool four = false,
                   const SolveUnit* one = nullptr);   // one: the launch works on ONE block column (host copy of its unit;
                                                      // strips: strip i = workgroup i) -- the descriptor travels with the arguments
+// selected inversion (selinv.hip): one launch of a SelinvProgram (SI_SYMM / SI_SCALE: tiles[first ..];
+// SI_DIAG: units[first ..]) on the Z arena; scratch: the program's scratch_size doubles
+void launch_selinv(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* units, const UpdTile* tiles,
+                   const SelinvRow* rows, const int* relpos, const double* L, const double* dinv, double* Z,
+                   double* scratch);
+// out[v] = Z[diag_pos[order[v]]]  (diag(A^-1) in the user's variable order)
+void launch_selinv_diag_gather(hipStream_t st, const double* Z, const int64_t* diag_pos, const int* order, int n,
+                               double* out);
+// out[0] = 2 sum_j log L[diag_pos[j]], in a fixed order
+void launch_log_det(hipStream_t st, const double* L, const int64_t* diag_pos, int n, double* out);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 

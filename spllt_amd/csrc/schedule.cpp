@@ -1493,3 +1493,136 @@ void build_solve_program(const Symbolic& S, int pw, int cb, SolveProgram& P, con
 }
 
 }  // namespace spx
+
+namespace spx {
+
+int build_selinv_program(const Symbolic& S, int pw, int cb, SelinvProgram& P) {
+  P = SelinvProgram();
+  pw = std::max(1, std::min(pw, kPanelMax));
+  cb = std::max(1, cb);
+  const int nn = S.nnodes, nbc = S.nbcol();
+  // dinv slot of every block column: the layout of the factorization (and of the solve)
+  std::vector<int64_t> dinv_base(nbc + 1, 0);
+  for (int b = 0; b < nbc; ++b) dinv_base[b + 1] = dinv_base[b] + winv_total(S.bcols[b].width, cb);
+  auto holder = [&](int s, int k, SelinvRow& d) {   // block column of node s holding its column k
+    const BlockCol& B = S.bcols[S.node_bcol0[s] + k / S.nb];
+    d.cbase = B.off - (int64_t)B.r0 * B.width + (k - B.r0);
+    d.ld = B.width;
+  };
+  // row descriptors and the ancestor row maps
+  P.rows.resize(S.rlist.size());
+  for (int s = 0; s < nn; ++s) {
+    const int m = S.nrow(s), nc = S.ncol(s);
+    const int* rows = S.rows(s);
+    for (int k = 0; k < nc; ++k) {
+      SelinvRow& d = P.rows[S.rptr[s] + k];
+      holder(s, k, d);
+      d.map = -1;
+    }
+    for (int k0 = nc; k0 < m;) {
+      const int a = S.snode_of[rows[k0]];
+      int k1 = k0;
+      while (k1 < m && S.snode_of[rows[k1]] == a) ++k1;
+      // node-local rows in a of rows k0 .. m-1 of s (closure: all of them are rows of a)
+      const int64_t base = (int64_t)P.relpos.size();
+      const int* ar = S.rows(a);
+      const int am = S.nrow(a);
+      int q = 0;
+      for (int i = k0; i < m; ++i) {
+        while (q < am && ar[q] < rows[i]) ++q;
+        if (q >= am || ar[q] != rows[i]) { P = SelinvProgram(); return -1; }   // row structure not closed
+        P.relpos.push_back(q);
+      }
+      for (int k = k0; k < k1; ++k) {
+        SelinvRow& d = P.rows[S.rptr[s] + k];
+        holder(a, rows[k] - S.sptr[a], d);
+        d.map = (int)(base + (k - k0));
+      }
+      k0 = k1;
+    }
+  }
+  P.diag_pos.resize(S.n);
+  for (int g = 0; g < S.n; ++g) {
+    const int s = S.snode_of[g], k = g - S.sptr[s];
+    const BlockCol& B = S.bcols[S.node_bcol0[s] + k / S.nb];
+    P.diag_pos[g] = B.off + (int64_t)(k - B.r0) * B.width + (k - B.r0);
+  }
+  // panels of every node, last first
+  struct Pan { int b, p; };
+  std::vector<std::vector<Pan>> pans(nn);
+  int maxlevel = -1;
+  for (int s = 0; s < nn; ++s) {
+    maxlevel = std::max(maxlevel, S.level[s]);
+    for (int b = S.node_bcol0[s + 1] - 1; b >= S.node_bcol0[s]; --b)
+      for (int p = (S.bcols[b].width + pw - 1) / pw - 1; p >= 0; --p) pans[s].push_back({b, p});
+  }
+  std::vector<std::vector<int>> by_level(maxlevel + 1);
+  for (int s = 0; s < nn; ++s) by_level[S.level[s]].push_back(s);
+  for (int lev = maxlevel; lev >= 0; --lev) {
+    size_t nsteps = 0;
+    for (int s : by_level[lev]) nsteps = std::max(nsteps, pans[s].size());
+    for (size_t t = 0; t < nsteps; ++t) {
+      const int64_t u0 = (int64_t)P.units.size();
+      int64_t ntiles = 0;
+      for (int s : by_level[lev]) {
+        if (t >= pans[s].size()) continue;
+        const BlockCol& B = S.bcols[pans[s][t].b];
+        SelinvUnit u{};
+        u.off = B.off;
+        u.ld = B.width;
+        u.c0 = pans[s][t].p * pw;
+        u.pn = std::min(pw, B.width - u.c0);
+        const int g0 = (u.c0 / cb) * cb;
+        u.dinv_off = dinv_base[pans[s][t].b] + winv_offset(B.width, pw, cb, pans[s][t].p) + (u.c0 - g0);
+        u.dinv_ld = winv_ld(B.width, cb, u.c0);
+        u.row_off = S.rptr[s];
+        u.nR = B.nrow - u.c0 - u.pn;
+        u.rbase = B.r0 + u.c0 + u.pn;
+        u.ntile = (u.nR + kSelinvTile - 1) / kSelinvTile;
+        u.gcol = S.sptr[s] + B.r0 + u.c0;
+        u.ncol = S.ncol(s);
+        u.nb = S.nb;
+        ntiles += u.ntile;
+        P.units.push_back(u);
+      }
+      const int64_t u1 = (int64_t)P.units.size();
+      // K slices: enough workgroups for the chip (256 CUs x 4 resident k_selinv_symm workgroups) when the
+      // step has few row tiles (at least 256 rows per slice, so that a slice outweighs its partial's
+      // round trip through the scratch)
+      constexpr int64_t kSlots = 1024;
+      const int64_t want = std::max<int64_t>(1, (kSlots + std::max<int64_t>(ntiles, 1) - 1) / std::max<int64_t>(ntiles, 1));
+      int64_t scr = 0;
+      double fl_symm = 0, fl_scale = 0, fl_diag = 0;
+      for (int64_t i = u0; i < u1; ++i) {
+        SelinvUnit& u = P.units[i];
+        int64_t ks = (u.nR + want - 1) / want;
+        ks = std::max<int64_t>(256, (ks + kSelinvTile - 1) / kSelinvTile * kSelinvTile);
+        u.kslice = (int)ks;
+        u.nsplit = u.nR > 0 ? (int)((u.nR + ks - 1) / ks) : 0;
+        u.y_off = scr;
+        scr += (int64_t)u.nsplit * u.nR * u.pn;
+        u.p_off = scr;
+        scr += (int64_t)u.ntile * u.pn * u.pn;
+        fl_symm += 2.0 * u.nR * u.nR * u.pn;
+        fl_scale += 3.0 * u.nR * u.pn * u.pn;
+        fl_diag += (double)u.pn * u.pn * u.pn;
+      }
+      P.scratch_size = std::max(P.scratch_size, scr);
+      const int64_t t0 = (int64_t)P.tiles.size();
+      for (int64_t i = u0; i < u1; ++i)
+        for (int ti = 0; ti < P.units[i].ntile; ++ti)
+          for (int k = 0; k < P.units[i].nsplit; ++k) P.tiles.push_back(UpdTile{(int)i, (short)ti, (short)k});
+      const int64_t t1 = (int64_t)P.tiles.size();
+      for (int64_t i = u0; i < u1; ++i)
+        for (int ti = 0; ti < P.units[i].ntile; ++ti) P.tiles.push_back(UpdTile{(int)i, (short)ti, (short)0});
+      const int64_t t2 = (int64_t)P.tiles.size();
+      if (t1 > t0) P.launches.push_back(SelinvLaunch{SI_SYMM, lev, t0, t1 - t0, fl_symm});
+      if (t2 > t1) P.launches.push_back(SelinvLaunch{SI_SCALE, lev, t1, t2 - t1, fl_scale});
+      P.launches.push_back(SelinvLaunch{SI_DIAG, lev, u0, u1 - u0, fl_diag});
+      P.flops += fl_symm + fl_scale + fl_diag;
+    }
+  }
+  return 0;
+}
+
+}  // namespace spx

@@ -412,4 +412,72 @@ struct SolveProgram {
 void build_solve_program(const Symbolic& S, int pw, int cb, SolveProgram& P,
                          const int* node_owner = nullptr, int rank = 0);
 
+// ---------------------------------------------------------------------------
+// Selected inversion: Z = (P A P^T)^-1 on the pattern of L (the Takahashi recurrences), written
+// into a second arena with L's layout.  Per panel J (pw columns of one block column), R = the
+// node-local rows below J (rest of its block column, later block columns, the ancestor rows):
+//   Y    = Z_RR L_RJ                       (SI_SYMM, K split over kslice-row slices)
+//   Z_RJ = -Y inv(L_JJ)                    (SI_SCALE: the slices summed in order, times the dinv slot,
+//                                           and per 64-row tile  L_RJ(tile)^T Z_RJ(tile)  for SI_DIAG)
+//   Z_JJ = inv(L_JJ)^T (inv(L_JJ) - L_RJ^T Z_RJ)   (SI_DIAG: the tile partials summed in order)
+// Panels run in reverse elimination order: levels from the root down, inside a node the last panel
+// first; the nodes of one level run side by side (step t: the t-th panel from the end of each).
+// Every index comes from the Symbolic structure (never from a factor program): the result does not
+// depend on the engine variant that produced L and the dinv slots.
+// ---------------------------------------------------------------------------
+// Where Z(r_i, r_k), r_i >= r_k, of a node's rows lives: row descriptor d of node-local row k gives
+//   Z[d.cbase + q * d.ld],  q = (d.map < 0 ? i : relpos[d.map + i - k])
+// (own column k: the node's block column holding it, q = i; ancestor row k: the block column of the
+// ancestor holding pivot r_k, q = the ancestor's node-local row of r_i).  r_i < r_k: read transposed.
+struct SelinvRow {
+  int64_t cbase;   // arena offset of (node-local row 0 of the holding node, column k)
+  int ld;          // row width of the holding block column
+  int map;         // -1: q = i (the node's own column); else index into selinv_relpos of row i = k
+};
+static_assert(sizeof(SelinvRow) == 16, "SelinvRow layout (mirrored in spllt_amd/api.py)");
+
+struct SelinvUnit {
+  int64_t off;       // arena offset of the panel's block column (the same in L and in Z)
+  int64_t dinv_off;  // inv(L_JJ) in the dinv scratch: entry (a, c) at dinv_off + a * dinv_ld + c
+  int64_t row_off;   // selinv_rows index of the node's row 0
+  int64_t y_off;     // scratch: K-slice partials of Y, nsplit x nR x pn row-major
+  int64_t p_off;     // scratch: per row tile  L_RJ^T Z_RJ,  ntile x pn x pn
+  int ld;            // block column width
+  int c0, pn;        // panel: first column inside the block column, width (<= kPanelMax)
+  int dinv_ld;
+  int nR;            // |R| (rows stored below the panel: block column rows c0 + pn ...)
+  int rbase;         // node-local row of R's first row
+  int ntile;         // 64-row tiles of R
+  int nsplit;        // K slices of SI_SYMM
+  int kslice;        // rows of R per K slice (a multiple of 64)
+  int gcol;          // pivot position of the panel's column 0
+  int ncol;          // columns of the node: node-local rows below ncol are its own columns
+  int nb;            // block column width of the node (own column k lies in block column k / nb)
+};
+static_assert(sizeof(SelinvUnit) == 88, "SelinvUnit layout (mirrored in spllt_amd/api.py)");
+
+enum SelinvKind : int { SI_SYMM = 0, SI_SCALE = 1, SI_DIAG = 2 };
+constexpr int kSelinvTile = 64;   // rows of R per output tile
+
+struct SelinvLaunch {
+  int kind;
+  int level;
+  int64_t first, count;  // SYMM / SCALE: range in tiles (unit, ti, tj = K slice); DIAG: range in units
+  double flops;          // useful flops
+};
+
+struct SelinvProgram {
+  std::vector<SelinvUnit> units;      // one per panel, in processing order
+  std::vector<UpdTile> tiles;
+  std::vector<SelinvLaunch> launches;
+  std::vector<SelinvRow> rows;        // per node, per node-local row (rptr order)
+  std::vector<int> relpos;
+  std::vector<int64_t> diag_pos;      // per pivot position: arena offset of its diagonal entry
+  int64_t scratch_size = 0;           // doubles (largest step)
+  double flops = 0;
+};
+
+// 0, or -1 when a node's rows below its columns are not all rows of their ancestors (no Z_RR storage)
+int build_selinv_program(const Symbolic& S, int pw, int cb, SelinvProgram& P);
+
 }  // namespace spx
