@@ -236,6 +236,25 @@ int spllt_hip_pending_exchange(void *fkeep);
  *   zero the entries this rank does not own    -> all-reduce(sum): x on every rank.
  * spllt_solve itself returns SPLLT_ERROR_UNIMPLEMENTED on a partitioned factor. */
 int spllt_hip_solve_dev(void *fkeep, void *y_dev, int nrhs, int job, int phase);
+/* ---- blocked solve for many right-hand sides (single GPU) ---------------------
+ * The substitution of spllt_solve on blocks of 32 right-hand sides per sweep (a tail of at most 16:
+ * one block of 16), products on the fp64 matrix cores, so that L is read once per block instead of
+ * once per four vectors.  X holds nrhs vectors, vector q at x[q*ldx .. q*ldx + n), ldx >= n,
+ * overwritten by the solution; entries outside those ranges are neither read nor written, and a
+ * tail that does not fill a block is padded inside the library.  job as spllt_solve (0 both sweeps,
+ * 1 forward, 2 backward).  nrhs = 0 is a no-op.  The permutation to pivot order and the transposition
+ * into the workspace (n*32 doubles, allocated on first use, kept with the handle) happen on the
+ * device.  The work is ordered on the engine's stream (spllt_hip_engine_stream) and has finished
+ * when the call returns.  A later factorization on the handle is picked up.
+ * Reproducibility: the row strips add into the right-hand sides with fp64 atomic adds, like
+ * spllt_solve: two runs agree to rounding, not bit for bit.
+ * Errors: null pointer, nrhs < 0, ldx < n, bad job, nothing factorized yet -> SPLLT_ERROR_PARAMETER;
+ * partitioned factor (spllt_hip_set_partition with nranks > 1) -> SPLLT_ERROR_UNIMPLEMENTED; no
+ * device memory for the workspace -> SPLLT_ERROR_ALLOCATION (the factor and spllt_solve stay
+ * usable).  Messages: spllt_hip_last_error. */
+int spllt_hip_solve_many(void *fkeep, int nrhs, double *x_host, int64_t ldx, int job);      /* host, user order */
+int spllt_hip_solve_many_dev(void *fkeep, int nrhs, double *x_dev, int64_t ldx, int job,
+                             int pivot_order);   /* device; 0 = user order, 1 = pivot order as spllt_hip_solve_dev */
 int spllt_hip_set_exchange_buffer(void *fkeep, void *dev_ptr);
 /* The HIP stream (hipStream_t) every caller-visible operation of this handle is ordered on:
  * spllt_factor ends by packing the exchange buffer on it and spllt_hip_continue starts by

@@ -60,6 +60,7 @@ HIP_SYMBOLS = [
     "spllt_hip_last_flag", "spllt_hip_debug", "spllt_hip_exchange_stream",
     "spllt_hip_selected_inverse", "spllt_hip_get_inverse", "spllt_hip_device_inverse", "spllt_hip_inverse_diag",
     "spllt_hip_log_det", "spllt_hip_release_inverse",
+    "spllt_hip_solve_many", "spllt_hip_solve_many_dev",
 ]
 
 _lib = None
@@ -150,6 +151,10 @@ def load():
     lib.spllt_hip_partition_get.restype = C.c_int64
     lib.spllt_hip_solve_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     lib.spllt_hip_solve_dev.restype = C.c_int
+    lib.spllt_hip_solve_many.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int]
+    lib.spllt_hip_solve_many.restype = C.c_int
+    lib.spllt_hip_solve_many_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int]
+    lib.spllt_hip_solve_many_dev.restype = C.c_int
     lib.spllt_hip_profile.argtypes = [vp, dp, C.c_int, C.POINTER(C.c_float), C.c_int]
     lib.spllt_hip_profile.restype = C.c_int
     lib.spllt_hip_profile_in_program.argtypes = [vp, dp, C.c_int, C.POINTER(C.c_float), C.c_int]

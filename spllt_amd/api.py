@@ -373,6 +373,29 @@ class Factorization:
             raise SplltError("spllt_hip_solve_dev", rc, self.last_error())
         return self
 
+    def solve_many(self, b, job=0):
+        """spllt_hip_solve_many on a copy of b (n or n x nrhs): the blocked solve, 32 right-hand sides per
+        sweep on the fp64 matrix cores.  Returns a new F-ordered array, like solve."""
+        x = np.array(b, dtype=np.float64, order="F", copy=True)
+        nrhs = 1 if x.ndim == 1 else x.shape[1]
+        ldx = x.shape[0]
+        rc = self.lib.spllt_hip_solve_many(self.fkeep, nrhs, _dp(x), ldx, job)
+        if rc < 0:
+            raise SplltError("spllt_hip_solve_many", rc, self.last_error())
+        return x
+
+    def solve_many_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
+        """spllt_hip_solve_many_dev: the blocked solve on device vectors, in place (vector q at
+        x[q*ldx .. q*ldx + n), ldx defaults to n); pivot_order=True: the vectors are in pivot order as for
+        solve_dev, else in the user's variable order."""
+        if ldx is None:
+            ldx = self.n
+        rc = self.lib.spllt_hip_solve_many_dev(self.fkeep, nrhs, C.c_void_p(x_dev_ptr), int(ldx), job,
+                                               1 if pivot_order else 0)
+        if rc < 0:
+            raise SplltError("spllt_hip_solve_many_dev", rc, self.last_error())
+        return self
+
     # ---- multi-GPU subtree partition ------------------------------------------
     def set_partition(self, rank, nranks):
         """Declare this process as `rank` of `nranks`; returns the number of

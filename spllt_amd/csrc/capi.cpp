@@ -757,6 +757,55 @@ double* spllt_hip_device_factor(void* fkeep) {
   return (f && f->eng) ? f->eng->device_L() : nullptr;
 }
 
+// ---- blocked solve for many right-hand sides ------------------------------
+// argument checks that need no device, then the handle's engine with its factor finished
+static int solve_many_engine(Fkeep* f, const char* what, int nrhs, const void* x, int64_t ldx, int job) {
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!x) bad = "the array of right-hand sides is null";
+  else if (nrhs < 0) bad = "nrhs < 0";
+  else if (ldx < f->S->n) bad = "ldx < n";
+  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
+  if (bad) {
+    f->last_error = std::string(what) + ": " + bad;
+    return SPLLT_ERROR_PARAMETER;
+  }
+  int rc = do_wait(f);
+  if (rc) return rc;
+  if (!f->eng) {
+    f->last_error = std::string(what) + ": nothing has been factorized on this handle";
+    return SPLLT_ERROR_PARAMETER;
+  }
+  if (f->eo.nranks > 1) {
+    f->last_error = std::string(what) + ": not available on a partitioned (multi-GPU) factor";
+    std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
+    return SPLLT_ERROR_UNIMPLEMENTED;
+  }
+  return 0;
+}
+
+static int solve_many_fail(Fkeep* f, int rc) {
+  if (!f->eng->solve_many_error().empty()) f->last_error = f->eng->solve_many_error();
+  else if (f->eng->status()) f->last_error = f->eng->error();
+  return rc;
+}
+
+int spllt_hip_solve_many(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_many_engine(f, "spllt_hip_solve_many", nrhs, x_host, ldx, job);
+  if (rc) return rc;
+  rc = f->eng->solve_many(x_host, nrhs, ldx, job);
+  return rc ? solve_many_fail(f, rc) : 0;
+}
+
+int spllt_hip_solve_many_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_many_engine(f, "spllt_hip_solve_many_dev", nrhs, x_dev, ldx, job);
+  if (rc) return rc;
+  rc = f->eng->solve_many_dev(x_dev, nrhs, ldx, job, pivot_order != 0);
+  return rc ? solve_many_fail(f, rc) : 0;
+}
+
 // ---- selected inversion ---------------------------------------------------
 // the handle's engine with its factor finished, or an error flag (with the message in last_error)
 static int selinv_engine(Fkeep* f, const char* what) {

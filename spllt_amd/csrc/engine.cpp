@@ -1638,6 +1638,122 @@ int Engine::solve(double* x_host, int nrhs, int job) {
   return 0;
 }
 
+// ---- blocked solve for many right-hand sides ---------------------------------------------------
+int Engine::prepare_solve_many(bool host_stage) {
+  int rc = prepare_solve();
+  if (rc) return rc;
+  const Symbolic& S = *S_;
+  const size_t wb = sizeof(double) * 32 * (size_t)std::max(1, S.n);
+  // (a failure here leaves the factor and the existing solve usable: the engine's status is not touched)
+  hipError_t e = hipSuccess;
+  if (!d_smW_) e = dalloc((void**)&d_smW_, wb);
+  if (e == hipSuccess && !d_smorder_) {
+    std::vector<int> order(S.order.begin(), S.order.end());
+    if (order.empty()) order.push_back(0);
+    e = dev_upload(&d_smorder_, order);
+  }
+  if (e == hipSuccess && host_stage && !d_smstage_) e = dalloc((void**)&d_smstage_, wb);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    sm_err_ = "solve_many: not enough device memory for the workspace of 32 right-hand sides (" +
+              std::to_string(wb >> 20) + " MiB): " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
+  }
+  if (sm_one_fwd_.size() != sprog_.fwd.size() || sm_one_bwd_.size() != sprog_.bwd.size()) {
+    // a launch on ONE block column (every step of the upper levels): its descriptor travels by value
+    auto ones = [&](const std::vector<SolveLaunch>& ls, std::vector<const SolveUnit*>& out) {
+      out.assign(ls.size(), nullptr);
+      for (size_t i = 0; i < ls.size(); ++i) {
+        if (ls[i].count <= 0) continue;
+        if (ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD) {
+          if (ls[i].count == 1) out[i] = &sprog_.units[(size_t)sprog_.diag_list[(size_t)ls[i].first]];
+        } else {
+          const UpdTile* tl = sprog_.tiles.data() + ls[i].first;
+          bool same = true;
+          for (int64_t q = 0; same && q < ls[i].count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
+          if (same && ls[i].count < 32768) out[i] = &sprog_.units[(size_t)tl[0].unit];
+        }
+      }
+    };
+    ones(sprog_.fwd, sm_one_fwd_);
+    ones(sprog_.bwd, sm_one_bwd_);
+  }
+  return 0;
+}
+
+// one block of nv <= rb vectors: pack, the sweeps `job` asks for, unpack (enqueue only)
+void Engine::enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order) {
+  const int n = S_->n;
+  const int* order = pivot_order ? nullptr : d_smorder_;
+  launch_solve_many_pack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
+  auto run = [&](const std::vector<SolveLaunch>& ls, const std::vector<const SolveUnit*>& one) {
+    for (size_t i = 0; i < ls.size(); ++i)
+      launch_solve_many(stream_, ls[i].kind, d_slist_, d_stiles_, ls[i].first, ls[i].count, d_sunits_, d_L_, d_dinv_,
+                        d_rlist_, d_smW_, rb, one[i]);
+  };
+  if (job == 0 || job == 1) run(sprog_.fwd, sm_one_fwd_);
+  if (job == 0 || job == 2) run(sprog_.bwd, sm_one_bwd_);
+  launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
+}
+
+int Engine::solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  if (status_) return status_;
+  sm_err_.clear();
+  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (pending_) return -10;          // (the caller waits first)
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_many(false);
+  if (rc) return rc;
+  // 32 per sweep while at least 32 are left; the tail as one zero-padded block of 16 or 32
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
+    enqueue_solve_many_block(x_dev + (int64_t)done * ldx, ldx, nv, rb, job, pivot_order);
+    done += nv;
+  }
+  HIPCHK(hipGetLastError(), "solve_many launch");
+  return sync_stream(stream_, "solve_many sync");
+}
+
+int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
+  if (status_) return status_;
+  sm_err_.clear();
+  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_many(true);
+  if (rc) return rc;
+  const int n = S_->n;
+  const size_t vb = sizeof(double) * (size_t)n;
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
+    double* xb = x_host + (int64_t)done * ldx;
+    // the block in the caller's layout, its n-vectors only (the permutation happens on the device)
+    if (ldx == n) {
+      HIPCHK(hipMemcpyAsync(d_smstage_, xb, vb * (size_t)nv, hipMemcpyHostToDevice, stream_), "rhs H2D");
+    } else {
+      for (int q = 0; q < nv; ++q)
+        HIPCHK(hipMemcpyAsync(d_smstage_ + (size_t)q * n, xb + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "rhs H2D");
+    }
+    enqueue_solve_many_block(d_smstage_, n, nv, rb, job, false);
+    HIPCHK(hipGetLastError(), "solve_many launch");
+    if (ldx == n) {
+      HIPCHK(hipMemcpyAsync(xb, d_smstage_, vb * (size_t)nv, hipMemcpyDeviceToHost, stream_), "x D2H");
+    } else {
+      for (int q = 0; q < nv; ++q)
+        HIPCHK(hipMemcpyAsync(xb + (int64_t)q * ldx, d_smstage_ + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "x D2H");
+    }
+    if ((rc = sync_stream(stream_, "solve_many sync"))) return rc;
+    done += nv;
+  }
+  return 0;
+}
+
 // Per-launch device time of one factorization from HIP events on the stream each launch
 // runs on.  serial = true: the whole program on one stream, launch after launch (the
 // kernels alone on the chip).  serial = false: the real multi-stream program; every

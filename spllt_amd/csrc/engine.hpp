@@ -124,6 +124,13 @@ class Engine {
   // substitution on device vectors in pivot order; phase -1 = all, 0/1/2 = partitioned phases
   int solve_dev(double* y_dev, int nrhs, int job, int phase);
   int prepare_solve();
+  // ---- blocked solve for many right-hand sides (solve_many.hip, single GPU): the same substitution
+  // program on blocks of 32 right-hand sides (a tail of at most 16: one block of 16), fp64 MFMA kernels,
+  // L read once per block.  x: vector q at x[q * ldx .. q * ldx + n), ldx >= n, overwritten; nothing
+  // outside those ranges is read or written.  The strips add with fp64 atomics: reproducible to rounding.
+  int solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order);
+  int solve_many(double* x_host, int nrhs, int64_t ldx, int job);   // host vectors, user order
+  const std::string& solve_many_error() const { return sm_err_; }
   // ---- selected inversion (selinv.hip, single GPU): Z = (P A P^T)^-1 on the pattern of L, in a
   // second arena with L's layout.  Computed from the current factor (after wait()); a later
   // factorization marks it stale: the readers below then fail instead of returning old numbers.
@@ -266,6 +273,14 @@ class Engine {
   int* d_rlist_ = nullptr;
   int* d_flag_ = nullptr;
   int* h_flag_ = nullptr;  // pinned
+  // blocked solve (workspace allocated on first use, kept with the engine)
+  int prepare_solve_many(bool host_stage);
+  void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
+  std::string sm_err_;
+  double* d_smW_ = nullptr;        // n * 32 doubles: W[p * rb + q]
+  double* d_smstage_ = nullptr;    // n * 32 doubles: a block of host vectors in the caller's order (solve_many)
+  int* d_smorder_ = nullptr;       // user variable -> pivot position
+  std::vector<const SolveUnit*> sm_one_fwd_, sm_one_bwd_;   // per launch: its ONE block column, or null
   // selected inversion (tables uploaded once per pattern, on first use)
   int prepare_selinv();
   void release_buffer(void* p);

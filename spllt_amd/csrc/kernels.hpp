@@ -82,6 +82,17 @@ void launch_solve(hipStream_t st, int kind, const int* list, const UpdTile* tile
                   const int* rlist, double* y, int nr, int64_t ldy, bool four = false,
                   const SolveUnit* one = nullptr);   // one: the launch works on ONE block column (host copy of its unit;
                                                      // strips: strip i = workgroup i) -- the descriptor travels with the arguments
+// blocked solve for many right-hand sides (solve_many.hip): one launch of the SAME solve program on the
+// workspace W[p * rb + q] (pivot position p, right-hand side q < rb; rb = 16 or 32), products on fp64 MFMA
+void launch_solve_many(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first,
+                       int64_t count, const SolveUnit* units, const double* L, const double* dinv,
+                       const int* rlist, double* W, int rb, const SolveUnit* one = nullptr);
+// W <- the caller's nv <= rb vectors x[q * ldx + i] (order: user variable i -> pivot position, null = x is in
+// pivot order), columns nv .. rb - 1 of W zero; and back (only the nv real vectors are written)
+void launch_solve_many_pack(hipStream_t st, const double* x, int64_t ldx, const int* order, int n, int nv, int rb,
+                            double* W);
+void launch_solve_many_unpack(hipStream_t st, double* x, int64_t ldx, const int* order, int n, int nv, int rb,
+                              double* W);
 // selected inversion (selinv.hip): one launch of a SelinvProgram (SI_SYMM / SI_SCALE: tiles[first ..];
 // SI_DIAG: units[first ..]) on the Z arena; scratch: the program's scratch_size doubles
 void launch_selinv(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* units, const UpdTile* tiles,
