@@ -306,6 +306,62 @@ double *spllt_hip_device_inverse(void *fkeep);                         /* device
 int     spllt_hip_inverse_diag(void *fkeep, double *out, int n);        /* (A^-1)_ii, user order, host */
 int     spllt_hip_log_det(void *fkeep, double *out);                    /* log det A of the last factor */
 int     spllt_hip_release_inverse(void *fkeep);                        /* free the Z arena early */
+/* ---- batched factorization (single GPU) ---------------------------------------
+ * nbatch value arrays on the pattern of ONE akeep / fkeep pair are factorized together,
+ * P A_b P^T = L_b L_b^T for b = 0 .. nbatch-1, and solved together.  The members share the symbolic
+ * structure and one set of program tables (uploaded on the first batch call of a handle); every kernel
+ * launch of the batch program carries all members, so the number of launches does not depend on nbatch
+ * (spllt_hip_batch_launches).  Each member has its own factor arena (the layout of
+ * spllt_hip_get_factor), its own not-positive-definite flag and its own log-determinant: one bad
+ * member does not spoil the others.  The batch program is the single-stream, unfused program of the
+ * pattern with 64-wide panels, whatever spllt_hip_set_engine chose for the handle's single
+ * factorization; it is meant for the small, launch-latency-bound end.
+ *
+ * Storage for nbatch members (arena + inverted panels each) is taken on the first call, grows when a
+ * later call brings a larger nbatch, and stays with the handle until spllt_hip_release_batch or
+ * spllt_deallocate_fkeep.  If the device cannot hold it the call returns SPLLT_ERROR_ALLOCATION, keeps
+ * nothing half-allocated, and the handle's single factorization stays usable.
+ *
+ * The batch and the handle's single factor are independent: spllt_hip_get_factor, spllt_solve,
+ * spllt_hip_solve_many and a valid selected inverse stay valid across spllt_hip_factor_batch, and the
+ * batch survives spllt_factor.  All work is ordered on spllt_hip_engine_stream and finished when a
+ * call returns.  Reproducibility is the default engine's: inter-node updates and the solve's strips add
+ * with fp64 atomics, two runs agree to rounding, not bit for bit.
+ *
+ * Only the allocation failure is promised to leave the single factorization usable: a HIP runtime error
+ * inside a batch call (SPLLT_ERROR_HIP) marks the handle's engine as failed, single factorization included.
+ *
+ * Errors: null pointer, negative count, nnz not the pattern's, ldval < nnz, ldx < n, bad job, bad
+ * member, a solve or reader before any batch -> SPLLT_ERROR_PARAMETER; a handle after
+ * spllt_hip_set_partition with nranks > 1 -> SPLLT_ERROR_UNIMPLEMENTED; no device -> SPLLT_ERROR_HIP; a
+ * batch program that holds something the batch kernels do not implement -> SPLLT_ERROR_UNKNOWN.
+ * Messages: spllt_hip_last_error.  nbatch = 0 and nrhs = 0 are no-ops that return 0. */
+/* values of member b at val[b*ldval .. b*ldval + nnz), ldval >= nnz.  0: every member factorized.
+ * SPLLT_ERROR_NOT_POSDEF: at least one member is not positive definite; the OTHER members are
+ * factorized and usable, spllt_hip_batch_status says which. */
+int spllt_hip_factor_batch(void *akeep, void *fkeep, int nbatch, int nnz, const double *val_host, int64_t ldval);
+int spllt_hip_factor_batch_dev(void *akeep, void *fkeep, int nbatch, int nnz, const double *val_dev, int64_t ldval);
+/* flag[b] = 0 or SPLLT_ERROR_NOT_POSDEF; column[b] = 1-based pivot position of the first non-positive
+ * pivot, 0 if none; either pointer may be NULL; at most `capacity` entries are written.  Returns the
+ * nbatch of the last batch (0: none yet). */
+int spllt_hip_batch_status(void *fkeep, int *flag, int *column, int capacity);
+/* nrhs vectors PER MEMBER: vector q of member b at x[(b*nrhs + q)*ldx .. + n), ldx >= n, overwritten;
+ * nothing else is read or written.  Vectors of a failed member are left unchanged; the return value is
+ * SPLLT_ERROR_NOT_POSDEF then and the other members are solved.  job 0 / 1 / 2 as spllt_solve.
+ * pivot_order as spllt_hip_solve_many_dev.  There is no nbatch argument: the call works on ALL members of
+ * the last batch (spllt_hip_batch_status returns their number), so x must hold nbatch * nrhs vectors. */
+int spllt_hip_solve_batch(void *fkeep, int nrhs, double *x_host, int64_t ldx, int job);
+int spllt_hip_solve_batch_dev(void *fkeep, int nrhs, double *x_dev, int64_t ldx, int job, int pivot_order);
+/* one member's arena -> host, the layout of spllt_hip_get_factor */
+int spllt_hip_get_factor_batch(void *fkeep, int member, double *out, int64_t count);
+/* device pointer of member 0's arena; member b starts *member_stride doubles further (NULL / 0: no batch) */
+double *spllt_hip_device_factor_batch(void *fkeep, int64_t *member_stride);
+/* out[b] = log det A_b, nbatch values; NaN for a failed member */
+int spllt_hip_log_det_batch(void *fkeep, double *out);
+/* kernel launches of the last batched factorization (initialisation included) */
+int spllt_hip_batch_launches(void *fkeep);
+/* give the batch's storage back; the next spllt_hip_factor_batch takes it again */
+int spllt_hip_release_batch(void *fkeep);
 /* timings of the last factorization, milliseconds */
 int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, double *h2d_ms,
                            int *launches);
@@ -321,7 +377,10 @@ int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, do
  * "selinv_tiles" (UpdTile bytes: unit, row tile, K slice), "selinv_launches" (int64 x 5 per
  * launch: kind, level, first, count, flops), "selinv_rows" (SelinvRow bytes), "selinv_relpos"
  * (int32), "selinv_diag" (int64 per pivot position: arena offset of its diagonal entry),
- * "selinv_scratch" (int64), "selinv_flops" (double).  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
+ * "selinv_scratch" (int64), "selinv_flops" (double); the program of the batched factorization (the
+ * same for every engine flag): "batch_launches", "batch_units", "batch_tiles", "batch_chains",
+ * "batch_relpos", "batch_dinv_size" with the layouts of their unprefixed counterparts (and
+ * "batch_potrf", empty, "batch_scratch_size", 0).  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
  * spllt_amd/api.py.  Returns the byte length. */
 int64_t spllt_hip_program_get(void *fkeep, const char *name, void *buf, int64_t capacity_bytes);
 /* per-launch device time (ms) of one profiled factorization; returns #launches */
@@ -343,7 +402,9 @@ const char *spllt_hip_version(void);
 
 /* test hooks: "wedge" marks the HIP runtime as not having returned from a call (what the wait /
  * submission deadlines do), "wedged" reads the mark (1 / 0), "teardown" runs the library's atexit
- * handler now (it must touch nothing once the mark is set).  -1: unknown request. */
+ * handler now (it must touch nothing once the mark is set); "batch_grid_limit=N": a launch of the batched
+ * factorization or solve whose (work items) x (members) exceeds N workgroups is split by member range
+ * (N <= 0: back to the hardware limit, (2^32 - 1) / 256 workgroups).  -1: unknown request. */
 int spllt_hip_debug(const char *what);
 
 #ifdef __cplusplus

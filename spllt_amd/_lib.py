@@ -61,6 +61,9 @@ HIP_SYMBOLS = [
     "spllt_hip_selected_inverse", "spllt_hip_get_inverse", "spllt_hip_device_inverse", "spllt_hip_inverse_diag",
     "spllt_hip_log_det", "spllt_hip_release_inverse",
     "spllt_hip_solve_many", "spllt_hip_solve_many_dev",
+    "spllt_hip_factor_batch", "spllt_hip_factor_batch_dev", "spllt_hip_batch_status", "spllt_hip_solve_batch",
+    "spllt_hip_solve_batch_dev", "spllt_hip_get_factor_batch", "spllt_hip_device_factor_batch",
+    "spllt_hip_log_det_batch", "spllt_hip_batch_launches", "spllt_hip_release_batch",
 ]
 
 _lib = None
@@ -204,5 +207,24 @@ def load():
     lib.spllt_hip_release_inverse.restype = C.c_int
     lib.spllt_hip_last_flag.argtypes = [vp]
     lib.spllt_hip_last_flag.restype = C.c_int
+    for fn in (lib.spllt_hip_factor_batch, lib.spllt_hip_factor_batch_dev):
+        fn.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int64]
+        fn.restype = C.c_int
+    lib.spllt_hip_batch_status.argtypes = [vp, ip, ip, C.c_int]
+    lib.spllt_hip_batch_status.restype = C.c_int
+    lib.spllt_hip_solve_batch.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int]
+    lib.spllt_hip_solve_batch.restype = C.c_int
+    lib.spllt_hip_solve_batch_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int]
+    lib.spllt_hip_solve_batch_dev.restype = C.c_int
+    lib.spllt_hip_get_factor_batch.argtypes = [vp, C.c_int, dp, C.c_int64]
+    lib.spllt_hip_get_factor_batch.restype = C.c_int
+    lib.spllt_hip_device_factor_batch.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.spllt_hip_device_factor_batch.restype = C.c_void_p
+    lib.spllt_hip_log_det_batch.argtypes = [vp, dp]
+    lib.spllt_hip_log_det_batch.restype = C.c_int
+    lib.spllt_hip_batch_launches.argtypes = [vp]
+    lib.spllt_hip_batch_launches.restype = C.c_int
+    lib.spllt_hip_release_batch.argtypes = [vp]
+    lib.spllt_hip_release_batch.restype = C.c_int
     _lib = lib
     return lib

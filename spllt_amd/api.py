@@ -162,6 +162,8 @@ class Factorization:
         raw = np.zeros(max(nbytes, 1), dtype=np.uint8)
         self.lib.spllt_hip_program_get(self.fkeep, name.encode(), raw.ctypes.data, nbytes)
         raw = raw[:nbytes]
+        if name.startswith("batch_"):    # the batch program: the layouts of the unprefixed names
+            name = name[len("batch_"):]
         if name == "launches":
             return raw.view(np.int64).reshape(-1, len(LAUNCH_COLS))
         if name == "units":
@@ -395,6 +397,108 @@ class Factorization:
         if rc < 0:
             raise SplltError("spllt_hip_solve_many_dev", rc, self.last_error())
         return self
+
+    # ---- batched factorization ------------------------------------------------
+    def _batch_rc(self, where, rc):
+        """every error raises, except -20: a batch with a member that is not positive definite returns
+        normally (batch_status() tells which), so that a sweep with one bad sample keeps the rest"""
+        if rc < 0 and rc != -20:
+            raise SplltError(where, rc, self.last_error())
+        return rc
+
+    def factor_batch(self, vals, ldval=None):
+        """spllt_hip_factor_batch: vals of shape (B, nnz), one row of values per member; finished on
+        return.  Returns 0, or -20 when at least one member is not positive definite."""
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if vals.ndim != 2:
+            raise ValueError("factor_batch: vals must have shape (B, nnz)")
+        if ldval is None:
+            ldval = vals.shape[1]
+        rc = self.lib.spllt_hip_factor_batch(self.akeep, self.fkeep, vals.shape[0], self.nnz,
+                                             C.c_void_p(vals.ctypes.data), int(ldval))
+        return self._batch_rc("spllt_hip_factor_batch", rc)
+
+    def factor_batch_dev(self, val_dev_ptr, nbatch, ldval=None):
+        """the same with the values in HBM (integer device pointer; member b at ptr + b * ldval doubles)"""
+        if ldval is None:
+            ldval = self.nnz
+        rc = self.lib.spllt_hip_factor_batch_dev(self.akeep, self.fkeep, int(nbatch), self.nnz,
+                                                 C.c_void_p(val_dev_ptr), int(ldval))
+        return self._batch_rc("spllt_hip_factor_batch_dev", rc)
+
+    def batch_status(self):
+        """(flags, columns) of the last batch: 0 / -20 per member, 1-based pivot position of the first
+        non-positive pivot (0: none)"""
+        nb = self.lib.spllt_hip_batch_status(self.fkeep, None, None, 0)
+        if nb < 0:
+            raise SplltError("spllt_hip_batch_status", nb, self.last_error())
+        flags = np.zeros(max(nb, 1), dtype=np.int32)
+        cols = np.zeros(max(nb, 1), dtype=np.int32)
+        self.lib.spllt_hip_batch_status(self.fkeep, _ip(flags), _ip(cols), nb)
+        return flags[:nb], cols[:nb]
+
+    def solve_batch(self, b, job=0):
+        """spllt_hip_solve_batch on a copy of b: shape (B, n), one vector per member, or (B, nrhs, n).
+        The vectors of a member that is not positive definite come back unchanged."""
+        x = np.array(b, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (2, 3):
+            raise ValueError("solve_batch: b must have shape (B, n) or (B, nrhs, n)")
+        nrhs = 1 if x.ndim == 2 else x.shape[1]
+        # the C entry point takes no nbatch: it reads and writes the vectors of EVERY member of the last batch
+        nb = self.lib.spllt_hip_batch_status(self.fkeep, None, None, 0)
+        if nb > 0 and x.shape[0] != nb:
+            raise ValueError(f"solve_batch: b holds vectors for {x.shape[0]} members, the last batch has {nb}")
+        if x.shape[-1] != self.n:
+            raise ValueError(f"solve_batch: the vectors have length {x.shape[-1]}, n = {self.n}")
+        rc = self.lib.spllt_hip_solve_batch(self.fkeep, nrhs, C.c_void_p(x.ctypes.data), x.shape[-1], job)
+        self._batch_rc("spllt_hip_solve_batch", rc)
+        return x
+
+    def solve_batch_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
+        """spllt_hip_solve_batch_dev: device vectors in place, vector q of member b at
+        x[(b*nrhs + q)*ldx .. + n); pivot_order as solve_many_dev.  Returns 0 or -20.
+        The library touches nbatch * nrhs vectors, nbatch being the size of the LAST batch
+        (batch_status()[0].size): the array behind the pointer must hold that many."""
+        if ldx is None:
+            ldx = self.n
+        rc = self.lib.spllt_hip_solve_batch_dev(self.fkeep, int(nrhs), C.c_void_p(x_dev_ptr), int(ldx), job,
+                                                1 if pivot_order else 0)
+        return self._batch_rc("spllt_hip_solve_batch_dev", rc)
+
+    def get_factor_batch(self, member, out=None):
+        """one member's arena on the host (the layout of get_factor)"""
+        arena = self.sym_info()["arena"]
+        if out is None:
+            out = np.zeros(max(arena, 1), dtype=np.float64)
+        assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
+        rc = self.lib.spllt_hip_get_factor_batch(self.fkeep, int(member), _dp(out), arena)
+        if rc < 0:
+            raise SplltError("spllt_hip_get_factor_batch", rc, self.last_error())
+        return out[:arena]
+
+    def device_factor_batch_ptr(self):
+        """(device pointer of member 0's arena, member stride in doubles)"""
+        stride = C.c_int64()
+        p = self.lib.spllt_hip_device_factor_batch(self.fkeep, C.byref(stride))
+        return p, stride.value
+
+    def log_det_batch(self):
+        """log det A_b of every member of the last batch (NaN for a failed member)"""
+        nb = self.lib.spllt_hip_batch_status(self.fkeep, None, None, 0)
+        out = np.zeros(max(nb, 1), dtype=np.float64)
+        rc = self.lib.spllt_hip_log_det_batch(self.fkeep, _dp(out))
+        if rc < 0:
+            raise SplltError("spllt_hip_log_det_batch", rc, self.last_error())
+        return out[:nb]
+
+    def batch_launches(self):
+        """kernel launches of the last batched factorization"""
+        return int(self.lib.spllt_hip_batch_launches(self.fkeep))
+
+    def release_batch(self):
+        rc = self.lib.spllt_hip_release_batch(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_batch", rc, self.last_error())
 
     # ---- multi-GPU subtree partition ------------------------------------------
     def set_partition(self, rank, nranks):

@@ -3,6 +3,7 @@
 // reference interfaces/C/spllt_data_ciface.F90: never aborts, messages on
 // stderr, status in info->flag.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,6 +45,10 @@ struct Fkeep {
   std::shared_ptr<const Symbolic> si_S;
   int si_pw = -1, si_cb = -1, si_rc = 0;
   SelinvProgram si_prog;
+  // the batch program of spllt_hip_program_get (built once per pattern)
+  std::shared_ptr<const Symbolic> bt_S;
+  int bt_rc = 0;
+  Program bt_prog;
 };
 
 std::mutex g_mu;
@@ -591,13 +596,18 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 }
 
 // test hooks of the process-wide "runtime is wedged" state (engine.cpp): "wedge" sets it, "wedged"
-// reads it, "teardown" runs the atexit handler of the pools now
+// reads it, "teardown" runs the atexit handler of the pools now; "batch_grid_limit=N" lowers the grid size
+// from which on a batched launch is split by member range (N <= 0: the hardware limit again)
 int spllt_hip_debug(const char* what) {
   if (!what) return -1;
   const std::string w(what);
   if (w == "wedge") { mark_runtime_wedged(); return 0; }
   if (w == "wedged") return runtime_wedged() ? 1 : 0;
   if (w == "teardown") { run_pools_teardown_for_test(); return 0; }
+  if (w.rfind("batch_grid_limit=", 0) == 0) {   // workgroups from which on a batched launch splits its members
+    set_batch_grid_limit(std::atoll(w.c_str() + 17));
+    return 0;
+  }
   return -1;
 }
 
@@ -806,6 +816,164 @@ int spllt_hip_solve_many_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, 
   return rc ? solve_many_fail(f, rc) : 0;
 }
 
+// ---- batched factorization --------------------------------------------------
+static int batch_param_error(Fkeep* f, const char* what, const char* bad) {
+  f->last_error = std::string(what) + ": " + bad;
+  return SPLLT_ERROR_PARAMETER;
+}
+
+static int batch_partitioned(Fkeep* f, const char* what) {
+  if (f->eo.nranks <= 1) return 0;
+  f->last_error = std::string(what) + ": not available on a partitioned (multi-GPU) handle";
+  std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
+  return SPLLT_ERROR_UNIMPLEMENTED;
+}
+
+static int batch_fail(Fkeep* f, int rc) {
+  if (!f->eng->batch_error().empty()) f->last_error = f->eng->batch_error();
+  else if (f->eng->status()) f->last_error = f->eng->error();
+  return rc;
+}
+
+// the handle's engine with a finished batch on it, or an error flag
+static int batch_reader(Fkeep* f, const char* what) {
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (int rc = batch_partitioned(f, what)) return rc;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (!f->eng || f->eng->batch_count() <= 0) return batch_param_error(f, what, "no batch has been factorized on this handle");
+  if (f->eng->pending()) (void)do_wait(f);   // (the single factorization shares the stream and the staging buffers)
+  return 0;
+}
+
+static int factor_batch_impl(void* akeep, void* fkeep, int nbatch, int nnz, const double* val, int64_t ldval, bool dev,
+                             const char* what) {
+  Akeep* a = static_cast<Akeep*>(akeep);
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!a || !f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!val) return batch_param_error(f, what, "the array of values is null");
+  if (nbatch < 0) return batch_param_error(f, what, "nbatch < 0");
+  if ((int64_t)nnz != f->S->nnzA) return batch_param_error(f, what, "nnz does not match the analysed pattern");
+  if (ldval < nnz) return batch_param_error(f, what, "ldval < nnz");
+  if (int rc = batch_partitioned(f, what)) return rc;
+  if (nbatch == 0) return 0;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (f->eng && f->eng->pending()) (void)do_wait(f);
+  if (!f->eng) {
+    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
+    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
+    f->eng->set_exchange_buffer(f->xbuf);
+  }
+  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
+  int rc = f->eng->factor_batch(val, dev, nbatch, ldval);
+  if (rc == SPLLT_ERROR_NOT_POSDEF) {
+    const std::vector<int>& fl = f->eng->batch_flags();
+    int nbad = 0, first = -1;
+    for (size_t b = 0; b < fl.size(); ++b)
+      if (fl[b] != INT_MAX) { if (first < 0) first = (int)b; ++nbad; }
+    f->last_error = std::string(what) + ": " + std::to_string(nbad) + " of " + std::to_string(nbatch) +
+                    " members are not positive definite (first: member " + std::to_string(first) + ", pivot column " +
+                    std::to_string(first >= 0 ? fl[(size_t)first] : 0) + " in elimination order)";
+    return rc;
+  }
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+int spllt_hip_factor_batch(void* akeep, void* fkeep, int nbatch, int nnz, const double* val_host, int64_t ldval) {
+  return factor_batch_impl(akeep, fkeep, nbatch, nnz, val_host, ldval, false, "spllt_hip_factor_batch");
+}
+
+int spllt_hip_factor_batch_dev(void* akeep, void* fkeep, int nbatch, int nnz, const double* val_dev, int64_t ldval) {
+  return factor_batch_impl(akeep, fkeep, nbatch, nnz, val_dev, ldval, true, "spllt_hip_factor_batch_dev");
+}
+
+int spllt_hip_batch_status(void* fkeep, int* flag, int* column, int capacity) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  if (!f->eng || f->dead) return 0;
+  const std::vector<int>& fl = f->eng->batch_flags();
+  const int nb = f->eng->batch_count();
+  for (int b = 0; b < nb && b < capacity; ++b) {
+    const bool bad = fl[(size_t)b] != INT_MAX;
+    if (flag) flag[b] = bad ? SPLLT_ERROR_NOT_POSDEF : 0;
+    if (column) column[b] = bad ? fl[(size_t)b] : 0;
+  }
+  return nb;
+}
+
+static int solve_batch_impl(void* fkeep, int nrhs, double* x, int64_t ldx, int job, bool dev, bool pivot_order,
+                            const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!x) return batch_param_error(f, what, "the array of right-hand sides is null");
+  if (nrhs < 0) return batch_param_error(f, what, "nrhs < 0");
+  if (ldx < f->S->n) return batch_param_error(f, what, "ldx < n");
+  if (job < 0 || job > 2) return batch_param_error(f, what, "job is not 0, 1 or 2");
+  int rc = batch_reader(f, what);
+  if (rc) return rc;
+  if (nrhs == 0) return 0;
+  rc = f->eng->solve_batch(x, dev, nrhs, ldx, job, pivot_order);
+  if (rc == SPLLT_ERROR_NOT_POSDEF) {
+    f->last_error = std::string(what) + ": the vectors of the members that are not positive definite were left unchanged "
+                                        "(spllt_hip_batch_status)";
+    return rc;
+  }
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+int spllt_hip_solve_batch(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
+  return solve_batch_impl(fkeep, nrhs, x_host, ldx, job, false, false, "spllt_hip_solve_batch");
+}
+
+int spllt_hip_solve_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  return solve_batch_impl(fkeep, nrhs, x_dev, ldx, job, true, pivot_order != 0, "spllt_hip_solve_batch_dev");
+}
+
+int spllt_hip_get_factor_batch(void* fkeep, int member, double* out, int64_t count) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_get_factor_batch";
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!out) return batch_param_error(f, what, "the output array is null");
+  if (count < 0) return batch_param_error(f, what, "count < 0");
+  int rc = batch_reader(f, what);
+  if (rc) return rc;
+  if (member < 0 || member >= f->eng->batch_count()) return batch_param_error(f, what, "member is not in [0, nbatch)");
+  rc = f->eng->download_batch(member, out, count);
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+double* spllt_hip_device_factor_batch(void* fkeep, int64_t* member_stride) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (member_stride) *member_stride = 0;
+  if (!f || !f->eng || f->dead) return nullptr;
+  return f->eng->device_batch(member_stride);
+}
+
+int spllt_hip_log_det_batch(void* fkeep, double* out) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_log_det_batch";
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!out) return batch_param_error(f, what, "the output array is null");
+  int rc = batch_reader(f, what);
+  if (rc) return rc;
+  rc = f->eng->log_det_batch(out);
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+int spllt_hip_batch_launches(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  return (f->eng && !f->dead) ? f->eng->batch_launches() : 0;
+}
+
+int spllt_hip_release_batch(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  if (!f->eng || f->dead) return 0;
+  if (f->eng->pending()) (void)do_wait(f);
+  int rc = f->eng->release_batch();
+  return rc ? batch_fail(f, rc) : 0;
+}
+
 // ---- selected inversion ---------------------------------------------------
 // the handle's engine with its factor finished, or an error flag (with the message in last_error)
 static int selinv_engine(Fkeep* f, const char* what) {
@@ -923,6 +1091,20 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
     if (buf && bytes) std::memcpy(buf, p, std::min<size_t>(bytes, (size_t)cap));
     return (int64_t)bytes;
   };
+  if (k.rfind("batch_", 0) == 0) {
+    // the program of the batched factorization: fixed options, independent of the handle's engine flags
+    if (f->bt_S != f->S) {
+      f->bt_rc = build_batch_program(*f->S, f->bt_prog, &f->last_error);
+      f->bt_S = f->S;
+    }
+    if (f->bt_rc) return -1;
+    P = &f->bt_prog;
+    k = k.substr(6);
+    // ("potrf" and "scratch_size" -- empty and 0 in this program -- because tests/emulate.py asks for them)
+    if (k != "launches" && k != "units" && k != "tiles" && k != "chains" && k != "relpos" && k != "dinv_size" &&
+        k != "potrf" && k != "scratch_size")
+      return -1;
+  }
   if (k == "launches") {
     std::vector<int64_t> v;
     for (const Launch& l : P->launches) {

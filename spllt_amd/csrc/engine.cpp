@@ -582,6 +582,25 @@ void pools_teardown() {
 }
 }  // namespace
 
+// the val -> L map bucketed by chunks of kInitChunk doubles of the arena (k_init_arena, k_batch_init): a
+// counting sort, two passes over the map; at least one chunk
+static void bucket_value_map(const Symbolic& S, std::vector<int64_t>& cptr, std::vector<unsigned short>& loc,
+                             std::vector<int>& src) {
+  const int64_t nch = std::max<int64_t>(1, (S.arena + kInitChunk - 1) / kInitChunk);
+  cptr.assign((size_t)nch + 1, 0);
+  for (int64_t d : S.map_dst) cptr[(size_t)(d / kInitChunk) + 1]++;
+  for (int64_t c = 0; c < nch; ++c) cptr[(size_t)c + 1] += cptr[(size_t)c];
+  std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
+  loc.resize(S.map_dst.size());
+  src.resize(S.map_dst.size());
+  for (size_t i = 0; i < S.map_dst.size(); ++i) {
+    const int64_t d = S.map_dst[i];
+    const int64_t at = fill[(size_t)(d / kInitChunk)]++;
+    loc[(size_t)at] = (unsigned short)(d % kInitChunk);
+    src[(size_t)at] = (int)S.map_src[i];
+  }
+}
+
 int Engine::upload() {
   const Symbolic& S = *S_;
   crumb("engine: upload begins");
@@ -665,19 +684,10 @@ int Engine::upload() {
     // (k_init_arena): a counting sort, two passes over the map
     static const bool one_pass = [] { const char* e = std::getenv("SPLLT_INIT_ONE_PASS"); return !(e && std::atoi(e) == 0); }();
     if (one_pass && S.arena > 0 && S.nnzA <= INT_MAX) {
-      const int64_t nch = (S.arena + kInitChunk - 1) / kInitChunk;
-      std::vector<int64_t> cptr((size_t)nch + 1, 0);
-      for (int64_t d : S.map_dst) cptr[(size_t)(d / kInitChunk) + 1]++;
-      for (int64_t c = 0; c < nch; ++c) cptr[(size_t)c + 1] += cptr[(size_t)c];
-      std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
-      std::vector<unsigned short> loc(S.map_dst.size());
-      std::vector<int> src(S.map_dst.size());
-      for (size_t i = 0; i < S.map_dst.size(); ++i) {
-        const int64_t d = S.map_dst[i];
-        const int64_t at = fill[(size_t)(d / kInitChunk)]++;
-        loc[(size_t)at] = (unsigned short)(d % kInitChunk);
-        src[(size_t)at] = (int)S.map_src[i];
-      }
+      std::vector<int64_t> cptr;
+      std::vector<unsigned short> loc;
+      std::vector<int> src;
+      bucket_value_map(S, cptr, loc, src);
       HIPCHK(dev_upload(&d_init_cptr_, cptr), "upload init map");
       HIPCHK(dev_upload(&d_init_loc_, loc), "upload init map");
       HIPCHK(dev_upload(&d_init_src_, src), "upload init map");
@@ -1751,6 +1761,333 @@ int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
     if ((rc = sync_stream(stream_, "solve_many sync"))) return rc;
     done += nv;
   }
+  return 0;
+}
+
+// ---- batched factorization ------------------------------------------------------------------------
+int build_batch_program(const Symbolic& S, Program& P, std::string* why) {
+  ScheduleOptions so;
+  so.pw = 64;
+  so.tile = 64;
+  so.cb = 64;
+  so.chain4 = false;
+  so.lookahead = false;
+  so.fused_panel = false;
+  so.subtrees = false;
+  so.deterministic = false;
+  P = Program();
+  build_program(S, so, P);
+  auto bad = [&](const std::string& what) {
+    if (why) *why = "batched factorization: the batch program holds " + what + ", which the batch kernels do not implement";
+    return -99;
+  };
+  if (P.pw != 64 || !P.exchanges.empty()) return bad("a panel width other than 64 or an exchange");
+  for (size_t i = 0; i < P.launches.size(); ++i) {
+    const Launch& l = P.launches[i];
+    if (l.kind != L_CHAIN && l.kind != L_GEMM) return bad("launch kind " + std::to_string(l.kind));
+    if (l.count <= 0) continue;
+    if (l.kind == L_CHAIN) {
+      for (int64_t q = l.first; q < l.first + l.count; ++q) {
+        const ChainUnit& u = P.chain_units[(size_t)q];
+        if (u.pn < 1 || u.pn > kPanelMax || u.cs != u.c0 || u.ce != u.c0 + u.pn) return bad("a chain block wider than its panel");
+      }
+      continue;
+    }
+    if (l.tile != 32 && l.tile != 64) return bad("tile edge " + std::to_string(l.tile));
+    for (int64_t q = l.first; q < l.first + l.count; ++q) {
+      const UpdUnit& u = P.units[(size_t)P.tiles[(size_t)q].unit];
+      if (u.mode != MODE_DIRECT && u.mode != MODE_SCATTER && u.mode != MODE_TRSM) return bad("unit mode " + std::to_string(u.mode));
+      if (u.mode == MODE_DIRECT && u.atomic) return bad("a DIRECT unit that subtracts with atomics");
+      // a TRSM tile overwrites its own operand rows: it must cover all the unit's columns, and the K
+      // window must be the inverted panel's
+      if (u.mode == MODE_TRSM && (u.N > l.tile || u.nseg != 1 || u.klen != u.dinv_ld)) return bad("a TRSM unit wider than its tile");
+    }
+  }
+  return 0;
+}
+
+void batch_diag_positions(const Symbolic& S, std::vector<int64_t>& pos) {
+  pos.resize((size_t)S.n);
+  for (int g = 0; g < S.n; ++g) {
+    const int s = S.snode_of[g], k = g - S.sptr[s];
+    const BlockCol& B = S.bcols[S.node_bcol0[s] + k / S.nb];
+    pos[(size_t)g] = B.off + (int64_t)(k - B.r0) * B.width + (k - B.r0);
+  }
+}
+
+BatchView Engine::batch_view() const {
+  BatchView v;
+  v.L = bt_.L;
+  v.dinv = bt_.dinv;
+  v.flag = bt_.flag;
+  v.lstride = bt_.lstride;
+  v.dstride = bt_.dstride;
+  v.nbatch = bt_.nbatch;
+  v.member_fast = bt_.member_fast;
+  return v;
+}
+
+static int batch_alloc_code(hipError_t e) { return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : kErrHip; }
+
+// program, solve program and index tables of the batch: built and uploaded once per engine
+int Engine::prepare_batch() {
+  if (bt_.ready) return 0;
+  const Symbolic& S = *S_;
+  int rc = build_batch_program(S, bt_.prog, &bt_err_);
+  if (rc) return rc;
+  build_solve_program(S, 64, 64, bt_.sprog);
+  // the bucketed value map: the engine's own tables where its one-pass initialisation uploaded them
+  std::vector<int64_t> cptr;
+  std::vector<unsigned short> loc;
+  std::vector<int> src;
+  bt_.own_init = !(d_init_cptr_ && d_init_loc_ && d_init_src_);
+  if (bt_.own_init) bucket_value_map(S, cptr, loc, src);
+  std::vector<int64_t> diag;
+  batch_diag_positions(S, diag);
+  std::vector<int> order(S.order.begin(), S.order.end());
+  TableStager tab;
+  tab.add(&bt_.units, bt_.prog.units);
+  tab.add(&bt_.tiles, bt_.prog.tiles);
+  tab.add(&bt_.chain, bt_.prog.chain_units);
+  tab.add(&bt_.relpos, bt_.prog.relpos);
+  if (bt_.own_init) {
+    tab.add(&bt_.init_cptr, cptr);
+    tab.add(&bt_.init_loc, loc);
+    tab.add(&bt_.init_src, src);
+  }
+  tab.add(&bt_.diag, diag);
+  tab.add(&bt_.order, order);
+  tab.add(&bt_.sunits, bt_.sprog.units);
+  tab.add(&bt_.slist, bt_.sprog.diag_list);
+  tab.add(&bt_.stiles, bt_.sprog.tiles);
+  // (a failure here leaves the single factorization usable: the engine's status is not touched)
+  hipError_t e = tab.commit(&bt_.d_tab, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (bt_.d_tab) { release_buffer(bt_.d_tab); bt_.d_tab = nullptr; }
+    bt_err_ = std::string("batched factorization: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
+    return batch_alloc_code(e);
+  }
+  if (!bt_.own_init) {
+    bt_.init_cptr = d_init_cptr_;
+    bt_.init_loc = d_init_loc_;
+    bt_.init_src = d_init_src_;
+  }
+  // experiment knob of scripts/factor_batch_bench.py (the A/B of the two grid mappings)
+  if (const char* env = std::getenv("SPLLT_BATCH_MEMBER_FAST")) bt_.member_fast = std::atoi(env) != 0;
+  bt_.ready = true;
+  return 0;
+}
+
+// arenas, dinv scratch, flags and log-det slots for nbatch members; all or nothing
+int Engine::reserve_batch(int nbatch) {
+  if (nbatch <= bt_.capacity) return 0;
+  auto drop = [this]() {
+    for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out})
+      if (p) release_buffer(p);
+    bt_.L = bt_.dinv = bt_.out = nullptr;
+    bt_.flag = nullptr;
+    bt_.capacity = bt_.nbatch = 0;
+    bt_.hflag.clear();
+  };
+  drop();
+  // member strides: multiples of 32 doubles, so that every member starts 256-byte aligned
+  bt_.lstride = std::max<int64_t>(32, (S_->arena + 31) / 32 * 32);
+  bt_.dstride = std::max<int64_t>(32, (bt_.prog.dinv_size + 31) / 32 * 32);
+  const size_t lb = sizeof(double) * (size_t)bt_.lstride * (size_t)nbatch;
+  const size_t db = sizeof(double) * (size_t)bt_.dstride * (size_t)nbatch;
+  hipError_t e = dalloc((void**)&bt_.L, lb);
+  if (e == hipSuccess) e = dalloc((void**)&bt_.dinv, db);
+  if (e == hipSuccess) e = dalloc((void**)&bt_.flag, sizeof(int) * (size_t)nbatch);
+  if (e == hipSuccess) e = dalloc((void**)&bt_.out, sizeof(double) * (size_t)nbatch);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    drop();
+    bt_err_ = "batched factorization: not enough device memory for " + std::to_string(nbatch) + " members (" +
+              std::to_string((lb + db) >> 20) + " MiB): " + hipGetErrorString(e);
+    return batch_alloc_code(e);
+  }
+  bt_.capacity = nbatch;
+  return 0;
+}
+
+int Engine::grow_batch_buffer(double** p, size_t* have, size_t need, const char* what) {
+  if (need <= *have && *p) return 0;
+  if (*p) release_buffer(*p);
+  *p = nullptr;
+  *have = 0;
+  hipError_t e = dalloc((void**)p, sizeof(double) * std::max<size_t>(need, 1));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    bt_err_ = std::string("batch: not enough device memory for ") + what + " (" +
+              std::to_string((sizeof(double) * need) >> 20) + " MiB): " + hipGetErrorString(e);
+    return batch_alloc_code(e);
+  }
+  *have = need;
+  return 0;
+}
+
+int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t ldval) {
+  if (status_) return status_;
+  bt_err_.clear();
+  const int64_t nnz = S_->nnzA;
+  if (!val || nbatch < 0 || ldval < nnz) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;          // (the caller waits first)
+  if (nbatch == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_batch();
+  if (rc) return rc;
+  if ((rc = reserve_batch(nbatch))) return rc;
+  bt_.nbatch = 0;                    // (no batch until this one is finished)
+  bt_.hflag.clear();
+  const double* vd = val;
+  int64_t ld = ldval;
+  if (!on_device) {
+    if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)nnz, "the staged values"))) return rc;
+    if (nnz > 0) {
+      if (ldval == nnz) {
+        HIPCHK(hipMemcpyAsync(bt_.stage, val, sizeof(double) * (size_t)nnz * (size_t)nbatch, hipMemcpyHostToDevice, stream_), "batch val H2D");
+      } else {
+        for (int b = 0; b < nbatch; ++b)
+          HIPCHK(hipMemcpyAsync(bt_.stage + (int64_t)b * nnz, val + (int64_t)b * ldval, sizeof(double) * (size_t)nnz,
+                                hipMemcpyHostToDevice, stream_), "batch val H2D");
+      }
+    }
+    vd = bt_.stage;
+    ld = nnz;
+  }
+  BatchView v = batch_view();
+  v.nbatch = nbatch;
+  bool fits = true;
+  int nl = 0;
+  auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
+  count(launch_batch_init(stream_, v, S_->arena, vd, ld, bt_.init_cptr, bt_.init_loc, bt_.init_src));
+  for (const Launch& l : bt_.prog.launches) {
+    if (l.count <= 0 || !fits) continue;
+    if (l.kind == L_CHAIN)
+      count(launch_batch_chain(stream_, v, bt_.chain + l.first, l.count));
+    else
+      count(launch_batch_update(stream_, v, l.tile, bt_.tiles + l.first, l.count, bt_.units, d_bc_off_, d_bc_w_,
+                                bt_.relpos, d_rlist_));
+  }
+  HIPCHK(hipGetLastError(), "batch factor launch");
+  // (the destination of the copy lives in bt_: a wait that runs into its deadline leaves it in flight)
+  bt_.hflag_pending.assign((size_t)nbatch, 0);
+  HIPCHK(hipMemcpyAsync(bt_.hflag_pending.data(), bt_.flag, sizeof(int) * (size_t)nbatch, hipMemcpyDeviceToHost, stream_), "batch flags D2H");
+  if ((rc = sync_stream(stream_, "batch factor sync"))) return rc;
+  if (!fits) {
+    bt_err_ = "batched factorization: a launch of the program has more work items for ONE member than a grid holds";
+    return -99;
+  }
+  bt_.launches = nl;
+  bt_.nbatch = nbatch;
+  bt_.hflag = bt_.hflag_pending;
+  for (int fl : bt_.hflag)
+    if (fl != INT_MAX) return kErrNotPosDef;
+  return 0;
+}
+
+int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  if (status_) return status_;
+  bt_err_.clear();
+  const int n = S_->n;
+  if (!x || nrhs < 0 || ldx < n || job < 0 || job > 2 || bt_.nbatch <= 0) return -10;
+  if (nrhs == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  const size_t nvec = (size_t)bt_.nbatch * (size_t)nrhs;
+  int rc = grow_batch_buffer(&bt_.Y, &bt_.y_elems, nvec * (size_t)n, "the solve workspace");
+  if (rc) return rc;
+  double* xd = x;
+  int64_t ld = ldx;
+  const size_t vb = sizeof(double) * (size_t)n;
+  if (!on_device) {
+    // the caller's n-vectors only, packed (what lies between them is neither read nor written)
+    if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, nvec * (size_t)n, "the staged right-hand sides"))) return rc;
+    if (ldx == n) {
+      HIPCHK(hipMemcpyAsync(bt_.stage, x, vb * nvec, hipMemcpyHostToDevice, stream_), "batch rhs H2D");
+    } else {
+      for (size_t q = 0; q < nvec; ++q)
+        HIPCHK(hipMemcpyAsync(bt_.stage + q * (size_t)n, x + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "batch rhs H2D");
+    }
+    xd = bt_.stage;
+    ld = n;
+  }
+  const BatchView v = batch_view();
+  const int* order = pivot_order ? nullptr : bt_.order;
+  // (a launch whose work items for one member overflow a grid: every launch has at most as many work items as
+  // the pack, which is checked first -- n / 256 blocks against the block columns and strips of n rows)
+  if (launch_batch_pack(stream_, v, false, xd, ld, nrhs, order, n, bt_.Y) < 0) {
+    bt_err_ = "batch solve: nrhs vectors of one member are more work items than a grid holds";
+    return -99;
+  }
+  bool fits = true;
+  auto run = [&](const std::vector<SolveLaunch>& ls) {
+    for (const SolveLaunch& l : ls)
+      if (launch_batch_solve(stream_, v, l.kind, bt_.slist, bt_.stiles, l.first, l.count, bt_.sunits, d_rlist_, bt_.Y,
+                             nrhs, n) < 0)
+        fits = false;
+  };
+  if (job == 0 || job == 1) run(bt_.sprog.fwd);
+  if (job == 0 || job == 2) run(bt_.sprog.bwd);
+  launch_batch_pack(stream_, v, true, xd, ld, nrhs, order, n, bt_.Y);
+  HIPCHK(hipGetLastError(), "batch solve launch");
+  if (!on_device) {
+    // (the vectors of a failed member come back as they went: nothing on the device touched them)
+    if (ldx == n) {
+      HIPCHK(hipMemcpyAsync(x, bt_.stage, vb * nvec, hipMemcpyDeviceToHost, stream_), "batch x D2H");
+    } else {
+      for (size_t q = 0; q < nvec; ++q)
+        HIPCHK(hipMemcpyAsync(x + (int64_t)q * ldx, bt_.stage + q * (size_t)n, vb, hipMemcpyDeviceToHost, stream_), "batch x D2H");
+    }
+  }
+  if ((rc = sync_stream(stream_, "batch solve sync"))) return rc;
+  if (!fits) {
+    bt_err_ = "batch solve: a launch has more work items for one member than a grid holds (the vectors are not solved)";
+    return -99;
+  }
+  for (int fl : bt_.hflag)
+    if (fl != INT_MAX) return kErrNotPosDef;
+  return 0;
+}
+
+int Engine::download_batch(int member, double* out, int64_t count) {
+  if (status_) return status_;
+  if (!out || member < 0 || member >= bt_.nbatch || count < 0) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  return staged_d2h(out, bt_.L + (int64_t)member * bt_.lstride, sizeof(double) * (size_t)std::min<int64_t>(count, S_->arena));
+}
+
+double* Engine::device_batch(int64_t* member_stride) {
+  if (member_stride) *member_stride = bt_.nbatch > 0 ? bt_.lstride : 0;
+  return bt_.nbatch > 0 ? bt_.L : nullptr;
+}
+
+int Engine::log_det_batch(double* out) {
+  if (status_) return status_;
+  if (!out || bt_.nbatch <= 0) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  launch_batch_log_det(stream_, batch_view(), bt_.diag, S_->n, bt_.out);
+  HIPCHK(hipGetLastError(), "batch log det launch");
+  HIPCHK(hipMemcpyAsync(out, bt_.out, sizeof(double) * (size_t)bt_.nbatch, hipMemcpyDeviceToHost, stream_), "batch log det D2H");
+  return sync_stream(stream_, "batch log det sync");
+}
+
+// the batch's storage back to the pool (the shared tables stay: they are small and per pattern)
+int Engine::release_batch() {
+  if (status_) return status_;
+  if (!bt_.L && !bt_.Y && !bt_.stage) { bt_.nbatch = 0; return 0; }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "batch release")) return rc;
+  for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out, (void*)bt_.Y, (void*)bt_.stage})
+    if (p) release_buffer(p);
+  bt_.L = bt_.dinv = bt_.out = bt_.Y = bt_.stage = nullptr;
+  bt_.flag = nullptr;
+  bt_.capacity = bt_.nbatch = 0;
+  bt_.y_elems = bt_.stage_elems = 0;
+  bt_.hflag.clear();
+  bt_.launches = 0;
   return 0;
 }
 

@@ -50,6 +50,8 @@ struct EngineOptions {
                            // program, -1 by problem size (env SPLLT_HIP_GRAPH overrides)
 };
 
+struct BatchView;   // kernels.hpp
+
 struct FactorStats {
   double submit_ms = 0;   // host time spent in factor_async
   double device_ms = 0;   // HIP-event time from first to last enqueued operation
@@ -143,6 +145,20 @@ class Engine {
   double* device_Z() { return z_valid_ ? d_Z_ : nullptr; }
   const SelinvProgram& selinv_program() const { return siprog_; }
   const std::string& selinv_error() const { return si_err_; }
+  // ---- batched factorization (batch.hip, single GPU): nbatch value sets on this pattern, factorized and
+  // solved together by a second program of the same Symbolic (build_batch_program) whose every launch
+  // carries all members.  The batch has its own arenas, dinv scratch and flags; the tables are shared
+  // by the members and uploaded on the first call.  Independent of the engine's single factor.
+  int factor_batch(const double* val, bool on_device, int nbatch, int64_t ldval);   // 0, -20 (some member), error
+  int batch_count() const { return bt_.nbatch; }
+  const std::vector<int>& batch_flags() const { return bt_.hflag; }   // per member: INT_MAX or 1-based pivot position
+  int solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order);
+  int download_batch(int member, double* out, int64_t count);
+  double* device_batch(int64_t* member_stride);
+  int log_det_batch(double* out);
+  int batch_launches() const { return bt_.launches; }
+  int release_batch();
+  const std::string& batch_error() const { return bt_err_; }
   double* device_L() { return d_L_; }
   hipStream_t stream() { return stream_; }
   // the stream the pending exchange is packed / unpacked on (its collective belongs there); the chain stream when none is pending
@@ -298,6 +314,55 @@ class Engine {
   double* d_Z_ = nullptr;
   double* d_siscratch_ = nullptr;
   double* d_siout_ = nullptr;      // n + 1 doubles: diag(A^-1), log det
+  // batched factorization: tables (uploaded once, on the first batch call) and per-batch storage (grows
+  // with nbatch, stays with the engine until release_batch)
+  struct BatchState {
+    bool ready = false;
+    Program prog;
+    SolveProgram sprog;
+    char* d_tab = nullptr;           // one allocation behind the table pointers below
+    UpdUnit* units = nullptr;
+    UpdTile* tiles = nullptr;
+    ChainUnit* chain = nullptr;
+    int* relpos = nullptr;
+    int64_t* init_cptr = nullptr;    // the value map bucketed by arena chunk (k_batch_init)
+    unsigned short* init_loc = nullptr;
+    int* init_src = nullptr;
+    int64_t* diag = nullptr;         // per pivot position: arena offset of its diagonal entry
+    int* order = nullptr;            // user variable -> pivot position
+    SolveUnit* sunits = nullptr;
+    int* slist = nullptr;
+    UpdTile* stiles = nullptr;
+    double* L = nullptr;             // capacity x lstride
+    double* dinv = nullptr;          // capacity x dstride
+    int* flag = nullptr;             // capacity
+    double* out = nullptr;           // capacity (log det)
+    int capacity = 0, nbatch = 0;
+    int64_t lstride = 0, dstride = 0;
+    double* Y = nullptr;             // solve workspace, pivot order
+    size_t y_elems = 0;
+    double* stage = nullptr;         // host entry points: the caller's values / vectors on the device
+    size_t stage_elems = 0;
+    std::vector<int> hflag;          // flags of the last batch
+    std::vector<int> hflag_pending;  // destination of the flags' D2H copy (outlives a wait that fails)
+    bool own_init = false;           // init_* are the batch's own upload (else the engine's d_init_* tables)
+    int launches = 0;
+    int member_fast = 0;
+  } bt_;
+  std::string bt_err_;
+  int prepare_batch();
+  int reserve_batch(int nbatch);
+  int grow_batch_buffer(double** p, size_t* have, size_t need, const char* what);
+  BatchView batch_view() const;
 };
+
+// The batch program of a pattern: build_program with fixed options (single stream, no fused panels, no
+// chain blocks, no subtree tasks, atomics, pw = tile = 64, no partition), whatever the handle's engine
+// flags say.  0, or -99 with *why when the program holds anything batch.hip does not implement (launch
+// kinds other than L_CHAIN / L_GEMM, tile edges other than 32 / 64, unit modes other than DIRECT /
+// SCATTER / TRSM, an atomic DIRECT unit): nothing is skipped silently.
+int build_batch_program(const Symbolic& S, Program& P, std::string* why);
+// arena offset of the diagonal entry of every pivot position (from the Symbolic structure alone)
+void batch_diag_positions(const Symbolic& S, std::vector<int64_t>& pos);
 
 }  // namespace spx

@@ -103,6 +103,41 @@ void launch_selinv_diag_gather(hipStream_t st, const double* Z, const int64_t* d
                                double* out);
 // out[0] = 2 sum_j log L[diag_pos[j]], in a fixed order
 void launch_log_det(hipStream_t st, const double* L, const int64_t* diag_pos, int n, double* out);
+// ---- batched factorization and solve (batch.hip): nbatch members on one pattern -------------------
+// Member b's arena, dinv scratch and flag: L + b * lstride, dinv + b * dstride, flag + b; every table
+// is shared.  member_fast: see batch.hip (the order of the workgroups of a launch).  Every wrapper
+// returns the number of kernel launches it made: one, unless (work items) x (members) overflows a grid,
+// in which case the members are split into ranges; -1 (nothing launched) when ONE member's work items overflow it.
+struct BatchView {
+  double* L;
+  double* dinv;
+  int* flag;
+  int64_t lstride, dstride;
+  int nbatch;
+  int member_fast;
+};
+// test hook: the number of workgroups from which on the members of a launch are split into ranges (<= 0: the
+// hardware limit of (2^32 - 1) / 256)
+void set_batch_grid_limit(int64_t workgroups);
+// arenas cleared, A_b = val[b * ldval ..] copied in (cptr / loc / src: the bucketed value map of
+// launch_init_arena), flags set to INT_MAX
+int launch_batch_init(hipStream_t st, const BatchView& v, int64_t arena, const double* val, int64_t ldval,
+                      const int64_t* cptr, const unsigned short* loc, const int* src);
+int launch_batch_chain(hipStream_t st, const BatchView& v, const ChainUnit* units, int64_t count);
+// tile = 32 or 64; unit modes DIRECT (exclusive owner), SCATTER, TRSM
+int launch_batch_update(hipStream_t st, const BatchView& v, int tile, const UpdTile* tiles, int64_t count,
+                        const UpdUnit* units, const int64_t* bc_off, const int* bc_w, const int* relpos,
+                        const int* rlist);
+// nrhs vectors per member: x[(b nrhs + q) ldx + i] <-> Y[(b nrhs + q) n + p(i)] (order: user variable ->
+// pivot position, null = x is in pivot order); members whose flag is set are skipped
+int launch_batch_pack(hipStream_t st, const BatchView& v, bool unpack, double* x, int64_t ldx, int nrhs,
+                      const int* order, int n, double* Y);
+// one launch (kind = SolveKind) of a SolveProgram built with pw = cb = 64 on the workspace Y
+int launch_batch_solve(hipStream_t st, const BatchView& v, int kind, const int* list, const UpdTile* tiles,
+                       int64_t first, int64_t count, const SolveUnit* units, const int* rlist, double* Y, int nrhs,
+                       int n);
+// out[b] = 2 sum_j log L_b[diag_pos[j]] in a fixed order; NaN for a member whose flag is set
+int launch_batch_log_det(hipStream_t st, const BatchView& v, const int64_t* diag_pos, int n, double* out);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 
