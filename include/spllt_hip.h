@@ -304,6 +304,9 @@ int     spllt_hip_selected_inverse(void *fkeep);                       /* comput
 int     spllt_hip_get_inverse(void *fkeep, double *out, int64_t count); /* Z arena -> host, L's layout */
 double *spllt_hip_device_inverse(void *fkeep);                         /* device pointer of the Z arena */
 int     spllt_hip_inverse_diag(void *fkeep, double *out, int n);        /* (A^-1)_ii, user order, host */
+/* out[k] = (A^-1) at the k-th entry of the analysed CSC-lower pattern (ptr, row), nnz values in the
+ * order of val, host: what tr(A^-1 dA/dtheta) needs.  One gather launch through the value map. */
+int     spllt_hip_inverse_on_pattern(void *fkeep, double *out);
 int     spllt_hip_log_det(void *fkeep, double *out);                    /* log det A of the last factor */
 int     spllt_hip_release_inverse(void *fkeep);                        /* free the Z arena early */
 /* ---- batched factorization (single GPU) ---------------------------------------
@@ -362,6 +365,44 @@ int spllt_hip_log_det_batch(void *fkeep, double *out);
 int spllt_hip_batch_launches(void *fkeep);
 /* give the batch's storage back; the next spllt_hip_factor_batch takes it again */
 int spllt_hip_release_batch(void *fkeep);
+/* ---- batched selected inversion (single GPU) -------------------------------------
+ * Z_b = (P A_b P^T)^-1 on the pattern of L for every member of the last batch, from the members' factors
+ * and inverted panels, by ONE selected-inversion program of the pattern (64-wide panels: those of the
+ * batch factorization, whatever the handle's panel width) whose every kernel launch carries all members.
+ * A step of the program whose panels all have at most 64 rows below them runs as one fused launch instead
+ * of three; the number of launches does not depend on nbatch
+ * (spllt_hip_batch_selinv_launches).  Member b's Z arena has the layout of spllt_hip_get_inverse.  No
+ * atomics: two inversions of one batch give a bit-identical Z for every member.
+ *
+ * The Z arenas (nbatch x the arena) and a step scratch are taken on the first call, grow with nbatch and
+ * stay until spllt_hip_release_inverse_batch, spllt_hip_release_batch or spllt_deallocate_fkeep.  Too
+ * little device memory -> SPLLT_ERROR_ALLOCATION, nothing is kept half-allocated, and the batch factor,
+ * spllt_hip_solve_batch and the single factorization stay usable.  All work is ordered on
+ * spllt_hip_engine_stream and finished when a call returns.
+ *
+ * spllt_hip_factor_batch (and _dev) makes the batch's Z stale: the readers then return
+ * SPLLT_ERROR_PARAMETER until spllt_hip_selected_inverse_batch runs again.  spllt_factor and
+ * spllt_hip_selected_inverse neither touch the batch's Z nor are touched by this call.
+ *
+ * A member that is not positive definite is skipped (nothing of it is read or written): the inversion
+ * returns SPLLT_ERROR_NOT_POSDEF and the other members are inverted; its rows of the two readers are NaN.
+ *
+ * Errors: null pointer, bad member, ldout too small, no batch yet, stale Z -> SPLLT_ERROR_PARAMETER; a
+ * partitioned handle -> SPLLT_ERROR_UNIMPLEMENTED; no device -> SPLLT_ERROR_HIP.  Messages:
+ * spllt_hip_last_error.  An empty batch is a no-op that returns 0. */
+int     spllt_hip_selected_inverse_batch(void *fkeep);
+/* one member's Z arena -> host, L's layout; a failed member: SPLLT_ERROR_NOT_POSDEF */
+int     spllt_hip_get_inverse_batch(void *fkeep, int member, double *out, int64_t count);
+/* device pointer of member 0's Z arena; member b starts *member_stride doubles further (NULL / 0: no valid Z) */
+double *spllt_hip_device_inverse_batch(void *fkeep, int64_t *member_stride);
+/* out[b*ldout + i] = (A_b^-1)_ii in the user's variable order, ldout >= n, host, one launch */
+int     spllt_hip_inverse_diag_batch(void *fkeep, double *out, int64_t ldout);
+/* out[b*ldout + k] = (A_b^-1) at the k-th entry of (ptr, row), the order of val, ldout >= nnz, host */
+int     spllt_hip_inverse_on_pattern_batch(void *fkeep, double *out, int64_t ldout);
+/* kernel launches of the last batched inversion */
+int     spllt_hip_batch_selinv_launches(void *fkeep);
+/* give the Z arenas and the scratch back; the batch factor and its solve stay */
+int     spllt_hip_release_inverse_batch(void *fkeep);
 /* timings of the last factorization, milliseconds */
 int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, double *h2d_ms,
                            int *launches);
@@ -380,7 +421,10 @@ int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, do
  * "selinv_scratch" (int64), "selinv_flops" (double); the program of the batched factorization (the
  * same for every engine flag): "batch_launches", "batch_units", "batch_tiles", "batch_chains",
  * "batch_relpos", "batch_dinv_size" with the layouts of their unprefixed counterparts (and
- * "batch_potrf", empty, "batch_scratch_size", 0).  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
+ * "batch_potrf", empty, "batch_scratch_size", 0); the selected-inversion program of the batch (panels of
+ * 64 columns, independent of the handle's panel width): "batch_selinv_units", "batch_selinv_tiles",
+ * "batch_selinv_launches", "batch_selinv_rows", "batch_selinv_relpos", "batch_selinv_diag",
+ * "batch_selinv_scratch", "batch_selinv_flops", the layouts of the "selinv_*" names.  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
  * spllt_amd/api.py.  Returns the byte length. */
 int64_t spllt_hip_program_get(void *fkeep, const char *name, void *buf, int64_t capacity_bytes);
 /* per-launch device time (ms) of one profiled factorization; returns #launches */
@@ -404,7 +448,9 @@ const char *spllt_hip_version(void);
  * submission deadlines do), "wedged" reads the mark (1 / 0), "teardown" runs the library's atexit
  * handler now (it must touch nothing once the mark is set); "batch_grid_limit=N": a launch of the batched
  * factorization or solve whose (work items) x (members) exceeds N workgroups is split by member range
- * (N <= 0: back to the hardware limit, (2^32 - 1) / 256 workgroups).  -1: unknown request. */
+ * (N <= 0: back to the hardware limit, (2^32 - 1) / 256 workgroups); "batch_selinv_fused=0" / "=1": the
+ * batched selected inversion runs every step as three launches / fuses the small steps (the default).
+ * -1: unknown request. */
 int spllt_hip_debug(const char *what);
 
 #ifdef __cplusplus

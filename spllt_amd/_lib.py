@@ -64,6 +64,9 @@ HIP_SYMBOLS = [
     "spllt_hip_factor_batch", "spllt_hip_factor_batch_dev", "spllt_hip_batch_status", "spllt_hip_solve_batch",
     "spllt_hip_solve_batch_dev", "spllt_hip_get_factor_batch", "spllt_hip_device_factor_batch",
     "spllt_hip_log_det_batch", "spllt_hip_batch_launches", "spllt_hip_release_batch",
+    "spllt_hip_selected_inverse_batch", "spllt_hip_get_inverse_batch", "spllt_hip_device_inverse_batch",
+    "spllt_hip_inverse_diag_batch", "spllt_hip_inverse_on_pattern_batch", "spllt_hip_batch_selinv_launches",
+    "spllt_hip_release_inverse_batch", "spllt_hip_inverse_on_pattern",
 ]
 
 _lib = None
@@ -226,5 +229,18 @@ def load():
     lib.spllt_hip_batch_launches.restype = C.c_int
     lib.spllt_hip_release_batch.argtypes = [vp]
     lib.spllt_hip_release_batch.restype = C.c_int
+    for fn in (lib.spllt_hip_selected_inverse_batch, lib.spllt_hip_batch_selinv_launches,
+               lib.spllt_hip_release_inverse_batch):
+        fn.argtypes = [vp]
+        fn.restype = C.c_int
+    lib.spllt_hip_get_inverse_batch.argtypes = [vp, C.c_int, dp, C.c_int64]
+    lib.spllt_hip_get_inverse_batch.restype = C.c_int
+    lib.spllt_hip_device_inverse_batch.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.spllt_hip_device_inverse_batch.restype = C.c_void_p
+    for fn in (lib.spllt_hip_inverse_diag_batch, lib.spllt_hip_inverse_on_pattern_batch):
+        fn.argtypes = [vp, dp, C.c_int64]
+        fn.restype = C.c_int
+    lib.spllt_hip_inverse_on_pattern.argtypes = [vp, dp]
+    lib.spllt_hip_inverse_on_pattern.restype = C.c_int
     _lib = lib
     return lib

@@ -310,6 +310,14 @@ class Factorization:
             raise SplltError("spllt_hip_log_det", rc, self.last_error())
         return v.value
 
+    def inverse_on_pattern(self):
+        """(A^-1) at the entries of the analysed CSC-lower pattern, nnz values in the order of val"""
+        out = np.zeros(max(self.nnz, 1), dtype=np.float64)
+        rc = self.lib.spllt_hip_inverse_on_pattern(self.fkeep, _dp(out))
+        if rc < 0:
+            raise SplltError("spllt_hip_inverse_on_pattern", rc, self.last_error())
+        return out[:self.nnz]
+
     def release_inverse(self):
         rc = self.lib.spllt_hip_release_inverse(self.fkeep)
         if rc < 0:
@@ -499,6 +507,57 @@ class Factorization:
         rc = self.lib.spllt_hip_release_batch(self.fkeep)
         if rc < 0:
             raise SplltError("spllt_hip_release_batch", rc, self.last_error())
+
+    # ---- batched selected inversion -------------------------------------------
+    def selected_inverse_batch(self):
+        """spllt_hip_selected_inverse_batch: Z_b on the pattern of L for every member of the last batch.
+        Returns 0, or -20 when a member is not positive definite (the others are inverted)."""
+        rc = self.lib.spllt_hip_selected_inverse_batch(self.fkeep)
+        return self._batch_rc("spllt_hip_selected_inverse_batch", rc)
+
+    def get_inverse_batch(self, member, out=None):
+        """one member's Z arena on the host (the layout of get_inverse); a failed member raises (-20)"""
+        arena = self.sym_info()["arena"]
+        if out is None:
+            out = np.zeros(max(arena, 1), dtype=np.float64)
+        assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
+        rc = self.lib.spllt_hip_get_inverse_batch(self.fkeep, int(member), _dp(out), arena)
+        if rc < 0:
+            raise SplltError("spllt_hip_get_inverse_batch", rc, self.last_error())
+        return out[:arena]
+
+    def device_inverse_batch_ptr(self):
+        """(device pointer of member 0's Z arena, member stride in doubles)"""
+        stride = C.c_int64()
+        p = self.lib.spllt_hip_device_inverse_batch(self.fkeep, C.byref(stride))
+        return p, stride.value
+
+    def _batch_rows(self, fn, where, width):
+        nb = self.lib.spllt_hip_batch_status(self.fkeep, None, None, 0)
+        out = np.zeros((max(nb, 1), max(width, 1)), dtype=np.float64)
+        rc = fn(self.fkeep, _dp(out), out.shape[1])
+        if rc < 0:
+            raise SplltError(where, rc, self.last_error())
+        return out[:nb, :width]
+
+    def inverse_diag_batch(self):
+        """(A_b^-1)_ii in the user's variable order, shape (nbatch, n); NaN rows for failed members"""
+        return self._batch_rows(self.lib.spllt_hip_inverse_diag_batch, "spllt_hip_inverse_diag_batch", self.n)
+
+    def inverse_on_pattern_batch(self):
+        """(A_b^-1) at the entries of the analysed pattern in the order of val, shape (nbatch, nnz); NaN
+        rows for failed members"""
+        return self._batch_rows(self.lib.spllt_hip_inverse_on_pattern_batch, "spllt_hip_inverse_on_pattern_batch",
+                                self.nnz)
+
+    def batch_selinv_launches(self):
+        """kernel launches of the last batched inversion"""
+        return int(self.lib.spllt_hip_batch_selinv_launches(self.fkeep))
+
+    def release_inverse_batch(self):
+        rc = self.lib.spllt_hip_release_inverse_batch(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_inverse_batch", rc, self.last_error())
 
     # ---- multi-GPU subtree partition ------------------------------------------
     def set_partition(self, rank, nranks):

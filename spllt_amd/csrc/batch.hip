@@ -432,6 +432,9 @@ void set_batch_grid_limit(int64_t workgroups) {
   g_grid_limit = workgroups > 0 ? std::min(workgroups, kGridMax) : kGridMax;
 }
 
+int64_t batch_grid_limit() { return g_grid_limit; }
+int64_t batch_grid_limit_max() { return kGridMax; }
+
 int launch_batch_init(hipStream_t st, const BatchView& v, int64_t arena, const double* val, int64_t ldval,
                       const int64_t* cptr, const unsigned short* loc, const int* src) {
   const int64_t nchunk = std::max<int64_t>(1, (arena + kInitChunk - 1) / kInitChunk);

@@ -1,0 +1,517 @@
+// Batched selected inversion on gfx950: Z_b = (P A_b P^T)^-1 on the pattern of L for the nbatch members of
+// a batch (batch.hip), by ONE SelinvProgram of the pattern (schedule.hpp, built with pw = cb = 64: the
+// panels and dinv slots of the batch factorization).  Every launch carries all members: the grid is
+// (work items) x (members), member b works on L + b lstride, dinv + b dstride, Z + b lstride and
+// scratch + b sstride, and every table is read shared.  A member whose not-positive-definite flag is set
+// is skipped by every workgroup: nothing of it is read or written.
+//
+//   k_batch_selinv_symm / _scale / _diag   the three step kernels of selinv.hip with the member dimension:
+//                         the same recurrences, the same fixed summation order
+//   k_batch_selinv_fused  a whole step (SYMM + SCALE + DIAG) of one unit with nR <= 64 and one K slice in
+//                         one workgroup: Z_RR gathered into LDS, the four products on
+//                         v_mfma_f64_16x16x4_f64, no scratch traffic
+//   k_batch_selinv_diag_gather   (A_b^-1)_ii in the user's variable order, NaN for a failed member
+//   k_batch_selinv_pattern       (A_b^-1) at the entries of the caller's CSC-lower pattern, in the order of
+//                                val (the value map of the analysis read backwards), NaN for a failed member
+//
+// No kernel uses atomics and every sum runs in a fixed order: two inversions of one batch give a
+// bit-identical Z for every member.  Nothing is read or written outside the rows and columns a table
+// entry names, so a member never touches its neighbour's arena.
+//
+// MFMA lane map (header of kernels.hip): lane l supplies A[l&15][l>>4] and B[l>>4][l&15] and receives
+// C[(l>>4) + 4 r][l&15] in register r.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "kernels.hpp"
+
+namespace spx {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+constexpr int BI_KC = 32;           // K rows per LDS stage of k_batch_selinv_symm
+constexpr int BI_T = kSelinvTile;   // 64
+constexpr int BI_LD = BI_T + 1;     // LDS row stride of the fused kernel's two operand buffers
+
+// workgroup -> (member, work item), as in batch.hip
+__device__ __forceinline__ void bsi_split(const BatchView& v, int64_t count, int& b, int64_t& t) {
+  const unsigned wg = blockIdx.x;
+  if (v.member_fast) {
+    b = (int)(wg % (unsigned)v.nbatch);
+    t = wg / (unsigned)v.nbatch;
+  } else {
+    b = (int)(wg / (unsigned)count);
+    t = wg % (unsigned)count;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// k_selinv_symm of selinv.hip for member b (dense-path shortcut included)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_batch_selinv_symm(BatchSelinvView s, const UpdTile* __restrict__ tiles, int64_t count,
+                                                           const SelinvUnit* __restrict__ units,
+                                                           const SelinvRow* __restrict__ rows,
+                                                           const int* __restrict__ relpos) {
+  __shared__ double As[BI_T][BI_KC + 1];
+  __shared__ double Bs[BI_KC][BI_T + 1];
+  __shared__ SelinvRow Ri[BI_T];
+  int b;
+  int64_t wi;
+  bsi_split(s.v, count, b, wi);
+  if (s.v.flag[b] != INT_MAX) return;
+  const double* __restrict__ L = s.v.L + (int64_t)b * s.v.lstride;
+  const double* __restrict__ Z = s.Z + (int64_t)b * s.v.lstride;
+  double* __restrict__ scratch = s.scratch + (int64_t)b * s.sstride;
+  const UpdTile t = tiles[wi];
+  const SelinvUnit u = units[t.unit];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int nR = u.nR, pn = u.pn;
+  const int i0 = t.ti * BI_T;
+  const int k0 = t.tj * u.kslice;
+  const int k1 = min(nR, k0 + u.kslice);
+  const SelinvRow* nrows = rows + u.row_off;
+  if (tid < BI_T && i0 + tid < nR) Ri[tid] = nrows[u.rbase + i0 + tid];
+  __syncthreads();
+  const int ak = tid % BI_KC, ai0 = tid / BI_KC;
+  const int bj = tid & 63, bk0 = tid >> 6;
+  const double* Lrj = L + u.off + (int64_t)(u.c0 + pn) * u.ld + u.c0;
+  double ra[8], rb[8];
+  auto upper = [&](int kb) { return i0 + BI_T <= kb; };
+  auto lower = [&](int kb) { return kb + BI_KC <= i0; };
+  auto own_block = [&](int first, int last) {   // R-local rows [first, last]
+    const int a = u.rbase + first, e = u.rbase + last;
+    return e < u.ncol && a / u.nb == e / u.nb;
+  };
+  const bool tile_dense = own_block(i0, min(nR, i0 + BI_T) - 1);
+  const SelinvRow dI0 = Ri[0];
+  auto load = [&](int kb) {
+    const int klast = min(k1, kb + BI_KC) - 1;
+    if (upper(kb) && tile_dense) {
+      const int il = tid & 63;
+      const bool iin = i0 + il < nR;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int kk = kb + (tid >> 6) + 4 * q;
+        ra[q] = (iin && kk < k1) ? Z[dI0.cbase + il + (int64_t)(u.rbase + kk) * dI0.ld] : 0.0;
+      }
+    } else if (lower(kb) && own_block(kb, klast)) {
+      const SelinvRow dK0 = nrows[u.rbase + kb];
+      const bool kin = kb + ak < k1;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int ii = i0 + ai0 + 8 * q;
+        ra[q] = (kin && ii < nR) ? Z[dK0.cbase + ak + (int64_t)(u.rbase + ii) * dK0.ld] : 0.0;
+      }
+    } else if (upper(kb)) {
+      const int il = tid & 63, ii = i0 + il;
+      const bool iin = ii < nR;
+      const SelinvRow d = iin ? Ri[il] : SelinvRow{0, 0, -1};
+      const int ri = u.rbase + ii;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int kk = kb + (tid >> 6) + 4 * q;
+        double v = 0.0;
+        if (iin && kk < k1) {
+          const int rk = u.rbase + kk;
+          const int64_t qpos = d.map < 0 ? (int64_t)rk : (int64_t)relpos[(int64_t)d.map + rk - ri];
+          v = Z[d.cbase + qpos * d.ld];
+        }
+        ra[q] = v;
+      }
+    } else {
+      const int kk = kb + ak;
+      const bool kin = kk < k1;
+      const int rk = u.rbase + kk;
+      SelinvRow dk{0, 0, -1};
+      if (kin) dk = nrows[rk];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int ii = i0 + ai0 + 8 * q;
+        double v = 0.0;
+        if (kin && ii < nR) {
+          const int ri = u.rbase + ii;
+          // lower half (r_i >= r_k) through row k's descriptor, upper half transposed through row i's
+          const SelinvRow d = ri >= rk ? dk : Ri[ai0 + 8 * q];
+          const int a = ri >= rk ? ri : rk, e = ri >= rk ? rk : ri;
+          const int64_t qpos = d.map < 0 ? (int64_t)a : (int64_t)relpos[(int64_t)d.map + a - e];
+          v = Z[d.cbase + qpos * d.ld];
+        }
+        ra[q] = v;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int kr = kb + bk0 + 4 * q;
+      rb[q] = (kr < k1 && bj < pn) ? Lrj[(int64_t)kr * u.ld + bj] : 0.0;
+    }
+  };
+  d4 acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
+  const int ncb = (pn + 15) >> 4;
+  load(k0);
+  for (int kb = k0; kb < k1; kb += BI_KC) {
+    __syncthreads();
+    if (upper(kb)) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) As[tid & 63][(tid >> 6) + 4 * q] = ra[q];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) As[ai0 + 8 * q][ak] = ra[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) Bs[bk0 + 4 * q][bj] = rb[q];
+    __syncthreads();
+    if (kb + BI_KC < k1) load(kb + BI_KC);   // in flight during the products
+#pragma unroll
+    for (int st = 0; st < BI_KC / 4; ++st) {
+      const double a = As[16 * wv + (lane & 15)][4 * st + (lane >> 4)];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < ncb) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[4 * st + (lane >> 4)][16 * c + (lane & 15)], acc[c], 0, 0, 0);
+    }
+  }
+  double* Y = scratch + u.y_off + (int64_t)t.tj * nR * pn;
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = i0 + 16 * wv + (lane >> 4) + 4 * r, col = 16 * c + (lane & 15);
+      if (row < nR && col < pn) Y[(int64_t)row * pn + col] = acc[c][r];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_selinv_scale of selinv.hip for member b
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_batch_selinv_scale(BatchSelinvView s, const UpdTile* __restrict__ tiles, int64_t count,
+                                                            const SelinvUnit* __restrict__ units) {
+  __shared__ double Ys[BI_T][BI_T + 1];
+  __shared__ double Ms[BI_T][BI_T + 1];   // inv(L_JJ), then the tile's rows of L_RJ
+  int b;
+  int64_t wi;
+  bsi_split(s.v, count, b, wi);
+  if (s.v.flag[b] != INT_MAX) return;
+  const double* __restrict__ L = s.v.L + (int64_t)b * s.v.lstride;
+  const double* __restrict__ dinv = s.v.dinv + (int64_t)b * s.v.dstride;
+  double* __restrict__ Z = s.Z + (int64_t)b * s.v.lstride;
+  double* __restrict__ scratch = s.scratch + (int64_t)b * s.sstride;
+  const UpdTile t = tiles[wi];
+  const SelinvUnit u = units[t.unit];
+  const int tid = threadIdx.x, j = tid & 63, i0w = tid >> 6;
+  const int nR = u.nR, pn = u.pn;
+  const int i0 = t.ti * BI_T;
+  const int nr = min(BI_T, nR - i0);
+  for (int q = 0; q < 16; ++q) {
+    const int i = i0w + 4 * q;
+    double y = 0.0, d = 0.0;
+    if (j < pn) {
+      if (i < nr)
+        for (int sl = 0; sl < u.nsplit; ++sl) y += scratch[u.y_off + ((int64_t)sl * nR + i0 + i) * pn + j];
+      if (i < pn && j <= i) d = dinv[u.dinv_off + (int64_t)i * u.dinv_ld + j];
+    }
+    Ys[i][j] = y;
+    Ms[i][j] = d;
+  }
+  __syncthreads();
+  double z[16];
+  for (int q = 0; q < 16; ++q) {
+    const int i = i0w + 4 * q;
+    double sum = 0.0;
+    for (int c = j; c < pn; ++c) sum += Ys[i][c] * Ms[c][j];
+    z[q] = -sum;
+  }
+  __syncthreads();
+  double* Zrj = Z + u.off + (int64_t)(u.c0 + pn + i0) * u.ld + u.c0;
+  const double* Lrj = L + u.off + (int64_t)(u.c0 + pn + i0) * u.ld + u.c0;
+  for (int q = 0; q < 16; ++q) {
+    const int i = i0w + 4 * q;
+    const bool in = i < nr && j < pn;
+    if (in) Zrj[(int64_t)i * u.ld + j] = z[q];
+    Ys[i][j] = in ? z[q] : 0.0;
+    Ms[i][j] = in ? Lrj[(int64_t)i * u.ld + j] : 0.0;
+  }
+  __syncthreads();
+  double* P = scratch + u.p_off + (int64_t)t.ti * pn * pn;
+  for (int q = 0; q < 16; ++q) {
+    const int a = i0w + 4 * q;
+    if (a >= pn || j >= pn) continue;
+    double sum = 0.0;
+    for (int i = 0; i < nr; ++i) sum += Ms[i][a] * Ys[i][j];
+    P[a * pn + j] = sum;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// k_selinv_diag of selinv.hip for member b
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_batch_selinv_diag(BatchSelinvView s, const SelinvUnit* __restrict__ units, int64_t count) {
+  __shared__ double Ds[BI_T][BI_T + 1];
+  __shared__ double Ts[BI_T][BI_T + 1];
+  int b;
+  int64_t wi;
+  bsi_split(s.v, count, b, wi);
+  if (s.v.flag[b] != INT_MAX) return;
+  const double* __restrict__ dinv = s.v.dinv + (int64_t)b * s.v.dstride;
+  double* __restrict__ Z = s.Z + (int64_t)b * s.v.lstride;
+  const double* __restrict__ scratch = s.scratch + (int64_t)b * s.sstride;
+  const SelinvUnit u = units[wi];
+  const int tid = threadIdx.x, e = tid & 63, a0 = tid >> 6;   // (1024 threads: 16 row groups)
+  const int pn = u.pn;
+  for (int q = 0; q < 4; ++q) {
+    const int a = a0 + 16 * q;
+    double d = 0.0, tt = 0.0;
+    if (a < pn && e < pn) {
+      if (e <= a) d = dinv[u.dinv_off + (int64_t)a * u.dinv_ld + e];
+      tt = d;
+      const double* p = scratch + u.p_off + (int64_t)a * pn + e;
+#pragma unroll 8
+      for (int ti = 0; ti < u.ntile; ++ti) tt -= p[(int64_t)ti * pn * pn];
+    }
+    Ds[a][e] = d;
+    Ts[a][e] = tt;
+  }
+  __syncthreads();
+  double* Zjj = Z + u.off + (int64_t)u.c0 * u.ld + u.c0;
+  for (int q = 0; q < 4; ++q) {
+    const int a = a0 + 16 * q;
+    if (a >= pn || e > a) continue;
+    double sum = 0.0;
+    for (int c = a; c < pn; ++c) sum += Ds[c][a] * Ts[c][e];
+    Zjj[(int64_t)a * u.ld + e] = sum;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// One whole step of one unit (nR <= 64, one K slice) per workgroup and member.  Two 64 x 64 LDS buffers
+// (A, B) carry the operands of four products in turn; wavefront w owns rows 16 w .. 16 w + 15 of every
+// product and all (<= 4) 16-column blocks.  What the next product needs from memory (inv(L_JJ), L_RJ) is
+// loaded into registers before the current one starts.
+//   1  A = Z_RR (gathered, symmetric), B = L_RJ          Y    = A B
+//   2  A = Y,                          B = inv(L_JJ)     Z_RJ = -(A B)            -> Z arena
+//   3  A = Z_RJ,                       B = L_RJ          P    = B^T A
+//   4  A = inv(L_JJ) - P,              B = inv(L_JJ)     Z_JJ = B^T A (lower)     -> Z arena
+// Both buffers are written in full (zero outside the unit's rows and columns) before every product: the K
+// loops run to a multiple of 4 and must not meet stale LDS.  nR = 0: products 1 - 3 are skipped, P = 0.
+// ---------------------------------------------------------------------------
+template <bool TA>
+__device__ __forceinline__ void bsi_mm(const double (*A)[BI_LD], const double (*B)[BI_LD], int K, int ncb, int wv, int g,
+                                       int col, d4 (&acc)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
+  const int ks = (K + 3) >> 2;
+  for (int st = 0; st < ks; ++st) {
+    const double a = TA ? A[4 * st + g][16 * wv + col] : A[16 * wv + col][4 * st + g];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < ncb) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, B[4 * st + g][16 * c + col], acc[c], 0, 0, 0);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_batch_selinv_fused(BatchSelinvView s, const SelinvUnit* __restrict__ units, int64_t count,
+                                                            const SelinvRow* __restrict__ rows,
+                                                            const int* __restrict__ relpos) {
+  __shared__ double Ab[BI_T][BI_LD];
+  __shared__ double Bb[BI_T][BI_LD];
+  __shared__ SelinvRow Ri[BI_T];
+  int b;
+  int64_t wi;
+  bsi_split(s.v, count, b, wi);
+  if (s.v.flag[b] != INT_MAX) return;
+  const SelinvUnit u = units[wi];
+  const double* __restrict__ L = s.v.L + (int64_t)b * s.v.lstride;
+  const double* __restrict__ D = s.v.dinv + (int64_t)b * s.v.dstride + u.dinv_off;
+  double* __restrict__ Z = s.Z + (int64_t)b * s.v.lstride;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int g = lane >> 4, col = lane & 15;
+  const int tj = tid & 63, ti0 = tid >> 6;        // tile loads: element (ti0 + 4 q, tj)
+  const int nR = u.nR, pn = u.pn;
+  const int ncb = (pn + 15) >> 4;
+  // inv(L_JJ): in the tile-load layout (for B) and in the accumulator layout (for inv(L_JJ) - P)
+  double dreg[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int i = ti0 + 4 * q;
+    dreg[q] = (i < pn && tj <= i) ? D[(int64_t)i * u.dinv_ld + tj] : 0.0;
+  }
+  d4 acc[4];
+  if (nR > 0) {   // (the same for every thread of the workgroup)
+    const SelinvRow* nrows = rows + u.row_off + u.rbase;
+    if (tid < nR) Ri[tid] = nrows[tid];
+    __syncthreads();
+    const double* Lrj = L + u.off + (int64_t)(u.c0 + pn) * u.ld + u.c0;
+    double lreg[16];
+    // 1: Z_RR, its lower half through the descriptor of the column's row (the K row fastest across the
+    // threads: coalesced), mirrored into the upper half; L_RJ
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int i = ti0 + 4 * q, k = tj;
+      double v = 0.0;
+      if (i < nR && k <= i) {
+        const SelinvRow d = Ri[k];
+        const int64_t qpos = d.map < 0 ? (int64_t)(u.rbase + i) : (int64_t)relpos[(int64_t)d.map + i - k];
+        v = Z[d.cbase + qpos * d.ld];
+      }
+      if (k <= i || i >= nR || k >= nR) Ab[i][k] = v;
+      if (k < i && i < nR) Ab[k][i] = v;
+      lreg[q] = (i < nR && tj < pn) ? Lrj[(int64_t)i * u.ld + tj] : 0.0;
+      Bb[i][tj] = lreg[q];
+    }
+    __syncthreads();
+    bsi_mm<false>(Ab, Bb, nR, ncb, wv, g, col, acc);
+    __syncthreads();
+    // 2: Y (zero beyond the unit's rows and columns: the operands were) and inv(L_JJ)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Ab[16 * wv + g + 4 * r][16 * c + col] = c < ncb ? acc[c][r] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) Bb[ti0 + 4 * q][tj] = dreg[q];
+    __syncthreads();
+    bsi_mm<false>(Ab, Bb, pn, ncb, wv, g, col, acc);
+    double* Zrj = Z + u.off + (int64_t)(u.c0 + pn) * u.ld + u.c0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * wv + g + 4 * r, cc = 16 * c + col;
+        acc[c][r] = -acc[c][r];
+        if (c < ncb && row < nR && cc < pn) Zrj[(int64_t)row * u.ld + cc] = acc[c][r];
+      }
+    __syncthreads();
+    // 3: Z_RJ and L_RJ again
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Ab[16 * wv + g + 4 * r][16 * c + col] = c < ncb ? acc[c][r] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) Bb[ti0 + 4 * q][tj] = lreg[q];
+    __syncthreads();
+    bsi_mm<true>(Bb, Ab, nR, ncb, wv, g, col, acc);
+    __syncthreads();
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
+  }
+  // 4: T = inv(L_JJ) - P in the accumulator layout, inv(L_JJ) in the tile layout
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * wv + g + 4 * r, cc = 16 * c + col;
+      const double d = (c < ncb && row < pn && cc <= row) ? D[(int64_t)row * u.dinv_ld + cc] : 0.0;
+      Ab[row][cc] = c < ncb ? d - acc[c][r] : 0.0;
+    }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) Bb[ti0 + 4 * q][tj] = dreg[q];
+  __syncthreads();
+  bsi_mm<true>(Bb, Ab, pn, ncb, wv, g, col, acc);
+  double* Zjj = Z + u.off + (int64_t)u.c0 * u.ld + u.c0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * wv + g + 4 * r, cc = 16 * c + col;
+      if (c < ncb && row < pn && cc <= row) Zjj[(int64_t)row * u.ld + cc] = acc[c][r];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// readers.  flag == nullptr: one arena that is known to be valid (the single-handle inverse)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_batch_selinv_diag_gather(BatchSelinvView s, const int64_t* __restrict__ diag_pos,
+                                                                  const int* __restrict__ order, int n, int64_t nblk,
+                                                                  double* __restrict__ out, int64_t ldout) {
+  int b;
+  int64_t blk;
+  bsi_split(s.v, nblk, b, blk);
+  const int64_t i = blk * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool ok = !s.v.flag || s.v.flag[b] == INT_MAX;
+  out[(int64_t)b * ldout + i] = ok ? s.Z[(int64_t)b * s.v.lstride + diag_pos[order[i]]] : NAN;
+}
+
+__global__ __launch_bounds__(256) void k_batch_selinv_pattern(BatchSelinvView s, const int64_t* __restrict__ map_dst,
+                                                              const int64_t* __restrict__ map_src, int64_t nmap, int64_t nblk,
+                                                              double* __restrict__ out, int64_t ldout) {
+  int b;
+  int64_t blk;
+  bsi_split(s.v, nblk, b, blk);
+  const int64_t e = blk * 256 + threadIdx.x;
+  if (e >= nmap) return;
+  const bool ok = !s.v.flag || s.v.flag[b] == INT_MAX;
+  out[(int64_t)b * ldout + map_src[e]] = ok ? s.Z[(int64_t)b * s.v.lstride + map_dst[e]] : NAN;
+}
+
+// ---------------------------------------------------------------------------
+// launch wrappers: one kernel launch per call as long as (work items) x (members) fits a grid (the limit
+// of batch.hip, test hook included); beyond that the members are split into ranges.  Every wrapper returns
+// the number of kernel launches it made (-1, nothing launched: ONE member's work items overflow a grid).
+// ---------------------------------------------------------------------------
+namespace {
+template <class Fn>
+int bsi_member_ranges(const BatchSelinvView& s, int64_t per_member, Fn&& fn) {
+  if (per_member <= 0 || s.v.nbatch <= 0) return 0;
+  const int64_t limit = batch_grid_limit();
+  if (per_member > batch_grid_limit_max()) return -1;
+  const int step = (int)std::max<int64_t>(1, std::min<int64_t>(s.v.nbatch, limit / per_member));
+  int launches = 0;
+  for (int b0 = 0; b0 < s.v.nbatch; b0 += step) {
+    BatchSelinvView r = s;
+    r.v.nbatch = std::min(step, s.v.nbatch - b0);
+    r.v.L += (int64_t)b0 * s.v.lstride;
+    r.v.dinv += (int64_t)b0 * s.v.dstride;
+    if (r.v.flag) r.v.flag += b0;
+    r.Z += (int64_t)b0 * s.v.lstride;
+    if (r.scratch) r.scratch += (int64_t)b0 * s.sstride;
+    fn(r, b0);
+    ++launches;
+  }
+  return launches;
+}
+}  // namespace
+
+int launch_batch_selinv(hipStream_t st, const BatchSelinvView& s, const SelinvLaunch& l, const SelinvUnit* units,
+                        const UpdTile* tiles, const SelinvRow* rows, const int* relpos) {
+  return bsi_member_ranges(s, l.count, [&](const BatchSelinvView& r, int) {
+    const dim3 grid((unsigned)(l.count * r.v.nbatch));
+    if (l.kind == SI_SYMM)
+      hipLaunchKernelGGL(k_batch_selinv_symm, grid, dim3(256), 0, st, r, tiles + l.first, l.count, units, rows, relpos);
+    else if (l.kind == SI_SCALE)
+      hipLaunchKernelGGL(k_batch_selinv_scale, grid, dim3(256), 0, st, r, tiles + l.first, l.count, units);
+    else
+      hipLaunchKernelGGL(k_batch_selinv_diag, grid, dim3(1024), 0, st, r, units + l.first, l.count);
+  });
+}
+
+int launch_batch_selinv_fused(hipStream_t st, const BatchSelinvView& s, const SelinvUnit* units, int64_t count,
+                              const SelinvRow* rows, const int* relpos) {
+  return bsi_member_ranges(s, count, [&](const BatchSelinvView& r, int) {
+    hipLaunchKernelGGL(k_batch_selinv_fused, dim3((unsigned)(count * r.v.nbatch)), dim3(256), 0, st, r, units, count, rows,
+                       relpos);
+  });
+}
+
+int launch_batch_selinv_diag_gather(hipStream_t st, const BatchSelinvView& s, const int64_t* diag_pos, const int* order,
+                                    int n, double* out, int64_t ldout) {
+  const int64_t nblk = ((int64_t)n + 255) / 256;
+  return bsi_member_ranges(s, nblk, [&](const BatchSelinvView& r, int b0) {
+    hipLaunchKernelGGL(k_batch_selinv_diag_gather, dim3((unsigned)(nblk * r.v.nbatch)), dim3(256), 0, st, r, diag_pos, order,
+                       n, nblk, out + (int64_t)b0 * ldout, ldout);
+  });
+}
+
+int launch_batch_selinv_pattern(hipStream_t st, const BatchSelinvView& s, const int64_t* map_dst, const int64_t* map_src,
+                                int64_t nmap, double* out, int64_t ldout) {
+  const int64_t nblk = (nmap + 255) / 256;
+  return bsi_member_ranges(s, nblk, [&](const BatchSelinvView& r, int b0) {
+    hipLaunchKernelGGL(k_batch_selinv_pattern, dim3((unsigned)(nblk * r.v.nbatch)), dim3(256), 0, st, r, map_dst, map_src,
+                       nmap, nblk, out + (int64_t)b0 * ldout, ldout);
+  });
+}
+
+}  // namespace spx

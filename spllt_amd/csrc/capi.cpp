@@ -49,6 +49,10 @@ struct Fkeep {
   std::shared_ptr<const Symbolic> bt_S;
   int bt_rc = 0;
   Program bt_prog;
+  // ... and the batch's selected-inversion program (panel width 64 whatever the handle's)
+  std::shared_ptr<const Symbolic> bsi_S;
+  int bsi_rc = 0;
+  SelinvProgram bsi_prog;
 };
 
 std::mutex g_mu;
@@ -597,7 +601,8 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 
 // test hooks of the process-wide "runtime is wedged" state (engine.cpp): "wedge" sets it, "wedged"
 // reads it, "teardown" runs the atexit handler of the pools now; "batch_grid_limit=N" lowers the grid size
-// from which on a batched launch is split by member range (N <= 0: the hardware limit again)
+// from which on a batched launch is split by member range (N <= 0: the hardware limit again);
+// "batch_selinv_fused=0|1": 0 forces the three-launch form of every step of the batched selected inversion
 int spllt_hip_debug(const char* what) {
   if (!what) return -1;
   const std::string w(what);
@@ -606,6 +611,10 @@ int spllt_hip_debug(const char* what) {
   if (w == "teardown") { run_pools_teardown_for_test(); return 0; }
   if (w.rfind("batch_grid_limit=", 0) == 0) {   // workgroups from which on a batched launch splits its members
     set_batch_grid_limit(std::atoll(w.c_str() + 17));
+    return 0;
+  }
+  if (w == "batch_selinv_fused=0" || w == "batch_selinv_fused=1") {
+    set_batch_selinv_fused(w.back() == '1');
     return 0;
   }
   return -1;
@@ -974,6 +983,98 @@ int spllt_hip_release_batch(void* fkeep) {
   return rc ? batch_fail(f, rc) : 0;
 }
 
+// ---- batched selected inversion ------------------------------------------------
+// the handle's engine with a valid batched inverse on it, or an error flag
+static int batch_inverse_reader(Fkeep* f, const char* what) {
+  int rc = batch_reader(f, what);
+  if (rc) return rc;
+  if (!f->eng->batch_inverse_valid())
+    return batch_param_error(f, what, "no selected inverse of the current batch (call spllt_hip_selected_inverse_batch "
+                                      "after every spllt_hip_factor_batch)");
+  return 0;
+}
+
+static int batch_member_failed(Fkeep* f, const char* what, int member) {
+  f->last_error = std::string(what) + ": member " + std::to_string(member) + " is not positive definite: it has no inverse "
+                                                                              "(spllt_hip_batch_status)";
+  return SPLLT_ERROR_NOT_POSDEF;
+}
+
+int spllt_hip_selected_inverse_batch(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_selected_inverse_batch";
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  int rc = batch_reader(f, what);
+  if (rc) return rc;
+  rc = f->eng->selected_inverse_batch();
+  if (rc == SPLLT_ERROR_NOT_POSDEF) {
+    f->last_error = std::string(what) + ": the members that are not positive definite were skipped, the others are "
+                                        "inverted (spllt_hip_batch_status)";
+    return rc;
+  }
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+int spllt_hip_get_inverse_batch(void* fkeep, int member, double* out, int64_t count) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_get_inverse_batch";
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!out) return batch_param_error(f, what, "the output array is null");
+  if (count < 0) return batch_param_error(f, what, "count < 0");
+  int rc = batch_inverse_reader(f, what);
+  if (rc) return rc;
+  if (member < 0 || member >= f->eng->batch_count()) return batch_param_error(f, what, "member is not in [0, nbatch)");
+  if (f->eng->batch_flags()[(size_t)member] != INT_MAX) return batch_member_failed(f, what, member);
+  rc = f->eng->download_inverse_batch(member, out, count);
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+double* spllt_hip_device_inverse_batch(void* fkeep, int64_t* member_stride) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (member_stride) *member_stride = 0;
+  if (!f || !f->eng || f->dead) return nullptr;
+  return f->eng->device_inverse_batch(member_stride);
+}
+
+int spllt_hip_inverse_diag_batch(void* fkeep, double* out, int64_t ldout) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_inverse_diag_batch";
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!out) return batch_param_error(f, what, "the output array is null");
+  if (ldout < f->S->n) return batch_param_error(f, what, "ldout < n");
+  int rc = batch_inverse_reader(f, what);
+  if (rc) return rc;
+  rc = f->eng->inverse_diag_batch(out, ldout);
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+int spllt_hip_inverse_on_pattern_batch(void* fkeep, double* out, int64_t ldout) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_inverse_on_pattern_batch";
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!out) return batch_param_error(f, what, "the output array is null");
+  if (ldout < f->S->nnzA) return batch_param_error(f, what, "ldout < nnz");
+  int rc = batch_inverse_reader(f, what);
+  if (rc) return rc;
+  rc = f->eng->inverse_on_pattern_batch(out, ldout);
+  return rc ? batch_fail(f, rc) : 0;
+}
+
+int spllt_hip_batch_selinv_launches(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  return (f->eng && !f->dead) ? f->eng->batch_selinv_launches() : 0;
+}
+
+int spllt_hip_release_inverse_batch(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  if (!f->eng || f->dead) return 0;
+  if (f->eng->pending()) (void)do_wait(f);
+  int rc = f->eng->release_inverse_batch();
+  return rc ? batch_fail(f, rc) : 0;
+}
+
 // ---- selected inversion ---------------------------------------------------
 // the handle's engine with its factor finished, or an error flag (with the message in last_error)
 static int selinv_engine(Fkeep* f, const char* what) {
@@ -1045,6 +1146,15 @@ int spllt_hip_inverse_diag(void* fkeep, double* out, int n) {
   return rc ? selinv_fail(f, rc) : 0;
 }
 
+int spllt_hip_inverse_on_pattern(void* fkeep, double* out) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!out) return SPLLT_ERROR_PARAMETER;
+  int rc = selinv_need_z(f, "spllt_hip_inverse_on_pattern");
+  if (rc) return rc;
+  rc = f->eng->inverse_on_pattern(out);
+  return rc ? selinv_fail(f, rc) : 0;
+}
+
 int spllt_hip_log_det(void* fkeep, double* out) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!out) return SPLLT_ERROR_PARAMETER;
@@ -1091,6 +1201,33 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
     if (buf && bytes) std::memcpy(buf, p, std::min<size_t>(bytes, (size_t)cap));
     return (int64_t)bytes;
   };
+  auto selinv_get = [&](const SelinvProgram& sp, const std::string& q) -> int64_t {   // q: the unprefixed name
+    if (q == "selinv_units") return raw(sp.units.data(), sp.units.size() * sizeof(SelinvUnit));
+    if (q == "selinv_tiles") return raw(sp.tiles.data(), sp.tiles.size() * sizeof(UpdTile));
+    if (q == "selinv_rows") return raw(sp.rows.data(), sp.rows.size() * sizeof(SelinvRow));
+    if (q == "selinv_relpos") return raw(sp.relpos.data(), sp.relpos.size() * sizeof(int));
+    if (q == "selinv_diag") return raw(sp.diag_pos.data(), sp.diag_pos.size() * sizeof(int64_t));
+    if (q == "selinv_scratch") return raw(&sp.scratch_size, sizeof(int64_t));
+    if (q == "selinv_flops") return raw(&sp.flops, sizeof(double));
+    if (q == "selinv_launches") {   // int64 x 5 per launch: kind, level, first, count, flops
+      std::vector<int64_t> v;
+      for (const SelinvLaunch& l : sp.launches) {
+        v.push_back(l.kind); v.push_back(l.level); v.push_back(l.first); v.push_back(l.count);
+        v.push_back((int64_t)l.flops);
+      }
+      return raw(v.data(), v.size() * sizeof(int64_t));
+    }
+    return -1;
+  };
+  if (k.rfind("batch_selinv_", 0) == 0) {
+    // the selected-inversion program of the batch: panels of 64 columns, from the symbolic structure alone
+    if (f->bsi_S != f->S) {
+      f->bsi_rc = build_selinv_program(*f->S, 64, 64, f->bsi_prog);
+      f->bsi_S = f->S;
+    }
+    if (f->bsi_rc) return -1;
+    return selinv_get(f->bsi_prog, k.substr(6));
+  }
   if (k.rfind("batch_", 0) == 0) {
     // the program of the batched factorization: fixed options, independent of the handle's engine flags
     if (f->bt_S != f->S) {
@@ -1155,23 +1292,7 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
       f->si_cb = P->cb;
     }
     if (f->si_rc) return -1;
-    const SelinvProgram& sp = f->si_prog;
-    if (k == "selinv_units") return raw(sp.units.data(), sp.units.size() * sizeof(SelinvUnit));
-    if (k == "selinv_tiles") return raw(sp.tiles.data(), sp.tiles.size() * sizeof(UpdTile));
-    if (k == "selinv_rows") return raw(sp.rows.data(), sp.rows.size() * sizeof(SelinvRow));
-    if (k == "selinv_relpos") return raw(sp.relpos.data(), sp.relpos.size() * sizeof(int));
-    if (k == "selinv_diag") return raw(sp.diag_pos.data(), sp.diag_pos.size() * sizeof(int64_t));
-    if (k == "selinv_scratch") return raw(&sp.scratch_size, sizeof(int64_t));
-    if (k == "selinv_flops") return raw(&sp.flops, sizeof(double));
-    if (k == "selinv_launches") {   // int64 x 5 per launch: kind, level, first, count, flops
-      std::vector<int64_t> v;
-      for (const SelinvLaunch& l : sp.launches) {
-        v.push_back(l.kind); v.push_back(l.level); v.push_back(l.first); v.push_back(l.count);
-        v.push_back((int64_t)l.flops);
-      }
-      return raw(v.data(), v.size() * sizeof(int64_t));
-    }
-    return -1;
+    return selinv_get(f->si_prog, k);
   }
   if (k.rfind("solve_", 0) == 0) {
     // the substitution program (partition-aware like the factor program)

@@ -1547,9 +1547,37 @@ int Engine::release_inverse() {
     if (int rc = sync_stream(stream_, "selinv release")) return rc;
     release_buffer(d_Z_);
     release_buffer(d_siscratch_);
-    d_Z_ = d_siscratch_ = nullptr;
+    if (d_sipat_) release_buffer(d_sipat_);
+    d_Z_ = d_siscratch_ = d_sipat_ = nullptr;
   }
   return 0;
+}
+
+int Engine::inverse_on_pattern(double* out) {
+  if (status_) return status_;
+  if (!z_valid_ || !out || opt_.nranks > 1) return -10;
+  const int64_t nnz = S_->nnzA;
+  if (nnz == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (!d_sipat_) {
+    hipError_t e = dalloc((void**)&d_sipat_, sizeof(double) * (size_t)nnz);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      d_sipat_ = nullptr;
+      si_err_ = std::string("inverse on pattern: not enough device memory for the gathered entries (") + hipGetErrorString(e) + ")";
+      return -1;
+    }
+  }
+  BatchSelinvView v{};   // one member, known to be valid: no flag
+  v.v.nbatch = 1;
+  v.Z = d_Z_;
+  if (launch_batch_selinv_pattern(stream_, v, d_map_dst_, d_map_src_, nmap_, d_sipat_, nnz) < 0) {
+    si_err_ = "inverse on pattern: the pattern has more entries than a grid holds work items";
+    return -99;
+  }
+  HIPCHK(hipGetLastError(), "inverse on pattern launch");
+  if (int rc = sync_stream(stream_, "inverse on pattern sync")) return rc;
+  return staged_d2h(out, d_sipat_, sizeof(double) * (size_t)nnz);
 }
 
 // Substitution on device vectors in pivot order (y[q * n + p], q < nrhs), in place.
@@ -1941,6 +1969,7 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   if (rc) return rc;
   if ((rc = reserve_batch(nbatch))) return rc;
   bt_.nbatch = 0;                    // (no batch until this one is finished)
+  bt_.z_valid = false;               // (the members' inverses belong to the factors this call replaces)
   bt_.hflag.clear();
   const double* vd = val;
   int64_t ld = ldval;
@@ -2077,17 +2106,217 @@ int Engine::log_det_batch(double* out) {
 // the batch's storage back to the pool (the shared tables stay: they are small and per pattern)
 int Engine::release_batch() {
   if (status_) return status_;
-  if (!bt_.L && !bt_.Y && !bt_.stage) { bt_.nbatch = 0; return 0; }
+  bt_.z_valid = false;
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
-  for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out, (void*)bt_.Y, (void*)bt_.stage})
+  for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out, (void*)bt_.Y, (void*)bt_.stage,
+                  (void*)bt_.Z, (void*)bt_.siscratch})
     if (p) release_buffer(p);
-  bt_.L = bt_.dinv = bt_.out = bt_.Y = bt_.stage = nullptr;
+  bt_.L = bt_.dinv = bt_.out = bt_.Y = bt_.stage = bt_.Z = bt_.siscratch = nullptr;
   bt_.flag = nullptr;
+  bt_.z_capacity = 0;
+  bt_.si_launches = 0;
   bt_.capacity = bt_.nbatch = 0;
   bt_.y_elems = bt_.stage_elems = 0;
   bt_.hflag.clear();
   bt_.launches = 0;
+  return 0;
+}
+
+// ---- batched selected inversion ---------------------------------------------------------------------
+namespace {
+std::atomic<bool> g_batch_selinv_fused{true};
+}
+void set_batch_selinv_fused(bool on) { g_batch_selinv_fused.store(on); }
+bool batch_selinv_fused() { return g_batch_selinv_fused.load(); }
+
+BatchSelinvView Engine::batch_selinv_view() const {
+  BatchSelinvView s;
+  s.v = batch_view();
+  s.Z = bt_.Z;
+  s.scratch = bt_.siscratch;
+  s.sstride = bt_.sstride;
+  return s;
+}
+
+// the selected-inversion program of the batch (pw = cb = 64: the panels and dinv slots k_batch_chain
+// leaves) and its tables: built and uploaded once per engine, shared by all members
+int Engine::prepare_batch_selinv() {
+  if (bt_.si_ready) return 0;
+  if (build_selinv_program(*S_, 64, 64, bt_.siprog)) {
+    bt_err_ = "batched selected inversion: the row structure of a node is not contained in its ancestors'";
+    return -10;
+  }
+  // a step = [SYMM] [SCALE] DIAG; the fused kernel takes it when every unit has at most 64 rows below its
+  // panel and at most one K slice (decided here, from the host copy of the units; the program is unchanged)
+  const SelinvProgram& P = bt_.siprog;
+  bt_.si_fusable.assign(P.launches.size(), 0);
+  for (size_t i = 0; i < P.launches.size(); ++i) {
+    const SelinvLaunch& l = P.launches[i];
+    if (l.kind != SI_DIAG) continue;
+    bool ok = l.count > 0;
+    for (int64_t q = l.first; q < l.first + l.count && ok; ++q)
+      ok = P.units[(size_t)q].nR <= kSelinvTile && P.units[(size_t)q].nsplit <= 1;
+    bt_.si_fusable[i] = ok;
+  }
+  TableStager tab;
+  tab.add(&bt_.siunits, P.units);
+  tab.add(&bt_.sitiles, P.tiles);
+  tab.add(&bt_.sirows, P.rows);
+  tab.add(&bt_.sirelpos, P.relpos);
+  hipError_t e = tab.commit(&bt_.d_sitab, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (bt_.d_sitab) { release_buffer(bt_.d_sitab); bt_.d_sitab = nullptr; }
+    bt_err_ = std::string("batched selected inversion: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
+    return batch_alloc_code(e);
+  }
+  bt_.sstride = std::max<int64_t>(32, (P.scratch_size + 31) / 32 * 32);
+  bt_.si_ready = true;
+  return 0;
+}
+
+// Z arenas and step scratch for nbatch members; all or nothing (a failure leaves the batch factor usable)
+int Engine::reserve_batch_inverse(int nbatch) {
+  if (nbatch <= bt_.z_capacity && bt_.Z && bt_.siscratch) return 0;
+  auto drop = [this]() {
+    if (bt_.Z) release_buffer(bt_.Z);
+    if (bt_.siscratch) release_buffer(bt_.siscratch);
+    bt_.Z = bt_.siscratch = nullptr;
+    bt_.z_capacity = 0;
+    bt_.z_valid = false;
+  };
+  drop();
+  const size_t zb = sizeof(double) * (size_t)bt_.lstride * (size_t)nbatch;
+  const size_t sb = sizeof(double) * (size_t)bt_.sstride * (size_t)nbatch;
+  hipError_t e = dalloc((void**)&bt_.Z, zb);
+  if (e == hipSuccess) e = dalloc((void**)&bt_.siscratch, sb);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    drop();
+    bt_err_ = "batched selected inversion: not enough device memory for the inverse arenas of " + std::to_string(nbatch) +
+              " members (" + std::to_string((zb + sb) >> 20) + " MiB): " + hipGetErrorString(e);
+    return -1;
+  }
+  bt_.z_capacity = nbatch;
+  return 0;
+}
+
+int Engine::selected_inverse_batch() {
+  if (status_) return status_;
+  bt_err_.clear();
+  if (opt_.nranks > 1) return -98;
+  if (pending_ || bt_.nbatch <= 0) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_batch_selinv();
+  if (rc) return rc;
+  if ((rc = reserve_batch_inverse(bt_.nbatch))) return rc;
+  bt_.z_valid = false;
+  const BatchSelinvView s = batch_selinv_view();
+  const SelinvProgram& P = bt_.siprog;
+  const bool fused = batch_selinv_fused();
+  bool fits = true;
+  int nl = 0;
+  auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
+  for (size_t i = 0; i < P.launches.size() && fits;) {
+    size_t j = i;
+    while (P.launches[j].kind != SI_DIAG) ++j;     // (every step ends with its DIAG launch)
+    const SelinvLaunch& d = P.launches[j];
+    if (fused && bt_.si_fusable[j]) {
+      count(launch_batch_selinv_fused(stream_, s, bt_.siunits + d.first, d.count, bt_.sirows, bt_.sirelpos));
+    } else {
+      for (size_t k = i; k <= j && fits; ++k)
+        count(launch_batch_selinv(stream_, s, P.launches[k], bt_.siunits, bt_.sitiles, bt_.sirows, bt_.sirelpos));
+    }
+    i = j + 1;
+  }
+  HIPCHK(hipGetLastError(), "batch selinv launch");
+  if ((rc = sync_stream(stream_, "batch selinv sync"))) return rc;
+  if (!fits) {
+    bt_err_ = "batched selected inversion: a launch of the program has more work items for ONE member than a grid holds";
+    return -99;
+  }
+  bt_.si_launches = nl;
+  bt_.z_valid = true;
+  for (int fl : bt_.hflag)
+    if (fl != INT_MAX) return kErrNotPosDef;
+  return 0;
+}
+
+int Engine::download_inverse_batch(int member, double* out, int64_t count) {
+  if (status_) return status_;
+  if (!bt_.z_valid || !out || member < 0 || member >= bt_.nbatch || count < 0) return -10;
+  if (bt_.hflag[(size_t)member] != INT_MAX) return kErrNotPosDef;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  return staged_d2h(out, bt_.Z + (int64_t)member * bt_.lstride, sizeof(double) * (size_t)std::min<int64_t>(count, S_->arena));
+}
+
+double* Engine::device_inverse_batch(int64_t* member_stride) {
+  const bool ok = bt_.z_valid && bt_.nbatch > 0;
+  if (member_stride) *member_stride = ok ? bt_.lstride : 0;
+  return ok ? bt_.Z : nullptr;
+}
+
+int Engine::batch_rows_to_host(double* out, int64_t ldout, int nrow, int64_t len, const char* what) {
+  if (ldout == len) {
+    HIPCHK(hipMemcpyAsync(out, bt_.stage, sizeof(double) * (size_t)len * (size_t)nrow, hipMemcpyDeviceToHost, stream_), what);
+  } else {
+    for (int r = 0; r < nrow; ++r)
+      HIPCHK(hipMemcpyAsync(out + (int64_t)r * ldout, bt_.stage + (int64_t)r * len, sizeof(double) * (size_t)len,
+                            hipMemcpyDeviceToHost, stream_), what);
+  }
+  return 0;
+}
+
+int Engine::inverse_diag_batch(double* out, int64_t ldout) {
+  if (status_) return status_;
+  bt_err_.clear();
+  const int n = S_->n;
+  if (!bt_.z_valid || !out || ldout < n || bt_.nbatch <= 0) return -10;
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)bt_.nbatch * (size_t)n, "the gathered diagonals");
+  if (rc) return rc;
+  if (launch_batch_selinv_diag_gather(stream_, batch_selinv_view(), bt_.diag, bt_.order, n, bt_.stage, n) < 0) {
+    bt_err_ = "batch inverse diagonal: one member's entries are more work items than a grid holds";
+    return -99;
+  }
+  HIPCHK(hipGetLastError(), "batch inverse diag launch");
+  if ((rc = batch_rows_to_host(out, ldout, bt_.nbatch, n, "batch inverse diag D2H"))) return rc;
+  return sync_stream(stream_, "batch inverse diag sync");
+}
+
+int Engine::inverse_on_pattern_batch(double* out, int64_t ldout) {
+  if (status_) return status_;
+  bt_err_.clear();
+  const int64_t nnz = S_->nnzA;
+  if (!bt_.z_valid || !out || ldout < nnz || bt_.nbatch <= 0) return -10;
+  if (nnz == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)bt_.nbatch * (size_t)nnz, "the gathered entries");
+  if (rc) return rc;
+  if (launch_batch_selinv_pattern(stream_, batch_selinv_view(), d_map_dst_, d_map_src_, nmap_, bt_.stage, nnz) < 0) {
+    bt_err_ = "batch inverse on pattern: one member's entries are more work items than a grid holds";
+    return -99;
+  }
+  HIPCHK(hipGetLastError(), "batch inverse on pattern launch");
+  if ((rc = batch_rows_to_host(out, ldout, bt_.nbatch, nnz, "batch inverse on pattern D2H"))) return rc;
+  return sync_stream(stream_, "batch inverse on pattern sync");
+}
+
+// the inverse arenas and the step scratch back to the pool; the batch factor and its solve stay
+int Engine::release_inverse_batch() {
+  if (status_) return status_;
+  bt_.z_valid = false;
+  bt_.si_launches = 0;
+  if (!bt_.Z && !bt_.siscratch) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "batch inverse release")) return rc;
+  if (bt_.Z) release_buffer(bt_.Z);
+  if (bt_.siscratch) release_buffer(bt_.siscratch);
+  bt_.Z = bt_.siscratch = nullptr;
+  bt_.z_capacity = 0;
   return 0;
 }
 

@@ -50,7 +50,13 @@ struct EngineOptions {
                            // program, -1 by problem size (env SPLLT_HIP_GRAPH overrides)
 };
 
-struct BatchView;   // kernels.hpp
+struct BatchView;         // kernels.hpp
+struct BatchSelinvView;   // kernels.hpp
+
+// debug hook (spllt_hip_debug "batch_selinv_fused=0|1"): 0 forces the three-launch form of every step of the
+// batched selected inversion; process-wide, read when an inversion is enqueued
+void set_batch_selinv_fused(bool on);
+bool batch_selinv_fused();
 
 struct FactorStats {
   double submit_ms = 0;   // host time spent in factor_async
@@ -142,6 +148,9 @@ class Engine {
   int inverse_diag(double* out, int n);               // (A^-1)_ii, user variable order, host
   int log_det(double* out);                           // 2 sum log L_jj of the current factor
   int release_inverse();                              // give the Z arena back to the pool
+  // out[k] = (A^-1) at the k-th entry of the analysed CSC-lower pattern (nnz doubles, host): the gather
+  // kernel of the batched inversion with one member
+  int inverse_on_pattern(double* out);
   double* device_Z() { return z_valid_ ? d_Z_ : nullptr; }
   const SelinvProgram& selinv_program() const { return siprog_; }
   const std::string& selinv_error() const { return si_err_; }
@@ -159,6 +168,20 @@ class Engine {
   int batch_launches() const { return bt_.launches; }
   int release_batch();
   const std::string& batch_error() const { return bt_err_; }
+  // ---- batched selected inversion (batch_selinv.hip): Z_b = (P A_b P^T)^-1 on the pattern of L for every
+  // member of the current batch, by a SelinvProgram built with pw = cb = 64 (the panels of the batch
+  // factorization) whose every launch carries all members.  The Z arenas (capacity x lstride) and the step
+  // scratch are taken on the first call, grow with nbatch and stay until release_batch /
+  // release_inverse_batch.  factor_batch marks Z stale.  Independent of selected_inverse() and its arena.
+  int selected_inverse_batch();                       // 0, -20 (some member failed: the others are inverted), error
+  bool batch_inverse_valid() const { return bt_.z_valid; }
+  int download_inverse_batch(int member, double* out, int64_t count);
+  double* device_inverse_batch(int64_t* member_stride);
+  int inverse_diag_batch(double* out, int64_t ldout);        // host, out[b * ldout + i], user order
+  int inverse_on_pattern_batch(double* out, int64_t ldout);  // host, out[b * ldout + k], the order of val
+  int batch_selinv_launches() const { return bt_.si_launches; }
+  int release_inverse_batch();
+  const SelinvProgram& batch_selinv_program() const { return bt_.siprog; }
   double* device_L() { return d_L_; }
   hipStream_t stream() { return stream_; }
   // the stream the pending exchange is packed / unpacked on (its collective belongs there); the chain stream when none is pending
@@ -314,6 +337,7 @@ class Engine {
   double* d_Z_ = nullptr;
   double* d_siscratch_ = nullptr;
   double* d_siout_ = nullptr;      // n + 1 doubles: diag(A^-1), log det
+  double* d_sipat_ = nullptr;      // nnz doubles: A^-1 on the analysed pattern (inverse_on_pattern)
   // batched factorization: tables (uploaded once, on the first batch call) and per-batch storage (grows
   // with nbatch, stays with the engine until release_batch)
   struct BatchState {
@@ -348,12 +372,32 @@ class Engine {
     bool own_init = false;           // init_* are the batch's own upload (else the engine's d_init_* tables)
     int launches = 0;
     int member_fast = 0;
+    // batched selected inversion: program and tables (once per engine), Z arenas and scratch (per batch)
+    bool si_ready = false;
+    SelinvProgram siprog;
+    std::vector<char> si_fusable;    // per launch of siprog: the DIAG launch of a step the fused kernel can take
+    char* d_sitab = nullptr;
+    SelinvUnit* siunits = nullptr;
+    UpdTile* sitiles = nullptr;
+    SelinvRow* sirows = nullptr;
+    int* sirelpos = nullptr;
+    double* Z = nullptr;             // z_capacity x lstride
+    double* siscratch = nullptr;     // z_capacity x sstride
+    int z_capacity = 0;
+    int64_t sstride = 0;
+    bool z_valid = false;
+    int si_launches = 0;
   } bt_;
   std::string bt_err_;
   int prepare_batch();
   int reserve_batch(int nbatch);
   int grow_batch_buffer(double** p, size_t* have, size_t need, const char* what);
   BatchView batch_view() const;
+  int prepare_batch_selinv();
+  int reserve_batch_inverse(int nbatch);
+  BatchSelinvView batch_selinv_view() const;
+  // the packed device rows of a batch reader (nrow x len in bt_.stage) to the caller's out[r * ldout ..]
+  int batch_rows_to_host(double* out, int64_t ldout, int nrow, int64_t len, const char* what);
 };
 
 // The batch program of a pattern: build_program with fixed options (single stream, no fused panels, no

@@ -138,6 +138,32 @@ int launch_batch_solve(hipStream_t st, const BatchView& v, int kind, const int* 
                        int n);
 // out[b] = 2 sum_j log L_b[diag_pos[j]] in a fixed order; NaN for a member whose flag is set
 int launch_batch_log_det(hipStream_t st, const BatchView& v, const int64_t* diag_pos, int n, double* out);
+// the limit in force (set_batch_grid_limit) and the hardware limit, for the other batched translation units
+int64_t batch_grid_limit();
+int64_t batch_grid_limit_max();
+// ---- batched selected inversion (batch_selinv.hip): Z_b on the pattern of L for every member ----------
+// The batch's view plus member b's inverse arena Z + b * v.lstride (L's layout) and step scratch
+// scratch + b * sstride.  The tables are those of a SelinvProgram built with pw = cb = 64 and are shared.
+// A member whose flag is set is skipped by every kernel; the two readers write NaN for it.  v.flag may be
+// null for the readers: one arena known to be valid.  Return values as above.
+struct BatchSelinvView {
+  BatchView v;
+  double* Z;
+  double* scratch;
+  int64_t sstride;
+};
+// one launch of the program (SI_SYMM / SI_SCALE / SI_DIAG) for all members
+int launch_batch_selinv(hipStream_t st, const BatchSelinvView& s, const SelinvLaunch& l, const SelinvUnit* units,
+                        const UpdTile* tiles, const SelinvRow* rows, const int* relpos);
+// one whole step (SYMM + SCALE + DIAG) of units[0 .. count), each with nR <= 64 and nsplit <= 1, in one launch
+int launch_batch_selinv_fused(hipStream_t st, const BatchSelinvView& s, const SelinvUnit* units, int64_t count,
+                              const SelinvRow* rows, const int* relpos);
+// out[b * ldout + i] = Z_b[diag_pos[order[i]]]  (diag(A_b^-1) in the user's variable order)
+int launch_batch_selinv_diag_gather(hipStream_t st, const BatchSelinvView& s, const int64_t* diag_pos, const int* order,
+                                    int n, double* out, int64_t ldout);
+// out[b * ldout + map_src[e]] = Z_b[map_dst[e]]  (A_b^-1 at the entries of the analysed pattern, in the order of val)
+int launch_batch_selinv_pattern(hipStream_t st, const BatchSelinvView& s, const int64_t* map_dst, const int64_t* map_src,
+                                int64_t nmap, double* out, int64_t ldout);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 
