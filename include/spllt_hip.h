@@ -403,6 +403,44 @@ int     spllt_hip_inverse_on_pattern_batch(void *fkeep, double *out, int64_t ldo
 int     spllt_hip_batch_selinv_launches(void *fkeep);
 /* give the Z arenas and the scratch back; the batch factor and its solve stay */
 int     spllt_hip_release_inverse_batch(void *fkeep);
+/* ---- refined solves (single GPU) ---------------------------------------------------
+ * The operator A on the analysed pattern lives on the device as a full (both triangles) CSR of P A P^T
+ * in pivot order, built on first use from the pattern alone: "matvec_rowptr" (int64), "matvec_col"
+ * (int32 pivot positions, sorted inside a row) and "matvec_src" (int32 indices into val) of
+ * spllt_hip_program_get.  y_p = sum_k val[src[k]] * x[col[k]] is a gather with a fixed summation order:
+ * no atomics, two products of the same inputs are bit-identical.
+ *
+ * spllt_hip_matvec: y = A x; val: nnz values in the order of spllt_factor (need not be the factored ones);
+ * nvec vectors, user order, x[q*ldx + i], y[q*ldy + i]; only those ranges are read or written.  The _dev
+ * twin takes device pointers; pivot_order = 1: x and y are in pivot order as for spllt_hip_solve_dev (x and
+ * y must not overlap).  The product needs no factor.
+ *
+ * spllt_hip_solve_refined: solve A x = b with A = (pattern, val) and the CURRENT factor as M, to the
+ * backward error e = ||b - A x||_2 / (||b||_2 + max|a_ij| ||x||_2) <= tol.  x holds b on entry, the solution
+ * on exit.  method 0: iterative refinement x += M^-1 (b - A x); method 1: conjugate gradients preconditioned
+ * by M, every vector with its own scalars; a vector that the recurrence residual declares converged is
+ * confirmed with a true residual and goes on from it if the confirmation fails.  tol > 0; max_iter >= 0;
+ * iterations (int) and error (double) receive nrhs values each, either may be NULL: iterations[q] = the
+ * applications of M^-1 after the first (0: M^-1 b passed), error[q] = e of a true residual.  Returns 0 when
+ * every vector reached tol and 1 when at least one did not: x then holds, per vector, the iterate with the
+ * smallest confirmed error (never worse than M^-1 b), and error[] says which.  A NaN in val or b ends that
+ * vector as not converged.  Vectors are worked on in groups of 32 (five work vectors and the best iterate
+ * per member of a group, taken from the device pool on first use together with the operator; kept until
+ * spllt_hip_release_refine or spllt_deallocate_fkeep).  M^-1 is spllt_hip_solve_dev for up to 4 vectors and
+ * spllt_hip_solve_many_dev above; a later factorization on the handle is picked up.  All work is ordered on
+ * spllt_hip_engine_stream and finished when a call returns; per iteration one array of 64 doubles is read
+ * back.  Reproducibility: products and reductions are bit-reproducible, the solution inherits the fp64
+ * atomics of the solves and agrees to rounding only.
+ * Errors: null pointer, negative count, nnz not the pattern's, ldx / ldy < n, bad method, tol <= 0, nothing
+ * factorized yet (refined solve only) -> SPLLT_ERROR_PARAMETER; partitioned handle ->
+ * SPLLT_ERROR_UNIMPLEMENTED; no device -> SPLLT_ERROR_HIP; no device memory -> SPLLT_ERROR_ALLOCATION
+ * (nothing is kept half-allocated, the factor and every other solve stay usable).  nvec = 0 and nrhs = 0
+ * are no-ops that return 0.  Messages: spllt_hip_last_error. */
+int spllt_hip_matvec    (void *fkeep, int nnz, const double *val_host, int nvec, const double *x_host, int64_t ldx, double *y_host, int64_t ldy);
+int spllt_hip_matvec_dev(void *fkeep, int nnz, const double *val_dev,  int nvec, const double *x_dev,  int64_t ldx, double *y_dev,  int64_t ldy, int pivot_order);
+int spllt_hip_solve_refined    (void *fkeep, int nnz, const double *val_host, int nrhs, double *x_host, int64_t ldx, int method, double tol, int max_iter, int *iterations, double *error);
+int spllt_hip_solve_refined_dev(void *fkeep, int nnz, const double *val_dev,  int nrhs, double *x_dev,  int64_t ldx, int method, double tol, int max_iter, int *iterations, double *error);
+int spllt_hip_release_refine(void *fkeep);   /* operator tables and work vectors back to the pool */
 /* timings of the last factorization, milliseconds */
 int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, double *h2d_ms,
                            int *launches);
@@ -424,7 +462,8 @@ int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, do
  * "batch_potrf", empty, "batch_scratch_size", 0); the selected-inversion program of the batch (panels of
  * 64 columns, independent of the handle's panel width): "batch_selinv_units", "batch_selinv_tiles",
  * "batch_selinv_launches", "batch_selinv_rows", "batch_selinv_relpos", "batch_selinv_diag",
- * "batch_selinv_scratch", "batch_selinv_flops", the layouts of the "selinv_*" names.  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
+ * "batch_selinv_scratch", "batch_selinv_flops", the layouts of the "selinv_*" names; the operator of the
+ * refined solves: "matvec_rowptr" (int64), "matvec_col", "matvec_src" (int32).  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
  * spllt_amd/api.py.  Returns the byte length. */
 int64_t spllt_hip_program_get(void *fkeep, const char *name, void *buf, int64_t capacity_bytes);
 /* per-launch device time (ms) of one profiled factorization; returns #launches */

@@ -67,6 +67,8 @@ HIP_SYMBOLS = [
     "spllt_hip_selected_inverse_batch", "spllt_hip_get_inverse_batch", "spllt_hip_device_inverse_batch",
     "spllt_hip_inverse_diag_batch", "spllt_hip_inverse_on_pattern_batch", "spllt_hip_batch_selinv_launches",
     "spllt_hip_release_inverse_batch", "spllt_hip_inverse_on_pattern",
+    "spllt_hip_matvec", "spllt_hip_matvec_dev", "spllt_hip_solve_refined", "spllt_hip_solve_refined_dev",
+    "spllt_hip_release_refine",
 ]
 
 _lib = None
@@ -161,6 +163,17 @@ def load():
     lib.spllt_hip_solve_many.restype = C.c_int
     lib.spllt_hip_solve_many_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int]
     lib.spllt_hip_solve_many_dev.restype = C.c_int
+    ip = C.POINTER(C.c_int)
+    lib.spllt_hip_matvec.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_int64, dp, C.c_int64]
+    lib.spllt_hip_matvec.restype = C.c_int
+    lib.spllt_hip_matvec_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int64, vp, C.c_int64, C.c_int]
+    lib.spllt_hip_matvec_dev.restype = C.c_int
+    lib.spllt_hip_solve_refined.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_int64, C.c_int, C.c_double, C.c_int, ip, dp]
+    lib.spllt_hip_solve_refined.restype = C.c_int
+    lib.spllt_hip_solve_refined_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int64, C.c_int, C.c_double, C.c_int, ip, dp]
+    lib.spllt_hip_solve_refined_dev.restype = C.c_int
+    lib.spllt_hip_release_refine.argtypes = [vp]
+    lib.spllt_hip_release_refine.restype = C.c_int
     lib.spllt_hip_profile.argtypes = [vp, dp, C.c_int, C.POINTER(C.c_float), C.c_int]
     lib.spllt_hip_profile.restype = C.c_int
     lib.spllt_hip_profile_in_program.argtypes = [vp, dp, C.c_int, C.POINTER(C.c_float), C.c_int]

@@ -162,6 +162,10 @@ class Factorization:
         raw = np.zeros(max(nbytes, 1), dtype=np.uint8)
         self.lib.spllt_hip_program_get(self.fkeep, name.encode(), raw.ctypes.data, nbytes)
         raw = raw[:nbytes]
+        if name == "matvec_rowptr":      # the operator of the refined solves
+            return raw.view(np.int64)
+        if name in ("matvec_col", "matvec_src"):
+            return raw.view(np.int32)
         if name.startswith("batch_"):    # the batch program: the layouts of the unprefixed names
             name = name[len("batch_"):]
         if name == "launches":
@@ -405,6 +409,86 @@ class Factorization:
         if rc < 0:
             raise SplltError("spllt_hip_solve_many_dev", rc, self.last_error())
         return self
+
+    # ---- refined solves --------------------------------------------------------
+    _METHODS = {"ir": 0, "pcg": 1, 0: 0, 1: 1}
+    refine_status = None     # return value of the last solve_refined() on this handle
+
+    def _values(self, val, where):
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        if val.ndim != 1:
+            raise SplltError(where, -10, "val must be one array of nnz values")
+        return val
+
+    def matvec(self, val, x):
+        """spllt_hip_matvec: A x on the device with A = (the analysed pattern, val); x is n or n x nvec.
+        Two calls with the same inputs return bit-identical results.  Needs no factor."""
+        val = self._values(val, "spllt_hip_matvec")
+        x = np.asarray(x, dtype=np.float64)
+        xs = np.asfortranarray(x.reshape(x.shape[0], -1))
+        y = np.empty_like(xs, order="F")
+        ld = max(1, xs.shape[0])
+        rc = self.lib.spllt_hip_matvec(self.fkeep, int(val.size), _dp(val), xs.shape[1], _dp(xs), ld, _dp(y), ld)
+        if rc < 0:
+            raise SplltError("spllt_hip_matvec", rc, self.last_error())
+        return y.reshape(x.shape, order="F")
+
+    def matvec_dev(self, val_dev_ptr, nnz, x_dev_ptr, y_dev_ptr, nvec, ldx=None, ldy=None, pivot_order=False):
+        """spllt_hip_matvec_dev: the product on device arrays (vector q at x[q*ldx .. q*ldx + n), y alike;
+        pivot_order as for solve_many_dev; x and y must not overlap)."""
+        rc = self.lib.spllt_hip_matvec_dev(self.fkeep, int(nnz), C.c_void_p(val_dev_ptr), nvec, C.c_void_p(x_dev_ptr),
+                                           int(self.n if ldx is None else ldx), C.c_void_p(y_dev_ptr),
+                                           int(self.n if ldy is None else ldy), 1 if pivot_order else 0)
+        if rc < 0:
+            raise SplltError("spllt_hip_matvec_dev", rc, self.last_error())
+        return self
+
+    def solve_refined(self, val, b, method="pcg", tol=1e-14, max_iter=50):
+        """spllt_hip_solve_refined on a copy of b (n or n x nrhs): solve A x = b for A = (pattern, val) with the
+        current factor as preconditioner, to the backward error tol.  method "ir" (refinement) or "pcg".
+        Returns (x, iterations, error): per vector the applications of the factor after the first and the
+        backward error of a true residual; `not error[q] <= tol` marks a vector that did not converge (x then
+        holds its best iterate).  self.refine_status keeps the call's return value (0: every vector reached tol,
+        1: at least one did not, negative: the flag of the error raised; None before the first call)."""
+        if method not in self._METHODS:
+            raise SplltError("spllt_hip_solve_refined", -10, "method is not 'ir' or 'pcg'")
+        val = self._values(val, "spllt_hip_solve_refined")
+        x = np.array(b, dtype=np.float64, order="F", copy=True)
+        nrhs = 1 if x.ndim == 1 else x.shape[1]
+        it = np.zeros(max(1, nrhs), dtype=np.int32)
+        err = np.zeros(max(1, nrhs), dtype=np.float64)
+        rc = self.lib.spllt_hip_solve_refined(self.fkeep, int(val.size), _dp(val), nrhs, _dp(x), max(1, x.shape[0]),
+                                              self._METHODS[method], float(tol), int(max_iter), _ip(it), _dp(err))
+        self.refine_status = rc
+        if rc < 0:
+            raise SplltError("spllt_hip_solve_refined", rc, self.last_error())
+        return x, it[:nrhs], err[:nrhs]
+
+    def solve_refined_dev(self, val_dev_ptr, nnz, x_dev_ptr, nrhs, ldx=None, method="pcg", tol=1e-14, max_iter=50):
+        """spllt_hip_solve_refined_dev: values and vectors on the device (user order, in place).  Returns
+        (status, iterations, error); status 0: every vector reached tol, 1: at least one did not."""
+        if method not in self._METHODS:
+            raise SplltError("spllt_hip_solve_refined_dev", -10, "method is not 'ir' or 'pcg'")
+        it = np.zeros(max(1, nrhs), dtype=np.int32)
+        err = np.zeros(max(1, nrhs), dtype=np.float64)
+        rc = self.lib.spllt_hip_solve_refined_dev(self.fkeep, int(nnz), C.c_void_p(val_dev_ptr), nrhs,
+                                                  C.c_void_p(x_dev_ptr), int(self.n if ldx is None else ldx),
+                                                  self._METHODS[method], float(tol), int(max_iter), _ip(it), _dp(err))
+        if rc < 0:
+            raise SplltError("spllt_hip_solve_refined_dev", rc, self.last_error())
+        return rc, it[:nrhs], err[:nrhs]
+
+    def release_refine(self):
+        """spllt_hip_release_refine: the operator tables and work vectors go back to the pool"""
+        rc = self.lib.spllt_hip_release_refine(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_refine", rc, self.last_error())
+        return self
+
+    def matvec_tables(self):
+        """the operator of the refined solves: (rowptr int64, col int32, src int32) of the full CSR of
+        P A P^T in pivot order ("matvec_*" of spllt_hip_program_get); needs no device"""
+        return self.program("matvec_rowptr"), self.program("matvec_col"), self.program("matvec_src")
 
     # ---- batched factorization ------------------------------------------------
     def _batch_rc(self, where, rc):

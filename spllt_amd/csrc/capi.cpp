@@ -53,6 +53,10 @@ struct Fkeep {
   std::shared_ptr<const Symbolic> bsi_S;
   int bsi_rc = 0;
   SelinvProgram bsi_prog;
+  // the operator tables of spllt_hip_program_get ("matvec_*", built once per pattern)
+  std::shared_ptr<const Symbolic> mv_S;
+  std::vector<int64_t> mv_rowptr;
+  std::vector<int> mv_col, mv_src;
 };
 
 std::mutex g_mu;
@@ -937,6 +941,101 @@ int spllt_hip_solve_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx,
   return solve_batch_impl(fkeep, nrhs, x_dev, ldx, job, true, pivot_order != 0, "spllt_hip_solve_batch_dev");
 }
 
+// ---- refined solves ---------------------------------------------------------
+static int refine_fail(Fkeep* f, int rc) {
+  if (!f->eng->refine_error().empty()) f->last_error = f->eng->refine_error();
+  else if (f->eng->status()) f->last_error = f->eng->error();
+  return rc;
+}
+
+// the argument checks that need no device: `bad` from the caller's own checks, nnz, partition, a dead handle
+static int refine_engine(Fkeep* f, const char* what, int nnz, const char* bad) {
+  if (!bad && (int64_t)nnz != f->S->nnzA) bad = "nnz does not match the analysed pattern";
+  if (bad) return batch_param_error(f, what, bad);
+  if (int rc = batch_partitioned(f, what)) return rc;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  return 0;
+}
+
+static int matvec_impl(void* fkeep, int nnz, const double* val, int nvec, const double* x, int64_t ldx, double* y,
+                       int64_t ldy, bool dev, bool pivot_order, const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!val) bad = "the array of values is null";
+  else if (!x || !y) bad = "a vector array is null";
+  else if (nvec < 0) bad = "nvec < 0";
+  else if (ldx < f->S->n) bad = "ldx < n";
+  else if (ldy < f->S->n) bad = "ldy < n";
+  if (int rc = refine_engine(f, what, nnz, bad)) return rc;
+  if (nvec == 0) return 0;
+  if (f->eng && f->eng->pending()) (void)do_wait(f);
+  if (!f->eng) {
+    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
+    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
+    f->eng->set_exchange_buffer(f->xbuf);
+  }
+  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
+  int rc = f->eng->matvec(val, nvec, x, ldx, y, ldy, dev, pivot_order);
+  return rc ? refine_fail(f, rc) : 0;
+}
+
+int spllt_hip_matvec(void* fkeep, int nnz, const double* val_host, int nvec, const double* x_host, int64_t ldx,
+                     double* y_host, int64_t ldy) {
+  return matvec_impl(fkeep, nnz, val_host, nvec, x_host, ldx, y_host, ldy, false, false, "spllt_hip_matvec");
+}
+
+int spllt_hip_matvec_dev(void* fkeep, int nnz, const double* val_dev, int nvec, const double* x_dev, int64_t ldx,
+                         double* y_dev, int64_t ldy, int pivot_order) {
+  return matvec_impl(fkeep, nnz, val_dev, nvec, x_dev, ldx, y_dev, ldy, true, pivot_order != 0, "spllt_hip_matvec_dev");
+}
+
+static int solve_refined_impl(void* fkeep, int nnz, const double* val, int nrhs, double* x, int64_t ldx, int method,
+                              double tol, int max_iter, int* iterations, double* error, bool dev, const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!val) bad = "the array of values is null";
+  else if (!x) bad = "the array of right-hand sides is null";
+  else if (nrhs < 0) bad = "nrhs < 0";
+  else if (ldx < f->S->n) bad = "ldx < n";
+  else if (method != 0 && method != 1) bad = "method is not 0 (refinement) or 1 (PCG)";
+  else if (!(tol > 0.0)) bad = "tol is not positive";
+  else if (max_iter < 0) bad = "max_iter < 0";
+  if (int rc = refine_engine(f, what, nnz, bad)) return rc;
+  if (nrhs == 0) return 0;
+  if (int rc = do_wait(f)) return rc;
+  if (!f->eng || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
+  int rc = f->eng->solve_refined(val, nrhs, x, ldx, dev, method, tol, max_iter, iterations, error);
+  if (rc == 1) {
+    f->last_error = std::string(what) + ": at least one vector did not reach tol (error[] says which)";
+    return 1;
+  }
+  return rc ? refine_fail(f, rc) : 0;
+}
+
+int spllt_hip_solve_refined(void* fkeep, int nnz, const double* val_host, int nrhs, double* x_host, int64_t ldx,
+                            int method, double tol, int max_iter, int* iterations, double* error) {
+  return solve_refined_impl(fkeep, nnz, val_host, nrhs, x_host, ldx, method, tol, max_iter, iterations, error, false,
+                            "spllt_hip_solve_refined");
+}
+
+int spllt_hip_solve_refined_dev(void* fkeep, int nnz, const double* val_dev, int nrhs, double* x_dev, int64_t ldx,
+                                int method, double tol, int max_iter, int* iterations, double* error) {
+  return solve_refined_impl(fkeep, nnz, val_dev, nrhs, x_dev, ldx, method, tol, max_iter, iterations, error, true,
+                            "spllt_hip_solve_refined_dev");
+}
+
+int spllt_hip_release_refine(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (!f->eng) return 0;
+  if (f->eng->pending()) (void)do_wait(f);
+  int rc = f->eng->release_refine();
+  return rc ? refine_fail(f, rc) : 0;
+}
+
 int spllt_hip_get_factor_batch(void* fkeep, int member, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   const char* what = "spllt_hip_get_factor_batch";
@@ -1219,6 +1318,17 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
     }
     return -1;
   };
+  if (k.rfind("matvec_", 0) == 0) {
+    // the operator of the refined solves: from the analysed pattern and the pivot order alone
+    if (f->mv_S != f->S) {
+      build_matvec_tables(*f->S, f->mv_rowptr, f->mv_col, f->mv_src);
+      f->mv_S = f->S;
+    }
+    if (k == "matvec_rowptr") return raw(f->mv_rowptr.data(), f->mv_rowptr.size() * sizeof(int64_t));
+    if (k == "matvec_col") return raw(f->mv_col.data(), f->mv_col.size() * sizeof(int));
+    if (k == "matvec_src") return raw(f->mv_src.data(), f->mv_src.size() * sizeof(int));
+    return -1;
+  }
   if (k.rfind("batch_selinv_", 0) == 0) {
     // the selected-inversion program of the batch: panels of 64 columns, from the symbolic structure alone
     if (f->bsi_S != f->S) {

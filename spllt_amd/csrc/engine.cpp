@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "kernels.hpp"
+#include "refine.hpp"
 
 namespace spx {
 
@@ -1281,6 +1282,7 @@ int Engine::factor_async_dev(const double* val_dev, int64_t nnz) {
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
   z_valid_ = false;
+  factored_ = true;
   double t0 = now_ms();
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipEventRecord(ev0_, stream_), "event");
@@ -1309,6 +1311,7 @@ int Engine::factor_async(const double* val_host, int64_t nnz) {
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
   z_valid_ = false;
+  factored_ = true;
   double t0 = now_ms();
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipEventRecord(ev0_, stream_), "event");
@@ -1790,6 +1793,269 @@ int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
     done += nv;
   }
   return 0;
+}
+
+// ---- refined solves --------------------------------------------------------------------------------
+// Operator tables (once per engine) and the work vectors of one group, all or nothing: a failed allocation
+// gives back what it got and leaves the factor and every other solve usable.
+int Engine::prepare_refine(bool host_val) {
+  const Symbolic& S = *S_;
+  const size_t n1 = (size_t)std::max(1, S.n);
+  hipError_t e = hipSuccess;
+  size_t want = 0;
+  if (!refine_ready_) {
+    std::vector<int64_t> rowptr;
+    std::vector<int> col, src, rows, order(S.order.begin(), S.order.end());
+    build_matvec_tables(S, rowptr, col, src);
+    // rows by length: at most 16 entries -> 4 lanes per row, at most 128 -> 16 lanes, longer -> a wavefront
+    rows.reserve((size_t)S.n);
+    for (int c = 0; c < 3; ++c) {
+      rf_nrows_[c] = 0;
+      for (int p = 0; p < S.n; ++p) {
+        const int64_t len = rowptr[(size_t)p + 1] - rowptr[(size_t)p];
+        const int cls = len <= 16 ? 0 : (len <= 128 ? 1 : 2);
+        if (cls == c) { rows.push_back(p); ++rf_nrows_[c]; }
+      }
+    }
+    RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+    const size_t slots = (size_t)std::max(std::max(spmv_slots(op), vec_slots(S.n)), RF_AMAX_WG);
+    TableStager tab;
+    tab.add(&d_rfrowptr_, rowptr);
+    tab.add(&d_rfcol_, col);
+    tab.add(&d_rfsrc_, src);
+    tab.add(&d_rfrows_, rows);
+    tab.add(&d_rforder_, order);
+    e = tab.commit(&d_rftab_, [this](void** q, size_t b) { return dalloc(q, b); });
+    want = sizeof(double) * 6 * RF_G * n1;
+    if (e == hipSuccess) e = dalloc((void**)&d_rfwork_, want);
+    if (e == hipSuccess) e = dalloc((void**)&d_rfpart_, sizeof(double) * 2 * RF_G * slots);
+    if (e == hipSuccess) e = dalloc((void**)&d_rfds_, sizeof(double) * RF_DS);
+    if (e == hipSuccess) e = dalloc((void**)&d_rfis_, sizeof(int) * RF_IS);
+    if (e == hipSuccess) e = hipMemsetAsync(d_rfis_, 0, sizeof(int) * RF_IS, stream_);
+    if (e == hipSuccess) e = hipMemsetAsync(d_rfds_, 0, sizeof(double) * RF_DS, stream_);
+  }
+  if (e == hipSuccess && host_val && !d_rfval_) {
+    want = sizeof(double) * (size_t)std::max<int64_t>(1, S.nnzA);
+    e = dalloc((void**)&d_rfval_, want);
+    if (e != hipSuccess) d_rfval_ = nullptr;
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (!refine_ready_) {
+      for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_})
+        if (p) release_buffer(p);
+      d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr;
+    }
+    rf_err_ = "refined solve: not enough device memory for the operator and the work vectors (" +
+              std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
+  }
+  refine_ready_ = true;
+  return 0;
+}
+
+int Engine::release_refine() {
+  if (status_) return status_;
+  if (!refine_ready_ && !d_rfval_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "refine release")) return rc;
+  for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_, (void*)d_rfval_})
+    if (p) release_buffer(p);
+  d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr; d_rfval_ = nullptr;
+  refine_ready_ = false;
+  return 0;
+}
+
+int Engine::matvec(const double* val, int nvec, const double* x, int64_t ldx, double* y, int64_t ldy, bool dev,
+                   bool pivot_order) {
+  if (status_) return status_;
+  rf_err_.clear();
+  const int n = S_->n;
+  if (!val || !x || !y || nvec < 0 || ldx < n || ldy < n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;   // (the caller waits first)
+  if (nvec == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_refine(!dev);
+  if (rc) return rc;
+  const size_t vb = sizeof(double) * (size_t)n;
+  const double* dval = val;
+  if (!dev) {
+    HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");
+    dval = d_rfval_;
+  }
+  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  const size_t gn = (size_t)RF_G * (size_t)n;
+  double *wb = d_rfwork_, *wr = d_rfwork_ + 2 * gn, *wq = d_rfwork_ + 4 * gn;
+  for (int done = 0; done < nvec;) {
+    const int nv = std::min(RF_G, nvec - done);
+    const double* xg = x + (int64_t)done * ldx;
+    double* yg = y + (int64_t)done * ldy;
+    if (dev && pivot_order) {
+      launch_spmv(stream_, op, dval, xg, ldx, nullptr, yg, ldy, nv, nullptr, 0, nullptr);
+    } else if (dev) {
+      launch_rf_pack(stream_, n, nv, xg, ldx, d_rforder_, wb);
+      launch_spmv(stream_, op, dval, wb, n, nullptr, wr, n, nv, nullptr, 0, nullptr);
+      launch_rf_unpack(stream_, n, nv, yg, ldy, d_rforder_, wr);
+    } else {
+      for (int q = 0; q < nv; ++q)
+        HIPCHK(hipMemcpyAsync(wq + (size_t)q * n, xg + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "x H2D");
+      launch_rf_pack(stream_, n, nv, wq, n, d_rforder_, wb);
+      launch_spmv(stream_, op, dval, wb, n, nullptr, wr, n, nv, nullptr, 0, nullptr);
+      launch_rf_unpack(stream_, n, nv, wq, n, d_rforder_, wr);
+      for (int q = 0; q < nv; ++q)
+        HIPCHK(hipMemcpyAsync(yg + (int64_t)q * ldy, wq + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "y D2H");
+    }
+    HIPCHK(hipGetLastError(), "matvec launch");
+    if (!dev && (rc = sync_stream(stream_, "matvec sync"))) return rc;
+    done += nv;
+  }
+  return sync_stream(stream_, "matvec sync");
+}
+
+// both sweeps with the current factor on nv work vectors (pivot order, ld = n), through the existing paths.
+// The sweeps take all nv columns, frozen vectors included (their columns are zero: launch_rf_copy), since the
+// existing paths know no mask; the columns of a sweep are independent of each other.
+int Engine::refine_apply_factor(double* v, int nv) {
+  const int rc = nv <= 4 ? solve_dev(v, nv, 0, -1) : solve_many_dev(v, nv, (int64_t)S_->n, 0, true);
+  if (rc && !sm_err_.empty()) rf_err_ = sm_err_;
+  return rc;
+}
+
+// the one array that crosses the bus per iteration: out[q] = best confirmed error, out[32 + q] = state
+int Engine::refine_readback(int nv, std::vector<double>& out) {
+  (void)nv;
+  HIPCHK(hipGetLastError(), "refine launch");
+  HIPCHK(hipMemcpyAsync(out.data(), d_rfds_ + RFD_OUT, sizeof(double) * 2 * RF_G, hipMemcpyDeviceToHost, stream_),
+         "refine state D2H");
+  return sync_stream(stream_, "refine sync");
+}
+
+int Engine::refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol,
+                         int max_iter, int* iterations, double* error) {
+  const int n = S_->n;
+  const size_t vb = sizeof(double) * (size_t)n;
+  const size_t gn = (size_t)RF_G * (size_t)n;
+  double *B = d_rfwork_, *X = B + gn, *R = X + gn, *P = R + gn, *Q = P + gn, *XB = Q + gn;
+  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  const int sslots = spmv_slots(op), vslots = vec_slots(n);
+  const int* st = d_rfis_ + RFI_ST;
+  const int* decl = d_rfis_ + RFI_DECL;
+  const int* improve = d_rfis_ + RFI_IMPROVE;
+  int rc = 0;
+  if (dev) {
+    launch_rf_pack(stream_, n, nv, x, ldx, d_rforder_, B);
+  } else {
+    for (int q = 0; q < nv; ++q)
+      HIPCHK(hipMemcpyAsync(Q + (size_t)q * n, x + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "rhs H2D");
+    launch_rf_pack(stream_, n, nv, Q, n, d_rforder_, B);
+  }
+  launch_rf_dot(stream_, n, nv, B, B, nullptr, 0, d_rfpart_);
+  launch_rf_finalize(stream_, RFS_BNORM, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
+  // x = M^-1 b, r = b - A x, the error of the first iterate
+  launch_rf_copy(stream_, n, nv, X, B, nullptr, 0);
+  if ((rc = refine_apply_factor(X, nv))) return rc;
+  auto true_residual = [&](const int* sel, int want, int flag) {
+    launch_spmv(stream_, op, dval, X, n, B, R, n, nv, sel, want, d_rfpart_);
+    launch_rf_finalize(stream_, RFS_TRUE, d_rfpart_, sslots, nv, tol, flag, d_rfds_, d_rfis_);
+    launch_rf_copy(stream_, n, nv, XB, X, improve, 1);   // the best confirmed iterate
+  };
+  true_residual(st, 0, 0);
+  std::vector<double> out(2 * RF_G, 0.0);
+  if ((rc = refine_readback(nv, out))) return rc;
+  auto active = [&]() {
+    for (int q = 0; q < nv; ++q)
+      if (out[(size_t)RF_G + q] == 0.0) return true;
+    return false;
+  };
+  std::vector<int> its((size_t)nv, 0);
+  for (int it = 0; it < max_iter && active();) {
+    ++it;
+    for (int q = 0; q < nv; ++q)
+      if (out[(size_t)RF_G + q] == 0.0) its[(size_t)q] = it;
+    if (method == 0) {
+      // x += M^-1 r ; r = b - A x
+      launch_rf_copy(stream_, n, nv, P, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
+      if ((rc = refine_apply_factor(P, nv))) return rc;
+      launch_rf_axpy(stream_, n, nv, nullptr, X, P, nullptr, nullptr, st, 0, nullptr);
+      true_residual(st, 0, 0);
+    } else {
+      // z = M^-1 r (in q) ; beta = r.z / (r.z)_old, 0 after a restart ; p = z + beta p
+      launch_rf_copy(stream_, n, nv, Q, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
+      if ((rc = refine_apply_factor(Q, nv))) return rc;
+      launch_rf_dot(stream_, n, nv, R, Q, st, 0, d_rfpart_);
+      launch_rf_finalize(stream_, RFS_BETA, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
+      launch_rf_pupdate(stream_, n, nv, d_rfds_ + RFD_BETA, P, Q, st, 0);
+      // q = A p with the partials of p.q ; alpha = r.z / p.q ; x += alpha p, r -= alpha q
+      launch_spmv(stream_, op, dval, P, n, nullptr, Q, n, nv, st, 0, d_rfpart_);
+      launch_rf_finalize(stream_, RFS_ALPHA, d_rfpart_, sslots, nv, tol, 0, d_rfds_, d_rfis_);
+      launch_rf_axpy(stream_, n, nv, d_rfds_ + RFD_ALPHA, X, P, R, Q, st, 0, d_rfpart_);
+      launch_rf_finalize(stream_, RFS_REC, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
+      // what the recurrence declares converged is confirmed with a true residual (no work if nothing is declared)
+      true_residual(decl, 1, 1);
+    }
+    if ((rc = refine_readback(nv, out))) return rc;
+  }
+  if (method == 1 && active()) {
+    // out of iterations: the error reported is that of a true residual
+    launch_rf_finalize(stream_, RFS_FINAL, d_rfpart_, 0, nv, tol, 0, d_rfds_, d_rfis_);
+    true_residual(decl, 1, 1);
+    if ((rc = refine_readback(nv, out))) return rc;
+  }
+  if (dev) {
+    launch_rf_unpack(stream_, n, nv, x, ldx, d_rforder_, XB);
+  } else {
+    launch_rf_unpack(stream_, n, nv, Q, n, d_rforder_, XB);
+    for (int q = 0; q < nv; ++q)
+      HIPCHK(hipMemcpyAsync(x + (int64_t)q * ldx, Q + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "x D2H");
+  }
+  HIPCHK(hipGetLastError(), "refine launch");
+  if ((rc = sync_stream(stream_, "refine sync"))) return rc;
+  int worst = 0;
+  for (int q = 0; q < nv; ++q) {
+    if (iterations) iterations[q] = its[(size_t)q];
+    if (error) error[q] = out[(size_t)q];
+    if (out[(size_t)RF_G + q] != 1.0) worst = 1;
+  }
+  return worst;
+}
+
+int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, bool dev, int method, double tol,
+                          int max_iter, int* iterations, double* error) {
+  if (status_) return status_;
+  rf_err_.clear();
+  const int n = S_->n;
+  if (!val || !x || nrhs < 0 || ldx < n || method < 0 || method > 1 || !(tol > 0.0) || max_iter < 0) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_ || !factored_) return -10;   // (the caller waits first)
+  if (nrhs == 0) return 0;
+  if (n == 0) {
+    for (int q = 0; q < nrhs; ++q) {
+      if (iterations) iterations[q] = 0;
+      if (error) error[q] = 0.0;
+    }
+    return 0;
+  }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_refine(!dev);
+  if (rc) return rc;
+  const double* dval = val;
+  if (!dev) {
+    HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");
+    dval = d_rfval_;
+  }
+  launch_rf_absmax(stream_, dval, S_->nnzA, d_rfpart_);
+  launch_rf_finalize(stream_, RFS_AMAX, d_rfpart_, RF_AMAX_WG, 0, tol, 0, d_rfds_, d_rfis_);
+  int worst = 0;
+  for (int done = 0; done < nrhs;) {
+    const int nv = std::min(RF_G, nrhs - done);
+    rc = refine_group(dval, nv, x + (int64_t)done * ldx, ldx, dev, method, tol, max_iter,
+                      iterations ? iterations + done : nullptr, error ? error + done : nullptr);
+    if (rc < 0) return rc;
+    worst |= rc;
+    done += nv;
+  }
+  return worst;
 }
 
 // ---- batched factorization ------------------------------------------------------------------------

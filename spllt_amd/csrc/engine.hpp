@@ -139,6 +139,20 @@ class Engine {
   int solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order);
   int solve_many(double* x_host, int nrhs, int64_t ldx, int job);   // host vectors, user order
   const std::string& solve_many_error() const { return sm_err_; }
+  // ---- refined solves (refine.hip, single GPU): the operator A on the analysed pattern, gather-only, in
+  // pivot order, and iterative refinement / conjugate gradients preconditioned by the CURRENT factor, to a
+  // requested backward error.  Groups of 32 vectors; the preconditioner is solve_dev (up to 4 vectors) or
+  // solve_many_dev in pivot order, unchanged.  val: nnz values on the analysed pattern (device when dev).
+  // y = A x; dev: device pointers, then pivot_order says that x and y are in pivot order (x, y distinct)
+  int matvec(const double* val, int nvec, const double* x, int64_t ldx, double* y, int64_t ldy, bool dev,
+             bool pivot_order);
+  // x: b on entry, the solution on exit (user order).  method 0 refinement, 1 PCG.  0: every vector reached
+  // tol; 1: at least one did not (x then holds its best confirmed iterate); < 0: error flag
+  int solve_refined(const double* val, int nrhs, double* x, int64_t ldx, bool dev, int method, double tol,
+                    int max_iter, int* iterations, double* error);
+  int release_refine();     // operator tables and work vectors back to the pool
+  bool factored() const { return factored_; }
+  const std::string& refine_error() const { return rf_err_; }
   // ---- selected inversion (selinv.hip, single GPU): Z = (P A P^T)^-1 on the pattern of L, in a
   // second arena with L's layout.  Computed from the current factor (after wait()); a later
   // factorization marks it stale: the readers below then fail instead of returning old numbers.
@@ -320,6 +334,27 @@ class Engine {
   double* d_smstage_ = nullptr;    // n * 32 doubles: a block of host vectors in the caller's order (solve_many)
   int* d_smorder_ = nullptr;       // user variable -> pivot position
   std::vector<const SolveUnit*> sm_one_fwd_, sm_one_bwd_;   // per launch: its ONE block column, or null
+  // refined solves: operator tables and work vectors (taken on first use, all or nothing)
+  int prepare_refine(bool host_val);
+  int refine_apply_factor(double* v, int nv);
+  int refine_readback(int nv, std::vector<double>& out);
+  int refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol, int max_iter,
+                   int* iterations, double* error);
+  bool factored_ = false;          // a factorization has been enqueued on this engine
+  std::string rf_err_;
+  bool refine_ready_ = false;
+  char* d_rftab_ = nullptr;        // one allocation behind the five tables below
+  int64_t* d_rfrowptr_ = nullptr;
+  int* d_rfcol_ = nullptr;
+  int* d_rfsrc_ = nullptr;
+  int* d_rfrows_ = nullptr;        // rows by length class
+  int* d_rforder_ = nullptr;       // user variable -> pivot position
+  int rf_nrows_[3] = {0, 0, 0};
+  double* d_rfwork_ = nullptr;     // 6 x 32 x n: b, x, r, p, q, best x
+  double* d_rfpart_ = nullptr;     // partial sums of the reductions
+  double* d_rfds_ = nullptr;       // device scalars (refine.hpp)
+  int* d_rfis_ = nullptr;
+  double* d_rfval_ = nullptr;      // nnz doubles: the values of a host entry point
   // selected inversion (tables uploaded once per pattern, on first use)
   int prepare_selinv();
   void release_buffer(void* p);

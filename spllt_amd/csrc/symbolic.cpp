@@ -633,7 +633,42 @@ int finish_symbolic(int n, const int64_t* ptr, const int* row, const std::vector
         S.map_src[k] = e;
       }
   }
+  S.a_ptr.assign(ptr, ptr + n + 1);
+  S.a_row.assign(row, row + ptr[n]);
   return 0;
+}
+
+void build_matvec_tables(const Symbolic& S, std::vector<int64_t>& rowptr, std::vector<int>& col,
+                         std::vector<int>& src) {
+  const int n = S.n;
+  rowptr.assign((size_t)n + 1, 0);
+  col.clear();
+  src.clear();
+  if (n <= 0 || S.a_ptr.empty()) return;
+  for (int j = 0; j < n; ++j)
+    for (int64_t e = S.a_ptr[j]; e < S.a_ptr[j + 1]; ++e) {
+      const int a = S.order[S.a_row[e]], b = S.order[j];
+      rowptr[(size_t)a + 1]++;
+      if (a != b) rowptr[(size_t)b + 1]++;
+    }
+  for (int p = 0; p < n; ++p) rowptr[(size_t)p + 1] += rowptr[(size_t)p];
+  std::vector<std::pair<int, int>> ent((size_t)rowptr[(size_t)n]);   // (column, source) per entry
+  std::vector<int64_t> pos(rowptr.begin(), rowptr.end() - 1);
+  for (int j = 0; j < n; ++j)
+    for (int64_t e = S.a_ptr[j]; e < S.a_ptr[j + 1]; ++e) {
+      const int a = S.order[S.a_row[e]], b = S.order[j];
+      ent[(size_t)pos[a]++] = {b, (int)e};
+      if (a != b) ent[(size_t)pos[b]++] = {a, (int)e};
+    }
+  col.resize(ent.size());
+  src.resize(ent.size());
+  for (int p = 0; p < n; ++p) {
+    std::sort(ent.begin() + rowptr[(size_t)p], ent.begin() + rowptr[(size_t)p + 1]);
+    for (int64_t k = rowptr[(size_t)p]; k < rowptr[(size_t)p + 1]; ++k) {
+      col[(size_t)k] = ent[(size_t)k].first;
+      src[(size_t)k] = ent[(size_t)k].second;
+    }
+  }
 }
 
 int analyse_symbolic(int n, const int64_t* ptr, const int* row, int nnodes, const int* sptr,

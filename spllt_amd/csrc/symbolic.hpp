@@ -78,6 +78,11 @@ struct Symbolic {
   std::vector<int64_t> map_src;
   std::vector<int64_t> lmap_ptr;  // nbcol+1 ranges of map_* per block column
 
+  // the analysed pattern itself (CSC of the lower triangle, 0-based, the order of val): what the
+  // operator tables of the refined solves are built from (build_matvec_tables)
+  std::vector<int64_t> a_ptr;     // n+1
+  std::vector<int> a_row;         // nnzA
+
   // statistics
   int64_t nnzL = 0;   // sum_nodes sum_j (m-n+j)
   int64_t flops = 0;  // sum_nodes sum_j (m-n+j)^2   (reference's F_sym)
@@ -104,6 +109,12 @@ int analyse_symbolic(int n, const int64_t* ptr, const int* row, int nnodes, cons
                      const SymOptions& opt, Symbolic& S);
 int finish_symbolic(int n, const int64_t* ptr, const int* row, const std::vector<int64_t>* xadj,
                     const std::vector<int>* adj, const SymOptions& opt, Symbolic& S);
+
+// The operator P A P^T of the analysed pattern as a full (both triangles) CSR in pivot order:
+// rowptr (n+1), col (pivot positions, sorted inside a row), src (index into the caller's val);
+// 2 nnzA - n entries: every off-diagonal entry of val twice, every diagonal entry once.
+void build_matvec_tables(const Symbolic& S, std::vector<int64_t>& rowptr, std::vector<int>& col,
+                         std::vector<int>& src);
 
 // Exposed for tests.
 void nested_dissection(int n, const std::vector<int64_t>& xadj,
