@@ -69,6 +69,7 @@ HIP_SYMBOLS = [
     "spllt_hip_release_inverse_batch", "spllt_hip_inverse_on_pattern",
     "spllt_hip_matvec", "spllt_hip_matvec_dev", "spllt_hip_solve_refined", "spllt_hip_solve_refined_dev",
     "spllt_hip_release_refine",
+    "spllt_hip_updown", "spllt_hip_updown_plan", "spllt_hip_updown_info", "spllt_hip_updown_time",
 ]
 
 _lib = None
@@ -174,6 +175,14 @@ def load():
     lib.spllt_hip_solve_refined_dev.restype = C.c_int
     lib.spllt_hip_release_refine.argtypes = [vp]
     lib.spllt_hip_release_refine.restype = C.c_int
+    lib.spllt_hip_updown.argtypes = [vp, C.c_int, ip, ip, dp, C.c_int]
+    lib.spllt_hip_updown.restype = C.c_int
+    lib.spllt_hip_updown_plan.argtypes = [vp, C.c_int, ip, ip, C.POINTER(C.c_int32), C.c_int64]
+    lib.spllt_hip_updown_plan.restype = C.c_int64
+    lib.spllt_hip_updown_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.spllt_hip_updown_info.restype = C.c_int
+    lib.spllt_hip_updown_time.argtypes = [vp, dp]
+    lib.spllt_hip_updown_time.restype = C.c_int
     lib.spllt_hip_profile.argtypes = [vp, dp, C.c_int, C.POINTER(C.c_float), C.c_int]
     lib.spllt_hip_profile.restype = C.c_int
     lib.spllt_hip_profile_in_program.argtypes = [vp, dp, C.c_int, C.POINTER(C.c_float), C.c_int]

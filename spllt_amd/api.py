@@ -485,6 +485,64 @@ class Factorization:
             raise SplltError("spllt_hip_release_refine", rc, self.last_error())
         return self
 
+    # ---- low-rank update / downdate ----------------------------------------------
+    def _updown_columns(self, W, where):
+        """W (scipy sparse n x k, a dense vector of length n or a dense n x k array; zeros dropped) as the
+        1-based CSC arrays of the C interface"""
+        import scipy.sparse as sp
+        if not sp.issparse(W):
+            W = np.asarray(W, dtype=np.float64)
+            if W.ndim == 1:
+                W = W.reshape(-1, 1)
+            if W.ndim != 2:
+                raise SplltError(where, -10, "W must be a vector or an n x k matrix")
+        if W.shape[0] != self.n:
+            raise SplltError(where, -10, f"W has {W.shape[0]} rows, n = {self.n}")
+        W = sp.csc_matrix(W, dtype=np.float64)
+        W.sum_duplicates()
+        W.eliminate_zeros()
+        W.sort_indices()
+        return (W.shape[1], np.ascontiguousarray(W.indptr + 1, dtype=np.int32),
+                np.ascontiguousarray(np.append(W.indices + 1, 0), dtype=np.int32),
+                np.ascontiguousarray(np.append(W.data, 0.0), dtype=np.float64))
+
+    def update(self, W, downdate=False):
+        """spllt_hip_updown: the factor of A + W W^T (downdate: A - W W^T) in place of the current one; the
+        pattern of every column of W must be a clique of the analysed matrix (include/spllt_hip.h).  A downdate
+        that is not positive definite raises with flag -20 and leaves the handle without a factor until the
+        next factor()."""
+        k, ptr, row, val = self._updown_columns(W, "spllt_hip_updown")
+        rc = self.lib.spllt_hip_updown(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), -1 if downdate else 1)
+        if rc < 0:
+            raise SplltError("spllt_hip_updown", rc, self.last_error())
+        return self
+
+    def updown_plan(self, W):
+        """spllt_hip_updown_plan: the block columns update(W) would visit, ascending (needs no device)"""
+        k, ptr, row, _ = self._updown_columns(W, "spllt_hip_updown_plan")
+        cnt = self.lib.spllt_hip_updown_plan(self.fkeep, k, _ip(ptr), _ip(row), None, 0)
+        if cnt < 0:
+            raise SplltError("spllt_hip_updown_plan", int(cnt), self.last_error())
+        out = np.zeros(max(cnt, 1), dtype=np.int32)
+        self.lib.spllt_hip_updown_plan(self.fkeep, k, _ip(ptr), _ip(row), out.ctypes.data_as(C.POINTER(C.c_int32)), cnt)
+        return out[:cnt]
+
+    def updown_info(self):
+        """of the last update(): block columns visited, entries of L in them, kernel launches, passes"""
+        out = np.zeros(4, dtype=np.int64)
+        rc = self.lib.spllt_hip_updown_info(self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        if rc < 0:
+            raise SplltError("spllt_hip_updown_info", rc, self.last_error())
+        return dict(zip(("bcols", "entries", "launches", "passes"), (int(v) for v in out)))
+
+    def updown_device_ms(self):
+        """spllt_hip_updown_time: device time of the last update(), first scatter to last kernel"""
+        v = C.c_double()
+        rc = self.lib.spllt_hip_updown_time(self.fkeep, C.byref(v))
+        if rc < 0:
+            raise SplltError("spllt_hip_updown_time", rc, self.last_error())
+        return v.value
+
     def matvec_tables(self):
         """the operator of the refined solves: (rowptr int64, col int32, src int32) of the full CSR of
         P A P^T in pivot order ("matvec_*" of spllt_hip_program_get); needs no device"""

@@ -99,10 +99,13 @@ int do_wait(Fkeep* f) {
   return f->last_flag;
 }
 
+// nothing factorized yet, or a failed downdate left the factor invalid (spllt_hip_updown)
+bool no_factor(const Fkeep* f) { return !f->eng || !f->eng->factor_valid(); }
+
 int ensure_hostL(Fkeep* f) {
   do_wait(f);
   if (f->last_flag) return f->last_flag;
-  if (!f->eng) return SPLLT_ERROR_PARAMETER;
+  if (no_factor(f)) return SPLLT_ERROR_PARAMETER;
   if (!f->hostL_valid) {
     f->hostL.resize((size_t)f->S->arena);
     int rc = f->eng->download(f->hostL.data(), f->S->arena);
@@ -399,7 +402,7 @@ void spllt_solve(void* fkeep, spllt_options_t* options, int* order, int nrhs, do
   }
   // Solve on the device-resident factor (no D2H of L).
   int rc = do_wait(f);
-  if (rc == 0 && !f->eng) rc = SPLLT_ERROR_PARAMETER;  // nothing factorized yet
+  if (rc == 0 && no_factor(f)) rc = SPLLT_ERROR_PARAMETER;  // nothing factorized yet
   if (rc) { if (info) info->flag = rc; return; }
   if (f->eo.nranks > 1 && !f->eng->has_communicator()) {
     // (with spllt_hip_set_communicator the engine runs the two all-reduces itself, below)
@@ -421,7 +424,7 @@ int spllt_hip_solve_dev(void* fkeep, void* y_dev, int nrhs, int job, int phase) 
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->S || !y_dev) return SPLLT_ERROR_PARAMETER;
   int rc = do_wait(f);
-  if (rc == 0 && !f->eng) rc = SPLLT_ERROR_PARAMETER;  // nothing factorized yet
+  if (rc == 0 && no_factor(f)) rc = SPLLT_ERROR_PARAMETER;  // nothing factorized yet
   if (rc) return rc;
   return f->eng->solve_dev(static_cast<double*>(y_dev), nrhs, job, phase);
 }
@@ -795,7 +798,7 @@ static int solve_many_engine(Fkeep* f, const char* what, int nrhs, const void* x
   }
   int rc = do_wait(f);
   if (rc) return rc;
-  if (!f->eng) {
+  if (no_factor(f)) {
     f->last_error = std::string(what) + ": nothing has been factorized on this handle";
     return SPLLT_ERROR_PARAMETER;
   }
@@ -1036,6 +1039,65 @@ int spllt_hip_release_refine(void* fkeep) {
   return rc ? refine_fail(f, rc) : 0;
 }
 
+// ---- low-rank update / downdate of the factor ------------------------------------------------------
+int64_t spllt_hip_updown_plan(void* fkeep, int k, const int* wptr, const int* wrow, int32_t* bcols, int64_t capacity) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  std::vector<int> plan;
+  std::string why;
+  if (build_updown_plan(*f->S, k, wptr, wrow, plan, nullptr, &why)) return batch_param_error(f, "spllt_hip_updown_plan", why.c_str());
+  return copy_out(plan, bcols, capacity);
+}
+
+int spllt_hip_updown(void* fkeep, int k, const int* wptr, const int* wrow, const double* wval, int sign) {
+  const char* what = "spllt_hip_updown";
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  // every check that needs no device first: a rejected call touches nothing
+  if (sign != 1 && sign != -1) return batch_param_error(f, what, "sign is not +1 or -1");
+  if (k > 0 && !wval) return batch_param_error(f, what, "the array of values is null");
+  std::vector<int> plan, first;
+  {
+    std::string why;
+    if (build_updown_plan(*f->S, k, wptr, wrow, plan, &first, &why)) return batch_param_error(f, what, why.c_str());
+  }
+  for (int e = 0; k > 0 && e < wptr[k] - 1; ++e)
+    if (!std::isfinite(wval[e])) return batch_param_error(f, what, "a value of W is not finite");
+  if (int rc = batch_partitioned(f, what)) return rc;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (int rc = do_wait(f)) return rc;
+  if (!f->eng) {
+    // no factorization yet: an engine only to tell "no device" from "nothing factorized"
+    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
+    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
+    f->eng->set_exchange_buffer(f->xbuf);
+  }
+  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
+  if (no_factor(f) || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
+  const int rc = f->eng->updown(k, wptr, wrow, wval, sign, plan, first);
+  f->hostL_valid = false;
+  if (rc) {
+    if (!f->eng->updown_error().empty()) f->last_error = f->eng->updown_error();
+    else if (f->eng->status()) f->last_error = f->eng->error();
+    if (rc == SPLLT_ERROR_NOT_POSDEF) std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
+  }
+  return rc;
+}
+
+int spllt_hip_updown_time(void* fkeep, double* device_ms) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !device_ms) return SPLLT_ERROR_PARAMETER;
+  *device_ms = f->eng ? f->eng->updown_device_ms() : 0.0;
+  return 0;
+}
+
+int spllt_hip_updown_info(void* fkeep, int64_t out[4]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 4; ++i) out[i] = f->eng ? f->eng->updown_info()[i] : 0;
+  return 0;
+}
+
 int spllt_hip_get_factor_batch(void* fkeep, int member, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   const char* what = "spllt_hip_get_factor_batch";
@@ -1180,7 +1242,7 @@ static int selinv_engine(Fkeep* f, const char* what) {
   if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
   int rc = do_wait(f);
   if (rc) return rc;
-  if (!f->eng) {
+  if (no_factor(f)) {
     f->last_error = std::string(what) + ": nothing has been factorized on this handle";
     return SPLLT_ERROR_PARAMETER;
   }

@@ -1283,6 +1283,7 @@ int Engine::factor_async_dev(const double* val_dev, int64_t nnz) {
   if (nnz != S_->nnzA) return -10;
   z_valid_ = false;
   factored_ = true;
+  ud_invalid_ = false;
   double t0 = now_ms();
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipEventRecord(ev0_, stream_), "event");
@@ -1312,6 +1313,7 @@ int Engine::factor_async(const double* val_host, int64_t nnz) {
   if (nnz != S_->nnzA) return -10;
   z_valid_ = false;
   factored_ = true;
+  ud_invalid_ = false;
   double t0 = now_ms();
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipEventRecord(ev0_, stream_), "event");
@@ -2056,6 +2058,139 @@ int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, b
     done += nv;
   }
   return worst;
+}
+
+// ---- low-rank update / downdate ---------------------------------------------------------------------
+// Per pass of up to kUpdownVec columns of W: their entries scattered into the work array, then the block
+// columns of the pass's plan in ascending order, each a generate launch (one workgroup: the diagonal square,
+// the coefficients, the dinv slots) and, where it has rows below the square, an apply launch.  The launches of
+// a sweep depend on each other through the work array: one stream, program order.
+int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, int sign, const std::vector<int>& all,
+                   const std::vector<int>& first) {
+  if (status_) return status_;
+  ud_err_.clear();
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (k < 0 || (k > 0 && (!wptr || !wrow || !wval)) || (sign != 1 && sign != -1) || (int)first.size() != k) return -10;
+  if (pending_) {
+    int rc = wait();
+    if (rc) return rc;
+  }
+  if (!factored_ || ud_invalid_) {
+    ud_err_ = "update: nothing has been factorized on this handle";
+    return -10;
+  }
+  const Symbolic& S = *S_;
+  for (int64_t& v : ud_info_) v = 0;
+  ud_device_ms_ = 0.0;
+  if (all.empty()) return 0;         // k = 0, or every column empty
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve();
+  if (rc) return rc;
+  // the non-empty columns in passes of kUpdownVec; per pass the (position in the work array, value) pairs
+  std::vector<int> cols;
+  for (int v = 0; v < k; ++v)
+    if (first[(size_t)v] >= 0) cols.push_back(v);
+  const int npass = ((int)cols.size() + kUpdownVec - 1) / kUpdownVec;
+  std::vector<int64_t> pos, pass_ptr(1, 0);
+  std::vector<double> val;
+  for (int p = 0; p < npass; ++p) {
+    for (int q = 0; q < kUpdownVec && p * kUpdownVec + q < (int)cols.size(); ++q) {
+      const int v = cols[(size_t)(p * kUpdownVec + q)];
+      for (int e = wptr[v] - 1; e < wptr[v + 1] - 1; ++e) {
+        pos.push_back((int64_t)S.order[(size_t)wrow[e] - 1] * kUpdownVec + q);
+        val.push_back(wval[e]);
+      }
+    }
+    pass_ptr.push_back((int64_t)pos.size());
+  }
+  int maxw = 1;
+  for (const BlockCol& B : S.bcols) maxw = std::max(maxw, B.width);
+  const size_t wb = sizeof(double) * kUpdownVec * (size_t)std::max(1, S.n);
+  const size_t cb = sizeof(double) * ((size_t)maxw * kUpdownVec * 3 + 2);
+  const size_t pb = sizeof(int64_t) * pos.size(), vb = sizeof(double) * val.size();
+  int64_t* d_pos = nullptr;
+  double* d_val = nullptr;
+  {
+    // a failure leaves the factor and every solve usable, and nothing of this call allocated
+    const bool had = d_udW_ != nullptr;
+    hipError_t e = hipSuccess;
+    if (!had) {
+      e = dalloc((void**)&d_udW_, wb);
+      if (e == hipSuccess) e = dalloc((void**)&d_udcoef_, cb);
+      if (e == hipSuccess) e = hipMemsetAsync(d_udW_, 0, wb, stream_);
+    }
+    if (e == hipSuccess) e = dalloc((void**)&d_pos, pb);
+    if (e == hipSuccess) e = dalloc((void**)&d_val, vb);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pos, pos.data(), pb, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_val, val.data(), vb, hipMemcpyHostToDevice, stream_);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      (void)sync_stream(stream_, "update staging");
+      if (d_val) release_buffer(d_val);
+      if (d_pos) release_buffer(d_pos);
+      if (!had) {
+        if (d_udcoef_) release_buffer(d_udcoef_);
+        if (d_udW_) release_buffer(d_udW_);
+        d_udW_ = d_udcoef_ = nullptr;
+      }
+      ud_err_ = "update: not enough device memory for the work array (" + std::to_string(wb >> 10) +
+                " KiB), the coefficient scratch and the entries of W: " + hipGetErrorString(e);
+      return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
+    }
+  }
+  int* d_flag = reinterpret_cast<int*>(d_udcoef_ + (size_t)maxw * kUpdownVec * 3);
+  int64_t launches = 0;
+  std::vector<int> plan;
+  for (int p = 0; p < npass; ++p) {
+    const int c0 = p * kUpdownVec, nc = std::min(kUpdownVec, (int)cols.size() - c0);
+    // the plan of this pass's columns (a subset of `all`)
+    std::vector<int> pf;
+    for (int q = 0; q < nc; ++q) pf.push_back(first[(size_t)cols[(size_t)(c0 + q)]]);
+    updown_paths(S, pf.data(), nc, plan);
+    if (p == 0) (void)hipEventRecord(ev0_, stream_);
+    launch_updown_scatter(stream_, d_pos + pass_ptr[(size_t)p], d_val + pass_ptr[(size_t)p],
+                          pass_ptr[(size_t)p + 1] - pass_ptr[(size_t)p], d_udW_, d_flag, p == 0);
+    ++launches;
+    for (int b : plan) {
+      const SolveUnit& u = sprog_.units[(size_t)b];
+      launch_updown_gen(stream_, u, d_L_, d_dinv_, d_udW_, d_udcoef_, d_flag, sign, nc);
+      ++launches;
+      if (u.nrow > u.w) {
+        launch_updown_apply(stream_, u, d_L_, d_rlist_, d_udW_, d_udcoef_, sign, nc);
+        ++launches;
+      }
+    }
+  }
+  int flag = INT_MAX;
+  hipError_t le = hipGetLastError();
+  if (le == hipSuccess) le = hipEventRecord(ev1_, stream_);
+  if (le == hipSuccess) le = hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, stream_);
+  rc = sync_stream(stream_, "update sync");
+  release_buffer(d_val);
+  release_buffer(d_pos);
+  z_valid_ = false;
+  if (le != hipSuccess || rc) {
+    // the sweep did not finish: the arena is half modified and the work array may not be zero
+    ud_invalid_ = true;
+    if (d_udW_) release_buffer(d_udW_);
+    if (d_udcoef_) release_buffer(d_udcoef_);
+    d_udW_ = d_udcoef_ = nullptr;
+    return le != hipSuccess ? fail(kErrHip, "update launch", le) : rc;
+  }
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) ud_device_ms_ = ms;
+  ud_info_[0] = (int64_t)all.size();
+  for (int b : all) ud_info_[1] += (int64_t)S.bcols[(size_t)b].nrow * S.bcols[(size_t)b].width;
+  ud_info_[2] = launches;
+  ud_info_[3] = npass;
+  if (flag != INT_MAX) {
+    npd_col_ = flag - 1;
+    ud_invalid_ = true;
+    ud_err_ = "downdate: the modified matrix is not positive definite (pivot column " + std::to_string(flag) +
+              " in elimination order); the factor is invalid until the next factorization";
+    return kErrNotPosDef;
+  }
+  return 0;
 }
 
 // ---- batched factorization ------------------------------------------------------------------------

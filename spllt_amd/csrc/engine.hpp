@@ -151,8 +151,25 @@ class Engine {
   int solve_refined(const double* val, int nrhs, double* x, int64_t ldx, bool dev, int method, double tol,
                     int max_iter, int* iterations, double* error);
   int release_refine();     // operator tables and work vectors back to the pool
-  bool factored() const { return factored_; }
+  bool factored() const { return factored_ && !ud_invalid_; }
   const std::string& refine_error() const { return rf_err_; }
+  // ---- low-rank update / downdate (updown.hip, single GPU): the factor of P (A + sign W W^T) P^T in place of
+  // the current one, same layout, the dinv slots of the visited block columns rebuilt -- every solve then works
+  // on the modified factor.  W: k columns, CSC, 1-based, user variable order; sign +1 / -1.  Every check
+  // (build_updown_plan, by the caller) happens before anything is enqueued; the call returns with the stream drained.  A
+  // success marks the selected inverse stale.  A downdate that meets a non-positive pivot returns -20 and
+  // leaves the factor INVALID (factor_valid() false) until the next factorization.  The work array (n x 8
+  // doubles, zero between calls) and the coefficient scratch stay with the engine; the staged entries of W
+  // are returned before the call ends.
+  // all / first: the plan and the first pivot positions of build_updown_plan for these columns (the caller has
+  // validated them: schedule.hpp).  A launch or a wait that fails mid-sweep leaves the factor invalid as well.
+  int updown(int k, const int* wptr, const int* wrow, const double* wval, int sign, const std::vector<int>& all,
+             const std::vector<int>& first);
+  double updown_device_ms() const { return ud_device_ms_; }   // last updown(): first scatter to last kernel, HIP events
+  bool factor_valid() const { return !ud_invalid_; }     // false: a failed downdate destroyed the factor
+  // of the last updown(): block columns visited, entries of L in them, kernel launches, passes
+  const int64_t* updown_info() const { return ud_info_; }
+  const std::string& updown_error() const { return ud_err_; }
   // ---- selected inversion (selinv.hip, single GPU): Z = (P A P^T)^-1 on the pattern of L, in a
   // second arena with L's layout.  Computed from the current factor (after wait()); a later
   // factorization marks it stale: the readers below then fail instead of returning old numbers.
@@ -355,6 +372,13 @@ class Engine {
   double* d_rfds_ = nullptr;       // device scalars (refine.hpp)
   int* d_rfis_ = nullptr;
   double* d_rfval_ = nullptr;      // nnz doubles: the values of a host entry point
+  // update / downdate: work array and coefficient scratch (taken on first use, both or neither)
+  std::string ud_err_;
+  bool ud_invalid_ = false;
+  int64_t ud_info_[4] = {0, 0, 0, 0};
+  double ud_device_ms_ = 0.0;
+  double* d_udW_ = nullptr;        // n x kUpdownVec doubles, zero between calls
+  double* d_udcoef_ = nullptr;     // (widest block column) x kUpdownVec x 3 doubles + the flag word
   // selected inversion (tables uploaded once per pattern, on first use)
   int prepare_selinv();
   void release_buffer(void* p);

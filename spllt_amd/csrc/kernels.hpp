@@ -164,6 +164,24 @@ int launch_batch_selinv_diag_gather(hipStream_t st, const BatchSelinvView& s, co
 // out[b * ldout + map_src[e]] = Z_b[map_dst[e]]  (A_b^-1 at the entries of the analysed pattern, in the order of val)
 int launch_batch_selinv_pattern(hipStream_t st, const BatchSelinvView& s, const int64_t* map_dst, const int64_t* map_src,
                                 int64_t nmap, double* out, int64_t ldout);
+// ---- low-rank update / downdate of the factor (updown.hip) ------------------------------------------
+// Wd: the work array, n x kUpdownVec doubles, Wd[p * kUpdownVec + q] for pivot position p and vector q of the
+// pass, zero between calls.  coef: (widest block column) x kUpdownVec x 3 doubles, the (c, t, 1 / c) of the
+// block column in flight.  flag: INT_MAX, or the smallest pivot position + 1 at which a downdate failed.
+constexpr int kUpdownVec = 8;      // vectors per pass
+constexpr int kUpdownRows = 256;   // rows per workgroup of the apply kernel, one per thread
+constexpr int kUpdownChunk = 16;   // columns of L staged through LDS at a time
+// Wd[pos[i]] = val[i]; reset_flag: *flag = INT_MAX as well
+void launch_updown_scatter(hipStream_t st, const int64_t* pos, const double* val, int64_t count, double* Wd, int* flag,
+                           bool reset_flag);
+// the diagonal square of block column u (host copy of its SolveUnit; pw = cb <= kPanelMax): coefficients,
+// rotations, the dinv slots of its panels; one workgroup
+// nv: the vectors of the pass (kernels for 1, 2, 4 and 8: the next of these)
+void launch_updown_gen(hipStream_t st, const SolveUnit& u, double* L, double* dinv, double* Wd, double* coef, int* flag,
+                       int sign, int nv);
+// the rows below the square (nothing is launched when there are none)
+void launch_updown_apply(hipStream_t st, const SolveUnit& u, double* L, const int* rlist, double* Wd, const double* coef,
+                         int sign, int nv);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 

@@ -1625,4 +1625,66 @@ int build_selinv_program(const Symbolic& S, int pw, int cb, SelinvProgram& P) {
   return 0;
 }
 
+// ---- low-rank update / downdate: the block columns a sweep visits -------------------------------------
+void updown_paths(const Symbolic& S, const int* first, int count, std::vector<int>& bcols) {
+  bcols.clear();
+  std::vector<char> visit((size_t)S.nbcol(), 0), full((size_t)S.nnodes, 0);
+  for (int v = 0; v < count; ++v) {
+    const int j = first[v];
+    if (j < 0) continue;
+    const int s = S.snode_of[(size_t)j];
+    if (full[(size_t)s]) continue;
+    for (int b = S.node_bcol0[s] + (j - S.sptr[s]) / S.nb; b < S.node_bcol0[s + 1]; ++b) visit[(size_t)b] = 1;
+    if (j == S.sptr[s]) full[(size_t)s] = 1;
+    for (int a = S.sparent[s]; a < S.nnodes && !full[(size_t)a]; a = S.sparent[a]) {
+      full[(size_t)a] = 1;
+      for (int b = S.node_bcol0[a]; b < S.node_bcol0[a + 1]; ++b) visit[(size_t)b] = 1;
+    }
+  }
+  for (int b = 0; b < S.nbcol(); ++b)
+    if (visit[(size_t)b]) bcols.push_back(b);
+}
+
+int build_updown_plan(const Symbolic& S, int k, const int* wptr, const int* wrow, std::vector<int>& bcols,
+                      std::vector<int>* first_pos, std::string* why) {
+  bcols.clear();
+  if (first_pos) first_pos->assign((size_t)std::max(k, 0), -1);
+  auto bad = [&](const std::string& what) {
+    if (why) *why = what;
+    return -10;
+  };
+  if (k < 0) return bad("k < 0");
+  if (k == 0) return 0;
+  if (!wptr || !wrow) return bad("a column pointer or row index array is null");
+  if (wptr[0] < 1) return bad("wptr[0] < 1 (the arrays are 1-based)");
+  std::vector<int> firsts((size_t)k, -1);
+  for (int v = 0; v < k; ++v) {
+    const std::string col = "column " + std::to_string(v + 1);
+    if (wptr[v + 1] < wptr[v]) return bad(col + ": the column pointers decrease");
+    const int lo = wptr[v] - 1, hi = wptr[v + 1] - 1;
+    if (lo == hi) continue;
+    int j = S.n;
+    for (int e = lo; e < hi; ++e) {
+      const int r = wrow[e];
+      if (r < 1 || r > S.n) return bad(col + ": row index " + std::to_string(r) + " is outside [1, n]");
+      if (e > lo && r <= wrow[e - 1]) return bad(col + ": the row indices are not strictly increasing");
+      j = std::min(j, S.order[(size_t)r - 1]);
+    }
+    const int s = S.snode_of[(size_t)j];
+    const int* rows = S.rows(s);
+    const int nrow = S.nrow(s);
+    for (int e = lo; e < hi; ++e) {
+      const int p = S.order[(size_t)wrow[e] - 1];
+      if (!std::binary_search(rows, rows + nrow, p))
+        return bad(col + ": not admissible -- variable " + std::to_string(wrow[e]) + " (pivot position " +
+                   std::to_string(p + 1) + ") is not in the row structure of the supernode of the column's first pivot (" +
+                   std::to_string(j + 1) + "): the pattern of a column must be a clique of the analysed matrix");
+    }
+    firsts[(size_t)v] = j;
+  }
+  updown_paths(S, firsts.data(), k, bcols);
+  if (first_pos) *first_pos = firsts;
+  return 0;
+}
+
 }  // namespace spx

@@ -17,6 +17,7 @@
 // Everything here is plain C++ (no HIP) so that it can be unit-tested on CPU.
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "symbolic.hpp"
@@ -479,5 +480,22 @@ struct SelinvProgram {
 
 // 0, or -1 when a node's rows below its columns are not all rows of their ancestors (no Z_RR storage)
 int build_selinv_program(const Symbolic& S, int pw, int cb, SelinvProgram& P);
+
+// ---------------------------------------------------------------------------
+// Low-rank update / downdate of the factor, A' = A + sign W W^T (updown.hip): the plan.  W: k sparse columns,
+// CSC, 1-based, in the user's variable order (as ptr / row of the analyse).  A column is admissible when, with
+// j the smallest pivot position of its pattern and s = snode_of[j], every pivot position of the pattern is a
+// row of node s (at or after j, as j is the smallest).  The rows of a node below its own columns are rows of
+// its parent, so the check at the first node covers the whole path.  The column then touches the block column
+// of s that holds j, the later block columns of s, and every block column of every ancestor of s; the plan is
+// the union over the columns, ascending -- a topological order of the sweep.
+// Returns 0, or -10 with *why: a null array, k < 0, a column pointer that decreases, a row index outside
+// [1, n], rows of a column not strictly increasing, a column that is not admissible.  first_pos (optional):
+// per column its smallest pivot position, -1 for an empty column.  Needs no device.
+// ---------------------------------------------------------------------------
+int build_updown_plan(const Symbolic& S, int k, const int* wptr, const int* wrow, std::vector<int>& bcols,
+                      std::vector<int>* first_pos, std::string* why);
+// the block columns on the paths from the pivot positions first[0 .. count) (-1: none) to the root, ascending
+void updown_paths(const Symbolic& S, const int* first, int count, std::vector<int>& bcols);
 
 }  // namespace spx
