@@ -503,18 +503,23 @@ __device__ __forceinline__ double a_sub(double a, double b) {
   asm volatile("v_add_f64 %0, %1, -%2" : "=v"(o) : "v"(a), "v"(b));
   return o;
 }
+__device__ __forceinline__ double a_neg0(double a) {                   // 0 - a
+  double o;
+  asm volatile("v_add_f64 %0, 0, -%1" : "=v"(o) : "v"(a));
+  return o;
+}
 // 16 x 16 Cholesky + inverse in registers.  Lane i of every row of 16 lanes holds row i of the
 // block (row[c]; four identical copies per wave); on return row[c] = L[i][c] for c <= i
 // (garbage above the diagonal) and wx[c] = W[c][i], column i of W = inv(L).  Returns the first
 // failed pivot (1 << 30: none); a failed pivot is not repaired (the block fills with NaNs or
 // garbage and the factorization is reported as failed).
 __device__ __forceinline__ int chol16_regs(double (&row)[16], double (&wx)[16], int lr) {
-  double wacc[16], delta[16];
+  // wacc[c] starts at -delta_ic instead of 0 and Wu[j][c] = 0 - wacc[j]: in the one lane where
+  // delta is 1 every product added to wacc is an exact zero (Wu is lower triangular), so the
+  // value is the delta - wacc of a separate delta[16], bit for bit, without its 32 registers
+  double wacc[16];
 #pragma unroll
-  for (int c = 0; c < 16; ++c) {
-    wacc[c] = 0.0;
-    delta[c] = (lr == c) ? 1.0 : 0.0;
-  }
+  for (int c = 0; c < 16; ++c) wacc[c] = (lr == c) ? -1.0 : 0.0;
   double dn = bcast_row<0>(row[0]);
   double dmine = dn;
   double y = rcp_newton(dn);
@@ -538,7 +543,7 @@ __device__ __forceinline__ int chol16_regs(double (&row)[16], double (&wx)[16], 
           } else {
             if constexpr (i == nR) {
               // Wu[j][c] = delta_jc - sum_{k<j} l_jk Wu[k][c]
-              wxj = a_sub(delta[j], wacc[j]);
+              wxj = a_neg0(wacc[j]);
               z = a_mul(wxj, y);
             }
             fmac_bc<j + 1 + i - nR>(wacc[j + 1 + i - nR], row[j], z);
@@ -561,7 +566,7 @@ __device__ __forceinline__ int chol16_regs(double (&row)[16], double (&wx)[16], 
       wx[j] = wxj;
       y = yn;
     } else {
-      wx[j] = delta[j] - wacc[j];
+      wx[j] = a_neg0(wacc[j]);
     }
   });
   STAMP2(true, 22);
@@ -591,12 +596,14 @@ __device__ __forceinline__ void potrf64_v2(PotrfShared& sh, double* __restrict__
   double (&T)[64 * TLD] = sh.T;
   double (&X)[64 * TLD] = sh.X;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, w = tid >> 6, lq = lane >> 4, lr = lane & 15;
+  // (the wave's number as a scalar: its role is a scalar branch, and what depends on it -- block
+  // indices, trip counts, LDS offsets -- stays out of the vector registers)
+  const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), lq = lane >> 4, lr = lane & 15;
   const int nblk = (n + 15) >> 4;
   const bool st_l = !(flags & 2), st_i = !(flags & 4), x_lower = (flags & 8) != 0;
   STAMP(0);
   // identity-padded lower triangle into LDS (see potrf64_body)
-  const int lw = tid >> 6, lc = tid & 63;
+  const int lw = w, lc = tid & 63;
   if (flags & 16) {
     // the caller has put the (identity-padded, lower) block into sh.T itself: only X is cleared
     if (tid < 256) {
@@ -704,8 +711,26 @@ __device__ __forceinline__ void potrf64_v2(PotrfShared& sh, double* __restrict__
     if (st_i && x_lower)
       for (int gi = ws; gi < 2; gi += ns) store_rows8(D, ldd, X, S * 16 + gi * 8, S * 16);
   };
-  for (int J = 0; J < nblk; ++J) {
-    if (w == 0) {
+  // blocks below the diagonal block of step J: X_IJ = A_IJ inv(D_J)^T
+  auto solve_below = [&](int J) {
+    if (w < 4 && J + 1 + w < nblk) {
+      const int I = J + 1 + w;
+      d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const double a = T[(I * 16 + lr) * TLD + J * 16 + 4 * t + lq];
+        const double b = X[(J * 16 + lr) * TLD + J * 16 + 4 * t + lq];     // W_JJ[lr][k]
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+      }
+      st_c(T, I * 16, J * 16, lane, acc);
+    }
+  };
+  // One loop per ROLE (w is a scalar: a real branch), each with the same two barriers per step:
+  // registers are allotted per kernel, to the larger of the two paths, and in one shared loop
+  // everything the shadow keeps across the steps (Xpre, its store addresses) stayed allotted
+  // all through wave 0's register Cholesky, which alone holds ~100
+  if (w == 0) {
+    for (int J = 0; J < nblk; ++J) {
       if (J > 0) upd_block(J, J, J - 1);                  // the only update on the critical path
       double row[16], wx[16];
       STAMP2(true, 20);
@@ -727,35 +752,28 @@ __device__ __forceinline__ void potrf64_v2(PotrfShared& sh, double* __restrict__
         for (int c = 0; c < 16; ++c) dst[c * TLD] = wx[c];
       }
       STAMP2(true, 25);
-    } else if (w < 4 && J > 0) {
-      shadow(J - 1, w - 1, 3, true);
+      __syncthreads();
+      STAMP(2 + 2 * J);
+      solve_below(J);
+      __syncthreads();
+      STAMP(3 + 2 * J);
     }
-    __syncthreads();
-    STAMP(2 + 2 * J);
-    // blocks below: X_IJ = A_IJ inv(D_J)^T
-    if (w < 4 && J + 1 + w < nblk) {
-      const int I = J + 1 + w;
-      d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double a = T[(I * 16 + lr) * TLD + J * 16 + 4 * t + lq];
-        const double b = X[(J * 16 + lr) * TLD + J * 16 + 4 * t + lq];     // W_JJ[lr][k]
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-      }
-      st_c(T, I * 16, J * 16, lane, acc);
-    }
-    __syncthreads();
-    STAMP(3 + 2 * J);
-  }
-  // the last step's shadow: the last block row of the inverse, the last diagonal blocks (wave 0
-  // takes the stores of its own blocks, waves 1-3 finish their block of the inverse)
-  if (w > 0 && w < 4) {
-    const int S = nblk - 1, K = w - 1;
-    if (K < S) shadow(S, K, 3, false);                    // (no updates are left; wave 0 stores)
-  } else if (w == 0) {
+    // wave 0 takes the stores of the last diagonal blocks
     const int S = nblk - 1;
     if (st_l) { store_rows8(A, ld, T, S * 16, S * 16); store_rows8(A, ld, T, S * 16 + 8, S * 16); }
     if (st_i && x_lower) { store_rows8(D, ldd, X, S * 16, S * 16); store_rows8(D, ldd, X, S * 16 + 8, S * 16); }
+  } else {
+    for (int J = 0; J < nblk; ++J) {
+      if (w < 4 && J > 0) shadow(J - 1, w - 1, 3, true);
+      __syncthreads();
+      solve_below(J);
+      __syncthreads();
+    }
+    // the last step's shadow: the last block row of the inverse (no updates are left)
+    if (w < 4) {
+      const int S = nblk - 1, K = w - 1;
+      if (K < S) shadow(S, K, 3, false);
+    }
   }
   STAMP(10);
   if (st_i && !x_lower) {
@@ -798,20 +816,27 @@ __global__ __launch_bounds__(256) void k_potrf_panel(const PotrfUnit* __restrict
 // One step of the panel chain (ChainUnit), one workgroup per block column: panel [c0, c0+pn)
 // of a block column (a11 spllt_factor_diag_block): L_pp = chol(A_pp) and inv(L_pp) into the
 // dinv scratch, which turns the triangular solve of the rows below into a product
-// (k_update, TRSM mode) and is what the solve phase applies.  256 threads and static LDS: two
+// (k_update, TRSM mode) and is what the solve phase applies.  256 threads and 75 KB of LDS: two
 // workgroups per CU -- the leaf levels of a large problem are thousands of such panels and run
 // at the rate the chip retires these workgroups.
+// Register budget: at the top levels a launch is ONE workgroup that has to find room on a CU
+// which the update streams keep full.  A retiring k_update<64,16,2,2> workgroup frees 96 + 32 =
+// 128 registers per lane per SIMD, so the kernel is held to 128 (4 waves per SIMD in the launch
+// bounds), without scratch; the build checks it (scripts/check_kernel_budget.py).  The LDS is
+// dynamic for that reason only: with 75 KB of static LDS the compiler knows that no more than two
+// waves per SIMD can be resident and ignores the bound (162 + 16 registers).
 // (Round 2 also had a 768-thread k_chain_panel that walked diagonal sub-tiles wider than a
 // panel -- solve and update of the sub-tile's rows inside the chain kernel, a k_winv kernel
 // for the left part of the rows below -- selected by a "chain block" knob.  It was slower at
 // every setting and every one of the three hangs this repository has
 // seen on the GPU box happened in a case that used it; it has been removed.)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_chain_potrf(const ChainUnit* __restrict__ units,
-                                                     double* __restrict__ L,
-                                                     double* __restrict__ dinv,
-                                                     int* __restrict__ flag, const ChainUnit u0) {
-  __shared__ PotrfShared sh;
+__global__ __launch_bounds__(256, 4) void k_chain_potrf(const ChainUnit* __restrict__ units,
+                                                        double* __restrict__ L,
+                                                        double* __restrict__ dinv,
+                                                        int* __restrict__ flag, const ChainUnit u0) {
+  extern __shared__ __attribute__((aligned(16))) double chain_smem[];
+  PotrfShared& sh = *reinterpret_cast<PotrfShared*>(chain_smem);
   __builtin_amdgcn_s_setprio(3);
   const ChainUnit u = blockIdx.x == 0 ? u0 : units[blockIdx.x];
   const int cq = u.c0 - u.cs;
@@ -2765,7 +2790,17 @@ void launch_potrf(hipStream_t st, const PotrfUnit* units, int64_t count, double*
 void launch_chain_panel(const LaunchSink& st, const ChainUnit* units, int64_t count, double* L, double* dinv,
                         int* flag, const ChainUnit& unit0) {
   if (count <= 0) return;
-  emit(st, k_chain_potrf, dim3((unsigned)count), dim3(256), 0, units, L, dinv, flag, unit0);
+  // PotrfShared as dynamic LDS (see k_chain_potrf): more than the default 64 KB per workgroup
+  static_assert(sizeof(PotrfShared) <= 80 * 1024, "k_chain_potrf: LDS budget (scripts/check_kernel_budget.py)");
+  const unsigned lds = (unsigned)sizeof(PotrfShared);
+  thread_local int attr_dev = -1;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != attr_dev) {
+    (void)hipFuncSetAttribute((const void*)k_chain_potrf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_dev = dev;
+  }
+  emit(st, k_chain_potrf, dim3((unsigned)count), dim3(256), lds, units, L, dinv, flag, unit0);
 }
 
 void launch_chain_block(const LaunchSink& st, const ChainUnit* units, int64_t count, double* L, double* dinv,
