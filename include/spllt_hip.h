@@ -247,7 +247,8 @@ int spllt_hip_solve_dev(void *fkeep, void *y_dev, int nrhs, int job, int phase);
  * device.  The work is ordered on the engine's stream (spllt_hip_engine_stream) and has finished
  * when the call returns.  A later factorization on the handle is picked up.
  * Reproducibility: the row strips add into the right-hand sides with fp64 atomic adds, like
- * spllt_solve: two runs agree to rounding, not bit for bit.
+ * spllt_solve: two runs agree to rounding, not bit for bit (spllt_hip_solve_repro below is the solve that
+ * repeats bit for bit; spllt_hip_set_reproducible_solve does not change this entry point).
  * Errors: null pointer, nrhs < 0, ldx < n, bad job, nothing factorized yet -> SPLLT_ERROR_PARAMETER;
  * partitioned factor (spllt_hip_set_partition with nranks > 1) -> SPLLT_ERROR_UNIMPLEMENTED; no
  * device memory for the workspace -> SPLLT_ERROR_ALLOCATION (the factor and spllt_solve stay
@@ -255,6 +256,48 @@ int spllt_hip_solve_dev(void *fkeep, void *y_dev, int nrhs, int job, int phase);
 int spllt_hip_solve_many(void *fkeep, int nrhs, double *x_host, int64_t ldx, int job);      /* host, user order */
 int spllt_hip_solve_many_dev(void *fkeep, int nrhs, double *x_dev, int64_t ldx, int job,
                              int pivot_order);   /* device; 0 = user order, 1 = pivot order as spllt_hip_solve_dev */
+/* ---- reproducible solve (single GPU) --------------------------------------------
+ * The substitution of spllt_solve -- the same block columns, the same (block column, strip) tiles, the same
+ * launch order -- with no atomic add: a row strip STORES its products into a scratch vector, and the launch
+ * that solves with a diagonal tile first subtracts the stored products from its rows in an order fixed by
+ * tables built from the symbolic structure alone (spllt_hip_program_get, all int64, offsets in doubles
+ * inside the scratch of ONE vector):
+ *   "rsolve_fslot"  per block column b: slot of the product for its first row below the diagonal tile
+ *                   (block column row w); rows w .. nrow-1 take consecutive slots
+ *   "rsolve_frows"  scalar: slots in all, the sum of nrow - w
+ *   "rsolve_gptr"   n + 1, "rsolve_gsrc" frows: for pivot position p, gsrc[gptr[p] .. gptr[p+1]) are the
+ *                   slots subtracted from y[p], ascending by source block column (elimination order).  On the
+ *                   device 16 lanes share a list: lane s adds the entries s, s + 16, ... in that order, the
+ *                   16 sums are combined by a fixed butterfly, the total is subtracted from y[p]
+ *   "rsolve_bslot"  per entry of "solve_tiles": offset of the w column sums the strip produces in the
+ *                   backward sweep; "rsolve_bsize": scalar, their total.  The strips of one block column are
+ *                   consecutive: strip t at "rsolve_bfirst"[b] + t * w (per block column, -1 without rows
+ *                   below); they are subtracted in ascending t.
+ * The promise: the same factor bits and the same right-hand-side bits give the same solution bits -- across
+ * calls, across group sizes (a vector's arithmetic does not depend on how many vectors share its sweep nor
+ * on its position among them), across the host / device / pivot-order entry points, and across handles
+ * with the same analysis and engine settings.  The limit: a bit-identical FACTOR across runs still needs
+ * engine flag 4096 (spllt_hip_set_engine); with the default engine the factor itself varies in its last bits.
+ * Layout, job, nrhs = 0, stream ordering and pickup of a later factorization or spllt_hip_updown as
+ * spllt_hip_solve_many above; vectors are swept 4, 2 or 1 at a time; the permutation between user and pivot
+ * order is a bitwise copy on the device.  On first use the tables, a scratch of 4 * max(rsolve_frows,
+ * rsolve_bsize) doubles and a staging block of 4 n doubles are taken from the device pool and kept until
+ * spllt_hip_release_solve_repro or spllt_deallocate_fkeep.
+ * Errors: null pointer, nrhs < 0, ldx < n, bad job, nothing factorized yet -> SPLLT_ERROR_PARAMETER;
+ * partitioned handle -> SPLLT_ERROR_UNIMPLEMENTED; no device -> SPLLT_ERROR_HIP; no device memory ->
+ * SPLLT_ERROR_ALLOCATION (nothing is kept half-allocated, the factor and every other solve stay usable).
+ * Messages: spllt_hip_last_error.  Debug: spllt_hip_debug("rsolve_poison=1") fills the scratch with NaN
+ * before every sweep ("=0": off), so that a slot read without having been written shows up in the result. */
+int spllt_hip_solve_repro(void *fkeep, int nrhs, double *x_host, int64_t ldx, int job);      /* host, user order */
+int spllt_hip_solve_repro_dev(void *fkeep, int nrhs, double *x_dev, int64_t ldx, int job,
+                              int pivot_order);   /* device; 0 = user order, 1 = pivot order as spllt_hip_solve_dev */
+/* on != 0: spllt_solve (single GPU), spllt_hip_solve_dev(phase = -1) and every M^-1 of
+ * spllt_hip_solve_refined* (for every group size, in sweeps of 4) go through the reproducible path; a
+ * refined solve is then bit-reproducible as a whole.  spllt_hip_solve_many* is NOT affected by the switch.
+ * Returns the PREVIOUS setting (0 / 1) or a negative flag (null handle: SPLLT_ERROR_PARAMETER; switching on
+ * for a partitioned handle: SPLLT_ERROR_UNIMPLEMENTED).  Default 0.  Needs no device. */
+int spllt_hip_set_reproducible_solve(void *fkeep, int on);
+int spllt_hip_release_solve_repro(void *fkeep);   /* tables and scratch back to the pool */
 int spllt_hip_set_exchange_buffer(void *fkeep, void *dev_ptr);
 /* The HIP stream (hipStream_t) every caller-visible operation of this handle is ordered on:
  * spllt_factor ends by packing the exchange buffer on it and spllt_hip_continue starts by
@@ -430,7 +473,8 @@ int     spllt_hip_release_inverse_batch(void *fkeep);
  * spllt_hip_solve_many_dev above; a later factorization on the handle is picked up.  All work is ordered on
  * spllt_hip_engine_stream and finished when a call returns; per iteration one array of 64 doubles is read
  * back.  Reproducibility: products and reductions are bit-reproducible, the solution inherits the fp64
- * atomics of the solves and agrees to rounding only.
+ * atomics of the solves and agrees to rounding only -- unless spllt_hip_set_reproducible_solve is on: M^-1 is
+ * then spllt_hip_solve_repro_dev for every group size and two calls return the same bits and iteration counts.
  * Errors: null pointer, negative count, nnz not the pattern's, ldx / ldy < n, bad method, tol <= 0, nothing
  * factorized yet (refined solve only) -> SPLLT_ERROR_PARAMETER; partitioned handle ->
  * SPLLT_ERROR_UNIMPLEMENTED; no device -> SPLLT_ERROR_HIP; no device memory -> SPLLT_ERROR_ALLOCATION

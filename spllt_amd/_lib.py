@@ -70,6 +70,8 @@ HIP_SYMBOLS = [
     "spllt_hip_matvec", "spllt_hip_matvec_dev", "spllt_hip_solve_refined", "spllt_hip_solve_refined_dev",
     "spllt_hip_release_refine",
     "spllt_hip_updown", "spllt_hip_updown_plan", "spllt_hip_updown_info", "spllt_hip_updown_time",
+    "spllt_hip_solve_repro", "spllt_hip_solve_repro_dev", "spllt_hip_set_reproducible_solve",
+    "spllt_hip_release_solve_repro",
 ]
 
 _lib = None
@@ -164,6 +166,14 @@ def load():
     lib.spllt_hip_solve_many.restype = C.c_int
     lib.spllt_hip_solve_many_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int]
     lib.spllt_hip_solve_many_dev.restype = C.c_int
+    lib.spllt_hip_solve_repro.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int]
+    lib.spllt_hip_solve_repro.restype = C.c_int
+    lib.spllt_hip_solve_repro_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int]
+    lib.spllt_hip_solve_repro_dev.restype = C.c_int
+    lib.spllt_hip_set_reproducible_solve.argtypes = [vp, C.c_int]
+    lib.spllt_hip_set_reproducible_solve.restype = C.c_int
+    lib.spllt_hip_release_solve_repro.argtypes = [vp]
+    lib.spllt_hip_release_solve_repro.restype = C.c_int
     ip = C.POINTER(C.c_int)
     lib.spllt_hip_matvec.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_int64, dp, C.c_int64]
     lib.spllt_hip_matvec.restype = C.c_int

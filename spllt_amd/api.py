@@ -210,6 +210,10 @@ class Factorization:
             return raw.view(np.int64).reshape(-1, 4)
         if name == "solve_split":
             return raw.view(np.int64)
+        if name in ("rsolve_fslot", "rsolve_bfirst", "rsolve_gptr", "rsolve_gsrc", "rsolve_bslot"):
+            return raw.view(np.int64)
+        if name in ("rsolve_frows", "rsolve_bsize"):
+            return int(raw.view(np.int64)[0])
         if name == "selinv_units":
             return raw.view(SELINV_UNIT_DTYPE)
         if name == "selinv_tiles":
@@ -408,6 +412,45 @@ class Factorization:
                                                1 if pivot_order else 0)
         if rc < 0:
             raise SplltError("spllt_hip_solve_many_dev", rc, self.last_error())
+        return self
+
+    # ---- reproducible solve ----------------------------------------------------
+    def solve_reproducible(self, b, job=0):
+        """spllt_hip_solve_repro on a copy of b (n or n x nrhs): the substitution without atomic adds -- the same
+        factor bits and the same b give the same bits of x, whatever the number of columns.  Returns a new
+        F-ordered array, like solve."""
+        x = np.array(b, dtype=np.float64, order="F", copy=True)
+        nrhs = 1 if x.ndim == 1 else x.shape[1]
+        ldx = x.shape[0]
+        rc = self.lib.spllt_hip_solve_repro(self.fkeep, nrhs, _dp(x), ldx, job)
+        if rc < 0:
+            raise SplltError("spllt_hip_solve_repro", rc, self.last_error())
+        return x
+
+    def solve_reproducible_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
+        """spllt_hip_solve_repro_dev: the reproducible solve on device vectors, in place (layout and
+        pivot_order as solve_many_dev)."""
+        if ldx is None:
+            ldx = self.n
+        rc = self.lib.spllt_hip_solve_repro_dev(self.fkeep, nrhs, C.c_void_p(x_dev_ptr), int(ldx), job,
+                                                1 if pivot_order else 0)
+        if rc < 0:
+            raise SplltError("spllt_hip_solve_repro_dev", rc, self.last_error())
+        return self
+
+    def set_reproducible_solve(self, on):
+        """Route solve, solve_dev(phase=-1) and the preconditioner of solve_refined through the reproducible
+        path (solve_many is not affected).  Returns the previous setting."""
+        rc = self.lib.spllt_hip_set_reproducible_solve(self.fkeep, 1 if on else 0)
+        if rc < 0:
+            raise SplltError("spllt_hip_set_reproducible_solve", rc, self.last_error())
+        return bool(rc)
+
+    def release_solve_repro(self):
+        """The tables and the scratch of the reproducible solve back to the device pool."""
+        rc = self.lib.spllt_hip_release_solve_repro(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_solve_repro", rc, self.last_error())
         return self
 
     # ---- refined solves --------------------------------------------------------

@@ -41,6 +41,7 @@ struct Fkeep {
   long worksize = 0;
   double* xbuf = nullptr;  // multi-GPU exchange buffer (caller-owned device memory)
   bool dead = false;       // a submission never returned: the engine belongs to the stuck helper thread
+  bool repro_solve = false;   // spllt_hip_set_reproducible_solve: handed to the engine before every solve
   // the selected-inversion program of spllt_hip_program_get (built once per pattern and panel layout)
   std::shared_ptr<const Symbolic> si_S;
   int si_pw = -1, si_cb = -1, si_rc = 0;
@@ -415,6 +416,7 @@ void spllt_solve(void* fkeep, spllt_options_t* options, int* order, int nrhs, do
     if (info) info->flag = SPLLT_ERROR_UNIMPLEMENTED;
     return;
   }
+  f->eng->set_reproducible_solve(f->repro_solve);
   rc = f->eng->solve(x, nrhs, job);
   if (rc) { if (info) info->flag = rc; return; }
   fill_info(*f->S, info);
@@ -426,6 +428,7 @@ int spllt_hip_solve_dev(void* fkeep, void* y_dev, int nrhs, int job, int phase) 
   int rc = do_wait(f);
   if (rc == 0 && no_factor(f)) rc = SPLLT_ERROR_PARAMETER;  // nothing factorized yet
   if (rc) return rc;
+  f->eng->set_reproducible_solve(f->repro_solve);
   return f->eng->solve_dev(static_cast<double*>(y_dev), nrhs, job, phase);
 }
 
@@ -609,7 +612,8 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 // test hooks of the process-wide "runtime is wedged" state (engine.cpp): "wedge" sets it, "wedged"
 // reads it, "teardown" runs the atexit handler of the pools now; "batch_grid_limit=N" lowers the grid size
 // from which on a batched launch is split by member range (N <= 0: the hardware limit again);
-// "batch_selinv_fused=0|1": 0 forces the three-launch form of every step of the batched selected inversion
+// "batch_selinv_fused=0|1": 0 forces the three-launch form of every step of the batched selected inversion;
+// "rsolve_poison=0|1": 1 fills the scratch of the reproducible solve with NaN before every sweep
 int spllt_hip_debug(const char* what) {
   if (!what) return -1;
   const std::string w(what);
@@ -622,6 +626,10 @@ int spllt_hip_debug(const char* what) {
   }
   if (w == "batch_selinv_fused=0" || w == "batch_selinv_fused=1") {
     set_batch_selinv_fused(w.back() == '1');
+    return 0;
+  }
+  if (w == "rsolve_poison=0" || w == "rsolve_poison=1") {   // NaN in the scratch of the reproducible solve before a sweep
+    set_rsolve_poison(w.back() == '1');
     return 0;
   }
   return -1;
@@ -832,6 +840,52 @@ int spllt_hip_solve_many_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, 
   return rc ? solve_many_fail(f, rc) : 0;
 }
 
+// ---- reproducible solve -----------------------------------------------------
+static int solve_repro_fail(Fkeep* f, int rc) {
+  if (!f->eng->solve_repro_error().empty()) f->last_error = f->eng->solve_repro_error();
+  else if (f->eng->status()) f->last_error = f->eng->error();
+  return rc;
+}
+
+int spllt_hip_solve_repro(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_many_engine(f, "spllt_hip_solve_repro", nrhs, x_host, ldx, job);
+  if (rc) return rc;
+  rc = f->eng->solve_repro(x_host, nrhs, ldx, job);
+  return rc ? solve_repro_fail(f, rc) : 0;
+}
+
+int spllt_hip_solve_repro_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_many_engine(f, "spllt_hip_solve_repro_dev", nrhs, x_dev, ldx, job);
+  if (rc) return rc;
+  rc = f->eng->solve_repro_dev(x_dev, nrhs, ldx, job, pivot_order != 0);
+  return rc ? solve_repro_fail(f, rc) : 0;
+}
+
+int spllt_hip_set_reproducible_solve(void* fkeep, int on) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (on && f->eo.nranks > 1) {
+    f->last_error = "spllt_hip_set_reproducible_solve: not available on a partitioned (multi-GPU) handle";
+    return SPLLT_ERROR_UNIMPLEMENTED;
+  }
+  const int before = f->repro_solve ? 1 : 0;
+  f->repro_solve = on != 0;
+  return before;
+}
+
+int spllt_hip_release_solve_repro(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (!f->eng) return 0;
+  int rc = do_wait(f);
+  if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
+  rc = f->eng->release_solve_repro();
+  return rc ? solve_repro_fail(f, rc) : 0;
+}
+
 // ---- batched factorization --------------------------------------------------
 static int batch_param_error(Fkeep* f, const char* what, const char* bad) {
   f->last_error = std::string(what) + ": " + bad;
@@ -1009,6 +1063,7 @@ static int solve_refined_impl(void* fkeep, int nnz, const double* val, int nrhs,
   if (nrhs == 0) return 0;
   if (int rc = do_wait(f)) return rc;
   if (!f->eng || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
+  f->eng->set_reproducible_solve(f->repro_solve);
   int rc = f->eng->solve_refined(val, nrhs, x, ldx, dev, method, tol, max_iter, iterations, error);
   if (rc == 1) {
     f->last_error = std::string(what) + ": at least one vector did not reach tol (error[] says which)";
@@ -1487,6 +1542,24 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
       int64_t v[2] = {(int64_t)sp.fwd_nsub, (int64_t)sp.bwd_ntop};
       return raw(v, sizeof v);
     }
+  }
+  if (k.rfind("rsolve_", 0) == 0) {
+    // the tables of the reproducible solve: from the symbolic structure and the substitution program alone
+    SolveProgram sp;
+    std::vector<int> owner;
+    if (f->eo.nranks > 1) assign_owners(*f->S, f->eo.nranks, owner);
+    build_solve_program(*f->S, f->eo.pw > 0 ? f->eo.pw : kPanelMax, P->cb, sp,
+                        f->eo.nranks > 1 ? owner.data() : nullptr, f->eo.rank);
+    RsolveTables R;
+    build_rsolve_tables(*f->S, sp, R);
+    auto vec = [&](const std::vector<int64_t>& v) { return raw(v.data(), v.size() * sizeof(int64_t)); };
+    if (k == "rsolve_fslot") return vec(R.fslot);
+    if (k == "rsolve_bfirst") return vec(R.bfirst);
+    if (k == "rsolve_gptr") return vec(R.gptr);
+    if (k == "rsolve_gsrc") return vec(R.gsrc);
+    if (k == "rsolve_bslot") return vec(R.bslot);
+    if (k == "rsolve_frows") return raw(&R.frows, sizeof(int64_t));
+    if (k == "rsolve_bsize") return raw(&R.bsize, sizeof(int64_t));
   }
   return -1;
 }

@@ -1442,6 +1442,29 @@ int Engine::prepare_solve() {
     const char* e = std::getenv("SPLLT_SOLVE_DIAG4");
     solve_four_ = prog_.pw == 64 && prog_.cb == 64 && !(e && std::atoi(e) == 0);
   }
+  // per launch, once: block columns of at most four 64-wide panels take the diagonal kernel that reads L in
+  // one round trip; a launch on ONE block column (every step of the upper levels) passes its descriptor by value
+  auto info = [&](const std::vector<SolveLaunch>& ls, std::vector<SolveLaunchInfo>& out) {
+    out.assign(ls.size(), SolveLaunchInfo{false, nullptr});
+    for (size_t i = 0; i < ls.size(); ++i) {
+      const bool diag = ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD;
+      bool four = solve_four_ && diag;
+      for (int64_t q = ls[i].first; four && q < ls[i].first + ls[i].count; ++q)
+        four = sprog_.units[(size_t)sprog_.diag_list[(size_t)q]].w <= 256;
+      out[i].four = four;
+      if (ls[i].count <= 0) continue;
+      if (diag) {
+        if (ls[i].count == 1) out[i].one = &sprog_.units[(size_t)sprog_.diag_list[(size_t)ls[i].first]];
+      } else {
+        const UpdTile* tl = sprog_.tiles.data() + ls[i].first;
+        bool same = true;
+        for (int64_t q = 0; same && q < ls[i].count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
+        if (same && ls[i].count < 32768) out[i].one = &sprog_.units[(size_t)tl[0].unit];
+      }
+    }
+  };
+  info(sprog_.fwd, sv_fwd_);
+  info(sprog_.bwd, sv_bwd_);
   solve_ready_ = true;
   return 0;
 }
@@ -1591,6 +1614,7 @@ int Engine::inverse_on_pattern(double* out) {
 int Engine::solve_dev(double* y_dev, int nrhs, int job, int phase) {
   if (status_) return status_;
   if (job < 0 || job > 2 || phase < -1 || phase > 2 || nrhs < 0 || !y_dev) return -10;
+  if (repro_on_ && phase == -1 && opt_.nranks == 1) return solve_repro_dev(y_dev, nrhs, (int64_t)S_->n, job, true);
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   int rc = prepare_solve();
   if (rc) return rc;
@@ -1600,33 +1624,16 @@ int Engine::solve_dev(double* y_dev, int nrhs, int job, int phase) {
     const int left = nrhs - done;
     const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);   // kernel variants: 4, 2 or 1 per sweep
     double* y = y_dev + (int64_t)done * n;
-    auto run = [&](const std::vector<SolveLaunch>& ls, size_t a, size_t b) {
-      for (size_t i = a; i < b; ++i) {
-        // block columns of at most four 64-wide panels: the diagonal kernel that reads L in one round trip
-        bool four = solve_four_ && (ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD);
-        for (int64_t q = ls[i].first; four && q < ls[i].first + ls[i].count; ++q)
-          four = sprog_.units[(size_t)sprog_.diag_list[(size_t)q]].w <= 256;
-        // a launch on ONE block column (every step of the upper levels): its descriptor by value
-        const SolveUnit* one = nullptr;
-        if (ls[i].count > 0) {
-          if (ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD) {
-            if (ls[i].count == 1) one = &sprog_.units[(size_t)sprog_.diag_list[(size_t)ls[i].first]];
-          } else {
-            const UpdTile* tl = sprog_.tiles.data() + ls[i].first;
-            bool same = true;
-            for (int64_t q = 0; same && q < ls[i].count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
-            if (same && ls[i].count < 32768) one = &sprog_.units[(size_t)tl[0].unit];
-          }
-        }
+    auto run = [&](const std::vector<SolveLaunch>& ls, const std::vector<SolveLaunchInfo>& li, size_t a, size_t b) {
+      for (size_t i = a; i < b; ++i)
         launch_solve(stream_, ls[i].kind, d_slist_, d_stiles_, ls[i].first, ls[i].count, d_sunits_, d_L_,
-                     d_dinv_, d_rlist_, y, cur, (int64_t)n, four, one);
-      }
+                     d_dinv_, d_rlist_, y, cur, (int64_t)n, li[i].four, li[i].one);
     };
     const size_t nf = sprog_.fwd.size(), nb = sprog_.bwd.size();
-    if (do_fwd && (phase == -1 || phase == 0)) run(sprog_.fwd, 0, sprog_.fwd_nsub);
-    if (do_fwd && (phase == -1 || phase == 1)) run(sprog_.fwd, sprog_.fwd_nsub, nf);
-    if (do_bwd && (phase == -1 || phase == 1)) run(sprog_.bwd, 0, sprog_.bwd_ntop);
-    if (do_bwd && (phase == -1 || phase == 2)) run(sprog_.bwd, sprog_.bwd_ntop, nb);
+    if (do_fwd && (phase == -1 || phase == 0)) run(sprog_.fwd, sv_fwd_, 0, sprog_.fwd_nsub);
+    if (do_fwd && (phase == -1 || phase == 1)) run(sprog_.fwd, sv_fwd_, sprog_.fwd_nsub, nf);
+    if (do_bwd && (phase == -1 || phase == 1)) run(sprog_.bwd, sv_bwd_, 0, sprog_.bwd_ntop);
+    if (do_bwd && (phase == -1 || phase == 2)) run(sprog_.bwd, sv_bwd_, sprog_.bwd_ntop, nb);
     done += cur;
   }
   HIPCHK(hipGetLastError(), "solve launch");
@@ -1637,6 +1644,7 @@ int Engine::solve(double* x_host, int nrhs, int job) {
   if (status_) return status_;
   if (job < 0 || job > 2) return -10;
   const Symbolic& S = *S_;
+  if (repro_on_ && opt_.nranks == 1 && nrhs >= 0 && x_host) return solve_repro(x_host, nrhs, (int64_t)S.n, job);
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   int rc = prepare_solve();
   if (rc) return rc;
@@ -1797,6 +1805,133 @@ int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
   return 0;
 }
 
+// ---- reproducible solve ----------------------------------------------------------------------------
+static std::atomic<bool> g_rsolve_poison{false};
+void set_rsolve_poison(bool on) { g_rsolve_poison.store(on); }
+
+int Engine::prepare_solve_repro() {
+  int rc = prepare_solve();
+  if (rc) return rc;
+  if (rs_ready_) return 0;
+  const Symbolic& S = *S_;
+  RsolveTables R;
+  build_rsolve_tables(S, sprog_, R);
+  std::vector<int> order(S.order.begin(), S.order.end());
+  rs_stride_ = std::max<int64_t>(1, std::max(R.frows, R.bsize));
+  const size_t sb = sizeof(double) * 4 * (size_t)rs_stride_;
+  TableStager tab;
+  tab.add(&d_rsfslot_, R.fslot);
+  tab.add(&d_rsbfirst_, R.bfirst);
+  tab.add(&d_rsgptr_, R.gptr);
+  tab.add(&d_rsgsrc_, R.gsrc);
+  tab.add(&d_rsbslot_, R.bslot);
+  tab.add(&d_rsorder_, order);
+  // (a failure here leaves the factor and the other solves usable: the engine's status is not touched)
+  hipError_t e = tab.commit(&d_rstab_, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e == hipSuccess) e = dalloc((void**)&d_rsscratch_, sb);
+  if (e == hipSuccess) e = dalloc((void**)&d_rsstage_, sizeof(double) * 4 * (size_t)std::max(1, S.n));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
+      if (p) release_buffer(p);
+    d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+    rs_err_ = "solve_repro: not enough device memory for the tables and the scratch of 4 right-hand sides (" +
+              std::to_string((sb + tab.host.size()) >> 20) + " MiB): " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
+  }
+  rs_ready_ = true;
+  return 0;
+}
+
+int Engine::release_solve_repro() {
+  if (status_) return status_;
+  if (!rs_ready_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "solve_repro release")) return rc;
+  for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
+    if (p) release_buffer(p);
+  d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+  rs_ready_ = false;
+  return 0;
+}
+
+// the sweeps `job` asks for on cur = 1, 2 or 4 vectors in pivot order, y[q * ldy + p] (enqueue only)
+int Engine::enqueue_solve_repro(double* y, int64_t ldy, int cur, int job) {
+  const RsolveView rv{d_rsfslot_, d_rsbfirst_, d_rsgptr_, d_rsgsrc_, d_rsbslot_, d_rsscratch_, rs_stride_};
+  auto run = [&](const std::vector<SolveLaunch>& ls, const std::vector<SolveLaunchInfo>& li) -> int {
+    // debug: a slot that is read without having been written in this sweep shows up as NaN
+    if (g_rsolve_poison.load())
+      HIPCHK(hipMemsetAsync(d_rsscratch_, 0xFF, sizeof(double) * 4 * (size_t)rs_stride_, stream_), "poison the scratch");
+    for (size_t i = 0; i < ls.size(); ++i)
+      launch_solve_repro(stream_, ls[i].kind, d_slist_, d_stiles_, ls[i].first, ls[i].count, d_sunits_, d_L_, d_dinv_,
+                         d_rlist_, y, cur, ldy, li[i].four, li[i].one, rv);
+    return 0;
+  };
+  int rc = 0;
+  if (job == 0 || job == 1) rc = run(sprog_.fwd, sv_fwd_);
+  if (!rc && (job == 0 || job == 2)) rc = run(sprog_.bwd, sv_bwd_);
+  return rc;
+}
+
+int Engine::solve_repro_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  if (status_) return status_;
+  rs_err_.clear();
+  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (pending_) return -10;          // (the caller waits first)
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_repro();
+  if (rc) return rc;
+  const int n = S_->n;
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+    double* xg = x_dev + (int64_t)done * ldx;
+    if (pivot_order) {
+      if ((rc = enqueue_solve_repro(xg, ldx, cur, job))) return rc;
+    } else {
+      launch_solve_repro_perm(stream_, false, xg, ldx, d_rsorder_, n, cur, d_y_);
+      if ((rc = enqueue_solve_repro(d_y_, (int64_t)n, cur, job))) return rc;
+      launch_solve_repro_perm(stream_, true, xg, ldx, d_rsorder_, n, cur, d_y_);
+    }
+    done += cur;
+  }
+  HIPCHK(hipGetLastError(), "solve_repro launch");
+  return sync_stream(stream_, "solve_repro sync");
+}
+
+int Engine::solve_repro(double* x_host, int nrhs, int64_t ldx, int job) {
+  if (status_) return status_;
+  rs_err_.clear();
+  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_repro();
+  if (rc) return rc;
+  const int n = S_->n;
+  const size_t vb = sizeof(double) * (size_t)n;
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+    double* xg = x_host + (int64_t)done * ldx;
+    // the group in the caller's layout, its n-vectors only (the permutation happens on the device)
+    for (int q = 0; q < cur; ++q)
+      HIPCHK(hipMemcpyAsync(d_rsstage_ + (size_t)q * n, xg + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "rhs H2D");
+    launch_solve_repro_perm(stream_, false, d_rsstage_, (int64_t)n, d_rsorder_, n, cur, d_y_);
+    if ((rc = enqueue_solve_repro(d_y_, (int64_t)n, cur, job))) return rc;
+    launch_solve_repro_perm(stream_, true, d_rsstage_, (int64_t)n, d_rsorder_, n, cur, d_y_);
+    HIPCHK(hipGetLastError(), "solve_repro launch");
+    for (int q = 0; q < cur; ++q)
+      HIPCHK(hipMemcpyAsync(xg + (int64_t)q * ldx, d_rsstage_ + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "x D2H");
+    if ((rc = sync_stream(stream_, "solve_repro sync"))) return rc;
+    done += cur;
+  }
+  return 0;
+}
+
 // ---- refined solves --------------------------------------------------------------------------------
 // Operator tables (once per engine) and the work vectors of one group, all or nothing: a failed allocation
 // gives back what it got and leaves the factor and every other solve usable.
@@ -1919,6 +2054,11 @@ int Engine::matvec(const double* val, int nvec, const double* x, int64_t ldx, do
 // The sweeps take all nv columns, frozen vectors included (their columns are zero: launch_rf_copy), since the
 // existing paths know no mask; the columns of a sweep are independent of each other.
 int Engine::refine_apply_factor(double* v, int nv) {
+  if (repro_on_) {   // every group size through the reproducible path, in sweeps of 4
+    const int rc = solve_repro_dev(v, nv, (int64_t)S_->n, 0, true);
+    if (rc && !rs_err_.empty()) rf_err_ = rs_err_;
+    return rc;
+  }
   const int rc = nv <= 4 ? solve_dev(v, nv, 0, -1) : solve_many_dev(v, nv, (int64_t)S_->n, 0, true);
   if (rc && !sm_err_.empty()) rf_err_ = sm_err_;
   return rc;

@@ -56,6 +56,8 @@ struct BatchSelinvView;   // kernels.hpp
 // debug hook (spllt_hip_debug "batch_selinv_fused=0|1"): 0 forces the three-launch form of every step of the
 // batched selected inversion; process-wide, read when an inversion is enqueued
 void set_batch_selinv_fused(bool on);
+// debug: the scratch of the reproducible solve is filled with NaN before every sweep
+void set_rsolve_poison(bool on);
 bool batch_selinv_fused();
 
 struct FactorStats {
@@ -139,6 +141,20 @@ class Engine {
   int solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order);
   int solve_many(double* x_host, int nrhs, int64_t ldx, int job);   // host vectors, user order
   const std::string& solve_many_error() const { return sm_err_; }
+  // ---- reproducible solve (solve_repro.hip, single GPU): the substitution program of solve_dev without an
+  // atomic add -- strips store their products, the diagonal launches subtract them in the order of the
+  // RsolveTables.  Same factor bits + same right-hand-side bits = same solution bits, whatever the group
+  // size, the entry point or the handle.  Layout of x as solve_many; sweeps of 4, 2 or 1 vectors.
+  // prepare_solve_repro: tables uploaded once, 4 x max(frows, bsize) doubles of scratch and a staging block
+  // of 4 n doubles for the host entry point, all or nothing (-1: no memory; the factor and every other solve
+  // stay usable).
+  int prepare_solve_repro();
+  int solve_repro_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order);
+  int solve_repro(double* x_host, int nrhs, int64_t ldx, int job);   // host vectors, user order
+  int release_solve_repro();                                          // tables and scratch back to the pool
+  // on: solve(), solve_dev(phase -1) and the preconditioner of solve_refined go through the path above
+  void set_reproducible_solve(bool on) { repro_on_ = on; }
+  const std::string& solve_repro_error() const { return rs_err_; }
   // ---- refined solves (refine.hip, single GPU): the operator A on the analysed pattern, gather-only, in
   // pivot order, and iterative refinement / conjugate gradients preconditioned by the CURRENT factor, to a
   // requested backward error.  Groups of 32 vectors; the preconditioner is solve_dev (up to 4 vectors) or
@@ -343,6 +359,24 @@ class Engine {
   int* d_rlist_ = nullptr;
   int* d_flag_ = nullptr;
   int* h_flag_ = nullptr;  // pinned
+  // per launch of sprog_.fwd / .bwd (prepare_solve): may it use k_solve_diag4, and its ONE block column or null
+  struct SolveLaunchInfo { bool four; const SolveUnit* one; };
+  std::vector<SolveLaunchInfo> sv_fwd_, sv_bwd_;
+  // reproducible solve (tables and scratch taken on first use, all or nothing)
+  int enqueue_solve_repro(double* y, int64_t ldy, int cur, int job);
+  bool repro_on_ = false;
+  bool rs_ready_ = false;
+  std::string rs_err_;
+  char* d_rstab_ = nullptr;        // one allocation behind the tables below
+  int64_t* d_rsfslot_ = nullptr;
+  int64_t* d_rsbfirst_ = nullptr;
+  int64_t* d_rsgptr_ = nullptr;
+  int64_t* d_rsgsrc_ = nullptr;
+  int64_t* d_rsbslot_ = nullptr;
+  int* d_rsorder_ = nullptr;       // user variable -> pivot position
+  double* d_rsscratch_ = nullptr;  // 4 x rs_stride_ doubles
+  double* d_rsstage_ = nullptr;    // 4 n doubles: host vectors in the caller's order
+  int64_t rs_stride_ = 0;
   // blocked solve (workspace allocated on first use, kept with the engine)
   int prepare_solve_many(bool host_stage);
   void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);

@@ -182,6 +182,25 @@ void launch_updown_gen(hipStream_t st, const SolveUnit& u, double* L, double* di
 // the rows below the square (nothing is launched when there are none)
 void launch_updown_apply(hipStream_t st, const SolveUnit& u, double* L, const int* rlist, double* Wd, const double* coef,
                          int sign, int nv);
+// ---- reproducible substitution (solve_repro.hip): launch_solve without atomic adds ------------------
+// The RsolveTables (schedule.hpp) on the device and the scratch: vector q of a sweep uses scratch + q * stride,
+// stride >= max(frows, bsize).
+struct RsolveView {
+  const int64_t* fslot;    // per block column
+  const int64_t* bfirst;   // per block column
+  const int64_t* gptr;     // n + 1
+  const int64_t* gsrc;     // frows
+  const int64_t* bslot;    // per tile
+  double* scratch;
+  int64_t stride;
+};
+// one launch of the SolveProgram, arguments as launch_solve
+void launch_solve_repro(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first, int64_t count,
+                        const SolveUnit* units, const double* L, const double* dinv, const int* rlist, double* y, int nr,
+                        int64_t ldy, bool four, const SolveUnit* one, const RsolveView& rv);
+// y[q * n + order[i]] = x[q * ldx + i] (unpack: the other way), q < nv: a bitwise copy
+void launch_solve_repro_perm(hipStream_t st, bool unpack, double* x, int64_t ldx, const int* order, int n, int nv,
+                             double* y);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 

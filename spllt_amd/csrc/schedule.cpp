@@ -1492,6 +1492,36 @@ void build_solve_program(const Symbolic& S, int pw, int cb, SolveProgram& P, con
   if (nsub_steps == 0) P.bwd_ntop = P.bwd.size();
 }
 
+void build_rsolve_tables(const Symbolic& S, const SolveProgram& P, RsolveTables& R) {
+  R = RsolveTables();
+  const size_t nbc = P.units.size();
+  const int n = S.n;
+  R.fslot.assign(nbc, 0);
+  R.bfirst.assign(nbc, -1);
+  R.gptr.assign((size_t)n + 1, 0);
+  for (size_t b = 0; b < nbc; ++b) {
+    const SolveUnit& u = P.units[b];
+    R.fslot[b] = R.frows;
+    R.frows += u.nrow - u.w;
+    for (int r = u.w; r < u.nrow; ++r) ++R.gptr[(size_t)S.rlist[(size_t)u.idx_off + r] + 1];
+  }
+  for (int p = 0; p < n; ++p) R.gptr[(size_t)p + 1] += R.gptr[(size_t)p];
+  // block columns ascending: every list comes out ascending by source block column
+  R.gsrc.assign((size_t)R.frows, 0);
+  std::vector<int64_t> fill(R.gptr.begin(), R.gptr.end() - 1);
+  for (size_t b = 0; b < nbc; ++b) {
+    const SolveUnit& u = P.units[b];
+    for (int r = u.w; r < u.nrow; ++r) R.gsrc[(size_t)fill[(size_t)S.rlist[(size_t)u.idx_off + r]]++] = R.fslot[b] + (r - u.w);
+  }
+  R.bslot.assign(P.tiles.size(), 0);
+  for (size_t i = 0; i < P.tiles.size(); ++i) {
+    const int b = P.tiles[i].unit;
+    R.bslot[i] = R.bsize;
+    if (P.tiles[i].ti == 0) R.bfirst[(size_t)b] = R.bsize;
+    R.bsize += P.units[(size_t)b].w;
+  }
+}
+
 }  // namespace spx
 
 namespace spx {

@@ -414,6 +414,28 @@ void build_solve_program(const Symbolic& S, int pw, int cb, SolveProgram& P,
                          const int* node_owner = nullptr, int rank = 0);
 
 // ---------------------------------------------------------------------------
+// Reproducible substitution (solve_repro.hip): the launches of a SolveProgram with every sum in an order
+// fixed by these tables.  A strip STORES its product into a scratch vector; the diagonal launch that
+// consumes a row subtracts the stored products in table order before its own arithmetic.  One scratch
+// vector per right-hand side of the sweep; all offsets below are in doubles inside one such vector.
+//   forward : the strip rows r = w .. nrow-1 of block column b go to scratch[fslot[b] + r - w] (frows slots
+//             in all).  For pivot position p, gsrc[gptr[p] .. gptr[p+1]) are the slots holding a product for
+//             y[p], ascending by source block column (= elimination order).
+//   backward: tile i of P.tiles (block column b, strip t) stores its w column sums at scratch[bslot[i] ..
+//             + w) (bsize doubles in all).  The strips of one block column are consecutive tiles, so their
+//             ranges are consecutive too: strip t at bfirst[b] + t * w; the diagonal launch subtracts them in
+//             ascending t.  bfirst[b] = -1: no rows below.
+// From the Symbolic structure and the launch order of P alone (no factor program).
+// ---------------------------------------------------------------------------
+struct RsolveTables {
+  std::vector<int64_t> fslot, bfirst;   // per block column
+  std::vector<int64_t> gptr, gsrc;      // n + 1, frows
+  std::vector<int64_t> bslot;           // per tile of the SolveProgram
+  int64_t frows = 0, bsize = 0;
+};
+void build_rsolve_tables(const Symbolic& S, const SolveProgram& P, RsolveTables& R);
+
+// ---------------------------------------------------------------------------
 // Selected inversion: Z = (P A P^T)^-1 on the pattern of L (the Takahashi recurrences), written
 // into a second arena with L's layout.  Per panel J (pw columns of one block column), R = the
 // node-local rows below J (rest of its block column, later block columns, the ancestor rows):
