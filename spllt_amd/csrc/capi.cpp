@@ -791,19 +791,10 @@ double* spllt_hip_device_factor(void* fkeep) {
   return (f && f->eng) ? f->eng->device_L() : nullptr;
 }
 
-// ---- blocked solve for many right-hand sides ------------------------------
-// argument checks that need no device, then the handle's engine with its factor finished
-static int solve_many_engine(Fkeep* f, const char* what, int nrhs, const void* x, int64_t ldx, int job) {
+// ---- what the features on a finished single-GPU factor share ----------------
+// the handle's engine with its factor finished, or an error flag (with the message in last_error)
+static int need_single_factor(Fkeep* f, const char* what) {
   if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  const char* bad = nullptr;
-  if (!x) bad = "the array of right-hand sides is null";
-  else if (nrhs < 0) bad = "nrhs < 0";
-  else if (ldx < f->S->n) bad = "ldx < n";
-  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
-  if (bad) {
-    f->last_error = std::string(what) + ": " + bad;
-    return SPLLT_ERROR_PARAMETER;
-  }
   int rc = do_wait(f);
   if (rc) return rc;
   if (no_factor(f)) {
@@ -818,10 +809,27 @@ static int solve_many_engine(Fkeep* f, const char* what, int nrhs, const void* x
   return 0;
 }
 
-static int solve_many_fail(Fkeep* f, int rc) {
-  if (!f->eng->solve_many_error().empty()) f->last_error = f->eng->solve_many_error();
+// the message of a failed engine call: the feature's own, else the engine's
+static int feature_fail(Fkeep* f, int rc) {
+  if (!f->eng->feature_error().empty()) f->last_error = f->eng->feature_error();
   else if (f->eng->status()) f->last_error = f->eng->error();
   return rc;
+}
+
+// ---- blocked solve for many right-hand sides ------------------------------
+// argument checks that need no device, then the handle's engine with its factor finished
+static int solve_many_engine(Fkeep* f, const char* what, int nrhs, const void* x, int64_t ldx, int job) {
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!x) bad = "the array of right-hand sides is null";
+  else if (nrhs < 0) bad = "nrhs < 0";
+  else if (ldx < f->S->n) bad = "ldx < n";
+  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
+  if (bad) {
+    f->last_error = std::string(what) + ": " + bad;
+    return SPLLT_ERROR_PARAMETER;
+  }
+  return need_single_factor(f, what);
 }
 
 int spllt_hip_solve_many(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
@@ -829,7 +837,7 @@ int spllt_hip_solve_many(void* fkeep, int nrhs, double* x_host, int64_t ldx, int
   int rc = solve_many_engine(f, "spllt_hip_solve_many", nrhs, x_host, ldx, job);
   if (rc) return rc;
   rc = f->eng->solve_many(x_host, nrhs, ldx, job);
-  return rc ? solve_many_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_solve_many_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
@@ -837,22 +845,16 @@ int spllt_hip_solve_many_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, 
   int rc = solve_many_engine(f, "spllt_hip_solve_many_dev", nrhs, x_dev, ldx, job);
   if (rc) return rc;
   rc = f->eng->solve_many_dev(x_dev, nrhs, ldx, job, pivot_order != 0);
-  return rc ? solve_many_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 // ---- reproducible solve -----------------------------------------------------
-static int solve_repro_fail(Fkeep* f, int rc) {
-  if (!f->eng->solve_repro_error().empty()) f->last_error = f->eng->solve_repro_error();
-  else if (f->eng->status()) f->last_error = f->eng->error();
-  return rc;
-}
-
 int spllt_hip_solve_repro(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   int rc = solve_many_engine(f, "spllt_hip_solve_repro", nrhs, x_host, ldx, job);
   if (rc) return rc;
   rc = f->eng->solve_repro(x_host, nrhs, ldx, job);
-  return rc ? solve_repro_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_solve_repro_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
@@ -860,7 +862,7 @@ int spllt_hip_solve_repro_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx,
   int rc = solve_many_engine(f, "spllt_hip_solve_repro_dev", nrhs, x_dev, ldx, job);
   if (rc) return rc;
   rc = f->eng->solve_repro_dev(x_dev, nrhs, ldx, job, pivot_order != 0);
-  return rc ? solve_repro_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_set_reproducible_solve(void* fkeep, int on) {
@@ -883,7 +885,7 @@ int spllt_hip_release_solve_repro(void* fkeep) {
   int rc = do_wait(f);
   if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
   rc = f->eng->release_solve_repro();
-  return rc ? solve_repro_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 // ---- batched factorization --------------------------------------------------
@@ -897,12 +899,6 @@ static int batch_partitioned(Fkeep* f, const char* what) {
   f->last_error = std::string(what) + ": not available on a partitioned (multi-GPU) handle";
   std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
   return SPLLT_ERROR_UNIMPLEMENTED;
-}
-
-static int batch_fail(Fkeep* f, int rc) {
-  if (!f->eng->batch_error().empty()) f->last_error = f->eng->batch_error();
-  else if (f->eng->status()) f->last_error = f->eng->error();
-  return rc;
 }
 
 // the handle's engine with a finished batch on it, or an error flag
@@ -945,7 +941,7 @@ static int factor_batch_impl(void* akeep, void* fkeep, int nbatch, int nnz, cons
                     std::to_string(first >= 0 ? fl[(size_t)first] : 0) + " in elimination order)";
     return rc;
   }
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_factor_batch(void* akeep, void* fkeep, int nbatch, int nnz, const double* val_host, int64_t ldval) {
@@ -987,7 +983,7 @@ static int solve_batch_impl(void* fkeep, int nrhs, double* x, int64_t ldx, int j
                                         "(spllt_hip_batch_status)";
     return rc;
   }
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_solve_batch(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
@@ -999,12 +995,6 @@ int spllt_hip_solve_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx,
 }
 
 // ---- refined solves ---------------------------------------------------------
-static int refine_fail(Fkeep* f, int rc) {
-  if (!f->eng->refine_error().empty()) f->last_error = f->eng->refine_error();
-  else if (f->eng->status()) f->last_error = f->eng->error();
-  return rc;
-}
-
 // the argument checks that need no device: `bad` from the caller's own checks, nnz, partition, a dead handle
 static int refine_engine(Fkeep* f, const char* what, int nnz, const char* bad) {
   if (!bad && (int64_t)nnz != f->S->nnzA) bad = "nnz does not match the analysed pattern";
@@ -1034,7 +1024,7 @@ static int matvec_impl(void* fkeep, int nnz, const double* val, int nvec, const 
   }
   if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
   int rc = f->eng->matvec(val, nvec, x, ldx, y, ldy, dev, pivot_order);
-  return rc ? refine_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_matvec(void* fkeep, int nnz, const double* val_host, int nvec, const double* x_host, int64_t ldx,
@@ -1069,7 +1059,7 @@ static int solve_refined_impl(void* fkeep, int nnz, const double* val, int nrhs,
     f->last_error = std::string(what) + ": at least one vector did not reach tol (error[] says which)";
     return 1;
   }
-  return rc ? refine_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_solve_refined(void* fkeep, int nnz, const double* val_host, int nrhs, double* x_host, int64_t ldx,
@@ -1091,7 +1081,7 @@ int spllt_hip_release_refine(void* fkeep) {
   if (!f->eng) return 0;
   if (f->eng->pending()) (void)do_wait(f);
   int rc = f->eng->release_refine();
-  return rc ? refine_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 // ---- low-rank update / downdate of the factor ------------------------------------------------------
@@ -1132,8 +1122,7 @@ int spllt_hip_updown(void* fkeep, int k, const int* wptr, const int* wrow, const
   const int rc = f->eng->updown(k, wptr, wrow, wval, sign, plan, first);
   f->hostL_valid = false;
   if (rc) {
-    if (!f->eng->updown_error().empty()) f->last_error = f->eng->updown_error();
-    else if (f->eng->status()) f->last_error = f->eng->error();
+    feature_fail(f, rc);
     if (rc == SPLLT_ERROR_NOT_POSDEF) std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
   }
   return rc;
@@ -1163,7 +1152,7 @@ int spllt_hip_get_factor_batch(void* fkeep, int member, double* out, int64_t cou
   if (rc) return rc;
   if (member < 0 || member >= f->eng->batch_count()) return batch_param_error(f, what, "member is not in [0, nbatch)");
   rc = f->eng->download_batch(member, out, count);
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 double* spllt_hip_device_factor_batch(void* fkeep, int64_t* member_stride) {
@@ -1181,7 +1170,7 @@ int spllt_hip_log_det_batch(void* fkeep, double* out) {
   int rc = batch_reader(f, what);
   if (rc) return rc;
   rc = f->eng->log_det_batch(out);
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_batch_launches(void* fkeep) {
@@ -1196,7 +1185,7 @@ int spllt_hip_release_batch(void* fkeep) {
   if (!f->eng || f->dead) return 0;
   if (f->eng->pending()) (void)do_wait(f);
   int rc = f->eng->release_batch();
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 // ---- batched selected inversion ------------------------------------------------
@@ -1228,7 +1217,7 @@ int spllt_hip_selected_inverse_batch(void* fkeep) {
                                         "inverted (spllt_hip_batch_status)";
     return rc;
   }
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_get_inverse_batch(void* fkeep, int member, double* out, int64_t count) {
@@ -1242,7 +1231,7 @@ int spllt_hip_get_inverse_batch(void* fkeep, int member, double* out, int64_t co
   if (member < 0 || member >= f->eng->batch_count()) return batch_param_error(f, what, "member is not in [0, nbatch)");
   if (f->eng->batch_flags()[(size_t)member] != INT_MAX) return batch_member_failed(f, what, member);
   rc = f->eng->download_inverse_batch(member, out, count);
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 double* spllt_hip_device_inverse_batch(void* fkeep, int64_t* member_stride) {
@@ -1261,7 +1250,7 @@ int spllt_hip_inverse_diag_batch(void* fkeep, double* out, int64_t ldout) {
   int rc = batch_inverse_reader(f, what);
   if (rc) return rc;
   rc = f->eng->inverse_diag_batch(out, ldout);
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_inverse_on_pattern_batch(void* fkeep, double* out, int64_t ldout) {
@@ -1273,7 +1262,7 @@ int spllt_hip_inverse_on_pattern_batch(void* fkeep, double* out, int64_t ldout) 
   int rc = batch_inverse_reader(f, what);
   if (rc) return rc;
   rc = f->eng->inverse_on_pattern_batch(out, ldout);
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_batch_selinv_launches(void* fkeep) {
@@ -1288,35 +1277,12 @@ int spllt_hip_release_inverse_batch(void* fkeep) {
   if (!f->eng || f->dead) return 0;
   if (f->eng->pending()) (void)do_wait(f);
   int rc = f->eng->release_inverse_batch();
-  return rc ? batch_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 // ---- selected inversion ---------------------------------------------------
-// the handle's engine with its factor finished, or an error flag (with the message in last_error)
-static int selinv_engine(Fkeep* f, const char* what) {
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  int rc = do_wait(f);
-  if (rc) return rc;
-  if (no_factor(f)) {
-    f->last_error = std::string(what) + ": nothing has been factorized on this handle";
-    return SPLLT_ERROR_PARAMETER;
-  }
-  if (f->eo.nranks > 1) {
-    f->last_error = std::string(what) + ": not available on a partitioned (multi-GPU) factor";
-    std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
-    return SPLLT_ERROR_UNIMPLEMENTED;
-  }
-  return 0;
-}
-
-static int selinv_fail(Fkeep* f, int rc) {
-  if (!f->eng->selinv_error().empty()) f->last_error = f->eng->selinv_error();
-  else if (f->eng->status()) f->last_error = f->eng->error();
-  return rc;
-}
-
 static int selinv_need_z(Fkeep* f, const char* what) {
-  int rc = selinv_engine(f, what);
+  int rc = need_single_factor(f, what);
   if (rc) return rc;
   if (!f->eng->inverse_valid()) {
     f->last_error = std::string(what) + ": no selected inverse of the current factor (call spllt_hip_selected_inverse "
@@ -1328,10 +1294,10 @@ static int selinv_need_z(Fkeep* f, const char* what) {
 
 int spllt_hip_selected_inverse(void* fkeep) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = selinv_engine(f, "spllt_hip_selected_inverse");
+  int rc = need_single_factor(f, "spllt_hip_selected_inverse");
   if (rc) return rc;
   rc = f->eng->selected_inverse();
-  return rc ? selinv_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_get_inverse(void* fkeep, double* out, int64_t count) {
@@ -1340,7 +1306,7 @@ int spllt_hip_get_inverse(void* fkeep, double* out, int64_t count) {
   int rc = selinv_need_z(f, "spllt_hip_get_inverse");
   if (rc) return rc;
   rc = f->eng->download_inverse(out, count);
-  return rc ? selinv_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 double* spllt_hip_device_inverse(void* fkeep) {
@@ -1359,7 +1325,7 @@ int spllt_hip_inverse_diag(void* fkeep, double* out, int n) {
     return SPLLT_ERROR_PARAMETER;
   }
   rc = f->eng->inverse_diag(out, n);
-  return rc ? selinv_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_inverse_on_pattern(void* fkeep, double* out) {
@@ -1368,16 +1334,16 @@ int spllt_hip_inverse_on_pattern(void* fkeep, double* out) {
   int rc = selinv_need_z(f, "spllt_hip_inverse_on_pattern");
   if (rc) return rc;
   rc = f->eng->inverse_on_pattern(out);
-  return rc ? selinv_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_log_det(void* fkeep, double* out) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!out) return SPLLT_ERROR_PARAMETER;
-  int rc = selinv_engine(f, "spllt_hip_log_det");
+  int rc = need_single_factor(f, "spllt_hip_log_det");
   if (rc) return rc;
   rc = f->eng->log_det(out);
-  return rc ? selinv_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_release_inverse(void* fkeep) {
@@ -1386,7 +1352,7 @@ int spllt_hip_release_inverse(void* fkeep) {
   if (!f->eng || f->dead) return 0;
   if (f->eng->pending()) do_wait(f);
   int rc = f->eng->release_inverse();
-  return rc ? selinv_fail(f, rc) : 0;
+  return rc ? feature_fail(f, rc) : 0;
 }
 
 int spllt_hip_factor_times(void* fkeep, double* submit_ms, double* device_ms, double* h2d_ms, int* launches) {

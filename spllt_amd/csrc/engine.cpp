@@ -16,24 +16,17 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "engine_detail.hpp"
 #include "kernels.hpp"
-#include "refine.hpp"
 
 namespace spx {
 
 namespace {
-constexpr int kErrHip = -30, kErrNotPosDef = -20;
 double now_ms() {
   using namespace std::chrono;
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 }  // namespace
-
-#define HIPCHK(call, what)                                   \
-  do {                                                       \
-    hipError_t e__ = (call);                                 \
-    if (e__ != hipSuccess) return fail(kErrHip, what, e__);  \
-  } while (0)
 
 int Engine::fail(int code, const char* what, hipError_t e) {
   status_ = code;
@@ -41,35 +34,6 @@ int Engine::fail(int code, const char* what, hipError_t e) {
   std::fprintf(stderr, "spllt-hip: %s\n", err_.c_str());
   return code;
 }
-
-// Tables of an engine go to the device as ONE allocation and ONE copy: the parts are laid out in
-// a host staging buffer (256-byte aligned), the typed device pointers are set after the upload.
-// (Two dozen allocations, synchronous copies and frees per engine were two dozen chances per
-// engine to sit in the runtime.)
-struct TableStager {
-  struct Slot { void** dptr; size_t off; };
-  std::vector<char> host;
-  std::vector<Slot> slots;
-  template <class Tp>
-  void add(Tp** dptr, const Tp* src, size_t count) {
-    const size_t off = (host.size() + 255) / 256 * 256;
-    const size_t bytes = std::max<size_t>(count * sizeof(Tp), 8);
-    host.resize(off + bytes, 0);
-    if (count) std::memcpy(host.data() + off, src, count * sizeof(Tp));
-    slots.push_back({(void**)dptr, off});
-  }
-  template <class Tp>
-  void add(Tp** dptr, const std::vector<Tp>& v) { add(dptr, v.data(), v.size()); }
-  template <class Alloc>
-  hipError_t commit(char** blob, Alloc&& alloc) {
-    hipError_t e = alloc((void**)blob, std::max<size_t>(host.size(), 8));
-    if (e != hipSuccess) return e;
-    if (!host.empty()) e = hipMemcpy(*blob, host.data(), host.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return e;
-    for (const Slot& sl : slots) *sl.dptr = *blob + sl.off;
-    return hipSuccess;
-  }
-};
 
 // pinned words for the "not positive definite" flag, pooled per process
 static std::vector<int*> g_pinned_words;
@@ -316,6 +280,35 @@ hipError_t Engine::dev_upload(Tp** dptr, const std::vector<Tp>& v) {
   if (e != hipSuccess) return e;
   if (!v.empty()) e = hipMemcpy(*dptr, v.data(), sizeof(Tp) * v.size(), hipMemcpyHostToDevice);
   return e;
+}
+
+// the "user variable -> pivot position" table of every device-side permutation: uploaded on first use, kept
+// until the engine dies (n = 0: one entry)
+hipError_t Engine::ensure_order() {
+  if (d_order_) return hipSuccess;
+  std::vector<int> order(S_->order.begin(), S_->order.end());
+  if (order.empty()) order.push_back(0);
+  hipError_t e = dev_upload(&d_order_, order);
+  if (e != hipSuccess) {
+    release_buffer(d_order_);
+    d_order_ = nullptr;
+  }
+  return e;
+}
+
+// nv vectors of len doubles (-1: n) between the caller's host array, vector q at host + q * ldx, and a packed
+// device block, on stream_: one copy when ldx == len, else one per vector
+int Engine::copy_vectors(bool to_device, double* dev, double* host, int64_t ldx, int64_t nv, const char* what,
+                         int64_t len) {
+  if (len < 0) len = S_->n;
+  const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  const int64_t ncopy = ldx == len ? 1 : nv;
+  const size_t bytes = sizeof(double) * (size_t)len * (size_t)(ldx == len ? nv : 1);
+  for (int64_t q = 0; q < ncopy; ++q) {
+    double *d = dev + q * len, *h = host + q * ldx;
+    HIPCHK(hipMemcpyAsync(to_device ? d : h, to_device ? h : d, bytes, kind, stream_), what);
+  }
+  return 0;
 }
 
 // EngineOptions -> ScheduleOptions, in ONE place (the engine and the host-only program of
@@ -1101,24 +1094,6 @@ int Engine::post_exchange(const Launch& X) {
 // RCCL, resolved at run time from the librccl the process already has (the caller created the
 // communicator with it; a Python process has torch's copy): no link-time dependency, one copy.
 // ---------------------------------------------------------------------------
-namespace {
-typedef int (*nccl_allreduce_t)(const void*, void*, size_t, int, int, void*, hipStream_t);
-typedef int (*nccl_reducescatter_t)(const void*, void*, size_t, int, int, void*, hipStream_t);
-typedef int (*nccl_broadcast_t)(const void*, void*, size_t, int, int, void*, hipStream_t);
-typedef int (*nccl_group_t)();
-typedef int (*nccl_query_t)(void*, int*);
-typedef const char* (*nccl_errstr_t)(int);
-struct Rccl {
-  void* handle = nullptr;
-  nccl_allreduce_t all_reduce = nullptr;
-  nccl_reducescatter_t reduce_scatter = nullptr;
-  nccl_broadcast_t broadcast = nullptr;
-  nccl_group_t group_start = nullptr, group_end = nullptr;
-  nccl_query_t comm_count = nullptr, comm_user_rank = nullptr;
-  nccl_errstr_t err_string = nullptr;
-  bool ok() const { return all_reduce && reduce_scatter && broadcast && group_start && group_end && comm_count && comm_user_rank; }
-};
-constexpr int kNcclDouble = 8, kNcclSum = 0;      // ncclFloat64, ncclSum (rccl.h)
 Rccl& rccl() {
   static Rccl r = [] {
     Rccl q;
@@ -1141,19 +1116,6 @@ Rccl& rccl() {
   }();
   return r;
 }
-}  // namespace
-
-#define NCCLCHK(call, what)                                                                      \
-  do {                                                                                           \
-    int r__ = (call);                                                                            \
-    if (r__ != 0) {                                                                              \
-      status_ = kErrHip;                                                                         \
-      err_ = std::string(what) + ": RCCL error " + std::to_string(r__) +                         \
-             (rccl().err_string ? std::string(" (") + rccl().err_string(r__) + ")" : std::string()); \
-      std::fprintf(stderr, "spllt-hip: %s\n", err_.c_str());                                     \
-      return kErrHip;                                                                            \
-    }                                                                                            \
-  } while (0)
 
 int Engine::set_communicator(void* nccl_comm) {
   if (status_) return status_;
@@ -1423,77 +1385,30 @@ int Engine::download(double* out, int64_t count) {
   return 0;
 }
 
-int Engine::prepare_solve() {
-  if (solve_ready_) return 0;
-  const Symbolic& S = *S_;
-  build_solve_program(S, prog_.pw, prog_.cb, sprog_, opt_.nranks > 1 ? owner_.data() : nullptr, opt_.rank);
-  if (!loc_off_.empty())
-    for (size_t b = 0; b < sprog_.units.size(); ++b)   // (units of block columns not held here are never launched)
-      if (loc_off_[b] >= 0) sprog_.units[b].off = loc_off_[b];
-  {
-    TableStager tab;
-    tab.add(&d_sunits_, sprog_.units);
-    tab.add(&d_slist_, sprog_.diag_list);
-    tab.add(&d_stiles_, sprog_.tiles);
-    HIPCHK(tab.commit(&d_solve_tables_, [this](void** q, size_t b) { return dalloc(q, b); }), "upload solve tables");
-  }
-  HIPCHK(dalloc((void**)&d_y_, sizeof(double) * 4 * (size_t)std::max(1, S.n)), "hipMalloc(y)");
-  {
-    const char* e = std::getenv("SPLLT_SOLVE_DIAG4");
-    solve_four_ = prog_.pw == 64 && prog_.cb == 64 && !(e && std::atoi(e) == 0);
-  }
-  // per launch, once: block columns of at most four 64-wide panels take the diagonal kernel that reads L in
-  // one round trip; a launch on ONE block column (every step of the upper levels) passes its descriptor by value
-  auto info = [&](const std::vector<SolveLaunch>& ls, std::vector<SolveLaunchInfo>& out) {
-    out.assign(ls.size(), SolveLaunchInfo{false, nullptr});
-    for (size_t i = 0; i < ls.size(); ++i) {
-      const bool diag = ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD;
-      bool four = solve_four_ && diag;
-      for (int64_t q = ls[i].first; four && q < ls[i].first + ls[i].count; ++q)
-        four = sprog_.units[(size_t)sprog_.diag_list[(size_t)q]].w <= 256;
-      out[i].four = four;
-      if (ls[i].count <= 0) continue;
-      if (diag) {
-        if (ls[i].count == 1) out[i].one = &sprog_.units[(size_t)sprog_.diag_list[(size_t)ls[i].first]];
-      } else {
-        const UpdTile* tl = sprog_.tiles.data() + ls[i].first;
-        bool same = true;
-        for (int64_t q = 0; same && q < ls[i].count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
-        if (same && ls[i].count < 32768) out[i].one = &sprog_.units[(size_t)tl[0].unit];
-      }
-    }
-  };
-  info(sprog_.fwd, sv_fwd_);
-  info(sprog_.bwd, sv_bwd_);
-  solve_ready_ = true;
-  return 0;
-}
-
 // ---- selected inversion --------------------------------------------------------------------------
 int Engine::prepare_selinv() {
   if (selinv_ready_) return 0;
   const Symbolic& S = *S_;
   if (build_selinv_program(S, prog_.pw, prog_.cb, siprog_)) {
-    si_err_ = "selected inversion: the row structure of a node is not contained in its ancestors'";
+    feature_err_ = "selected inversion: the row structure of a node is not contained in its ancestors'";
     return -10;
   }
-  std::vector<int> order(S.order.begin(), S.order.end());
   TableStager tab;
   tab.add(&d_siunits_, siprog_.units);
   tab.add(&d_sitiles_, siprog_.tiles);
   tab.add(&d_sirows_, siprog_.rows);
   tab.add(&d_sirelpos_, siprog_.relpos);
   tab.add(&d_sidiag_, siprog_.diag_pos);
-  tab.add(&d_siorder_, order);
   // (a failure here leaves the factor and the solve usable: the engine's status is not touched)
   hipError_t e = tab.commit(&d_selinv_tables_, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e == hipSuccess) e = ensure_order();
   if (e == hipSuccess) e = dalloc((void**)&d_siout_, sizeof(double) * ((size_t)S.n + 1));
   if (e != hipSuccess) {
     (void)hipGetLastError();
     if (d_selinv_tables_) { release_buffer(d_selinv_tables_); d_selinv_tables_ = nullptr; }
-    si_err_ = std::string("selected inversion: not enough device memory for the program tables (") +
-              hipGetErrorString(e) + ")";
-    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
+    feature_err_ = std::string("selected inversion: not enough device memory for the program tables (") +
+                   hipGetErrorString(e) + ")";
+    return alloc_code(e);
   }
   selinv_ready_ = true;
   return 0;
@@ -1509,10 +1424,10 @@ void Engine::release_buffer(void* p) {
 }
 
 int Engine::selected_inverse() {
+  feature_err_.clear();
   if (status_) return status_;
   if (pending_) return -10;   // (the caller waits first)
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  si_err_.clear();
   int rc = prepare_selinv();
   if (rc) return rc;
   if (!d_Z_ || !d_siscratch_) {
@@ -1524,8 +1439,8 @@ int Engine::selected_inverse() {
     if (e != hipSuccess) {
       (void)hipGetLastError();
       if (d_Z_) { release_buffer(d_Z_); d_Z_ = nullptr; }
-      si_err_ = "selected inversion: not enough device memory for the inverse arena (" + std::to_string(zb >> 20) +
-                " MiB) and its scratch (" + std::to_string(sb >> 20) + " MiB)";
+      feature_err_ = "selected inversion: not enough device memory for the inverse arena (" + std::to_string(zb >> 20) +
+                     " MiB) and its scratch (" + std::to_string(sb >> 20) + " MiB)";
       return -1;
     }
   }
@@ -1539,6 +1454,7 @@ int Engine::selected_inverse() {
 }
 
 int Engine::download_inverse(double* out, int64_t count) {
+  feature_err_.clear();
   if (status_) return status_;
   if (!z_valid_) return -10;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
@@ -1546,16 +1462,18 @@ int Engine::download_inverse(double* out, int64_t count) {
 }
 
 int Engine::inverse_diag(double* out, int n) {
+  feature_err_.clear();
   if (status_) return status_;
   if (!z_valid_ || n != S_->n) return -10;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  launch_selinv_diag_gather(stream_, d_Z_, d_sidiag_, d_siorder_, n, d_siout_);
+  launch_selinv_diag_gather(stream_, d_Z_, d_sidiag_, d_order_, n, d_siout_);
   HIPCHK(hipGetLastError(), "selinv diag launch");
   HIPCHK(hipMemcpyAsync(out, d_siout_, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, stream_), "diag D2H");
   return sync_stream(stream_, "selinv diag sync");
 }
 
 int Engine::log_det(double* out) {
+  feature_err_.clear();
   if (status_) return status_;
   if (pending_) return -10;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
@@ -1568,6 +1486,7 @@ int Engine::log_det(double* out) {
 }
 
 int Engine::release_inverse() {
+  feature_err_.clear();
   if (status_) return status_;
   z_valid_ = false;
   if (d_Z_) {
@@ -1582,6 +1501,7 @@ int Engine::release_inverse() {
 }
 
 int Engine::inverse_on_pattern(double* out) {
+  feature_err_.clear();
   if (status_) return status_;
   if (!z_valid_ || !out || opt_.nranks > 1) return -10;
   const int64_t nnz = S_->nnzA;
@@ -1592,7 +1512,7 @@ int Engine::inverse_on_pattern(double* out) {
     if (e != hipSuccess) {
       (void)hipGetLastError();
       d_sipat_ = nullptr;
-      si_err_ = std::string("inverse on pattern: not enough device memory for the gathered entries (") + hipGetErrorString(e) + ")";
+      feature_err_ = std::string("inverse on pattern: not enough device memory for the gathered entries (") + hipGetErrorString(e) + ")";
       return -1;
     }
   }
@@ -1600,604 +1520,12 @@ int Engine::inverse_on_pattern(double* out) {
   v.v.nbatch = 1;
   v.Z = d_Z_;
   if (launch_batch_selinv_pattern(stream_, v, d_map_dst_, d_map_src_, nmap_, d_sipat_, nnz) < 0) {
-    si_err_ = "inverse on pattern: the pattern has more entries than a grid holds work items";
+    feature_err_ = "inverse on pattern: the pattern has more entries than a grid holds work items";
     return -99;
   }
   HIPCHK(hipGetLastError(), "inverse on pattern launch");
   if (int rc = sync_stream(stream_, "inverse on pattern sync")) return rc;
   return staged_d2h(out, d_sipat_, sizeof(double) * (size_t)nnz);
-}
-
-// Substitution on device vectors in pivot order (y[q * n + p], q < nrhs), in place.
-// phase -1: everything that `job` asks for; 0/1/2: the three phases of a
-// partitioned solve (schedule.hpp, SolveProgram).
-int Engine::solve_dev(double* y_dev, int nrhs, int job, int phase) {
-  if (status_) return status_;
-  if (job < 0 || job > 2 || phase < -1 || phase > 2 || nrhs < 0 || !y_dev) return -10;
-  if (repro_on_ && phase == -1 && opt_.nranks == 1) return solve_repro_dev(y_dev, nrhs, (int64_t)S_->n, job, true);
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve();
-  if (rc) return rc;
-  const int n = S_->n;
-  const bool do_fwd = job == 0 || job == 1, do_bwd = job == 0 || job == 2;
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);   // kernel variants: 4, 2 or 1 per sweep
-    double* y = y_dev + (int64_t)done * n;
-    auto run = [&](const std::vector<SolveLaunch>& ls, const std::vector<SolveLaunchInfo>& li, size_t a, size_t b) {
-      for (size_t i = a; i < b; ++i)
-        launch_solve(stream_, ls[i].kind, d_slist_, d_stiles_, ls[i].first, ls[i].count, d_sunits_, d_L_,
-                     d_dinv_, d_rlist_, y, cur, (int64_t)n, li[i].four, li[i].one);
-    };
-    const size_t nf = sprog_.fwd.size(), nb = sprog_.bwd.size();
-    if (do_fwd && (phase == -1 || phase == 0)) run(sprog_.fwd, sv_fwd_, 0, sprog_.fwd_nsub);
-    if (do_fwd && (phase == -1 || phase == 1)) run(sprog_.fwd, sv_fwd_, sprog_.fwd_nsub, nf);
-    if (do_bwd && (phase == -1 || phase == 1)) run(sprog_.bwd, sv_bwd_, 0, sprog_.bwd_ntop);
-    if (do_bwd && (phase == -1 || phase == 2)) run(sprog_.bwd, sv_bwd_, sprog_.bwd_ntop, nb);
-    done += cur;
-  }
-  HIPCHK(hipGetLastError(), "solve launch");
-  return sync_stream(stream_, "solve sync");
-}
-
-int Engine::solve(double* x_host, int nrhs, int job) {
-  if (status_) return status_;
-  if (job < 0 || job > 2) return -10;
-  const Symbolic& S = *S_;
-  if (repro_on_ && opt_.nranks == 1 && nrhs >= 0 && x_host) return solve_repro(x_host, nrhs, (int64_t)S.n, job);
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve();
-  if (rc) return rc;
-  const int n = S.n;
-  // up to four right-hand sides per sweep: every entry of L is read once for all of them
-  std::vector<double> yh((size_t)n * 4);
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
-    for (int q = 0; q < cur; ++q) {
-      const double* xr = x_host + (int64_t)(done + q) * n;
-      double* yq = yh.data() + (size_t)q * n;
-      for (int i = 0; i < n; ++i) yq[S.order[i]] = xr[i];
-    }
-    HIPCHK(hipMemcpyAsync(d_y_, yh.data(), sizeof(double) * (size_t)n * cur, hipMemcpyHostToDevice, stream_), "rhs H2D");
-    if (comm_ && opt_.nranks > 1) {
-      // partitioned solve inside the library (every rank passes the same right-hand sides and gets
-      // the same solution): forward substitution on the own subtrees, all-reduce of the vector,
-      // the top tree on every rank, backward substitution on the own subtrees, all-reduce
-      if (job != 0) return -98;
-      Rccl& R = rccl();
-      launch_mask(stream_, d_y_, d_owned_, n, cur, (int64_t)n);
-      if ((rc = solve_dev(d_y_, cur, 0, 0))) return rc;
-      NCCLCHK(R.all_reduce(d_y_, d_y_, (size_t)n * cur, kNcclDouble, kNcclSum, comm_, stream_), "ncclAllReduce(rhs)");
-      if ((rc = solve_dev(d_y_, cur, 0, 1))) return rc;
-      if ((rc = solve_dev(d_y_, cur, 0, 2))) return rc;
-      launch_mask(stream_, d_y_, d_owned_, n, cur, (int64_t)n);
-      NCCLCHK(R.all_reduce(d_y_, d_y_, (size_t)n * cur, kNcclDouble, kNcclSum, comm_, stream_), "ncclAllReduce(x)");
-      if ((rc = sync_stream(stream_, "solve sync"))) return rc;
-    } else {
-      rc = solve_dev(d_y_, cur, job, -1);
-      if (rc) return rc;
-    }
-    HIPCHK(hipMemcpy(yh.data(), d_y_, sizeof(double) * (size_t)n * cur, hipMemcpyDeviceToHost), "x D2H");
-    for (int q = 0; q < cur; ++q) {
-      double* xr = x_host + (int64_t)(done + q) * n;
-      const double* yq = yh.data() + (size_t)q * n;
-      for (int i = 0; i < n; ++i) xr[i] = yq[S.order[i]];
-    }
-    done += cur;
-  }
-  return 0;
-}
-
-// ---- blocked solve for many right-hand sides ---------------------------------------------------
-int Engine::prepare_solve_many(bool host_stage) {
-  int rc = prepare_solve();
-  if (rc) return rc;
-  const Symbolic& S = *S_;
-  const size_t wb = sizeof(double) * 32 * (size_t)std::max(1, S.n);
-  // (a failure here leaves the factor and the existing solve usable: the engine's status is not touched)
-  hipError_t e = hipSuccess;
-  if (!d_smW_) e = dalloc((void**)&d_smW_, wb);
-  if (e == hipSuccess && !d_smorder_) {
-    std::vector<int> order(S.order.begin(), S.order.end());
-    if (order.empty()) order.push_back(0);
-    e = dev_upload(&d_smorder_, order);
-  }
-  if (e == hipSuccess && host_stage && !d_smstage_) e = dalloc((void**)&d_smstage_, wb);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    sm_err_ = "solve_many: not enough device memory for the workspace of 32 right-hand sides (" +
-              std::to_string(wb >> 20) + " MiB): " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
-  }
-  if (sm_one_fwd_.size() != sprog_.fwd.size() || sm_one_bwd_.size() != sprog_.bwd.size()) {
-    // a launch on ONE block column (every step of the upper levels): its descriptor travels by value
-    auto ones = [&](const std::vector<SolveLaunch>& ls, std::vector<const SolveUnit*>& out) {
-      out.assign(ls.size(), nullptr);
-      for (size_t i = 0; i < ls.size(); ++i) {
-        if (ls[i].count <= 0) continue;
-        if (ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD) {
-          if (ls[i].count == 1) out[i] = &sprog_.units[(size_t)sprog_.diag_list[(size_t)ls[i].first]];
-        } else {
-          const UpdTile* tl = sprog_.tiles.data() + ls[i].first;
-          bool same = true;
-          for (int64_t q = 0; same && q < ls[i].count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
-          if (same && ls[i].count < 32768) out[i] = &sprog_.units[(size_t)tl[0].unit];
-        }
-      }
-    };
-    ones(sprog_.fwd, sm_one_fwd_);
-    ones(sprog_.bwd, sm_one_bwd_);
-  }
-  return 0;
-}
-
-// one block of nv <= rb vectors: pack, the sweeps `job` asks for, unpack (enqueue only)
-void Engine::enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order) {
-  const int n = S_->n;
-  const int* order = pivot_order ? nullptr : d_smorder_;
-  launch_solve_many_pack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
-  auto run = [&](const std::vector<SolveLaunch>& ls, const std::vector<const SolveUnit*>& one) {
-    for (size_t i = 0; i < ls.size(); ++i)
-      launch_solve_many(stream_, ls[i].kind, d_slist_, d_stiles_, ls[i].first, ls[i].count, d_sunits_, d_L_, d_dinv_,
-                        d_rlist_, d_smW_, rb, one[i]);
-  };
-  if (job == 0 || job == 1) run(sprog_.fwd, sm_one_fwd_);
-  if (job == 0 || job == 2) run(sprog_.bwd, sm_one_bwd_);
-  launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
-}
-
-int Engine::solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
-  if (status_) return status_;
-  sm_err_.clear();
-  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
-  if (pending_) return -10;          // (the caller waits first)
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_many(false);
-  if (rc) return rc;
-  // 32 per sweep while at least 32 are left; the tail as one zero-padded block of 16 or 32
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
-    enqueue_solve_many_block(x_dev + (int64_t)done * ldx, ldx, nv, rb, job, pivot_order);
-    done += nv;
-  }
-  HIPCHK(hipGetLastError(), "solve_many launch");
-  return sync_stream(stream_, "solve_many sync");
-}
-
-int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
-  if (status_) return status_;
-  sm_err_.clear();
-  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_many(true);
-  if (rc) return rc;
-  const int n = S_->n;
-  const size_t vb = sizeof(double) * (size_t)n;
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
-    double* xb = x_host + (int64_t)done * ldx;
-    // the block in the caller's layout, its n-vectors only (the permutation happens on the device)
-    if (ldx == n) {
-      HIPCHK(hipMemcpyAsync(d_smstage_, xb, vb * (size_t)nv, hipMemcpyHostToDevice, stream_), "rhs H2D");
-    } else {
-      for (int q = 0; q < nv; ++q)
-        HIPCHK(hipMemcpyAsync(d_smstage_ + (size_t)q * n, xb + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "rhs H2D");
-    }
-    enqueue_solve_many_block(d_smstage_, n, nv, rb, job, false);
-    HIPCHK(hipGetLastError(), "solve_many launch");
-    if (ldx == n) {
-      HIPCHK(hipMemcpyAsync(xb, d_smstage_, vb * (size_t)nv, hipMemcpyDeviceToHost, stream_), "x D2H");
-    } else {
-      for (int q = 0; q < nv; ++q)
-        HIPCHK(hipMemcpyAsync(xb + (int64_t)q * ldx, d_smstage_ + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "x D2H");
-    }
-    if ((rc = sync_stream(stream_, "solve_many sync"))) return rc;
-    done += nv;
-  }
-  return 0;
-}
-
-// ---- reproducible solve ----------------------------------------------------------------------------
-static std::atomic<bool> g_rsolve_poison{false};
-void set_rsolve_poison(bool on) { g_rsolve_poison.store(on); }
-
-int Engine::prepare_solve_repro() {
-  int rc = prepare_solve();
-  if (rc) return rc;
-  if (rs_ready_) return 0;
-  const Symbolic& S = *S_;
-  RsolveTables R;
-  build_rsolve_tables(S, sprog_, R);
-  std::vector<int> order(S.order.begin(), S.order.end());
-  rs_stride_ = std::max<int64_t>(1, std::max(R.frows, R.bsize));
-  const size_t sb = sizeof(double) * 4 * (size_t)rs_stride_;
-  TableStager tab;
-  tab.add(&d_rsfslot_, R.fslot);
-  tab.add(&d_rsbfirst_, R.bfirst);
-  tab.add(&d_rsgptr_, R.gptr);
-  tab.add(&d_rsgsrc_, R.gsrc);
-  tab.add(&d_rsbslot_, R.bslot);
-  tab.add(&d_rsorder_, order);
-  // (a failure here leaves the factor and the other solves usable: the engine's status is not touched)
-  hipError_t e = tab.commit(&d_rstab_, [this](void** q, size_t b) { return dalloc(q, b); });
-  if (e == hipSuccess) e = dalloc((void**)&d_rsscratch_, sb);
-  if (e == hipSuccess) e = dalloc((void**)&d_rsstage_, sizeof(double) * 4 * (size_t)std::max(1, S.n));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
-      if (p) release_buffer(p);
-    d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
-    rs_err_ = "solve_repro: not enough device memory for the tables and the scratch of 4 right-hand sides (" +
-              std::to_string((sb + tab.host.size()) >> 20) + " MiB): " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
-  }
-  rs_ready_ = true;
-  return 0;
-}
-
-int Engine::release_solve_repro() {
-  if (status_) return status_;
-  if (!rs_ready_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "solve_repro release")) return rc;
-  for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
-    if (p) release_buffer(p);
-  d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
-  rs_ready_ = false;
-  return 0;
-}
-
-// the sweeps `job` asks for on cur = 1, 2 or 4 vectors in pivot order, y[q * ldy + p] (enqueue only)
-int Engine::enqueue_solve_repro(double* y, int64_t ldy, int cur, int job) {
-  const RsolveView rv{d_rsfslot_, d_rsbfirst_, d_rsgptr_, d_rsgsrc_, d_rsbslot_, d_rsscratch_, rs_stride_};
-  auto run = [&](const std::vector<SolveLaunch>& ls, const std::vector<SolveLaunchInfo>& li) -> int {
-    // debug: a slot that is read without having been written in this sweep shows up as NaN
-    if (g_rsolve_poison.load())
-      HIPCHK(hipMemsetAsync(d_rsscratch_, 0xFF, sizeof(double) * 4 * (size_t)rs_stride_, stream_), "poison the scratch");
-    for (size_t i = 0; i < ls.size(); ++i)
-      launch_solve_repro(stream_, ls[i].kind, d_slist_, d_stiles_, ls[i].first, ls[i].count, d_sunits_, d_L_, d_dinv_,
-                         d_rlist_, y, cur, ldy, li[i].four, li[i].one, rv);
-    return 0;
-  };
-  int rc = 0;
-  if (job == 0 || job == 1) rc = run(sprog_.fwd, sv_fwd_);
-  if (!rc && (job == 0 || job == 2)) rc = run(sprog_.bwd, sv_bwd_);
-  return rc;
-}
-
-int Engine::solve_repro_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
-  if (status_) return status_;
-  rs_err_.clear();
-  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
-  if (pending_) return -10;          // (the caller waits first)
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_repro();
-  if (rc) return rc;
-  const int n = S_->n;
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
-    double* xg = x_dev + (int64_t)done * ldx;
-    if (pivot_order) {
-      if ((rc = enqueue_solve_repro(xg, ldx, cur, job))) return rc;
-    } else {
-      launch_solve_repro_perm(stream_, false, xg, ldx, d_rsorder_, n, cur, d_y_);
-      if ((rc = enqueue_solve_repro(d_y_, (int64_t)n, cur, job))) return rc;
-      launch_solve_repro_perm(stream_, true, xg, ldx, d_rsorder_, n, cur, d_y_);
-    }
-    done += cur;
-  }
-  HIPCHK(hipGetLastError(), "solve_repro launch");
-  return sync_stream(stream_, "solve_repro sync");
-}
-
-int Engine::solve_repro(double* x_host, int nrhs, int64_t ldx, int job) {
-  if (status_) return status_;
-  rs_err_.clear();
-  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_repro();
-  if (rc) return rc;
-  const int n = S_->n;
-  const size_t vb = sizeof(double) * (size_t)n;
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
-    double* xg = x_host + (int64_t)done * ldx;
-    // the group in the caller's layout, its n-vectors only (the permutation happens on the device)
-    for (int q = 0; q < cur; ++q)
-      HIPCHK(hipMemcpyAsync(d_rsstage_ + (size_t)q * n, xg + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "rhs H2D");
-    launch_solve_repro_perm(stream_, false, d_rsstage_, (int64_t)n, d_rsorder_, n, cur, d_y_);
-    if ((rc = enqueue_solve_repro(d_y_, (int64_t)n, cur, job))) return rc;
-    launch_solve_repro_perm(stream_, true, d_rsstage_, (int64_t)n, d_rsorder_, n, cur, d_y_);
-    HIPCHK(hipGetLastError(), "solve_repro launch");
-    for (int q = 0; q < cur; ++q)
-      HIPCHK(hipMemcpyAsync(xg + (int64_t)q * ldx, d_rsstage_ + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "x D2H");
-    if ((rc = sync_stream(stream_, "solve_repro sync"))) return rc;
-    done += cur;
-  }
-  return 0;
-}
-
-// ---- refined solves --------------------------------------------------------------------------------
-// Operator tables (once per engine) and the work vectors of one group, all or nothing: a failed allocation
-// gives back what it got and leaves the factor and every other solve usable.
-int Engine::prepare_refine(bool host_val) {
-  const Symbolic& S = *S_;
-  const size_t n1 = (size_t)std::max(1, S.n);
-  hipError_t e = hipSuccess;
-  size_t want = 0;
-  if (!refine_ready_) {
-    std::vector<int64_t> rowptr;
-    std::vector<int> col, src, rows, order(S.order.begin(), S.order.end());
-    build_matvec_tables(S, rowptr, col, src);
-    // rows by length: at most 16 entries -> 4 lanes per row, at most 128 -> 16 lanes, longer -> a wavefront
-    rows.reserve((size_t)S.n);
-    for (int c = 0; c < 3; ++c) {
-      rf_nrows_[c] = 0;
-      for (int p = 0; p < S.n; ++p) {
-        const int64_t len = rowptr[(size_t)p + 1] - rowptr[(size_t)p];
-        const int cls = len <= 16 ? 0 : (len <= 128 ? 1 : 2);
-        if (cls == c) { rows.push_back(p); ++rf_nrows_[c]; }
-      }
-    }
-    RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
-    const size_t slots = (size_t)std::max(std::max(spmv_slots(op), vec_slots(S.n)), RF_AMAX_WG);
-    TableStager tab;
-    tab.add(&d_rfrowptr_, rowptr);
-    tab.add(&d_rfcol_, col);
-    tab.add(&d_rfsrc_, src);
-    tab.add(&d_rfrows_, rows);
-    tab.add(&d_rforder_, order);
-    e = tab.commit(&d_rftab_, [this](void** q, size_t b) { return dalloc(q, b); });
-    want = sizeof(double) * 6 * RF_G * n1;
-    if (e == hipSuccess) e = dalloc((void**)&d_rfwork_, want);
-    if (e == hipSuccess) e = dalloc((void**)&d_rfpart_, sizeof(double) * 2 * RF_G * slots);
-    if (e == hipSuccess) e = dalloc((void**)&d_rfds_, sizeof(double) * RF_DS);
-    if (e == hipSuccess) e = dalloc((void**)&d_rfis_, sizeof(int) * RF_IS);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rfis_, 0, sizeof(int) * RF_IS, stream_);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rfds_, 0, sizeof(double) * RF_DS, stream_);
-  }
-  if (e == hipSuccess && host_val && !d_rfval_) {
-    want = sizeof(double) * (size_t)std::max<int64_t>(1, S.nnzA);
-    e = dalloc((void**)&d_rfval_, want);
-    if (e != hipSuccess) d_rfval_ = nullptr;
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (!refine_ready_) {
-      for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_})
-        if (p) release_buffer(p);
-      d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr;
-    }
-    rf_err_ = "refined solve: not enough device memory for the operator and the work vectors (" +
-              std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
-  }
-  refine_ready_ = true;
-  return 0;
-}
-
-int Engine::release_refine() {
-  if (status_) return status_;
-  if (!refine_ready_ && !d_rfval_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "refine release")) return rc;
-  for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_, (void*)d_rfval_})
-    if (p) release_buffer(p);
-  d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr; d_rfval_ = nullptr;
-  refine_ready_ = false;
-  return 0;
-}
-
-int Engine::matvec(const double* val, int nvec, const double* x, int64_t ldx, double* y, int64_t ldy, bool dev,
-                   bool pivot_order) {
-  if (status_) return status_;
-  rf_err_.clear();
-  const int n = S_->n;
-  if (!val || !x || !y || nvec < 0 || ldx < n || ldy < n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;   // (the caller waits first)
-  if (nvec == 0 || n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_refine(!dev);
-  if (rc) return rc;
-  const size_t vb = sizeof(double) * (size_t)n;
-  const double* dval = val;
-  if (!dev) {
-    HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");
-    dval = d_rfval_;
-  }
-  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
-  const size_t gn = (size_t)RF_G * (size_t)n;
-  double *wb = d_rfwork_, *wr = d_rfwork_ + 2 * gn, *wq = d_rfwork_ + 4 * gn;
-  for (int done = 0; done < nvec;) {
-    const int nv = std::min(RF_G, nvec - done);
-    const double* xg = x + (int64_t)done * ldx;
-    double* yg = y + (int64_t)done * ldy;
-    if (dev && pivot_order) {
-      launch_spmv(stream_, op, dval, xg, ldx, nullptr, yg, ldy, nv, nullptr, 0, nullptr);
-    } else if (dev) {
-      launch_rf_pack(stream_, n, nv, xg, ldx, d_rforder_, wb);
-      launch_spmv(stream_, op, dval, wb, n, nullptr, wr, n, nv, nullptr, 0, nullptr);
-      launch_rf_unpack(stream_, n, nv, yg, ldy, d_rforder_, wr);
-    } else {
-      for (int q = 0; q < nv; ++q)
-        HIPCHK(hipMemcpyAsync(wq + (size_t)q * n, xg + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "x H2D");
-      launch_rf_pack(stream_, n, nv, wq, n, d_rforder_, wb);
-      launch_spmv(stream_, op, dval, wb, n, nullptr, wr, n, nv, nullptr, 0, nullptr);
-      launch_rf_unpack(stream_, n, nv, wq, n, d_rforder_, wr);
-      for (int q = 0; q < nv; ++q)
-        HIPCHK(hipMemcpyAsync(yg + (int64_t)q * ldy, wq + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "y D2H");
-    }
-    HIPCHK(hipGetLastError(), "matvec launch");
-    if (!dev && (rc = sync_stream(stream_, "matvec sync"))) return rc;
-    done += nv;
-  }
-  return sync_stream(stream_, "matvec sync");
-}
-
-// both sweeps with the current factor on nv work vectors (pivot order, ld = n), through the existing paths.
-// The sweeps take all nv columns, frozen vectors included (their columns are zero: launch_rf_copy), since the
-// existing paths know no mask; the columns of a sweep are independent of each other.
-int Engine::refine_apply_factor(double* v, int nv) {
-  if (repro_on_) {   // every group size through the reproducible path, in sweeps of 4
-    const int rc = solve_repro_dev(v, nv, (int64_t)S_->n, 0, true);
-    if (rc && !rs_err_.empty()) rf_err_ = rs_err_;
-    return rc;
-  }
-  const int rc = nv <= 4 ? solve_dev(v, nv, 0, -1) : solve_many_dev(v, nv, (int64_t)S_->n, 0, true);
-  if (rc && !sm_err_.empty()) rf_err_ = sm_err_;
-  return rc;
-}
-
-// the one array that crosses the bus per iteration: out[q] = best confirmed error, out[32 + q] = state
-int Engine::refine_readback(int nv, std::vector<double>& out) {
-  (void)nv;
-  HIPCHK(hipGetLastError(), "refine launch");
-  HIPCHK(hipMemcpyAsync(out.data(), d_rfds_ + RFD_OUT, sizeof(double) * 2 * RF_G, hipMemcpyDeviceToHost, stream_),
-         "refine state D2H");
-  return sync_stream(stream_, "refine sync");
-}
-
-int Engine::refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol,
-                         int max_iter, int* iterations, double* error) {
-  const int n = S_->n;
-  const size_t vb = sizeof(double) * (size_t)n;
-  const size_t gn = (size_t)RF_G * (size_t)n;
-  double *B = d_rfwork_, *X = B + gn, *R = X + gn, *P = R + gn, *Q = P + gn, *XB = Q + gn;
-  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
-  const int sslots = spmv_slots(op), vslots = vec_slots(n);
-  const int* st = d_rfis_ + RFI_ST;
-  const int* decl = d_rfis_ + RFI_DECL;
-  const int* improve = d_rfis_ + RFI_IMPROVE;
-  int rc = 0;
-  if (dev) {
-    launch_rf_pack(stream_, n, nv, x, ldx, d_rforder_, B);
-  } else {
-    for (int q = 0; q < nv; ++q)
-      HIPCHK(hipMemcpyAsync(Q + (size_t)q * n, x + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "rhs H2D");
-    launch_rf_pack(stream_, n, nv, Q, n, d_rforder_, B);
-  }
-  launch_rf_dot(stream_, n, nv, B, B, nullptr, 0, d_rfpart_);
-  launch_rf_finalize(stream_, RFS_BNORM, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
-  // x = M^-1 b, r = b - A x, the error of the first iterate
-  launch_rf_copy(stream_, n, nv, X, B, nullptr, 0);
-  if ((rc = refine_apply_factor(X, nv))) return rc;
-  auto true_residual = [&](const int* sel, int want, int flag) {
-    launch_spmv(stream_, op, dval, X, n, B, R, n, nv, sel, want, d_rfpart_);
-    launch_rf_finalize(stream_, RFS_TRUE, d_rfpart_, sslots, nv, tol, flag, d_rfds_, d_rfis_);
-    launch_rf_copy(stream_, n, nv, XB, X, improve, 1);   // the best confirmed iterate
-  };
-  true_residual(st, 0, 0);
-  std::vector<double> out(2 * RF_G, 0.0);
-  if ((rc = refine_readback(nv, out))) return rc;
-  auto active = [&]() {
-    for (int q = 0; q < nv; ++q)
-      if (out[(size_t)RF_G + q] == 0.0) return true;
-    return false;
-  };
-  std::vector<int> its((size_t)nv, 0);
-  for (int it = 0; it < max_iter && active();) {
-    ++it;
-    for (int q = 0; q < nv; ++q)
-      if (out[(size_t)RF_G + q] == 0.0) its[(size_t)q] = it;
-    if (method == 0) {
-      // x += M^-1 r ; r = b - A x
-      launch_rf_copy(stream_, n, nv, P, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
-      if ((rc = refine_apply_factor(P, nv))) return rc;
-      launch_rf_axpy(stream_, n, nv, nullptr, X, P, nullptr, nullptr, st, 0, nullptr);
-      true_residual(st, 0, 0);
-    } else {
-      // z = M^-1 r (in q) ; beta = r.z / (r.z)_old, 0 after a restart ; p = z + beta p
-      launch_rf_copy(stream_, n, nv, Q, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
-      if ((rc = refine_apply_factor(Q, nv))) return rc;
-      launch_rf_dot(stream_, n, nv, R, Q, st, 0, d_rfpart_);
-      launch_rf_finalize(stream_, RFS_BETA, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
-      launch_rf_pupdate(stream_, n, nv, d_rfds_ + RFD_BETA, P, Q, st, 0);
-      // q = A p with the partials of p.q ; alpha = r.z / p.q ; x += alpha p, r -= alpha q
-      launch_spmv(stream_, op, dval, P, n, nullptr, Q, n, nv, st, 0, d_rfpart_);
-      launch_rf_finalize(stream_, RFS_ALPHA, d_rfpart_, sslots, nv, tol, 0, d_rfds_, d_rfis_);
-      launch_rf_axpy(stream_, n, nv, d_rfds_ + RFD_ALPHA, X, P, R, Q, st, 0, d_rfpart_);
-      launch_rf_finalize(stream_, RFS_REC, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
-      // what the recurrence declares converged is confirmed with a true residual (no work if nothing is declared)
-      true_residual(decl, 1, 1);
-    }
-    if ((rc = refine_readback(nv, out))) return rc;
-  }
-  if (method == 1 && active()) {
-    // out of iterations: the error reported is that of a true residual
-    launch_rf_finalize(stream_, RFS_FINAL, d_rfpart_, 0, nv, tol, 0, d_rfds_, d_rfis_);
-    true_residual(decl, 1, 1);
-    if ((rc = refine_readback(nv, out))) return rc;
-  }
-  if (dev) {
-    launch_rf_unpack(stream_, n, nv, x, ldx, d_rforder_, XB);
-  } else {
-    launch_rf_unpack(stream_, n, nv, Q, n, d_rforder_, XB);
-    for (int q = 0; q < nv; ++q)
-      HIPCHK(hipMemcpyAsync(x + (int64_t)q * ldx, Q + (size_t)q * n, vb, hipMemcpyDeviceToHost, stream_), "x D2H");
-  }
-  HIPCHK(hipGetLastError(), "refine launch");
-  if ((rc = sync_stream(stream_, "refine sync"))) return rc;
-  int worst = 0;
-  for (int q = 0; q < nv; ++q) {
-    if (iterations) iterations[q] = its[(size_t)q];
-    if (error) error[q] = out[(size_t)q];
-    if (out[(size_t)RF_G + q] != 1.0) worst = 1;
-  }
-  return worst;
-}
-
-int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, bool dev, int method, double tol,
-                          int max_iter, int* iterations, double* error) {
-  if (status_) return status_;
-  rf_err_.clear();
-  const int n = S_->n;
-  if (!val || !x || nrhs < 0 || ldx < n || method < 0 || method > 1 || !(tol > 0.0) || max_iter < 0) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_ || !factored_) return -10;   // (the caller waits first)
-  if (nrhs == 0) return 0;
-  if (n == 0) {
-    for (int q = 0; q < nrhs; ++q) {
-      if (iterations) iterations[q] = 0;
-      if (error) error[q] = 0.0;
-    }
-    return 0;
-  }
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_refine(!dev);
-  if (rc) return rc;
-  const double* dval = val;
-  if (!dev) {
-    HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");
-    dval = d_rfval_;
-  }
-  launch_rf_absmax(stream_, dval, S_->nnzA, d_rfpart_);
-  launch_rf_finalize(stream_, RFS_AMAX, d_rfpart_, RF_AMAX_WG, 0, tol, 0, d_rfds_, d_rfis_);
-  int worst = 0;
-  for (int done = 0; done < nrhs;) {
-    const int nv = std::min(RF_G, nrhs - done);
-    rc = refine_group(dval, nv, x + (int64_t)done * ldx, ldx, dev, method, tol, max_iter,
-                      iterations ? iterations + done : nullptr, error ? error + done : nullptr);
-    if (rc < 0) return rc;
-    worst |= rc;
-    done += nv;
-  }
-  return worst;
 }
 
 // ---- low-rank update / downdate ---------------------------------------------------------------------
@@ -2207,8 +1535,8 @@ int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, b
 // a sweep depend on each other through the work array: one stream, program order.
 int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, int sign, const std::vector<int>& all,
                    const std::vector<int>& first) {
+  feature_err_.clear();
   if (status_) return status_;
-  ud_err_.clear();
   if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
   if (k < 0 || (k > 0 && (!wptr || !wrow || !wval)) || (sign != 1 && sign != -1) || (int)first.size() != k) return -10;
   if (pending_) {
@@ -2216,7 +1544,7 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
     if (rc) return rc;
   }
   if (!factored_ || ud_invalid_) {
-    ud_err_ = "update: nothing has been factorized on this handle";
+    feature_err_ = "update: nothing has been factorized on this handle";
     return -10;
   }
   const Symbolic& S = *S_;
@@ -2273,9 +1601,9 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
         if (d_udW_) release_buffer(d_udW_);
         d_udW_ = d_udcoef_ = nullptr;
       }
-      ud_err_ = "update: not enough device memory for the work array (" + std::to_string(wb >> 10) +
-                " KiB), the coefficient scratch and the entries of W: " + hipGetErrorString(e);
-      return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : -30;
+      feature_err_ = "update: not enough device memory for the work array (" + std::to_string(wb >> 10) +
+                     " KiB), the coefficient scratch and the entries of W: " + hipGetErrorString(e);
+      return alloc_code(e);
     }
   }
   int* d_flag = reinterpret_cast<int*>(d_udcoef_ + (size_t)maxw * kUpdownVec * 3);
@@ -2326,8 +1654,8 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   if (flag != INT_MAX) {
     npd_col_ = flag - 1;
     ud_invalid_ = true;
-    ud_err_ = "downdate: the modified matrix is not positive definite (pivot column " + std::to_string(flag) +
-              " in elimination order); the factor is invalid until the next factorization";
+    feature_err_ = "downdate: the modified matrix is not positive definite (pivot column " + std::to_string(flag) +
+                   " in elimination order); the factor is invalid until the next factorization";
     return kErrNotPosDef;
   }
   return 0;
@@ -2396,13 +1724,11 @@ BatchView Engine::batch_view() const {
   return v;
 }
 
-static int batch_alloc_code(hipError_t e) { return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : kErrHip; }
-
 // program, solve program and index tables of the batch: built and uploaded once per engine
 int Engine::prepare_batch() {
   if (bt_.ready) return 0;
   const Symbolic& S = *S_;
-  int rc = build_batch_program(S, bt_.prog, &bt_err_);
+  int rc = build_batch_program(S, bt_.prog, &feature_err_);
   if (rc) return rc;
   build_solve_program(S, 64, 64, bt_.sprog);
   // the bucketed value map: the engine's own tables where its one-pass initialisation uploaded them
@@ -2413,7 +1739,6 @@ int Engine::prepare_batch() {
   if (bt_.own_init) bucket_value_map(S, cptr, loc, src);
   std::vector<int64_t> diag;
   batch_diag_positions(S, diag);
-  std::vector<int> order(S.order.begin(), S.order.end());
   TableStager tab;
   tab.add(&bt_.units, bt_.prog.units);
   tab.add(&bt_.tiles, bt_.prog.tiles);
@@ -2425,17 +1750,17 @@ int Engine::prepare_batch() {
     tab.add(&bt_.init_src, src);
   }
   tab.add(&bt_.diag, diag);
-  tab.add(&bt_.order, order);
   tab.add(&bt_.sunits, bt_.sprog.units);
   tab.add(&bt_.slist, bt_.sprog.diag_list);
   tab.add(&bt_.stiles, bt_.sprog.tiles);
   // (a failure here leaves the single factorization usable: the engine's status is not touched)
   hipError_t e = tab.commit(&bt_.d_tab, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e == hipSuccess) e = ensure_order();
   if (e != hipSuccess) {
     (void)hipGetLastError();
     if (bt_.d_tab) { release_buffer(bt_.d_tab); bt_.d_tab = nullptr; }
-    bt_err_ = std::string("batched factorization: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
-    return batch_alloc_code(e);
+    feature_err_ = std::string("batched factorization: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
+    return alloc_code(e);
   }
   if (!bt_.own_init) {
     bt_.init_cptr = d_init_cptr_;
@@ -2472,9 +1797,9 @@ int Engine::reserve_batch(int nbatch) {
   if (e != hipSuccess) {
     (void)hipGetLastError();
     drop();
-    bt_err_ = "batched factorization: not enough device memory for " + std::to_string(nbatch) + " members (" +
-              std::to_string((lb + db) >> 20) + " MiB): " + hipGetErrorString(e);
-    return batch_alloc_code(e);
+    feature_err_ = "batched factorization: not enough device memory for " + std::to_string(nbatch) + " members (" +
+                   std::to_string((lb + db) >> 20) + " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
   }
   bt_.capacity = nbatch;
   return 0;
@@ -2489,17 +1814,17 @@ int Engine::grow_batch_buffer(double** p, size_t* have, size_t need, const char*
   if (e != hipSuccess) {
     (void)hipGetLastError();
     *p = nullptr;
-    bt_err_ = std::string("batch: not enough device memory for ") + what + " (" +
-              std::to_string((sizeof(double) * need) >> 20) + " MiB): " + hipGetErrorString(e);
-    return batch_alloc_code(e);
+    feature_err_ = std::string("batch: not enough device memory for ") + what + " (" +
+                   std::to_string((sizeof(double) * need) >> 20) + " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
   }
   *have = need;
   return 0;
 }
 
 int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t ldval) {
+  feature_err_.clear();
   if (status_) return status_;
-  bt_err_.clear();
   const int64_t nnz = S_->nnzA;
   if (!val || nbatch < 0 || ldval < nnz) return -10;
   if (opt_.nranks > 1) return -98;
@@ -2516,15 +1841,8 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   int64_t ld = ldval;
   if (!on_device) {
     if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)nnz, "the staged values"))) return rc;
-    if (nnz > 0) {
-      if (ldval == nnz) {
-        HIPCHK(hipMemcpyAsync(bt_.stage, val, sizeof(double) * (size_t)nnz * (size_t)nbatch, hipMemcpyHostToDevice, stream_), "batch val H2D");
-      } else {
-        for (int b = 0; b < nbatch; ++b)
-          HIPCHK(hipMemcpyAsync(bt_.stage + (int64_t)b * nnz, val + (int64_t)b * ldval, sizeof(double) * (size_t)nnz,
-                                hipMemcpyHostToDevice, stream_), "batch val H2D");
-      }
-    }
+    if (nnz > 0 && (rc = copy_vectors_to_device(bt_.stage, val, ldval, nbatch, "batch val H2D", nnz)))
+      return rc;
     vd = bt_.stage;
     ld = nnz;
   }
@@ -2548,7 +1866,7 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   HIPCHK(hipMemcpyAsync(bt_.hflag_pending.data(), bt_.flag, sizeof(int) * (size_t)nbatch, hipMemcpyDeviceToHost, stream_), "batch flags D2H");
   if ((rc = sync_stream(stream_, "batch factor sync"))) return rc;
   if (!fits) {
-    bt_err_ = "batched factorization: a launch of the program has more work items for ONE member than a grid holds";
+    feature_err_ = "batched factorization: a launch of the program has more work items for ONE member than a grid holds";
     return -99;
   }
   bt_.launches = nl;
@@ -2560,8 +1878,8 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
 }
 
 int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  feature_err_.clear();
   if (status_) return status_;
-  bt_err_.clear();
   const int n = S_->n;
   if (!x || nrhs < 0 || ldx < n || job < 0 || job > 2 || bt_.nbatch <= 0) return -10;
   if (nrhs == 0 || n == 0) return 0;
@@ -2571,25 +1889,19 @@ int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int jo
   if (rc) return rc;
   double* xd = x;
   int64_t ld = ldx;
-  const size_t vb = sizeof(double) * (size_t)n;
   if (!on_device) {
     // the caller's n-vectors only, packed (what lies between them is neither read nor written)
     if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, nvec * (size_t)n, "the staged right-hand sides"))) return rc;
-    if (ldx == n) {
-      HIPCHK(hipMemcpyAsync(bt_.stage, x, vb * nvec, hipMemcpyHostToDevice, stream_), "batch rhs H2D");
-    } else {
-      for (size_t q = 0; q < nvec; ++q)
-        HIPCHK(hipMemcpyAsync(bt_.stage + q * (size_t)n, x + (int64_t)q * ldx, vb, hipMemcpyHostToDevice, stream_), "batch rhs H2D");
-    }
+    if ((rc = copy_vectors(true, bt_.stage, x, ldx, (int64_t)nvec, "batch rhs H2D"))) return rc;
     xd = bt_.stage;
     ld = n;
   }
   const BatchView v = batch_view();
-  const int* order = pivot_order ? nullptr : bt_.order;
+  const int* order = pivot_order ? nullptr : d_order_;
   // (a launch whose work items for one member overflow a grid: every launch has at most as many work items as
   // the pack, which is checked first -- n / 256 blocks against the block columns and strips of n rows)
   if (launch_batch_pack(stream_, v, false, xd, ld, nrhs, order, n, bt_.Y) < 0) {
-    bt_err_ = "batch solve: nrhs vectors of one member are more work items than a grid holds";
+    feature_err_ = "batch solve: nrhs vectors of one member are more work items than a grid holds";
     return -99;
   }
   bool fits = true;
@@ -2603,18 +1915,11 @@ int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int jo
   if (job == 0 || job == 2) run(bt_.sprog.bwd);
   launch_batch_pack(stream_, v, true, xd, ld, nrhs, order, n, bt_.Y);
   HIPCHK(hipGetLastError(), "batch solve launch");
-  if (!on_device) {
-    // (the vectors of a failed member come back as they went: nothing on the device touched them)
-    if (ldx == n) {
-      HIPCHK(hipMemcpyAsync(x, bt_.stage, vb * nvec, hipMemcpyDeviceToHost, stream_), "batch x D2H");
-    } else {
-      for (size_t q = 0; q < nvec; ++q)
-        HIPCHK(hipMemcpyAsync(x + (int64_t)q * ldx, bt_.stage + q * (size_t)n, vb, hipMemcpyDeviceToHost, stream_), "batch x D2H");
-    }
-  }
+  // (the vectors of a failed member come back as they went: nothing on the device touched them)
+  if (!on_device && (rc = copy_vectors(false, bt_.stage, x, ldx, (int64_t)nvec, "batch x D2H"))) return rc;
   if ((rc = sync_stream(stream_, "batch solve sync"))) return rc;
   if (!fits) {
-    bt_err_ = "batch solve: a launch has more work items for one member than a grid holds (the vectors are not solved)";
+    feature_err_ = "batch solve: a launch has more work items for one member than a grid holds (the vectors are not solved)";
     return -99;
   }
   for (int fl : bt_.hflag)
@@ -2623,6 +1928,7 @@ int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int jo
 }
 
 int Engine::download_batch(int member, double* out, int64_t count) {
+  feature_err_.clear();
   if (status_) return status_;
   if (!out || member < 0 || member >= bt_.nbatch || count < 0) return -10;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
@@ -2635,6 +1941,7 @@ double* Engine::device_batch(int64_t* member_stride) {
 }
 
 int Engine::log_det_batch(double* out) {
+  feature_err_.clear();
   if (status_) return status_;
   if (!out || bt_.nbatch <= 0) return -10;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
@@ -2646,6 +1953,7 @@ int Engine::log_det_batch(double* out) {
 
 // the batch's storage back to the pool (the shared tables stay: they are small and per pattern)
 int Engine::release_batch() {
+  feature_err_.clear();
   if (status_) return status_;
   bt_.z_valid = false;
   if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z) { bt_.nbatch = 0; return 0; }
@@ -2686,7 +1994,7 @@ BatchSelinvView Engine::batch_selinv_view() const {
 int Engine::prepare_batch_selinv() {
   if (bt_.si_ready) return 0;
   if (build_selinv_program(*S_, 64, 64, bt_.siprog)) {
-    bt_err_ = "batched selected inversion: the row structure of a node is not contained in its ancestors'";
+    feature_err_ = "batched selected inversion: the row structure of a node is not contained in its ancestors'";
     return -10;
   }
   // a step = [SYMM] [SCALE] DIAG; the fused kernel takes it when every unit has at most 64 rows below its
@@ -2710,8 +2018,8 @@ int Engine::prepare_batch_selinv() {
   if (e != hipSuccess) {
     (void)hipGetLastError();
     if (bt_.d_sitab) { release_buffer(bt_.d_sitab); bt_.d_sitab = nullptr; }
-    bt_err_ = std::string("batched selected inversion: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
-    return batch_alloc_code(e);
+    feature_err_ = std::string("batched selected inversion: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
+    return alloc_code(e);
   }
   bt_.sstride = std::max<int64_t>(32, (P.scratch_size + 31) / 32 * 32);
   bt_.si_ready = true;
@@ -2736,8 +2044,8 @@ int Engine::reserve_batch_inverse(int nbatch) {
   if (e != hipSuccess) {
     (void)hipGetLastError();
     drop();
-    bt_err_ = "batched selected inversion: not enough device memory for the inverse arenas of " + std::to_string(nbatch) +
-              " members (" + std::to_string((zb + sb) >> 20) + " MiB): " + hipGetErrorString(e);
+    feature_err_ = "batched selected inversion: not enough device memory for the inverse arenas of " + std::to_string(nbatch) +
+                   " members (" + std::to_string((zb + sb) >> 20) + " MiB): " + hipGetErrorString(e);
     return -1;
   }
   bt_.z_capacity = nbatch;
@@ -2745,8 +2053,8 @@ int Engine::reserve_batch_inverse(int nbatch) {
 }
 
 int Engine::selected_inverse_batch() {
+  feature_err_.clear();
   if (status_) return status_;
-  bt_err_.clear();
   if (opt_.nranks > 1) return -98;
   if (pending_ || bt_.nbatch <= 0) return -10;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
@@ -2775,7 +2083,7 @@ int Engine::selected_inverse_batch() {
   HIPCHK(hipGetLastError(), "batch selinv launch");
   if ((rc = sync_stream(stream_, "batch selinv sync"))) return rc;
   if (!fits) {
-    bt_err_ = "batched selected inversion: a launch of the program has more work items for ONE member than a grid holds";
+    feature_err_ = "batched selected inversion: a launch of the program has more work items for ONE member than a grid holds";
     return -99;
   }
   bt_.si_launches = nl;
@@ -2786,6 +2094,7 @@ int Engine::selected_inverse_batch() {
 }
 
 int Engine::download_inverse_batch(int member, double* out, int64_t count) {
+  feature_err_.clear();
   if (status_) return status_;
   if (!bt_.z_valid || !out || member < 0 || member >= bt_.nbatch || count < 0) return -10;
   if (bt_.hflag[(size_t)member] != INT_MAX) return kErrNotPosDef;
@@ -2799,38 +2108,27 @@ double* Engine::device_inverse_batch(int64_t* member_stride) {
   return ok ? bt_.Z : nullptr;
 }
 
-int Engine::batch_rows_to_host(double* out, int64_t ldout, int nrow, int64_t len, const char* what) {
-  if (ldout == len) {
-    HIPCHK(hipMemcpyAsync(out, bt_.stage, sizeof(double) * (size_t)len * (size_t)nrow, hipMemcpyDeviceToHost, stream_), what);
-  } else {
-    for (int r = 0; r < nrow; ++r)
-      HIPCHK(hipMemcpyAsync(out + (int64_t)r * ldout, bt_.stage + (int64_t)r * len, sizeof(double) * (size_t)len,
-                            hipMemcpyDeviceToHost, stream_), what);
-  }
-  return 0;
-}
-
 int Engine::inverse_diag_batch(double* out, int64_t ldout) {
+  feature_err_.clear();
   if (status_) return status_;
-  bt_err_.clear();
   const int n = S_->n;
   if (!bt_.z_valid || !out || ldout < n || bt_.nbatch <= 0) return -10;
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   int rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)bt_.nbatch * (size_t)n, "the gathered diagonals");
   if (rc) return rc;
-  if (launch_batch_selinv_diag_gather(stream_, batch_selinv_view(), bt_.diag, bt_.order, n, bt_.stage, n) < 0) {
-    bt_err_ = "batch inverse diagonal: one member's entries are more work items than a grid holds";
+  if (launch_batch_selinv_diag_gather(stream_, batch_selinv_view(), bt_.diag, d_order_, n, bt_.stage, n) < 0) {
+    feature_err_ = "batch inverse diagonal: one member's entries are more work items than a grid holds";
     return -99;
   }
   HIPCHK(hipGetLastError(), "batch inverse diag launch");
-  if ((rc = batch_rows_to_host(out, ldout, bt_.nbatch, n, "batch inverse diag D2H"))) return rc;
+  if ((rc = copy_vectors(false, bt_.stage, out, ldout, bt_.nbatch, "batch inverse diag D2H"))) return rc;
   return sync_stream(stream_, "batch inverse diag sync");
 }
 
 int Engine::inverse_on_pattern_batch(double* out, int64_t ldout) {
+  feature_err_.clear();
   if (status_) return status_;
-  bt_err_.clear();
   const int64_t nnz = S_->nnzA;
   if (!bt_.z_valid || !out || ldout < nnz || bt_.nbatch <= 0) return -10;
   if (nnz == 0) return 0;
@@ -2838,16 +2136,17 @@ int Engine::inverse_on_pattern_batch(double* out, int64_t ldout) {
   int rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)bt_.nbatch * (size_t)nnz, "the gathered entries");
   if (rc) return rc;
   if (launch_batch_selinv_pattern(stream_, batch_selinv_view(), d_map_dst_, d_map_src_, nmap_, bt_.stage, nnz) < 0) {
-    bt_err_ = "batch inverse on pattern: one member's entries are more work items than a grid holds";
+    feature_err_ = "batch inverse on pattern: one member's entries are more work items than a grid holds";
     return -99;
   }
   HIPCHK(hipGetLastError(), "batch inverse on pattern launch");
-  if ((rc = batch_rows_to_host(out, ldout, bt_.nbatch, nnz, "batch inverse on pattern D2H"))) return rc;
+  if ((rc = copy_vectors(false, bt_.stage, out, ldout, bt_.nbatch, "batch inverse on pattern D2H", nnz))) return rc;
   return sync_stream(stream_, "batch inverse on pattern sync");
 }
 
 // the inverse arenas and the step scratch back to the pool; the batch factor and its solve stay
 int Engine::release_inverse_batch() {
+  feature_err_.clear();
   if (status_) return status_;
   bt_.z_valid = false;
   bt_.si_launches = 0;

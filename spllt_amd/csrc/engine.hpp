@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "kernels.hpp"
 #include "schedule.hpp"
 #include "symbolic.hpp"
 
@@ -50,9 +51,6 @@ struct EngineOptions {
                            // program, -1 by problem size (env SPLLT_HIP_GRAPH overrides)
 };
 
-struct BatchView;         // kernels.hpp
-struct BatchSelinvView;   // kernels.hpp
-
 // debug hook (spllt_hip_debug "batch_selinv_fused=0|1"): 0 forces the three-launch form of every step of the
 // batched selected inversion; process-wide, read when an inversion is enqueued
 void set_batch_selinv_fused(bool on);
@@ -90,6 +88,9 @@ class Engine {
   bool comm_rehearsal() const { return comm_rehearsal_; }
   void poison(const std::string& why) { poisoned_ = true; status_ = -30; err_ = why; }
   const std::string& error() const { return err_; }
+  // what the last call of a feature below (blocked / reproducible / refined solve, update, selected inversion,
+  // batch) has to say about its failure; empty: see error().  Every such call clears it on entry.
+  const std::string& feature_error() const { return feature_err_; }
 
   // spllt_factor: enqueue H2D of val, value scatter and the whole program.
   int factor_async(const double* val_host, int64_t nnz);
@@ -140,7 +141,6 @@ class Engine {
   // outside those ranges is read or written.  The strips add with fp64 atomics: reproducible to rounding.
   int solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order);
   int solve_many(double* x_host, int nrhs, int64_t ldx, int job);   // host vectors, user order
-  const std::string& solve_many_error() const { return sm_err_; }
   // ---- reproducible solve (solve_repro.hip, single GPU): the substitution program of solve_dev without an
   // atomic add -- strips store their products, the diagonal launches subtract them in the order of the
   // RsolveTables.  Same factor bits + same right-hand-side bits = same solution bits, whatever the group
@@ -154,7 +154,6 @@ class Engine {
   int release_solve_repro();                                          // tables and scratch back to the pool
   // on: solve(), solve_dev(phase -1) and the preconditioner of solve_refined go through the path above
   void set_reproducible_solve(bool on) { repro_on_ = on; }
-  const std::string& solve_repro_error() const { return rs_err_; }
   // ---- refined solves (refine.hip, single GPU): the operator A on the analysed pattern, gather-only, in
   // pivot order, and iterative refinement / conjugate gradients preconditioned by the CURRENT factor, to a
   // requested backward error.  Groups of 32 vectors; the preconditioner is solve_dev (up to 4 vectors) or
@@ -168,7 +167,6 @@ class Engine {
                     int max_iter, int* iterations, double* error);
   int release_refine();     // operator tables and work vectors back to the pool
   bool factored() const { return factored_ && !ud_invalid_; }
-  const std::string& refine_error() const { return rf_err_; }
   // ---- low-rank update / downdate (updown.hip, single GPU): the factor of P (A + sign W W^T) P^T in place of
   // the current one, same layout, the dinv slots of the visited block columns rebuilt -- every solve then works
   // on the modified factor.  W: k columns, CSC, 1-based, user variable order; sign +1 / -1.  Every check
@@ -185,7 +183,6 @@ class Engine {
   bool factor_valid() const { return !ud_invalid_; }     // false: a failed downdate destroyed the factor
   // of the last updown(): block columns visited, entries of L in them, kernel launches, passes
   const int64_t* updown_info() const { return ud_info_; }
-  const std::string& updown_error() const { return ud_err_; }
   // ---- selected inversion (selinv.hip, single GPU): Z = (P A P^T)^-1 on the pattern of L, in a
   // second arena with L's layout.  Computed from the current factor (after wait()); a later
   // factorization marks it stale: the readers below then fail instead of returning old numbers.
@@ -200,7 +197,6 @@ class Engine {
   int inverse_on_pattern(double* out);
   double* device_Z() { return z_valid_ ? d_Z_ : nullptr; }
   const SelinvProgram& selinv_program() const { return siprog_; }
-  const std::string& selinv_error() const { return si_err_; }
   // ---- batched factorization (batch.hip, single GPU): nbatch value sets on this pattern, factorized and
   // solved together by a second program of the same Symbolic (build_batch_program) whose every launch
   // carries all members.  The batch has its own arenas, dinv scratch and flags; the tables are shared
@@ -214,7 +210,6 @@ class Engine {
   int log_det_batch(double* out);
   int batch_launches() const { return bt_.launches; }
   int release_batch();
-  const std::string& batch_error() const { return bt_err_; }
   // ---- batched selected inversion (batch_selinv.hip): Z_b = (P A_b P^T)^-1 on the pattern of L for every
   // member of the current batch, by a SelinvProgram built with pw = cb = 64 (the panels of the batch
   // factorization) whose every launch carries all members.  The Z arenas (capacity x lstride) and the step
@@ -360,31 +355,40 @@ class Engine {
   int* d_flag_ = nullptr;
   int* h_flag_ = nullptr;  // pinned
   // per launch of sprog_.fwd / .bwd (prepare_solve): may it use k_solve_diag4, and its ONE block column or null
-  struct SolveLaunchInfo { bool four; const SolveUnit* one; };
   std::vector<SolveLaunchInfo> sv_fwd_, sv_bwd_;
+  SolveTablesView solve_tables() const { return {d_slist_, d_stiles_, d_sunits_, d_L_, d_dinv_, d_rlist_}; }
+  // f(launch, info) for the launches `job` and `phase` ask for, in program order (engine_solve.cpp)
+  template <class F> void for_each_solve_launch(int job, int phase, F&& f) const;
+  // user variable -> pivot position, for every permutation on the device: uploaded on first use, kept
+  int* d_order_ = nullptr;
+  hipError_t ensure_order();
+  // nv vectors of len doubles (-1: n) between host + q * ldx and the packed device block dev, on stream_
+  int copy_vectors(bool to_device, double* dev, double* host, int64_t ldx, int64_t nv, const char* what,
+                   int64_t len = -1);
+  // (a read-only host side can only go to the device)
+  int copy_vectors_to_device(double* dev, const double* host, int64_t ldx, int64_t nv, const char* what,
+                             int64_t len = -1) {
+    return copy_vectors(true, dev, const_cast<double*>(host), ldx, nv, what, len);
+  }
+  std::string feature_err_;
   // reproducible solve (tables and scratch taken on first use, all or nothing)
   int enqueue_solve_repro(double* y, int64_t ldy, int cur, int job);
   bool repro_on_ = false;
   bool rs_ready_ = false;
-  std::string rs_err_;
   char* d_rstab_ = nullptr;        // one allocation behind the tables below
   int64_t* d_rsfslot_ = nullptr;
   int64_t* d_rsbfirst_ = nullptr;
   int64_t* d_rsgptr_ = nullptr;
   int64_t* d_rsgsrc_ = nullptr;
   int64_t* d_rsbslot_ = nullptr;
-  int* d_rsorder_ = nullptr;       // user variable -> pivot position
   double* d_rsscratch_ = nullptr;  // 4 x rs_stride_ doubles
   double* d_rsstage_ = nullptr;    // 4 n doubles: host vectors in the caller's order
   int64_t rs_stride_ = 0;
   // blocked solve (workspace allocated on first use, kept with the engine)
   int prepare_solve_many(bool host_stage);
   void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
-  std::string sm_err_;
   double* d_smW_ = nullptr;        // n * 32 doubles: W[p * rb + q]
   double* d_smstage_ = nullptr;    // n * 32 doubles: a block of host vectors in the caller's order (solve_many)
-  int* d_smorder_ = nullptr;       // user variable -> pivot position
-  std::vector<const SolveUnit*> sm_one_fwd_, sm_one_bwd_;   // per launch: its ONE block column, or null
   // refined solves: operator tables and work vectors (taken on first use, all or nothing)
   int prepare_refine(bool host_val);
   int refine_apply_factor(double* v, int nv);
@@ -392,14 +396,12 @@ class Engine {
   int refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol, int max_iter,
                    int* iterations, double* error);
   bool factored_ = false;          // a factorization has been enqueued on this engine
-  std::string rf_err_;
   bool refine_ready_ = false;
-  char* d_rftab_ = nullptr;        // one allocation behind the five tables below
+  char* d_rftab_ = nullptr;        // one allocation behind the four tables below
   int64_t* d_rfrowptr_ = nullptr;
   int* d_rfcol_ = nullptr;
   int* d_rfsrc_ = nullptr;
   int* d_rfrows_ = nullptr;        // rows by length class
-  int* d_rforder_ = nullptr;       // user variable -> pivot position
   int rf_nrows_[3] = {0, 0, 0};
   double* d_rfwork_ = nullptr;     // 6 x 32 x n: b, x, r, p, q, best x
   double* d_rfpart_ = nullptr;     // partial sums of the reductions
@@ -407,7 +409,6 @@ class Engine {
   int* d_rfis_ = nullptr;
   double* d_rfval_ = nullptr;      // nnz doubles: the values of a host entry point
   // update / downdate: work array and coefficient scratch (taken on first use, both or neither)
-  std::string ud_err_;
   bool ud_invalid_ = false;
   int64_t ud_info_[4] = {0, 0, 0, 0};
   double ud_device_ms_ = 0.0;
@@ -419,14 +420,12 @@ class Engine {
   SelinvProgram siprog_;
   bool selinv_ready_ = false;
   bool z_valid_ = false;
-  std::string si_err_;
   char* d_selinv_tables_ = nullptr;
   SelinvUnit* d_siunits_ = nullptr;
   UpdTile* d_sitiles_ = nullptr;
   SelinvRow* d_sirows_ = nullptr;
   int* d_sirelpos_ = nullptr;
   int64_t* d_sidiag_ = nullptr;
-  int* d_siorder_ = nullptr;
   double* d_Z_ = nullptr;
   double* d_siscratch_ = nullptr;
   double* d_siout_ = nullptr;      // n + 1 doubles: diag(A^-1), log det
@@ -446,7 +445,6 @@ class Engine {
     unsigned short* init_loc = nullptr;
     int* init_src = nullptr;
     int64_t* diag = nullptr;         // per pivot position: arena offset of its diagonal entry
-    int* order = nullptr;            // user variable -> pivot position
     SolveUnit* sunits = nullptr;
     int* slist = nullptr;
     UpdTile* stiles = nullptr;
@@ -481,7 +479,6 @@ class Engine {
     bool z_valid = false;
     int si_launches = 0;
   } bt_;
-  std::string bt_err_;
   int prepare_batch();
   int reserve_batch(int nbatch);
   int grow_batch_buffer(double** p, size_t* have, size_t need, const char* what);
@@ -489,8 +486,6 @@ class Engine {
   int prepare_batch_selinv();
   int reserve_batch_inverse(int nbatch);
   BatchSelinvView batch_selinv_view() const;
-  // the packed device rows of a batch reader (nrow x len in bt_.stage) to the caller's out[r * ldout ..]
-  int batch_rows_to_host(double* out, int64_t ldout, int nrow, int64_t len, const char* what);
 };
 
 // The batch program of a pattern: build_program with fixed options (single stream, no fused panels, no

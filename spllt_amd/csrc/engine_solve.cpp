@@ -1,0 +1,607 @@
+// The solve family of the Engine: the substitution program on the device (solve, solve_dev), the blocked solve
+// for many right-hand sides, the reproducible solve and the refined solves.  They share one walk over the
+// program's launches, one table view, one order table and one staging helper.
+#include <atomic>
+#include <climits>
+#include <cstdlib>
+
+#include "engine.hpp"
+#include "engine_detail.hpp"
+#include "refine.hpp"
+
+namespace spx {
+
+int Engine::prepare_solve() {
+  if (solve_ready_) return 0;
+  const Symbolic& S = *S_;
+  build_solve_program(S, prog_.pw, prog_.cb, sprog_, opt_.nranks > 1 ? owner_.data() : nullptr, opt_.rank);
+  if (!loc_off_.empty())
+    for (size_t b = 0; b < sprog_.units.size(); ++b)   // (units of block columns not held here are never launched)
+      if (loc_off_[b] >= 0) sprog_.units[b].off = loc_off_[b];
+  {
+    TableStager tab;
+    tab.add(&d_sunits_, sprog_.units);
+    tab.add(&d_slist_, sprog_.diag_list);
+    tab.add(&d_stiles_, sprog_.tiles);
+    HIPCHK(tab.commit(&d_solve_tables_, [this](void** q, size_t b) { return dalloc(q, b); }), "upload solve tables");
+  }
+  HIPCHK(dalloc((void**)&d_y_, sizeof(double) * 4 * (size_t)std::max(1, S.n)), "hipMalloc(y)");
+  {
+    const char* e = std::getenv("SPLLT_SOLVE_DIAG4");
+    solve_four_ = prog_.pw == 64 && prog_.cb == 64 && !(e && std::atoi(e) == 0);
+  }
+  // per launch, once: block columns of at most four 64-wide panels take the diagonal kernel that reads L in
+  // one round trip; a launch on ONE block column (every step of the upper levels) passes its descriptor by value
+  auto info = [&](const std::vector<SolveLaunch>& ls, std::vector<SolveLaunchInfo>& out) {
+    out.assign(ls.size(), SolveLaunchInfo{false, nullptr});
+    for (size_t i = 0; i < ls.size(); ++i) {
+      const bool diag = ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD;
+      bool four = solve_four_ && diag;
+      for (int64_t q = ls[i].first; four && q < ls[i].first + ls[i].count; ++q)
+        four = sprog_.units[(size_t)sprog_.diag_list[(size_t)q]].w <= 256;
+      out[i].four = four;
+      if (ls[i].count <= 0) continue;
+      if (diag) {
+        if (ls[i].count == 1) out[i].one = &sprog_.units[(size_t)sprog_.diag_list[(size_t)ls[i].first]];
+      } else {
+        const UpdTile* tl = sprog_.tiles.data() + ls[i].first;
+        bool same = true;
+        for (int64_t q = 0; same && q < ls[i].count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
+        if (same && ls[i].count < 32768) out[i].one = &sprog_.units[(size_t)tl[0].unit];
+      }
+    }
+  };
+  info(sprog_.fwd, sv_fwd_);
+  info(sprog_.bwd, sv_bwd_);
+  solve_ready_ = true;
+  return 0;
+}
+
+// the launches of the substitution program that `job` (0 both sweeps, 1 forward, 2 backward) and `phase` (-1
+// everything; 0 / 1 / 2: the phases of a partitioned solve, schedule.hpp) ask for, in program order
+template <class F>
+void Engine::for_each_solve_launch(int job, int phase, F&& f) const {
+  auto run = [&](const std::vector<SolveLaunch>& ls, const std::vector<SolveLaunchInfo>& li, size_t a, size_t b) {
+    for (size_t i = a; i < b; ++i) f(ls[i], li[i]);
+  };
+  const bool do_fwd = job == 0 || job == 1, do_bwd = job == 0 || job == 2;
+  if (do_fwd && (phase == -1 || phase == 0)) run(sprog_.fwd, sv_fwd_, 0, sprog_.fwd_nsub);
+  if (do_fwd && (phase == -1 || phase == 1)) run(sprog_.fwd, sv_fwd_, sprog_.fwd_nsub, sprog_.fwd.size());
+  if (do_bwd && (phase == -1 || phase == 1)) run(sprog_.bwd, sv_bwd_, 0, sprog_.bwd_ntop);
+  if (do_bwd && (phase == -1 || phase == 2)) run(sprog_.bwd, sv_bwd_, sprog_.bwd_ntop, sprog_.bwd.size());
+}
+
+// Substitution on device vectors in pivot order (y[q * n + p], q < nrhs), in place.
+// phase -1: everything that `job` asks for; 0/1/2: the three phases of a
+// partitioned solve (schedule.hpp, SolveProgram).
+int Engine::solve_dev(double* y_dev, int nrhs, int job, int phase) {
+  if (status_) return status_;
+  if (job < 0 || job > 2 || phase < -1 || phase > 2 || nrhs < 0 || !y_dev) return -10;
+  if (repro_on_ && phase == -1 && opt_.nranks == 1) return solve_repro_dev(y_dev, nrhs, (int64_t)S_->n, job, true);
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve();
+  if (rc) return rc;
+  const int n = S_->n;
+  const SolveTablesView tv = solve_tables();
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);   // kernel variants: 4, 2 or 1 per sweep
+    double* y = y_dev + (int64_t)done * n;
+    for_each_solve_launch(job, phase, [&](const SolveLaunch& l, const SolveLaunchInfo& li) {
+      launch_solve(stream_, tv, l, li, y, cur, (int64_t)n);
+    });
+    done += cur;
+  }
+  HIPCHK(hipGetLastError(), "solve launch");
+  return sync_stream(stream_, "solve sync");
+}
+
+int Engine::solve(double* x_host, int nrhs, int job) {
+  if (status_) return status_;
+  if (job < 0 || job > 2) return -10;
+  const Symbolic& S = *S_;
+  if (repro_on_ && opt_.nranks == 1 && nrhs >= 0 && x_host) return solve_repro(x_host, nrhs, (int64_t)S.n, job);
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve();
+  if (rc) return rc;
+  const int n = S.n;
+  // up to four right-hand sides per sweep: every entry of L is read once for all of them
+  std::vector<double> yh((size_t)n * 4);
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+    for (int q = 0; q < cur; ++q) {
+      const double* xr = x_host + (int64_t)(done + q) * n;
+      double* yq = yh.data() + (size_t)q * n;
+      for (int i = 0; i < n; ++i) yq[S.order[i]] = xr[i];
+    }
+    HIPCHK(hipMemcpyAsync(d_y_, yh.data(), sizeof(double) * (size_t)n * cur, hipMemcpyHostToDevice, stream_), "rhs H2D");
+    if (comm_ && opt_.nranks > 1) {
+      // partitioned solve inside the library (every rank passes the same right-hand sides and gets
+      // the same solution): forward substitution on the own subtrees, all-reduce of the vector,
+      // the top tree on every rank, backward substitution on the own subtrees, all-reduce
+      if (job != 0) return -98;
+      Rccl& R = rccl();
+      launch_mask(stream_, d_y_, d_owned_, n, cur, (int64_t)n);
+      if ((rc = solve_dev(d_y_, cur, 0, 0))) return rc;
+      NCCLCHK(R.all_reduce(d_y_, d_y_, (size_t)n * cur, kNcclDouble, kNcclSum, comm_, stream_), "ncclAllReduce(rhs)");
+      if ((rc = solve_dev(d_y_, cur, 0, 1))) return rc;
+      if ((rc = solve_dev(d_y_, cur, 0, 2))) return rc;
+      launch_mask(stream_, d_y_, d_owned_, n, cur, (int64_t)n);
+      NCCLCHK(R.all_reduce(d_y_, d_y_, (size_t)n * cur, kNcclDouble, kNcclSum, comm_, stream_), "ncclAllReduce(x)");
+      if ((rc = sync_stream(stream_, "solve sync"))) return rc;
+    } else {
+      rc = solve_dev(d_y_, cur, job, -1);
+      if (rc) return rc;
+    }
+    HIPCHK(hipMemcpy(yh.data(), d_y_, sizeof(double) * (size_t)n * cur, hipMemcpyDeviceToHost), "x D2H");
+    for (int q = 0; q < cur; ++q) {
+      double* xr = x_host + (int64_t)(done + q) * n;
+      const double* yq = yh.data() + (size_t)q * n;
+      for (int i = 0; i < n; ++i) xr[i] = yq[S.order[i]];
+    }
+    done += cur;
+  }
+  return 0;
+}
+
+// ---- blocked solve for many right-hand sides ---------------------------------------------------
+int Engine::prepare_solve_many(bool host_stage) {
+  int rc = prepare_solve();
+  if (rc) return rc;
+  const Symbolic& S = *S_;
+  const size_t wb = sizeof(double) * 32 * (size_t)std::max(1, S.n);
+  // (a failure here leaves the factor and the existing solve usable: the engine's status is not touched)
+  hipError_t e = hipSuccess;
+  if (!d_smW_) e = dalloc((void**)&d_smW_, wb);
+  if (e == hipSuccess) e = ensure_order();
+  if (e == hipSuccess && host_stage && !d_smstage_) e = dalloc((void**)&d_smstage_, wb);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    feature_err_ = "solve_many: not enough device memory for the workspace of 32 right-hand sides (" +
+                   std::to_string(wb >> 20) + " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  return 0;
+}
+
+// one block of nv <= rb vectors: pack, the sweeps `job` asks for, unpack (enqueue only)
+void Engine::enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order) {
+  const int n = S_->n;
+  const int* order = pivot_order ? nullptr : d_order_;
+  const SolveTablesView tv = solve_tables();
+  launch_solve_many_pack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
+  for_each_solve_launch(job, -1, [&](const SolveLaunch& l, const SolveLaunchInfo& li) {
+    launch_solve_many(stream_, tv, l, li, d_smW_, rb);
+  });
+  launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
+}
+
+int Engine::solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (pending_) return -10;          // (the caller waits first)
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_many(false);
+  if (rc) return rc;
+  // 32 per sweep while at least 32 are left; the tail as one zero-padded block of 16 or 32
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
+    enqueue_solve_many_block(x_dev + (int64_t)done * ldx, ldx, nv, rb, job, pivot_order);
+    done += nv;
+  }
+  HIPCHK(hipGetLastError(), "solve_many launch");
+  return sync_stream(stream_, "solve_many sync");
+}
+
+int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_many(true);
+  if (rc) return rc;
+  const int n = S_->n;
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
+    double* xb = x_host + (int64_t)done * ldx;
+    // the block in the caller's layout, its n-vectors only (the permutation happens on the device)
+    if ((rc = copy_vectors(true, d_smstage_, xb, ldx, nv, "rhs H2D"))) return rc;
+    enqueue_solve_many_block(d_smstage_, n, nv, rb, job, false);
+    HIPCHK(hipGetLastError(), "solve_many launch");
+    if ((rc = copy_vectors(false, d_smstage_, xb, ldx, nv, "x D2H"))) return rc;
+    if ((rc = sync_stream(stream_, "solve_many sync"))) return rc;
+    done += nv;
+  }
+  return 0;
+}
+
+// ---- reproducible solve ----------------------------------------------------------------------------
+static std::atomic<bool> g_rsolve_poison{false};
+void set_rsolve_poison(bool on) { g_rsolve_poison.store(on); }
+
+int Engine::prepare_solve_repro() {
+  int rc = prepare_solve();
+  if (rc) return rc;
+  if (rs_ready_) return 0;
+  const Symbolic& S = *S_;
+  RsolveTables R;
+  build_rsolve_tables(S, sprog_, R);
+  rs_stride_ = std::max<int64_t>(1, std::max(R.frows, R.bsize));
+  const size_t sb = sizeof(double) * 4 * (size_t)rs_stride_;
+  TableStager tab;
+  tab.add(&d_rsfslot_, R.fslot);
+  tab.add(&d_rsbfirst_, R.bfirst);
+  tab.add(&d_rsgptr_, R.gptr);
+  tab.add(&d_rsgsrc_, R.gsrc);
+  tab.add(&d_rsbslot_, R.bslot);
+  // (a failure here leaves the factor and the other solves usable: the engine's status is not touched)
+  hipError_t e = tab.commit(&d_rstab_, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e == hipSuccess) e = ensure_order();
+  if (e == hipSuccess) e = dalloc((void**)&d_rsscratch_, sb);
+  if (e == hipSuccess) e = dalloc((void**)&d_rsstage_, sizeof(double) * 4 * (size_t)std::max(1, S.n));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
+      if (p) release_buffer(p);
+    d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+    feature_err_ = "solve_repro: not enough device memory for the tables and the scratch of 4 right-hand sides (" +
+                   std::to_string((sb + tab.host.size()) >> 20) + " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  rs_ready_ = true;
+  return 0;
+}
+
+int Engine::release_solve_repro() {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!rs_ready_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "solve_repro release")) return rc;
+  for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
+    if (p) release_buffer(p);
+  d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+  rs_ready_ = false;
+  return 0;
+}
+
+// the sweeps `job` asks for on cur = 1, 2 or 4 vectors in pivot order, y[q * ldy + p] (enqueue only)
+int Engine::enqueue_solve_repro(double* y, int64_t ldy, int cur, int job) {
+  const RsolveView rv{d_rsfslot_, d_rsbfirst_, d_rsgptr_, d_rsgsrc_, d_rsbslot_, d_rsscratch_, rs_stride_};
+  const SolveTablesView tv = solve_tables();
+  for (int sweep = 1; sweep <= 2; ++sweep) {   // forward, backward
+    if (job != 0 && job != sweep) continue;
+    // debug: a slot that is read without having been written in this sweep shows up as NaN
+    if (g_rsolve_poison.load())
+      HIPCHK(hipMemsetAsync(d_rsscratch_, 0xFF, sizeof(double) * 4 * (size_t)rs_stride_, stream_), "poison the scratch");
+    for_each_solve_launch(sweep, -1, [&](const SolveLaunch& l, const SolveLaunchInfo& li) {
+      launch_solve_repro(stream_, tv, l, li, y, cur, ldy, rv);
+    });
+  }
+  return 0;
+}
+
+int Engine::solve_repro_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (pending_) return -10;          // (the caller waits first)
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_repro();
+  if (rc) return rc;
+  const int n = S_->n;
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+    double* xg = x_dev + (int64_t)done * ldx;
+    if (pivot_order) {
+      if ((rc = enqueue_solve_repro(xg, ldx, cur, job))) return rc;
+    } else {
+      launch_permute_vectors(stream_, false, xg, ldx, d_order_, n, cur, d_y_);
+      if ((rc = enqueue_solve_repro(d_y_, (int64_t)n, cur, job))) return rc;
+      launch_permute_vectors(stream_, true, xg, ldx, d_order_, n, cur, d_y_);
+    }
+    done += cur;
+  }
+  HIPCHK(hipGetLastError(), "solve_repro launch");
+  return sync_stream(stream_, "solve_repro sync");
+}
+
+int Engine::solve_repro(double* x_host, int nrhs, int64_t ldx, int job) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nrhs == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_repro();
+  if (rc) return rc;
+  const int n = S_->n;
+  for (int done = 0; done < nrhs;) {
+    const int left = nrhs - done;
+    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+    double* xg = x_host + (int64_t)done * ldx;
+    // the group in the caller's layout, its n-vectors only (the permutation happens on the device)
+    if ((rc = copy_vectors(true, d_rsstage_, xg, ldx, cur, "rhs H2D"))) return rc;
+    launch_permute_vectors(stream_, false, d_rsstage_, (int64_t)n, d_order_, n, cur, d_y_);
+    if ((rc = enqueue_solve_repro(d_y_, (int64_t)n, cur, job))) return rc;
+    launch_permute_vectors(stream_, true, d_rsstage_, (int64_t)n, d_order_, n, cur, d_y_);
+    HIPCHK(hipGetLastError(), "solve_repro launch");
+    if ((rc = copy_vectors(false, d_rsstage_, xg, ldx, cur, "x D2H"))) return rc;
+    if ((rc = sync_stream(stream_, "solve_repro sync"))) return rc;
+    done += cur;
+  }
+  return 0;
+}
+
+// ---- refined solves --------------------------------------------------------------------------------
+// Operator tables (once per engine) and the work vectors of one group, all or nothing: a failed allocation
+// gives back what it got and leaves the factor and every other solve usable.
+int Engine::prepare_refine(bool host_val) {
+  const Symbolic& S = *S_;
+  const size_t n1 = (size_t)std::max(1, S.n);
+  hipError_t e = hipSuccess;
+  size_t want = 0;
+  if (!refine_ready_) {
+    std::vector<int64_t> rowptr;
+    std::vector<int> col, src, rows;
+    build_matvec_tables(S, rowptr, col, src);
+    // rows by length: at most 16 entries -> 4 lanes per row, at most 128 -> 16 lanes, longer -> a wavefront
+    rows.reserve((size_t)S.n);
+    for (int c = 0; c < 3; ++c) {
+      rf_nrows_[c] = 0;
+      for (int p = 0; p < S.n; ++p) {
+        const int64_t len = rowptr[(size_t)p + 1] - rowptr[(size_t)p];
+        const int cls = len <= 16 ? 0 : (len <= 128 ? 1 : 2);
+        if (cls == c) { rows.push_back(p); ++rf_nrows_[c]; }
+      }
+    }
+    RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+    const size_t slots = (size_t)std::max(std::max(spmv_slots(op), vec_slots(S.n)), RF_AMAX_WG);
+    TableStager tab;
+    tab.add(&d_rfrowptr_, rowptr);
+    tab.add(&d_rfcol_, col);
+    tab.add(&d_rfsrc_, src);
+    tab.add(&d_rfrows_, rows);
+    e = tab.commit(&d_rftab_, [this](void** q, size_t b) { return dalloc(q, b); });
+    want = sizeof(double) * 6 * RF_G * n1;
+    if (e == hipSuccess) e = ensure_order();
+    if (e == hipSuccess) e = dalloc((void**)&d_rfwork_, want);
+    if (e == hipSuccess) e = dalloc((void**)&d_rfpart_, sizeof(double) * 2 * RF_G * slots);
+    if (e == hipSuccess) e = dalloc((void**)&d_rfds_, sizeof(double) * RF_DS);
+    if (e == hipSuccess) e = dalloc((void**)&d_rfis_, sizeof(int) * RF_IS);
+    if (e == hipSuccess) e = hipMemsetAsync(d_rfis_, 0, sizeof(int) * RF_IS, stream_);
+    if (e == hipSuccess) e = hipMemsetAsync(d_rfds_, 0, sizeof(double) * RF_DS, stream_);
+  }
+  if (e == hipSuccess && host_val && !d_rfval_) {
+    want = sizeof(double) * (size_t)std::max<int64_t>(1, S.nnzA);
+    e = dalloc((void**)&d_rfval_, want);
+    if (e != hipSuccess) d_rfval_ = nullptr;
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (!refine_ready_) {
+      for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_})
+        if (p) release_buffer(p);
+      d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr;
+    }
+    feature_err_ = "refined solve: not enough device memory for the operator and the work vectors (" +
+                   std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  refine_ready_ = true;
+  return 0;
+}
+
+int Engine::release_refine() {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!refine_ready_ && !d_rfval_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "refine release")) return rc;
+  for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_, (void*)d_rfval_})
+    if (p) release_buffer(p);
+  d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr; d_rfval_ = nullptr;
+  refine_ready_ = false;
+  return 0;
+}
+
+int Engine::matvec(const double* val, int nvec, const double* x, int64_t ldx, double* y, int64_t ldy, bool dev,
+                   bool pivot_order) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n;
+  if (!val || !x || !y || nvec < 0 || ldx < n || ldy < n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;   // (the caller waits first)
+  if (nvec == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_refine(!dev);
+  if (rc) return rc;
+  const double* dval = val;
+  if (!dev) {
+    HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");
+    dval = d_rfval_;
+  }
+  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  const size_t gn = (size_t)RF_G * (size_t)n;
+  double *wb = d_rfwork_, *wr = d_rfwork_ + 2 * gn, *wq = d_rfwork_ + 4 * gn;
+  for (int done = 0; done < nvec;) {
+    const int nv = std::min(RF_G, nvec - done);
+    const double* xg = x + (int64_t)done * ldx;
+    double* yg = y + (int64_t)done * ldy;
+    if (dev && pivot_order) {
+      launch_spmv(stream_, op, dval, xg, ldx, nullptr, yg, ldy, nv, nullptr, 0, nullptr);
+    } else if (dev) {
+      launch_permute_vectors(stream_, false, const_cast<double*>(xg), ldx, d_order_, n, nv, wb);   // (reads xg)
+      launch_spmv(stream_, op, dval, wb, n, nullptr, wr, n, nv, nullptr, 0, nullptr);
+      launch_permute_vectors(stream_, true, yg, ldy, d_order_, n, nv, wr);
+    } else {
+      if ((rc = copy_vectors_to_device(wq, xg, ldx, nv, "x H2D"))) return rc;
+      launch_permute_vectors(stream_, false, wq, n, d_order_, n, nv, wb);
+      launch_spmv(stream_, op, dval, wb, n, nullptr, wr, n, nv, nullptr, 0, nullptr);
+      launch_permute_vectors(stream_, true, wq, n, d_order_, n, nv, wr);
+      if ((rc = copy_vectors(false, wq, yg, ldy, nv, "y D2H"))) return rc;
+    }
+    HIPCHK(hipGetLastError(), "matvec launch");
+    if (!dev && (rc = sync_stream(stream_, "matvec sync"))) return rc;
+    done += nv;
+  }
+  return sync_stream(stream_, "matvec sync");
+}
+
+// both sweeps with the current factor on nv work vectors (pivot order, ld = n), through the existing paths.
+// The sweeps take all nv columns, frozen vectors included (their columns are zero: launch_rf_copy), since the
+// existing paths know no mask; the columns of a sweep are independent of each other.
+int Engine::refine_apply_factor(double* v, int nv) {
+  // (reproducible: every group size through that path, in sweeps of 4)
+  if (repro_on_) return solve_repro_dev(v, nv, (int64_t)S_->n, 0, true);
+  return nv <= 4 ? solve_dev(v, nv, 0, -1) : solve_many_dev(v, nv, (int64_t)S_->n, 0, true);
+}
+
+// the one array that crosses the bus per iteration: out[q] = best confirmed error, out[32 + q] = state
+int Engine::refine_readback(int nv, std::vector<double>& out) {
+  (void)nv;
+  HIPCHK(hipGetLastError(), "refine launch");
+  HIPCHK(hipMemcpyAsync(out.data(), d_rfds_ + RFD_OUT, sizeof(double) * 2 * RF_G, hipMemcpyDeviceToHost, stream_),
+         "refine state D2H");
+  return sync_stream(stream_, "refine sync");
+}
+
+int Engine::refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol,
+                         int max_iter, int* iterations, double* error) {
+  const int n = S_->n;
+  const size_t gn = (size_t)RF_G * (size_t)n;
+  double *B = d_rfwork_, *X = B + gn, *R = X + gn, *P = R + gn, *Q = P + gn, *XB = Q + gn;
+  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  const int sslots = spmv_slots(op), vslots = vec_slots(n);
+  const int* st = d_rfis_ + RFI_ST;
+  const int* decl = d_rfis_ + RFI_DECL;
+  const int* improve = d_rfis_ + RFI_IMPROVE;
+  int rc = 0;
+  if (dev) {
+    launch_permute_vectors(stream_, false, x, ldx, d_order_, n, nv, B);
+  } else {
+    if ((rc = copy_vectors(true, Q, x, ldx, nv, "rhs H2D"))) return rc;
+    launch_permute_vectors(stream_, false, Q, n, d_order_, n, nv, B);
+  }
+  launch_rf_dot(stream_, n, nv, B, B, nullptr, 0, d_rfpart_);
+  launch_rf_finalize(stream_, RFS_BNORM, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
+  // x = M^-1 b, r = b - A x, the error of the first iterate
+  launch_rf_copy(stream_, n, nv, X, B, nullptr, 0);
+  if ((rc = refine_apply_factor(X, nv))) return rc;
+  auto true_residual = [&](const int* sel, int want, int flag) {
+    launch_spmv(stream_, op, dval, X, n, B, R, n, nv, sel, want, d_rfpart_);
+    launch_rf_finalize(stream_, RFS_TRUE, d_rfpart_, sslots, nv, tol, flag, d_rfds_, d_rfis_);
+    launch_rf_copy(stream_, n, nv, XB, X, improve, 1);   // the best confirmed iterate
+  };
+  true_residual(st, 0, 0);
+  std::vector<double> out(2 * RF_G, 0.0);
+  if ((rc = refine_readback(nv, out))) return rc;
+  auto active = [&]() {
+    for (int q = 0; q < nv; ++q)
+      if (out[(size_t)RF_G + q] == 0.0) return true;
+    return false;
+  };
+  std::vector<int> its((size_t)nv, 0);
+  for (int it = 0; it < max_iter && active();) {
+    ++it;
+    for (int q = 0; q < nv; ++q)
+      if (out[(size_t)RF_G + q] == 0.0) its[(size_t)q] = it;
+    if (method == 0) {
+      // x += M^-1 r ; r = b - A x
+      launch_rf_copy(stream_, n, nv, P, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
+      if ((rc = refine_apply_factor(P, nv))) return rc;
+      launch_rf_axpy(stream_, n, nv, nullptr, X, P, nullptr, nullptr, st, 0, nullptr);
+      true_residual(st, 0, 0);
+    } else {
+      // z = M^-1 r (in q) ; beta = r.z / (r.z)_old, 0 after a restart ; p = z + beta p
+      launch_rf_copy(stream_, n, nv, Q, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
+      if ((rc = refine_apply_factor(Q, nv))) return rc;
+      launch_rf_dot(stream_, n, nv, R, Q, st, 0, d_rfpart_);
+      launch_rf_finalize(stream_, RFS_BETA, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
+      launch_rf_pupdate(stream_, n, nv, d_rfds_ + RFD_BETA, P, Q, st, 0);
+      // q = A p with the partials of p.q ; alpha = r.z / p.q ; x += alpha p, r -= alpha q
+      launch_spmv(stream_, op, dval, P, n, nullptr, Q, n, nv, st, 0, d_rfpart_);
+      launch_rf_finalize(stream_, RFS_ALPHA, d_rfpart_, sslots, nv, tol, 0, d_rfds_, d_rfis_);
+      launch_rf_axpy(stream_, n, nv, d_rfds_ + RFD_ALPHA, X, P, R, Q, st, 0, d_rfpart_);
+      launch_rf_finalize(stream_, RFS_REC, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
+      // what the recurrence declares converged is confirmed with a true residual (no work if nothing is declared)
+      true_residual(decl, 1, 1);
+    }
+    if ((rc = refine_readback(nv, out))) return rc;
+  }
+  if (method == 1 && active()) {
+    // out of iterations: the error reported is that of a true residual
+    launch_rf_finalize(stream_, RFS_FINAL, d_rfpart_, 0, nv, tol, 0, d_rfds_, d_rfis_);
+    true_residual(decl, 1, 1);
+    if ((rc = refine_readback(nv, out))) return rc;
+  }
+  if (dev) {
+    launch_permute_vectors(stream_, true, x, ldx, d_order_, n, nv, XB);
+  } else {
+    launch_permute_vectors(stream_, true, Q, n, d_order_, n, nv, XB);
+    if ((rc = copy_vectors(false, Q, x, ldx, nv, "x D2H"))) return rc;
+  }
+  HIPCHK(hipGetLastError(), "refine launch");
+  if ((rc = sync_stream(stream_, "refine sync"))) return rc;
+  int worst = 0;
+  for (int q = 0; q < nv; ++q) {
+    if (iterations) iterations[q] = its[(size_t)q];
+    if (error) error[q] = out[(size_t)q];
+    if (out[(size_t)RF_G + q] != 1.0) worst = 1;
+  }
+  return worst;
+}
+
+int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, bool dev, int method, double tol,
+                          int max_iter, int* iterations, double* error) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n;
+  if (!val || !x || nrhs < 0 || ldx < n || method < 0 || method > 1 || !(tol > 0.0) || max_iter < 0) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_ || !factored_) return -10;   // (the caller waits first)
+  if (nrhs == 0) return 0;
+  if (n == 0) {
+    for (int q = 0; q < nrhs; ++q) {
+      if (iterations) iterations[q] = 0;
+      if (error) error[q] = 0.0;
+    }
+    return 0;
+  }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_refine(!dev);
+  if (rc) return rc;
+  const double* dval = val;
+  if (!dev) {
+    HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");
+    dval = d_rfval_;
+  }
+  launch_rf_absmax(stream_, dval, S_->nnzA, d_rfpart_);
+  launch_rf_finalize(stream_, RFS_AMAX, d_rfpart_, RF_AMAX_WG, 0, tol, 0, d_rfds_, d_rfis_);
+  int worst = 0;
+  for (int done = 0; done < nrhs;) {
+    const int nv = std::min(RF_G, nrhs - done);
+    rc = refine_group(dval, nv, x + (int64_t)done * ldx, ldx, dev, method, tol, max_iter,
+                      iterations ? iterations + done : nullptr, error ? error + done : nullptr);
+    if (rc < 0) return rc;
+    worst |= rc;
+    done += nv;
+  }
+  return worst;
+}
+
+}  // namespace spx

@@ -2340,46 +2340,45 @@ __global__ __launch_bounds__(256) void k_solve_strip(const UpdTile* __restrict__
 }
 
 template <int NR>
-static void launch_solve_nr(hipStream_t st, int kind, const int* list, const UpdTile* tiles,
-                            int64_t first, int64_t count, const SolveUnit* units, const double* L,
-                            const double* dinv, const int* rlist, double* y, int64_t ldy, bool four,
-                            const SolveUnit* one) {
-  const dim3 g((unsigned)count), b(256);
-  const SolveUnit u0 = one ? *one : SolveUnit{};
-  const int single = one ? 1 : 0;
-  switch (kind) {
+static void launch_solve_nr(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li,
+                            double* y, int64_t ldy) {
+  const dim3 g((unsigned)l.count), b(256);
+  const int* list = t.list + l.first;          // DIAG launches: the block columns
+  const UpdTile* tiles = t.tiles + l.first;    // STRIP launches: the (block column, strip) pairs
+  const SolveUnit u0 = li.one ? *li.one : SolveUnit{};
+  const int single = li.one ? 1 : 0;
+  switch (l.kind) {
     case SV_DIAG_FWD:
-      if (four)
-        hipLaunchKernelGGL((k_solve_diag4<false, NR>), g, b, 0, st, list + first, units, L, dinv, rlist, y, ldy, u0, single);
+      if (li.four)
+        hipLaunchKernelGGL((k_solve_diag4<false, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, t.rlist, y, ldy, u0, single);
       else
-        hipLaunchKernelGGL((k_solve_diag<false, NR>), g, b, 0, st, list + first, units, L, dinv, rlist, y, ldy, u0, single);
+        hipLaunchKernelGGL((k_solve_diag<false, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, t.rlist, y, ldy, u0, single);
       break;
     case SV_DIAG_BWD:
-      if (four)
-        hipLaunchKernelGGL((k_solve_diag4<true, NR>), g, b, 0, st, list + first, units, L, dinv, rlist, y, ldy, u0, single);
+      if (li.four)
+        hipLaunchKernelGGL((k_solve_diag4<true, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, t.rlist, y, ldy, u0, single);
       else
-        hipLaunchKernelGGL((k_solve_diag<true, NR>), g, b, 0, st, list + first, units, L, dinv, rlist, y, ldy, u0, single);
+        hipLaunchKernelGGL((k_solve_diag<true, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, t.rlist, y, ldy, u0, single);
       break;
     case SV_STRIP_FWD:
-      hipLaunchKernelGGL((k_solve_strip<false, NR>), g, b, 0, st, tiles + first, units, L, rlist, y, ldy, u0, single);
+      hipLaunchKernelGGL((k_solve_strip<false, NR>), g, b, 0, st, tiles, t.units, t.L, t.rlist, y, ldy, u0, single);
       break;
     default:
-      hipLaunchKernelGGL((k_solve_strip<true, NR>), g, b, 0, st, tiles + first, units, L, rlist, y, ldy, u0, single);
+      hipLaunchKernelGGL((k_solve_strip<true, NR>), g, b, 0, st, tiles, t.units, t.L, t.rlist, y, ldy, u0, single);
       break;
   }
 }
 
 // nr = 1, 2 or 4 right-hand sides per sweep: y[q * ldy + i]
-void launch_solve(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first,
-                  int64_t count, const SolveUnit* units, const double* L, const double* dinv,
-                  const int* rlist, double* y, int nr, int64_t ldy, bool four, const SolveUnit* one) {
-  if (count <= 0) return;
+void launch_solve(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li, double* y,
+                  int nr, int64_t ldy) {
+  if (l.count <= 0) return;
   if (nr >= 4)
-    launch_solve_nr<4>(st, kind, list, tiles, first, count, units, L, dinv, rlist, y, ldy, four, one);
+    launch_solve_nr<4>(st, t, l, li, y, ldy);
   else if (nr >= 2)
-    launch_solve_nr<2>(st, kind, list, tiles, first, count, units, L, dinv, rlist, y, ldy, four, one);
+    launch_solve_nr<2>(st, t, l, li, y, ldy);
   else
-    launch_solve_nr<1>(st, kind, list, tiles, first, count, units, L, dinv, rlist, y, ldy, four, one);
+    launch_solve_nr<1>(st, t, l, li, y, ldy);
 }
 
 // ---------------------------------------------------------------------------
@@ -2578,6 +2577,24 @@ __global__ __launch_bounds__(256) void k_mask(double* __restrict__ y, const doub
 void launch_mask(hipStream_t st, double* y, const double* keep, int n, int nrhs, int64_t ldy) {
   if (n <= 0 || nrhs <= 0) return;
   hipLaunchKernelGGL(k_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, y, keep, n, nrhs, ldy);
+}
+// user order <-> pivot order: blockIdx.y is the vector; the 64 bits of an entry move as an integer
+__global__ __launch_bounds__(256) void k_permute_vectors(int unpack, unsigned long long* __restrict__ x, int64_t ldx,
+                                                         const int* __restrict__ order, int n,
+                                                         unsigned long long* __restrict__ y) {
+  const int q = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t iy = (int64_t)q * n + order[i], ix = (int64_t)q * ldx + i;
+  if (unpack) x[ix] = y[iy];
+  else y[iy] = x[ix];
+}
+void launch_permute_vectors(hipStream_t st, bool unpack, double* x, int64_t ldx, const int* order, int n, int nv,
+                            double* y) {
+  if (n <= 0 || nv <= 0) return;
+  hipLaunchKernelGGL(k_permute_vectors, dim3((unsigned)((n + 255) / 256), (unsigned)nv), dim3(256), 0, st,
+                     unpack ? 1 : 0, reinterpret_cast<unsigned long long*>(x), ldx, order, n,
+                     reinterpret_cast<unsigned long long*>(y));
 }
 void launch_flag_pack(hipStream_t st, const int* flag, double* slot) {
   hipLaunchKernelGGL(k_flag_pack, dim3(1), dim3(1), 0, st, flag, slot);

@@ -60,6 +60,10 @@ void launch_flag_pack(hipStream_t st, const int* flag, double* slot);
 void launch_flag_unpack(hipStream_t st, const double* slot, int* flag);
 // y[q * ldy + i] *= keep[i]  (multi-GPU solve: a rank's share of a distributed vector)
 void launch_mask(hipStream_t st, double* y, const double* keep, int n, int nrhs, int64_t ldy);
+// y[q * n + order[i]] = x[q * ldx + i] (unpack: the other way), q < nv: user order <-> pivot order, a copy of
+// the 64 bits of every entry
+void launch_permute_vectors(hipStream_t st, bool unpack, double* x, int64_t ldx, const int* order, int n, int nv,
+                            double* y);
 // debug: fill the LDS of every CU with signalling NaNs
 void launch_poison_lds(hipStream_t st);
 void launch_update(const LaunchSink& st, int tile, const UpdTile* tiles, int64_t count,
@@ -75,18 +79,30 @@ void launch_scatter_block(hipStream_t st, int s_m, int s_n, const int* rsrc_inde
                           const int* rdest_index, int d_m, const int* cdest_index, int d_n,
                           double* dest, int ldd);
 
-// one launch of the device solve (kind = SolveKind); four: every block column of a DIAG launch has at
-// most four 64-wide panels (pw = cb = 64, w <= 256) -- the kernel that reads L in one round trip
-void launch_solve(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first,
-                  int64_t count, const SolveUnit* units, const double* L, const double* dinv,
-                  const int* rlist, double* y, int nr, int64_t ldy, bool four = false,
-                  const SolveUnit* one = nullptr);   // one: the launch works on ONE block column (host copy of its unit;
-                                                     // strips: strip i = workgroup i) -- the descriptor travels with the arguments
+// the device tables every launch of a SolveProgram reads, and the factor they point into
+struct SolveTablesView {
+  const int* list;
+  const UpdTile* tiles;
+  const SolveUnit* units;
+  const double* L;
+  const double* dinv;
+  const int* rlist;
+};
+// per launch of a SolveProgram, decided once on the host: four -- every block column of a DIAG launch has at
+// most four 64-wide panels (pw = cb = 64, w <= 256), the kernel that reads L in one round trip; one -- the
+// launch works on ONE block column (host copy of its unit; strips: strip i = workgroup i), the descriptor
+// travels with the arguments
+struct SolveLaunchInfo {
+  bool four;
+  const SolveUnit* one;
+};
+// one launch of the device solve on nr = 1, 2 or 4 vectors y[q * ldy + i]
+void launch_solve(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li, double* y,
+                  int nr, int64_t ldy);
 // blocked solve for many right-hand sides (solve_many.hip): one launch of the SAME solve program on the
 // workspace W[p * rb + q] (pivot position p, right-hand side q < rb; rb = 16 or 32), products on fp64 MFMA
-void launch_solve_many(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first,
-                       int64_t count, const SolveUnit* units, const double* L, const double* dinv,
-                       const int* rlist, double* W, int rb, const SolveUnit* one = nullptr);
+void launch_solve_many(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li,
+                       double* W, int rb);
 // W <- the caller's nv <= rb vectors x[q * ldx + i] (order: user variable i -> pivot position, null = x is in
 // pivot order), columns nv .. rb - 1 of W zero; and back (only the nv real vectors are written)
 void launch_solve_many_pack(hipStream_t st, const double* x, int64_t ldx, const int* order, int n, int nv, int rb,
@@ -195,12 +211,8 @@ struct RsolveView {
   int64_t stride;
 };
 // one launch of the SolveProgram, arguments as launch_solve
-void launch_solve_repro(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first, int64_t count,
-                        const SolveUnit* units, const double* L, const double* dinv, const int* rlist, double* y, int nr,
-                        int64_t ldy, bool four, const SolveUnit* one, const RsolveView& rv);
-// y[q * n + order[i]] = x[q * ldx + i] (unpack: the other way), q < nv: a bitwise copy
-void launch_solve_repro_perm(hipStream_t st, bool unpack, double* x, int64_t ldx, const int* order, int n, int nv,
-                             double* y);
+void launch_solve_repro(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li,
+                        double* y, int nr, int64_t ldy, const RsolveView& rv);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 

@@ -7,7 +7,7 @@
 //   k_rf_axpy          x += alpha p, r -= alpha q, partials of |r|^2 and |x|^2
 //   k_rf_pupdate       p = z + beta p
 //   k_rf_dot           partials of a.b
-//   k_rf_copy (optionally zeroing the vectors it does not copy), k_rf_pack, k_rf_unpack, k_rf_absmax
+//   k_rf_copy (optionally zeroing the vectors it does not copy), k_rf_absmax
 //   k_rf_finalize      the second stage of every reduction and the scalar arithmetic behind it
 //
 // alpha, beta and the per-vector state are read from device memory; a vector that is not selected is
@@ -197,18 +197,6 @@ __global__ __launch_bounds__(256) void k_rf_absmax(const double* __restrict__ va
   if (threadIdx.x == 0) part[blockIdx.x] = rf_nanmax(rf_nanmax(rf_nanmax(red[0], red[1]), red[2]), red[3]);
 }
 
-// the idea of k_sm_pack: the permutation to pivot order happens on the device, through the order table
-template <bool UNPACK>
-__global__ __launch_bounds__(256) void k_rf_pack(int n, double* __restrict__ x, int64_t ldx, const int* __restrict__ order,
-                                                 double* __restrict__ w) {
-  const int q = blockIdx.y;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int64_t iw = (int64_t)q * n + order[i], ix = (int64_t)q * ldx + i;
-  if (UNPACK) x[ix] = w[iw];
-  else w[iw] = x[ix];
-}
-
 // ---------------------------------------------------------------------------------------------------
 // One workgroup of 256: thread t adds the partials of vector t & 31 in slots (t >> 5), (t >> 5) + 8, ... ;
 // the eight slices of a vector are then added in order by thread q, which also does the scalar step.
@@ -374,18 +362,6 @@ void launch_rf_copy(hipStream_t st, int n, int nvec, double* dst, const double* 
 
 void launch_rf_absmax(hipStream_t st, const double* val, int64_t nnz, double* part) {
   hipLaunchKernelGGL(k_rf_absmax, dim3(RF_AMAX_WG), dim3(256), 0, st, val, nnz, part);
-}
-
-void launch_rf_pack(hipStream_t st, int n, int nvec, const double* x, int64_t ldx, const int* order, double* w) {
-  if (n <= 0 || nvec <= 0) return;
-  hipLaunchKernelGGL((k_rf_pack<false>), dim3((unsigned)((n + 255) / 256), (unsigned)nvec), dim3(256), 0, st, n,
-                     const_cast<double*>(x), ldx, order, w);
-}
-
-void launch_rf_unpack(hipStream_t st, int n, int nvec, double* x, int64_t ldx, const int* order, const double* w) {
-  if (n <= 0 || nvec <= 0) return;
-  hipLaunchKernelGGL((k_rf_pack<true>), dim3((unsigned)((n + 255) / 256), (unsigned)nvec), dim3(256), 0, st, n, x, ldx,
-                     order, const_cast<double*>(w));
 }
 
 void launch_rf_finalize(hipStream_t st, int stage, const double* part, int nslots, int nvec, double tol, int flag,

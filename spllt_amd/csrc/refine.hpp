@@ -63,9 +63,6 @@ void launch_rf_copy(hipStream_t st, int n, int nvec, double* dst, const double* 
                     bool zero_others = false);
 // part[slot] = max |val| of the slot's share, a NaN wins (RF_AMAX_WG slots)
 void launch_rf_absmax(hipStream_t st, const double* val, int64_t nnz, double* part);
-// w[q * n + p(i)] = x[q * ldx + i] and back; order: user variable -> pivot position
-void launch_rf_pack(hipStream_t st, int n, int nvec, const double* x, int64_t ldx, const int* order, double* w);
-void launch_rf_unpack(hipStream_t st, int n, int nvec, double* x, int64_t ldx, const int* order, const double* w);
 // second stage of every reduction and the scalar step that follows it (one workgroup)
 void launch_rf_finalize(hipStream_t st, int stage, const double* part, int nslots, int nvec, double tol, int pcg,
                         double* ds, int* is);

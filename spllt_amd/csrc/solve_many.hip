@@ -285,36 +285,36 @@ __global__ __launch_bounds__(256) void k_sm_strip_bwd(const UpdTile* __restrict_
 // launch wrappers
 // ---------------------------------------------------------------------------
 template <int RB>
-static void launch_solve_many_rb(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first,
-                                 int64_t count, const SolveUnit* units, const double* L, const double* dinv,
-                                 const int* rlist, double* W, const SolveUnit* one) {
-  const dim3 g((unsigned)count), b(256);
-  const SolveUnit u0 = one ? *one : SolveUnit{};
-  const int single = one ? 1 : 0;
-  switch (kind) {
+static void launch_solve_many_rb(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l,
+                                 const SolveLaunchInfo& li, double* W) {
+  const dim3 g((unsigned)l.count), b(256);
+  const int* list = t.list + l.first;          // DIAG launches: the block columns
+  const UpdTile* tiles = t.tiles + l.first;    // STRIP launches: the (block column, strip) pairs
+  const SolveUnit u0 = li.one ? *li.one : SolveUnit{};
+  const int single = li.one ? 1 : 0;
+  switch (l.kind) {
     case SV_DIAG_FWD:
-      hipLaunchKernelGGL((k_sm_diag<false, RB>), g, b, 0, st, list + first, units, L, dinv, W, u0, single);
+      hipLaunchKernelGGL((k_sm_diag<false, RB>), g, b, 0, st, list, t.units, t.L, t.dinv, W, u0, single);
       break;
     case SV_DIAG_BWD:
-      hipLaunchKernelGGL((k_sm_diag<true, RB>), g, b, 0, st, list + first, units, L, dinv, W, u0, single);
+      hipLaunchKernelGGL((k_sm_diag<true, RB>), g, b, 0, st, list, t.units, t.L, t.dinv, W, u0, single);
       break;
     case SV_STRIP_FWD:
-      hipLaunchKernelGGL((k_sm_strip_fwd<RB>), g, b, 0, st, tiles + first, units, L, rlist, W, u0, single);
+      hipLaunchKernelGGL((k_sm_strip_fwd<RB>), g, b, 0, st, tiles, t.units, t.L, t.rlist, W, u0, single);
       break;
     default:
-      hipLaunchKernelGGL((k_sm_strip_bwd<RB>), g, b, 0, st, tiles + first, units, L, rlist, W, u0, single);
+      hipLaunchKernelGGL((k_sm_strip_bwd<RB>), g, b, 0, st, tiles, t.units, t.L, t.rlist, W, u0, single);
       break;
   }
 }
 
-void launch_solve_many(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first,
-                       int64_t count, const SolveUnit* units, const double* L, const double* dinv,
-                       const int* rlist, double* W, int rb, const SolveUnit* one) {
-  if (count <= 0) return;
+void launch_solve_many(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li,
+                       double* W, int rb) {
+  if (l.count <= 0) return;
   if (rb == 32)
-    launch_solve_many_rb<32>(st, kind, list, tiles, first, count, units, L, dinv, rlist, W, one);
+    launch_solve_many_rb<32>(st, t, l, li, W);
   else
-    launch_solve_many_rb<16>(st, kind, list, tiles, first, count, units, L, dinv, rlist, W, one);
+    launch_solve_many_rb<16>(st, t, l, li, W);
 }
 
 void launch_solve_many_pack(hipStream_t st, const double* x, int64_t ldx, const int* order, int n, int nv, int rb,

@@ -161,67 +161,46 @@ __global__ __launch_bounds__(256) void k_rsolve_strip(const UpdTile* __restrict_
 }
 
 template <int NR>
-static void launch_rsolve_nr(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first, int64_t count,
-                             const SolveUnit* units, const double* L, const double* dinv, const int* rlist, double* y,
-                             int64_t ldy, bool four, const SolveUnit* one, const RsolveView& rv) {
-  const dim3 g((unsigned)count), b(256);
-  const SolveUnit u0 = one ? *one : SolveUnit{};
-  const int single = one ? 1 : 0;
-  switch (kind) {
+static void launch_rsolve_nr(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li,
+                             double* y, int64_t ldy, const RsolveView& rv) {
+  const dim3 g((unsigned)l.count), b(256);
+  const int* list = t.list + l.first;          // DIAG launches: the block columns
+  const UpdTile* tiles = t.tiles + l.first;    // STRIP launches: the (block column, strip) pairs
+  const SolveUnit u0 = li.one ? *li.one : SolveUnit{};
+  const int single = li.one ? 1 : 0;
+  switch (l.kind) {
     case SV_DIAG_FWD:
-      if (four)
-        hipLaunchKernelGGL((k_rsolve_diag<false, true, NR>), g, b, 0, st, list + first, units, L, dinv, y, ldy, u0, single, rv);
+      if (li.four)
+        hipLaunchKernelGGL((k_rsolve_diag<false, true, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, y, ldy, u0, single, rv);
       else
-        hipLaunchKernelGGL((k_rsolve_diag<false, false, NR>), g, b, 0, st, list + first, units, L, dinv, y, ldy, u0, single, rv);
+        hipLaunchKernelGGL((k_rsolve_diag<false, false, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, y, ldy, u0, single, rv);
       break;
     case SV_DIAG_BWD:
-      if (four)
-        hipLaunchKernelGGL((k_rsolve_diag<true, true, NR>), g, b, 0, st, list + first, units, L, dinv, y, ldy, u0, single, rv);
+      if (li.four)
+        hipLaunchKernelGGL((k_rsolve_diag<true, true, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, y, ldy, u0, single, rv);
       else
-        hipLaunchKernelGGL((k_rsolve_diag<true, false, NR>), g, b, 0, st, list + first, units, L, dinv, y, ldy, u0, single, rv);
+        hipLaunchKernelGGL((k_rsolve_diag<true, false, NR>), g, b, 0, st, list, t.units, t.L, t.dinv, y, ldy, u0, single, rv);
       break;
     case SV_STRIP_FWD:
-      hipLaunchKernelGGL((k_rsolve_strip<false, NR>), g, b, 0, st, tiles + first, units, L, rlist, y, ldy, u0, single, rv,
-                         rv.bslot + first);
+      hipLaunchKernelGGL((k_rsolve_strip<false, NR>), g, b, 0, st, tiles, t.units, t.L, t.rlist, y, ldy, u0, single, rv,
+                         rv.bslot + l.first);
       break;
     default:
-      hipLaunchKernelGGL((k_rsolve_strip<true, NR>), g, b, 0, st, tiles + first, units, L, rlist, y, ldy, u0, single, rv,
-                         rv.bslot + first);
+      hipLaunchKernelGGL((k_rsolve_strip<true, NR>), g, b, 0, st, tiles, t.units, t.L, t.rlist, y, ldy, u0, single, rv,
+                         rv.bslot + l.first);
       break;
   }
 }
 
-void launch_solve_repro(hipStream_t st, int kind, const int* list, const UpdTile* tiles, int64_t first, int64_t count,
-                        const SolveUnit* units, const double* L, const double* dinv, const int* rlist, double* y, int nr,
-                        int64_t ldy, bool four, const SolveUnit* one, const RsolveView& rv) {
-  if (count <= 0) return;
+void launch_solve_repro(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li,
+                        double* y, int nr, int64_t ldy, const RsolveView& rv) {
+  if (l.count <= 0) return;
   if (nr >= 4)
-    launch_rsolve_nr<4>(st, kind, list, tiles, first, count, units, L, dinv, rlist, y, ldy, four, one, rv);
+    launch_rsolve_nr<4>(st, t, l, li, y, ldy, rv);
   else if (nr >= 2)
-    launch_rsolve_nr<2>(st, kind, list, tiles, first, count, units, L, dinv, rlist, y, ldy, four, one, rv);
+    launch_rsolve_nr<2>(st, t, l, li, y, ldy, rv);
   else
-    launch_rsolve_nr<1>(st, kind, list, tiles, first, count, units, L, dinv, rlist, y, ldy, four, one, rv);
-}
-
-// user order <-> pivot order, a copy of the 64 bits of every entry
-__global__ __launch_bounds__(256) void k_rsolve_perm(int unpack, unsigned long long* __restrict__ x, int64_t ldx,
-                                                     const int* __restrict__ order, int n, int nv,
-                                                     unsigned long long* __restrict__ y) {
-  const int64_t total = (int64_t)n * nv;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int q = (int)(e / n), i = (int)(e - (int64_t)q * n);
-    const int64_t xi = (int64_t)q * ldx + i, yi = (int64_t)q * n + order[i];
-    if (unpack) x[xi] = y[yi];
-    else y[yi] = x[xi];
-  }
-}
-
-void launch_solve_repro_perm(hipStream_t st, bool unpack, double* x, int64_t ldx, const int* order, int n, int nv,
-                             double* y) {
-  if (n <= 0 || nv <= 0) return;
-  const int64_t blocks = std::min<int64_t>(((int64_t)n * nv + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_rsolve_perm, dim3((unsigned)blocks), dim3(256), 0, st, unpack ? 1 : 0,
-                     reinterpret_cast<unsigned long long*>(x), ldx, order, n, nv, reinterpret_cast<unsigned long long*>(y));
+    launch_rsolve_nr<1>(st, t, l, li, y, ldy, rv);
 }
 
 }  // namespace spx
