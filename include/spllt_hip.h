@@ -338,10 +338,11 @@ double *spllt_hip_device_factor(void *fkeep);
  * down.  The Z arena has exactly L's layout (spllt_hip_get_factor): every position that holds L
  * holds the entry of Z with the same (row, column) in pivot order; the never-read strict upper
  * triangle of the diagonal tiles is unspecified.  Entries of A^-1 outside the pattern of L need
- * solves.  A later factorization makes Z stale: the readers then return SPLLT_ERROR_PARAMETER until
- * spllt_hip_selected_inverse runs again.  L and the solve stay usable.  No atomics: two runs on the
- * same factor give a bit-identical Z.  A partitioned factor returns SPLLT_ERROR_UNIMPLEMENTED; too
- * little device memory for the Z arena (L's size) returns SPLLT_ERROR_ALLOCATION.  Messages:
+ * solves: spllt_hip_solve_sparse with unit columns and the wanted rows.  A later factorization
+ * makes Z stale: the readers then return SPLLT_ERROR_PARAMETER until spllt_hip_selected_inverse
+ * runs again.  L and the solve stay usable.  No atomics: two runs on the same factor give a
+ * bit-identical Z.  A partitioned factor returns SPLLT_ERROR_UNIMPLEMENTED; too little device
+ * memory for the Z arena (L's size) returns SPLLT_ERROR_ALLOCATION.  Messages:
  * spllt_hip_last_error. */
 int     spllt_hip_selected_inverse(void *fkeep);                       /* compute Z on the device */
 int     spllt_hip_get_inverse(void *fkeep, double *out, int64_t count); /* Z arena -> host, L's layout */
@@ -529,6 +530,60 @@ int spllt_hip_updown_info(void *fkeep, int64_t out[4]);
 /* device time of the last spllt_hip_updown, ms: first scatter to last kernel, between two HIP events on the
  * engine stream (without the host's plan and the staging of W) */
 int spllt_hip_updown_time(void *fkeep, double *device_ms);
+/* ---- sparse right-hand sides and selected outputs (single GPU) -------------------------------
+ * spllt_hip_solve_sparse*: X = A^-1 B (job 0), L^-1 P B (job 1) or L^-T of the scattered B (job 2) for k SPARSE
+ * columns B, at SELECTED entries.  The forward sweep visits only the block columns on the elimination-tree paths
+ * from the nonzeros of B to the root, the backward sweep only those on the paths from the wanted entries to the
+ * root (spllt_hip_solve_sparse_plan lists both sets); skipping a block column whose part of the vector is exactly
+ * zero removes additions of zero only, so the result is that of the full solve up to the order of the atomic
+ * adds.  This is the route to entries of A^-1 outside the pattern of L (unit columns, one wanted entry each), to
+ * a few entries of x for a b with a few nonzeros, and, with spllt_hip_gram_sparse, to B^T A^-1 B.
+ * B: CSC, 1-based, in the user's variable order, exactly like W of spllt_hip_updown: rows strictly increasing
+ * inside a column, empty columns allowed.  Any pattern is legal; the values are not inspected (a NaN propagates
+ * through its column).  sel: nsel 1-based user variables in any order, duplicates allowed; sel == NULL or
+ * nsel < 0: all n entries.
+ * Output: x[q * ldx + t] = the solution of column q at variable sel[t], ldx >= nsel (all entries wanted:
+ * x[q * ldx + i] at variable i, ldx >= n); nothing else is written.  Under job 1 and job 2 a wanted variable
+ * means what it means to spllt_solve: the vector comes back in user order through the pivot permutation.  A
+ * wanted entry that no sweep reaches is an exact 0.0; an empty column gives an exact zero column under jobs 0
+ * and 1.
+ * Columns are worked on in consecutive groups of 32 (a tail of at most 16: one block of 16, as in
+ * spllt_hip_solve_many), each group with its own plan and the blocked fp64-MFMA kernels of solve_many on the
+ * shared workspace of 32 n doubles.  Reproducibility, ordering and pickup are those of spllt_hip_solve_many:
+ * the strips add with atomics (reproducible to rounding), spllt_hip_set_reproducible_solve has no effect here,
+ * all work is ordered on spllt_hip_engine_stream and finished on return, a later factorization or
+ * spllt_hip_updown is picked up.  The staged lists of a group and (host entry points) the gathered block stay
+ * with the handle and grow on demand; spllt_hip_release_solve_sparse returns them.
+ * spllt_hip_gram_sparse: G = B^T A^-1 B = Y^T Y with Y = L^-1 P B, by forward sweeps only; k x k, column-major,
+ * both triangles (exactly symmetric), ldg >= k.  One workspace of 32 n doubles per group of columns stays alive
+ * until the products are done.
+ * Cost (MI355X): the sweeps are bound by dependent launches, one surviving block column
+ * per level of a path -- see there for what the restriction gains and where it does not.
+ * Errors, all decided on the host before anything is enqueued, x untouched: null fkeep, bptr, x or g; brow or
+ * bval null with a non-empty B; k < 0; bptr[0] < 1 or decreasing pointers; a row or sel index outside [1, n];
+ * rows not strictly increasing; ldx or ldg too small; a job other than 0, 1, 2; nothing factorized ->
+ * SPLLT_ERROR_PARAMETER; partitioned handle -> SPLLT_ERROR_UNIMPLEMENTED; no device -> SPLLT_ERROR_HIP; no
+ * device memory -> SPLLT_ERROR_ALLOCATION (nothing of this feature stays allocated; the factor and every other
+ * solve stay usable).  A pending factorization is waited for.  k = 0 and nsel = 0 return 0 and do nothing.
+ * Messages: spllt_hip_last_error. */
+int spllt_hip_solve_sparse    (void *fkeep, int k, const int *bptr, const int *brow, const double *bval,
+                               int nsel, const int *sel, double *x_host, int64_t ldx, int job);
+int spllt_hip_solve_sparse_dev(void *fkeep, int k, const int *bptr, const int *brow, const double *bval,
+                               int nsel, const int *sel, double *x_dev,  int64_t ldx, int job);
+int spllt_hip_gram_sparse     (void *fkeep, int k, const int *bptr, const int *brow, const double *bval,
+                               double *g_host, int64_t ldg);
+/* host only, needs no device and no factor: the block columns the two sweeps would visit for these columns
+ * taken as ONE group, ascending (ids as in "bcol_*" of spllt_hip_sym_get).  The forward set is empty under job 2,
+ * the backward set under job 1.  counts[0 .. 1] receive the two sizes; either array may be NULL to query.
+ * Returns 0 or SPLLT_ERROR_PARAMETER. */
+int spllt_hip_solve_sparse_plan(void *fkeep, int k, const int *bptr, const int *brow, int nsel, const int *sel,
+                                int job, int32_t *fwd_bcols, int64_t fwd_cap, int32_t *bwd_bcols, int64_t bwd_cap,
+                                int64_t counts[2]);
+/* of the last sparse solve or gram, summed over its groups and counted from the lists that were uploaded: block
+ * columns of the forward sweep, of the backward sweep, doubles of L (sum of nrow * width) in the forward set, in
+ * the backward set, kernel launches, workgroups launched by the sweeps */
+int spllt_hip_solve_sparse_info(void *fkeep, int64_t out[6]);
+int spllt_hip_release_solve_sparse(void *fkeep);   /* staged lists, gathered block, gram workspaces back to the pool */
 /* timings of the last factorization, milliseconds */
 int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, double *h2d_ms,
                            int *launches);
@@ -551,7 +606,10 @@ int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, do
  * 64 columns, independent of the handle's panel width): "batch_selinv_units", "batch_selinv_tiles",
  * "batch_selinv_launches", "batch_selinv_rows", "batch_selinv_relpos", "batch_selinv_diag",
  * "batch_selinv_scratch", "batch_selinv_flops", the layouts of the "selinv_*" names; the operator of the
- * refined solves: "matvec_rowptr" (int64), "matvec_col", "matvec_src" (int32).  Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
+ * refined solves: "matvec_rowptr" (int64), "matvec_col", "matvec_src" (int32); "solve_sparse_host_us" (int64):
+ * the host microseconds the last spllt_hip_solve_sparse* / spllt_hip_gram_sparse on THIS handle spent, before its
+ * first device call, on the plans of its groups, the filtered launches and the arrays to upload (not the upload).
+ * Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in
  * spllt_amd/api.py.  Returns the byte length. */
 int64_t spllt_hip_program_get(void *fkeep, const char *name, void *buf, int64_t capacity_bytes);
 /* per-launch device time (ms) of one profiled factorization; returns #launches */
@@ -576,7 +634,9 @@ const char *spllt_hip_version(void);
  * handler now (it must touch nothing once the mark is set); "batch_grid_limit=N": a launch of the batched
  * factorization or solve whose (work items) x (members) exceeds N workgroups is split by member range
  * (N <= 0: back to the hardware limit, (2^32 - 1) / 256 workgroups); "batch_selinv_fused=0" / "=1": the
- * batched selected inversion runs every step as three launches / fuses the small steps (the default).
+ * batched selected inversion runs every step as three launches / fuses the small steps (the default);
+ * "solve_sparse_poison=1" / "=0": the whole workspace of a sparse solve is filled with NaN before its touched
+ * rows are zeroed, so that a sweep that reads a row outside the plan shows up in the result.
  * -1: unknown request. */
 int spllt_hip_debug(const char *what);
 

@@ -72,6 +72,8 @@ HIP_SYMBOLS = [
     "spllt_hip_updown", "spllt_hip_updown_plan", "spllt_hip_updown_info", "spllt_hip_updown_time",
     "spllt_hip_solve_repro", "spllt_hip_solve_repro_dev", "spllt_hip_set_reproducible_solve",
     "spllt_hip_release_solve_repro",
+    "spllt_hip_solve_sparse", "spllt_hip_solve_sparse_dev", "spllt_hip_gram_sparse", "spllt_hip_solve_sparse_plan",
+    "spllt_hip_solve_sparse_info", "spllt_hip_release_solve_sparse",
 ]
 
 _lib = None
@@ -174,6 +176,19 @@ def load():
     lib.spllt_hip_set_reproducible_solve.restype = C.c_int
     lib.spllt_hip_release_solve_repro.argtypes = [vp]
     lib.spllt_hip_release_solve_repro.restype = C.c_int
+    lib.spllt_hip_solve_sparse.argtypes = [vp, C.c_int, ip, ip, dp, C.c_int, ip, dp, C.c_int64, C.c_int]
+    lib.spllt_hip_solve_sparse.restype = C.c_int
+    lib.spllt_hip_solve_sparse_dev.argtypes = [vp, C.c_int, ip, ip, dp, C.c_int, ip, vp, C.c_int64, C.c_int]
+    lib.spllt_hip_solve_sparse_dev.restype = C.c_int
+    lib.spllt_hip_gram_sparse.argtypes = [vp, C.c_int, ip, ip, dp, dp, C.c_int64]
+    lib.spllt_hip_gram_sparse.restype = C.c_int
+    lib.spllt_hip_solve_sparse_plan.argtypes = [vp, C.c_int, ip, ip, C.c_int, ip, C.c_int, C.POINTER(C.c_int32),
+                                                C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)]
+    lib.spllt_hip_solve_sparse_plan.restype = C.c_int
+    lib.spllt_hip_solve_sparse_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.spllt_hip_solve_sparse_info.restype = C.c_int
+    lib.spllt_hip_release_solve_sparse.argtypes = [vp]
+    lib.spllt_hip_release_solve_sparse.restype = C.c_int
     ip = C.POINTER(C.c_int)
     lib.spllt_hip_matvec.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_int64, dp, C.c_int64]
     lib.spllt_hip_matvec.restype = C.c_int

@@ -162,6 +162,8 @@ class Factorization:
         raw = np.zeros(max(nbytes, 1), dtype=np.uint8)
         self.lib.spllt_hip_program_get(self.fkeep, name.encode(), raw.ctypes.data, nbytes)
         raw = raw[:nbytes]
+        if name == "solve_sparse_host_us":
+            return int(raw.view(np.int64)[0])
         if name == "matvec_rowptr":      # the operator of the refined solves
             return raw.view(np.int64)
         if name in ("matvec_col", "matvec_src"):
@@ -333,8 +335,8 @@ class Factorization:
 
     def inverse_entries(self, i, j, Z=None):
         """(A^-1)_{ij} for 0-based user indices i, j (scalars or arrays) whose pivot pair lies in the
-        pattern of L; ValueError for a pair outside it.  Z: the host Z arena (get_inverse()) to read,
-        fetched when not given."""
+        pattern of L; ValueError for a pair outside it (inverse_block(i, j) is the route for those: sparse
+        solves with unit columns).  Z: the host Z arena (get_inverse()) to read, fetched when not given."""
         i, j = np.broadcast_arrays(np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64))
         if ((i < 0) | (i >= self.n) | (j < 0) | (j >= self.n)).any():
             raise ValueError("inverse_entries: index out of range")
@@ -451,6 +453,119 @@ class Factorization:
         rc = self.lib.spllt_hip_release_solve_repro(self.fkeep)
         if rc < 0:
             raise SplltError("spllt_hip_release_solve_repro", rc, self.last_error())
+        return self
+
+    # ---- sparse right-hand sides and selected outputs -----------------------------
+    def _sparse_columns(self, B, where):
+        """B (scipy sparse n x k, or dense) as the 1-based CSC arrays of the C interface; explicit zeros stay"""
+        import scipy.sparse as sp
+        if not sp.issparse(B):
+            B = np.asarray(B, dtype=np.float64)
+            if B.ndim == 1:
+                B = B.reshape(-1, 1)
+        if B.ndim != 2 or B.shape[0] != self.n:
+            raise SplltError(where, -10, f"B must have n = {self.n} rows")
+        B = sp.csc_matrix(B, dtype=np.float64)
+        B.sum_duplicates()
+        B.sort_indices()
+        return (B.shape[1], np.ascontiguousarray(B.indptr + 1, dtype=np.int32),
+                np.ascontiguousarray(np.append(B.indices + 1, 0), dtype=np.int32),
+                np.ascontiguousarray(np.append(B.data, 0.0), dtype=np.float64))
+
+    @staticmethod
+    def _wanted(rows):
+        """rows (0-based variables, None: all) as (nsel, 1-based int32 array or None)"""
+        if rows is None:
+            return -1, None
+        sel = np.ascontiguousarray(np.append(np.asarray(rows, dtype=np.int64).ravel() + 1, 0), dtype=np.int32)
+        return len(sel) - 1, sel
+
+    def solve_sparse(self, B, rows=None, job=0):
+        """spllt_hip_solve_sparse: A^-1 B (job 1: L^-1 P B, job 2: L^-T of the scattered B) for the sparse columns
+        of B (scipy sparse, n x k) at the 0-based variables `rows` (any order, duplicates allowed; None: all n).
+        Only the block columns on the elimination-tree paths of B's nonzeros and of the wanted rows are visited.
+        Returns an F-ordered (len(rows) or n) x k array."""
+        where = "spllt_hip_solve_sparse"
+        k, ptr, row, val = self._sparse_columns(B, where)
+        nsel, sel = self._wanted(rows)
+        m = self.n if sel is None else nsel
+        x = np.zeros((max(m, 1), max(k, 1)), dtype=np.float64, order="F")   # (never a null pointer)
+        rc = self.lib.spllt_hip_solve_sparse(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), nsel,
+                                             None if sel is None else _ip(sel), _dp(x), max(m, 1), job)
+        if rc < 0:
+            raise SplltError(where, rc, self.last_error())
+        return np.asfortranarray(x[:m, :k])
+
+    def solve_sparse_dev(self, B, x_dev_ptr, ldx, rows=None, job=0):
+        """spllt_hip_solve_sparse_dev: as solve_sparse with the result written to device memory, column q at
+        x[q*ldx .. q*ldx + (len(rows) or n)); nothing else is written."""
+        where = "spllt_hip_solve_sparse_dev"
+        k, ptr, row, val = self._sparse_columns(B, where)
+        nsel, sel = self._wanted(rows)
+        rc = self.lib.spllt_hip_solve_sparse_dev(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), nsel,
+                                                 None if sel is None else _ip(sel), C.c_void_p(x_dev_ptr), int(ldx), job)
+        if rc < 0:
+            raise SplltError(where, rc, self.last_error())
+        return self
+
+    def gram(self, B):
+        """spllt_hip_gram_sparse: B^T A^-1 B for the sparse columns of B (n x k), by forward sweeps on the paths
+        of B's nonzeros only; k x k, exactly symmetric."""
+        where = "spllt_hip_gram_sparse"
+        k, ptr, row, val = self._sparse_columns(B, where)
+        G = np.zeros((max(k, 1), max(k, 1)), dtype=np.float64, order="F")
+        rc = self.lib.spllt_hip_gram_sparse(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), _dp(G), max(k, 1))
+        if rc < 0:
+            raise SplltError(where, rc, self.last_error())
+        return G[:k, :k]
+
+    def inverse_block(self, i, j):
+        """A^-1[i][:, j] for any 0-based index sets i, j, inside the pattern of L or not: sparse solves with the
+        unit columns e_j and the wanted rows i."""
+        import scipy.sparse as sp
+        i = np.asarray(i, dtype=np.int64).ravel()
+        j = np.asarray(j, dtype=np.int64).ravel()
+        if ((i < 0) | (i >= self.n)).any() or ((j < 0) | (j >= self.n)).any():
+            raise ValueError("inverse_block: index out of range")
+        E = sp.csc_matrix((np.ones(len(j)), (j, np.arange(len(j)))), shape=(self.n, len(j)))
+        return self.solve_sparse(E, rows=i)
+
+    def solve_sparse_plan(self, B, rows=None, job=0):
+        """spllt_hip_solve_sparse_plan: (fwd, bwd), the block columns the two sweeps of solve_sparse(B, rows, job)
+        would visit with B's columns taken as one group, ascending (needs no device and no factor)"""
+        where = "spllt_hip_solve_sparse_plan"
+        k, ptr, row, _ = self._sparse_columns(B, where)
+        nsel, sel = self._wanted(rows)
+        selp = None if sel is None else _ip(sel)
+        cnt = np.zeros(2, dtype=np.int64)
+        cp = cnt.ctypes.data_as(C.POINTER(C.c_int64))
+        rc = self.lib.spllt_hip_solve_sparse_plan(self.fkeep, k, _ip(ptr), _ip(row), nsel, selp, job, None, 0, None, 0, cp)
+        if rc < 0:
+            raise SplltError(where, rc, self.last_error())
+        fwd = np.zeros(max(int(cnt[0]), 1), dtype=np.int32)
+        bwd = np.zeros(max(int(cnt[1]), 1), dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        rc = self.lib.spllt_hip_solve_sparse_plan(self.fkeep, k, _ip(ptr), _ip(row), nsel, selp, job,
+                                                  fwd.ctypes.data_as(i32), len(fwd), bwd.ctypes.data_as(i32), len(bwd), cp)
+        if rc < 0:
+            raise SplltError(where, rc, self.last_error())
+        return fwd[:int(cnt[0])], bwd[:int(cnt[1])]
+
+    def solve_sparse_info(self):
+        """of the last solve_sparse / gram, summed over its groups of columns: block columns and doubles of L the
+        forward / backward sweeps visited, kernel launches, workgroups of the sweeps"""
+        out = np.zeros(6, dtype=np.int64)
+        rc = self.lib.spllt_hip_solve_sparse_info(self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        if rc < 0:
+            raise SplltError("spllt_hip_solve_sparse_info", rc, self.last_error())
+        return dict(zip(("fwd_bcols", "bwd_bcols", "fwd_entries", "bwd_entries", "launches", "workgroups"),
+                        (int(v) for v in out)))
+
+    def release_solve_sparse(self):
+        """The staged lists, the gathered block and the gram workspaces back to the device pool."""
+        rc = self.lib.spllt_hip_release_solve_sparse(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_solve_sparse", rc, self.last_error())
         return self
 
     # ---- refined solves --------------------------------------------------------

@@ -613,7 +613,8 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 // reads it, "teardown" runs the atexit handler of the pools now; "batch_grid_limit=N" lowers the grid size
 // from which on a batched launch is split by member range (N <= 0: the hardware limit again);
 // "batch_selinv_fused=0|1": 0 forces the three-launch form of every step of the batched selected inversion;
-// "rsolve_poison=0|1": 1 fills the scratch of the reproducible solve with NaN before every sweep
+// "rsolve_poison=0|1": 1 fills the scratch of the reproducible solve with NaN before every sweep;
+// "solve_sparse_poison=0|1": 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
 int spllt_hip_debug(const char* what) {
   if (!what) return -1;
   const std::string w(what);
@@ -626,6 +627,10 @@ int spllt_hip_debug(const char* what) {
   }
   if (w == "batch_selinv_fused=0" || w == "batch_selinv_fused=1") {
     set_batch_selinv_fused(w.back() == '1');
+    return 0;
+  }
+  if (w == "solve_sparse_poison=0" || w == "solve_sparse_poison=1") {   // NaN in the workspace of a sparse solve
+    set_solve_sparse_poison(w.back() == '1');
     return 0;
   }
   if (w == "rsolve_poison=0" || w == "rsolve_poison=1") {   // NaN in the scratch of the reproducible solve before a sweep
@@ -1142,6 +1147,103 @@ int spllt_hip_updown_info(void* fkeep, int64_t out[4]) {
   return 0;
 }
 
+// ---- sparse right-hand sides and selected outputs --------------------------------------------------
+// every check that needs no device (a rejected call touches nothing), then the handle's engine with its factor
+// finished; out: the output array, ld against the number of wanted entries (gram: against k)
+static int solve_sparse_engine(Fkeep* f, const char* what, int k, const int* bptr, const int* brow, const double* bval,
+                               int nsel, const int* sel, const void* out, int64_t ld, int64_t ld_min, int job) {
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!out) return batch_param_error(f, what, "the output array is null");
+  if (job < 0 || job > 2) return batch_param_error(f, what, "job is not 0, 1 or 2");
+  {
+    std::string why;
+    if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) return batch_param_error(f, what, why.c_str());
+  }
+  if (k > 0 && bptr[k] > bptr[0] && !bval) return batch_param_error(f, what, "the array of values is null");
+  if (ld < ld_min) return batch_param_error(f, what, "the leading dimension of the output is too small");
+  if (int rc = batch_partitioned(f, what)) return rc;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (int rc = do_wait(f)) return rc;
+  if (!f->eng) {
+    // no factorization yet: an engine only to tell "no device" from "nothing factorized"
+    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
+    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
+    f->eng->set_exchange_buffer(f->xbuf);
+  }
+  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
+  if (no_factor(f) || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
+  return 0;
+}
+
+static int solve_sparse_impl(const char* what, void* fkeep, int k, const int* bptr, const int* brow, const double* bval,
+                             int nsel, const int* sel, double* x, int64_t ldx, int job, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!sel || nsel < 0) { sel = nullptr; nsel = -1; }
+  const int64_t nout = !f || !f->S ? 0 : (sel ? nsel : f->S->n);
+  int rc = solve_sparse_engine(f, what, k, bptr, brow, bval, nsel, sel, x, ldx, nout, job);
+  if (rc) return rc;
+  rc = f->eng->solve_sparse(k, bptr, brow, bval, nsel, sel, x, ldx, job, dev);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_solve_sparse(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, int nsel,
+                           const int* sel, double* x_host, int64_t ldx, int job) {
+  return solve_sparse_impl("spllt_hip_solve_sparse", fkeep, k, bptr, brow, bval, nsel, sel, x_host, ldx, job, false);
+}
+
+int spllt_hip_solve_sparse_dev(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, int nsel,
+                               const int* sel, double* x_dev, int64_t ldx, int job) {
+  return solve_sparse_impl("spllt_hip_solve_sparse_dev", fkeep, k, bptr, brow, bval, nsel, sel, x_dev, ldx, job, true);
+}
+
+int spllt_hip_gram_sparse(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, double* g_host,
+                          int64_t ldg) {
+  const char* what = "spllt_hip_gram_sparse";
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_sparse_engine(f, what, k, bptr, brow, bval, -1, nullptr, g_host, ldg, k, 0);
+  if (rc) return rc;
+  rc = f->eng->gram_sparse(k, bptr, brow, bval, g_host, ldg);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_solve_sparse_plan(void* fkeep, int k, const int* bptr, const int* brow, int nsel, const int* sel, int job,
+                                int32_t* fwd_bcols, int64_t fwd_cap, int32_t* bwd_bcols, int64_t bwd_cap,
+                                int64_t counts[2]) {
+  const char* what = "spllt_hip_solve_sparse_plan";
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!counts) return batch_param_error(f, what, "counts is null");
+  if (job < 0 || job > 2) return batch_param_error(f, what, "job is not 0, 1 or 2");
+  if (!sel || nsel < 0) { sel = nullptr; nsel = -1; }
+  std::string why;
+  if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) return batch_param_error(f, what, why.c_str());
+  SolveSparsePlan P;
+  build_solve_sparse_plan(*f->S, 0, k, bptr, brow, nsel, sel, job, P);
+  counts[0] = (int64_t)P.fwd.size();
+  counts[1] = (int64_t)P.bwd.size();
+  if (fwd_bcols) (void)copy_out(P.fwd, fwd_bcols, fwd_cap);
+  if (bwd_bcols) (void)copy_out(P.bwd, bwd_bcols, bwd_cap);
+  return 0;
+}
+
+int spllt_hip_solve_sparse_info(void* fkeep, int64_t out[6]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 6; ++i) out[i] = f->eng ? f->eng->solve_sparse_info()[i] : 0;
+  return 0;
+}
+
+int spllt_hip_release_solve_sparse(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (!f->eng) return 0;
+  int rc = do_wait(f);
+  if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
+  rc = f->eng->release_solve_sparse();
+  return rc ? feature_fail(f, rc) : 0;
+}
+
 int spllt_hip_get_factor_batch(void* fkeep, int member, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   const char* what = "spllt_hip_get_factor_batch";
@@ -1371,6 +1473,11 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
   if (!f || !f->S || !name) return -1;
   // The program can be inspected without a GPU: build it on demand.
   Program local;
+  if (std::string(name) == "solve_sparse_host_us") {   // (of this handle's last sparse solve or gram; no program needed)
+    const int64_t v = f->eng ? f->eng->solve_sparse_host_us() : 0;
+    if (buf && cap >= (int64_t)sizeof v) std::memcpy(buf, &v, sizeof v);
+    return (int64_t)sizeof v;
+  }
   const Program* P;
   if (f->eng && !f->eng->status()) {
     P = &f->eng->program();

@@ -56,6 +56,8 @@ struct EngineOptions {
 void set_batch_selinv_fused(bool on);
 // debug: the scratch of the reproducible solve is filled with NaN before every sweep
 void set_rsolve_poison(bool on);
+// debug: the workspace of a sparse solve is filled with NaN before its touched rows are zeroed
+void set_solve_sparse_poison(bool on);
 bool batch_selinv_fused();
 
 struct FactorStats {
@@ -152,6 +154,24 @@ class Engine {
   int solve_repro_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order);
   int solve_repro(double* x_host, int nrhs, int64_t ldx, int job);   // host vectors, user order
   int release_solve_repro();                                          // tables and scratch back to the pool
+  // ---- sparse right-hand sides and selected outputs (solve_sparse.hip, single GPU): B = k sparse columns (CSC,
+  // 1-based, user order, validated by the caller: check_sparse_columns), sel = nsel wanted user variables (null:
+  // all n).  Per group of 32 columns (a tail of at most 16: a block of 16) the substitution program is filtered
+  // to the block columns of build_solve_sparse_plan and run by the kernels of solve_many on the shared
+  // workspace; x[q * ldx + t] = the solution of column q at sel[t] (at variable t when all are wanted).
+  // Everything a call needs on the device is taken before anything is enqueued (-1: no memory, nothing of
+  // this feature stays allocated); the stream is drained on return.
+  int solve_sparse(int k, const int* bptr, const int* brow, const double* bval, int nsel, const int* sel, double* x,
+                   int64_t ldx, int job, bool dev);
+  // G = B^T A^-1 B (k x k, column-major, both triangles, host): forward sweeps only, one workspace per group
+  int gram_sparse(int k, const int* bptr, const int* brow, const double* bval, double* g_host, int64_t ldg);
+  // of the last solve_sparse / gram_sparse: block columns of the forward / backward sweeps, doubles of L in
+  // them, kernel launches, workgroups of the sweeps -- summed over the groups, from the uploaded lists
+  const int64_t* solve_sparse_info() const { return ss_info_; }
+  // host microseconds the last solve_sparse / gram_sparse of this engine spent, before its first device call, on
+  // the plans of its groups, the filtered launches and the arrays to be uploaded (not the upload itself)
+  int64_t solve_sparse_host_us() const { return ss_host_us_; }
+  int release_solve_sparse();
   // on: solve(), solve_dev(phase -1) and the preconditioner of solve_refined go through the path above
   void set_reproducible_solve(bool on) { repro_on_ = on; }
   // ---- refined solves (refine.hip, single GPU): the operator A on the analysed pattern, gather-only, in
@@ -357,6 +377,17 @@ class Engine {
   // per launch of sprog_.fwd / .bwd (prepare_solve): may it use k_solve_diag4, and its ONE block column or null
   std::vector<SolveLaunchInfo> sv_fwd_, sv_bwd_;
   SolveTablesView solve_tables() const { return {d_slist_, d_stiles_, d_sunits_, d_L_, d_dinv_, d_rlist_}; }
+  // the rule of prepare_solve for one launch over the lists it indexes (the program's, or filtered ones)
+  SolveLaunchInfo solve_launch_info(const SolveLaunch& l, const int* list, const UpdTile* tiles) const;
+  // where block column b sits in the program (prepare_solve): its launches of fwd / bwd (-1: no strips), its
+  // entry of diag_list and its tiles -- what filtering the program to a set of block columns walks
+  struct SolveBcolSlot {
+    int fdiag = -1, fstrip = -1, bdiag = -1, bstrip = -1;
+    int64_t dpos = 0, t0 = 0, tn = 0;
+  };
+  std::vector<SolveBcolSlot> sv_slot_;
+  int64_t sv_entries_ = 0, sv_bwd_wgs_ = 0;   // doubles of L in all block columns; workgroups of the whole backward sweep
+  bool sv_slot_ok_ = true;   // the program has the shape the slots assume (checked while they are built)
   // f(launch, info) for the launches `job` and `phase` ask for, in program order (engine_solve.cpp)
   template <class F> void for_each_solve_launch(int job, int phase, F&& f) const;
   // user variable -> pivot position, for every permutation on the device: uploaded on first use, kept
@@ -389,6 +420,34 @@ class Engine {
   void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
   double* d_smW_ = nullptr;        // n * 32 doubles: W[p * rb + q]
   double* d_smstage_ = nullptr;    // n * 32 doubles: a block of host vectors in the caller's order (solve_many)
+  // sparse right-hand sides: one group of columns, planned and filtered on the host
+  struct SsGroup {
+    int c0 = 0, nv = 0, rb = 16;
+    bool bwd_full = false;                        // all entries wanted: the backward sweep is the unfiltered program
+    std::vector<SolveLaunch> fwd, bwd;            // filtered launches, `first` into the compacted lists
+    std::vector<SolveLaunchInfo> fwd_i, bwd_i;
+    std::vector<int> list, chunks, selpos;        // compacted diag list; (first, length) chunks; wanted positions
+    std::vector<UpdTile> tiles;
+    std::vector<int64_t> pos;                     // scatter: pivot position * rb + column
+    std::vector<double> val;
+    int64_t info[6] = {0, 0, 0, 0, 0, 0};
+    size_t bytes = 0;                             // of the staged tables
+  };
+  struct SsTables { int* list; UpdTile* tiles; int* chunks; int* selpos; int64_t* pos; double* val; };
+  void ss_filter(bool bwd, const std::vector<int>& set, SsGroup& g) const;
+  void ss_plan_group(SsGroup& g, const int* bptr, const int* brow, const double* bval, int nsel, const int* sel,
+                     int job, const std::vector<int>* zero_ranges);
+  int ss_upload(const SsGroup& g, SsTables& t);
+  int ss_enqueue(const SsGroup& g, const SsTables& t, int job, double* W);
+  hipError_t ss_reserve(void** p, size_t* cap, size_t bytes);
+  int ss_fail_alloc(const char* what, size_t bytes, hipError_t e);
+  char* d_sstab_ = nullptr;        // staged tables of one group (grows, stays)
+  double* d_ssout_ = nullptr;      // gathered entries / G of a host entry point, the partial products of gram
+  double* d_ssgramW_ = nullptr;    // gram: the workspaces of the groups after the first
+  size_t ss_tab_cap_ = 0, ss_out_cap_ = 0, ss_gram_cap_ = 0;
+  int64_t ss_info_[6] = {0, 0, 0, 0, 0, 0};
+  int64_t ss_host_us_ = 0;
+  int ss_filterable();
   // refined solves: operator tables and work vectors (taken on first use, all or nothing)
   int prepare_refine(bool host_val);
   int refine_apply_factor(double* v, int nv);

@@ -2,6 +2,7 @@
 // for many right-hand sides, the reproducible solve and the refined solves.  They share one walk over the
 // program's launches, one table view, one order table and one staging helper.
 #include <atomic>
+#include <chrono>
 #include <climits>
 #include <cstdlib>
 
@@ -30,31 +31,71 @@ int Engine::prepare_solve() {
     const char* e = std::getenv("SPLLT_SOLVE_DIAG4");
     solve_four_ = prog_.pw == 64 && prog_.cb == 64 && !(e && std::atoi(e) == 0);
   }
-  // per launch, once: block columns of at most four 64-wide panels take the diagonal kernel that reads L in
-  // one round trip; a launch on ONE block column (every step of the upper levels) passes its descriptor by value
+  // per launch, once (solve_launch_info), and per block column where it sits in the launches (sv_slot_)
   auto info = [&](const std::vector<SolveLaunch>& ls, std::vector<SolveLaunchInfo>& out) {
     out.assign(ls.size(), SolveLaunchInfo{false, nullptr});
-    for (size_t i = 0; i < ls.size(); ++i) {
-      const bool diag = ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD;
-      bool four = solve_four_ && diag;
-      for (int64_t q = ls[i].first; four && q < ls[i].first + ls[i].count; ++q)
-        four = sprog_.units[(size_t)sprog_.diag_list[(size_t)q]].w <= 256;
-      out[i].four = four;
-      if (ls[i].count <= 0) continue;
-      if (diag) {
-        if (ls[i].count == 1) out[i].one = &sprog_.units[(size_t)sprog_.diag_list[(size_t)ls[i].first]];
-      } else {
-        const UpdTile* tl = sprog_.tiles.data() + ls[i].first;
-        bool same = true;
-        for (int64_t q = 0; same && q < ls[i].count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
-        if (same && ls[i].count < 32768) out[i].one = &sprog_.units[(size_t)tl[0].unit];
-      }
-    }
+    for (size_t i = 0; i < ls.size(); ++i) out[i] = solve_launch_info(ls[i], sprog_.diag_list.data(), sprog_.tiles.data());
   };
   info(sprog_.fwd, sv_fwd_);
   info(sprog_.bwd, sv_bwd_);
+  sv_slot_.assign(sprog_.units.size(), SolveBcolSlot{});
+  sv_slot_ok_ = true;
+  sv_entries_ = 0;
+  sv_bwd_wgs_ = 0;
+  for (const SolveUnit& u : sprog_.units) sv_entries_ += (int64_t)u.nrow * u.w;
+  for (const SolveLaunch& l : sprog_.bwd) sv_bwd_wgs_ += l.count;
+  for (int sweep = 0; sweep < 2; ++sweep) {
+    const std::vector<SolveLaunch>& ls = sweep ? sprog_.bwd : sprog_.fwd;
+    for (size_t i = 0; i < ls.size(); ++i) {
+      const bool diag = ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD;
+      for (int64_t q = ls[i].first; q < ls[i].first + ls[i].count; ++q) {
+        SolveBcolSlot& sl = sv_slot_[(size_t)(diag ? sprog_.diag_list[(size_t)q] : sprog_.tiles[(size_t)q].unit)];
+        // what the filter relies on: per sweep a block column sits in ONE diagonal launch, and its strips are one
+        // run of consecutive tiles (strip 0, 1, ...) of ONE strip launch, the same run in both sweeps
+        if (diag) {
+          int& at = sweep ? sl.bdiag : sl.fdiag;
+          if (at >= 0 || (sweep && sl.dpos != q)) sv_slot_ok_ = false;
+          at = (int)i;
+          sl.dpos = q;
+        } else {
+          int& at = sweep ? sl.bstrip : sl.fstrip;
+          if (at >= 0 && at != (int)i) sv_slot_ok_ = false;
+          at = (int)i;
+          const int64_t ti = sprog_.tiles[(size_t)q].ti;
+          if (!sweep) {   // (the backward launches index the same tiles)
+            if (sl.tn == 0) sl.t0 = q;
+            if (q != sl.t0 + sl.tn || ti != sl.tn) sv_slot_ok_ = false;
+            ++sl.tn;
+          } else if (q < sl.t0 || q >= sl.t0 + sl.tn || ti != q - sl.t0) {
+            sv_slot_ok_ = false;
+          }
+        }
+      }
+    }
+  }
   solve_ready_ = true;
   return 0;
+}
+
+// block columns of at most four 64-wide panels take the diagonal kernel that reads L in one round trip; a launch
+// on ONE block column (every step of the upper levels) passes its descriptor by value.  list / tiles: the
+// arrays l.first indexes.
+SolveLaunchInfo Engine::solve_launch_info(const SolveLaunch& l, const int* list, const UpdTile* tiles) const {
+  SolveLaunchInfo out{false, nullptr};
+  const bool diag = l.kind == SV_DIAG_FWD || l.kind == SV_DIAG_BWD;
+  bool four = solve_four_ && diag;
+  for (int64_t q = l.first; four && q < l.first + l.count; ++q) four = sprog_.units[(size_t)list[q]].w <= 256;
+  out.four = four;
+  if (l.count <= 0) return out;
+  if (diag) {
+    if (l.count == 1) out.one = &sprog_.units[(size_t)list[l.first]];
+  } else {
+    const UpdTile* tl = tiles + l.first;
+    bool same = true;
+    for (int64_t q = 0; same && q < l.count; ++q) same = tl[q].unit == tl[0].unit && tl[q].ti == (short)q;
+    if (same && l.count < 32768) out.one = &sprog_.units[(size_t)tl[0].unit];
+  }
+  return out;
 }
 
 // the launches of the substitution program that `job` (0 both sweeps, 1 forward, 2 backward) and `phase` (-1
@@ -221,6 +262,304 @@ int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
     if ((rc = sync_stream(stream_, "solve_many sync"))) return rc;
     done += nv;
   }
+  return 0;
+}
+
+// ---- sparse right-hand sides and selected outputs ----------------------------------------------------
+static std::atomic<bool> g_ss_poison{false};
+void set_solve_sparse_poison(bool on) { g_ss_poison.store(on); }
+
+// the launches of one sweep that hold a block column of `set` (ascending), with their entries compacted into
+// g.list / g.tiles in program order; a launch left empty is dropped.  Work: the set and its tiles, sorted.
+void Engine::ss_filter(bool bwd, const std::vector<int>& set, SsGroup& g) const {
+  struct Item { int launch; int64_t key; int b; };
+  std::vector<Item> items;
+  items.reserve(2 * set.size());
+  for (int b : set) {
+    const SolveBcolSlot& sl = sv_slot_[(size_t)b];
+    const int ld = bwd ? sl.bdiag : sl.fdiag, ls = bwd ? sl.bstrip : sl.fstrip;
+    if (ld >= 0) items.push_back({ld, sl.dpos, b});
+    if (ls >= 0) items.push_back({ls, sl.t0, b});
+  }
+  std::sort(items.begin(), items.end(),
+            [](const Item& a, const Item& b) { return a.launch != b.launch ? a.launch < b.launch : a.key < b.key; });
+  const std::vector<SolveLaunch>& prog = bwd ? sprog_.bwd : sprog_.fwd;
+  std::vector<SolveLaunch>& out = bwd ? g.bwd : g.fwd;
+  for (size_t i = 0; i < items.size();) {
+    const SolveLaunch& src = prog[(size_t)items[i].launch];
+    const bool diag = src.kind == SV_DIAG_FWD || src.kind == SV_DIAG_BWD;
+    SolveLaunch l{src.kind, src.level, (int64_t)(diag ? g.list.size() : g.tiles.size()), 0};
+    size_t j = i;
+    for (; j < items.size() && items[j].launch == items[i].launch; ++j) {
+      const SolveBcolSlot& sl = sv_slot_[(size_t)items[j].b];
+      if (diag) {
+        g.list.push_back(items[j].b);
+        ++l.count;
+        g.info[bwd ? 1 : 0] += 1;
+        g.info[bwd ? 3 : 2] += (int64_t)sprog_.units[(size_t)items[j].b].nrow * sprog_.units[(size_t)items[j].b].w;
+      } else {
+        g.tiles.insert(g.tiles.end(), sprog_.tiles.begin() + sl.t0, sprog_.tiles.begin() + sl.t0 + sl.tn);
+        l.count += sl.tn;
+      }
+    }
+    out.push_back(l);
+    g.info[5] += l.count;
+    i = j;
+  }
+}
+
+// plan, filter and stage one group (host only).  zero_ranges: the rows to clear when they are not the group's own
+// touched rows (gram: those of the whole call)
+void Engine::ss_plan_group(SsGroup& g, const int* bptr, const int* brow, const double* bval, int nsel, const int* sel,
+                           int job, const std::vector<int>* zero_ranges) {
+  const Symbolic& S = *S_;
+  SolveSparsePlan P;
+  build_solve_sparse_plan(S, g.c0, g.c0 + g.nv, bptr, brow, nsel, sel, job, P);
+  ss_filter(false, P.fwd, g);
+  if (!P.bwd.empty() && P.bwd.size() == sprog_.units.size()) {
+    // every block column: the backward sweep is the program's own, on the tables that are resident already
+    g.bwd_full = true;
+    g.info[1] += (int64_t)sprog_.units.size();
+    g.info[3] += sv_entries_;
+    g.info[5] += sv_bwd_wgs_;
+  } else {
+    ss_filter(true, P.bwd, g);
+  }
+  g.fwd_i.resize(g.fwd.size());
+  g.bwd_i.resize(g.bwd.size());
+  for (size_t i = 0; i < g.fwd.size(); ++i) g.fwd_i[i] = solve_launch_info(g.fwd[i], g.list.data(), g.tiles.data());
+  for (size_t i = 0; i < g.bwd.size(); ++i) g.bwd_i[i] = solve_launch_info(g.bwd[i], g.list.data(), g.tiles.data());
+  const std::vector<int>& rg = zero_ranges ? *zero_ranges : P.range;
+  for (size_t r = 0; r + 1 < rg.size(); r += 2)
+    for (int o = 0; o < rg[r + 1]; o += kSsChunkRows) {
+      g.chunks.push_back(rg[r] + o);
+      g.chunks.push_back(std::min(kSsChunkRows, rg[r + 1] - o));
+    }
+  // the entries of B in touched rows (job 2: what lies outside the closure of the wanted rows cannot reach them)
+  auto touched = [&](int p) {
+    size_t lo = 0, hi = P.range.size() / 2;
+    while (lo < hi) {
+      const size_t mid = (lo + hi) / 2;
+      if (P.range[2 * mid] + P.range[2 * mid + 1] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo < P.range.size() / 2 && P.range[2 * lo] <= p;
+  };
+  for (int q = 0; q < g.nv; ++q)
+    for (int e = bptr[g.c0 + q] - 1; e < bptr[g.c0 + q + 1] - 1; ++e) {
+      const int p = S.order[(size_t)brow[e] - 1];
+      if (job == 2 && !touched(p)) continue;
+      g.pos.push_back((int64_t)p * g.rb + q);
+      g.val.push_back(bval[e]);
+    }
+  if (sel && nsel >= 0)
+    for (int t = 0; t < nsel; ++t) g.selpos.push_back(S.order[(size_t)sel[t] - 1]);
+  // (the size TableStager will lay these six arrays out in: 256-byte aligned slots of at least 8 bytes)
+  g.bytes = 0;
+  for (size_t b : {g.list.size() * sizeof(int), g.tiles.size() * sizeof(UpdTile), g.chunks.size() * sizeof(int),
+                   g.selpos.size() * sizeof(int), g.pos.size() * sizeof(int64_t), g.val.size() * sizeof(double)})
+    g.bytes = (g.bytes + 255) / 256 * 256 + std::max<size_t>(b, 8);
+}
+
+// 0, or -99 when the substitution program does not have the shape the filter relies on (prepare_solve)
+int Engine::ss_filterable() {
+  if (sv_slot_ok_) return 0;
+  feature_err_ = "solve_sparse: the substitution program holds a block column in more than one diagonal launch or "
+                 "with strips that are not one run of one launch; filtering it is not implemented";
+  return -99;
+}
+
+hipError_t Engine::ss_reserve(void** p, size_t* cap, size_t bytes) {
+  if (*p && *cap >= bytes) return hipSuccess;
+  if (*p) release_buffer(*p);
+  *p = nullptr;
+  *cap = 0;
+  hipError_t e = dalloc(p, std::max<size_t>(bytes, 8));
+  if (e == hipSuccess) *cap = bytes; else *p = nullptr;
+  return e;
+}
+
+int Engine::ss_fail_alloc(const char* what, size_t bytes, hipError_t e) {
+  (void)hipGetLastError();
+  for (void* p : {(void*)d_sstab_, (void*)d_ssout_, (void*)d_ssgramW_})
+    if (p) release_buffer(p);
+  d_sstab_ = nullptr; d_ssout_ = nullptr; d_ssgramW_ = nullptr;
+  ss_tab_cap_ = ss_out_cap_ = ss_gram_cap_ = 0;
+  feature_err_ = std::string(what) + ": not enough device memory (" + std::to_string(bytes >> 20) + " MiB): " +
+                 hipGetErrorString(e);
+  return alloc_code(e);
+}
+
+// the tables of a group into the pool buffer (reserved by the caller; the stream is idle)
+int Engine::ss_upload(const SsGroup& g, SsTables& t) {
+  TableStager tab;
+  tab.add(&t.list, g.list);
+  tab.add(&t.tiles, g.tiles);
+  tab.add(&t.chunks, g.chunks);
+  tab.add(&t.selpos, g.selpos);
+  tab.add(&t.pos, g.pos);
+  tab.add(&t.val, g.val);
+  char* blob = nullptr;
+  HIPCHK(tab.commit(&blob, [this](void** q, size_t b) {
+    *q = d_sstab_;
+    return b <= ss_tab_cap_ ? hipSuccess : hipErrorOutOfMemory;
+  }), "upload the tables of a sparse solve");
+  return 0;
+}
+
+// zero the touched rows of W, scatter the group's entries, the filtered sweeps `job` asks for (enqueue only);
+// returns the number of kernel launches
+int Engine::ss_enqueue(const SsGroup& g, const SsTables& t, int job, double* W) {
+  if (g_ss_poison.load())
+    (void)hipMemsetAsync(W, 0xFF, sizeof(double) * (size_t)g.rb * (size_t)S_->n, stream_);
+  launch_ss_zero(stream_, t.chunks, (int)(g.chunks.size() / 2), g.rb, W);
+  launch_ss_scatter(stream_, t.pos, t.val, (int64_t)g.pos.size(), W);
+  SolveTablesView tv = solve_tables();
+  tv.list = t.list;
+  tv.tiles = t.tiles;
+  if (job != 2)
+    for (size_t i = 0; i < g.fwd.size(); ++i) launch_solve_many(stream_, tv, g.fwd[i], g.fwd_i[i], W, g.rb);
+  const std::vector<SolveLaunch>& bwd = g.bwd_full ? sprog_.bwd : g.bwd;
+  const std::vector<SolveLaunchInfo>& bwd_i = g.bwd_full ? sv_bwd_ : g.bwd_i;
+  const SolveTablesView tb = g.bwd_full ? solve_tables() : tv;
+  if (job != 1)
+    for (size_t i = 0; i < bwd.size(); ++i) launch_solve_many(stream_, tb, bwd[i], bwd_i[i], W, g.rb);
+  return (g.chunks.empty() ? 0 : 1) + (g.pos.empty() ? 0 : 1) + (int)(job != 2 ? g.fwd.size() : 0) +
+         (int)(job != 1 ? bwd.size() : 0);
+}
+
+int Engine::solve_sparse(int k, const int* bptr, const int* brow, const double* bval, int nsel, const int* sel,
+                         double* x, int64_t ldx, int job, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n;
+  const bool all = !sel || nsel < 0;
+  const int64_t nout = all ? n : nsel;
+  if (job < 0 || job > 2 || k < 0 || !bptr || !x || ldx < nout) return -10;
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (k == 0 || nout == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_many(false);
+  if (rc) return rc;
+  if ((rc = ss_filterable())) return rc;
+  // every group planned, filtered and staged on the host, and all device memory taken, before anything runs
+  const auto host_t0 = std::chrono::steady_clock::now();
+  std::vector<SsGroup> groups;
+  size_t tab_bytes = 0;
+  for (int done = 0; done < k;) {
+    const int left = k - done;
+    SsGroup g;
+    g.c0 = done;
+    g.rb = left > 16 ? 32 : 16;
+    g.nv = std::min(left, g.rb);
+    ss_plan_group(g, bptr, brow, bval, all ? -1 : nsel, all ? nullptr : sel, job, nullptr);
+    tab_bytes = std::max(tab_bytes, g.bytes);
+    done += g.nv;
+    groups.push_back(std::move(g));
+  }
+  ss_host_us_ = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
+  const size_t out_bytes = dev ? 0 : sizeof(double) * (size_t)nout * 32;
+  hipError_t e = ss_reserve((void**)&d_sstab_, &ss_tab_cap_, tab_bytes);
+  if (e == hipSuccess && !dev) e = ss_reserve((void**)&d_ssout_, &ss_out_cap_, out_bytes);
+  if (e != hipSuccess) return ss_fail_alloc("solve_sparse", tab_bytes + out_bytes, e);
+  for (int64_t& v : ss_info_) v = 0;
+  for (const SsGroup& g : groups) {
+    SsTables t{};
+    if ((rc = ss_upload(g, t))) return rc;
+    ss_info_[4] += 1 + ss_enqueue(g, t, job, d_smW_);   // (+ the gather)
+    double* xg = dev ? x + (int64_t)g.c0 * ldx : d_ssout_;
+    const int64_t ldg = dev ? ldx : nout;
+    if (all)
+      launch_solve_many_unpack(stream_, xg, ldg, d_order_, n, g.nv, g.rb, d_smW_);
+    else
+      launch_ss_gather(stream_, xg, ldg, t.selpos, nsel, g.nv, g.rb, d_smW_);
+    HIPCHK(hipGetLastError(), "solve_sparse launch");
+    if (!dev && (rc = copy_vectors(false, d_ssout_, x + (int64_t)g.c0 * ldx, ldx, g.nv, "x D2H", nout))) return rc;
+    if ((rc = sync_stream(stream_, "solve_sparse sync"))) return rc;   // (the next group reuses the tables)
+    for (int i = 0; i < 6; ++i) ss_info_[i] += g.info[i];
+  }
+  return 0;
+}
+
+int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* bval, double* g_host, int64_t ldg) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n;
+  if (k < 0 || !bptr || !g_host || ldg < k) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (k == 0) return 0;
+  if (n == 0) {
+    for (int j = 0; j < k; ++j)
+      for (int i = 0; i < k; ++i) g_host[(int64_t)j * ldg + i] = 0.0;
+    return 0;
+  }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_many(false);
+  if (rc) return rc;
+  if ((rc = ss_filterable())) return rc;
+  // the rows the products run over: those any column of the call touches, cleared in every group's workspace
+  static const int none = 0;
+  const auto host_t0 = std::chrono::steady_clock::now();
+  SolveSparsePlan U;
+  build_solve_sparse_plan(*S_, 0, k, bptr, brow, 0, &none, 1, U);
+  std::vector<SsGroup> groups;
+  size_t tab_bytes = 0;
+  for (int done = 0; done < k;) {
+    const int left = k - done;
+    SsGroup g;
+    g.c0 = done;
+    g.rb = left > 16 ? 32 : 16;
+    g.nv = std::min(left, g.rb);
+    ss_plan_group(g, bptr, brow, bval, 0, &none, 1, &U.range);
+    tab_bytes = std::max(tab_bytes, g.bytes);
+    done += g.nv;
+    groups.push_back(std::move(g));
+  }
+  ss_host_us_ = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
+  const size_t ng = groups.size(), nchunk = groups[0].chunks.size() / 2;
+  const size_t wstride = (size_t)32 * (size_t)n;
+  const size_t gram_bytes = sizeof(double) * wstride * (ng - 1);
+  const size_t out_bytes = sizeof(double) * ((size_t)k * (size_t)k + nchunk * 1024);
+  hipError_t e = ss_reserve((void**)&d_sstab_, &ss_tab_cap_, tab_bytes);
+  if (e == hipSuccess) e = ss_reserve((void**)&d_ssout_, &ss_out_cap_, out_bytes);
+  if (e == hipSuccess && ng > 1) e = ss_reserve((void**)&d_ssgramW_, &ss_gram_cap_, gram_bytes);
+  if (e != hipSuccess) return ss_fail_alloc("gram_sparse", tab_bytes + out_bytes + gram_bytes, e);
+  for (int64_t& v : ss_info_) v = 0;
+  auto workspace = [&](size_t gi) { return gi == 0 ? d_smW_ : d_ssgramW_ + (gi - 1) * wstride; };
+  SsTables t{};
+  for (size_t gi = 0; gi < ng; ++gi) {
+    const SsGroup& g = groups[gi];
+    if ((rc = ss_upload(g, t))) return rc;
+    ss_info_[4] += ss_enqueue(g, t, 1, workspace(gi));
+    HIPCHK(hipGetLastError(), "gram_sparse launch");
+    if ((rc = sync_stream(stream_, "gram_sparse sync"))) return rc;   // (the next group reuses the tables)
+    for (int i = 0; i < 6; ++i) ss_info_[i] += g.info[i];
+  }
+  // (the chunk list of the last group, the same in every group, is still in the tables)
+  double* dG = d_ssout_;
+  double* part = d_ssout_ + (size_t)k * (size_t)k;
+  for (size_t I = 0; I < ng; ++I)
+    for (size_t J = 0; J <= I; ++J) {
+      launch_ss_gram(stream_, t.chunks, (int)nchunk, workspace(I), groups[I].rb, workspace(J), groups[J].rb, part);
+      launch_ss_gram_reduce(stream_, part, (int)nchunk, groups[I].nv, groups[J].nv, I == J,
+                            dG + (size_t)groups[J].c0 * (size_t)k + groups[I].c0,
+                            dG + (size_t)groups[I].c0 * (size_t)k + groups[J].c0, (int64_t)k);
+      ss_info_[4] += nchunk ? 2 : 1;
+    }
+  HIPCHK(hipGetLastError(), "gram_sparse launch");
+  if ((rc = copy_vectors(false, dG, g_host, ldg, k, "G D2H", k))) return rc;
+  return sync_stream(stream_, "gram_sparse sync");
+}
+
+int Engine::release_solve_sparse() {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!d_sstab_ && !d_ssout_ && !d_ssgramW_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "solve_sparse release")) return rc;
+  for (void* p : {(void*)d_sstab_, (void*)d_ssout_, (void*)d_ssgramW_})
+    if (p) release_buffer(p);
+  d_sstab_ = nullptr; d_ssout_ = nullptr; d_ssgramW_ = nullptr;
+  ss_tab_cap_ = ss_out_cap_ = ss_gram_cap_ = 0;
   return 0;
 }
 

@@ -109,6 +109,21 @@ void launch_solve_many_pack(hipStream_t st, const double* x, int64_t ldx, const 
                             double* W);
 void launch_solve_many_unpack(hipStream_t st, double* x, int64_t ldx, const int* order, int n, int nv, int rb,
                               double* W);
+// ---- sparse right-hand sides and selected outputs (solve_sparse.hip), on the workspace W of solve_many ----
+constexpr int kSsChunkRows = 1024;   // most rows of one chunk of the touched-row list
+// chunks: (first pivot position, length <= kSsChunkRows) pairs on the device; the rows of every chunk <- 0
+void launch_ss_zero(hipStream_t st, const int* chunks, int nchunk, int rb, double* W);
+// W[pos[i]] = val[i], pos[i] = pivot position * rb + column of the group
+void launch_ss_scatter(hipStream_t st, const int64_t* pos, const double* val, int64_t count, double* W);
+// x[q * ldx + t] = W[pos[t] * rb + q] for t < nsel, q < nv (pos: pivot positions)
+void launch_ss_gather(hipStream_t st, double* x, int64_t ldx, const int* pos, int64_t nsel, int nv, int rb,
+                      const double* W);
+// part[c * 1024 + i * 32 + j] = sum over the rows p of chunk c of WI[p * rbI + i] WJ[p * rbJ + j] (fp64 MFMA)
+void launch_ss_gram(hipStream_t st, const int* chunks, int nchunk, const double* WI, int rbI, const double* WJ, int rbJ,
+                    double* part);
+// Gij[j * ldg + i] = Gji[i * ldg + j] = the blocks summed in ascending chunk order, i < nvI, j < nvJ (diag: I = J)
+void launch_ss_gram_reduce(hipStream_t st, const double* part, int nchunk, int nvI, int nvJ, bool diag, double* Gij,
+                           double* Gji, int64_t ldg);
 // selected inversion (selinv.hip): one launch of a SelinvProgram (SI_SYMM / SI_SCALE: tiles[first ..];
 // SI_DIAG: units[first ..]) on the Z arena; scratch: the program's scratch_size doubles
 void launch_selinv(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* units, const UpdTile* tiles,

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <iterator>
 #include <cstdio>
 
 namespace spx {
@@ -1715,6 +1716,87 @@ int build_updown_plan(const Symbolic& S, int k, const int* wptr, const int* wrow
   updown_paths(S, firsts.data(), k, bcols);
   if (first_pos) *first_pos = firsts;
   return 0;
+}
+
+// ---- sparse right-hand sides: the block columns and the rows a restricted solve touches -----------------
+int check_sparse_columns(const Symbolic& S, int k, const int* bptr, const int* brow, int nsel, const int* sel,
+                         std::string* why) {
+  auto bad = [&](const std::string& what) {
+    if (why) *why = what;
+    return -10;
+  };
+  if (k < 0) return bad("k < 0");
+  if (!bptr) return bad("the column pointer array is null");
+  if (bptr[0] < 1) return bad("bptr[0] < 1 (the arrays are 1-based)");
+  for (int v = 0; v < k; ++v)
+    if (bptr[v + 1] < bptr[v]) return bad("column " + std::to_string(v + 1) + ": the column pointers decrease");
+  if (k > 0 && bptr[k] > bptr[0] && !brow) return bad("the row index array is null");
+  for (int v = 0; v < k; ++v) {
+    const std::string col = "column " + std::to_string(v + 1);
+    for (int e = bptr[v] - 1; e < bptr[v + 1] - 1; ++e) {
+      const int r = brow[e];
+      if (r < 1 || r > S.n) return bad(col + ": row index " + std::to_string(r) + " is outside [1, n]");
+      if (e > bptr[v] - 1 && r <= brow[e - 1]) return bad(col + ": the row indices are not strictly increasing");
+    }
+  }
+  for (int t = 0; sel && t < nsel; ++t)
+    if (sel[t] < 1 || sel[t] > S.n)
+      return bad("sel[" + std::to_string(t) + "] = " + std::to_string(sel[t]) + " is outside [1, n]");
+  return 0;
+}
+
+void build_solve_sparse_plan(const Symbolic& S, int c0, int c1, const int* bptr, const int* brow, int nsel,
+                             const int* sel, int job, SolveSparsePlan& P) {
+  P.fwd.clear();
+  P.bwd.clear();
+  P.range.clear();
+  const bool all = sel == nullptr || nsel < 0;
+  std::vector<int> start, want;
+  if (job != 2 && c1 > c0) {
+    for (int e = bptr[c0] - 1; e < bptr[c1] - 1; ++e) start.push_back(S.order[(size_t)brow[e] - 1]);
+    updown_paths(S, start.data(), (int)start.size(), P.fwd);
+  }
+  if (!all)
+    for (int t = 0; t < nsel; ++t) want.push_back(S.order[(size_t)sel[t] - 1]);
+  if (job != 1) {
+    if (all) {
+      P.bwd.resize((size_t)S.nbcol());
+      for (int b = 0; b < S.nbcol(); ++b) P.bwd[(size_t)b] = b;
+    } else {
+      updown_paths(S, want.data(), (int)want.size(), P.bwd);
+    }
+  }
+  if (all) {
+    if (S.n > 0) P.range = {0, S.n};
+    return;
+  }
+  // the own columns of the union of the two sets (block columns ascend with their first pivot position), then the
+  // wanted positions that no block column of a set holds (job 1)
+  std::vector<std::pair<int, int>> rg;
+  std::vector<int> both;
+  std::set_union(P.fwd.begin(), P.fwd.end(), P.bwd.begin(), P.bwd.end(), std::back_inserter(both));
+  for (int b : both) {
+    const BlockCol& B = S.bcols[(size_t)b];
+    rg.push_back({S.sptr[B.node] + B.r0, B.width});
+  }
+  if (job == 1) {
+    const size_t nb0 = rg.size();
+    for (int p : want) rg.push_back({p, 1});
+    std::sort(rg.begin() + (long)nb0, rg.end());
+    std::inplace_merge(rg.begin(), rg.begin() + (long)nb0, rg.end());
+  }
+  for (const auto& r : rg) {
+    if (!P.range.empty()) {
+      int& f = P.range[P.range.size() - 2];
+      int& l = P.range[P.range.size() - 1];
+      if (r.first <= f + l) {
+        l = std::max(l, r.first + r.second - f);
+        continue;
+      }
+    }
+    P.range.push_back(r.first);
+    P.range.push_back(r.second);
+  }
 }
 
 }  // namespace spx

@@ -520,4 +520,27 @@ int build_updown_plan(const Symbolic& S, int k, const int* wptr, const int* wrow
 // the block columns on the paths from the pivot positions first[0 .. count) (-1: none) to the root, ascending
 void updown_paths(const Symbolic& S, const int* first, int count, std::vector<int>& bcols);
 
+// ---------------------------------------------------------------------------
+// Sparse right-hand sides and selected outputs (solve_sparse.hip): the block columns the
+// two sweeps have to visit.  B: sparse columns, CSC, 1-based, user variable order (as W above, any pattern);
+// sel: 1-based user variables whose entries of the solution are wanted (null: all n).
+//   fwd   : for every nonzero at pivot position p the block column that holds p, the later block columns of
+//           its node and every block column of every ancestor (empty under job 2)
+//   bwd   : the same closure of the wanted positions; every block column when all are wanted (empty under job 1)
+//   range : the touched rows as (first pivot position, length) pairs, ascending, disjoint, not adjacent: the
+//           own columns of the block columns of either set plus the wanted positions.  A sweep restricted to
+//           its set reads and writes touched rows only.
+// ---------------------------------------------------------------------------
+struct SolveSparsePlan {
+  std::vector<int> fwd, bwd;
+  std::vector<int> range;   // 2 per range
+};
+// 0, or -10 with *why: a null array, k < 0, bptr[0] < 1, a column pointer that decreases, a row index outside
+// [1, n], rows of a column not strictly increasing; a sel index outside [1, n]
+int check_sparse_columns(const Symbolic& S, int k, const int* bptr, const int* brow, int nsel, const int* sel,
+                         std::string* why);
+// the plan of columns [c0, c1) of a checked B taken as one group
+void build_solve_sparse_plan(const Symbolic& S, int c0, int c1, const int* bptr, const int* brow, int nsel,
+                             const int* sel, int job, SolveSparsePlan& P);
+
 }  // namespace spx
