@@ -587,6 +587,48 @@ int spllt_hip_release_solve_sparse(void *fkeep);   /* staged lists, gathered blo
 /* timings of the last factorization, milliseconds */
 int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, double *h2d_ms,
                            int *launches);
+/* ---- sampled outer product on the pattern, device-side readers (single GPU) -----------------
+ * What the adjoints of x = A^-1 b and of log det A with respect to the stored values need on the device
+ * (the torch front end is spllt_amd/torch_ops.py).  The k-th stored value val[k]
+ * stands for BOTH a_ij and a_ji (i >= j, the k-th entry of the analysed CSC-lower pattern in user
+ * variables), so
+ *
+ *     out[k] = alpha * sum_q ( u_q[i] v_q[j] + [i != j] u_q[j] v_q[i] ),   q = 0 .. nvec-1
+ *
+ * with u = the adjoint solution A^-1 xbar, v = x and alpha = -1 is d loss / d val[k].  Vector q is at
+ * u[q*ldu .. q*ldu + n) and v[q*ldv .. q*ldv + n) in the user's variable order (the layout of
+ * spllt_hip_solve_many_dev), ldu, ldv >= n; nothing outside those ranges is read and exactly nnz doubles
+ * are written.  One gather kernel (spllt_amd/csrc/pattern_outer.hip): no atomics; per entry the sum over
+ * q is ONE chain of fma in ascending q (first u_i v_j, then u_j v_i), alpha is applied once at the end, so
+ * the same input bits give the same output bits whatever the launch shape.  Needs the analysis only, no
+ * factor.  The (row, column) tables are built on first use from the analysed pattern, int32, 0-based user
+ * variables, exported as "pattern_row" / "pattern_col" by spllt_hip_program_get and released with the handle.
+ * nvec = 0 writes alpha * 0 to every entry.
+ *
+ * Errors, all decided on the host before the device is touched: a null pointer, nvec < 0, nbatch < 0,
+ * ldu < n, ldv < n, ldout < nnz -> SPLLT_ERROR_PARAMETER; a partitioned handle ->
+ * SPLLT_ERROR_UNIMPLEMENTED; no device -> SPLLT_ERROR_HIP.  Messages: spllt_hip_last_error.  All work is
+ * ordered on spllt_hip_engine_stream and finished when a call returns. */
+int spllt_hip_pattern_outer(void *fkeep, int nvec, const double *u_host, int64_t ldu, const double *v_host,
+                            int64_t ldv, double alpha, double *out_host);
+int spllt_hip_pattern_outer_dev(void *fkeep, int nvec, const double *u_dev, int64_t ldu, const double *v_dev,
+                                int64_t ldv, double alpha, double *out_dev);
+/* nbatch members in one launch: vector q of member b at u[(b*nvec + q)*ldu ..] (the layout of
+ * spllt_hip_solve_batch_dev), out[b*ldout + k], ldout >= nnz.  Member b's row equals the single call on
+ * its vectors bit for bit.  Needs no batch factor. */
+int spllt_hip_pattern_outer_batch_dev(void *fkeep, int nbatch, int nvec, const double *u_dev, int64_t ldu,
+                                      const double *v_dev, int64_t ldv, double alpha, double *out_dev,
+                                      int64_t ldout);
+/* spllt_hip_inverse_on_pattern / _batch with the output in device memory (nnz doubles / nbatch rows of
+ * ldout >= nnz doubles): the same gather launch, the same bits, no copy to the host.  The rows of a failed
+ * member are NaN. */
+int spllt_hip_inverse_on_pattern_dev(void *fkeep, double *out_dev);
+int spllt_hip_inverse_on_pattern_batch_dev(void *fkeep, double *out_dev, int64_t ldout);
+/* a counter that every successful change of the factor increments: which = 0 the single factor
+ * (spllt_factor, spllt_hip_factor_dev, spllt_hip_updown, the profiling entry points), which = 1 the batch
+ * (spllt_hip_factor_batch*).  0 on a fresh handle; needs no device.  A caller that saved state computed
+ * from a factor compares the counter to know whether that factor is still the current one. */
+int64_t spllt_hip_factor_serial(const void *fkeep, int which);
 /* program export for tests: "launches" (int64 x 12 per launch: kind, level,
  * first, count, tile, flops, stream, record, wait0..wait3), "chains" (ChainUnit bytes),
  * "potrf" (PotrfUnit bytes), "units" (UpdUnit bytes), "tiles" (UpdTile bytes),
@@ -606,7 +648,8 @@ int spllt_hip_factor_times(void *fkeep, double *submit_ms, double *device_ms, do
  * 64 columns, independent of the handle's panel width): "batch_selinv_units", "batch_selinv_tiles",
  * "batch_selinv_launches", "batch_selinv_rows", "batch_selinv_relpos", "batch_selinv_diag",
  * "batch_selinv_scratch", "batch_selinv_flops", the layouts of the "selinv_*" names; the operator of the
- * refined solves: "matvec_rowptr" (int64), "matvec_col", "matvec_src" (int32); "solve_sparse_host_us" (int64):
+ * refined solves: "matvec_rowptr" (int64), "matvec_col", "matvec_src" (int32); the index stream of the sampled
+ * outer product: "pattern_row", "pattern_col" (int32, one per entry of val); "solve_sparse_host_us" (int64):
  * the host microseconds the last spllt_hip_solve_sparse* / spllt_hip_gram_sparse on THIS handle spent, before its
  * first device call, on the plans of its groups, the filtered launches and the arrays to upload (not the upload).
  * Struct layouts: spllt_amd/csrc/schedule.hpp, mirrored as numpy dtypes in

@@ -74,6 +74,8 @@ HIP_SYMBOLS = [
     "spllt_hip_release_solve_repro",
     "spllt_hip_solve_sparse", "spllt_hip_solve_sparse_dev", "spllt_hip_gram_sparse", "spllt_hip_solve_sparse_plan",
     "spllt_hip_solve_sparse_info", "spllt_hip_release_solve_sparse",
+    "spllt_hip_pattern_outer", "spllt_hip_pattern_outer_dev", "spllt_hip_pattern_outer_batch_dev",
+    "spllt_hip_inverse_on_pattern_dev", "spllt_hip_inverse_on_pattern_batch_dev", "spllt_hip_factor_serial",
 ]
 
 _lib = None
@@ -289,5 +291,18 @@ def load():
         fn.restype = C.c_int
     lib.spllt_hip_inverse_on_pattern.argtypes = [vp, dp]
     lib.spllt_hip_inverse_on_pattern.restype = C.c_int
+    lib.spllt_hip_pattern_outer.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_double, dp]
+    lib.spllt_hip_pattern_outer.restype = C.c_int
+    lib.spllt_hip_pattern_outer_dev.argtypes = [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, C.c_double, vp]
+    lib.spllt_hip_pattern_outer_dev.restype = C.c_int
+    lib.spllt_hip_pattern_outer_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, C.c_double, vp,
+                                                      C.c_int64]
+    lib.spllt_hip_pattern_outer_batch_dev.restype = C.c_int
+    lib.spllt_hip_inverse_on_pattern_dev.argtypes = [vp, vp]
+    lib.spllt_hip_inverse_on_pattern_dev.restype = C.c_int
+    lib.spllt_hip_inverse_on_pattern_batch_dev.argtypes = [vp, vp, C.c_int64]
+    lib.spllt_hip_inverse_on_pattern_batch_dev.restype = C.c_int
+    lib.spllt_hip_factor_serial.argtypes = [vp, C.c_int]
+    lib.spllt_hip_factor_serial.restype = C.c_int64
     _lib = lib
     return lib

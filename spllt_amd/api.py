@@ -328,6 +328,60 @@ class Factorization:
             raise SplltError("spllt_hip_inverse_on_pattern", rc, self.last_error())
         return out[:self.nnz]
 
+    def inverse_on_pattern_dev(self, out_dev_ptr):
+        """spllt_hip_inverse_on_pattern_dev: the same nnz values into device memory (integer device pointer)"""
+        rc = self.lib.spllt_hip_inverse_on_pattern_dev(self.fkeep, C.c_void_p(out_dev_ptr))
+        if rc < 0:
+            raise SplltError("spllt_hip_inverse_on_pattern_dev", rc, self.last_error())
+        return self
+
+    def factor_serial(self, which=0):
+        """spllt_hip_factor_serial: how often the single factor (which=0) or the batch (which=1) has been
+        changed successfully on this handle; needs no device"""
+        return int(self.lib.spllt_hip_factor_serial(self.fkeep, int(which)))
+
+    # ---- sampled outer product on the pattern ---------------------------------
+    def pattern_tables(self):
+        """(row, col) int32 per entry of val, 0-based user variables ("pattern_row" / "pattern_col" of
+        spllt_hip_program_get); needs no device"""
+        return self.program("pattern_row").view(np.int32), self.program("pattern_col").view(np.int32)
+
+    def pattern_outer(self, u, v, alpha=1.0):
+        """spllt_hip_pattern_outer on host arrays u, v of shape (n,) or (n, nvec): out[k] = alpha sum_q
+        (u_q[i] v_q[j] + [i != j] u_q[j] v_q[i]) at the k-th entry (i, j) of the analysed pattern"""
+        u = np.asfortranarray(np.asarray(u, dtype=np.float64).reshape(self.n, -1))
+        v = np.asfortranarray(np.asarray(v, dtype=np.float64).reshape(self.n, -1))
+        if u.shape != v.shape:
+            raise ValueError("pattern_outer: u and v must have the same shape")
+        out = np.zeros(max(self.nnz, 1), dtype=np.float64)
+        rc = self.lib.spllt_hip_pattern_outer(self.fkeep, u.shape[1], _dp(u), max(self.n, 1), _dp(v), max(self.n, 1),
+                                              float(alpha), _dp(out))
+        if rc < 0:
+            raise SplltError("spllt_hip_pattern_outer", rc, self.last_error())
+        return out[:self.nnz]
+
+    def pattern_outer_dev(self, u_dev_ptr, v_dev_ptr, nvec, out_dev_ptr, ldu=None, ldv=None, alpha=1.0):
+        """spllt_hip_pattern_outer_dev: device vectors (vector q at u[q*ldu .. + n), ld defaults to n), nnz
+        doubles written at out_dev_ptr"""
+        rc = self.lib.spllt_hip_pattern_outer_dev(self.fkeep, int(nvec), C.c_void_p(u_dev_ptr),
+                                                  int(self.n if ldu is None else ldu), C.c_void_p(v_dev_ptr),
+                                                  int(self.n if ldv is None else ldv), float(alpha),
+                                                  C.c_void_p(out_dev_ptr))
+        if rc < 0:
+            raise SplltError("spllt_hip_pattern_outer_dev", rc, self.last_error())
+        return self
+
+    def pattern_outer_batch_dev(self, u_dev_ptr, v_dev_ptr, nbatch, nvec, out_dev_ptr, ldu=None, ldv=None, ldout=None,
+                                alpha=1.0):
+        """spllt_hip_pattern_outer_batch_dev: vector q of member b at u[(b*nvec + q)*ldu ..], out[b*ldout + k]"""
+        rc = self.lib.spllt_hip_pattern_outer_batch_dev(self.fkeep, int(nbatch), int(nvec), C.c_void_p(u_dev_ptr),
+                                                        int(self.n if ldu is None else ldu), C.c_void_p(v_dev_ptr),
+                                                        int(self.n if ldv is None else ldv), float(alpha),
+                                                        C.c_void_p(out_dev_ptr), int(self.nnz if ldout is None else ldout))
+        if rc < 0:
+            raise SplltError("spllt_hip_pattern_outer_batch_dev", rc, self.last_error())
+        return self
+
     def release_inverse(self):
         rc = self.lib.spllt_hip_release_inverse(self.fkeep)
         if rc < 0:
@@ -849,6 +903,14 @@ class Factorization:
         rows for failed members"""
         return self._batch_rows(self.lib.spllt_hip_inverse_on_pattern_batch, "spllt_hip_inverse_on_pattern_batch",
                                 self.nnz)
+
+    def inverse_on_pattern_batch_dev(self, out_dev_ptr, ldout=None):
+        """spllt_hip_inverse_on_pattern_batch_dev: the same rows into device memory, out[b*ldout + k]"""
+        rc = self.lib.spllt_hip_inverse_on_pattern_batch_dev(self.fkeep, C.c_void_p(out_dev_ptr),
+                                                             int(self.nnz if ldout is None else ldout))
+        if rc < 0:
+            raise SplltError("spllt_hip_inverse_on_pattern_batch_dev", rc, self.last_error())
+        return self
 
     def batch_selinv_launches(self):
         """kernel launches of the last batched inversion"""

@@ -58,6 +58,11 @@ struct Fkeep {
   std::shared_ptr<const Symbolic> mv_S;
   std::vector<int64_t> mv_rowptr;
   std::vector<int> mv_col, mv_src;
+  // the (row, column) tables of spllt_hip_program_get ("pattern_row" / "pattern_col", built once per pattern)
+  std::shared_ptr<const Symbolic> po_S;
+  std::vector<int> po_row, po_col;
+  // spllt_hip_factor_serial: successful changes of the single factor [0] and of the batch [1]
+  int64_t serial[2] = {0, 0};
 };
 
 std::mutex g_mu;
@@ -270,6 +275,7 @@ void factor_impl(void* akeep, void* fkeep, int nnz, const double* val, bool dev,
   f->last_flag = rc;
   f->hostL_valid = false;
   if (rc == 0) {
+    ++f->serial[0];
     std::lock_guard<std::mutex> lk(g_mu);
     if (std::find(g_pending.begin(), g_pending.end(), f) == g_pending.end()) g_pending.push_back(f);
   } else {
@@ -936,6 +942,7 @@ static int factor_batch_impl(void* akeep, void* fkeep, int nbatch, int nnz, cons
   }
   if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
   int rc = f->eng->factor_batch(val, dev, nbatch, ldval);
+  if (rc == 0 || rc == SPLLT_ERROR_NOT_POSDEF) ++f->serial[1];   // (the members that are positive definite were factorized)
   if (rc == SPLLT_ERROR_NOT_POSDEF) {
     const std::vector<int>& fl = f->eng->batch_flags();
     int nbad = 0, first = -1;
@@ -1126,6 +1133,7 @@ int spllt_hip_updown(void* fkeep, int k, const int* wptr, const int* wrow, const
   if (no_factor(f) || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
   const int rc = f->eng->updown(k, wptr, wrow, wval, sign, plan, first);
   f->hostL_valid = false;
+  ++f->serial[0];   // (a failed downdate has changed the factor as well: it is invalid now)
   if (rc) {
     feature_fail(f, rc);
     if (rc == SPLLT_ERROR_NOT_POSDEF) std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
@@ -1367,6 +1375,18 @@ int spllt_hip_inverse_on_pattern_batch(void* fkeep, double* out, int64_t ldout) 
   return rc ? feature_fail(f, rc) : 0;
 }
 
+int spllt_hip_inverse_on_pattern_batch_dev(void* fkeep, double* out_dev, int64_t ldout) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_inverse_on_pattern_batch_dev";
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!out_dev) return batch_param_error(f, what, "the output array is null");
+  if (ldout < f->S->nnzA) return batch_param_error(f, what, "ldout < nnz");
+  int rc = batch_inverse_reader(f, what);
+  if (rc) return rc;
+  rc = f->eng->inverse_on_pattern_batch_dev(out_dev, ldout);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
 int spllt_hip_batch_selinv_launches(void* fkeep) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f) return SPLLT_ERROR_PARAMETER;
@@ -1439,6 +1459,69 @@ int spllt_hip_inverse_on_pattern(void* fkeep, double* out) {
   return rc ? feature_fail(f, rc) : 0;
 }
 
+int spllt_hip_inverse_on_pattern_dev(void* fkeep, double* out_dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!out_dev) return SPLLT_ERROR_PARAMETER;
+  int rc = selinv_need_z(f, "spllt_hip_inverse_on_pattern_dev");
+  if (rc) return rc;
+  rc = f->eng->inverse_on_pattern_dev(out_dev);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int64_t spllt_hip_factor_serial(const void* fkeep, int which) {
+  const Fkeep* f = static_cast<const Fkeep*>(fkeep);
+  if (!f || which < 0 || which > 1) return SPLLT_ERROR_PARAMETER;
+  return f->serial[which];
+}
+
+// ---- sampled outer product on the analysed pattern ---------------------------------------------------
+// every check that needs no device (a rejected call touches nothing), then the handle's engine: the operation
+// needs the analysis only, so an engine is created when the handle has none yet
+static int pattern_outer_impl(const char* what, void* fkeep, int nbatch, int nvec, const double* u, int64_t ldu,
+                              const double* v, int64_t ldv, double alpha, double* out, int64_t ldout, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!u || !v) return batch_param_error(f, what, "a vector array is null");
+  if (!out) return batch_param_error(f, what, "the output array is null");
+  if (nbatch < 0) return batch_param_error(f, what, "nbatch < 0");
+  if (nvec < 0) return batch_param_error(f, what, "nvec < 0");
+  if (ldu < f->S->n) return batch_param_error(f, what, "ldu < n");
+  if (ldv < f->S->n) return batch_param_error(f, what, "ldv < n");
+  if (ldout < f->S->nnzA) return batch_param_error(f, what, "ldout < nnz");
+  if (int rc = batch_partitioned(f, what)) return rc;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (nbatch == 0) return 0;
+  if (f->eng && f->eng->pending()) (void)do_wait(f);
+  if (!f->eng) {
+    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
+    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
+    f->eng->set_exchange_buffer(f->xbuf);
+  }
+  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
+  int rc = f->eng->pattern_outer(nbatch, nvec, u, ldu, v, ldv, alpha, out, ldout, dev);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_pattern_outer(void* fkeep, int nvec, const double* u_host, int64_t ldu, const double* v_host, int64_t ldv,
+                            double alpha, double* out_host) {
+  const Fkeep* f = static_cast<const Fkeep*>(fkeep);
+  return pattern_outer_impl("spllt_hip_pattern_outer", fkeep, 1, nvec, u_host, ldu, v_host, ldv, alpha, out_host,
+                            f && f->S ? f->S->nnzA : 0, false);
+}
+
+int spllt_hip_pattern_outer_dev(void* fkeep, int nvec, const double* u_dev, int64_t ldu, const double* v_dev, int64_t ldv,
+                                double alpha, double* out_dev) {
+  const Fkeep* f = static_cast<const Fkeep*>(fkeep);
+  return pattern_outer_impl("spllt_hip_pattern_outer_dev", fkeep, 1, nvec, u_dev, ldu, v_dev, ldv, alpha, out_dev,
+                            f && f->S ? f->S->nnzA : 0, true);
+}
+
+int spllt_hip_pattern_outer_batch_dev(void* fkeep, int nbatch, int nvec, const double* u_dev, int64_t ldu,
+                                      const double* v_dev, int64_t ldv, double alpha, double* out_dev, int64_t ldout) {
+  return pattern_outer_impl("spllt_hip_pattern_outer_batch_dev", fkeep, nbatch, nvec, u_dev, ldu, v_dev, ldv, alpha,
+                            out_dev, ldout, true);
+}
+
 int spllt_hip_log_det(void* fkeep, double* out) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!out) return SPLLT_ERROR_PARAMETER;
@@ -1477,6 +1560,19 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
     const int64_t v = f->eng ? f->eng->solve_sparse_host_us() : 0;
     if (buf && cap >= (int64_t)sizeof v) std::memcpy(buf, &v, sizeof v);
     return (int64_t)sizeof v;
+  }
+  if (std::string(name).rfind("pattern_", 0) == 0) {
+    // the index stream of the sampled outer product: from the analysed pattern alone (no program needed)
+    if (f->po_S != f->S) {
+      build_pattern_tables(*f->S, f->po_row, f->po_col);
+      f->po_S = f->S;
+    }
+    const std::string q(name);
+    const std::vector<int>* t = q == "pattern_row" ? &f->po_row : (q == "pattern_col" ? &f->po_col : nullptr);
+    if (!t) return -1;
+    const size_t bytes = t->size() * sizeof(int);
+    if (buf && bytes) std::memcpy(buf, t->data(), std::min<size_t>(bytes, (size_t)std::max<int64_t>(cap, 0)));
+    return (int64_t)bytes;
   }
   const Program* P;
   if (f->eng && !f->eng->status()) {
@@ -1656,6 +1752,7 @@ static int profile_impl(void* fkeep, const double* val, int nnz, float* ms, int 
   if (rc) return rc;
   for (int i = 0; i < (int)v.size() && i < capacity; ++i) ms[i] = v[i];
   f->hostL_valid = false;
+  ++f->serial[0];
   return (int)v.size();
 }
 
@@ -1671,6 +1768,7 @@ int spllt_hip_timeline(void* fkeep, const double* val, int nnz, float* t_ms, int
   if (rc) return rc;
   for (int i = 0; i < (int)v.size() && i < capacity; ++i) t_ms[i] = v[i];
   f->hostL_valid = false;
+  ++f->serial[0];
   return (int)v.size();
 }
 

@@ -1500,6 +1500,20 @@ int Engine::release_inverse() {
   return 0;
 }
 
+// A^-1 at the entries of the analysed pattern into nnz doubles of device memory: the gather kernel of the
+// batched inversion with one member, enqueued on stream_ (what both readers below share)
+int Engine::gather_inverse_on_pattern(double* out_dev) {
+  BatchSelinvView v{};   // one member, known to be valid: no flag
+  v.v.nbatch = 1;
+  v.Z = d_Z_;
+  if (launch_batch_selinv_pattern(stream_, v, d_map_dst_, d_map_src_, nmap_, out_dev, S_->nnzA) < 0) {
+    feature_err_ = "inverse on pattern: the pattern has more entries than a grid holds work items";
+    return -99;
+  }
+  HIPCHK(hipGetLastError(), "inverse on pattern launch");
+  return sync_stream(stream_, "inverse on pattern sync");
+}
+
 int Engine::inverse_on_pattern(double* out) {
   feature_err_.clear();
   if (status_) return status_;
@@ -1516,16 +1530,90 @@ int Engine::inverse_on_pattern(double* out) {
       return -1;
     }
   }
-  BatchSelinvView v{};   // one member, known to be valid: no flag
-  v.v.nbatch = 1;
-  v.Z = d_Z_;
-  if (launch_batch_selinv_pattern(stream_, v, d_map_dst_, d_map_src_, nmap_, d_sipat_, nnz) < 0) {
-    feature_err_ = "inverse on pattern: the pattern has more entries than a grid holds work items";
+  if (int rc = gather_inverse_on_pattern(d_sipat_)) return rc;
+  return staged_d2h(out, d_sipat_, sizeof(double) * (size_t)nnz);
+}
+
+int Engine::inverse_on_pattern_dev(double* out_dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!z_valid_ || !out_dev || opt_.nranks > 1) return -10;
+  if (S_->nnzA == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  return gather_inverse_on_pattern(out_dev);
+}
+
+// ---- sampled outer product on the analysed pattern ---------------------------------------------------
+int Engine::pattern_outer(int nbatch, int nvec, const double* u, int64_t ldu, const double* v, int64_t ldv,
+                          double alpha, double* out, int64_t ldout, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n;
+  const int64_t nnz = S_->nnzA;
+  if (!u || !v || !out || nbatch < 0 || nvec < 0 || ldu < n || ldv < n || ldout < nnz) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;   // (the caller waits first)
+  if (nbatch == 0 || nnz == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (!d_potab_) {
+    std::vector<int> row, col;
+    build_pattern_tables(*S_, row, col);
+    TableStager tab;
+    tab.add(&d_porow_, row);
+    tab.add(&d_pocol_, col);
+    hipError_t e = tab.commit(&d_potab_, [this](void** q, size_t b) { return dalloc(q, b); });
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      if (d_potab_) release_buffer(d_potab_);
+      d_potab_ = nullptr;
+      feature_err_ = std::string("pattern outer product: not enough device memory for the tables of the pattern (") +
+                     hipGetErrorString(e) + ")";
+      return alloc_code(e);
+    }
+  }
+  const int64_t nv = (int64_t)nbatch * nvec;
+  const double *du = u, *dv = v;
+  double* dout = out;
+  int64_t dldu = ldu, dldv = ldv, dldout = ldout;
+  if (!dev) {
+    // the caller's arrays packed: 2 nv vectors of n doubles, then nbatch rows of nnz doubles
+    const size_t need = 2 * (size_t)nv * (size_t)n + (size_t)nbatch * (size_t)nnz;
+    if (need > po_stage_elems_ || !d_postage_) {
+      if (d_postage_) {
+        if (int rc = sync_stream(stream_, "pattern outer product staging")) return rc;
+        release_buffer(d_postage_);
+      }
+      d_postage_ = nullptr;
+      po_stage_elems_ = 0;
+      hipError_t e = dalloc((void**)&d_postage_, sizeof(double) * need);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        d_postage_ = nullptr;
+        feature_err_ = "pattern outer product: not enough device memory to stage the vectors (" +
+                       std::to_string((sizeof(double) * need) >> 20) + " MiB): " + hipGetErrorString(e);
+        return alloc_code(e);
+      }
+      po_stage_elems_ = need;
+    }
+    double* su = d_postage_;
+    double* sv = su + (size_t)nv * (size_t)n;
+    dout = sv + (size_t)nv * (size_t)n;
+    if (nv > 0) {
+      if (int rc = copy_vectors_to_device(su, u, ldu, nv, "u H2D")) return rc;
+      if (int rc = copy_vectors_to_device(sv, v, ldv, nv, "v H2D")) return rc;
+    }
+    du = su; dv = sv;
+    dldu = dldv = n;
+    dldout = nnz;
+  }
+  if (launch_pattern_outer(stream_, d_porow_, d_pocol_, nnz, nbatch, nvec, du, dldu, dv, dldv, alpha, dout, dldout) < 0) {
+    feature_err_ = "pattern outer product: the pattern has more entries than a grid holds work items";
     return -99;
   }
-  HIPCHK(hipGetLastError(), "inverse on pattern launch");
-  if (int rc = sync_stream(stream_, "inverse on pattern sync")) return rc;
-  return staged_d2h(out, d_sipat_, sizeof(double) * (size_t)nnz);
+  HIPCHK(hipGetLastError(), "pattern outer product launch");
+  if (!dev)
+    if (int rc = copy_vectors(false, dout, out, ldout, nbatch, "pattern outer product D2H", nnz)) return rc;
+  return sync_stream(stream_, "pattern outer product sync");
 }
 
 // ---- low-rank update / downdate ---------------------------------------------------------------------
@@ -2141,6 +2229,21 @@ int Engine::inverse_on_pattern_batch(double* out, int64_t ldout) {
   }
   HIPCHK(hipGetLastError(), "batch inverse on pattern launch");
   if ((rc = copy_vectors(false, bt_.stage, out, ldout, bt_.nbatch, "batch inverse on pattern D2H", nnz))) return rc;
+  return sync_stream(stream_, "batch inverse on pattern sync");
+}
+
+int Engine::inverse_on_pattern_batch_dev(double* out_dev, int64_t ldout) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int64_t nnz = S_->nnzA;
+  if (!bt_.z_valid || !out_dev || ldout < nnz || bt_.nbatch <= 0) return -10;
+  if (nnz == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (launch_batch_selinv_pattern(stream_, batch_selinv_view(), d_map_dst_, d_map_src_, nmap_, out_dev, ldout) < 0) {
+    feature_err_ = "batch inverse on pattern: one member's entries are more work items than a grid holds";
+    return -99;
+  }
+  HIPCHK(hipGetLastError(), "batch inverse on pattern launch");
   return sync_stream(stream_, "batch inverse on pattern sync");
 }
 

@@ -215,6 +215,14 @@ class Engine {
   // out[k] = (A^-1) at the k-th entry of the analysed CSC-lower pattern (nnz doubles, host): the gather
   // kernel of the batched inversion with one member
   int inverse_on_pattern(double* out);
+  int inverse_on_pattern_dev(double* out_dev);        // the same launch, nnz doubles of device memory
+  // ---- sampled outer product on the analysed pattern (pattern_outer.hip, single GPU): needs the analysis
+  // only, no factor.  out[b * ldout + k] = alpha sum_q (u_q[i] v_q[j] + [i != j] u_q[j] v_q[i]) for entry k =
+  // (i, j) of the pattern and member b, vector q of member b at u[(b * nvec + q) * ldu ..], user order.  The
+  // (row, column) tables go to the device on first use and stay with the engine.  dev: device pointers, read
+  // and written in place; else the three arrays are staged through a buffer that grows with the call.
+  int pattern_outer(int nbatch, int nvec, const double* u, int64_t ldu, const double* v, int64_t ldv, double alpha,
+                    double* out, int64_t ldout, bool dev);
   double* device_Z() { return z_valid_ ? d_Z_ : nullptr; }
   const SelinvProgram& selinv_program() const { return siprog_; }
   // ---- batched factorization (batch.hip, single GPU): nbatch value sets on this pattern, factorized and
@@ -241,6 +249,7 @@ class Engine {
   double* device_inverse_batch(int64_t* member_stride);
   int inverse_diag_batch(double* out, int64_t ldout);        // host, out[b * ldout + i], user order
   int inverse_on_pattern_batch(double* out, int64_t ldout);  // host, out[b * ldout + k], the order of val
+  int inverse_on_pattern_batch_dev(double* out_dev, int64_t ldout);   // the same launch, device output
   int batch_selinv_launches() const { return bt_.si_launches; }
   int release_inverse_batch();
   const SelinvProgram& batch_selinv_program() const { return bt_.siprog; }
@@ -489,6 +498,14 @@ class Engine {
   double* d_siscratch_ = nullptr;
   double* d_siout_ = nullptr;      // n + 1 doubles: diag(A^-1), log det
   double* d_sipat_ = nullptr;      // nnz doubles: A^-1 on the analysed pattern (inverse_on_pattern)
+  int gather_inverse_on_pattern(double* out_dev);
+  // sampled outer product: the (row, column) tables of the pattern (one allocation, on first use) and the
+  // staging block of the host entry point
+  char* d_potab_ = nullptr;
+  int* d_porow_ = nullptr;
+  int* d_pocol_ = nullptr;
+  double* d_postage_ = nullptr;
+  size_t po_stage_elems_ = 0;
   // batched factorization: tables (uploaded once, on the first batch call) and per-batch storage (grows
   // with nbatch, stays with the engine until release_batch)
   struct BatchState {

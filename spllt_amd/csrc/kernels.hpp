@@ -195,6 +195,14 @@ int launch_batch_selinv_diag_gather(hipStream_t st, const BatchSelinvView& s, co
 // out[b * ldout + map_src[e]] = Z_b[map_dst[e]]  (A_b^-1 at the entries of the analysed pattern, in the order of val)
 int launch_batch_selinv_pattern(hipStream_t st, const BatchSelinvView& s, const int64_t* map_dst, const int64_t* map_src,
                                 int64_t nmap, double* out, int64_t ldout);
+// ---- sampled outer product on the analysed pattern (pattern_outer.hip) ---------------------------------
+// out[b * ldout + k] = alpha * sum_q ( u_q[i] v_q[j] + [i != j] u_q[j] v_q[i] ) for entry k = (prow[k], pcol[k]) =
+// (i, j) of the pattern (0-based user variables) and member b, whose vector q is at u + (b * nvec + q) * ldu;
+// one fma chain per entry in ascending q, gather only.  Returns the number of kernel launches as the batched
+// wrappers above (the members are split into ranges past the grid limit; -1: one member overflows a grid).
+int launch_pattern_outer(hipStream_t st, const int* prow, const int* pcol, int64_t nnz, int nbatch, int nvec,
+                         const double* u, int64_t ldu, const double* v, int64_t ldv, double alpha, double* out,
+                         int64_t ldout);
 // ---- low-rank update / downdate of the factor (updown.hip) ------------------------------------------
 // Wd: the work array, n x kUpdownVec doubles, Wd[p * kUpdownVec + q] for pivot position p and vector q of the
 // pass, zero between calls.  coef: (widest block column) x kUpdownVec x 3 doubles, the (c, t, 1 / c) of the

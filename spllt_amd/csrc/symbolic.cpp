@@ -671,6 +671,14 @@ void build_matvec_tables(const Symbolic& S, std::vector<int64_t>& rowptr, std::v
   }
 }
 
+void build_pattern_tables(const Symbolic& S, std::vector<int>& row, std::vector<int>& col) {
+  row.assign(S.a_row.begin(), S.a_row.end());
+  col.assign(S.a_row.size(), 0);
+  if (S.a_ptr.empty()) return;
+  for (int j = 0; j < S.n; ++j)
+    for (int64_t e = S.a_ptr[j]; e < S.a_ptr[j + 1]; ++e) col[(size_t)e] = j;
+}
+
 int analyse_symbolic(int n, const int64_t* ptr, const int* row, int nnodes, const int* sptr,
                      const int* sparent, const int64_t* rptr, const int* rlist, const int* order,
                      const SymOptions& opt, Symbolic& S) {

@@ -116,6 +116,10 @@ int finish_symbolic(int n, const int64_t* ptr, const int* row, const std::vector
 void build_matvec_tables(const Symbolic& S, std::vector<int64_t>& rowptr, std::vector<int>& col,
                          std::vector<int>& src);
 
+// The analysed pattern as one (row, column) pair per entry, 0-based user variables, in the order of val
+// (row >= column): the index stream of the sampled outer product (pattern_outer.hip).
+void build_pattern_tables(const Symbolic& S, std::vector<int>& row, std::vector<int>& col);
+
 // Exposed for tests.
 void nested_dissection(int n, const std::vector<int64_t>& xadj,
                        const std::vector<int>& adj, int leaf, std::vector<int>& order);

@@ -1,0 +1,338 @@
+"""PyTorch front end: differentiable sparse SPD solve and log-determinant on the GPU.
+
+``SparseCholesky`` owns one analysed pattern (an ``api.Factorization``) and offers ``solve``, ``logdet`` and their
+batched twins as ``torch.autograd.Function``s over device tensors.  Nothing is computed here: the factorization,
+the solves, the selected inverse and the sampled outer product of the backward pass are the library's HIP kernels,
+called on the tensors' own memory.
+
+Convention: ``val[k]`` is the k-th stored value of the CSC lower triangle and stands for BOTH a_ij and a_ji, so
+
+    d loss / d val[k] = -(lam_i x_j + [i != j] lam_j x_i)      for x = A^-1 b,  lam = A^-1 xbar
+    d logdet / d val[k] = (2 - delta_ij) (A^-1)_ij
+
+Out of scope: CPU tensors, float32, partitioned handles, sparse right-hand sides, second derivatives.
+"""
+import weakref
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from .api import Factorization, SplltError, csc_lower_1based
+
+__all__ = ["SparseCholesky"]
+
+_NOT_POSDEF = -20
+
+
+class SparseCholesky:
+    """A sparse SPD matrix pattern with differentiable operations on its values.
+
+    A_or_pattern: a scipy sparse symmetric matrix (its lower triangle gives the pattern and the order of ``val``) or
+    the triple (n, ptr, row) of a 1-based CSC lower triangle.  reproducible=True: the deterministic engine (flag
+    4096) and the reproducible solve -- forward and backward of ``solve`` and ``logdet`` are then bit-reproducible
+    across calls; the batch has no deterministic form and raises NotImplementedError.
+
+    One factorization serves every operation on the same values: the object remembers the tensor it factorized last
+    (a weak reference and its ``_version``) and the library's factor serial, and factorizes again only when one of
+    them differs.  A write that bypasses the version counter (``val.data``, a raw pointer) is not seen, exactly as
+    autograd's own check of saved tensors does not see it: pass a fresh tensor or call ``invalidate()`` then.
+    """
+
+    def __init__(self, A_or_pattern, nb=256, reproducible=False, **analyse_kw):
+        if isinstance(A_or_pattern, (tuple, list)):
+            n, ptr, row = A_or_pattern
+        else:
+            n, ptr, row, _ = csc_lower_1based(A_or_pattern)
+        self.reproducible = bool(reproducible)
+        flags = int(analyse_kw.pop("engine_flags", 0)) | (4096 if self.reproducible else 0)
+        self.f = Factorization(n, ptr, row, nb=nb, engine_flags=flags, **analyse_kw)
+        self.n, self.nnz = self.f.n, self.f.nnz
+        self.device = None            # the device of the first tensor; the engine is created there
+        self._stream = None
+        self._weight = None           # 2 - delta_ij per entry of val
+        self.invalidate()
+
+    # ---- checks: before any library call ----------------------------------------------------------
+    def _tensor(self, t, name, shape, device=None):
+        """device: where the tensor has to be when the handle has no device yet (that of the call's first tensor)"""
+        device = self.device if self.device is not None else device
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float64:
+            raise TypeError(f"{name}: expected float64, got {t.dtype}")
+        if t.device.type != "cuda":
+            raise ValueError(f"{name}: expected a tensor on the GPU, got one on {t.device}")
+        if device is not None and t.device != device:
+            raise ValueError(f"{name}: expected a tensor on {device} like the handle's other tensors, got one on {t.device}")
+        if len(shape) != t.dim() or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+            want = "(" + ", ".join("*" if s is None else str(s) for s in shape) + ")"
+            raise ValueError(f"{name}: expected shape {want}, got {tuple(t.shape)}")
+        return t
+
+    def _values(self, t, name, shape):
+        """the values are read in place by the factorization: they have to be contiguous"""
+        self._tensor(t, name, shape)
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous tensor (the factorization reads it in place)")
+        return t
+
+    def _rhs(self, B, name, device=None):
+        if isinstance(B, torch.Tensor) and B.dim() == 1:
+            return self._tensor(B, name, (self.n,), device)
+        return self._tensor(B, name, (self.n, None), device)
+
+    def _enter(self, t):
+        """the handle's device fixed by the first tensor; no library call under stream capture"""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("SparseCholesky: the library synchronizes with the host, it cannot run under stream capture")
+        if self.device is None:
+            self.device = t.device
+
+    def _sync(self):
+        """the engine stream waits for the work torch has enqueued on its current stream"""
+        with torch.cuda.device(self.device):
+            if self._stream is None:
+                self._stream = torch.cuda.ExternalStream(self.f.engine_stream(), device=self.device)
+            self._stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    # ---- the factor cache ---------------------------------------------------------------------------
+    def invalidate(self):
+        """forget which tensors the current factors came from: the next operation factorizes again"""
+        self._fac = (None, -1, -1)    # (weak reference, _version, factor serial) of the single factor
+        self._bat = (None, -1, -1)    # ... of the batch
+        self._z_serial = (-1, -1)     # factor serials whose selected inverse is on the device
+
+    @staticmethod
+    def _current(slot, t, serial):
+        ref, version, ser = slot
+        return ref is not None and ref() is t and version == t._version and ser == serial
+
+    def _ensure_factor(self, val):
+        """the factor of val on the device; returns its serial"""
+        serial = self.f.factor_serial(0)
+        if self._current(self._fac, val, serial):
+            return serial
+        self._fac = (None, -1, -1)
+        self._sync()
+        with torch.cuda.device(self.device):
+            self.f.factor_dev(val.data_ptr())
+            self.f.wait()             # raises SplltError on a matrix that is not positive definite
+        serial = self.f.factor_serial(0)
+        self._fac = (weakref.ref(val), val._version, serial)
+        return serial
+
+    def _ensure_batch(self, vals):
+        serial = self.f.factor_serial(1)
+        if self._current(self._bat, vals, serial):
+            return serial
+        self._bat = (None, -1, -1)
+        self._sync()
+        with torch.cuda.device(self.device):
+            rc = self.f.factor_batch_dev(vals.data_ptr(), vals.shape[0], ldval=self.nnz)
+        if rc == _NOT_POSDEF:
+            flags, cols = self.f.batch_status()
+            bad = [int(b) for b in np.nonzero(flags)[0]]
+            raise SplltError("spllt_hip_factor_batch_dev", rc,
+                             f"members {bad} are not positive definite (pivot columns {[int(cols[b]) for b in bad]})")
+        serial = self.f.factor_serial(1)
+        self._bat = (weakref.ref(vals), vals._version, serial)
+        return serial
+
+    def _weights(self):
+        if self._weight is None:
+            row, col = self.f.pattern_tables()
+            self._weight = torch.as_tensor(np.where(row == col, 1.0, 2.0), dtype=torch.float64, device=self.device)
+        return self._weight
+
+    # ---- library calls on tensors ---------------------------------------------------------------------
+    def _solve_inplace(self, work):
+        """work: (nrhs, n) contiguous, overwritten with the solutions"""
+        self._sync()
+        with torch.cuda.device(self.device):
+            if self.reproducible:
+                self.f.solve_reproducible_dev(work.data_ptr(), work.shape[0], ldx=self.n)
+            else:
+                self.f.solve_many_dev(work.data_ptr(), work.shape[0], ldx=self.n)
+        return work
+
+    def _solve_batch_inplace(self, work):
+        """work: (nbatch, nrhs, n) contiguous, overwritten"""
+        self._sync()
+        with torch.cuda.device(self.device):
+            self.f.solve_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n)
+        return work
+
+    def _outer(self, ut, vt, alpha):
+        """ut, vt: (nvec, n) contiguous -> (nnz,)"""
+        out = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
+        self._sync()
+        with torch.cuda.device(self.device):
+            self.f.pattern_outer_dev(ut.data_ptr(), vt.data_ptr(), ut.shape[0], out.data_ptr(), alpha=alpha)
+        return out
+
+    def _outer_batch(self, ut, vt, alpha):
+        """ut, vt: (nbatch, nvec, n) contiguous -> (nbatch, nnz)"""
+        out = torch.empty((ut.shape[0], self.nnz), dtype=torch.float64, device=self.device)
+        self._sync()
+        with torch.cuda.device(self.device):
+            self.f.pattern_outer_batch_dev(ut.data_ptr(), vt.data_ptr(), ut.shape[0], ut.shape[1], out.data_ptr(),
+                                           alpha=alpha)
+        return out
+
+    def _inverse_on_pattern(self, serial):
+        out = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
+        self._sync()
+        with torch.cuda.device(self.device):
+            if self._z_serial[0] != serial:
+                self.f.selected_inverse()
+                self._z_serial = (serial, self._z_serial[1])
+            self.f.inverse_on_pattern_dev(out.data_ptr())
+        return out
+
+    def _inverse_on_pattern_batch(self, nbatch, serial):
+        out = torch.empty((nbatch, self.nnz), dtype=torch.float64, device=self.device)
+        self._sync()
+        with torch.cuda.device(self.device):
+            if self._z_serial[1] != serial:
+                self.f.selected_inverse_batch()
+                self._z_serial = (self._z_serial[0], serial)
+            self.f.inverse_on_pattern_batch_dev(out.data_ptr(), ldout=self.nnz)
+        return out
+
+    # ---- the public operations ----------------------------------------------------------------------
+    def solve(self, val, B):
+        """x = A(val)^-1 B.  val: (nnz,), B: (n,) or (n, nrhs); differentiable in both"""
+        self._values(val, "val", (self.nnz,))
+        self._rhs(B, "B", val.device)
+        self._enter(val)
+        return _Solve.apply(self, val, B)
+
+    def logdet(self, val):
+        """log det A(val), a 0-dim tensor; differentiable in val"""
+        self._values(val, "val", (self.nnz,))
+        self._enter(val)
+        return _LogDet.apply(self, val)
+
+    def solve_batch(self, vals, B):
+        """X_b = A(vals[b])^-1 B[b].  vals: (nbatch, nnz), B: (nbatch, n, nrhs); differentiable in both"""
+        if self.reproducible:
+            raise NotImplementedError("solve_batch: the batch has no deterministic form (reproducible=True)")
+        self._values(vals, "vals", (None, self.nnz))
+        self._tensor(B, "B", (vals.shape[0], self.n, None), vals.device)
+        self._enter(vals)
+        return _SolveBatch.apply(self, vals, B)
+
+    def logdet_batch(self, vals):
+        """log det A(vals[b]), shape (nbatch,); differentiable in vals"""
+        if self.reproducible:
+            raise NotImplementedError("logdet_batch: the batch has no deterministic form (reproducible=True)")
+        self._values(vals, "vals", (None, self.nnz))
+        self._enter(vals)
+        return _LogDetBatch.apply(self, vals)
+
+    def pattern_outer(self, U, V, alpha=1.0):
+        """out[k] = alpha sum_q (U[i, q] V[j, q] + [i != j] U[j, q] V[i, q]) at the k-th entry (i, j) of the pattern.
+        U, V: (n, nvec) or (n,); not differentiable"""
+        self._rhs(U, "U")
+        self._tensor(V, "V", tuple(U.shape), U.device)
+        self._enter(U)
+        with torch.no_grad():
+            ut = U.reshape(self.n, -1).t().contiguous()
+            vt = V.reshape(self.n, -1).t().contiguous()
+            return self._outer(ut, vt, float(alpha))
+
+    def close(self):
+        self.f.close()
+
+
+def _to_vectors(B):
+    """(n,) or (n, nrhs) -> a fresh contiguous (nrhs, n) work tensor: the library wants every vector contiguous"""
+    return B.detach().reshape(B.shape[0], -1).t().clone(memory_format=torch.contiguous_format)
+
+
+class _Solve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, chol, val, B):
+        ctx.chol = chol
+        ctx.serial = chol._ensure_factor(val)
+        work = chol._solve_inplace(_to_vectors(B))
+        ctx.vector = B.dim() == 1
+        ctx.save_for_backward(val, work)
+        return work.view(-1) if ctx.vector else work.t()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol = ctx.chol
+        val, xt = ctx.saved_tensors
+        if chol.f.factor_serial(0) != ctx.serial:       # another matrix was factorized in between
+            chol._ensure_factor(val)
+        lam = chol._solve_inplace(_to_vectors(grad))
+        gval = chol._outer(lam, xt, -1.0) if ctx.needs_input_grad[1] else None
+        return None, gval, (lam.view(-1) if ctx.vector else lam.t())
+
+
+class _LogDet(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, chol, val):
+        ctx.chol = chol
+        ctx.serial = chol._ensure_factor(val)
+        chol._sync()
+        with torch.cuda.device(chol.device):
+            ld = chol.f.log_det()
+        ctx.save_for_backward(val)
+        return torch.tensor(ld, dtype=torch.float64, device=chol.device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol = ctx.chol
+        (val,) = ctx.saved_tensors
+        serial = ctx.serial
+        if chol.f.factor_serial(0) != serial:
+            serial = chol._ensure_factor(val)
+        return None, chol._weights() * chol._inverse_on_pattern(serial) * grad
+
+
+class _SolveBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, chol, vals, B):
+        ctx.chol = chol
+        ctx.serial = chol._ensure_batch(vals)
+        work = chol._solve_batch_inplace(B.detach().transpose(1, 2).clone(memory_format=torch.contiguous_format))
+        ctx.save_for_backward(vals, work)
+        return work.transpose(1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol = ctx.chol
+        vals, xt = ctx.saved_tensors
+        if chol.f.factor_serial(1) != ctx.serial:
+            chol._ensure_batch(vals)
+        lam = chol._solve_batch_inplace(grad.transpose(1, 2).clone(memory_format=torch.contiguous_format))
+        gvals = chol._outer_batch(lam, xt, -1.0) if ctx.needs_input_grad[1] else None
+        return None, gvals, lam.transpose(1, 2)
+
+
+class _LogDetBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, chol, vals):
+        ctx.chol = chol
+        ctx.serial = chol._ensure_batch(vals)
+        chol._sync()
+        with torch.cuda.device(chol.device):
+            ld = chol.f.log_det_batch()
+        ctx.save_for_backward(vals)
+        return torch.as_tensor(ld, dtype=torch.float64, device=chol.device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol = ctx.chol
+        (vals,) = ctx.saved_tensors
+        serial = ctx.serial
+        if chol.f.factor_serial(1) != serial:
+            serial = chol._ensure_batch(vals)
+        return None, chol._weights() * chol._inverse_on_pattern_batch(vals.shape[0], serial) * grad[:, None]
