@@ -298,6 +298,63 @@ int spllt_hip_solve_repro_dev(void *fkeep, int nrhs, double *x_dev, int64_t ldx,
  * for a partitioned handle: SPLLT_ERROR_UNIMPLEMENTED).  Default 0.  Needs no device. */
 int spllt_hip_set_reproducible_solve(void *fkeep, int on);
 int spllt_hip_release_solve_repro(void *fkeep);   /* tables and scratch back to the pool */
+/* ---- products with the factor (single GPU) ----------------------------------------
+ * The calls that APPLY the factor in the arena, where the solves invert it.  X holds nvec vectors laid out as
+ * in spllt_hip_solve_many (vector q at x[q*ldx .. q*ldx + n), ldx >= n, overwritten in place, nothing outside
+ * those ranges read or written).  The job numbers mirror spllt_solve, so that factor_mult(job) undoes
+ * solve_many(job) and the other way round:
+ *   job 0   x <- P^T L L^T P x   the product with the matrix the factor stands for (after spllt_hip_updown:
+ *                                A +- W W^T, for which no value array exists)
+ *   job 1   x <- P^T L x         the input is a pivot-order vector laid out in user positions, exactly as
+ *                                solve_many(job = 1) leaves it
+ *   job 2   x <- L^T P x         the mirror: what solve_many(job = 2) takes
+ * pivot_order = 1 skips both permutations, as in spllt_hip_solve_many_dev.  nvec = 0 is a no-op.
+ * Blocks of 32 vectors (a tail of at most 16: one block of 16) in the workspace layout of solve_many; a
+ * product is out of place between that workspace and a second one and has no dependency chain: per direction
+ * one launch over all (block column, strip) tiles of "solve_tiles", which STORE their products at the slots
+ * of the "rsolve_*" tables above (a slot is one row of 16 or 32 doubles here), and one launch over the chunks
+ * of 64 pivot positions of every block column, which multiplies with the diagonal tile -- read from the
+ * arena and masked to its lower triangle, never from the inverted panels -- and adds the stored products:
+ * for L x those of "rsolve_gsrc"[gptr[p] .. gptr[p+1]) in that order, one after the other; for L^T x the
+ * strips of the block column in ascending order.  Two launches per direction, four for job 0, plus pack and
+ * unpack; every product on v_mfma_f64_16x16x4_f64.
+ * Reproducibility: no atomic add anywhere.  The same factor bits and vector bits give the same result bits
+ * across calls, group sizes, positions within a group, and the host / device / pivot-order entry points.
+ * Memory: on first use the tables (shared with the reproducible solve when they are resident), a second
+ * workspace of 32 n doubles and a scratch of 32 * max(rsolve_frows, rsolve_bsize) doubles are taken from the
+ * device pool and kept until spllt_hip_release_factor_mult or spllt_deallocate_fkeep.  When that does not
+ * fit, both are taken for 16 vectors and every block is a block of 16: per vector the bits are the same.
+ * The work is ordered on the engine's stream and has finished when the call returns; a later spllt_factor or
+ * spllt_hip_updown on the handle is picked up.
+ * Errors: null pointer, nvec < 0, ldx < n, bad job, nothing factorized yet -> SPLLT_ERROR_PARAMETER;
+ * partitioned handle -> SPLLT_ERROR_UNIMPLEMENTED; no device memory for blocks of 16 either ->
+ * SPLLT_ERROR_ALLOCATION (nothing is kept half-allocated, the factor and every solve stay usable).
+ * Debug: spllt_hip_debug("fmult_poison=1") fills the scratch with NaN before every direction ("=0": off);
+ * "fmult_alloc_fail=N" makes the next N allocations of the second workspace and the scratch fail. */
+int spllt_hip_factor_mult(void *fkeep, int nvec, double *x_host, int64_t ldx, int job);      /* host, user order */
+int spllt_hip_factor_mult_dev(void *fkeep, int nvec, double *x_dev, int64_t ldx, int job,
+                              int pivot_order);   /* device; 0 = user order, 1 = pivot order */
+int spllt_hip_release_factor_mult(void *fkeep);   /* workspace, scratch and tables back to the pool */
+/* ---- Gaussian sampling (single GPU) -----------------------------------------------
+ * Noise: entry (pivot position p, sample s) is ONE Philox4x32-10 block with counter (p, 0, s lo, s hi) and
+ * key (seed lo, seed hi), s = first_sample + q.  Words 0 (low) and 1 (high) give u1 = ((w >> 11) + 1) 2^-53
+ * in (0, 1], words 2 and 3 give u2 = (w >> 11) 2^-53 in [0, 1); z = sqrt(-2 ln u1) cos(2 pi u2) in fp64.
+ * Only this one value of a block is used: an entry depends on (seed, p, s) alone -- not on nsamp, the group
+ * it falls into or the entry point.  spllt_hip_white_noise_dev writes z in PIVOT order, z[q*ldz + p].
+ * spllt_hip_sample*: sample q at x[q*ldx .. q*ldx + n), user order.
+ *   kind 1 (A is a covariance):  x = mean + P^T L z, through the product above: repeats bit for bit.
+ *   kind 0 (A is a precision):   x = mean + P^T L^-T z, the backward sweep.  With
+ *          spllt_hip_set_reproducible_solve on for the handle it goes through spllt_hip_solve_repro and
+ *          repeats bit for bit; otherwise through spllt_hip_solve_many, which is faster and repeats to
+ *          rounding only.
+ * mean: null, or n doubles in user order (device memory for _dev), added on the device.
+ * Errors as for the products, and a kind other than 0 or 1 -> SPLLT_ERROR_PARAMETER. */
+int spllt_hip_sample_dev(void *fkeep, int nsamp, double *x_dev, int64_t ldx, int kind,
+                         uint64_t seed, uint64_t first_sample, const double *mean_dev);
+int spllt_hip_sample(void *fkeep, int nsamp, double *x_host, int64_t ldx, int kind,
+                     uint64_t seed, uint64_t first_sample, const double *mean_host);
+int spllt_hip_white_noise_dev(void *fkeep, int nsamp, double *z_dev, int64_t ldz,
+                              uint64_t seed, uint64_t first_sample);
 int spllt_hip_set_exchange_buffer(void *fkeep, void *dev_ptr);
 /* The HIP stream (hipStream_t) every caller-visible operation of this handle is ordered on:
  * spllt_factor ends by packing the exchange buffer on it and spllt_hip_continue starts by

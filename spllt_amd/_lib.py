@@ -72,6 +72,8 @@ HIP_SYMBOLS = [
     "spllt_hip_updown", "spllt_hip_updown_plan", "spllt_hip_updown_info", "spllt_hip_updown_time",
     "spllt_hip_solve_repro", "spllt_hip_solve_repro_dev", "spllt_hip_set_reproducible_solve",
     "spllt_hip_release_solve_repro",
+    "spllt_hip_factor_mult", "spllt_hip_factor_mult_dev", "spllt_hip_release_factor_mult",
+    "spllt_hip_sample", "spllt_hip_sample_dev", "spllt_hip_white_noise_dev",
     "spllt_hip_solve_sparse", "spllt_hip_solve_sparse_dev", "spllt_hip_gram_sparse", "spllt_hip_solve_sparse_plan",
     "spllt_hip_solve_sparse_info", "spllt_hip_release_solve_sparse",
     "spllt_hip_pattern_outer", "spllt_hip_pattern_outer_dev", "spllt_hip_pattern_outer_batch_dev",
@@ -178,6 +180,18 @@ def load():
     lib.spllt_hip_set_reproducible_solve.restype = C.c_int
     lib.spllt_hip_release_solve_repro.argtypes = [vp]
     lib.spllt_hip_release_solve_repro.restype = C.c_int
+    lib.spllt_hip_factor_mult.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int]
+    lib.spllt_hip_factor_mult.restype = C.c_int
+    lib.spllt_hip_factor_mult_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int]
+    lib.spllt_hip_factor_mult_dev.restype = C.c_int
+    lib.spllt_hip_release_factor_mult.argtypes = [vp]
+    lib.spllt_hip_release_factor_mult.restype = C.c_int
+    lib.spllt_hip_sample.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, dp]
+    lib.spllt_hip_sample.restype = C.c_int
+    lib.spllt_hip_sample_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, vp]
+    lib.spllt_hip_sample_dev.restype = C.c_int
+    lib.spllt_hip_white_noise_dev.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_uint64, C.c_uint64]
+    lib.spllt_hip_white_noise_dev.restype = C.c_int
     lib.spllt_hip_solve_sparse.argtypes = [vp, C.c_int, ip, ip, dp, C.c_int, ip, dp, C.c_int64, C.c_int]
     lib.spllt_hip_solve_sparse.restype = C.c_int
     lib.spllt_hip_solve_sparse_dev.argtypes = [vp, C.c_int, ip, ip, dp, C.c_int, ip, vp, C.c_int64, C.c_int]

@@ -509,6 +509,79 @@ class Factorization:
             raise SplltError("spllt_hip_release_solve_repro", rc, self.last_error())
         return self
 
+    # ---- products with the factor, Gaussian sampling ------------------------------
+    def factor_mult(self, x, job=0):
+        """spllt_hip_factor_mult on a copy of x (n or n x nvec): job 0 P^T L L^T P x, 1 P^T L x, 2 L^T P x -- the
+        inverse of solve_many(job), bit-reproducible.  Returns a new F-ordered array, like solve."""
+        y = np.array(x, dtype=np.float64, order="F", copy=True)
+        nvec = 1 if y.ndim == 1 else y.shape[1]
+        rc = self.lib.spllt_hip_factor_mult(self.fkeep, nvec, _dp(y), y.shape[0], job)
+        if rc < 0:
+            raise SplltError("spllt_hip_factor_mult", rc, self.last_error())
+        return y
+
+    def factor_mult_dev(self, x_dev_ptr, nvec, ldx=None, job=0, pivot_order=False):
+        """spllt_hip_factor_mult_dev: the product on device vectors, in place (layout and pivot_order as
+        solve_many_dev)."""
+        if ldx is None:
+            ldx = self.n
+        rc = self.lib.spllt_hip_factor_mult_dev(self.fkeep, nvec, C.c_void_p(x_dev_ptr), int(ldx), job,
+                                                1 if pivot_order else 0)
+        if rc < 0:
+            raise SplltError("spllt_hip_factor_mult_dev", rc, self.last_error())
+        return self
+
+    def release_factor_mult(self):
+        """The second workspace, the scratch and the tables of the factor products back to the device pool."""
+        rc = self.lib.spllt_hip_release_factor_mult(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_factor_mult", rc, self.last_error())
+        return self
+
+    _SAMPLE_KINDS = {"precision": 0, "covariance": 1}
+
+    def _sample_kind(self, kind):
+        """0 / 1 of the C interface; an unknown name goes on as -1 and is rejected by the library"""
+        return self._SAMPLE_KINDS.get(kind, -1) if isinstance(kind, str) else int(kind)
+
+    def sample(self, nsamp, seed=0, kind="precision", mean=None, first_sample=0):
+        """spllt_hip_sample: nsamp draws of N(mean, A^-1) (kind "precision") or N(mean, A) ("covariance") from
+        the current factor, as an F-ordered (n, nsamp) array in user order.  Sample q is a function of (seed,
+        first_sample + q) alone."""
+        k = self._sample_kind(kind)
+        x = np.zeros((self.n, nsamp), dtype=np.float64, order="F")
+        m = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        assert m is None or m.shape == (self.n,)
+        rc = self.lib.spllt_hip_sample(self.fkeep, nsamp, _dp(x), max(self.n, 1), k, int(seed), int(first_sample),
+                                       None if m is None else _dp(m))
+        if rc < 0:
+            raise SplltError("spllt_hip_sample", rc, self.last_error())
+        return x
+
+    def sample_dev(self, x_dev_ptr, nsamp, ldx=None, seed=0, kind="precision", mean_dev_ptr=None, first_sample=0):
+        """spllt_hip_sample_dev: the samples into device memory (sample q at x[q*ldx .. q*ldx + n), user order);
+        mean_dev_ptr: n doubles on the device or None."""
+        if ldx is None:
+            ldx = self.n
+        k = self._sample_kind(kind)
+        rc = self.lib.spllt_hip_sample_dev(self.fkeep, nsamp, C.c_void_p(x_dev_ptr), int(ldx),
+                                           k, int(seed), int(first_sample),
+                                           None if mean_dev_ptr is None else C.c_void_p(mean_dev_ptr))
+        if rc < 0:
+            raise SplltError("spllt_hip_sample_dev", rc, self.last_error())
+        return self
+
+    def white_noise(self, nsamp, seed, first_sample=0):
+        """spllt_hip_white_noise_dev, copied to the host: the (n, nsamp) standard normals the samplers use, in
+        PIVOT order (row p = pivot position p)."""
+        import torch
+        z = torch.empty((nsamp, max(self.n, 1)), dtype=torch.float64, device="cuda")
+        rc = self.lib.spllt_hip_white_noise_dev(self.fkeep, nsamp, C.c_void_p(z.data_ptr()), max(self.n, 1), int(seed),
+                                                int(first_sample))
+        if rc < 0:
+            raise SplltError("spllt_hip_white_noise_dev", rc, self.last_error())
+        return np.asfortranarray(z.cpu().numpy()[:, :self.n].T)
+
     # ---- sparse right-hand sides and selected outputs -----------------------------
     def _sparse_columns(self, B, where):
         """B (scipy sparse n x k, or dense) as the 1-based CSC arrays of the C interface; explicit zeros stay"""

@@ -620,7 +620,9 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 // from which on a batched launch is split by member range (N <= 0: the hardware limit again);
 // "batch_selinv_fused=0|1": 0 forces the three-launch form of every step of the batched selected inversion;
 // "rsolve_poison=0|1": 1 fills the scratch of the reproducible solve with NaN before every sweep;
-// "solve_sparse_poison=0|1": 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
+// "solve_sparse_poison=0|1": 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed;
+// "fmult_poison=0|1": 1 fills the scratch of the factor products with NaN before every direction;
+// "fmult_alloc_fail=N": the next N allocations of the products' second workspace and scratch fail
 int spllt_hip_debug(const char* what) {
   if (!what) return -1;
   const std::string w(what);
@@ -637,6 +639,14 @@ int spllt_hip_debug(const char* what) {
   }
   if (w == "solve_sparse_poison=0" || w == "solve_sparse_poison=1") {   // NaN in the workspace of a sparse solve
     set_solve_sparse_poison(w.back() == '1');
+    return 0;
+  }
+  if (w == "fmult_poison=0" || w == "fmult_poison=1") {   // NaN in the scratch of the factor products before a direction
+    set_fmult_poison(w.back() == '1');
+    return 0;
+  }
+  if (w.rfind("fmult_alloc_fail=", 0) == 0) {   // the next N allocations of the products' workspace and scratch fail
+    set_fmult_alloc_fail(std::atoi(w.c_str() + 17));
     return 0;
   }
   if (w == "rsolve_poison=0" || w == "rsolve_poison=1") {   // NaN in the scratch of the reproducible solve before a sweep
@@ -896,6 +906,70 @@ int spllt_hip_release_solve_repro(void* fkeep) {
   int rc = do_wait(f);
   if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
   rc = f->eng->release_solve_repro();
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+// ---- products with the factor, Gaussian sampling ----------------------------
+int spllt_hip_factor_mult(void* fkeep, int nvec, double* x_host, int64_t ldx, int job) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_many_engine(f, "spllt_hip_factor_mult", nvec, x_host, ldx, job);
+  if (rc) return rc;
+  rc = f->eng->factor_mult(x_host, nvec, ldx, job);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_factor_mult_dev(void* fkeep, int nvec, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_many_engine(f, "spllt_hip_factor_mult_dev", nvec, x_dev, ldx, job);
+  if (rc) return rc;
+  rc = f->eng->factor_mult_dev(x_dev, nvec, ldx, job, pivot_order != 0);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_release_factor_mult(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (!f->eng) return 0;
+  int rc = do_wait(f);
+  if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
+  rc = f->eng->release_factor_mult();
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+static int sample_engine(Fkeep* f, const char* what, int nsamp, const void* x, int64_t ldx, int kind) {
+  if (f && f->S && x && nsamp >= 0 && ldx >= f->S->n && (kind < 0 || kind > 1)) {
+    f->last_error = std::string(what) + ": kind is not 0 (precision) or 1 (covariance)";
+    return SPLLT_ERROR_PARAMETER;
+  }
+  return solve_many_engine(f, what, nsamp, x, ldx, 0);
+}
+
+int spllt_hip_sample_dev(void* fkeep, int nsamp, double* x_dev, int64_t ldx, int kind, uint64_t seed,
+                         uint64_t first_sample, const double* mean_dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = sample_engine(f, "spllt_hip_sample_dev", nsamp, x_dev, ldx, kind);
+  if (rc) return rc;
+  f->eng->set_reproducible_solve(f->repro_solve);
+  rc = f->eng->sample(x_dev, nsamp, ldx, kind, seed, first_sample, mean_dev, true);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_sample(void* fkeep, int nsamp, double* x_host, int64_t ldx, int kind, uint64_t seed,
+                     uint64_t first_sample, const double* mean_host) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = sample_engine(f, "spllt_hip_sample", nsamp, x_host, ldx, kind);
+  if (rc) return rc;
+  f->eng->set_reproducible_solve(f->repro_solve);
+  rc = f->eng->sample(x_host, nsamp, ldx, kind, seed, first_sample, mean_host, false);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_white_noise_dev(void* fkeep, int nsamp, double* z_dev, int64_t ldz, uint64_t seed, uint64_t first_sample) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = solve_many_engine(f, "spllt_hip_white_noise_dev", nsamp, z_dev, ldz, 0);
+  if (rc) return rc;
+  rc = f->eng->white_noise_dev(z_dev, nsamp, ldz, seed, first_sample);
   return rc ? feature_fail(f, rc) : 0;
 }
 

@@ -56,6 +56,10 @@ struct EngineOptions {
 void set_batch_selinv_fused(bool on);
 // debug: the scratch of the reproducible solve is filled with NaN before every sweep
 void set_rsolve_poison(bool on);
+// debug: the scratch of the factor products is filled with NaN before every direction
+void set_fmult_poison(bool on);
+// debug: the next n allocations of the factor products' workspace and scratch fail (the fall-back to blocks of 16)
+void set_fmult_alloc_fail(int n);
 // debug: the workspace of a sparse solve is filled with NaN before its touched rows are zeroed
 void set_solve_sparse_poison(bool on);
 bool batch_selinv_fused();
@@ -154,6 +158,22 @@ class Engine {
   int solve_repro_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order);
   int solve_repro(double* x_host, int nrhs, int64_t ldx, int job);   // host vectors, user order
   int release_solve_repro();                                          // tables and scratch back to the pool
+  // ---- products with the factor and Gaussian sampling (factor_mult.hip, single GPU): x <- P^T L L^T P x (job 0),
+  // P^T L x (job 1), L^T P x (job 2) on blocks of 32 vectors (a tail of at most 16: one block of 16), out of
+  // place between the workspace of solve_many and a second one, two launches per direction, no atomic add:
+  // the same factor bits and vector bits give the same result bits whatever the block, the place in it or the
+  // entry point.  Layout of x as solve_many.  prepare_factor_mult: the RsolveTables (shared with the
+  // reproducible solve when resident), the second workspace (rb n doubles) and a scratch of rb * max(frows,
+  // bsize) doubles, rb = 32, or 16 when that does not fit (-1: no memory either way; the factor and every
+  // solve stay usable).
+  int factor_mult_dev(double* x_dev, int nvec, int64_t ldx, int job, bool pivot_order);
+  int factor_mult(double* x_host, int nvec, int64_t ldx, int job);   // host vectors, user order
+  // z[q * ldz + p] = N(0, 1) of (seed, pivot position p, sample first + q): Philox4x32-10 + Box-Muller
+  int white_noise_dev(double* z_dev, int nsamp, int64_t ldz, uint64_t seed, uint64_t first);
+  // x[q * ldx ..] = mean + P^T L z_q (kind 1) or mean + P^T L^-T z_q (kind 0: the backward sweep of solve_repro
+  // when set_reproducible_solve is on, else of solve_many); mean: n doubles in user order or null; user order
+  int sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, const double* mean, bool dev);
+  int release_factor_mult();                                          // workspace, scratch and tables back to the pool
   // ---- sparse right-hand sides and selected outputs (solve_sparse.hip, single GPU): B = k sparse columns (CSC,
   // 1-based, user order, validated by the caller: check_sparse_columns), sel = nsel wanted user variables (null:
   // all n).  Per group of 32 columns (a tail of at most 16: a block of 16) the substitution program is filtered
@@ -424,6 +444,21 @@ class Engine {
   double* d_rsscratch_ = nullptr;  // 4 x rs_stride_ doubles
   double* d_rsstage_ = nullptr;    // 4 n doubles: host vectors in the caller's order
   int64_t rs_stride_ = 0;
+  // the RsolveTables on the device: shared by the reproducible solve and the factor products, given back when
+  // the last of the two is released
+  hipError_t ensure_rsolve_tables();
+  void drop_rsolve_tables();
+  // factor products (taken on first use, all or nothing)
+  int prepare_factor_mult(bool host_stage);
+  void enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
+  bool fm_ready_ = false;
+  int fm_rb_ = 32;                 // widest block the workspace and the scratch hold (32, or 16 when memory is short)
+  char* d_fmtab_ = nullptr;        // the (block column, chunk of 64 positions) pairs
+  UpdTile* d_fmchunks_ = nullptr;
+  int64_t fm_nchunks_ = 0;
+  double* d_fmW_ = nullptr;        // fm_rb_ * n doubles: the second workspace
+  double* d_fmscratch_ = nullptr;  // fm_rb_ * rs_stride_ doubles
+  double* d_fmmean_ = nullptr;     // n doubles: the mean of a host entry point
   // blocked solve (workspace allocated on first use, kept with the engine)
   int prepare_solve_many(bool host_stage);
   void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);

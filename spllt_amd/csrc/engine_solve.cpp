@@ -567,33 +567,48 @@ int Engine::release_solve_sparse() {
 static std::atomic<bool> g_rsolve_poison{false};
 void set_rsolve_poison(bool on) { g_rsolve_poison.store(on); }
 
-int Engine::prepare_solve_repro() {
-  int rc = prepare_solve();
-  if (rc) return rc;
-  if (rs_ready_) return 0;
-  const Symbolic& S = *S_;
+// the RsolveTables of the substitution program, uploaded once; rs_stride_ = max(frows, bsize)
+hipError_t Engine::ensure_rsolve_tables() {
+  if (d_rstab_) return hipSuccess;
   RsolveTables R;
-  build_rsolve_tables(S, sprog_, R);
+  build_rsolve_tables(*S_, sprog_, R);
   rs_stride_ = std::max<int64_t>(1, std::max(R.frows, R.bsize));
-  const size_t sb = sizeof(double) * 4 * (size_t)rs_stride_;
   TableStager tab;
   tab.add(&d_rsfslot_, R.fslot);
   tab.add(&d_rsbfirst_, R.bfirst);
   tab.add(&d_rsgptr_, R.gptr);
   tab.add(&d_rsgsrc_, R.gsrc);
   tab.add(&d_rsbslot_, R.bslot);
-  // (a failure here leaves the factor and the other solves usable: the engine's status is not touched)
   hipError_t e = tab.commit(&d_rstab_, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e != hipSuccess) drop_rsolve_tables();
+  return e;
+}
+
+// (the caller has checked that neither user is left)
+void Engine::drop_rsolve_tables() {
+  if (d_rstab_) release_buffer(d_rstab_);
+  d_rstab_ = nullptr;
+}
+
+int Engine::prepare_solve_repro() {
+  int rc = prepare_solve();
+  if (rc) return rc;
+  if (rs_ready_) return 0;
+  const Symbolic& S = *S_;
+  // (a failure here leaves the factor and the other solves usable: the engine's status is not touched)
+  hipError_t e = ensure_rsolve_tables();
+  const size_t sb = sizeof(double) * 4 * (size_t)rs_stride_;
   if (e == hipSuccess) e = ensure_order();
   if (e == hipSuccess) e = dalloc((void**)&d_rsscratch_, sb);
   if (e == hipSuccess) e = dalloc((void**)&d_rsstage_, sizeof(double) * 4 * (size_t)std::max(1, S.n));
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
+    for (void* p : {(void*)d_rsscratch_, (void*)d_rsstage_})
       if (p) release_buffer(p);
-    d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+    d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+    if (!fm_ready_) drop_rsolve_tables();
     feature_err_ = "solve_repro: not enough device memory for the tables and the scratch of 4 right-hand sides (" +
-                   std::to_string((sb + tab.host.size()) >> 20) + " MiB): " + hipGetErrorString(e);
+                   std::to_string(sb >> 20) + " MiB): " + hipGetErrorString(e);
     return alloc_code(e);
   }
   rs_ready_ = true;
@@ -606,9 +621,10 @@ int Engine::release_solve_repro() {
   if (!rs_ready_) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "solve_repro release")) return rc;
-  for (void* p : {(void*)d_rstab_, (void*)d_rsscratch_, (void*)d_rsstage_})
+  for (void* p : {(void*)d_rsscratch_, (void*)d_rsstage_})
     if (p) release_buffer(p);
-  d_rstab_ = nullptr; d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+  d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
+  if (!fm_ready_) drop_rsolve_tables();
   rs_ready_ = false;
   return 0;
 }
@@ -681,6 +697,211 @@ int Engine::solve_repro(double* x_host, int nrhs, int64_t ldx, int job) {
     if ((rc = copy_vectors(false, d_rsstage_, xg, ldx, cur, "x D2H"))) return rc;
     if ((rc = sync_stream(stream_, "solve_repro sync"))) return rc;
     done += cur;
+  }
+  return 0;
+}
+
+// ---- products with the factor, Gaussian sampling ---------------------------------------------------
+static std::atomic<bool> g_fmult_poison{false};
+static std::atomic<int> g_fmult_alloc_fail{0};
+void set_fmult_poison(bool on) { g_fmult_poison.store(on); }
+void set_fmult_alloc_fail(int n) { g_fmult_alloc_fail.store(n); }
+
+int Engine::prepare_factor_mult(bool host_stage) {
+  int rc = prepare_solve_many(host_stage);
+  if (rc) return rc;
+  if (fm_ready_) return 0;
+  const size_t n1 = (size_t)std::max(1, S_->n);
+  // the (block column, chunk of 64 pivot positions) pairs of the diagonal launches, block columns ascending
+  std::vector<UpdTile> chunks;
+  for (size_t b = 0; b < sprog_.units.size(); ++b)
+    for (int c = 0; c * 64 < sprog_.units[b].w; ++c) chunks.push_back(UpdTile{(int)b, (short)c, 0});
+  fm_nchunks_ = (int64_t)chunks.size();
+  // (a failure here leaves the factor and every solve usable: the engine's status is not touched)
+  hipError_t e = ensure_rsolve_tables();
+  if (e == hipSuccess) {
+    TableStager tab;
+    tab.add(&d_fmchunks_, chunks);
+    e = tab.commit(&d_fmtab_, [this](void** q, size_t b) { return dalloc(q, b); });
+  }
+  size_t want = 0;
+  auto take = [&](void** p, size_t bytes) {
+    if (g_fmult_alloc_fail.load() > 0) {
+      g_fmult_alloc_fail.fetch_sub(1);
+      return hipErrorOutOfMemory;
+    }
+    return dalloc(p, bytes);
+  };
+  // blocks of 32 vectors; when that does not fit, blocks of 16 (per vector the same sums in the same order)
+  for (int rb = 32; e == hipSuccess && rb >= 16; rb /= 2) {
+    want = sizeof(double) * (size_t)rb * (n1 + (size_t)rs_stride_);
+    e = take((void**)&d_fmW_, sizeof(double) * (size_t)rb * n1);
+    if (e == hipSuccess) e = take((void**)&d_fmscratch_, sizeof(double) * (size_t)rb * (size_t)rs_stride_);
+    fm_rb_ = rb;
+    if (e == hipSuccess) break;
+    (void)hipGetLastError();
+    for (void* p : {(void*)d_fmW_, (void*)d_fmscratch_})
+      if (p) release_buffer(p);
+    d_fmW_ = nullptr; d_fmscratch_ = nullptr;
+    if (rb > 16 && alloc_code(e) == -1) e = hipSuccess;   // (out of memory: once more with half of it)
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (d_fmtab_) release_buffer(d_fmtab_);
+    d_fmtab_ = nullptr; d_fmchunks_ = nullptr;
+    if (!rs_ready_) drop_rsolve_tables();
+    feature_err_ = "factor_mult: not enough device memory for the tables, the second workspace and the scratch of 16 "
+                   "vectors (" + std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  fm_ready_ = true;
+  return 0;
+}
+
+int Engine::release_factor_mult() {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!fm_ready_ && !d_fmmean_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "factor_mult release")) return rc;
+  for (void* p : {(void*)d_fmtab_, (void*)d_fmW_, (void*)d_fmscratch_, (void*)d_fmmean_})
+    if (p) release_buffer(p);
+  d_fmtab_ = nullptr; d_fmchunks_ = nullptr; d_fmW_ = nullptr; d_fmscratch_ = nullptr; d_fmmean_ = nullptr;
+  fm_ready_ = false;
+  if (!rs_ready_) drop_rsolve_tables();
+  return 0;
+}
+
+// one block of nv <= rb vectors: pack, the products `job` asks for, unpack (enqueue only).  Job 0 is L^T X into
+// the second workspace and L of that back into the first; job 1 / 2 end in the second one.
+void Engine::enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order) {
+  const int n = S_->n;
+  const int* order = pivot_order ? nullptr : d_order_;
+  const SolveTablesView tv = solve_tables();
+  const FmultView fv{d_rsfslot_, d_rsbfirst_, d_rsgptr_, d_rsgsrc_, d_rsbslot_, d_fmscratch_};
+  const int64_t ntiles = (int64_t)sprog_.tiles.size();
+  auto product = [&](bool transpose, const double* X, double* Y) {
+    // debug: a slot that is read without having been written by this product shows up as NaN
+    if (g_fmult_poison.load())
+      (void)hipMemsetAsync(d_fmscratch_, 0xFF, sizeof(double) * (size_t)fm_rb_ * (size_t)rs_stride_, stream_);
+    launch_factor_mult(stream_, tv, ntiles, d_fmchunks_, fm_nchunks_, transpose, X, Y, rb, fv);
+  };
+  launch_solve_many_pack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
+  if (job != 1) product(true, d_smW_, d_fmW_);
+  if (job == 0) product(false, d_fmW_, d_smW_);
+  if (job == 1) product(false, d_smW_, d_fmW_);
+  launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, job == 0 ? d_smW_ : d_fmW_);
+}
+
+int Engine::factor_mult_dev(double* x_dev, int nvec, int64_t ldx, int job, bool pivot_order) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (job < 0 || job > 2 || nvec < 0 || !x_dev || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (pending_) return -10;          // (the caller waits first)
+  if (nvec == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_factor_mult(false);
+  if (rc) return rc;
+  for (int done = 0; done < nvec;) {
+    const int left = nvec - done;
+    const int rb = left > 16 && fm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
+    enqueue_factor_mult_block(x_dev + (int64_t)done * ldx, ldx, nv, rb, job, pivot_order);
+    done += nv;
+  }
+  HIPCHK(hipGetLastError(), "factor_mult launch");
+  return sync_stream(stream_, "factor_mult sync");
+}
+
+int Engine::factor_mult(double* x_host, int nvec, int64_t ldx, int job) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (job < 0 || job > 2 || nvec < 0 || !x_host || ldx < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nvec == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_factor_mult(true);
+  if (rc) return rc;
+  const int n = S_->n;
+  for (int done = 0; done < nvec;) {
+    const int left = nvec - done;
+    const int rb = left > 16 && fm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
+    double* xb = x_host + (int64_t)done * ldx;
+    if ((rc = copy_vectors(true, d_smstage_, xb, ldx, nv, "x H2D"))) return rc;
+    enqueue_factor_mult_block(d_smstage_, n, nv, rb, job, false);
+    HIPCHK(hipGetLastError(), "factor_mult launch");
+    if ((rc = copy_vectors(false, d_smstage_, xb, ldx, nv, "y D2H"))) return rc;
+    if ((rc = sync_stream(stream_, "factor_mult sync"))) return rc;
+    done += nv;
+  }
+  return 0;
+}
+
+int Engine::white_noise_dev(double* z_dev, int nsamp, int64_t ldz, uint64_t seed, uint64_t first) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (nsamp < 0 || !z_dev || ldz < S_->n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nsamp == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  launch_white_noise(stream_, z_dev, ldz, nullptr, S_->n, nsamp, seed, first);
+  HIPCHK(hipGetLastError(), "white_noise launch");
+  return sync_stream(stream_, "white_noise sync");
+}
+
+// The noise is written where the operation that follows expects a pivot-order vector laid out in user
+// positions (x[i] = z[order[i]]): the product and the sweeps then run through their own entry points.
+int Engine::sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, const double* mean,
+                   bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n;
+  if (kind < 0 || kind > 1 || nsamp < 0 || !x || ldx < n) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nsamp == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = kind == 1 ? prepare_factor_mult(!dev) : (repro_on_ ? prepare_solve_repro() : 0);
+  if (!rc) rc = prepare_solve_many(!dev);   // (the order table; the staging block of the host entry point)
+  if (rc) return rc;
+  const double* dmean = mean;
+  if (mean && !dev) {
+    if (!d_fmmean_) {
+      hipError_t e = dalloc((void**)&d_fmmean_, sizeof(double) * (size_t)n);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        d_fmmean_ = nullptr;
+        feature_err_ = std::string("sample: not enough device memory for the mean: ") + hipGetErrorString(e);
+        return alloc_code(e);
+      }
+    }
+    HIPCHK(hipMemcpyAsync(d_fmmean_, mean, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream_), "mean H2D");
+    dmean = d_fmmean_;
+  }
+  // one group on device vectors xg (vector q at xg + q * ld): noise, the operation, the mean
+  auto group = [&](double* xg, int64_t ld, int nv, uint64_t s0) -> int {
+    launch_white_noise(stream_, xg, ld, d_order_, n, nv, seed, s0);
+    int r = 0;
+    if (kind == 1) r = factor_mult_dev(xg, nv, ld, 1, false);
+    else if (repro_on_) r = solve_repro_dev(xg, nv, ld, 2, false);
+    else r = solve_many_dev(xg, nv, ld, 2, false);
+    if (r) return r;
+    if (dmean) launch_add_mean(stream_, xg, ld, dmean, n, nv);
+    HIPCHK(hipGetLastError(), "sample launch");
+    return 0;
+  };
+  if (dev) {
+    if ((rc = group(x, ldx, nsamp, first))) return rc;
+    return sync_stream(stream_, "sample sync");
+  }
+  for (int done = 0; done < nsamp;) {   // the staging block holds 32 vectors
+    const int nv = std::min(32, nsamp - done);
+    if ((rc = group(d_smstage_, (int64_t)n, nv, first + (uint64_t)done))) return rc;
+    if ((rc = copy_vectors(false, d_smstage_, x + (int64_t)done * ldx, ldx, nv, "x D2H"))) return rc;
+    if ((rc = sync_stream(stream_, "sample sync"))) return rc;
+    done += nv;
   }
   return 0;
 }

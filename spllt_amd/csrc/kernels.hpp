@@ -236,6 +236,27 @@ struct RsolveView {
 // one launch of the SolveProgram, arguments as launch_solve
 void launch_solve_repro(hipStream_t st, const SolveTablesView& t, const SolveLaunch& l, const SolveLaunchInfo& li,
                         double* y, int nr, int64_t ldy, const RsolveView& rv);
+// ---- products with the factor and Gaussian noise (factor_mult.hip) ----------------------------------
+// The RsolveTables on the device and the scratch of the products: slot s of the tables is the row
+// scratch[s * rb .. s * rb + rb) of a block of rb vectors, rb * max(frows, bsize) doubles in all.
+struct FmultView {
+  const int64_t* fslot;    // per block column
+  const int64_t* bfirst;   // per block column
+  const int64_t* gptr;     // n + 1
+  const int64_t* gsrc;     // frows
+  const int64_t* bslot;    // per tile
+  double* scratch;
+};
+// Y = L X (transpose: L^T X) on the workspaces X[p * rb + q], Y[p * rb + q] (X != Y), rb = 16 or 32: one
+// launch over all ntiles tiles of the SolveProgram (t.tiles) and one over the nchunks (block column, 64
+// pivot positions) pairs of `chunks` (UpdTile: unit, ti = chunk); no atomic add
+void launch_factor_mult(hipStream_t st, const SolveTablesView& t, int64_t ntiles, const UpdTile* chunks, int64_t nchunks,
+                        bool transpose, const double* X, double* Y, int rb, const FmultView& fv);
+// z[q * ldz + i] = the standard normal of (pivot position order[i] (null: i), sample first + q, seed), q < nsamp
+void launch_white_noise(hipStream_t st, double* z, int64_t ldz, const int* order, int n, int nsamp, uint64_t seed,
+                        uint64_t first);
+// x[q * ldx + i] += mean[i], q < nvec
+void launch_add_mean(hipStream_t st, double* x, int64_t ldx, const double* mean, int n, int nvec);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 

@@ -10,7 +10,8 @@ Convention: ``val[k]`` is the k-th stored value of the CSC lower triangle and st
     d loss / d val[k] = -(lam_i x_j + [i != j] lam_j x_i)      for x = A^-1 b,  lam = A^-1 xbar
     d logdet / d val[k] = (2 - delta_ij) (A^-1)_ij
 
-Out of scope: CPU tensors, float32, partitioned handles, sparse right-hand sides, second derivatives.
+Out of scope: CPU tensors, float32, partitioned handles, sparse right-hand sides, second derivatives, gradients of
+samples with respect to the matrix values.
 """
 import weakref
 
@@ -241,6 +242,29 @@ class SparseCholesky:
             ut = U.reshape(self.n, -1).t().contiguous()
             vt = V.reshape(self.n, -1).t().contiguous()
             return self._outer(ut, vt, float(alpha))
+
+    def sample(self, val, nsamp, seed=0, kind="precision", mean=None):
+        """nsamp draws of N(mean, A(val)^-1) (kind "precision") or N(mean, A(val)) ("covariance") from the cached
+        factor of val: a float64 device tensor (n, nsamp); sample q is a function of (seed, q) alone
+        (Factorization.sample).  The result carries NO gradient to val -- pathwise derivatives through L are out of
+        scope -- but it does carry the gradient to mean (the identity).  reproducible=True: the precision kind
+        goes through the reproducible solve and repeats bit for bit, like the covariance kind always does."""
+        self._values(val, "val", (self.nnz,))
+        if mean is not None:
+            self._tensor(mean, "mean", (self.n,), val.device)
+        self._enter(val)
+        with torch.no_grad():
+            self._ensure_factor(val)
+            work = torch.empty((int(nsamp), self.n), dtype=torch.float64, device=self.device)
+            self._sync()
+            with torch.cuda.device(self.device):
+                before = self.f.set_reproducible_solve(self.reproducible)
+                try:
+                    self.f.sample_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed, kind=kind)
+                finally:
+                    self.f.set_reproducible_solve(before)
+        x = work.t()
+        return x if mean is None else x + mean[:, None]
 
     def close(self):
         self.f.close()
