@@ -681,6 +681,46 @@ int spllt_hip_pattern_outer_batch_dev(void *fkeep, int nbatch, int nvec, const d
  * member are NaN. */
 int spllt_hip_inverse_on_pattern_dev(void *fkeep, double *out_dev);
 int spllt_hip_inverse_on_pattern_batch_dev(void *fkeep, double *out_dev, int64_t ldout);
+/* ---- reverse-mode derivative of the factor -----------------------------------------
+ * G is a further arena with the layout of spllt_hip_get_factor.  Seeded, it holds Lbar = d loss / d L on the
+ * lower positions of L in pivot order (the strict upper triangle of a diagonal tile is never read).
+ * spllt_hip_factor_adjoint sweeps it in place -- the panels of the selected inversion in the same order, three
+ * launches per step, no atomics, every sum in a fixed order: the same bits for the same L and Lbar -- into
+ * d loss / d (P A P^T)_ij on every stored lower position, a stored lower entry standing for a_ij AND a_ji, and
+ * returns the values at the entries of A: gval[k] = d loss / d val[k], nnz doubles in the order of val.
+ *
+ * _seed: G (+)= alpha sum_q a_q[r] b_q[c] at every lower position (r, c); vector q at a + q * ld, ld >= n.
+ * order_flags bit 0: a is in pivot order, bit 1: b is (spllt_hip_white_noise_dev writes pivot order); else a
+ * vector is in the user's variable order.  accumulate = 0 overwrites (nvec = 0: zeroes the arena), 1 adds to
+ * a seeded arena.  Per entry the sum is one fma chain over q ascending, alpha applied once: a vector's
+ * contribution does not depend on nvec or on its place among the others.  The seeds of the uses, all
+ * vectors in pivot order, ybar the incoming gradient:  y = L x: + ybar x^T;  y = L^T x: + x ybar^T;
+ * y = L^-1 x: - (L^-T ybar) y^T;  y = L^-T x: - y (L^-1 ybar)^T.  The map Lbar -> gval is linear: any number
+ * of vectors shares one sweep.
+ * _set / _get: the whole arena from / to the host (an arbitrary Lbar; after the sweep the result).
+ * spllt_hip_device_factor_adjoint: the arena on the device, null while it is unseeded.
+ *
+ * States: unseeded (also after spllt_factor, spllt_hip_factor_dev, spllt_hip_updown: stale), seeded, swept.
+ * The arena is taken on first use and kept until spllt_hip_release_factor_adjoint or the handle is freed; the
+ * program tables and the step scratch are shared with spllt_hip_selected_inverse, whose Z arena is untouched.
+ *
+ * Errors, decided before anything is enqueued: a null pointer, nvec < 0, ld < n, count < the arena, nothing
+ * factorized, accumulate = 1 on an arena that is not seeded, a sweep of an arena that is not freshly seeded
+ * (a second sweep included), _get on an unseeded arena -> SPLLT_ERROR_PARAMETER; a partitioned handle ->
+ * SPLLT_ERROR_UNIMPLEMENTED; no memory for G -> SPLLT_ERROR_ALLOCATION (nothing is kept half-allocated, the
+ * factor and the solves stay usable); a symbolic structure the selected-inversion program cannot be built
+ * for -> the flag of spllt_hip_selected_inverse.  All work is ordered on spllt_hip_engine_stream and finished
+ * when a call returns. */
+int spllt_hip_factor_adjoint_seed_dev(void *fkeep, int nvec, const double *a_dev, const double *b_dev, int64_t ld,
+                                      double alpha, int accumulate, int order_flags);
+int spllt_hip_factor_adjoint_seed(void *fkeep, int nvec, const double *a_host, const double *b_host, int64_t ld,
+                                  double alpha, int accumulate, int order_flags);
+int spllt_hip_set_factor_adjoint(void *fkeep, const double *host_arena, int64_t count);
+int spllt_hip_get_factor_adjoint(void *fkeep, double *out, int64_t count);
+double *spllt_hip_device_factor_adjoint(void *fkeep);
+int spllt_hip_factor_adjoint_dev(void *fkeep, double *gval_dev);
+int spllt_hip_factor_adjoint(void *fkeep, double *gval_host);
+int spllt_hip_release_factor_adjoint(void *fkeep);
 /* a counter that every successful change of the factor increments: which = 0 the single factor
  * (spllt_factor, spllt_hip_factor_dev, spllt_hip_updown, the profiling entry points), which = 1 the batch
  * (spllt_hip_factor_batch*).  0 on a fresh handle; needs no device.  A caller that saved state computed

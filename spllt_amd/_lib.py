@@ -78,6 +78,9 @@ HIP_SYMBOLS = [
     "spllt_hip_solve_sparse_info", "spllt_hip_release_solve_sparse",
     "spllt_hip_pattern_outer", "spllt_hip_pattern_outer_dev", "spllt_hip_pattern_outer_batch_dev",
     "spllt_hip_inverse_on_pattern_dev", "spllt_hip_inverse_on_pattern_batch_dev", "spllt_hip_factor_serial",
+    "spllt_hip_factor_adjoint_seed", "spllt_hip_factor_adjoint_seed_dev", "spllt_hip_set_factor_adjoint",
+    "spllt_hip_get_factor_adjoint", "spllt_hip_device_factor_adjoint", "spllt_hip_factor_adjoint",
+    "spllt_hip_factor_adjoint_dev", "spllt_hip_release_factor_adjoint",
 ]
 
 _lib = None
@@ -312,6 +315,21 @@ def load():
     lib.spllt_hip_pattern_outer_batch_dev.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, C.c_double, vp,
                                                       C.c_int64]
     lib.spllt_hip_pattern_outer_batch_dev.restype = C.c_int
+    lib.spllt_hip_factor_adjoint_seed.argtypes = [vp, C.c_int, dp, dp, C.c_int64, C.c_double, C.c_int, C.c_int]
+    lib.spllt_hip_factor_adjoint_seed.restype = C.c_int
+    lib.spllt_hip_factor_adjoint_seed_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_double, C.c_int, C.c_int]
+    lib.spllt_hip_factor_adjoint_seed_dev.restype = C.c_int
+    for fn in (lib.spllt_hip_set_factor_adjoint, lib.spllt_hip_get_factor_adjoint):
+        fn.argtypes = [vp, dp, C.c_int64]
+        fn.restype = C.c_int
+    lib.spllt_hip_device_factor_adjoint.argtypes = [vp]
+    lib.spllt_hip_device_factor_adjoint.restype = C.c_void_p
+    lib.spllt_hip_factor_adjoint.argtypes = [vp, dp]
+    lib.spllt_hip_factor_adjoint.restype = C.c_int
+    lib.spllt_hip_factor_adjoint_dev.argtypes = [vp, vp]
+    lib.spllt_hip_factor_adjoint_dev.restype = C.c_int
+    lib.spllt_hip_release_factor_adjoint.argtypes = [vp]
+    lib.spllt_hip_release_factor_adjoint.restype = C.c_int
     lib.spllt_hip_inverse_on_pattern_dev.argtypes = [vp, vp]
     lib.spllt_hip_inverse_on_pattern_dev.restype = C.c_int
     lib.spllt_hip_inverse_on_pattern_batch_dev.argtypes = [vp, vp, C.c_int64]

@@ -538,6 +538,83 @@ class Factorization:
             raise SplltError("spllt_hip_release_factor_mult", rc, self.last_error())
         return self
 
+    # ---- reverse-mode derivative of the factor ------------------------------------
+    @staticmethod
+    def _order_flags(a_pivot_order, b_pivot_order):
+        return (1 if a_pivot_order else 0) | (2 if b_pivot_order else 0)
+
+    def factor_adjoint_seed(self, a, b, alpha=1.0, accumulate=False, a_pivot_order=False, b_pivot_order=False):
+        """spllt_hip_factor_adjoint_seed on host arrays a, b of shape (n,) or (n, nvec): Lbar (+)= alpha sum_q
+        a_q b_q^T on the lower positions of L; a vector is in the user's variable order unless its flag says
+        pivot order"""
+        a = np.asfortranarray(np.asarray(a, dtype=np.float64).reshape(self.n, -1))
+        b = np.asfortranarray(np.asarray(b, dtype=np.float64).reshape(self.n, -1))
+        if a.shape != b.shape:
+            raise ValueError("factor_adjoint_seed: a and b must have the same shape")
+        rc = self.lib.spllt_hip_factor_adjoint_seed(self.fkeep, a.shape[1], _dp(a), _dp(b), max(self.n, 1), float(alpha),
+                                                    1 if accumulate else 0,
+                                                    self._order_flags(a_pivot_order, b_pivot_order))
+        if rc < 0:
+            raise SplltError("spllt_hip_factor_adjoint_seed", rc, self.last_error())
+        return self
+
+    def factor_adjoint_seed_dev(self, a_dev_ptr, b_dev_ptr, nvec, ld=None, alpha=1.0, accumulate=False,
+                                a_pivot_order=False, b_pivot_order=False):
+        """spllt_hip_factor_adjoint_seed_dev: the seed from device vectors (vector q at a[q*ld .. q*ld + n))"""
+        if ld is None:
+            ld = self.n
+        rc = self.lib.spllt_hip_factor_adjoint_seed_dev(self.fkeep, int(nvec), C.c_void_p(a_dev_ptr), C.c_void_p(b_dev_ptr),
+                                                        int(ld), float(alpha), 1 if accumulate else 0,
+                                                        self._order_flags(a_pivot_order, b_pivot_order))
+        if rc < 0:
+            raise SplltError("spllt_hip_factor_adjoint_seed_dev", rc, self.last_error())
+        return self
+
+    def set_factor_adjoint(self, arena):
+        """spllt_hip_set_factor_adjoint: an arbitrary Lbar, the layout of get_factor (its strict upper triangles of
+        diagonal tiles are never read)"""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        rc = self.lib.spllt_hip_set_factor_adjoint(self.fkeep, _dp(arena), arena.size)
+        if rc < 0:
+            raise SplltError("spllt_hip_set_factor_adjoint", rc, self.last_error())
+        return self
+
+    def get_factor_adjoint(self, out=None):
+        """the adjoint arena on the host: Lbar as seeded, or after factor_adjoint() d loss / d (P A P^T) on the
+        stored lower positions"""
+        arena = self.sym_info()["arena"]
+        if out is None:
+            out = np.zeros(max(arena, 1), dtype=np.float64)
+        assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
+        rc = self.lib.spllt_hip_get_factor_adjoint(self.fkeep, _dp(out), arena)
+        if rc < 0:
+            raise SplltError("spllt_hip_get_factor_adjoint", rc, self.last_error())
+        return out[:arena]
+
+    def device_factor_adjoint_ptr(self):
+        return self.lib.spllt_hip_device_factor_adjoint(self.fkeep)
+
+    def factor_adjoint(self):
+        """spllt_hip_factor_adjoint: the sweep over the seeded arena; returns d loss / d val, nnz values"""
+        out = np.zeros(max(self.nnz, 1), dtype=np.float64)
+        rc = self.lib.spllt_hip_factor_adjoint(self.fkeep, _dp(out))
+        if rc < 0:
+            raise SplltError("spllt_hip_factor_adjoint", rc, self.last_error())
+        return out[:self.nnz]
+
+    def factor_adjoint_dev(self, gval_dev_ptr):
+        """spllt_hip_factor_adjoint_dev: the same sweep, the nnz values into device memory"""
+        rc = self.lib.spllt_hip_factor_adjoint_dev(self.fkeep, C.c_void_p(gval_dev_ptr))
+        if rc < 0:
+            raise SplltError("spllt_hip_factor_adjoint_dev", rc, self.last_error())
+        return self
+
+    def release_factor_adjoint(self):
+        rc = self.lib.spllt_hip_release_factor_adjoint(self.fkeep)
+        if rc < 0:
+            raise SplltError("spllt_hip_release_factor_adjoint", rc, self.last_error())
+        return self
+
     _SAMPLE_KINDS = {"precision": 0, "covariance": 1}
 
     def _sample_kind(self, kind):
@@ -569,6 +646,17 @@ class Factorization:
                                            None if mean_dev_ptr is None else C.c_void_p(mean_dev_ptr))
         if rc < 0:
             raise SplltError("spllt_hip_sample_dev", rc, self.last_error())
+        return self
+
+    def white_noise_dev(self, z_dev_ptr, nsamp, ldz=None, seed=0, first_sample=0):
+        """spllt_hip_white_noise_dev: the standard normals the samplers use into device memory, sample q at
+        z[q*ldz .. q*ldz + n) in PIVOT order"""
+        if ldz is None:
+            ldz = max(self.n, 1)
+        rc = self.lib.spllt_hip_white_noise_dev(self.fkeep, int(nsamp), C.c_void_p(z_dev_ptr), int(ldz), int(seed),
+                                                int(first_sample))
+        if rc < 0:
+            raise SplltError("spllt_hip_white_noise_dev", rc, self.last_error())
         return self
 
     def white_noise(self, nsamp, seed, first_sample=0):

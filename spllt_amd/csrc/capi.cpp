@@ -1614,6 +1614,106 @@ int spllt_hip_release_inverse(void* fkeep) {
   return rc ? feature_fail(f, rc) : 0;
 }
 
+// ---- reverse-mode derivative of the factor --------------------------------------------------------
+// the argument checks that need no device, then the handle's engine with its factor finished
+static int fadj_engine(Fkeep* f, const char* what, const char* bad) {
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (bad) {
+    f->last_error = std::string(what) + ": " + bad;
+    return SPLLT_ERROR_PARAMETER;
+  }
+  if (int rc = batch_partitioned(f, what)) return rc;
+  return need_single_factor(f, what);
+}
+
+static int fadj_seed_impl(const char* what, void* fkeep, int nvec, const double* a, const double* b, int64_t ld,
+                          double alpha, int accumulate, int order_flags, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* bad = nullptr;
+  if (f && f->S) {
+    if (!a || !b) bad = "a vector array is null";
+    else if (nvec < 0) bad = "nvec < 0";
+    else if (ld < f->S->n) bad = "ld < n";
+    else if (accumulate < 0 || accumulate > 1) bad = "accumulate is not 0 or 1";
+    else if (order_flags < 0 || order_flags > 3) bad = "order_flags is not 0 .. 3";
+  }
+  int rc = fadj_engine(f, what, bad);
+  if (rc) return rc;
+  rc = f->eng->fadj_seed(nvec, a, b, ld, alpha, accumulate != 0, order_flags, dev);
+  if (rc == SPLLT_ERROR_PARAMETER && f->eng->feature_error().empty())
+    f->last_error = std::string(what) + ": the factor is not available";
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_factor_adjoint_seed_dev(void* fkeep, int nvec, const double* a_dev, const double* b_dev, int64_t ld,
+                                      double alpha, int accumulate, int order_flags) {
+  return fadj_seed_impl("spllt_hip_factor_adjoint_seed_dev", fkeep, nvec, a_dev, b_dev, ld, alpha, accumulate,
+                        order_flags, true);
+}
+
+int spllt_hip_factor_adjoint_seed(void* fkeep, int nvec, const double* a_host, const double* b_host, int64_t ld,
+                                  double alpha, int accumulate, int order_flags) {
+  return fadj_seed_impl("spllt_hip_factor_adjoint_seed", fkeep, nvec, a_host, b_host, ld, alpha, accumulate,
+                        order_flags, false);
+}
+
+int spllt_hip_set_factor_adjoint(void* fkeep, const double* host_arena, int64_t count) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_set_factor_adjoint";
+  const char* bad = nullptr;
+  if (f && f->S) {
+    if (!host_arena) bad = "the arena is null";
+    else if (count < f->S->arena) bad = "count is smaller than the factor arena";
+  }
+  int rc = fadj_engine(f, what, bad);
+  if (rc) return rc;
+  rc = f->eng->fadj_upload(host_arena, count);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_get_factor_adjoint(void* fkeep, double* out, int64_t count) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_get_factor_adjoint";
+  int rc = fadj_engine(f, what, (f && f->S && !out) ? "the output array is null" : nullptr);
+  if (rc) return rc;
+  if (f->eng->fadj_state() == Engine::FADJ_UNSEEDED) {
+    f->last_error = std::string(what) + ": no factor adjoint of the current factor (seed it after every factorization)";
+    return SPLLT_ERROR_PARAMETER;
+  }
+  rc = f->eng->fadj_download(out, count);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+double* spllt_hip_device_factor_adjoint(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  return (f && f->eng && !f->eng->pending()) ? f->eng->device_G() : nullptr;
+}
+
+static int fadj_sweep_impl(const char* what, void* fkeep, double* gval, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  int rc = fadj_engine(f, what, (f && f->S && !gval) ? "the gradient array is null" : nullptr);
+  if (rc) return rc;
+  rc = f->eng->fadj_sweep(gval, dev);
+  return rc ? feature_fail(f, rc) : 0;
+}
+
+int spllt_hip_factor_adjoint_dev(void* fkeep, double* gval_dev) {
+  return fadj_sweep_impl("spllt_hip_factor_adjoint_dev", fkeep, gval_dev, true);
+}
+
+int spllt_hip_factor_adjoint(void* fkeep, double* gval_host) {
+  return fadj_sweep_impl("spllt_hip_factor_adjoint", fkeep, gval_host, false);
+}
+
+int spllt_hip_release_factor_adjoint(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  if (!f->eng || f->dead) return 0;
+  if (f->eng->pending()) do_wait(f);
+  int rc = f->eng->release_factor_adjoint();
+  return rc ? feature_fail(f, rc) : 0;
+}
+
 int spllt_hip_factor_times(void* fkeep, double* submit_ms, double* device_ms, double* h2d_ms, int* launches) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->eng) return SPLLT_ERROR_PARAMETER;

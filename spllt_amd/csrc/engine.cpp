@@ -1244,6 +1244,7 @@ int Engine::factor_async_dev(const double* val_dev, int64_t nnz) {
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
   z_valid_ = false;
+  fadj_state_ = FADJ_UNSEEDED;
   factored_ = true;
   ud_invalid_ = false;
   double t0 = now_ms();
@@ -1274,6 +1275,7 @@ int Engine::factor_async(const double* val_host, int64_t nnz) {
   if (status_) return status_;
   if (nnz != S_->nnzA) return -10;
   z_valid_ = false;
+  fadj_state_ = FADJ_UNSEEDED;
   factored_ = true;
   ud_invalid_ = false;
   double t0 = now_ms();
@@ -1493,19 +1495,178 @@ int Engine::release_inverse() {
     HIPCHK(hipSetDevice(device_), "hipSetDevice");
     if (int rc = sync_stream(stream_, "selinv release")) return rc;
     release_buffer(d_Z_);
-    release_buffer(d_siscratch_);
+    if (!d_G_) release_buffer(d_siscratch_);   // (the factor adjoint shares the scratch)
     if (d_sipat_) release_buffer(d_sipat_);
-    d_Z_ = d_siscratch_ = d_sipat_ = nullptr;
+    d_Z_ = d_sipat_ = nullptr;
+    if (!d_G_) d_siscratch_ = nullptr;
+  }
+  return 0;
+}
+
+// ---- reverse-mode derivative of the factor ---------------------------------------------------------
+int Engine::prepare_fadj() {
+  int rc = prepare_selinv();
+  if (rc) return rc;
+  const Symbolic& S = *S_;
+  if (!d_fadj_tables_) {
+    std::vector<FadjCol> cols((size_t)S.nbcol());
+    std::vector<UpdTile> tiles;
+    for (int b = 0; b < S.nbcol(); ++b) {
+      const BlockCol& bc = S.bcols[(size_t)b];
+      cols[(size_t)b] = FadjCol{bc.off, S.rptr[(size_t)bc.node] + bc.r0, bc.width, bc.nrow, S.sptr[(size_t)bc.node] + bc.r0, 0};
+      for (int t = 0; t * kSelinvTile < bc.nrow; ++t) tiles.push_back(UpdTile{b, (short)t, 0});
+    }
+    TableStager tab;
+    tab.add(&d_facols_, cols);
+    tab.add(&d_fatiles_, tiles);
+    tab.add(&d_faporder_, S.porder);
+    hipError_t e = tab.commit(&d_fadj_tables_, [this](void** q, size_t b) { return dalloc(q, b); });
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      if (d_fadj_tables_) { release_buffer(d_fadj_tables_); d_fadj_tables_ = nullptr; }
+      feature_err_ = std::string("factor adjoint: not enough device memory for the seed tables (") + hipGetErrorString(e) + ")";
+      return alloc_code(e);
+    }
+    fa_ntiles_ = (int64_t)tiles.size();
+  }
+  if (!d_G_ || !d_siscratch_) {
+    const size_t gb = sizeof(double) * (size_t)std::max<int64_t>(1, S.arena);
+    const size_t sb = sizeof(double) * (size_t)std::max<int64_t>(1, siprog_.scratch_size);
+    const bool had_g = d_G_ != nullptr;
+    hipError_t e = d_G_ ? hipSuccess : dalloc((void**)&d_G_, gb);
+    if (e == hipSuccess && !d_siscratch_) e = dalloc((void**)&d_siscratch_, sb);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      if (d_G_ && !had_g) { release_buffer(d_G_); d_G_ = nullptr; fadj_state_ = FADJ_UNSEEDED; }
+      feature_err_ = "factor adjoint: not enough device memory for the adjoint arena (" + std::to_string(gb >> 20) +
+                     " MiB) and the scratch (" + std::to_string(sb >> 20) + " MiB)";
+      return -1;
+    }
+  }
+  return 0;
+}
+
+int Engine::fadj_seed(int nvec, const double* a, const double* b, int64_t ld, double alpha, bool accumulate,
+                      int order_flags, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (pending_ || !a || !b || nvec < 0 || ld < S_->n || opt_.nranks > 1) return -10;
+  if (accumulate && fadj_state_ != FADJ_SEEDED) {
+    feature_err_ = "factor adjoint: accumulate = 1 needs a seeded adjoint arena of the current factor (this one is " +
+                   std::string(fadj_state_ == FADJ_SWEPT ? "swept" : "unseeded or stale") + ")";
+    return -10;
+  }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_fadj();
+  if (rc) return rc;
+  const int n = S_->n;
+  double* stage = nullptr;
+  const double *ad = a, *bd = b;
+  int64_t ldd = ld;
+  if (!dev && nvec > 0 && n > 0) {
+    hipError_t e = dalloc((void**)&stage, sizeof(double) * 2 * (size_t)nvec * (size_t)n);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      feature_err_ = std::string("factor adjoint: not enough device memory to stage the seed vectors (") + hipGetErrorString(e) + ")";
+      return alloc_code(e);
+    }
+    if ((rc = copy_vectors(true, stage, const_cast<double*>(a), ld, nvec, "seed H2D"))) return rc;
+    if ((rc = copy_vectors(true, stage + (int64_t)nvec * n, const_cast<double*>(b), ld, nvec, "seed H2D"))) return rc;
+    ad = stage;
+    bd = stage + (int64_t)nvec * n;
+    ldd = n;
+  }
+  if (!accumulate) fadj_state_ = FADJ_UNSEEDED;
+  launch_fadj_seed(stream_, d_fatiles_, fa_ntiles_, d_facols_, d_rlist_, d_faporder_, d_G_, nvec, ad, bd, ldd, alpha,
+                   accumulate, order_flags);
+  HIPCHK(hipGetLastError(), "factor adjoint seed launch");
+  rc = sync_stream(stream_, "factor adjoint seed sync");
+  if (stage && !rc) release_buffer(stage);
+  if (rc) return rc;
+  fadj_state_ = FADJ_SEEDED;
+  return 0;
+}
+
+int Engine::fadj_upload(const double* host_arena, int64_t count) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (pending_ || !host_arena || count < S_->arena || opt_.nranks > 1) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_fadj();
+  if (rc) return rc;
+  fadj_state_ = FADJ_UNSEEDED;
+  if (S_->arena > 0)
+    HIPCHK(hipMemcpyAsync(d_G_, host_arena, sizeof(double) * (size_t)S_->arena, hipMemcpyHostToDevice, stream_), "adjoint H2D");
+  if ((rc = sync_stream(stream_, "factor adjoint upload sync"))) return rc;
+  fadj_state_ = FADJ_SEEDED;
+  return 0;
+}
+
+int Engine::fadj_download(double* out, int64_t count) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (fadj_state_ == FADJ_UNSEEDED || !out) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  return staged_d2h(out, d_G_, sizeof(double) * (size_t)std::min<int64_t>(count, S_->arena));
+}
+
+int Engine::fadj_sweep(double* gval, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (pending_ || !gval || opt_.nranks > 1) return -10;
+  if (fadj_state_ != FADJ_SEEDED) {
+    feature_err_ = "factor adjoint: the sweep needs a freshly seeded adjoint arena of the current factor (this one is " +
+                   std::string(fadj_state_ == FADJ_SWEPT ? "already swept" : "unseeded or stale") + ")";
+    return -10;
+  }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_fadj();
+  if (rc) return rc;
+  const int64_t nnz = S_->nnzA;
+  if (!dev && !d_gpat_ && nnz > 0) {
+    hipError_t e = dalloc((void**)&d_gpat_, sizeof(double) * (size_t)nnz);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      d_gpat_ = nullptr;
+      feature_err_ = std::string("factor adjoint: not enough device memory for the gathered gradient (") + hipGetErrorString(e) + ")";
+      return alloc_code(e);
+    }
+  }
+  fadj_state_ = FADJ_UNSEEDED;   // (a sweep that fails half way leaves nothing to read)
+  for (const SelinvLaunch& l : siprog_.launches)
+    launch_fadj(stream_, l, d_siunits_, d_sitiles_, d_sirows_, d_sirelpos_, d_L_, d_dinv_, d_G_, d_siscratch_);
+  HIPCHK(hipGetLastError(), "factor adjoint launch");
+  if (nnz > 0) {
+    if ((rc = gather_inverse_on_pattern(dev ? gval : d_gpat_, d_G_))) return rc;
+    if (!dev && (rc = staged_d2h(gval, d_gpat_, sizeof(double) * (size_t)nnz))) return rc;
+  } else if ((rc = sync_stream(stream_, "factor adjoint sync"))) {
+    return rc;
+  }
+  fadj_state_ = FADJ_SWEPT;
+  return 0;
+}
+
+int Engine::release_factor_adjoint() {
+  feature_err_.clear();
+  if (status_) return status_;
+  fadj_state_ = FADJ_UNSEEDED;
+  if (d_G_) {
+    HIPCHK(hipSetDevice(device_), "hipSetDevice");
+    if (int rc = sync_stream(stream_, "factor adjoint release")) return rc;
+    release_buffer(d_G_);
+    d_G_ = nullptr;
+    if (d_gpat_) { release_buffer(d_gpat_); d_gpat_ = nullptr; }
+    if (!d_Z_ && d_siscratch_) { release_buffer(d_siscratch_); d_siscratch_ = nullptr; }
   }
   return 0;
 }
 
 // A^-1 at the entries of the analysed pattern into nnz doubles of device memory: the gather kernel of the
 // batched inversion with one member, enqueued on stream_ (what both readers below share)
-int Engine::gather_inverse_on_pattern(double* out_dev) {
+int Engine::gather_inverse_on_pattern(double* out_dev, double* arena) {
   BatchSelinvView v{};   // one member, known to be valid: no flag
   v.v.nbatch = 1;
-  v.Z = d_Z_;
+  v.Z = arena ? arena : d_Z_;
   if (launch_batch_selinv_pattern(stream_, v, d_map_dst_, d_map_src_, nmap_, out_dev, S_->nnzA) < 0) {
     feature_err_ = "inverse on pattern: the pattern has more entries than a grid holds work items";
     return -99;
@@ -1725,6 +1886,7 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   release_buffer(d_val);
   release_buffer(d_pos);
   z_valid_ = false;
+  fadj_state_ = FADJ_UNSEEDED;
   if (le != hipSuccess || rc) {
     // the sweep did not finish: the arena is half modified and the work array may not be zero
     ud_invalid_ = true;
@@ -2273,6 +2435,7 @@ int Engine::profile_launches(const double* val_host, int64_t nnz, std::vector<fl
   if (nnz != S_->nnzA) return -10;
   if (!prog_.exchanges.empty()) return -98;   // single-GPU programs only
   z_valid_ = false;                           // (L is factored again from val)
+  fadj_state_ = FADJ_UNSEEDED;
   const Symbolic& S = *S_;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipMemcpy(d_val_, val_host, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice), "val H2D");
@@ -2317,6 +2480,7 @@ int Engine::timeline(const double* val_host, int64_t nnz, std::vector<float>& t)
   if (nnz != S_->nnzA) return -10;
   if (!prog_.exchanges.empty()) return -98;   // single-GPU programs only
   z_valid_ = false;                           // (L is factored again from val)
+  fadj_state_ = FADJ_UNSEEDED;
   const Symbolic& S = *S_;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   HIPCHK(hipMemcpy(d_val_, val_host, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice), "val H2D");

@@ -244,6 +244,23 @@ class Engine {
   int pattern_outer(int nbatch, int nvec, const double* u, int64_t ldu, const double* v, int64_t ldv, double alpha,
                     double* out, int64_t ldout, bool dev);
   double* device_Z() { return z_valid_ ? d_Z_ : nullptr; }
+  // ---- reverse-mode derivative of the factor (factor_adjoint.hip, single GPU): G, a third arena with L's
+  // layout, holds d loss / d L (seeded or uploaded), and after the sweep d loss / d (P A P^T) on every stored
+  // lower position.  The sweep runs siprog_ (the tables and the scratch are shared with the selected inverse).
+  // G is taken on first use and kept until release_factor_adjoint; a factorization or an update of the factor
+  // makes it unseeded again.  Every check happens before anything is enqueued; every call returns with the
+  // stream drained.
+  enum FadjState : int { FADJ_UNSEEDED = 0, FADJ_SEEDED = 1, FADJ_SWEPT = 2 };
+  int fadj_state() const { return fadj_state_; }
+  // G (+)= alpha sum_q a_q b_q^T on the lower positions; vector q at a + q * ld; order_flags bit 0 / 1: a / b is in
+  // pivot order (else user order); dev: device pointers
+  int fadj_seed(int nvec, const double* a, const double* b, int64_t ld, double alpha, bool accumulate, int order_flags,
+                bool dev);
+  int fadj_upload(const double* host_arena, int64_t count);   // an arbitrary seed, the layout of download()
+  int fadj_download(double* out, int64_t count);
+  int fadj_sweep(double* gval, bool dev);                     // gval: nnz doubles in the order of val
+  double* device_G() { return fadj_state_ != FADJ_UNSEEDED ? d_G_ : nullptr; }
+  int release_factor_adjoint();
   const SelinvProgram& selinv_program() const { return siprog_; }
   // ---- batched factorization (batch.hip, single GPU): nbatch value sets on this pattern, factorized and
   // solved together by a second program of the same Symbolic (build_batch_program) whose every launch
@@ -533,7 +550,17 @@ class Engine {
   double* d_siscratch_ = nullptr;
   double* d_siout_ = nullptr;      // n + 1 doubles: diag(A^-1), log det
   double* d_sipat_ = nullptr;      // nnz doubles: A^-1 on the analysed pattern (inverse_on_pattern)
-  int gather_inverse_on_pattern(double* out_dev);
+  int gather_inverse_on_pattern(double* out_dev, double* arena = nullptr);   // arena: null = d_Z_
+  // factor adjoint: the arena, the (block column, strip) tiles of the seed kernel and the position -> variable table
+  int prepare_fadj();
+  int fadj_state_ = FADJ_UNSEEDED;
+  double* d_G_ = nullptr;
+  double* d_gpat_ = nullptr;       // nnz doubles: the gradient on the analysed pattern (host entry point)
+  char* d_fadj_tables_ = nullptr;
+  FadjCol* d_facols_ = nullptr;
+  UpdTile* d_fatiles_ = nullptr;
+  int* d_faporder_ = nullptr;
+  int64_t fa_ntiles_ = 0;
   // sampled outer product: the (row, column) tables of the pattern (one allocation, on first use) and the
   // staging block of the host entry point
   char* d_potab_ = nullptr;

@@ -129,6 +129,29 @@ void launch_ss_gram_reduce(hipStream_t st, const double* part, int nchunk, int n
 void launch_selinv(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* units, const UpdTile* tiles,
                    const SelinvRow* rows, const int* relpos, const double* L, const double* dinv, double* Z,
                    double* scratch);
+// the SI_SYMM launch with the diagonal of the gathered symmetric block doubled (the factor adjoint)
+void launch_selinv_symm_doubled(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* units, const UpdTile* tiles,
+                                const SelinvRow* rows, const int* relpos, const double* L, const double* G,
+                                double* scratch);
+// ---- reverse-mode derivative of the factor (factor_adjoint.hip) --------------------------------------
+// a block column for k_fadj_seed: rows rlist[idx_off ..], columns the pivot positions gcol0 .. gcol0 + w - 1
+struct FadjCol {
+  int64_t off;       // arena offset of the block column
+  int64_t idx_off;   // offset into rlist[] of its first row
+  int w, nrow;
+  int gcol0;
+  int pad_;
+};
+// G[lower position (r_i, c_j)] = (accumulate ? G : 0) + alpha sum_q a[q ld + x(r_i)] b[q ld + x(c_j)], one fma
+// chain per entry in ascending q; x(p) = p for a vector in pivot order (order_flags bit 0: a, bit 1: b), else
+// porder[p].  tiles: (block column, 64-row strip) pairs (UpdTile: unit, ti)
+void launch_fadj_seed(hipStream_t st, const UpdTile* tiles, int64_t ntiles, const FadjCol* cols, const int* rlist,
+                      const int* porder, double* G, int nvec, const double* a, const double* b, int64_t ld, double alpha,
+                      bool accumulate, int order_flags);
+// one launch of the SelinvProgram on the adjoint arena G (arguments as launch_selinv)
+void launch_fadj(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* units, const UpdTile* tiles,
+                 const SelinvRow* rows, const int* relpos, const double* L, const double* dinv, double* G,
+                 double* scratch);
 // out[v] = Z[diag_pos[order[v]]]  (diag(A^-1) in the user's variable order)
 void launch_selinv_diag_gather(hipStream_t st, const double* Z, const int64_t* diag_pos, const int* order, int n,
                                double* out);

@@ -29,6 +29,10 @@ constexpr int SI_T = kSelinvTile;   // 64
 // rows 16 w .. 16 w + 15 of the tile and all (<= 64) columns.  Lane l supplies A[l&15][l>>4] and
 // B[l>>4][l&15] and receives C[(l>>4) + 4 r][l&15] in register r.
 // ---------------------------------------------------------------------------
+// kDoubleDiag: the gathered block is S = tril(G_RR) + tril(G_RR)^T of the factor adjoint (factor_adjoint.hip),
+// whose diagonal counts twice; a diagonal entry occurs in the generic branch only (r_i == r_k), the two
+// dense-path branches hold chunks strictly above or below the tile.  Selected inversion instantiates false.
+template <bool kDoubleDiag>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_selinv_symm(const UpdTile* __restrict__ tiles, const SelinvUnit* __restrict__ units,
                                                      const SelinvRow* __restrict__ rows, const int* __restrict__ relpos,
                                                      const double* __restrict__ L, const double* __restrict__ Z,
@@ -116,6 +120,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           const int a = ri >= rk ? ri : rk, b = ri >= rk ? rk : ri;
           const int64_t qpos = d.map < 0 ? (int64_t)a : (int64_t)relpos[(int64_t)d.map + a - b];
           v = Z[d.cbase + qpos * d.ld];
+          if (kDoubleDiag && ri == rk) v += v;
         }
         ra[q] = v;
       }
@@ -279,11 +284,19 @@ void launch_selinv(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* unit
   if (l.count <= 0) return;
   const dim3 grid((unsigned)l.count), block(256);
   if (l.kind == SI_SYMM)
-    hipLaunchKernelGGL(k_selinv_symm, grid, block, 0, st, tiles + l.first, units, rows, relpos, L, (const double*)Z, scratch);
+    hipLaunchKernelGGL(k_selinv_symm<false>, grid, block, 0, st, tiles + l.first, units, rows, relpos, L, (const double*)Z, scratch);
   else if (l.kind == SI_SCALE)
     hipLaunchKernelGGL(k_selinv_scale, grid, block, 0, st, tiles + l.first, units, L, dinv, Z, scratch);
   else
     hipLaunchKernelGGL(k_selinv_diag, grid, dim3(1024), 0, st, units + l.first, dinv, Z, (const double*)scratch);
+}
+
+void launch_selinv_symm_doubled(hipStream_t st, const SelinvLaunch& l, const SelinvUnit* units, const UpdTile* tiles,
+                                const SelinvRow* rows, const int* relpos, const double* L, const double* G,
+                                double* scratch) {
+  if (l.count <= 0 || l.kind != SI_SYMM) return;
+  hipLaunchKernelGGL(k_selinv_symm<true>, dim3((unsigned)l.count), dim3(256), 0, st, tiles + l.first, units, rows, relpos,
+                     L, G, scratch);
 }
 
 void launch_selinv_diag_gather(hipStream_t st, const double* Z, const int64_t* diag_pos, const int* order, int n,

@@ -1,17 +1,25 @@
-"""PyTorch front end: differentiable sparse SPD solve and log-determinant on the GPU.
+"""PyTorch front end: differentiable sparse SPD solve, log-determinant, factor products and sampling on the GPU.
 
-``SparseCholesky`` owns one analysed pattern (an ``api.Factorization``) and offers ``solve``, ``logdet`` and their
-batched twins as ``torch.autograd.Function``s over device tensors.  Nothing is computed here: the factorization,
-the solves, the selected inverse and the sampled outer product of the backward pass are the library's HIP kernels,
-called on the tensors' own memory.
+``SparseCholesky`` owns one analysed pattern (an ``api.Factorization``) and offers ``solve``, ``logdet``, their
+batched twins, ``factor_apply`` (L, L^T, L^-1, L^-T times a block of vectors) and ``rsample`` (reparameterised
+Gaussian draws) as ``torch.autograd.Function``s over device tensors.  Nothing is computed here: the factorization,
+the solves, the selected inverse, the sampled outer product and the adjoint of the factor of the backward passes
+are the library's HIP kernels, called on the tensors' own memory (DESIGN.md sections 17 and 19).
 
 Convention: ``val[k]`` is the k-th stored value of the CSC lower triangle and stands for BOTH a_ij and a_ji, so
 
     d loss / d val[k] = -(lam_i x_j + [i != j] lam_j x_i)      for x = A^-1 b,  lam = A^-1 xbar
     d logdet / d val[k] = (2 - delta_ij) (A^-1)_ij
 
-Out of scope: CPU tensors, float32, partitioned handles, sparse right-hand sides, second derivatives, gradients of
-samples with respect to the matrix values.
+The factor itself is differentiated by one sweep (spllt_hip_factor_adjoint): with all vectors in pivot order
+
+    y = L x: Lbar = ybar x^T        y = L^-1 x: Lbar = -(L^-T ybar) y^T
+    y = L^T x: Lbar = x ybar^T      y = L^-T x: Lbar = -y (L^-1 ybar)^T
+
+restricted to the pattern of L, any number of columns in ONE sweep (the map Lbar -> d loss / d val is linear).
+
+Out of scope: CPU tensors, float32, partitioned handles, sparse right-hand sides, second derivatives, gradients
+through the batch's factors; ``sample`` stays without a gradient to the matrix values (``rsample`` has it).
 """
 import weakref
 
@@ -266,6 +274,61 @@ class SparseCholesky:
         x = work.t()
         return x if mean is None else x + mean[:, None]
 
+    # ---- operations with the factor in the graph ------------------------------------------------------
+    def _factor_op_inplace(self, work, op):
+        """work: (nvec, n) contiguous, overwritten with op(L) applied to every vector (user layout)"""
+        self._sync()
+        with torch.cuda.device(self.device):
+            job = 1 if op in ("L", "Linv") else 2
+            if op in ("L", "Lt"):
+                self.f.factor_mult_dev(work.data_ptr(), work.shape[0], ldx=self.n, job=job)
+            elif self.reproducible:
+                self.f.solve_reproducible_dev(work.data_ptr(), work.shape[0], ldx=self.n, job=job)
+            else:
+                self.f.solve_many_dev(work.data_ptr(), work.shape[0], ldx=self.n, job=job)
+        return work
+
+    def _factor_adjoint(self, a, b, alpha, b_pivot_order=False):
+        """a, b: (nvec, n) contiguous -> d/dval of the seed alpha sum_q a_q b_q^T, (nnz,): seed passes of 32 vectors,
+        one sweep, the reader"""
+        nvec, step = a.shape[0], 32
+        if nvec == 0:
+            return torch.zeros(self.nnz, dtype=torch.float64, device=self.device)
+        out = torch.empty(self.nnz, dtype=torch.float64, device=self.device)
+        self._sync()
+        with torch.cuda.device(self.device):
+            for q in range(0, nvec, step):
+                self.f.factor_adjoint_seed_dev(a[q:].data_ptr(), b[q:].data_ptr(), min(step, nvec - q), ld=self.n,
+                                               alpha=alpha, accumulate=q > 0, b_pivot_order=b_pivot_order)
+            self.f.factor_adjoint_dev(out.data_ptr())
+        return out
+
+    _FACTOR_OPS = ("L", "Lt", "Linv", "Ltinv")
+
+    def factor_apply(self, val, X, op):
+        """Y = op(L) X for the Cholesky factor P A(val) P^T = L L^T; op: "L", "Lt", "Linv", "Ltinv".  X: (n,) or
+        (n, nvec), a pivot-order vector laid out in user positions as Factorization.factor_mult (job 1, 2) and
+        solve_many (job 1, 2) take and leave it.  Differentiable in val and X; the backward pass is one library call
+        for the gradient of X, then the seed, ONE sweep of the factor's adjoint and its reader for val."""
+        if op not in self._FACTOR_OPS:
+            raise ValueError(f"op: expected one of {self._FACTOR_OPS}, got {op!r}")
+        self._values(val, "val", (self.nnz,))
+        self._rhs(X, "X", val.device)
+        self._enter(val)
+        return _FactorApply.apply(self, val, X, op)
+
+    def rsample(self, val, nsamp, seed=0, kind="precision", mean=None):
+        """``sample`` with the pathwise gradient: the same bits forward, differentiable in val and mean.  The noise is
+        not kept: the backward pass draws it again (covariance) or does not need it (precision)."""
+        self._values(val, "val", (self.nnz,))
+        if mean is not None:
+            self._tensor(mean, "mean", (self.n,), val.device)
+        if kind not in ("precision", "covariance"):
+            raise ValueError(f"kind: expected 'precision' or 'covariance', got {kind!r}")
+        self._enter(val)
+        x = _RSample.apply(self, val, int(nsamp), int(seed), kind)
+        return x if mean is None else x + mean[:, None]
+
     def close(self):
         self.f.close()
 
@@ -295,6 +358,86 @@ class _Solve(torch.autograd.Function):
         lam = chol._solve_inplace(_to_vectors(grad))
         gval = chol._outer(lam, xt, -1.0) if ctx.needs_input_grad[1] else None
         return None, gval, (lam.view(-1) if ctx.vector else lam.t())
+
+
+class _FactorApply(torch.autograd.Function):
+    """Y = op(L) X; the table of the module docstring"""
+    _ADJOINT = {"L": "Lt", "Lt": "L", "Linv": "Ltinv", "Ltinv": "Linv"}
+
+    @staticmethod
+    def forward(ctx, chol, val, X, op):
+        ctx.chol, ctx.op = chol, op
+        ctx.serial = chol._ensure_factor(val)
+        work = chol._factor_op_inplace(_to_vectors(X), op)
+        ctx.vector = X.dim() == 1
+        # the products need their input, the solves their output
+        ctx.save_for_backward(val, _to_vectors(X) if op in ("L", "Lt") else work)
+        return work.view(-1) if ctx.vector else work.t()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol, op = ctx.chol, ctx.op
+        val, kept = ctx.saved_tensors
+        if chol.f.factor_serial(0) != ctx.serial:       # another matrix was factorized in between
+            chol._ensure_factor(val)
+        gt = _to_vectors(grad)
+        xbar = chol._factor_op_inplace(gt.clone(), _FactorApply._ADJOINT[op])
+        gval = None
+        if ctx.needs_input_grad[1]:
+            if op == "L":
+                gval = chol._factor_adjoint(gt, kept, 1.0)
+            elif op == "Lt":
+                gval = chol._factor_adjoint(kept, gt, 1.0)
+            elif op == "Linv":
+                gval = chol._factor_adjoint(xbar, kept, -1.0)
+            else:
+                gval = chol._factor_adjoint(kept, xbar, -1.0)
+        return None, gval, (xbar.view(-1) if ctx.vector else xbar.t()), None
+
+
+class _RSample(torch.autograd.Function):
+    """x = P^T L^-T z (precision) or P^T L z (covariance), z the white noise of (seed, sample); the mean is added
+    outside (its gradient is autograd's)"""
+
+    @staticmethod
+    def forward(ctx, chol, val, nsamp, seed, kind):
+        ctx.chol, ctx.nsamp, ctx.seed, ctx.kind = chol, nsamp, seed, kind
+        ctx.serial = chol._ensure_factor(val)
+        work = torch.empty((nsamp, chol.n), dtype=torch.float64, device=chol.device)
+        chol._sync()
+        with torch.cuda.device(chol.device):
+            before = chol.f.set_reproducible_solve(chol.reproducible)
+            try:
+                chol.f.sample_dev(work.data_ptr(), nsamp, ldx=chol.n, seed=seed, kind=kind)
+            finally:
+                chol.f.set_reproducible_solve(before)
+        if kind == "precision":
+            ctx.save_for_backward(val, work)
+        else:
+            ctx.save_for_backward(val)
+        return work.t()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol = ctx.chol
+        val = ctx.saved_tensors[0]
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        if chol.f.factor_serial(0) != ctx.serial:
+            chol._ensure_factor(val)
+        gt = _to_vectors(grad)
+        if ctx.kind == "precision":      # y = L^-T z: Lbar = -y (L^-1 ybar)^T
+            u = chol._factor_op_inplace(gt, "Linv")
+            gval = chol._factor_adjoint(ctx.saved_tensors[1], u, -1.0)
+        else:                            # y = L z: Lbar = ybar z^T, z in pivot order as white_noise_dev writes it
+            z = torch.empty((max(ctx.nsamp, 1), chol.n), dtype=torch.float64, device=chol.device)
+            chol._sync()
+            with torch.cuda.device(chol.device):
+                chol.f.white_noise_dev(z.data_ptr(), ctx.nsamp, ldz=chol.n, seed=ctx.seed)
+            gval = chol._factor_adjoint(gt, z[:ctx.nsamp], 1.0, b_pivot_order=True)
+        return None, gval, None, None, None
 
 
 class _LogDet(torch.autograd.Function):
