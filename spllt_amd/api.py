@@ -274,9 +274,7 @@ class Factorization:
         if out is None:
             out = np.zeros(max(arena, 1), dtype=np.float64)
         assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
-        rc = self.lib.spllt_hip_get_factor(self.fkeep, _dp(out), arena)
-        if rc < 0:
-            raise SplltError("spllt_hip_get_factor", rc, self.last_error())
+        self._call("spllt_hip_get_factor", self.fkeep, _dp(out), arena)
         return out[:arena]
 
     def device_factor_ptr(self):
@@ -285,9 +283,7 @@ class Factorization:
     # ---- selected inversion ---------------------------------------------------
     def selected_inverse(self):
         """spllt_hip_selected_inverse: Z = (P A P^T)^-1 on the pattern of L, on the device"""
-        rc = self.lib.spllt_hip_selected_inverse(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_selected_inverse", rc, self.last_error())
+        self._call("spllt_hip_selected_inverse", self.fkeep)
         return self
 
     def get_inverse(self, out=None):
@@ -296,9 +292,7 @@ class Factorization:
         if out is None:
             out = np.zeros(max(arena, 1), dtype=np.float64)
         assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
-        rc = self.lib.spllt_hip_get_inverse(self.fkeep, _dp(out), arena)
-        if rc < 0:
-            raise SplltError("spllt_hip_get_inverse", rc, self.last_error())
+        self._call("spllt_hip_get_inverse", self.fkeep, _dp(out), arena)
         return out[:arena]
 
     def device_inverse_ptr(self):
@@ -307,32 +301,24 @@ class Factorization:
     def inverse_diag(self):
         """(A^-1)_ii in the user's variable order"""
         out = np.zeros(max(self.n, 1), dtype=np.float64)
-        rc = self.lib.spllt_hip_inverse_diag(self.fkeep, _dp(out), self.n)
-        if rc < 0:
-            raise SplltError("spllt_hip_inverse_diag", rc, self.last_error())
+        self._call("spllt_hip_inverse_diag", self.fkeep, _dp(out), self.n)
         return out[:self.n]
 
     def log_det(self):
         """log det A of the last factorization (2 sum log L_jj)"""
         v = C.c_double()
-        rc = self.lib.spllt_hip_log_det(self.fkeep, C.byref(v))
-        if rc < 0:
-            raise SplltError("spllt_hip_log_det", rc, self.last_error())
+        self._call("spllt_hip_log_det", self.fkeep, C.byref(v))
         return v.value
 
     def inverse_on_pattern(self):
         """(A^-1) at the entries of the analysed CSC-lower pattern, nnz values in the order of val"""
         out = np.zeros(max(self.nnz, 1), dtype=np.float64)
-        rc = self.lib.spllt_hip_inverse_on_pattern(self.fkeep, _dp(out))
-        if rc < 0:
-            raise SplltError("spllt_hip_inverse_on_pattern", rc, self.last_error())
+        self._call("spllt_hip_inverse_on_pattern", self.fkeep, _dp(out))
         return out[:self.nnz]
 
     def inverse_on_pattern_dev(self, out_dev_ptr):
         """spllt_hip_inverse_on_pattern_dev: the same nnz values into device memory (integer device pointer)"""
-        rc = self.lib.spllt_hip_inverse_on_pattern_dev(self.fkeep, C.c_void_p(out_dev_ptr))
-        if rc < 0:
-            raise SplltError("spllt_hip_inverse_on_pattern_dev", rc, self.last_error())
+        self._call("spllt_hip_inverse_on_pattern_dev", self.fkeep, C.c_void_p(out_dev_ptr))
         return self
 
     def factor_serial(self, which=0):
@@ -354,38 +340,30 @@ class Factorization:
         if u.shape != v.shape:
             raise ValueError("pattern_outer: u and v must have the same shape")
         out = np.zeros(max(self.nnz, 1), dtype=np.float64)
-        rc = self.lib.spllt_hip_pattern_outer(self.fkeep, u.shape[1], _dp(u), max(self.n, 1), _dp(v), max(self.n, 1),
-                                              float(alpha), _dp(out))
-        if rc < 0:
-            raise SplltError("spllt_hip_pattern_outer", rc, self.last_error())
+        self._call("spllt_hip_pattern_outer", self.fkeep, u.shape[1], _dp(u), max(self.n, 1), _dp(v), max(self.n, 1),
+                   float(alpha), _dp(out))
         return out[:self.nnz]
 
     def pattern_outer_dev(self, u_dev_ptr, v_dev_ptr, nvec, out_dev_ptr, ldu=None, ldv=None, alpha=1.0):
         """spllt_hip_pattern_outer_dev: device vectors (vector q at u[q*ldu .. + n), ld defaults to n), nnz
         doubles written at out_dev_ptr"""
-        rc = self.lib.spllt_hip_pattern_outer_dev(self.fkeep, int(nvec), C.c_void_p(u_dev_ptr),
-                                                  int(self.n if ldu is None else ldu), C.c_void_p(v_dev_ptr),
-                                                  int(self.n if ldv is None else ldv), float(alpha),
-                                                  C.c_void_p(out_dev_ptr))
-        if rc < 0:
-            raise SplltError("spllt_hip_pattern_outer_dev", rc, self.last_error())
+        self._call("spllt_hip_pattern_outer_dev", self.fkeep, int(nvec), C.c_void_p(u_dev_ptr),
+                   int(self.n if ldu is None else ldu), C.c_void_p(v_dev_ptr),
+                   int(self.n if ldv is None else ldv), float(alpha),
+                   C.c_void_p(out_dev_ptr))
         return self
 
     def pattern_outer_batch_dev(self, u_dev_ptr, v_dev_ptr, nbatch, nvec, out_dev_ptr, ldu=None, ldv=None, ldout=None,
                                 alpha=1.0):
         """spllt_hip_pattern_outer_batch_dev: vector q of member b at u[(b*nvec + q)*ldu ..], out[b*ldout + k]"""
-        rc = self.lib.spllt_hip_pattern_outer_batch_dev(self.fkeep, int(nbatch), int(nvec), C.c_void_p(u_dev_ptr),
-                                                        int(self.n if ldu is None else ldu), C.c_void_p(v_dev_ptr),
-                                                        int(self.n if ldv is None else ldv), float(alpha),
-                                                        C.c_void_p(out_dev_ptr), int(self.nnz if ldout is None else ldout))
-        if rc < 0:
-            raise SplltError("spllt_hip_pattern_outer_batch_dev", rc, self.last_error())
+        self._call("spllt_hip_pattern_outer_batch_dev", self.fkeep, int(nbatch), int(nvec), C.c_void_p(u_dev_ptr),
+                   int(self.n if ldu is None else ldu), C.c_void_p(v_dev_ptr),
+                   int(self.n if ldv is None else ldv), float(alpha),
+                   C.c_void_p(out_dev_ptr), int(self.nnz if ldout is None else ldout))
         return self
 
     def release_inverse(self):
-        rc = self.lib.spllt_hip_release_inverse(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_inverse", rc, self.last_error())
+        self._call("spllt_hip_release_inverse", self.fkeep)
 
     def inverse_entries(self, i, j, Z=None):
         """(A^-1)_{ij} for 0-based user indices i, j (scalars or arrays) whose pivot pair lies in the
@@ -442,9 +420,7 @@ class Factorization:
     def solve_dev(self, y_dev_ptr, nrhs=1, job=0, phase=-1):
         """spllt_hip_solve_dev: substitution on device vectors in pivot order
         (y[q*n + p(i)] = b_q[i], p = 0-based pivot position ("order" of spllt_hip_sym_get)), in place; phase 0/1/2 on a partitioned factor."""
-        rc = self.lib.spllt_hip_solve_dev(self.fkeep, C.c_void_p(y_dev_ptr), nrhs, job, phase)
-        if rc < 0:
-            raise SplltError("spllt_hip_solve_dev", rc, self.last_error())
+        self._call("spllt_hip_solve_dev", self.fkeep, C.c_void_p(y_dev_ptr), nrhs, job, phase)
         return self
 
     def solve_many(self, b, job=0):
@@ -453,9 +429,7 @@ class Factorization:
         x = np.array(b, dtype=np.float64, order="F", copy=True)
         nrhs = 1 if x.ndim == 1 else x.shape[1]
         ldx = x.shape[0]
-        rc = self.lib.spllt_hip_solve_many(self.fkeep, nrhs, _dp(x), ldx, job)
-        if rc < 0:
-            raise SplltError("spllt_hip_solve_many", rc, self.last_error())
+        self._call("spllt_hip_solve_many", self.fkeep, nrhs, _dp(x), ldx, job)
         return x
 
     def solve_many_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
@@ -464,10 +438,8 @@ class Factorization:
         solve_dev, else in the user's variable order."""
         if ldx is None:
             ldx = self.n
-        rc = self.lib.spllt_hip_solve_many_dev(self.fkeep, nrhs, C.c_void_p(x_dev_ptr), int(ldx), job,
-                                               1 if pivot_order else 0)
-        if rc < 0:
-            raise SplltError("spllt_hip_solve_many_dev", rc, self.last_error())
+        self._call("spllt_hip_solve_many_dev", self.fkeep, nrhs, C.c_void_p(x_dev_ptr), int(ldx), job,
+                   1 if pivot_order else 0)
         return self
 
     # ---- reproducible solve ----------------------------------------------------
@@ -478,9 +450,7 @@ class Factorization:
         x = np.array(b, dtype=np.float64, order="F", copy=True)
         nrhs = 1 if x.ndim == 1 else x.shape[1]
         ldx = x.shape[0]
-        rc = self.lib.spllt_hip_solve_repro(self.fkeep, nrhs, _dp(x), ldx, job)
-        if rc < 0:
-            raise SplltError("spllt_hip_solve_repro", rc, self.last_error())
+        self._call("spllt_hip_solve_repro", self.fkeep, nrhs, _dp(x), ldx, job)
         return x
 
     def solve_reproducible_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
@@ -488,25 +458,19 @@ class Factorization:
         pivot_order as solve_many_dev)."""
         if ldx is None:
             ldx = self.n
-        rc = self.lib.spllt_hip_solve_repro_dev(self.fkeep, nrhs, C.c_void_p(x_dev_ptr), int(ldx), job,
-                                                1 if pivot_order else 0)
-        if rc < 0:
-            raise SplltError("spllt_hip_solve_repro_dev", rc, self.last_error())
+        self._call("spllt_hip_solve_repro_dev", self.fkeep, nrhs, C.c_void_p(x_dev_ptr), int(ldx), job,
+                   1 if pivot_order else 0)
         return self
 
     def set_reproducible_solve(self, on):
         """Route solve, solve_dev(phase=-1) and the preconditioner of solve_refined through the reproducible
         path (solve_many is not affected).  Returns the previous setting."""
-        rc = self.lib.spllt_hip_set_reproducible_solve(self.fkeep, 1 if on else 0)
-        if rc < 0:
-            raise SplltError("spllt_hip_set_reproducible_solve", rc, self.last_error())
+        rc = self._call("spllt_hip_set_reproducible_solve", self.fkeep, 1 if on else 0)
         return bool(rc)
 
     def release_solve_repro(self):
         """The tables and the scratch of the reproducible solve back to the device pool."""
-        rc = self.lib.spllt_hip_release_solve_repro(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_solve_repro", rc, self.last_error())
+        self._call("spllt_hip_release_solve_repro", self.fkeep)
         return self
 
     # ---- products with the factor, Gaussian sampling ------------------------------
@@ -515,9 +479,7 @@ class Factorization:
         inverse of solve_many(job), bit-reproducible.  Returns a new F-ordered array, like solve."""
         y = np.array(x, dtype=np.float64, order="F", copy=True)
         nvec = 1 if y.ndim == 1 else y.shape[1]
-        rc = self.lib.spllt_hip_factor_mult(self.fkeep, nvec, _dp(y), y.shape[0], job)
-        if rc < 0:
-            raise SplltError("spllt_hip_factor_mult", rc, self.last_error())
+        self._call("spllt_hip_factor_mult", self.fkeep, nvec, _dp(y), y.shape[0], job)
         return y
 
     def factor_mult_dev(self, x_dev_ptr, nvec, ldx=None, job=0, pivot_order=False):
@@ -525,17 +487,13 @@ class Factorization:
         solve_many_dev)."""
         if ldx is None:
             ldx = self.n
-        rc = self.lib.spllt_hip_factor_mult_dev(self.fkeep, nvec, C.c_void_p(x_dev_ptr), int(ldx), job,
-                                                1 if pivot_order else 0)
-        if rc < 0:
-            raise SplltError("spllt_hip_factor_mult_dev", rc, self.last_error())
+        self._call("spllt_hip_factor_mult_dev", self.fkeep, nvec, C.c_void_p(x_dev_ptr), int(ldx), job,
+                   1 if pivot_order else 0)
         return self
 
     def release_factor_mult(self):
         """The second workspace, the scratch and the tables of the factor products back to the device pool."""
-        rc = self.lib.spllt_hip_release_factor_mult(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_factor_mult", rc, self.last_error())
+        self._call("spllt_hip_release_factor_mult", self.fkeep)
         return self
 
     # ---- reverse-mode derivative of the factor ------------------------------------
@@ -551,11 +509,9 @@ class Factorization:
         b = np.asfortranarray(np.asarray(b, dtype=np.float64).reshape(self.n, -1))
         if a.shape != b.shape:
             raise ValueError("factor_adjoint_seed: a and b must have the same shape")
-        rc = self.lib.spllt_hip_factor_adjoint_seed(self.fkeep, a.shape[1], _dp(a), _dp(b), max(self.n, 1), float(alpha),
-                                                    1 if accumulate else 0,
-                                                    self._order_flags(a_pivot_order, b_pivot_order))
-        if rc < 0:
-            raise SplltError("spllt_hip_factor_adjoint_seed", rc, self.last_error())
+        self._call("spllt_hip_factor_adjoint_seed", self.fkeep, a.shape[1], _dp(a), _dp(b), max(self.n, 1), float(alpha),
+                   1 if accumulate else 0,
+                   self._order_flags(a_pivot_order, b_pivot_order))
         return self
 
     def factor_adjoint_seed_dev(self, a_dev_ptr, b_dev_ptr, nvec, ld=None, alpha=1.0, accumulate=False,
@@ -563,20 +519,16 @@ class Factorization:
         """spllt_hip_factor_adjoint_seed_dev: the seed from device vectors (vector q at a[q*ld .. q*ld + n))"""
         if ld is None:
             ld = self.n
-        rc = self.lib.spllt_hip_factor_adjoint_seed_dev(self.fkeep, int(nvec), C.c_void_p(a_dev_ptr), C.c_void_p(b_dev_ptr),
-                                                        int(ld), float(alpha), 1 if accumulate else 0,
-                                                        self._order_flags(a_pivot_order, b_pivot_order))
-        if rc < 0:
-            raise SplltError("spllt_hip_factor_adjoint_seed_dev", rc, self.last_error())
+        self._call("spllt_hip_factor_adjoint_seed_dev", self.fkeep, int(nvec), C.c_void_p(a_dev_ptr), C.c_void_p(b_dev_ptr),
+                   int(ld), float(alpha), 1 if accumulate else 0,
+                   self._order_flags(a_pivot_order, b_pivot_order))
         return self
 
     def set_factor_adjoint(self, arena):
         """spllt_hip_set_factor_adjoint: an arbitrary Lbar, the layout of get_factor (its strict upper triangles of
         diagonal tiles are never read)"""
         arena = np.ascontiguousarray(arena, dtype=np.float64)
-        rc = self.lib.spllt_hip_set_factor_adjoint(self.fkeep, _dp(arena), arena.size)
-        if rc < 0:
-            raise SplltError("spllt_hip_set_factor_adjoint", rc, self.last_error())
+        self._call("spllt_hip_set_factor_adjoint", self.fkeep, _dp(arena), arena.size)
         return self
 
     def get_factor_adjoint(self, out=None):
@@ -586,9 +538,7 @@ class Factorization:
         if out is None:
             out = np.zeros(max(arena, 1), dtype=np.float64)
         assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
-        rc = self.lib.spllt_hip_get_factor_adjoint(self.fkeep, _dp(out), arena)
-        if rc < 0:
-            raise SplltError("spllt_hip_get_factor_adjoint", rc, self.last_error())
+        self._call("spllt_hip_get_factor_adjoint", self.fkeep, _dp(out), arena)
         return out[:arena]
 
     def device_factor_adjoint_ptr(self):
@@ -597,22 +547,16 @@ class Factorization:
     def factor_adjoint(self):
         """spllt_hip_factor_adjoint: the sweep over the seeded arena; returns d loss / d val, nnz values"""
         out = np.zeros(max(self.nnz, 1), dtype=np.float64)
-        rc = self.lib.spllt_hip_factor_adjoint(self.fkeep, _dp(out))
-        if rc < 0:
-            raise SplltError("spllt_hip_factor_adjoint", rc, self.last_error())
+        self._call("spllt_hip_factor_adjoint", self.fkeep, _dp(out))
         return out[:self.nnz]
 
     def factor_adjoint_dev(self, gval_dev_ptr):
         """spllt_hip_factor_adjoint_dev: the same sweep, the nnz values into device memory"""
-        rc = self.lib.spllt_hip_factor_adjoint_dev(self.fkeep, C.c_void_p(gval_dev_ptr))
-        if rc < 0:
-            raise SplltError("spllt_hip_factor_adjoint_dev", rc, self.last_error())
+        self._call("spllt_hip_factor_adjoint_dev", self.fkeep, C.c_void_p(gval_dev_ptr))
         return self
 
     def release_factor_adjoint(self):
-        rc = self.lib.spllt_hip_release_factor_adjoint(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_factor_adjoint", rc, self.last_error())
+        self._call("spllt_hip_release_factor_adjoint", self.fkeep)
         return self
 
     _SAMPLE_KINDS = {"precision": 0, "covariance": 1}
@@ -629,10 +573,8 @@ class Factorization:
         x = np.zeros((self.n, nsamp), dtype=np.float64, order="F")
         m = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
         assert m is None or m.shape == (self.n,)
-        rc = self.lib.spllt_hip_sample(self.fkeep, nsamp, _dp(x), max(self.n, 1), k, int(seed), int(first_sample),
-                                       None if m is None else _dp(m))
-        if rc < 0:
-            raise SplltError("spllt_hip_sample", rc, self.last_error())
+        self._call("spllt_hip_sample", self.fkeep, nsamp, _dp(x), max(self.n, 1), k, int(seed), int(first_sample),
+                   None if m is None else _dp(m))
         return x
 
     def sample_dev(self, x_dev_ptr, nsamp, ldx=None, seed=0, kind="precision", mean_dev_ptr=None, first_sample=0):
@@ -641,11 +583,9 @@ class Factorization:
         if ldx is None:
             ldx = self.n
         k = self._sample_kind(kind)
-        rc = self.lib.spllt_hip_sample_dev(self.fkeep, nsamp, C.c_void_p(x_dev_ptr), int(ldx),
-                                           k, int(seed), int(first_sample),
-                                           None if mean_dev_ptr is None else C.c_void_p(mean_dev_ptr))
-        if rc < 0:
-            raise SplltError("spllt_hip_sample_dev", rc, self.last_error())
+        self._call("spllt_hip_sample_dev", self.fkeep, nsamp, C.c_void_p(x_dev_ptr), int(ldx),
+                   k, int(seed), int(first_sample),
+                   None if mean_dev_ptr is None else C.c_void_p(mean_dev_ptr))
         return self
 
     def white_noise_dev(self, z_dev_ptr, nsamp, ldz=None, seed=0, first_sample=0):
@@ -653,10 +593,8 @@ class Factorization:
         z[q*ldz .. q*ldz + n) in PIVOT order"""
         if ldz is None:
             ldz = max(self.n, 1)
-        rc = self.lib.spllt_hip_white_noise_dev(self.fkeep, int(nsamp), C.c_void_p(z_dev_ptr), int(ldz), int(seed),
-                                                int(first_sample))
-        if rc < 0:
-            raise SplltError("spllt_hip_white_noise_dev", rc, self.last_error())
+        self._call("spllt_hip_white_noise_dev", self.fkeep, int(nsamp), C.c_void_p(z_dev_ptr), int(ldz), int(seed),
+                   int(first_sample))
         return self
 
     def white_noise(self, nsamp, seed, first_sample=0):
@@ -664,10 +602,8 @@ class Factorization:
         PIVOT order (row p = pivot position p)."""
         import torch
         z = torch.empty((nsamp, max(self.n, 1)), dtype=torch.float64, device="cuda")
-        rc = self.lib.spllt_hip_white_noise_dev(self.fkeep, nsamp, C.c_void_p(z.data_ptr()), max(self.n, 1), int(seed),
-                                                int(first_sample))
-        if rc < 0:
-            raise SplltError("spllt_hip_white_noise_dev", rc, self.last_error())
+        self._call("spllt_hip_white_noise_dev", self.fkeep, nsamp, C.c_void_p(z.data_ptr()), max(self.n, 1), int(seed),
+                   int(first_sample))
         return np.asfortranarray(z.cpu().numpy()[:, :self.n].T)
 
     # ---- sparse right-hand sides and selected outputs -----------------------------
@@ -705,10 +641,8 @@ class Factorization:
         nsel, sel = self._wanted(rows)
         m = self.n if sel is None else nsel
         x = np.zeros((max(m, 1), max(k, 1)), dtype=np.float64, order="F")   # (never a null pointer)
-        rc = self.lib.spllt_hip_solve_sparse(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), nsel,
-                                             None if sel is None else _ip(sel), _dp(x), max(m, 1), job)
-        if rc < 0:
-            raise SplltError(where, rc, self.last_error())
+        self._call(where, self.fkeep, k, _ip(ptr), _ip(row), _dp(val), nsel,
+                   None if sel is None else _ip(sel), _dp(x), max(m, 1), job)
         return np.asfortranarray(x[:m, :k])
 
     def solve_sparse_dev(self, B, x_dev_ptr, ldx, rows=None, job=0):
@@ -717,10 +651,8 @@ class Factorization:
         where = "spllt_hip_solve_sparse_dev"
         k, ptr, row, val = self._sparse_columns(B, where)
         nsel, sel = self._wanted(rows)
-        rc = self.lib.spllt_hip_solve_sparse_dev(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), nsel,
-                                                 None if sel is None else _ip(sel), C.c_void_p(x_dev_ptr), int(ldx), job)
-        if rc < 0:
-            raise SplltError(where, rc, self.last_error())
+        self._call(where, self.fkeep, k, _ip(ptr), _ip(row), _dp(val), nsel,
+                   None if sel is None else _ip(sel), C.c_void_p(x_dev_ptr), int(ldx), job)
         return self
 
     def gram(self, B):
@@ -729,9 +661,7 @@ class Factorization:
         where = "spllt_hip_gram_sparse"
         k, ptr, row, val = self._sparse_columns(B, where)
         G = np.zeros((max(k, 1), max(k, 1)), dtype=np.float64, order="F")
-        rc = self.lib.spllt_hip_gram_sparse(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), _dp(G), max(k, 1))
-        if rc < 0:
-            raise SplltError(where, rc, self.last_error())
+        self._call(where, self.fkeep, k, _ip(ptr), _ip(row), _dp(val), _dp(G), max(k, 1))
         return G[:k, :k]
 
     def inverse_block(self, i, j):
@@ -754,33 +684,25 @@ class Factorization:
         selp = None if sel is None else _ip(sel)
         cnt = np.zeros(2, dtype=np.int64)
         cp = cnt.ctypes.data_as(C.POINTER(C.c_int64))
-        rc = self.lib.spllt_hip_solve_sparse_plan(self.fkeep, k, _ip(ptr), _ip(row), nsel, selp, job, None, 0, None, 0, cp)
-        if rc < 0:
-            raise SplltError(where, rc, self.last_error())
+        self._call(where, self.fkeep, k, _ip(ptr), _ip(row), nsel, selp, job, None, 0, None, 0, cp)
         fwd = np.zeros(max(int(cnt[0]), 1), dtype=np.int32)
         bwd = np.zeros(max(int(cnt[1]), 1), dtype=np.int32)
         i32 = C.POINTER(C.c_int32)
-        rc = self.lib.spllt_hip_solve_sparse_plan(self.fkeep, k, _ip(ptr), _ip(row), nsel, selp, job,
-                                                  fwd.ctypes.data_as(i32), len(fwd), bwd.ctypes.data_as(i32), len(bwd), cp)
-        if rc < 0:
-            raise SplltError(where, rc, self.last_error())
+        self._call(where, self.fkeep, k, _ip(ptr), _ip(row), nsel, selp, job,
+                   fwd.ctypes.data_as(i32), len(fwd), bwd.ctypes.data_as(i32), len(bwd), cp)
         return fwd[:int(cnt[0])], bwd[:int(cnt[1])]
 
     def solve_sparse_info(self):
         """of the last solve_sparse / gram, summed over its groups of columns: block columns and doubles of L the
         forward / backward sweeps visited, kernel launches, workgroups of the sweeps"""
         out = np.zeros(6, dtype=np.int64)
-        rc = self.lib.spllt_hip_solve_sparse_info(self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
-        if rc < 0:
-            raise SplltError("spllt_hip_solve_sparse_info", rc, self.last_error())
+        self._call("spllt_hip_solve_sparse_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
         return dict(zip(("fwd_bcols", "bwd_bcols", "fwd_entries", "bwd_entries", "launches", "workgroups"),
                         (int(v) for v in out)))
 
     def release_solve_sparse(self):
         """The staged lists, the gathered block and the gram workspaces back to the device pool."""
-        rc = self.lib.spllt_hip_release_solve_sparse(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_solve_sparse", rc, self.last_error())
+        self._call("spllt_hip_release_solve_sparse", self.fkeep)
         return self
 
     # ---- refined solves --------------------------------------------------------
@@ -801,19 +723,15 @@ class Factorization:
         xs = np.asfortranarray(x.reshape(x.shape[0], -1))
         y = np.empty_like(xs, order="F")
         ld = max(1, xs.shape[0])
-        rc = self.lib.spllt_hip_matvec(self.fkeep, int(val.size), _dp(val), xs.shape[1], _dp(xs), ld, _dp(y), ld)
-        if rc < 0:
-            raise SplltError("spllt_hip_matvec", rc, self.last_error())
+        self._call("spllt_hip_matvec", self.fkeep, int(val.size), _dp(val), xs.shape[1], _dp(xs), ld, _dp(y), ld)
         return y.reshape(x.shape, order="F")
 
     def matvec_dev(self, val_dev_ptr, nnz, x_dev_ptr, y_dev_ptr, nvec, ldx=None, ldy=None, pivot_order=False):
         """spllt_hip_matvec_dev: the product on device arrays (vector q at x[q*ldx .. q*ldx + n), y alike;
         pivot_order as for solve_many_dev; x and y must not overlap)."""
-        rc = self.lib.spllt_hip_matvec_dev(self.fkeep, int(nnz), C.c_void_p(val_dev_ptr), nvec, C.c_void_p(x_dev_ptr),
-                                           int(self.n if ldx is None else ldx), C.c_void_p(y_dev_ptr),
-                                           int(self.n if ldy is None else ldy), 1 if pivot_order else 0)
-        if rc < 0:
-            raise SplltError("spllt_hip_matvec_dev", rc, self.last_error())
+        self._call("spllt_hip_matvec_dev", self.fkeep, int(nnz), C.c_void_p(val_dev_ptr), nvec, C.c_void_p(x_dev_ptr),
+                   int(self.n if ldx is None else ldx), C.c_void_p(y_dev_ptr),
+                   int(self.n if ldy is None else ldy), 1 if pivot_order else 0)
         return self
 
     def solve_refined(self, val, b, method="pcg", tol=1e-14, max_iter=50):
@@ -844,18 +762,14 @@ class Factorization:
             raise SplltError("spllt_hip_solve_refined_dev", -10, "method is not 'ir' or 'pcg'")
         it = np.zeros(max(1, nrhs), dtype=np.int32)
         err = np.zeros(max(1, nrhs), dtype=np.float64)
-        rc = self.lib.spllt_hip_solve_refined_dev(self.fkeep, int(nnz), C.c_void_p(val_dev_ptr), nrhs,
-                                                  C.c_void_p(x_dev_ptr), int(self.n if ldx is None else ldx),
-                                                  self._METHODS[method], float(tol), int(max_iter), _ip(it), _dp(err))
-        if rc < 0:
-            raise SplltError("spllt_hip_solve_refined_dev", rc, self.last_error())
+        rc = self._call("spllt_hip_solve_refined_dev", self.fkeep, int(nnz), C.c_void_p(val_dev_ptr), nrhs,
+                        C.c_void_p(x_dev_ptr), int(self.n if ldx is None else ldx),
+                        self._METHODS[method], float(tol), int(max_iter), _ip(it), _dp(err))
         return rc, it[:nrhs], err[:nrhs]
 
     def release_refine(self):
         """spllt_hip_release_refine: the operator tables and work vectors go back to the pool"""
-        rc = self.lib.spllt_hip_release_refine(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_refine", rc, self.last_error())
+        self._call("spllt_hip_release_refine", self.fkeep)
         return self
 
     # ---- low-rank update / downdate ----------------------------------------------
@@ -885,9 +799,7 @@ class Factorization:
         that is not positive definite raises with flag -20 and leaves the handle without a factor until the
         next factor()."""
         k, ptr, row, val = self._updown_columns(W, "spllt_hip_updown")
-        rc = self.lib.spllt_hip_updown(self.fkeep, k, _ip(ptr), _ip(row), _dp(val), -1 if downdate else 1)
-        if rc < 0:
-            raise SplltError("spllt_hip_updown", rc, self.last_error())
+        self._call("spllt_hip_updown", self.fkeep, k, _ip(ptr), _ip(row), _dp(val), -1 if downdate else 1)
         return self
 
     def updown_plan(self, W):
@@ -903,17 +815,13 @@ class Factorization:
     def updown_info(self):
         """of the last update(): block columns visited, entries of L in them, kernel launches, passes"""
         out = np.zeros(4, dtype=np.int64)
-        rc = self.lib.spllt_hip_updown_info(self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
-        if rc < 0:
-            raise SplltError("spllt_hip_updown_info", rc, self.last_error())
+        self._call("spllt_hip_updown_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
         return dict(zip(("bcols", "entries", "launches", "passes"), (int(v) for v in out)))
 
     def updown_device_ms(self):
         """spllt_hip_updown_time: device time of the last update(), first scatter to last kernel"""
         v = C.c_double()
-        rc = self.lib.spllt_hip_updown_time(self.fkeep, C.byref(v))
-        if rc < 0:
-            raise SplltError("spllt_hip_updown_time", rc, self.last_error())
+        self._call("spllt_hip_updown_time", self.fkeep, C.byref(v))
         return v.value
 
     def matvec_tables(self):
@@ -922,12 +830,9 @@ class Factorization:
         return self.program("matvec_rowptr"), self.program("matvec_col"), self.program("matvec_src")
 
     # ---- batched factorization ------------------------------------------------
-    def _batch_rc(self, where, rc):
-        """every error raises, except -20: a batch with a member that is not positive definite returns
-        normally (batch_status() tells which), so that a sweep with one bad sample keeps the rest"""
-        if rc < 0 and rc != -20:
-            raise SplltError(where, rc, self.last_error())
-        return rc
+    # every error of a batch call raises, except -20: a batch with a member that is not positive definite returns
+    # normally (batch_status() tells which), so that a sweep with one bad sample keeps the rest
+    _BATCH_OK = (-20,)
 
     def factor_batch(self, vals, ldval=None):
         """spllt_hip_factor_batch: vals of shape (B, nnz), one row of values per member; finished on
@@ -937,17 +842,15 @@ class Factorization:
             raise ValueError("factor_batch: vals must have shape (B, nnz)")
         if ldval is None:
             ldval = vals.shape[1]
-        rc = self.lib.spllt_hip_factor_batch(self.akeep, self.fkeep, vals.shape[0], self.nnz,
-                                             C.c_void_p(vals.ctypes.data), int(ldval))
-        return self._batch_rc("spllt_hip_factor_batch", rc)
+        return self._call("spllt_hip_factor_batch", self.akeep, self.fkeep, vals.shape[0], self.nnz,
+                          C.c_void_p(vals.ctypes.data), int(ldval), ok=self._BATCH_OK)
 
     def factor_batch_dev(self, val_dev_ptr, nbatch, ldval=None):
         """the same with the values in HBM (integer device pointer; member b at ptr + b * ldval doubles)"""
         if ldval is None:
             ldval = self.nnz
-        rc = self.lib.spllt_hip_factor_batch_dev(self.akeep, self.fkeep, int(nbatch), self.nnz,
-                                                 C.c_void_p(val_dev_ptr), int(ldval))
-        return self._batch_rc("spllt_hip_factor_batch_dev", rc)
+        return self._call("spllt_hip_factor_batch_dev", self.akeep, self.fkeep, int(nbatch), self.nnz,
+                          C.c_void_p(val_dev_ptr), int(ldval), ok=self._BATCH_OK)
 
     def batch_status(self):
         """(flags, columns) of the last batch: 0 / -20 per member, 1-based pivot position of the first
@@ -973,8 +876,7 @@ class Factorization:
             raise ValueError(f"solve_batch: b holds vectors for {x.shape[0]} members, the last batch has {nb}")
         if x.shape[-1] != self.n:
             raise ValueError(f"solve_batch: the vectors have length {x.shape[-1]}, n = {self.n}")
-        rc = self.lib.spllt_hip_solve_batch(self.fkeep, nrhs, C.c_void_p(x.ctypes.data), x.shape[-1], job)
-        self._batch_rc("spllt_hip_solve_batch", rc)
+        self._call("spllt_hip_solve_batch", self.fkeep, nrhs, C.c_void_p(x.ctypes.data), x.shape[-1], job, ok=self._BATCH_OK)
         return x
 
     def solve_batch_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
@@ -984,9 +886,8 @@ class Factorization:
         (batch_status()[0].size): the array behind the pointer must hold that many."""
         if ldx is None:
             ldx = self.n
-        rc = self.lib.spllt_hip_solve_batch_dev(self.fkeep, int(nrhs), C.c_void_p(x_dev_ptr), int(ldx), job,
-                                                1 if pivot_order else 0)
-        return self._batch_rc("spllt_hip_solve_batch_dev", rc)
+        return self._call("spllt_hip_solve_batch_dev", self.fkeep, int(nrhs), C.c_void_p(x_dev_ptr), int(ldx), job,
+                          1 if pivot_order else 0, ok=self._BATCH_OK)
 
     def get_factor_batch(self, member, out=None):
         """one member's arena on the host (the layout of get_factor)"""
@@ -994,9 +895,7 @@ class Factorization:
         if out is None:
             out = np.zeros(max(arena, 1), dtype=np.float64)
         assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
-        rc = self.lib.spllt_hip_get_factor_batch(self.fkeep, int(member), _dp(out), arena)
-        if rc < 0:
-            raise SplltError("spllt_hip_get_factor_batch", rc, self.last_error())
+        self._call("spllt_hip_get_factor_batch", self.fkeep, int(member), _dp(out), arena)
         return out[:arena]
 
     def device_factor_batch_ptr(self):
@@ -1009,9 +908,7 @@ class Factorization:
         """log det A_b of every member of the last batch (NaN for a failed member)"""
         nb = self.lib.spllt_hip_batch_status(self.fkeep, None, None, 0)
         out = np.zeros(max(nb, 1), dtype=np.float64)
-        rc = self.lib.spllt_hip_log_det_batch(self.fkeep, _dp(out))
-        if rc < 0:
-            raise SplltError("spllt_hip_log_det_batch", rc, self.last_error())
+        self._call("spllt_hip_log_det_batch", self.fkeep, _dp(out))
         return out[:nb]
 
     def batch_launches(self):
@@ -1019,16 +916,13 @@ class Factorization:
         return int(self.lib.spllt_hip_batch_launches(self.fkeep))
 
     def release_batch(self):
-        rc = self.lib.spllt_hip_release_batch(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_batch", rc, self.last_error())
+        self._call("spllt_hip_release_batch", self.fkeep)
 
     # ---- batched selected inversion -------------------------------------------
     def selected_inverse_batch(self):
         """spllt_hip_selected_inverse_batch: Z_b on the pattern of L for every member of the last batch.
         Returns 0, or -20 when a member is not positive definite (the others are inverted)."""
-        rc = self.lib.spllt_hip_selected_inverse_batch(self.fkeep)
-        return self._batch_rc("spllt_hip_selected_inverse_batch", rc)
+        return self._call("spllt_hip_selected_inverse_batch", self.fkeep, ok=self._BATCH_OK)
 
     def get_inverse_batch(self, member, out=None):
         """one member's Z arena on the host (the layout of get_inverse); a failed member raises (-20)"""
@@ -1036,9 +930,7 @@ class Factorization:
         if out is None:
             out = np.zeros(max(arena, 1), dtype=np.float64)
         assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
-        rc = self.lib.spllt_hip_get_inverse_batch(self.fkeep, int(member), _dp(out), arena)
-        if rc < 0:
-            raise SplltError("spllt_hip_get_inverse_batch", rc, self.last_error())
+        self._call("spllt_hip_get_inverse_batch", self.fkeep, int(member), _dp(out), arena)
         return out[:arena]
 
     def device_inverse_batch_ptr(self):
@@ -1047,30 +939,25 @@ class Factorization:
         p = self.lib.spllt_hip_device_inverse_batch(self.fkeep, C.byref(stride))
         return p, stride.value
 
-    def _batch_rows(self, fn, where, width):
+    def _batch_rows(self, name, width):
         nb = self.lib.spllt_hip_batch_status(self.fkeep, None, None, 0)
         out = np.zeros((max(nb, 1), max(width, 1)), dtype=np.float64)
-        rc = fn(self.fkeep, _dp(out), out.shape[1])
-        if rc < 0:
-            raise SplltError(where, rc, self.last_error())
+        self._call(name, self.fkeep, _dp(out), out.shape[1])
         return out[:nb, :width]
 
     def inverse_diag_batch(self):
         """(A_b^-1)_ii in the user's variable order, shape (nbatch, n); NaN rows for failed members"""
-        return self._batch_rows(self.lib.spllt_hip_inverse_diag_batch, "spllt_hip_inverse_diag_batch", self.n)
+        return self._batch_rows("spllt_hip_inverse_diag_batch", self.n)
 
     def inverse_on_pattern_batch(self):
         """(A_b^-1) at the entries of the analysed pattern in the order of val, shape (nbatch, nnz); NaN
         rows for failed members"""
-        return self._batch_rows(self.lib.spllt_hip_inverse_on_pattern_batch, "spllt_hip_inverse_on_pattern_batch",
-                                self.nnz)
+        return self._batch_rows("spllt_hip_inverse_on_pattern_batch", self.nnz)
 
     def inverse_on_pattern_batch_dev(self, out_dev_ptr, ldout=None):
         """spllt_hip_inverse_on_pattern_batch_dev: the same rows into device memory, out[b*ldout + k]"""
-        rc = self.lib.spllt_hip_inverse_on_pattern_batch_dev(self.fkeep, C.c_void_p(out_dev_ptr),
-                                                             int(self.nnz if ldout is None else ldout))
-        if rc < 0:
-            raise SplltError("spllt_hip_inverse_on_pattern_batch_dev", rc, self.last_error())
+        self._call("spllt_hip_inverse_on_pattern_batch_dev", self.fkeep, C.c_void_p(out_dev_ptr),
+                   int(self.nnz if ldout is None else ldout))
         return self
 
     def batch_selinv_launches(self):
@@ -1078,9 +965,7 @@ class Factorization:
         return int(self.lib.spllt_hip_batch_selinv_launches(self.fkeep))
 
     def release_inverse_batch(self):
-        rc = self.lib.spllt_hip_release_inverse_batch(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_release_inverse_batch", rc, self.last_error())
+        self._call("spllt_hip_release_inverse_batch", self.fkeep)
 
     # ---- multi-GPU subtree partition ------------------------------------------
     def set_partition(self, rank, nranks):
@@ -1096,9 +981,7 @@ class Factorization:
     def set_communicator(self, nccl_comm):
         """hand the caller's RCCL communicator (ncclComm_t as an integer) to the library: the
         exchanges of the partition then run inside spllt_factor / spllt_wait / spllt_solve"""
-        rc = self.lib.spllt_hip_set_communicator(self.fkeep, C.c_void_p(nccl_comm))
-        if rc < 0:
-            raise SplltError("spllt_hip_set_communicator", rc, self.last_error())
+        self._call("spllt_hip_set_communicator", self.fkeep, C.c_void_p(nccl_comm))
 
     def set_exchange_buffer(self, dev_ptr):
         rc = self.lib.spllt_hip_set_exchange_buffer(self.fkeep, C.c_void_p(dev_ptr))
@@ -1117,9 +1000,7 @@ class Factorization:
         return int(self.lib.spllt_hip_exchange_stream(self.fkeep) or 0)
 
     def continue_after_exchange(self):
-        rc = self.lib.spllt_hip_continue(self.fkeep)
-        if rc < 0:
-            raise SplltError("spllt_hip_continue", rc, self.last_error())
+        self._call("spllt_hip_continue", self.fkeep)
         return self
 
     def pending_exchange(self):
@@ -1144,10 +1025,8 @@ class Factorization:
         val = np.ascontiguousarray(val, dtype=np.float64)
         nl = len(self.program("launches"))
         ms = np.zeros(max(nl, 1), dtype=np.float32)
-        fn = self.lib.spllt_hip_profile_in_program if in_program else self.lib.spllt_hip_profile
-        rc = fn(self.fkeep, _dp(val), self.nnz, ms.ctypes.data_as(C.POINTER(C.c_float)), nl)
-        if rc < 0:
-            raise SplltError("spllt_hip_profile", rc, self.last_error())
+        rc = self._call("spllt_hip_profile_in_program" if in_program else "spllt_hip_profile", self.fkeep, _dp(val),
+                        self.nnz, ms.ctypes.data_as(C.POINTER(C.c_float)), nl, where="spllt_hip_profile")
         return ms[:rc]
 
     def timeline(self, val):
@@ -1156,10 +1035,15 @@ class Factorization:
         val = np.ascontiguousarray(val, dtype=np.float64)
         nl = len(self.program("launches")) + 1
         t = np.zeros(nl, dtype=np.float32)
-        rc = self.lib.spllt_hip_timeline(self.fkeep, _dp(val), self.nnz, t.ctypes.data_as(C.POINTER(C.c_float)), nl)
-        if rc < 0:
-            raise SplltError("spllt_hip_timeline", rc, self.last_error())
+        rc = self._call("spllt_hip_timeline", self.fkeep, _dp(val), self.nnz, t.ctypes.data_as(C.POINTER(C.c_float)), nl)
         return t[:rc]
+
+    def _call(self, name, *args, ok=(), where=None):
+        """lib.<name>(*args); a negative return value that is not in `ok` raises with the handle's message"""
+        rc = getattr(self.lib, name)(*args)
+        if rc < 0 and rc not in ok:
+            raise SplltError(where or name, rc, self.last_error())
+        return rc
 
     def last_error(self):
         return (self.lib.spllt_hip_last_error(self.fkeep) or b"").decode()

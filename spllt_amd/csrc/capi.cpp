@@ -2,7 +2,19 @@
 // plus the extensions of include/spllt_hip.h.  Mirrors the behaviour of
 // reference interfaces/C/spllt_data_ciface.F90: never aborts, messages on
 // stderr, status in info->flag.
+//
+// Every extension that works on a handle goes through one ladder, enter(), whose order is fixed: every check
+// that needs no device comes first, so a rejected call touches nothing.
+//   1. handle and analysis      SPLLT_ERROR_PARAMETER, no message
+//   2. the caller's own argument check (`bad`; "" refuses without a message)
+//   3. partition                SPLLT_ERROR_UNIMPLEMENTED and a line on stderr (SINGLE, SINGLE_F)
+//   4. dead                     SPLLT_ERROR_HIP: a submission of this handle never returned
+//   5. wait                     for a pending factorization (WAIT returns its failure, WAIT_IGNORE does not)
+//   6. engine                   created when there is none (ENGINE); its failure with its message
+//   7. factor, batch or inverse SPLLT_ERROR_PARAMETER with a message saying what is missing
+// ensure_engine() is the only place that constructs an Engine, leave() the one way out after the engine call.
 #include <algorithm>
+#include <cassert>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -21,6 +33,32 @@
 using namespace spx;
 
 namespace {
+
+// a table of spllt_hip_program_get: rebuilt when the handle has been analysed again or the key differs
+template <class T>
+struct Cached {
+  std::shared_ptr<const Symbolic> S;
+  int key[2] = {-1, -1};
+  int rc = 0;
+  T value;
+  template <class Build>
+  const T* get(const std::shared_ptr<Symbolic>& s, int k0, int k1, Build build) {   // null: the build failed
+    if (S != s || key[0] != k0 || key[1] != k1) {
+      rc = build(value);
+      S = s;
+      key[0] = k0;
+      key[1] = k1;
+    }
+    return rc ? nullptr : &value;
+  }
+};
+struct MatvecTables {
+  std::vector<int64_t> rowptr;
+  std::vector<int> col, src;
+};
+struct PatternTables {
+  std::vector<int> row, col;
+};
 
 struct Akeep {
   std::shared_ptr<Symbolic> S;
@@ -42,25 +80,12 @@ struct Fkeep {
   double* xbuf = nullptr;  // multi-GPU exchange buffer (caller-owned device memory)
   bool dead = false;       // a submission never returned: the engine belongs to the stuck helper thread
   bool repro_solve = false;   // spllt_hip_set_reproducible_solve: handed to the engine before every solve
-  // the selected-inversion program of spllt_hip_program_get (built once per pattern and panel layout)
-  std::shared_ptr<const Symbolic> si_S;
-  int si_pw = -1, si_cb = -1, si_rc = 0;
-  SelinvProgram si_prog;
-  // the batch program of spllt_hip_program_get (built once per pattern)
-  std::shared_ptr<const Symbolic> bt_S;
-  int bt_rc = 0;
-  Program bt_prog;
-  // ... and the batch's selected-inversion program (panel width 64 whatever the handle's)
-  std::shared_ptr<const Symbolic> bsi_S;
-  int bsi_rc = 0;
-  SelinvProgram bsi_prog;
-  // the operator tables of spllt_hip_program_get ("matvec_*", built once per pattern)
-  std::shared_ptr<const Symbolic> mv_S;
-  std::vector<int64_t> mv_rowptr;
-  std::vector<int> mv_col, mv_src;
-  // the (row, column) tables of spllt_hip_program_get ("pattern_row" / "pattern_col", built once per pattern)
-  std::shared_ptr<const Symbolic> po_S;
-  std::vector<int> po_row, po_col;
+  // what spllt_hip_program_get builds from the analysis alone, each once per pattern (and key):
+  Cached<SelinvProgram> si;    // the selected-inversion program, keyed by panel width and chain block
+  Cached<SelinvProgram> bsi;   // ... and the batch's (panel width 64 whatever the handle's)
+  Cached<Program> bt;          // the batch program
+  Cached<MatvecTables> mv;     // the operator tables ("matvec_*")
+  Cached<PatternTables> po;    // the (row, column) tables ("pattern_row" / "pattern_col")
   // spllt_hip_factor_serial: successful changes of the single factor [0] and of the batch [1]
   int64_t serial[2] = {0, 0};
 };
@@ -108,16 +133,90 @@ int do_wait(Fkeep* f) {
 // nothing factorized yet, or a failed downdate left the factor invalid (spllt_hip_updown)
 bool no_factor(const Fkeep* f) { return !f->eng || !f->eng->factor_valid(); }
 
-int ensure_hostL(Fkeep* f) {
-  do_wait(f);
-  if (f->last_flag) return f->last_flag;
-  if (no_factor(f)) return SPLLT_ERROR_PARAMETER;
-  if (!f->hostL_valid) {
-    f->hostL.resize((size_t)f->S->arena);
-    int rc = f->eng->download(f->hostL.data(), f->S->arena);
-    if (rc) return rc;
-    f->hostL_valid = true;
+bool analysed(const Fkeep* f) { return f && f->S; }
+
+void mark_pending(Fkeep* f) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (std::find(g_pending.begin(), g_pending.end(), f) == g_pending.end()) g_pending.push_back(f);
+}
+
+// a refusal with its message
+int fail(Fkeep* f, const char* what, const std::string& msg, int rc = SPLLT_ERROR_PARAMETER) {
+  f->last_error = std::string(what) + ": " + msg;
+  return rc;
+}
+
+// the one way out after an engine call; the message of a failed one: the feature's own, else the engine's
+int leave(Fkeep* f, int rc) {
+  if (!rc) return 0;
+  if (!f->eng->feature_error().empty()) f->last_error = f->eng->feature_error();
+  else if (f->eng->status()) f->last_error = f->eng->error();
+  return rc;
+}
+
+// the handle's engine, created when there is none: 0, SPLLT_ERROR_ALLOCATION, or the engine's status with its
+// message in last_error (message = false: on the helper thread of factor_impl, which must not write the handle's
+// strings -- after a deadline the caller owns them)
+int ensure_engine(Fkeep* f, bool message = true) {
+  if (!f->eng) {
+    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
+    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
+    f->eng->set_exchange_buffer(f->xbuf);
   }
+  if (message && f->eng->status()) f->last_error = f->eng->error();
+  return f->eng->status();
+}
+
+// what a call needs of its handle (the ladder at the top of the file)
+enum Need : unsigned {
+  SINGLE = 1u << 0,            // a single GPU: "... on a partitioned (multi-GPU) handle"
+  SINGLE_F = 1u << 1,          // the same in the words of the older calls: "... on a partitioned (multi-GPU) factor"
+  WAIT = 1u << 2,              // wait for a pending factorization and return its failure
+  WAIT_IGNORE = 1u << 3,       // wait, whatever it reports (it shares the stream and the staging buffers)
+  WAIT_NOT_POSDEF = 1u << 4,   // release() only: "not positive definite" is no reason not to release
+  ENGINE = 1u << 5,            // create the engine
+  FACTOR = 1u << 6,            // an engine whose factor no failed downdate has destroyed (the older calls: when
+                               // nothing was factorized on it, the engine itself says so)
+  FACTORED = 1u << 7,          // ... on which a factorization has been enqueued
+  BATCH = 1u << 8,             // a batch
+  INVERSE = 1u << 9,           // a selected inverse of the current factor
+  BATCH_INVERSE = 1u << 10,    // a selected inverse of the current batch
+  EMPTY = 1u << 11,            // the call has nothing to do: kEmpty once the checks that need no device are through
+  EMPTY_FIRST = 1u << 12,      // ... even on a dead handle (spllt_hip_factor_batch)
+  LENIENT = 1u << 13,          // release() only
+};
+// what enter() returns for EMPTY: no flag of the library; the caller hands its result on through done()
+constexpr int kEmpty = INT_MAX;
+int done(int rc) { return rc == kEmpty ? 0 : rc; }
+
+// what == nullptr: the plain calls, which refuse without messages (and never ask for SINGLE: that refusal has one)
+int enter(Fkeep* f, const char* what, const char* bad, unsigned need) {
+  auto refuse = [&](const std::string& msg) { return what ? fail(f, what, msg) : SPLLT_ERROR_PARAMETER; };
+  assert(what || !(need & (SINGLE | SINGLE_F)));
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (bad) return *bad ? refuse(bad) : SPLLT_ERROR_PARAMETER;
+  if ((need & (SINGLE | SINGLE_F)) && f->eo.nranks > 1) {
+    fail(f, what, std::string("not available on a partitioned (multi-GPU) ") + ((need & SINGLE_F) ? "factor" : "handle"));
+    std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
+    return SPLLT_ERROR_UNIMPLEMENTED;
+  }
+  if (need & EMPTY_FIRST) return kEmpty;
+  if (f->dead) return SPLLT_ERROR_HIP;
+  if (need & EMPTY) return kEmpty;
+  if (need & (WAIT | WAIT_IGNORE)) {
+    const int rc = do_wait(f);
+    if (rc && (need & WAIT)) return rc;
+  }
+  if (need & ENGINE)
+    if (int rc = ensure_engine(f)) return rc;
+  if ((need & (FACTOR | FACTORED)) && (no_factor(f) || ((need & FACTORED) && !f->eng->factored())))
+    return refuse("nothing has been factorized on this handle");
+  if ((need & BATCH) && (!f->eng || f->eng->batch_count() <= 0)) return refuse("no batch has been factorized on this handle");
+  if ((need & INVERSE) && !f->eng->inverse_valid())
+    return refuse("no selected inverse of the current factor (call spllt_hip_selected_inverse after every factorization)");
+  if ((need & BATCH_INVERSE) && !f->eng->batch_inverse_valid())
+    return refuse("no selected inverse of the current batch (call spllt_hip_selected_inverse_batch after every "
+                  "spllt_hip_factor_batch)");
   return 0;
 }
 
@@ -254,12 +353,7 @@ void factor_impl(void* akeep, void* fkeep, int nnz, const double* val, bool dev,
   // engine creation and submission on the helper thread, under the deadline (engine.cpp)
   std::string why;
   int rc = run_with_deadline([f, dev, val, nnz]() -> int {
-    if (!f->eng) {
-      f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-      if (!f->eng) return SPLLT_ERROR_ALLOCATION;
-      f->eng->set_exchange_buffer(f->xbuf);
-    }
-    if (f->eng->status()) return f->eng->status();
+    if (int erc = ensure_engine(f, false)) return erc;   // (the message is copied below, on this thread)
     return dev ? f->eng->factor_async_dev(val, nnz) : f->eng->factor_async(val, nnz);
   }, &why);
   if (!why.empty()) {
@@ -276,8 +370,7 @@ void factor_impl(void* akeep, void* fkeep, int nnz, const double* val, bool dev,
   f->hostL_valid = false;
   if (rc == 0) {
     ++f->serial[0];
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (std::find(g_pending.begin(), g_pending.end(), f) == g_pending.end()) g_pending.push_back(f);
+    mark_pending(f);
   } else {
     f->last_error = f->eng->error();
   }
@@ -285,14 +378,19 @@ void factor_impl(void* akeep, void* fkeep, int nnz, const double* val, bool dev,
   if (info) info->flag = rc;
 }
 
-template <class Tp>
-static int64_t copy_out(const std::vector<Tp>& v, void* buf, int64_t cap) {
-  if (buf) {
-    int64_t k = std::min<int64_t>(cap, (int64_t)v.size());
-    if (k > 0) std::memcpy(buf, v.data(), sizeof(Tp) * (size_t)k);
+// the one way out of the getters: what fits of the data into buf (when there is one), the full size returned
+struct Out {
+  void* buf;
+  int64_t cap;   // in the unit of the size returned
+  int64_t copy(const void* p, int64_t count, size_t unit) const {
+    const int64_t k = std::min(cap, count);
+    if (buf && k > 0) std::memcpy(buf, p, unit * (size_t)k);
+    return count;
   }
-  return (int64_t)v.size();
-}
+  template <class Tp> int64_t elems(const std::vector<Tp>& v) const { return copy(v.data(), (int64_t)v.size(), sizeof(Tp)); }
+  template <class Tp> int64_t bytes(const std::vector<Tp>& v) const { return bytes(v.data(), v.size() * sizeof(Tp)); }
+  int64_t bytes(const void* p, size_t n) const { return copy(p, (int64_t)n, 1); }
+};
 
 }  // namespace
 
@@ -430,10 +528,7 @@ void spllt_solve(void* fkeep, spllt_options_t* options, int* order, int nrhs, do
 
 int spllt_hip_solve_dev(void* fkeep, void* y_dev, int nrhs, int job, int phase) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S || !y_dev) return SPLLT_ERROR_PARAMETER;
-  int rc = do_wait(f);
-  if (rc == 0 && no_factor(f)) rc = SPLLT_ERROR_PARAMETER;  // nothing factorized yet
-  if (rc) return rc;
+  if (int rc = enter(f, nullptr, y_dev ? nullptr : "", WAIT | FACTOR)) return rc;
   f->eng->set_reproducible_solve(f->repro_solve);
   return f->eng->solve_dev(static_cast<double*>(y_dev), nrhs, job, phase);
 }
@@ -562,31 +657,32 @@ int64_t spllt_hip_sym_get(const void* akeep, const char* name, void* buf, int64_
   if (!a || !a->S || !name) return -1;
   const Symbolic& S = *a->S;
   std::string k(name);
-  if (k == "order") return copy_out(S.order, buf, cap);
-  if (k == "sptr") return copy_out(S.sptr, buf, cap);
-  if (k == "sparent") return copy_out(S.sparent, buf, cap);
-  if (k == "rlist") return copy_out(S.rlist, buf, cap);
-  if (k == "small") return copy_out(S.small, buf, cap);
-  if (k == "level") return copy_out(S.level, buf, cap);
-  if (k == "rptr") return copy_out(S.rptr, buf, cap);
-  if (k == "map_dst") return copy_out(S.map_dst, buf, cap);
-  if (k == "map_src") return copy_out(S.map_src, buf, cap);
-  if (k == "lmap_ptr") return copy_out(S.lmap_ptr, buf, cap);
-  if (k == "weight") return copy_out(S.weight, buf, cap);
-  if (k == "node_bcol0") return copy_out(S.node_bcol0, buf, cap);
+  const Out o{buf, cap};
+  if (k == "order") return o.elems(S.order);
+  if (k == "sptr") return o.elems(S.sptr);
+  if (k == "sparent") return o.elems(S.sparent);
+  if (k == "rlist") return o.elems(S.rlist);
+  if (k == "small") return o.elems(S.small);
+  if (k == "level") return o.elems(S.level);
+  if (k == "rptr") return o.elems(S.rptr);
+  if (k == "map_dst") return o.elems(S.map_dst);
+  if (k == "map_src") return o.elems(S.map_src);
+  if (k == "lmap_ptr") return o.elems(S.lmap_ptr);
+  if (k == "weight") return o.elems(S.weight);
+  if (k == "node_bcol0") return o.elems(S.node_bcol0);
   if (k.rfind("bcol_", 0) == 0) {
     const int nb = S.nbcol();
     if (k == "bcol_off") {
       std::vector<int64_t> v(nb);
       for (int b = 0; b < nb; ++b) v[b] = S.bcols[b].off;
-      return copy_out(v, buf, cap);
+      return o.elems(v);
     }
     std::vector<int> v(nb);
     for (int b = 0; b < nb; ++b) {
       const BlockCol& B = S.bcols[b];
       v[b] = k == "bcol_node" ? B.node : k == "bcol_width" ? B.width : k == "bcol_r0" ? B.r0 : k == "bcol_nrow" ? B.nrow : -1;
     }
-    return copy_out(v, buf, cap);
+    return o.elems(v);
   }
   return -1;
 }
@@ -616,43 +712,30 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 }
 
 // test hooks of the process-wide "runtime is wedged" state (engine.cpp): "wedge" sets it, "wedged"
-// reads it, "teardown" runs the atexit handler of the pools now; "batch_grid_limit=N" lowers the grid size
-// from which on a batched launch is split by member range (N <= 0: the hardware limit again);
-// "batch_selinv_fused=0|1": 0 forces the three-launch form of every step of the batched selected inversion;
-// "rsolve_poison=0|1": 1 fills the scratch of the reproducible solve with NaN before every sweep;
-// "solve_sparse_poison=0|1": 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed;
-// "fmult_poison=0|1": 1 fills the scratch of the factor products with NaN before every direction;
-// "fmult_alloc_fail=N": the next N allocations of the products' second workspace and scratch fail
+// reads it, "teardown" runs the atexit handler of the pools now; then the "name=value" switches:
+//   batch_grid_limit=N      the grid size from which on a batched launch is split by member range (N <= 0: the
+//                           hardware limit again)
+//   fmult_alloc_fail=N      the next N allocations of the products' second workspace and scratch fail
+//   batch_selinv_fused=0|1  0 forces the three-launch form of every step of the batched selected inversion
+//   rsolve_poison=0|1       1 fills the scratch of the reproducible solve with NaN before every sweep
+//   solve_sparse_poison=0|1 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
+//   fmult_poison=0|1        1 fills the scratch of the factor products with NaN before every direction
 int spllt_hip_debug(const char* what) {
   if (!what) return -1;
   const std::string w(what);
   if (w == "wedge") { mark_runtime_wedged(); return 0; }
   if (w == "wedged") return runtime_wedged() ? 1 : 0;
   if (w == "teardown") { run_pools_teardown_for_test(); return 0; }
-  if (w.rfind("batch_grid_limit=", 0) == 0) {   // workgroups from which on a batched launch splits its members
-    set_batch_grid_limit(std::atoll(w.c_str() + 17));
-    return 0;
-  }
-  if (w == "batch_selinv_fused=0" || w == "batch_selinv_fused=1") {
-    set_batch_selinv_fused(w.back() == '1');
-    return 0;
-  }
-  if (w == "solve_sparse_poison=0" || w == "solve_sparse_poison=1") {   // NaN in the workspace of a sparse solve
-    set_solve_sparse_poison(w.back() == '1');
-    return 0;
-  }
-  if (w == "fmult_poison=0" || w == "fmult_poison=1") {   // NaN in the scratch of the factor products before a direction
-    set_fmult_poison(w.back() == '1');
-    return 0;
-  }
-  if (w.rfind("fmult_alloc_fail=", 0) == 0) {   // the next N allocations of the products' workspace and scratch fail
-    set_fmult_alloc_fail(std::atoi(w.c_str() + 17));
-    return 0;
-  }
-  if (w == "rsolve_poison=0" || w == "rsolve_poison=1") {   // NaN in the scratch of the reproducible solve before a sweep
-    set_rsolve_poison(w.back() == '1');
-    return 0;
-  }
+  const size_t eq = w.find('=');
+  if (eq == std::string::npos) return -1;
+  const std::string name = w.substr(0, eq), value = w.substr(eq + 1);
+  if (name == "batch_grid_limit") { set_batch_grid_limit(std::atoll(value.c_str())); return 0; }
+  if (name == "fmult_alloc_fail") { set_fmult_alloc_fail(std::atoi(value.c_str())); return 0; }
+  static const struct { const char* name; void (*set)(bool); } kSwitches[] = {
+      {"batch_selinv_fused", set_batch_selinv_fused}, {"rsolve_poison", set_rsolve_poison},
+      {"solve_sparse_poison", set_solve_sparse_poison}, {"fmult_poison", set_fmult_poison}};
+  for (const auto& s : kSwitches)
+    if (name == s.name && (value == "0" || value == "1")) { s.set(value == "1"); return 0; }
   return -1;
 }
 
@@ -715,11 +798,8 @@ int spllt_hip_set_partition(void* fkeep, int rank, int nranks, int64_t* exchange
 void* spllt_hip_engine_stream(void* fkeep) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->S) return nullptr;
-  if (!f->eng) {   // created here so that the caller can order its collective on it before the first factor
-    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-    if (!f->eng || f->eng->status()) return nullptr;
-    f->eng->set_exchange_buffer(f->xbuf);
-  }
+  // (created here so that the caller can order its collective on it before the first factor)
+  if (ensure_engine(f)) return nullptr;
   return (void*)f->eng->stream();
 }
 
@@ -731,14 +811,7 @@ void* spllt_hip_exchange_stream(void* fkeep) {
 
 int spllt_hip_set_communicator(void* fkeep, void* nccl_comm) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (!f->eng) {
-    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
-    f->eng->set_exchange_buffer(f->xbuf);
-  }
-  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
+  if (int rc = enter(f, nullptr, nullptr, ENGINE)) return rc;
   int rc = f->eng->set_communicator(nccl_comm);
   if (rc) f->last_error = f->eng->error();
   return rc;
@@ -763,10 +836,7 @@ int spllt_hip_continue(void* fkeep) {
   if (!f || !f->eng) return SPLLT_ERROR_PARAMETER;
   int rc = f->eng->continue_after_exchange();
   f->last_flag = rc;
-  if (rc == 0) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    if (std::find(g_pending.begin(), g_pending.end(), f) == g_pending.end()) g_pending.push_back(f);
-  }
+  if (rc == 0) mark_pending(f);
   return rc;
 }
 
@@ -777,32 +847,32 @@ int64_t spllt_hip_partition_get(void* fkeep, const char* name, void* buf, int64_
   std::vector<char> keep;
   int64_t elems = 0;
   partition_tables(f, owner, top, keep, elems);
-  std::string k(name);
-  auto raw = [&](const void* p, size_t bytes) -> int64_t {
-    if (buf && bytes) std::memcpy(buf, p, std::min<size_t>(bytes, (size_t)cap));
-    return (int64_t)bytes;
-  };
+  const std::string k(name);
+  const Out o{buf, cap};
   if (k == "arena_elems") {   // int64 x 2: doubles of the factor arena held on this rank's device, of the whole arena
     int64_t v[2] = {f->eng ? f->eng->arena_elems() : f->S->arena, f->S->arena};
-    return raw(v, sizeof v);
+    return o.bytes(v, sizeof v);
   }
-  if (k == "owner") return raw(owner.data(), owner.size() * sizeof(int));
+  if (k == "owner") return o.bytes(owner);
   if (k == "top_bcol_owner") {   // empty: the top tree is replicated
     ScheduleOptions so;
     std::vector<int> o2, top_owner;
     partition_options(*f->S, f->eo, o2, top_owner, so);
-    return raw(top_owner.data(), top_owner.size() * sizeof(int));
+    return o.bytes(top_owner);
   }
-  if (k == "top_bcols") return raw(top.data(), top.size() * sizeof(int));
-  if (k == "map_keep") return raw(keep.data(), keep.size());
+  if (k == "top_bcols") return o.bytes(top);
+  if (k == "map_keep") return o.bytes(keep);
   return -1;
 }
 
 int spllt_hip_get_factor(void* fkeep, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !out) return SPLLT_ERROR_PARAMETER;
-  int rc = ensure_hostL(f);
-  if (rc) return rc;
+  if (int rc = enter(f, nullptr, out ? nullptr : "", WAIT | FACTOR)) return rc;
+  if (!f->hostL_valid) {
+    f->hostL.resize((size_t)f->S->arena);
+    if (int rc = f->eng->download(f->hostL.data(), f->S->arena)) return rc;
+    f->hostL_valid = true;
+  }
   std::memcpy(out, f->hostL.data(), sizeof(double) * (size_t)std::min<int64_t>(count, f->S->arena));
   return 0;
 }
@@ -812,84 +882,57 @@ double* spllt_hip_device_factor(void* fkeep) {
   return (f && f->eng) ? f->eng->device_L() : nullptr;
 }
 
-// ---- what the features on a finished single-GPU factor share ----------------
-// the handle's engine with its factor finished, or an error flag (with the message in last_error)
-static int need_single_factor(Fkeep* f, const char* what) {
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  int rc = do_wait(f);
-  if (rc) return rc;
-  if (no_factor(f)) {
-    f->last_error = std::string(what) + ": nothing has been factorized on this handle";
-    return SPLLT_ERROR_PARAMETER;
-  }
-  if (f->eo.nranks > 1) {
-    f->last_error = std::string(what) + ": not available on a partitioned (multi-GPU) factor";
-    std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
-    return SPLLT_ERROR_UNIMPLEMENTED;
-  }
-  return 0;
+// ---- blocked, reproducible and product sweeps over many vectors --------------
+// what the argument checks of the vector calls name; nrhs also stands for nvec and nsamp
+static const char* vectors_bad(const Fkeep* f, int nrhs, const void* x, int64_t ldx, int job) {
+  if (!x) return "the array of right-hand sides is null";
+  if (nrhs < 0) return "nrhs < 0";
+  if (ldx < f->S->n) return "ldx < n";
+  if (job < 0 || job > 2) return "job is not 0, 1 or 2";
+  return nullptr;
 }
 
-// the message of a failed engine call: the feature's own, else the engine's
-static int feature_fail(Fkeep* f, int rc) {
-  if (!f->eng->feature_error().empty()) f->last_error = f->eng->feature_error();
-  else if (f->eng->status()) f->last_error = f->eng->error();
-  return rc;
-}
-
-// ---- blocked solve for many right-hand sides ------------------------------
-// argument checks that need no device, then the handle's engine with its factor finished
-static int solve_many_engine(Fkeep* f, const char* what, int nrhs, const void* x, int64_t ldx, int job) {
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  const char* bad = nullptr;
-  if (!x) bad = "the array of right-hand sides is null";
-  else if (nrhs < 0) bad = "nrhs < 0";
-  else if (ldx < f->S->n) bad = "ldx < n";
-  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
-  if (bad) {
-    f->last_error = std::string(what) + ": " + bad;
-    return SPLLT_ERROR_PARAMETER;
-  }
-  return need_single_factor(f, what);
+static int vectors_impl(const char* what, void* fkeep, int nrhs, double* x, int64_t ldx, int job,
+                        int (Engine::*host)(double*, int, int64_t, int), int (Engine::*dev)(double*, int, int64_t, int, bool),
+                        bool pivot_order) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (int rc = enter(f, what, vectors_bad(f, nrhs, x, ldx, job), SINGLE_F | WAIT | FACTOR)) return rc;
+  Engine& e = *f->eng;
+  return leave(f, host ? (e.*host)(x, nrhs, ldx, job) : (e.*dev)(x, nrhs, ldx, job, pivot_order));
 }
 
 int spllt_hip_solve_many(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_many_engine(f, "spllt_hip_solve_many", nrhs, x_host, ldx, job);
-  if (rc) return rc;
-  rc = f->eng->solve_many(x_host, nrhs, ldx, job);
-  return rc ? feature_fail(f, rc) : 0;
+  return vectors_impl("spllt_hip_solve_many", fkeep, nrhs, x_host, ldx, job, &Engine::solve_many, nullptr, false);
 }
 
 int spllt_hip_solve_many_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_many_engine(f, "spllt_hip_solve_many_dev", nrhs, x_dev, ldx, job);
-  if (rc) return rc;
-  rc = f->eng->solve_many_dev(x_dev, nrhs, ldx, job, pivot_order != 0);
-  return rc ? feature_fail(f, rc) : 0;
+  return vectors_impl("spllt_hip_solve_many_dev", fkeep, nrhs, x_dev, ldx, job, nullptr, &Engine::solve_many_dev,
+                      pivot_order != 0);
 }
 
-// ---- reproducible solve -----------------------------------------------------
 int spllt_hip_solve_repro(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_many_engine(f, "spllt_hip_solve_repro", nrhs, x_host, ldx, job);
-  if (rc) return rc;
-  rc = f->eng->solve_repro(x_host, nrhs, ldx, job);
-  return rc ? feature_fail(f, rc) : 0;
+  return vectors_impl("spllt_hip_solve_repro", fkeep, nrhs, x_host, ldx, job, &Engine::solve_repro, nullptr, false);
 }
 
 int spllt_hip_solve_repro_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_many_engine(f, "spllt_hip_solve_repro_dev", nrhs, x_dev, ldx, job);
-  if (rc) return rc;
-  rc = f->eng->solve_repro_dev(x_dev, nrhs, ldx, job, pivot_order != 0);
-  return rc ? feature_fail(f, rc) : 0;
+  return vectors_impl("spllt_hip_solve_repro_dev", fkeep, nrhs, x_dev, ldx, job, nullptr, &Engine::solve_repro_dev,
+                      pivot_order != 0);
+}
+
+int spllt_hip_factor_mult(void* fkeep, int nvec, double* x_host, int64_t ldx, int job) {
+  return vectors_impl("spllt_hip_factor_mult", fkeep, nvec, x_host, ldx, job, &Engine::factor_mult, nullptr, false);
+}
+
+int spllt_hip_factor_mult_dev(void* fkeep, int nvec, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  return vectors_impl("spllt_hip_factor_mult_dev", fkeep, nvec, x_dev, ldx, job, nullptr, &Engine::factor_mult_dev,
+                      pivot_order != 0);
 }
 
 int spllt_hip_set_reproducible_solve(void* fkeep, int on) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (on && f->eo.nranks > 1) {
+  if (on && f->eo.nranks > 1) {   // (a plain setter: refused without the stderr line of the guard)
     f->last_error = "spllt_hip_set_reproducible_solve: not available on a partitioned (multi-GPU) handle";
     return SPLLT_ERROR_UNIMPLEMENTED;
   }
@@ -898,136 +941,62 @@ int spllt_hip_set_reproducible_solve(void* fkeep, int on) {
   return before;
 }
 
-int spllt_hip_release_solve_repro(void* fkeep) {
+// ---- Gaussian sampling ---------------------------------------------------------
+static int sample_impl(const char* what, void* fkeep, int nsamp, double* x, int64_t ldx, int kind, uint64_t seed,
+                       uint64_t first_sample, const double* mean, bool dev) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (!f->eng) return 0;
-  int rc = do_wait(f);
-  if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
-  rc = f->eng->release_solve_repro();
-  return rc ? feature_fail(f, rc) : 0;
-}
-
-// ---- products with the factor, Gaussian sampling ----------------------------
-int spllt_hip_factor_mult(void* fkeep, int nvec, double* x_host, int64_t ldx, int job) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_many_engine(f, "spllt_hip_factor_mult", nvec, x_host, ldx, job);
-  if (rc) return rc;
-  rc = f->eng->factor_mult(x_host, nvec, ldx, job);
-  return rc ? feature_fail(f, rc) : 0;
-}
-
-int spllt_hip_factor_mult_dev(void* fkeep, int nvec, double* x_dev, int64_t ldx, int job, int pivot_order) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_many_engine(f, "spllt_hip_factor_mult_dev", nvec, x_dev, ldx, job);
-  if (rc) return rc;
-  rc = f->eng->factor_mult_dev(x_dev, nvec, ldx, job, pivot_order != 0);
-  return rc ? feature_fail(f, rc) : 0;
-}
-
-int spllt_hip_release_factor_mult(void* fkeep) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (!f->eng) return 0;
-  int rc = do_wait(f);
-  if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
-  rc = f->eng->release_factor_mult();
-  return rc ? feature_fail(f, rc) : 0;
-}
-
-static int sample_engine(Fkeep* f, const char* what, int nsamp, const void* x, int64_t ldx, int kind) {
-  if (f && f->S && x && nsamp >= 0 && ldx >= f->S->n && (kind < 0 || kind > 1)) {
-    f->last_error = std::string(what) + ": kind is not 0 (precision) or 1 (covariance)";
-    return SPLLT_ERROR_PARAMETER;
-  }
-  return solve_many_engine(f, what, nsamp, x, ldx, 0);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = vectors_bad(f, nsamp, x, ldx, 0);
+  if (!bad && (kind < 0 || kind > 1)) bad = "kind is not 0 (precision) or 1 (covariance)";
+  if (int rc = enter(f, what, bad, SINGLE_F | WAIT | FACTOR)) return rc;
+  f->eng->set_reproducible_solve(f->repro_solve);
+  return leave(f, f->eng->sample(x, nsamp, ldx, kind, seed, first_sample, mean, dev));
 }
 
 int spllt_hip_sample_dev(void* fkeep, int nsamp, double* x_dev, int64_t ldx, int kind, uint64_t seed,
                          uint64_t first_sample, const double* mean_dev) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = sample_engine(f, "spllt_hip_sample_dev", nsamp, x_dev, ldx, kind);
-  if (rc) return rc;
-  f->eng->set_reproducible_solve(f->repro_solve);
-  rc = f->eng->sample(x_dev, nsamp, ldx, kind, seed, first_sample, mean_dev, true);
-  return rc ? feature_fail(f, rc) : 0;
+  return sample_impl("spllt_hip_sample_dev", fkeep, nsamp, x_dev, ldx, kind, seed, first_sample, mean_dev, true);
 }
 
 int spllt_hip_sample(void* fkeep, int nsamp, double* x_host, int64_t ldx, int kind, uint64_t seed,
                      uint64_t first_sample, const double* mean_host) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = sample_engine(f, "spllt_hip_sample", nsamp, x_host, ldx, kind);
-  if (rc) return rc;
-  f->eng->set_reproducible_solve(f->repro_solve);
-  rc = f->eng->sample(x_host, nsamp, ldx, kind, seed, first_sample, mean_host, false);
-  return rc ? feature_fail(f, rc) : 0;
+  return sample_impl("spllt_hip_sample", fkeep, nsamp, x_host, ldx, kind, seed, first_sample, mean_host, false);
 }
 
 int spllt_hip_white_noise_dev(void* fkeep, int nsamp, double* z_dev, int64_t ldz, uint64_t seed, uint64_t first_sample) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_many_engine(f, "spllt_hip_white_noise_dev", nsamp, z_dev, ldz, 0);
-  if (rc) return rc;
-  rc = f->eng->white_noise_dev(z_dev, nsamp, ldz, seed, first_sample);
-  return rc ? feature_fail(f, rc) : 0;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (int rc = enter(f, "spllt_hip_white_noise_dev", vectors_bad(f, nsamp, z_dev, ldz, 0), SINGLE_F | WAIT | FACTOR))
+    return rc;
+  return leave(f, f->eng->white_noise_dev(z_dev, nsamp, ldz, seed, first_sample));
 }
 
 // ---- batched factorization --------------------------------------------------
-static int batch_param_error(Fkeep* f, const char* what, const char* bad) {
-  f->last_error = std::string(what) + ": " + bad;
-  return SPLLT_ERROR_PARAMETER;
-}
-
-static int batch_partitioned(Fkeep* f, const char* what) {
-  if (f->eo.nranks <= 1) return 0;
-  f->last_error = std::string(what) + ": not available on a partitioned (multi-GPU) handle";
-  std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
-  return SPLLT_ERROR_UNIMPLEMENTED;
-}
-
-// the handle's engine with a finished batch on it, or an error flag
-static int batch_reader(Fkeep* f, const char* what) {
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (int rc = batch_partitioned(f, what)) return rc;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (!f->eng || f->eng->batch_count() <= 0) return batch_param_error(f, what, "no batch has been factorized on this handle");
-  if (f->eng->pending()) (void)do_wait(f);   // (the single factorization shares the stream and the staging buffers)
-  return 0;
-}
-
 static int factor_batch_impl(void* akeep, void* fkeep, int nbatch, int nnz, const double* val, int64_t ldval, bool dev,
                              const char* what) {
-  Akeep* a = static_cast<Akeep*>(akeep);
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!a || !f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!val) return batch_param_error(f, what, "the array of values is null");
-  if (nbatch < 0) return batch_param_error(f, what, "nbatch < 0");
-  if ((int64_t)nnz != f->S->nnzA) return batch_param_error(f, what, "nnz does not match the analysed pattern");
-  if (ldval < nnz) return batch_param_error(f, what, "ldval < nnz");
-  if (int rc = batch_partitioned(f, what)) return rc;
-  if (nbatch == 0) return 0;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (f->eng && f->eng->pending()) (void)do_wait(f);
-  if (!f->eng) {
-    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
-    f->eng->set_exchange_buffer(f->xbuf);
-  }
-  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
+  if (!akeep || !analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!val) bad = "the array of values is null";
+  else if (nbatch < 0) bad = "nbatch < 0";
+  else if ((int64_t)nnz != f->S->nnzA) bad = "nnz does not match the analysed pattern";
+  else if (ldval < nnz) bad = "ldval < nnz";
+  // (EMPTY_FIRST: an empty batch is accepted on a dead handle)
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | ENGINE | (nbatch == 0 ? EMPTY | EMPTY_FIRST : 0)))
+    return done(rc);
   int rc = f->eng->factor_batch(val, dev, nbatch, ldval);
   if (rc == 0 || rc == SPLLT_ERROR_NOT_POSDEF) ++f->serial[1];   // (the members that are positive definite were factorized)
-  if (rc == SPLLT_ERROR_NOT_POSDEF) {
+  if (rc == SPLLT_ERROR_NOT_POSDEF) {   // -20 of the batch calls: the batch stands, the message says which members failed
     const std::vector<int>& fl = f->eng->batch_flags();
     int nbad = 0, first = -1;
     for (size_t b = 0; b < fl.size(); ++b)
       if (fl[b] != INT_MAX) { if (first < 0) first = (int)b; ++nbad; }
-    f->last_error = std::string(what) + ": " + std::to_string(nbad) + " of " + std::to_string(nbatch) +
-                    " members are not positive definite (first: member " + std::to_string(first) + ", pivot column " +
-                    std::to_string(first >= 0 ? fl[(size_t)first] : 0) + " in elimination order)";
-    return rc;
+    return fail(f, what, std::to_string(nbad) + " of " + std::to_string(nbatch) +
+                             " members are not positive definite (first: member " + std::to_string(first) +
+                             ", pivot column " + std::to_string(first >= 0 ? fl[(size_t)first] : 0) + " in elimination order)",
+                rc);
   }
-  return rc ? feature_fail(f, rc) : 0;
+  return leave(f, rc);
 }
 
 int spllt_hip_factor_batch(void* akeep, void* fkeep, int nbatch, int nnz, const double* val_host, int64_t ldval) {
@@ -1055,21 +1024,14 @@ int spllt_hip_batch_status(void* fkeep, int* flag, int* column, int capacity) {
 static int solve_batch_impl(void* fkeep, int nrhs, double* x, int64_t ldx, int job, bool dev, bool pivot_order,
                             const char* what) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!x) return batch_param_error(f, what, "the array of right-hand sides is null");
-  if (nrhs < 0) return batch_param_error(f, what, "nrhs < 0");
-  if (ldx < f->S->n) return batch_param_error(f, what, "ldx < n");
-  if (job < 0 || job > 2) return batch_param_error(f, what, "job is not 0, 1 or 2");
-  int rc = batch_reader(f, what);
-  if (rc) return rc;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (int rc = enter(f, what, vectors_bad(f, nrhs, x, ldx, job), SINGLE | WAIT_IGNORE | BATCH)) return rc;
   if (nrhs == 0) return 0;
-  rc = f->eng->solve_batch(x, dev, nrhs, ldx, job, pivot_order);
-  if (rc == SPLLT_ERROR_NOT_POSDEF) {
-    f->last_error = std::string(what) + ": the vectors of the members that are not positive definite were left unchanged "
-                                        "(spllt_hip_batch_status)";
-    return rc;
-  }
-  return rc ? feature_fail(f, rc) : 0;
+  int rc = f->eng->solve_batch(x, dev, nrhs, ldx, job, pivot_order);
+  if (rc == SPLLT_ERROR_NOT_POSDEF)   // -20 of the batch calls
+    return fail(f, what, "the vectors of the members that are not positive definite were left unchanged "
+                         "(spllt_hip_batch_status)", rc);
+  return leave(f, rc);
 }
 
 int spllt_hip_solve_batch(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
@@ -1081,36 +1043,19 @@ int spllt_hip_solve_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx,
 }
 
 // ---- refined solves ---------------------------------------------------------
-// the argument checks that need no device: `bad` from the caller's own checks, nnz, partition, a dead handle
-static int refine_engine(Fkeep* f, const char* what, int nnz, const char* bad) {
-  if (!bad && (int64_t)nnz != f->S->nnzA) bad = "nnz does not match the analysed pattern";
-  if (bad) return batch_param_error(f, what, bad);
-  if (int rc = batch_partitioned(f, what)) return rc;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  return 0;
-}
-
 static int matvec_impl(void* fkeep, int nnz, const double* val, int nvec, const double* x, int64_t ldx, double* y,
                        int64_t ldy, bool dev, bool pivot_order, const char* what) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
   const char* bad = nullptr;
   if (!val) bad = "the array of values is null";
   else if (!x || !y) bad = "a vector array is null";
   else if (nvec < 0) bad = "nvec < 0";
   else if (ldx < f->S->n) bad = "ldx < n";
   else if (ldy < f->S->n) bad = "ldy < n";
-  if (int rc = refine_engine(f, what, nnz, bad)) return rc;
-  if (nvec == 0) return 0;
-  if (f->eng && f->eng->pending()) (void)do_wait(f);
-  if (!f->eng) {
-    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
-    f->eng->set_exchange_buffer(f->xbuf);
-  }
-  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
-  int rc = f->eng->matvec(val, nvec, x, ldx, y, ldy, dev, pivot_order);
-  return rc ? feature_fail(f, rc) : 0;
+  else if ((int64_t)nnz != f->S->nnzA) bad = "nnz does not match the analysed pattern";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | ENGINE | (nvec == 0 ? EMPTY : 0))) return done(rc);
+  return leave(f, f->eng->matvec(val, nvec, x, ldx, y, ldy, dev, pivot_order));
 }
 
 int spllt_hip_matvec(void* fkeep, int nnz, const double* val_host, int nvec, const double* x_host, int64_t ldx,
@@ -1126,7 +1071,7 @@ int spllt_hip_matvec_dev(void* fkeep, int nnz, const double* val_dev, int nvec, 
 static int solve_refined_impl(void* fkeep, int nnz, const double* val, int nrhs, double* x, int64_t ldx, int method,
                               double tol, int max_iter, int* iterations, double* error, bool dev, const char* what) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
   const char* bad = nullptr;
   if (!val) bad = "the array of values is null";
   else if (!x) bad = "the array of right-hand sides is null";
@@ -1135,17 +1080,13 @@ static int solve_refined_impl(void* fkeep, int nnz, const double* val, int nrhs,
   else if (method != 0 && method != 1) bad = "method is not 0 (refinement) or 1 (PCG)";
   else if (!(tol > 0.0)) bad = "tol is not positive";
   else if (max_iter < 0) bad = "max_iter < 0";
-  if (int rc = refine_engine(f, what, nnz, bad)) return rc;
-  if (nrhs == 0) return 0;
-  if (int rc = do_wait(f)) return rc;
-  if (!f->eng || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
+  else if ((int64_t)nnz != f->S->nnzA) bad = "nnz does not match the analysed pattern";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT | FACTORED | (nrhs == 0 ? EMPTY : 0))) return done(rc);
   f->eng->set_reproducible_solve(f->repro_solve);
   int rc = f->eng->solve_refined(val, nrhs, x, ldx, dev, method, tol, max_iter, iterations, error);
-  if (rc == 1) {
-    f->last_error = std::string(what) + ": at least one vector did not reach tol (error[] says which)";
-    return 1;
-  }
-  return rc ? feature_fail(f, rc) : 0;
+  if (rc == 1)   // rc 1 of the refined solve: not an error, the vectors hold their best iterates
+    return fail(f, what, "at least one vector did not reach tol (error[] says which)", 1);
+  return leave(f, rc);
 }
 
 int spllt_hip_solve_refined(void* fkeep, int nnz, const double* val_host, int nrhs, double* x_host, int64_t ldx,
@@ -1160,58 +1101,35 @@ int spllt_hip_solve_refined_dev(void* fkeep, int nnz, const double* val_dev, int
                             "spllt_hip_solve_refined_dev");
 }
 
-int spllt_hip_release_refine(void* fkeep) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (!f->eng) return 0;
-  if (f->eng->pending()) (void)do_wait(f);
-  int rc = f->eng->release_refine();
-  return rc ? feature_fail(f, rc) : 0;
-}
-
 // ---- low-rank update / downdate of the factor ------------------------------------------------------
 int64_t spllt_hip_updown_plan(void* fkeep, int k, const int* wptr, const int* wrow, int32_t* bcols, int64_t capacity) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
   std::vector<int> plan;
   std::string why;
-  if (build_updown_plan(*f->S, k, wptr, wrow, plan, nullptr, &why)) return batch_param_error(f, "spllt_hip_updown_plan", why.c_str());
-  return copy_out(plan, bcols, capacity);
+  if (build_updown_plan(*f->S, k, wptr, wrow, plan, nullptr, &why)) return fail(f, "spllt_hip_updown_plan", why);
+  return Out{bcols, capacity}.elems(plan);
 }
 
 int spllt_hip_updown(void* fkeep, int k, const int* wptr, const int* wrow, const double* wval, int sign) {
   const char* what = "spllt_hip_updown";
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  // every check that needs no device first: a rejected call touches nothing
-  if (sign != 1 && sign != -1) return batch_param_error(f, what, "sign is not +1 or -1");
-  if (k > 0 && !wval) return batch_param_error(f, what, "the array of values is null");
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
   std::vector<int> plan, first;
-  {
-    std::string why;
-    if (build_updown_plan(*f->S, k, wptr, wrow, plan, &first, &why)) return batch_param_error(f, what, why.c_str());
-  }
-  for (int e = 0; k > 0 && e < wptr[k] - 1; ++e)
-    if (!std::isfinite(wval[e])) return batch_param_error(f, what, "a value of W is not finite");
-  if (int rc = batch_partitioned(f, what)) return rc;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (int rc = do_wait(f)) return rc;
-  if (!f->eng) {
-    // no factorization yet: an engine only to tell "no device" from "nothing factorized"
-    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
-    f->eng->set_exchange_buffer(f->xbuf);
-  }
-  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
-  if (no_factor(f) || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
+  std::string why;
+  const char* bad = nullptr;
+  if (sign != 1 && sign != -1) bad = "sign is not +1 or -1";
+  else if (k > 0 && !wval) bad = "the array of values is null";
+  else if (build_updown_plan(*f->S, k, wptr, wrow, plan, &first, &why)) bad = why.c_str();
+  for (int e = 0; !bad && k > 0 && e < wptr[k] - 1; ++e)
+    if (!std::isfinite(wval[e])) bad = "a value of W is not finite";
+  // (without a factorization the engine is created only to tell "no device" from "nothing factorized")
+  if (int rc = enter(f, what, bad, SINGLE | WAIT | ENGINE | FACTORED)) return rc;
   const int rc = f->eng->updown(k, wptr, wrow, wval, sign, plan, first);
   f->hostL_valid = false;
   ++f->serial[0];   // (a failed downdate has changed the factor as well: it is invalid now)
-  if (rc) {
-    feature_fail(f, rc);
-    if (rc == SPLLT_ERROR_NOT_POSDEF) std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
-  }
+  leave(f, rc);
+  if (rc == SPLLT_ERROR_NOT_POSDEF) std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
   return rc;
 }
 
@@ -1230,42 +1148,28 @@ int spllt_hip_updown_info(void* fkeep, int64_t out[4]) {
 }
 
 // ---- sparse right-hand sides and selected outputs --------------------------------------------------
-// every check that needs no device (a rejected call touches nothing), then the handle's engine with its factor
-// finished; out: the output array, ld against the number of wanted entries (gram: against k)
-static int solve_sparse_engine(Fkeep* f, const char* what, int k, const int* bptr, const int* brow, const double* bval,
-                               int nsel, const int* sel, const void* out, int64_t ld, int64_t ld_min, int job) {
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!out) return batch_param_error(f, what, "the output array is null");
-  if (job < 0 || job > 2) return batch_param_error(f, what, "job is not 0, 1 or 2");
-  {
-    std::string why;
-    if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) return batch_param_error(f, what, why.c_str());
-  }
-  if (k > 0 && bptr[k] > bptr[0] && !bval) return batch_param_error(f, what, "the array of values is null");
-  if (ld < ld_min) return batch_param_error(f, what, "the leading dimension of the output is too small");
-  if (int rc = batch_partitioned(f, what)) return rc;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (int rc = do_wait(f)) return rc;
-  if (!f->eng) {
-    // no factorization yet: an engine only to tell "no device" from "nothing factorized"
-    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
-    f->eng->set_exchange_buffer(f->xbuf);
-  }
-  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
-  if (no_factor(f) || !f->eng->factored()) return batch_param_error(f, what, "nothing has been factorized on this handle");
-  return 0;
+// the ladder of the sparse solves; out: the output array, ld against the number of wanted entries (gram: against k)
+static int solve_sparse_enter(Fkeep* f, const char* what, int k, const int* bptr, const int* brow, const double* bval,
+                              int nsel, const int* sel, const void* out, int64_t ld, int64_t ld_min, int job) {
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  std::string why;
+  const char* bad = nullptr;
+  if (!out) bad = "the output array is null";
+  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
+  else if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) bad = why.c_str();
+  else if (k > 0 && bptr[k] > bptr[0] && !bval) bad = "the array of values is null";
+  else if (ld < ld_min) bad = "the leading dimension of the output is too small";
+  // (without a factorization the engine is created only to tell "no device" from "nothing factorized")
+  return enter(f, what, bad, SINGLE | WAIT | ENGINE | FACTORED);
 }
 
 static int solve_sparse_impl(const char* what, void* fkeep, int k, const int* bptr, const int* brow, const double* bval,
                              int nsel, const int* sel, double* x, int64_t ldx, int job, bool dev) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!sel || nsel < 0) { sel = nullptr; nsel = -1; }
-  const int64_t nout = !f || !f->S ? 0 : (sel ? nsel : f->S->n);
-  int rc = solve_sparse_engine(f, what, k, bptr, brow, bval, nsel, sel, x, ldx, nout, job);
-  if (rc) return rc;
-  rc = f->eng->solve_sparse(k, bptr, brow, bval, nsel, sel, x, ldx, job, dev);
-  return rc ? feature_fail(f, rc) : 0;
+  const int64_t nout = !analysed(f) ? 0 : (sel ? nsel : f->S->n);
+  if (int rc = solve_sparse_enter(f, what, k, bptr, brow, bval, nsel, sel, x, ldx, nout, job)) return rc;
+  return leave(f, f->eng->solve_sparse(k, bptr, brow, bval, nsel, sel, x, ldx, job, dev));
 }
 
 int spllt_hip_solve_sparse(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, int nsel,
@@ -1280,12 +1184,10 @@ int spllt_hip_solve_sparse_dev(void* fkeep, int k, const int* bptr, const int* b
 
 int spllt_hip_gram_sparse(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, double* g_host,
                           int64_t ldg) {
-  const char* what = "spllt_hip_gram_sparse";
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = solve_sparse_engine(f, what, k, bptr, brow, bval, -1, nullptr, g_host, ldg, k, 0);
-  if (rc) return rc;
-  rc = f->eng->gram_sparse(k, bptr, brow, bval, g_host, ldg);
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = solve_sparse_enter(f, "spllt_hip_gram_sparse", k, bptr, brow, bval, -1, nullptr, g_host, ldg, k, 0))
+    return rc;
+  return leave(f, f->eng->gram_sparse(k, bptr, brow, bval, g_host, ldg));
 }
 
 int spllt_hip_solve_sparse_plan(void* fkeep, int k, const int* bptr, const int* brow, int nsel, const int* sel, int job,
@@ -1293,18 +1195,16 @@ int spllt_hip_solve_sparse_plan(void* fkeep, int k, const int* bptr, const int* 
                                 int64_t counts[2]) {
   const char* what = "spllt_hip_solve_sparse_plan";
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!counts) return batch_param_error(f, what, "counts is null");
-  if (job < 0 || job > 2) return batch_param_error(f, what, "job is not 0, 1 or 2");
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (!counts) return fail(f, what, "counts is null");
+  if (job < 0 || job > 2) return fail(f, what, "job is not 0, 1 or 2");
   if (!sel || nsel < 0) { sel = nullptr; nsel = -1; }
   std::string why;
-  if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) return batch_param_error(f, what, why.c_str());
+  if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) return fail(f, what, why);
   SolveSparsePlan P;
   build_solve_sparse_plan(*f->S, 0, k, bptr, brow, nsel, sel, job, P);
-  counts[0] = (int64_t)P.fwd.size();
-  counts[1] = (int64_t)P.bwd.size();
-  if (fwd_bcols) (void)copy_out(P.fwd, fwd_bcols, fwd_cap);
-  if (bwd_bcols) (void)copy_out(P.bwd, bwd_bcols, bwd_cap);
+  counts[0] = Out{fwd_bcols, fwd_cap}.elems(P.fwd);
+  counts[1] = Out{bwd_bcols, bwd_cap}.elems(P.bwd);
   return 0;
 }
 
@@ -1315,28 +1215,14 @@ int spllt_hip_solve_sparse_info(void* fkeep, int64_t out[6]) {
   return 0;
 }
 
-int spllt_hip_release_solve_sparse(void* fkeep) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (!f->eng) return 0;
-  int rc = do_wait(f);
-  if (rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
-  rc = f->eng->release_solve_sparse();
-  return rc ? feature_fail(f, rc) : 0;
-}
-
+// ---- readers of the batch ------------------------------------------------------
 int spllt_hip_get_factor_batch(void* fkeep, int member, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   const char* what = "spllt_hip_get_factor_batch";
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!out) return batch_param_error(f, what, "the output array is null");
-  if (count < 0) return batch_param_error(f, what, "count < 0");
-  int rc = batch_reader(f, what);
-  if (rc) return rc;
-  if (member < 0 || member >= f->eng->batch_count()) return batch_param_error(f, what, "member is not in [0, nbatch)");
-  rc = f->eng->download_batch(member, out, count);
-  return rc ? feature_fail(f, rc) : 0;
+  const char* bad = !out ? "the output array is null" : count < 0 ? "count < 0" : nullptr;
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (member < 0 || member >= f->eng->batch_count()) return fail(f, what, "member is not in [0, nbatch)");
+  return leave(f, f->eng->download_batch(member, out, count));
 }
 
 double* spllt_hip_device_factor_batch(void* fkeep, int64_t* member_stride) {
@@ -1348,13 +1234,9 @@ double* spllt_hip_device_factor_batch(void* fkeep, int64_t* member_stride) {
 
 int spllt_hip_log_det_batch(void* fkeep, double* out) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  const char* what = "spllt_hip_log_det_batch";
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!out) return batch_param_error(f, what, "the output array is null");
-  int rc = batch_reader(f, what);
-  if (rc) return rc;
-  rc = f->eng->log_det_batch(out);
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, "spllt_hip_log_det_batch", out ? nullptr : "the output array is null", SINGLE | WAIT_IGNORE | BATCH))
+    return rc;
+  return leave(f, f->eng->log_det_batch(out));
 }
 
 int spllt_hip_batch_launches(void* fkeep) {
@@ -1363,59 +1245,28 @@ int spllt_hip_batch_launches(void* fkeep) {
   return (f->eng && !f->dead) ? f->eng->batch_launches() : 0;
 }
 
-int spllt_hip_release_batch(void* fkeep) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f) return SPLLT_ERROR_PARAMETER;
-  if (!f->eng || f->dead) return 0;
-  if (f->eng->pending()) (void)do_wait(f);
-  int rc = f->eng->release_batch();
-  return rc ? feature_fail(f, rc) : 0;
-}
-
 // ---- batched selected inversion ------------------------------------------------
-// the handle's engine with a valid batched inverse on it, or an error flag
-static int batch_inverse_reader(Fkeep* f, const char* what) {
-  int rc = batch_reader(f, what);
-  if (rc) return rc;
-  if (!f->eng->batch_inverse_valid())
-    return batch_param_error(f, what, "no selected inverse of the current batch (call spllt_hip_selected_inverse_batch "
-                                      "after every spllt_hip_factor_batch)");
-  return 0;
-}
-
-static int batch_member_failed(Fkeep* f, const char* what, int member) {
-  f->last_error = std::string(what) + ": member " + std::to_string(member) + " is not positive definite: it has no inverse "
-                                                                              "(spllt_hip_batch_status)";
-  return SPLLT_ERROR_NOT_POSDEF;
-}
-
 int spllt_hip_selected_inverse_batch(void* fkeep) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   const char* what = "spllt_hip_selected_inverse_batch";
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  int rc = batch_reader(f, what);
-  if (rc) return rc;
-  rc = f->eng->selected_inverse_batch();
-  if (rc == SPLLT_ERROR_NOT_POSDEF) {
-    f->last_error = std::string(what) + ": the members that are not positive definite were skipped, the others are "
-                                        "inverted (spllt_hip_batch_status)";
-    return rc;
-  }
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, what, nullptr, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  int rc = f->eng->selected_inverse_batch();
+  if (rc == SPLLT_ERROR_NOT_POSDEF)   // -20 of the batch calls
+    return fail(f, what, "the members that are not positive definite were skipped, the others are inverted "
+                         "(spllt_hip_batch_status)", rc);
+  return leave(f, rc);
 }
 
 int spllt_hip_get_inverse_batch(void* fkeep, int member, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   const char* what = "spllt_hip_get_inverse_batch";
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!out) return batch_param_error(f, what, "the output array is null");
-  if (count < 0) return batch_param_error(f, what, "count < 0");
-  int rc = batch_inverse_reader(f, what);
-  if (rc) return rc;
-  if (member < 0 || member >= f->eng->batch_count()) return batch_param_error(f, what, "member is not in [0, nbatch)");
-  if (f->eng->batch_flags()[(size_t)member] != INT_MAX) return batch_member_failed(f, what, member);
-  rc = f->eng->download_inverse_batch(member, out, count);
-  return rc ? feature_fail(f, rc) : 0;
+  const char* bad = !out ? "the output array is null" : count < 0 ? "count < 0" : nullptr;
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH | BATCH_INVERSE)) return rc;
+  if (member < 0 || member >= f->eng->batch_count()) return fail(f, what, "member is not in [0, nbatch)");
+  if (f->eng->batch_flags()[(size_t)member] != INT_MAX)
+    return fail(f, what, "member " + std::to_string(member) + " is not positive definite: it has no inverse "
+                         "(spllt_hip_batch_status)", SPLLT_ERROR_NOT_POSDEF);
+  return leave(f, f->eng->download_inverse_batch(member, out, count));
 }
 
 double* spllt_hip_device_inverse_batch(void* fkeep, int64_t* member_stride) {
@@ -1425,40 +1276,28 @@ double* spllt_hip_device_inverse_batch(void* fkeep, int64_t* member_stride) {
   return f->eng->device_inverse_batch(member_stride);
 }
 
-int spllt_hip_inverse_diag_batch(void* fkeep, double* out, int64_t ldout) {
+// one row of `width` values per member; ld_name: what a short leading dimension is called
+static int batch_rows_impl(const char* what, void* fkeep, double* out, int64_t ldout, bool nnz_wide, const char* ld_name,
+                           int (Engine::*fn)(double*, int64_t)) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  const char* what = "spllt_hip_inverse_diag_batch";
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!out) return batch_param_error(f, what, "the output array is null");
-  if (ldout < f->S->n) return batch_param_error(f, what, "ldout < n");
-  int rc = batch_inverse_reader(f, what);
-  if (rc) return rc;
-  rc = f->eng->inverse_diag_batch(out, ldout);
-  return rc ? feature_fail(f, rc) : 0;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = !out ? "the output array is null" : ldout < (nnz_wide ? f->S->nnzA : f->S->n) ? ld_name : nullptr;
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH | BATCH_INVERSE)) return rc;
+  return leave(f, (f->eng.get()->*fn)(out, ldout));
+}
+
+int spllt_hip_inverse_diag_batch(void* fkeep, double* out, int64_t ldout) {
+  return batch_rows_impl("spllt_hip_inverse_diag_batch", fkeep, out, ldout, false, "ldout < n", &Engine::inverse_diag_batch);
 }
 
 int spllt_hip_inverse_on_pattern_batch(void* fkeep, double* out, int64_t ldout) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  const char* what = "spllt_hip_inverse_on_pattern_batch";
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!out) return batch_param_error(f, what, "the output array is null");
-  if (ldout < f->S->nnzA) return batch_param_error(f, what, "ldout < nnz");
-  int rc = batch_inverse_reader(f, what);
-  if (rc) return rc;
-  rc = f->eng->inverse_on_pattern_batch(out, ldout);
-  return rc ? feature_fail(f, rc) : 0;
+  return batch_rows_impl("spllt_hip_inverse_on_pattern_batch", fkeep, out, ldout, true, "ldout < nnz",
+                         &Engine::inverse_on_pattern_batch);
 }
 
 int spllt_hip_inverse_on_pattern_batch_dev(void* fkeep, double* out_dev, int64_t ldout) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  const char* what = "spllt_hip_inverse_on_pattern_batch_dev";
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!out_dev) return batch_param_error(f, what, "the output array is null");
-  if (ldout < f->S->nnzA) return batch_param_error(f, what, "ldout < nnz");
-  int rc = batch_inverse_reader(f, what);
-  if (rc) return rc;
-  rc = f->eng->inverse_on_pattern_batch_dev(out_dev, ldout);
-  return rc ? feature_fail(f, rc) : 0;
+  return batch_rows_impl("spllt_hip_inverse_on_pattern_batch_dev", fkeep, out_dev, ldout, true, "ldout < nnz",
+                         &Engine::inverse_on_pattern_batch_dev);
 }
 
 int spllt_hip_batch_selinv_launches(void* fkeep) {
@@ -1467,42 +1306,18 @@ int spllt_hip_batch_selinv_launches(void* fkeep) {
   return (f->eng && !f->dead) ? f->eng->batch_selinv_launches() : 0;
 }
 
-int spllt_hip_release_inverse_batch(void* fkeep) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f) return SPLLT_ERROR_PARAMETER;
-  if (!f->eng || f->dead) return 0;
-  if (f->eng->pending()) (void)do_wait(f);
-  int rc = f->eng->release_inverse_batch();
-  return rc ? feature_fail(f, rc) : 0;
-}
-
 // ---- selected inversion ---------------------------------------------------
-static int selinv_need_z(Fkeep* f, const char* what) {
-  int rc = need_single_factor(f, what);
-  if (rc) return rc;
-  if (!f->eng->inverse_valid()) {
-    f->last_error = std::string(what) + ": no selected inverse of the current factor (call spllt_hip_selected_inverse "
-                                        "after every factorization)";
-    return SPLLT_ERROR_PARAMETER;
-  }
-  return 0;
-}
-
+// (a null output array of these older calls is refused without a message: bad = "")
 int spllt_hip_selected_inverse(void* fkeep) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = need_single_factor(f, "spllt_hip_selected_inverse");
-  if (rc) return rc;
-  rc = f->eng->selected_inverse();
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, "spllt_hip_selected_inverse", nullptr, SINGLE_F | WAIT | FACTOR)) return rc;
+  return leave(f, f->eng->selected_inverse());
 }
 
 int spllt_hip_get_inverse(void* fkeep, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!out) return SPLLT_ERROR_PARAMETER;
-  int rc = selinv_need_z(f, "spllt_hip_get_inverse");
-  if (rc) return rc;
-  rc = f->eng->download_inverse(out, count);
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, "spllt_hip_get_inverse", out ? nullptr : "", SINGLE_F | WAIT | FACTOR | INVERSE)) return rc;
+  return leave(f, f->eng->download_inverse(out, count));
 }
 
 double* spllt_hip_device_inverse(void* fkeep) {
@@ -1512,34 +1327,31 @@ double* spllt_hip_device_inverse(void* fkeep) {
 
 int spllt_hip_inverse_diag(void* fkeep, double* out, int n) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!out) return SPLLT_ERROR_PARAMETER;
-  int rc = selinv_need_z(f, "spllt_hip_inverse_diag");
-  if (rc) return rc;
-  if (n != f->S->n) {
-    f->last_error = "spllt_hip_inverse_diag: n = " + std::to_string(n) + " does not match the analysed order " +
-                    std::to_string(f->S->n);
-    return SPLLT_ERROR_PARAMETER;
-  }
-  rc = f->eng->inverse_diag(out, n);
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, "spllt_hip_inverse_diag", out ? nullptr : "", SINGLE_F | WAIT | FACTOR | INVERSE)) return rc;
+  if (n != f->S->n)
+    return fail(f, "spllt_hip_inverse_diag", "n = " + std::to_string(n) + " does not match the analysed order " +
+                                             std::to_string(f->S->n));
+  return leave(f, f->eng->inverse_diag(out, n));
+}
+
+static int inverse_on_pattern_impl(const char* what, void* fkeep, double* out, int (Engine::*fn)(double*)) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (int rc = enter(f, what, out ? nullptr : "", SINGLE_F | WAIT | FACTOR | INVERSE)) return rc;
+  return leave(f, (f->eng.get()->*fn)(out));
 }
 
 int spllt_hip_inverse_on_pattern(void* fkeep, double* out) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!out) return SPLLT_ERROR_PARAMETER;
-  int rc = selinv_need_z(f, "spllt_hip_inverse_on_pattern");
-  if (rc) return rc;
-  rc = f->eng->inverse_on_pattern(out);
-  return rc ? feature_fail(f, rc) : 0;
+  return inverse_on_pattern_impl("spllt_hip_inverse_on_pattern", fkeep, out, &Engine::inverse_on_pattern);
 }
 
 int spllt_hip_inverse_on_pattern_dev(void* fkeep, double* out_dev) {
+  return inverse_on_pattern_impl("spllt_hip_inverse_on_pattern_dev", fkeep, out_dev, &Engine::inverse_on_pattern_dev);
+}
+
+int spllt_hip_log_det(void* fkeep, double* out) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!out_dev) return SPLLT_ERROR_PARAMETER;
-  int rc = selinv_need_z(f, "spllt_hip_inverse_on_pattern_dev");
-  if (rc) return rc;
-  rc = f->eng->inverse_on_pattern_dev(out_dev);
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, "spllt_hip_log_det", out ? nullptr : "", SINGLE_F | WAIT | FACTOR)) return rc;
+  return leave(f, f->eng->log_det(out));
 }
 
 int64_t spllt_hip_factor_serial(const void* fkeep, int which) {
@@ -1549,45 +1361,35 @@ int64_t spllt_hip_factor_serial(const void* fkeep, int which) {
 }
 
 // ---- sampled outer product on the analysed pattern ---------------------------------------------------
-// every check that needs no device (a rejected call touches nothing), then the handle's engine: the operation
-// needs the analysis only, so an engine is created when the handle has none yet
+// the operation needs the analysis only, so an engine is created when the handle has none yet
 static int pattern_outer_impl(const char* what, void* fkeep, int nbatch, int nvec, const double* u, int64_t ldu,
                               const double* v, int64_t ldv, double alpha, double* out, int64_t ldout, bool dev) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (!u || !v) return batch_param_error(f, what, "a vector array is null");
-  if (!out) return batch_param_error(f, what, "the output array is null");
-  if (nbatch < 0) return batch_param_error(f, what, "nbatch < 0");
-  if (nvec < 0) return batch_param_error(f, what, "nvec < 0");
-  if (ldu < f->S->n) return batch_param_error(f, what, "ldu < n");
-  if (ldv < f->S->n) return batch_param_error(f, what, "ldv < n");
-  if (ldout < f->S->nnzA) return batch_param_error(f, what, "ldout < nnz");
-  if (int rc = batch_partitioned(f, what)) return rc;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  if (nbatch == 0) return 0;
-  if (f->eng && f->eng->pending()) (void)do_wait(f);
-  if (!f->eng) {
-    f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-    if (!f->eng) return SPLLT_ERROR_ALLOCATION;
-    f->eng->set_exchange_buffer(f->xbuf);
-  }
-  if (f->eng->status()) { f->last_error = f->eng->error(); return f->eng->status(); }
-  int rc = f->eng->pattern_outer(nbatch, nvec, u, ldu, v, ldv, alpha, out, ldout, dev);
-  return rc ? feature_fail(f, rc) : 0;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!u || !v) bad = "a vector array is null";
+  else if (!out) bad = "the output array is null";
+  else if (nbatch < 0) bad = "nbatch < 0";
+  else if (nvec < 0) bad = "nvec < 0";
+  else if (ldu < f->S->n) bad = "ldu < n";
+  else if (ldv < f->S->n) bad = "ldv < n";
+  else if (ldout < f->S->nnzA) bad = "ldout < nnz";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | ENGINE | (nbatch == 0 ? EMPTY : 0))) return done(rc);
+  return leave(f, f->eng->pattern_outer(nbatch, nvec, u, ldu, v, ldv, alpha, out, ldout, dev));
 }
 
 int spllt_hip_pattern_outer(void* fkeep, int nvec, const double* u_host, int64_t ldu, const double* v_host, int64_t ldv,
                             double alpha, double* out_host) {
   const Fkeep* f = static_cast<const Fkeep*>(fkeep);
   return pattern_outer_impl("spllt_hip_pattern_outer", fkeep, 1, nvec, u_host, ldu, v_host, ldv, alpha, out_host,
-                            f && f->S ? f->S->nnzA : 0, false);
+                            analysed(f) ? f->S->nnzA : 0, false);
 }
 
 int spllt_hip_pattern_outer_dev(void* fkeep, int nvec, const double* u_dev, int64_t ldu, const double* v_dev, int64_t ldv,
                                 double alpha, double* out_dev) {
   const Fkeep* f = static_cast<const Fkeep*>(fkeep);
   return pattern_outer_impl("spllt_hip_pattern_outer_dev", fkeep, 1, nvec, u_dev, ldu, v_dev, ldv, alpha, out_dev,
-                            f && f->S ? f->S->nnzA : 0, true);
+                            analysed(f) ? f->S->nnzA : 0, true);
 }
 
 int spllt_hip_pattern_outer_batch_dev(void* fkeep, int nbatch, int nvec, const double* u_dev, int64_t ldu,
@@ -1596,53 +1398,24 @@ int spllt_hip_pattern_outer_batch_dev(void* fkeep, int nbatch, int nvec, const d
                             out_dev, ldout, true);
 }
 
-int spllt_hip_log_det(void* fkeep, double* out) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!out) return SPLLT_ERROR_PARAMETER;
-  int rc = need_single_factor(f, "spllt_hip_log_det");
-  if (rc) return rc;
-  rc = f->eng->log_det(out);
-  return rc ? feature_fail(f, rc) : 0;
-}
-
-int spllt_hip_release_inverse(void* fkeep) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f) return SPLLT_ERROR_PARAMETER;
-  if (!f->eng || f->dead) return 0;
-  if (f->eng->pending()) do_wait(f);
-  int rc = f->eng->release_inverse();
-  return rc ? feature_fail(f, rc) : 0;
-}
-
 // ---- reverse-mode derivative of the factor --------------------------------------------------------
-// the argument checks that need no device, then the handle's engine with its factor finished
-static int fadj_engine(Fkeep* f, const char* what, const char* bad) {
-  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
-  if (bad) {
-    f->last_error = std::string(what) + ": " + bad;
-    return SPLLT_ERROR_PARAMETER;
-  }
-  if (int rc = batch_partitioned(f, what)) return rc;
-  return need_single_factor(f, what);
-}
+constexpr unsigned kAdjoint = SINGLE | WAIT | FACTOR;
 
 static int fadj_seed_impl(const char* what, void* fkeep, int nvec, const double* a, const double* b, int64_t ld,
                           double alpha, int accumulate, int order_flags, bool dev) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
   const char* bad = nullptr;
-  if (f && f->S) {
-    if (!a || !b) bad = "a vector array is null";
-    else if (nvec < 0) bad = "nvec < 0";
-    else if (ld < f->S->n) bad = "ld < n";
-    else if (accumulate < 0 || accumulate > 1) bad = "accumulate is not 0 or 1";
-    else if (order_flags < 0 || order_flags > 3) bad = "order_flags is not 0 .. 3";
-  }
-  int rc = fadj_engine(f, what, bad);
-  if (rc) return rc;
-  rc = f->eng->fadj_seed(nvec, a, b, ld, alpha, accumulate != 0, order_flags, dev);
+  if (!a || !b) bad = "a vector array is null";
+  else if (nvec < 0) bad = "nvec < 0";
+  else if (ld < f->S->n) bad = "ld < n";
+  else if (accumulate < 0 || accumulate > 1) bad = "accumulate is not 0 or 1";
+  else if (order_flags < 0 || order_flags > 3) bad = "order_flags is not 0 .. 3";
+  if (int rc = enter(f, what, bad, kAdjoint)) return rc;
+  const int rc = f->eng->fadj_seed(nvec, a, b, ld, alpha, accumulate != 0, order_flags, dev);
   if (rc == SPLLT_ERROR_PARAMETER && f->eng->feature_error().empty())
     f->last_error = std::string(what) + ": the factor is not available";
-  return rc ? feature_fail(f, rc) : 0;
+  return leave(f, rc);
 }
 
 int spllt_hip_factor_adjoint_seed_dev(void* fkeep, int nvec, const double* a_dev, const double* b_dev, int64_t ld,
@@ -1659,29 +1432,19 @@ int spllt_hip_factor_adjoint_seed(void* fkeep, int nvec, const double* a_host, c
 
 int spllt_hip_set_factor_adjoint(void* fkeep, const double* host_arena, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  const char* what = "spllt_hip_set_factor_adjoint";
-  const char* bad = nullptr;
-  if (f && f->S) {
-    if (!host_arena) bad = "the arena is null";
-    else if (count < f->S->arena) bad = "count is smaller than the factor arena";
-  }
-  int rc = fadj_engine(f, what, bad);
-  if (rc) return rc;
-  rc = f->eng->fadj_upload(host_arena, count);
-  return rc ? feature_fail(f, rc) : 0;
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = !host_arena ? "the arena is null" : count < f->S->arena ? "count is smaller than the factor arena" : nullptr;
+  if (int rc = enter(f, "spllt_hip_set_factor_adjoint", bad, kAdjoint)) return rc;
+  return leave(f, f->eng->fadj_upload(host_arena, count));
 }
 
 int spllt_hip_get_factor_adjoint(void* fkeep, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   const char* what = "spllt_hip_get_factor_adjoint";
-  int rc = fadj_engine(f, what, (f && f->S && !out) ? "the output array is null" : nullptr);
-  if (rc) return rc;
-  if (f->eng->fadj_state() == Engine::FADJ_UNSEEDED) {
-    f->last_error = std::string(what) + ": no factor adjoint of the current factor (seed it after every factorization)";
-    return SPLLT_ERROR_PARAMETER;
-  }
-  rc = f->eng->fadj_download(out, count);
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, what, out ? nullptr : "the output array is null", kAdjoint)) return rc;
+  if (f->eng->fadj_state() == Engine::FADJ_UNSEEDED)
+    return fail(f, what, "no factor adjoint of the current factor (seed it after every factorization)");
+  return leave(f, f->eng->fadj_download(out, count));
 }
 
 double* spllt_hip_device_factor_adjoint(void* fkeep) {
@@ -1691,10 +1454,8 @@ double* spllt_hip_device_factor_adjoint(void* fkeep) {
 
 static int fadj_sweep_impl(const char* what, void* fkeep, double* gval, bool dev) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  int rc = fadj_engine(f, what, (f && f->S && !gval) ? "the gradient array is null" : nullptr);
-  if (rc) return rc;
-  rc = f->eng->fadj_sweep(gval, dev);
-  return rc ? feature_fail(f, rc) : 0;
+  if (int rc = enter(f, what, gval ? nullptr : "the gradient array is null", kAdjoint)) return rc;
+  return leave(f, f->eng->fadj_sweep(gval, dev));
 }
 
 int spllt_hip_factor_adjoint_dev(void* fkeep, double* gval_dev) {
@@ -1705,14 +1466,30 @@ int spllt_hip_factor_adjoint(void* fkeep, double* gval_host) {
   return fadj_sweep_impl("spllt_hip_factor_adjoint", fkeep, gval_host, false);
 }
 
-int spllt_hip_release_factor_adjoint(void* fkeep) {
+// ---- giving a feature's device memory back ---------------------------------------------------------
+// Three shapes have grown, and they differ observably; the differences stay, as flags:
+//   WAIT_NOT_POSDEF  a pending failure other than "not positive definite" is returned, nothing released
+//   WAIT_IGNORE      whatever the pending factorization reports, the memory is released
+//   LENIENT          a handle without an analysis or a dead one has nothing to release: 0 (else -10 / -30)
+static int release(void* fkeep, int (Engine::*fn)(), unsigned need) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f) return SPLLT_ERROR_PARAMETER;
-  if (!f->eng || f->dead) return 0;
-  if (f->eng->pending()) do_wait(f);
-  int rc = f->eng->release_factor_adjoint();
-  return rc ? feature_fail(f, rc) : 0;
+  const bool lenient = (need & LENIENT) != 0;
+  if (!f || (!lenient && !f->S)) return SPLLT_ERROR_PARAMETER;
+  if (f->dead) return lenient ? 0 : SPLLT_ERROR_HIP;
+  if (!f->eng) return 0;
+  const int rc = do_wait(f);
+  if ((need & WAIT_NOT_POSDEF) && rc && rc != SPLLT_ERROR_NOT_POSDEF) return rc;
+  return leave(f, (f->eng.get()->*fn)());
 }
+
+int spllt_hip_release_solve_repro(void* fkeep) { return release(fkeep, &Engine::release_solve_repro, WAIT_NOT_POSDEF); }
+int spllt_hip_release_factor_mult(void* fkeep) { return release(fkeep, &Engine::release_factor_mult, WAIT_NOT_POSDEF); }
+int spllt_hip_release_solve_sparse(void* fkeep) { return release(fkeep, &Engine::release_solve_sparse, WAIT_NOT_POSDEF); }
+int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::release_refine, WAIT_IGNORE); }
+int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::release_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_inverse_batch(void* fkeep) { return release(fkeep, &Engine::release_inverse_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_inverse(void* fkeep) { return release(fkeep, &Engine::release_inverse, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_factor_adjoint(void* fkeep) { return release(fkeep, &Engine::release_factor_adjoint, WAIT_IGNORE | LENIENT); }
 
 int spllt_hip_factor_times(void* fkeep, double* submit_ms, double* device_ms, double* h2d_ms, int* launches) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
@@ -1725,29 +1502,154 @@ int spllt_hip_factor_times(void* fkeep, double* submit_ms, double* device_ms, do
   return 0;
 }
 
+// ---- spllt_hip_program_get: one function per family of names ---------------------------------------
+// "pattern_*": the index stream of the sampled outer product, from the analysed pattern alone
+static int64_t get_pattern(Fkeep* f, const std::string& k, const Out& o) {
+  const PatternTables* t = f->po.get(f->S, 0, 0, [&](PatternTables& v) { build_pattern_tables(*f->S, v.row, v.col); return 0; });
+  if (k == "pattern_row") return o.bytes(t->row);
+  if (k == "pattern_col") return o.bytes(t->col);
+  return -1;
+}
+
+// "matvec_*": the operator of the refined solves, from the analysed pattern and the pivot order alone
+static int64_t get_matvec(Fkeep* f, const std::string& k, const Out& o) {
+  const MatvecTables* t = f->mv.get(f->S, 0, 0, [&](MatvecTables& v) {
+    build_matvec_tables(*f->S, v.rowptr, v.col, v.src);
+    return 0;
+  });
+  if (k == "matvec_rowptr") return o.bytes(t->rowptr);
+  if (k == "matvec_col") return o.bytes(t->col);
+  if (k == "matvec_src") return o.bytes(t->src);
+  return -1;
+}
+
+// (the rows of the tables that go out as int64 columns)
+static void put(std::vector<int64_t>& v, std::initializer_list<int64_t> row) {
+  for (int64_t x : row) v.push_back(x);
+}
+
+// "selinv_*" of a selected-inversion program (the handle's, or the batch's under "batch_selinv_*")
+static int64_t get_selinv(const SelinvProgram* sp, const std::string& q, const Out& o) {
+  if (!sp) return -1;
+  if (q == "selinv_units") return o.bytes(sp->units);
+  if (q == "selinv_tiles") return o.bytes(sp->tiles);
+  if (q == "selinv_rows") return o.bytes(sp->rows);
+  if (q == "selinv_relpos") return o.bytes(sp->relpos);
+  if (q == "selinv_diag") return o.bytes(sp->diag_pos);
+  if (q == "selinv_scratch") return o.bytes(&sp->scratch_size, sizeof(int64_t));
+  if (q == "selinv_flops") return o.bytes(&sp->flops, sizeof(double));
+  if (q == "selinv_launches") {   // int64 x 5 per launch: kind, level, first, count, flops
+    std::vector<int64_t> v;
+    for (const SelinvLaunch& l : sp->launches)
+      put(v, {(int64_t)l.kind, (int64_t)l.level, (int64_t)l.first, (int64_t)l.count, (int64_t)l.flops});
+    return o.bytes(v);
+  }
+  return -1;
+}
+
+// "solve_*" and "rsolve_*": the substitution program (partition-aware like the factor program) and the tables of
+// the reproducible solve, which follow from it and the symbolic structure alone
+static int64_t get_solve(Fkeep* f, int cb, const std::string& k, const Out& o) {
+  SolveProgram sp;
+  std::vector<int> owner;
+  if (f->eo.nranks > 1) assign_owners(*f->S, f->eo.nranks, owner);
+  build_solve_program(*f->S, f->eo.pw > 0 ? f->eo.pw : kPanelMax, cb, sp, f->eo.nranks > 1 ? owner.data() : nullptr,
+                      f->eo.rank);
+  if (k == "solve_units") return o.bytes(sp.units);
+  if (k == "solve_list") return o.bytes(sp.diag_list);
+  if (k == "solve_tiles") return o.bytes(sp.tiles);
+  if (k == "solve_fwd" || k == "solve_bwd") {
+    std::vector<int64_t> v;
+    for (const SolveLaunch& l : (k == "solve_fwd" ? sp.fwd : sp.bwd))
+      put(v, {(int64_t)l.kind, (int64_t)l.level, (int64_t)l.first, (int64_t)l.count});
+    return o.bytes(v);
+  }
+  if (k == "solve_split") {
+    int64_t v[2] = {(int64_t)sp.fwd_nsub, (int64_t)sp.bwd_ntop};
+    return o.bytes(v, sizeof v);
+  }
+  if (k.rfind("rsolve_", 0) != 0) return -1;
+  RsolveTables R;
+  build_rsolve_tables(*f->S, sp, R);
+  if (k == "rsolve_fslot") return o.bytes(R.fslot);
+  if (k == "rsolve_bfirst") return o.bytes(R.bfirst);
+  if (k == "rsolve_gptr") return o.bytes(R.gptr);
+  if (k == "rsolve_gsrc") return o.bytes(R.gsrc);
+  if (k == "rsolve_bslot") return o.bytes(R.bslot);
+  if (k == "rsolve_frows") return o.bytes(&R.frows, sizeof(int64_t));
+  if (k == "rsolve_bsize") return o.bytes(&R.bsize, sizeof(int64_t));
+  return -1;
+}
+
+// the plain names: the tables of a factor program (the handle's, or the batch's under "batch_*")
+static int64_t get_plain(const Program* P, const std::string& k, const Out& o) {
+  auto scalar = [&](int64_t v) { return o.bytes(&v, sizeof v); };
+  if (k == "launches") {
+    std::vector<int64_t> v;
+    for (const Launch& l : P->launches) {
+      put(v, {(int64_t)l.kind, (int64_t)l.level, (int64_t)l.first, (int64_t)l.count, (int64_t)l.tile,
+                         (int64_t)l.flops, (int64_t)l.stream, (int64_t)l.record});
+      for (int w : l.wait) v.push_back(w);
+    }
+    return o.bytes(v);
+  }
+  if (k == "potrf") return o.bytes(P->potrf_units);
+  if (k == "units") return o.bytes(P->units);
+  if (k == "tiles") return o.bytes(P->tiles);
+  if (k == "relpos") return o.bytes(P->relpos);
+  if (k == "exchanges") {   // int64 x 5 per exchange: kind, first_item, nitems, elems, chunk
+    std::vector<int64_t> t;
+    for (const Exchange& e : P->exchanges)
+      put(t, {(int64_t)e.kind, (int64_t)e.first_item, (int64_t)e.nitems, (int64_t)e.elems, (int64_t)e.chunk});
+    return o.bytes(t);
+  }
+  if (k == "xitems") {      // int64 x 6 per item: block column, root, offset in the buffer, count,
+    std::vector<int64_t> t; // offset in the arena / dinv scratch, space (0 arena, 1 dinv)
+    for (const ExchangeItem& e : P->xitems)
+      put(t, {(int64_t)e.bcol, (int64_t)e.root, (int64_t)e.xoff, (int64_t)e.count, (int64_t)e.off,
+                         (int64_t)e.space});
+    return o.bytes(t);
+  }
+  if (k == "xbuf_elems") return scalar(P->xbuf_elems);
+  if (k == "panels") return o.bytes(P->panel_units);
+  if (k == "sub_tasks") return o.bytes(P->sub_tasks);
+  if (k == "sub_nodes") return o.bytes(P->sub_nodes);
+  if (k == "gen_size") return scalar(P->gen_size);
+  if (k == "chains") return o.bytes(P->chain_units);
+  if (k == "chain_block") return scalar(P->cb);
+  if (k == "panel_width") return scalar(P->pw);
+  if (k == "gather_tiles") return o.bytes(P->gather_tiles);
+  if (k == "gather_items") return o.bytes(P->gather_items);
+  if (k == "scratch_size") return scalar(P->scratch_size);
+  if (k == "dinv_size") return scalar(P->dinv_size);
+  return -1;
+}
+
+// "batch_*": the program of the batched factorization (fixed options, independent of the handle's engine flags)
+static int64_t get_batch(Fkeep* f, const std::string& q, const Out& o) {   // q: the unprefixed name
+  const Program* P = f->bt.get(f->S, 0, 0, [&](Program& v) { return build_batch_program(*f->S, v, &f->last_error); });
+  if (!P) return -1;
+  // ("potrf" and "scratch_size" -- empty and 0 in this program -- because tests/emulate.py asks for them)
+  static const char* const kNames[] = {"launches", "units", "tiles", "chains", "relpos", "dinv_size", "potrf", "scratch_size"};
+  for (const char* n : kNames)
+    if (q == n) return get_plain(P, q, o);
+  return -1;
+}
+
 int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t cap) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->S || !name) return -1;
+  const std::string k(name);
+  auto is = [&](const char* prefix) { return k.rfind(prefix, 0) == 0; };
+  if (k == "solve_sparse_host_us") {   // (of this handle's last sparse solve or gram; written whole or not at all)
+    const int64_t v = f->eng ? f->eng->solve_sparse_host_us() : 0;
+    return Out{cap >= (int64_t)sizeof v ? buf : nullptr, cap}.bytes(&v, sizeof v);
+  }
+  const Out o{buf, cap};
+  if (is("pattern_")) return get_pattern(f, k, o);
+  if (is("matvec_")) return get_matvec(f, k, o);
   // The program can be inspected without a GPU: build it on demand.
   Program local;
-  if (std::string(name) == "solve_sparse_host_us") {   // (of this handle's last sparse solve or gram; no program needed)
-    const int64_t v = f->eng ? f->eng->solve_sparse_host_us() : 0;
-    if (buf && cap >= (int64_t)sizeof v) std::memcpy(buf, &v, sizeof v);
-    return (int64_t)sizeof v;
-  }
-  if (std::string(name).rfind("pattern_", 0) == 0) {
-    // the index stream of the sampled outer product: from the analysed pattern alone (no program needed)
-    if (f->po_S != f->S) {
-      build_pattern_tables(*f->S, f->po_row, f->po_col);
-      f->po_S = f->S;
-    }
-    const std::string q(name);
-    const std::vector<int>* t = q == "pattern_row" ? &f->po_row : (q == "pattern_col" ? &f->po_col : nullptr);
-    if (!t) return -1;
-    const size_t bytes = t->size() * sizeof(int);
-    if (buf && bytes) std::memcpy(buf, t->data(), std::min<size_t>(bytes, (size_t)std::max<int64_t>(cap, 0)));
-    return (int64_t)bytes;
-  }
   const Program* P;
   if (f->eng && !f->eng->status()) {
     P = &f->eng->program();
@@ -1755,195 +1657,43 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
     build_local_program(f, local);
     P = &local;
   }
-  std::string k(name);
-  auto raw = [&](const void* p, size_t bytes) -> int64_t {
-    if (buf && bytes) std::memcpy(buf, p, std::min<size_t>(bytes, (size_t)cap));
-    return (int64_t)bytes;
-  };
-  auto selinv_get = [&](const SelinvProgram& sp, const std::string& q) -> int64_t {   // q: the unprefixed name
-    if (q == "selinv_units") return raw(sp.units.data(), sp.units.size() * sizeof(SelinvUnit));
-    if (q == "selinv_tiles") return raw(sp.tiles.data(), sp.tiles.size() * sizeof(UpdTile));
-    if (q == "selinv_rows") return raw(sp.rows.data(), sp.rows.size() * sizeof(SelinvRow));
-    if (q == "selinv_relpos") return raw(sp.relpos.data(), sp.relpos.size() * sizeof(int));
-    if (q == "selinv_diag") return raw(sp.diag_pos.data(), sp.diag_pos.size() * sizeof(int64_t));
-    if (q == "selinv_scratch") return raw(&sp.scratch_size, sizeof(int64_t));
-    if (q == "selinv_flops") return raw(&sp.flops, sizeof(double));
-    if (q == "selinv_launches") {   // int64 x 5 per launch: kind, level, first, count, flops
-      std::vector<int64_t> v;
-      for (const SelinvLaunch& l : sp.launches) {
-        v.push_back(l.kind); v.push_back(l.level); v.push_back(l.first); v.push_back(l.count);
-        v.push_back((int64_t)l.flops);
-      }
-      return raw(v.data(), v.size() * sizeof(int64_t));
-    }
-    return -1;
-  };
-  if (k.rfind("matvec_", 0) == 0) {
-    // the operator of the refined solves: from the analysed pattern and the pivot order alone
-    if (f->mv_S != f->S) {
-      build_matvec_tables(*f->S, f->mv_rowptr, f->mv_col, f->mv_src);
-      f->mv_S = f->S;
-    }
-    if (k == "matvec_rowptr") return raw(f->mv_rowptr.data(), f->mv_rowptr.size() * sizeof(int64_t));
-    if (k == "matvec_col") return raw(f->mv_col.data(), f->mv_col.size() * sizeof(int));
-    if (k == "matvec_src") return raw(f->mv_src.data(), f->mv_src.size() * sizeof(int));
-    return -1;
-  }
-  if (k.rfind("batch_selinv_", 0) == 0) {
-    // the selected-inversion program of the batch: panels of 64 columns, from the symbolic structure alone
-    if (f->bsi_S != f->S) {
-      f->bsi_rc = build_selinv_program(*f->S, 64, 64, f->bsi_prog);
-      f->bsi_S = f->S;
-    }
-    if (f->bsi_rc) return -1;
-    return selinv_get(f->bsi_prog, k.substr(6));
-  }
-  if (k.rfind("batch_", 0) == 0) {
-    // the program of the batched factorization: fixed options, independent of the handle's engine flags
-    if (f->bt_S != f->S) {
-      f->bt_rc = build_batch_program(*f->S, f->bt_prog, &f->last_error);
-      f->bt_S = f->S;
-    }
-    if (f->bt_rc) return -1;
-    P = &f->bt_prog;
-    k = k.substr(6);
-    // ("potrf" and "scratch_size" -- empty and 0 in this program -- because tests/emulate.py asks for them)
-    if (k != "launches" && k != "units" && k != "tiles" && k != "chains" && k != "relpos" && k != "dinv_size" &&
-        k != "potrf" && k != "scratch_size")
-      return -1;
-  }
-  if (k == "launches") {
-    std::vector<int64_t> v;
-    for (const Launch& l : P->launches) {
-      v.push_back(l.kind); v.push_back(l.level); v.push_back(l.first);
-      v.push_back(l.count); v.push_back(l.tile); v.push_back((int64_t)l.flops);
-      v.push_back(l.stream); v.push_back(l.record);
-      for (int w : l.wait) v.push_back(w);
-    }
-    return raw(v.data(), v.size() * sizeof(int64_t));
-  }
-  if (k == "potrf") return raw(P->potrf_units.data(), P->potrf_units.size() * sizeof(PotrfUnit));
-  if (k == "units") return raw(P->units.data(), P->units.size() * sizeof(UpdUnit));
-  if (k == "tiles") return raw(P->tiles.data(), P->tiles.size() * sizeof(UpdTile));
-  if (k == "relpos") return raw(P->relpos.data(), P->relpos.size() * sizeof(int));
-  if (k == "exchanges") {   // int64 x 5 per exchange: kind, first_item, nitems, elems, chunk
-    std::vector<int64_t> t;
-    for (const Exchange& e : P->exchanges) {
-      t.push_back(e.kind); t.push_back(e.first_item); t.push_back(e.nitems); t.push_back(e.elems); t.push_back(e.chunk);
-    }
-    return raw(t.data(), t.size() * sizeof(int64_t));
-  }
-  if (k == "xitems") {      // int64 x 6 per item: block column, root, offset in the buffer, count,
-    std::vector<int64_t> t; // offset in the arena / dinv scratch, space (0 arena, 1 dinv)
-    for (const ExchangeItem& e : P->xitems) {
-      t.push_back(e.bcol); t.push_back(e.root); t.push_back(e.xoff); t.push_back(e.count);
-      t.push_back(e.off); t.push_back(e.space);
-    }
-    return raw(t.data(), t.size() * sizeof(int64_t));
-  }
-  if (k == "xbuf_elems") return raw(&P->xbuf_elems, sizeof(int64_t));
-  if (k == "panels") return raw(P->panel_units.data(), P->panel_units.size() * sizeof(PanelUnit));
-  if (k == "sub_tasks") return raw(P->sub_tasks.data(), P->sub_tasks.size() * sizeof(SubTask));
-  if (k == "sub_nodes") return raw(P->sub_nodes.data(), P->sub_nodes.size() * sizeof(SubNode));
-  if (k == "gen_size") { int64_t v = P->gen_size; return raw(&v, sizeof v); }
-  if (k == "chains") return raw(P->chain_units.data(), P->chain_units.size() * sizeof(ChainUnit));
-  if (k == "chain_block") { int64_t v = P->cb; return raw(&v, sizeof v); }
-  if (k == "panel_width") { int64_t v = P->pw; return raw(&v, sizeof v); }
-  if (k == "gather_tiles") return raw(P->gather_tiles.data(), P->gather_tiles.size() * sizeof(GatherTile));
-  if (k == "gather_items") return raw(P->gather_items.data(), P->gather_items.size() * sizeof(GatherItem));
-  if (k == "scratch_size") { int64_t v = P->scratch_size; return raw(&v, sizeof v); }
-  if (k == "dinv_size") { int64_t v = P->dinv_size; return raw(&v, sizeof v); }
-  if (k.rfind("selinv_", 0) == 0) {
-    // the selected-inversion program (single GPU; built from the symbolic structure alone)
-    if (f->si_S != f->S || f->si_pw != P->pw || f->si_cb != P->cb) {
-      f->si_rc = build_selinv_program(*f->S, P->pw, P->cb, f->si_prog);
-      f->si_S = f->S;
-      f->si_pw = P->pw;
-      f->si_cb = P->cb;
-    }
-    if (f->si_rc) return -1;
-    return selinv_get(f->si_prog, k);
-  }
-  if (k.rfind("solve_", 0) == 0) {
-    // the substitution program (partition-aware like the factor program)
-    SolveProgram sp;
-    std::vector<int> owner;
-    if (f->eo.nranks > 1) assign_owners(*f->S, f->eo.nranks, owner);
-    build_solve_program(*f->S, f->eo.pw > 0 ? f->eo.pw : kPanelMax, P->cb, sp,
-                        f->eo.nranks > 1 ? owner.data() : nullptr, f->eo.rank);
-    if (k == "solve_units") return raw(sp.units.data(), sp.units.size() * sizeof(SolveUnit));
-    if (k == "solve_list") return raw(sp.diag_list.data(), sp.diag_list.size() * sizeof(int));
-    if (k == "solve_tiles") return raw(sp.tiles.data(), sp.tiles.size() * sizeof(UpdTile));
-    if (k == "solve_fwd" || k == "solve_bwd") {
-      std::vector<int64_t> v;
-      for (const SolveLaunch& l : (k == "solve_fwd" ? sp.fwd : sp.bwd)) {
-        v.push_back(l.kind); v.push_back(l.level); v.push_back(l.first); v.push_back(l.count);
-      }
-      return raw(v.data(), v.size() * sizeof(int64_t));
-    }
-    if (k == "solve_split") {
-      int64_t v[2] = {(int64_t)sp.fwd_nsub, (int64_t)sp.bwd_ntop};
-      return raw(v, sizeof v);
-    }
-  }
-  if (k.rfind("rsolve_", 0) == 0) {
-    // the tables of the reproducible solve: from the symbolic structure and the substitution program alone
-    SolveProgram sp;
-    std::vector<int> owner;
-    if (f->eo.nranks > 1) assign_owners(*f->S, f->eo.nranks, owner);
-    build_solve_program(*f->S, f->eo.pw > 0 ? f->eo.pw : kPanelMax, P->cb, sp,
-                        f->eo.nranks > 1 ? owner.data() : nullptr, f->eo.rank);
-    RsolveTables R;
-    build_rsolve_tables(*f->S, sp, R);
-    auto vec = [&](const std::vector<int64_t>& v) { return raw(v.data(), v.size() * sizeof(int64_t)); };
-    if (k == "rsolve_fslot") return vec(R.fslot);
-    if (k == "rsolve_bfirst") return vec(R.bfirst);
-    if (k == "rsolve_gptr") return vec(R.gptr);
-    if (k == "rsolve_gsrc") return vec(R.gsrc);
-    if (k == "rsolve_bslot") return vec(R.bslot);
-    if (k == "rsolve_frows") return raw(&R.frows, sizeof(int64_t));
-    if (k == "rsolve_bsize") return raw(&R.bsize, sizeof(int64_t));
-  }
-  return -1;
+  if (is("batch_selinv_"))   // panels of 64 columns whatever the handle's, from the symbolic structure alone
+    return get_selinv(f->bsi.get(f->S, 64, 64, [&](SelinvProgram& v) { return build_selinv_program(*f->S, 64, 64, v); }),
+                      k.substr(6), o);
+  if (is("batch_")) return get_batch(f, k.substr(6), o);
+  if (is("selinv_"))         // (single GPU; built from the symbolic structure alone)
+    return get_selinv(f->si.get(f->S, P->pw, P->cb, [&](SelinvProgram& v) { return build_selinv_program(*f->S, P->pw, P->cb, v); }),
+                      k, o);
+  if (is("solve_") || is("rsolve_")) return get_solve(f, P->cb, k, o);
+  return get_plain(P, k, o);
 }
 
-static int profile_impl(void* fkeep, const double* val, int nnz, float* ms, int capacity, bool serial);
-int spllt_hip_profile(void* fkeep, const double* val, int nnz, float* ms, int capacity) {
-  return profile_impl(fkeep, val, nnz, ms, capacity, true);
-}
-int spllt_hip_profile_in_program(void* fkeep, const double* val, int nnz, float* ms, int capacity) {
-  return profile_impl(fkeep, val, nnz, ms, capacity, false);
-}
-static int profile_impl(void* fkeep, const double* val, int nnz, float* ms, int capacity, bool serial) {
+// ---- timing runs -------------------------------------------------------------------------------------
+// one factorization for its per-launch times; an engine that cannot be had is a device error here
+enum Timing { PROFILE_SERIAL, PROFILE_IN_PROGRAM, TIMELINE };
+
+static int timing_impl(void* fkeep, const double* val, int nnz, float* ms, int capacity, Timing how) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S || !val) return SPLLT_ERROR_PARAMETER;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  (void)do_wait(f);            // a factorization still in flight owns the streams and the events
-  if (!f->eng) f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-  if (!f->eng || f->eng->status()) return SPLLT_ERROR_HIP;
+  // (WAIT_IGNORE: a factorization still in flight owns the streams and the events)
+  if (int rc = enter(f, nullptr, val ? nullptr : "", WAIT_IGNORE)) return rc;
+  if (ensure_engine(f)) return SPLLT_ERROR_HIP;
   std::vector<float> v;
-  int rc = f->eng->profile_launches(val, nnz, v, serial);
-  if (rc) return rc;
+  if (int rc = how == TIMELINE ? f->eng->timeline(val, nnz, v) : f->eng->profile_launches(val, nnz, v, how == PROFILE_SERIAL))
+    return rc;
   for (int i = 0; i < (int)v.size() && i < capacity; ++i) ms[i] = v[i];
   f->hostL_valid = false;
   ++f->serial[0];
   return (int)v.size();
 }
 
+int spllt_hip_profile(void* fkeep, const double* val, int nnz, float* ms, int capacity) {
+  return timing_impl(fkeep, val, nnz, ms, capacity, PROFILE_SERIAL);
+}
+int spllt_hip_profile_in_program(void* fkeep, const double* val, int nnz, float* ms, int capacity) {
+  return timing_impl(fkeep, val, nnz, ms, capacity, PROFILE_IN_PROGRAM);
+}
 int spllt_hip_timeline(void* fkeep, const double* val, int nnz, float* t_ms, int capacity) {
-  Fkeep* f = static_cast<Fkeep*>(fkeep);
-  if (!f || !f->S || !val) return SPLLT_ERROR_PARAMETER;
-  if (f->dead) return SPLLT_ERROR_HIP;
-  (void)do_wait(f);            // a factorization still in flight owns the streams and the events
-  if (!f->eng) f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
-  if (!f->eng || f->eng->status()) return SPLLT_ERROR_HIP;
-  std::vector<float> v;
-  int rc = f->eng->timeline(val, nnz, v);
-  if (rc) return rc;
-  for (int i = 0; i < (int)v.size() && i < capacity; ++i) t_ms[i] = v[i];
-  f->hostL_valid = false;
-  ++f->serial[0];
-  return (int)v.size();
+  return timing_impl(fkeep, val, nnz, t_ms, capacity, TIMELINE);
 }
 
 int spllt_hip_last_flag(const void* fkeep) {

@@ -23,6 +23,7 @@ def test_every_declared_symbol_is_exported():
     lib = _lib.load()
     names = _declared("spllt_iface.h") | _declared("spllt_hip.h")
     assert set(_lib.IFACE_SYMBOLS) <= names and set(_lib.HIP_SYMBOLS) <= names
+    assert set(_lib.PROTOTYPES) == set(_lib.IFACE_SYMBOLS) | set(_lib.HIP_SYMBOLS)
     missing = [s for s in sorted(names) if not hasattr(lib, s)]
     assert not missing, missing
 
