@@ -1921,6 +1921,7 @@ int build_batch_program(const Symbolic& S, Program& P, std::string* why) {
   so.lookahead = false;
   so.fused_panel = false;
   so.subtrees = false;
+  so.env_switches = false;      // (SPLLT_CHAIN4=1 / SPLLT_SUBTREES=1 are experiments of the single-handle engine)
   so.deterministic = false;
   P = Program();
   build_program(S, so, P);

@@ -307,7 +307,9 @@ __device__ __forceinline__ void potrf64_body(PotrfShared& sh, double* __restrict
 #pragma unroll
         for (int k = j + 1; k < 16; ++k) tk[k] = bcast16(row[j], k);
         double djj = bcast16(row[j], j);
-        if (!(djj > 0.0)) {
+        // positive AND finite (as batch.hip): rsq(+Inf) = 0 turns into NaN in the Newton step, and
+        // where no pivot follows -- the last column of a root -- nothing else would report it
+        if (!(djj > 0.0 && djj < INFINITY)) {
           if (failcol == (1 << 30)) failcol = j;
           djj = 1.0;
         }
@@ -586,8 +588,9 @@ __device__ __forceinline__ int chol16_regs(double (&row)[16], double (&wx)[16], 
   });
   (void)rs;
   STAMP2(true, 23);
-  // lane j holds pivot j: the first one that is not positive
-  const unsigned long long bad = __ballot(!(dmine > 0.0)) & 0xffffull;
+  // lane j holds pivot j: the first one that is not positive and finite (rcp(+Inf) = 0 turns into
+  // NaN in the Newton step, which only a LATER pivot would show)
+  const unsigned long long bad = __ballot(!(dmine > 0.0 && dmine < INFINITY)) & 0xffffull;
   return bad ? __builtin_ctzll(bad) : (1 << 30);
 }
 

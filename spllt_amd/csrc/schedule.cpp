@@ -23,6 +23,9 @@ struct Builder {
   const Symbolic& S;
   const ScheduleOptions& opt;
   Program& P;
+  // an engine switch of the environment, where the program's owner lets the environment decide
+  // (ScheduleOptions::env_switches; the batch program does not: batch.hip fixes its options)
+  int64_t engine_switch(const char* name, int64_t dflt) const { return opt.env_switches ? env_int(name, dflt) : dflt; }
   int nb, pw;
 
   Builder(const Symbolic& s, const ScheduleOptions& o, Program& p)
@@ -487,8 +490,8 @@ struct Builder {
   void subtree_tasks(const std::vector<int64_t>& dinv_slot) {
     const int nn = S.nnodes;
     in_sub.assign((size_t)nn, 0);
-    const double budget = (double)env_int("SPLLT_SUBTREE_US", opt.subtree_us);
-    if (!env_int("SPLLT_SUBTREES", opt.subtrees ? 1 : 0) || budget <= 0) return;
+    const double budget = (double)engine_switch("SPLLT_SUBTREE_US", opt.subtree_us);
+    if (!engine_switch("SPLLT_SUBTREES", opt.subtrees ? 1 : 0) || budget <= 0) return;
     for (int s = 0; s < nn; ++s)
       if (S.sparent[s] <= s) return;                        // (children before parents, or no tasks)
     // modelled time of a node inside a task (one CU): Cholesky of the panel, solve of the 64-row
@@ -627,7 +630,7 @@ struct Builder {
     // k_trsm_rows) -- two dependent launches per 4 pw columns of the panel chain instead of twelve
     // (POTRF, TRSM, in-panel update per panel).  chain4 off: one panel per chain step.  The layout
     // of the inverses is per panel either way (cb = pw).
-    const bool chain4 = env_int("SPLLT_CHAIN4", opt.chain4 ? 1 : 0) != 0;
+    const bool chain4 = engine_switch("SPLLT_CHAIN4", opt.chain4 ? 1 : 0) != 0;
     const int cb = pw;                       // layout of the dinv slots: one pn x pn inverse per panel
     P.cb = cb;
     const int nn = S.nnodes;
@@ -646,16 +649,16 @@ struct Builder {
       dinv_slot[S.nbcol()] = o;
       P.dinv_size = o;
     }
-    const int64_t fused_max = env_int("SPLLT_FUSED_PANEL_MAX", opt.fused_panel_max);
-    int super_panel = (int)env_int("SPLLT_SUPER_PANEL", opt.super_panel);
+    const int64_t fused_max = engine_switch("SPLLT_FUSED_PANEL_MAX", opt.fused_panel_max);
+    int super_panel = (int)engine_switch("SPLLT_SUPER_PANEL", opt.super_panel);
     if (super_panel % (4 * pw) != 0) super_panel = 0;      // (a multiple of the chain block, or off)
 
     const bool la = opt.lookahead;
     const bool det_all = opt.deterministic;
     // levels below this one assemble their inter-node updates through the buffer + ordered gather
     // (no atomics) even in the default engine: see ScheduleOptions::buffer_levels
-    const int buffer_levels = (int)env_int("SPLLT_BUFFER_LEVELS", opt.buffer_levels);
-    const bool pair_sources = env_int("SPLLT_PAIR_TRAILING", opt.pair_sources ? 1 : 0) != 0;
+    const int buffer_levels = (int)engine_switch("SPLLT_BUFFER_LEVELS", opt.buffer_levels);
+    const bool pair_sources = engine_switch("SPLLT_PAIR_TRAILING", opt.pair_sources ? 1 : 0) != 0;
     auto edge = [&](int stream) {
       Edge e;
       e.stream = la ? stream : ST_CHAIN;

@@ -264,6 +264,9 @@ struct Program {
 };
 
 struct ScheduleOptions {
+  bool env_switches = true;  // SPLLT_CHAIN4, SPLLT_SUBTREES, SPLLT_SUBTREE_US, SPLLT_FUSED_PANEL_MAX, SPLLT_SUPER_PANEL,
+                             // SPLLT_BUFFER_LEVELS, SPLLT_PAIR_TRAILING of the environment override the options below;
+                             // false where the kernels fix them (the batch program)
   int pw = 64;          // inner panel width (<= kPanelMax)
   int tile = 128;       // GEMM tile edge for large units
   int cb = 64;          // ignored (chain block of the removed sub-tile chain kernels)

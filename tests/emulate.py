@@ -9,10 +9,39 @@ import scipy.linalg as sl
 MODE_DIRECT, MODE_SCATTER, MODE_TRSM = 0, 1, 2
 
 
-def emulate_program(f, val, exchange=None, partitioned=False):
+def chain_block_inverse_multiply(S, pw, chol_inv):
+    """the cw x cw diagonal block S (symmetric) of a chain block as k_chain_block factors it: panel by
+    panel, right-looking, the rows below a panel as a PRODUCT with inv(L_pp).  Returns (L, [inv(L_pp)])."""
+    B = np.array(S, copy=True)
+    cw = len(B)
+    invs = []
+    for p0 in range(0, cw, pw):
+        n = min(pw, cw - p0)
+        p1 = p0 + n
+        Lpp, W = chol_inv(B[p0:p1, p0:p1])
+        B[p0:p1, p0:p1] = Lpp
+        invs.append(W)
+        if p1 < cw:
+            X = B[p1:, p0:p1] @ W.T
+            B[p1:, p0:p1] = X
+            B[p1:, p1:] -= X @ X.T
+    return np.tril(B), invs
+
+
+def emulate_program(f, val, exchange=None, partitioned=False, panel_chol=None, chain_inverse_multiply=False):
     """exchange(k, xbuf) -> xbuf after the collective is called at every EXCHANGE launch of a
     partitioned (multi-GPU) program: k = index into f.program("exchanges"), xbuf = this rank's
-    packed exchange buffer (spllt_amd.multigpu.run_exchange is the production collective)."""
+    packed exchange buffer (spllt_amd.multigpu.run_exchange is the production collective).
+    panel_chol(S) -> (L, inv(L)) replaces LAPACK's dpotrf + dtrtri-by-substitution on every diagonal
+    panel (S symmetric, of order <= the panel width); chain_inverse_multiply=True models the chain blocks
+    (k_chain_block, k_trsm_rows) as the kernels compute them, a product with inv(L_pp) per panel, instead
+    of one dpotrf of the block and a true substitution.  The defaults keep the interpreter as it was,
+    bit for bit (tests/test_conditioning_cpu.py uses both to model the algorithm on hard input)."""
+    def chol_inv(S):
+        if panel_chol is not None:
+            return panel_chol(S)
+        Lc = sl.cholesky(S, lower=True)
+        return Lc, sl.solve_triangular(Lc, np.eye(len(Lc)), lower=True)
     info = f.sym_info()
     arena = np.zeros(info["arena"])
     md, ms = f.sym("map_dst"), f.sym("map_src")
@@ -76,9 +105,8 @@ def emulate_program(f, val, exchange=None, partitioned=False):
                     w, m, off = int(nd["w"]), int(nd["nrow"]), int(nd["off"])
                     blk = arena[off:off + m * w].reshape(m, w)          # (view: a node has ONE block column)
                     dd = np.tril(blk[:w])
-                    Lb = sl.cholesky(dd + np.tril(dd, -1).T, lower=True)
+                    Lb, inv = chol_inv(dd + np.tril(dd, -1).T)
                     blk[:w][np.tril_indices(w)] = Lb[np.tril_indices(w)]
-                    inv = sl.solve_triangular(Lb, np.eye(w), lower=True)
                     do = int(nd["dinv_off"])
                     dinv[do:do + w * w] = inv.ravel()
                     blk[w:] = blk[w:] @ inv.T
@@ -120,10 +148,9 @@ def emulate_program(f, val, exchange=None, partitioned=False):
                     return off + np.arange(r0, r1)[:, None] * ld + np.arange(k0, k1)[None, :]
                 dd = idx(c0, c0 + pn, c0, c0 + pn)
                 blk = np.tril(arena[dd])
-                Lb = sl.cholesky(blk + np.tril(blk, -1).T, lower=True)
+                Lb, inv = chol_inv(blk + np.tril(blk, -1).T)
                 low = np.tril_indices(pn)
                 arena[dd[low]] = Lb[low]
-                inv = sl.solve_triangular(Lb, np.eye(pn), lower=True)
                 wo = int(q["winv_off"])
                 ldw = ce - cs                                            # row stride: the chain block's width
                 Wv = dinv[wo:wo + pn * ldw].reshape(pn, ldw)             # view: the panel's rows of the block's inverse
@@ -144,13 +171,17 @@ def emulate_program(f, val, exchange=None, partitioned=False):
                 assert int(q["cs"]) == c0 and int(q["ce"]) == c0 + cw and cw <= 4 * pw and c0 % pw == 0
                 dd = off + np.arange(c0, c0 + cw)[:, None] * ld + np.arange(c0, c0 + cw)[None, :]
                 blk = np.tril(arena[dd])
-                Lb = sl.cholesky(blk + np.tril(blk, -1).T, lower=True)
+                if chain_inverse_multiply:
+                    Lb, invs = chain_block_inverse_multiply(blk + np.tril(blk, -1).T, pw, chol_inv)
+                else:
+                    Lb, invs = sl.cholesky(blk + np.tril(blk, -1).T, lower=True), None
                 low = np.tril_indices(cw)
                 arena[dd[low]] = Lb[low]
                 wo = int(q["winv_off"])
                 for p0 in range(0, cw, pw):
                     n = min(pw, cw - p0)
-                    inv = sl.solve_triangular(Lb[p0:p0 + n, p0:p0 + n], np.eye(n), lower=True)
+                    inv = (invs[p0 // pw] if invs is not None else
+                           sl.solve_triangular(Lb[p0:p0 + n, p0:p0 + n], np.eye(n), lower=True))
                     dinv[wo:wo + n * n] = inv.ravel()
                     wo += n * n
             continue
@@ -171,8 +202,7 @@ def emulate_program(f, val, exchange=None, partitioned=False):
                     inv = dinv[do:do + pn * pn].reshape(pn, pn).copy()
                 else:
                     blk = np.tril(snap[dd])
-                    Lb = sl.cholesky(blk + np.tril(blk, -1).T, lower=True)
-                    inv = sl.solve_triangular(Lb, np.eye(pn), lower=True)
+                    Lb, inv = chol_inv(blk + np.tril(blk, -1).T)
                 ti = int(t["ti"])
                 if ti == 0 and not factored:
                     low = np.tril_indices(pn)
@@ -222,11 +252,12 @@ def emulate_program(f, val, exchange=None, partitioned=False):
                 n, ld, off = int(q["n"]), int(q["ld"]), int(q["off"])
                 idx = off + np.arange(n)[:, None] * ld + np.arange(n)[None, :]
                 blk = np.tril(arena[idx])
-                Lb = blk if (q["flags"] & 1) else sl.cholesky(blk + np.tril(blk, -1).T, lower=True)
-                if not (q["flags"] & 1):
+                if q["flags"] & 1:
+                    X = sl.solve_triangular(blk, np.eye(n), lower=True)
+                else:
+                    Lb, X = chol_inv(blk + np.tril(blk, -1).T)
                     low = np.tril_indices(n)
                     arena[idx[low]] = Lb[low]
-                X = sl.solve_triangular(Lb, np.eye(n), lower=True)
                 dinv[int(q["dinv_off"]):int(q["dinv_off"]) + n * n] = X.ravel()
             continue
         T = int(tile)
@@ -241,6 +272,17 @@ def emulate_program(f, val, exchange=None, partitioned=False):
                 assert int(u["k0"]) == cs and int(u["klen"]) == cw and int(u["d_row0"]) == cs + cw
                 dd = off + np.arange(cs, cs + cw)[:, None] * ld + np.arange(cs, cs + cw)[None, :]
                 xi = off + np.arange(rr, rr + mi)[:, None] * ld + np.arange(cs, cs + cw)[None, :]
+                if chain_inverse_multiply:      # X_p = (A_p - sum_{q<p} X_q L_pq^T) inv(L_pp)^T, p = 0 .. np-1
+                    pw_, Ld, Xr = f.program("panel_width"), np.tril(arena[dd]), arena[xi]
+                    wo = int(u["dinv_off"])         # the panels' inverses, one behind the other (k_chain_block)
+                    for p0 in range(0, cw, pw_):
+                        p1 = min(p0 + pw_, cw)
+                        n = p1 - p0
+                        W = dinv[wo:wo + n * n].reshape(n, n)
+                        wo += n * n
+                        Xr[:, p0:p1] = (Xr[:, p0:p1] - Xr[:, :p0] @ Ld[p0:p1, :p0].T) @ W.T
+                    arena[xi] = Xr
+                    continue
                 arena[xi] = sl.solve_triangular(np.tril(arena[dd]), arena[xi].T, lower=True).T
                 continue
             assert mi > 0 and nj > 0

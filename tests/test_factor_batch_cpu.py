@@ -99,6 +99,29 @@ def test_batch_program_does_not_depend_on_the_engine_flags(name):
     f1.close()
 
 
+@pytest.mark.parametrize("name", ["box11-nb64", "fe27-nb768"])
+def test_batch_program_does_not_depend_on_the_engine_switches_of_the_environment(name, monkeypatch):
+    """SPLLT_CHAIN4=1 / SPLLT_SUBTREES=1 (and the other switches of the program's shape, such as the size limit
+    of the fused panels) are switches of the single-handle engine; the batch kernels implement
+    neither chain blocks nor subtree tasks, and the batch program keeps its fixed options under them (it used to
+    be built WITH them, and factor_batch then refused it with -99)."""
+    make = next(c[1] for c in CASES if c[0] == name)
+    A, f, val = make()
+    ref = [np.asarray(f.program(k)).tobytes() if k != "batch_dinv_size" else f.program(k) for k in PROGRAM_NAMES]
+    f.close()
+    monkeypatch.setenv("SPLLT_CHAIN4", "1")
+    monkeypatch.setenv("SPLLT_SUBTREES", "1")
+    monkeypatch.setenv("SPLLT_SUBTREE_US", "300")
+    monkeypatch.setenv("SPLLT_FUSED_PANEL_MAX", "1000000")
+    A, f, val = make()
+    kinds = set(f.program("launches")[:, 0].tolist())
+    assert 10 in kinds and (name != "fe27-nb768" or 8 in kinds)      # the handle's own program follows the switches
+    check_batch_program(f)
+    tabs = [np.asarray(f.program(k)).tobytes() if k != "batch_dinv_size" else f.program(k) for k in PROGRAM_NAMES]
+    assert tabs == ref
+    f.close()
+
+
 def test_unknown_batch_program_name():
     f, val = make_case(matgen.poisson2d(8), nb=8, nemin=4)
     with pytest.raises(KeyError):
