@@ -1,4 +1,4 @@
-"""ctypes binding of libspllt_hip.so (the C-ABI of include/spllt_iface.h + spllt_hip.h).
+"""ctypes binding of libspllt_hip.so (the C-ABI of include/spllt_iface.h + spllt_hip.h + spllt_hip_batch_mult.h).
 
 The library is built in-tree by ``__graft_entry__.build()`` /
 ``make -C spllt_amd/csrc``.  There is no Python or CPU fallback for the
@@ -169,9 +169,23 @@ _HIP = {
     "spllt_hip_release_factor_adjoint": (i32, [vp]),
 }
 PROTOTYPES = {**_IFACE, **_HIP}
+# every symbol declared in include/spllt_hip_batch_mult.h: the batched factor products and samplers.  A table of its
+# own, applied by load() after PROTOTYPES: the header is separate until the recorded ladder of the C boundary is
+# regenerated (see the header), and PROTOTYPES stays what tests/test_abi.py ties to the two older headers.
+u32 = C.c_uint32
+_BATCH_MULT = {
+    "spllt_hip_factor_mult_batch": (i32, [vp, i32, vp, i64, i32]),
+    "spllt_hip_factor_mult_batch_dev": (i32, [vp, i32, vp, i64, i32, i32]),
+    "spllt_hip_white_noise_batch_dev": (i32, [vp, i32, vp, i64, u64, u64, u32, i32]),
+    "spllt_hip_sample_batch": (i32, [vp, i32, vp, i64, i32, u64, u64, u32, i32, vp, i64]),
+    "spllt_hip_sample_batch_dev": (i32, [vp, i32, vp, i64, i32, u64, u64, u32, i32, vp, i64]),
+    "spllt_hip_release_factor_mult_batch": (i32, [vp]),
+}
+del u32
 del vp, vpp, i32, i64, u64, f64, cstr, long, ip, i64p, dp, fp, longp, ipp, dpp, opt, inf   # (names of the table only)
 IFACE_SYMBOLS = list(_IFACE)
 HIP_SYMBOLS = list(_HIP)
+BATCH_MULT_SYMBOLS = list(_BATCH_MULT)
 
 _lib = None
 
@@ -186,8 +200,9 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C spllt_amd/csrc`. spllt_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in (PROTOTYPES, _BATCH_MULT):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib

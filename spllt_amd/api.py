@@ -918,6 +918,99 @@ class Factorization:
     def release_batch(self):
         self._call("spllt_hip_release_batch", self.fkeep)
 
+    # ---- batched factor products and sampling (include/spllt_hip_batch_mult.h) -----
+    def _batch_count(self):
+        return int(self.lib.spllt_hip_batch_status(self.fkeep, None, None, 0))
+
+    def factor_mult_batch(self, X, job=0):
+        """spllt_hip_factor_mult_batch on a copy of X: shape (B, n), one vector per member, or (B, nvec, n), like
+        solve_batch.  job 0 P^T L_b L_b^T P x, 1 P^T L_b x, 2 L_b^T P x: the inverse of solve_batch(job),
+        bit-reproducible.  The vectors of a member that is not positive definite come back unchanged."""
+        x = np.array(X, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (2, 3):
+            raise ValueError("factor_mult_batch: X must have shape (B, n) or (B, nvec, n)")
+        nvec = 1 if x.ndim == 2 else x.shape[1]
+        if x.shape[-1] != self.n:
+            raise ValueError(f"factor_mult_batch: the vectors have length {x.shape[-1]}, n = {self.n}")
+        nb = self._batch_count()
+        if nb > 0 and x.shape[0] != nb:
+            raise ValueError(f"factor_mult_batch: X holds vectors for {x.shape[0]} members, the last batch has {nb}")
+        self._call("spllt_hip_factor_mult_batch", self.fkeep, nvec, C.c_void_p(x.ctypes.data), x.shape[-1], job,
+                   ok=self._BATCH_OK)
+        return x
+
+    def factor_mult_batch_dev(self, x_dev_ptr, nvec, ldx=None, job=0, pivot_order=False):
+        """spllt_hip_factor_mult_batch_dev: device vectors in place, the layout of solve_batch_dev.  Returns 0 or
+        -20."""
+        if ldx is None:
+            ldx = self.n
+        return self._call("spllt_hip_factor_mult_batch_dev", self.fkeep, int(nvec), C.c_void_p(x_dev_ptr), int(ldx), job,
+                          1 if pivot_order else 0, ok=self._BATCH_OK)
+
+    def _batch_mean(self, mean, where):
+        """(array or None, ldmean) of a mean of shape (n,) -- shared by all members -- or (B, n)"""
+        if mean is None:
+            return None, 0
+        m = np.ascontiguousarray(mean, dtype=np.float64)
+        if m.shape == (self.n,):
+            return m, 0
+        if m.ndim != 2 or m.shape[1] != self.n:
+            raise ValueError(f"{where}: mean must have shape (n,) or (B, n), n = {self.n}, not {m.shape}")
+        nb = self._batch_count()
+        if m.ndim == 2 and m.shape[1] == self.n and (nb <= 0 or m.shape[0] == nb):
+            return m, max(self.n, 1)
+        raise ValueError(f"{where}: mean must have shape (n,) or (B, n) = ({nb}, {self.n}), not {m.shape}")
+
+    def sample_batch(self, nsamp, seed=0, kind="precision", mean=None, first_sample=0, stream0=0, common_noise=False):
+        """spllt_hip_sample_batch: nsamp draws per member of the last batch of N(mean_b, A_b^-1) (kind
+        "precision") or N(mean_b, A_b) ("covariance"), as a (B, nsamp, n) array in user order.  mean: (n,) for all
+        members or (B, n).  Member b draws from noise stream stream0 + b; common_noise gives every member the
+        noise of stream0.  The samples of a member that is not positive definite are NaN."""
+        if int(nsamp) < 0:
+            raise ValueError("sample_batch: nsamp < 0")
+        k = self._sample_kind(kind)
+        m, ldm = self._batch_mean(mean, "sample_batch")
+        x = np.zeros((max(self._batch_count(), 0), int(nsamp), self.n), dtype=np.float64)
+        self._call("spllt_hip_sample_batch", self.fkeep, int(nsamp), C.c_void_p(x.ctypes.data), max(self.n, 1), k,
+                   int(seed), int(first_sample), int(stream0), 0 if common_noise else 1,
+                   None if m is None else C.c_void_p(m.ctypes.data), ldm, ok=self._BATCH_OK)
+        return x
+
+    def sample_batch_dev(self, x_dev_ptr, nsamp, ldx=None, seed=0, kind="precision", mean_dev_ptr=None, ldmean=0,
+                         first_sample=0, stream0=0, common_noise=False):
+        """spllt_hip_sample_batch_dev: the samples into device memory, sample q of member b at
+        x[(b*nsamp + q)*ldx .. + n); mean_dev_ptr: device doubles (ldmean 0: one mean, >= n: per member) or None.
+        Returns 0 or -20."""
+        if ldx is None:
+            ldx = max(self.n, 1)
+        return self._call("spllt_hip_sample_batch_dev", self.fkeep, int(nsamp), C.c_void_p(x_dev_ptr), int(ldx),
+                          self._sample_kind(kind), int(seed), int(first_sample), int(stream0), 0 if common_noise else 1,
+                          None if mean_dev_ptr is None else C.c_void_p(mean_dev_ptr), int(ldmean), ok=self._BATCH_OK)
+
+    def white_noise_batch_dev(self, z_dev_ptr, nsamp, ldz=None, seed=0, first_sample=0, stream0=0, common_noise=False):
+        """spllt_hip_white_noise_batch_dev: the standard normals the batched samplers use into device memory,
+        sample q of member b at z[(b*nsamp + q)*ldz .. + n) in PIVOT order.  Returns 0 or -20."""
+        if ldz is None:
+            ldz = max(self.n, 1)
+        return self._call("spllt_hip_white_noise_batch_dev", self.fkeep, int(nsamp), C.c_void_p(z_dev_ptr), int(ldz),
+                          int(seed), int(first_sample), int(stream0), 0 if common_noise else 1, ok=self._BATCH_OK)
+
+    def white_noise_batch(self, nsamp, seed, first_sample=0, stream0=0, common_noise=False):
+        """white_noise_batch_dev, copied to the host: (B, n, nsamp), row p = pivot position p (member b's slice is
+        what white_noise returns, for its stream)."""
+        import torch
+        if int(nsamp) < 0:
+            raise ValueError("white_noise_batch: nsamp < 0")
+        nb, n1 = max(self._batch_count(), 0), max(self.n, 1)
+        z = torch.empty((max(nb, 1), int(nsamp), n1), dtype=torch.float64, device="cuda")
+        self.white_noise_batch_dev(z.data_ptr(), nsamp, n1, seed, first_sample, stream0, common_noise)
+        return np.ascontiguousarray(z.cpu().numpy()[:nb, :, :self.n].transpose(0, 2, 1))
+
+    def release_factor_mult_batch(self):
+        """The workspaces and the scratch of the batched products back to the device pool."""
+        self._call("spllt_hip_release_factor_mult_batch", self.fkeep)
+        return self
+
     # ---- batched selected inversion -------------------------------------------
     def selected_inverse_batch(self):
         """spllt_hip_selected_inverse_batch: Z_b on the pattern of L for every member of the last batch.

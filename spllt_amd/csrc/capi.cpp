@@ -28,6 +28,7 @@
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "spllt_hip.h"
+#include "spllt_hip_batch_mult.h"
 #include "symbolic.hpp"
 
 using namespace spx;
@@ -715,11 +716,13 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 // reads it, "teardown" runs the atexit handler of the pools now; then the "name=value" switches:
 //   batch_grid_limit=N      the grid size from which on a batched launch is split by member range (N <= 0: the
 //                           hardware limit again)
-//   fmult_alloc_fail=N      the next N allocations of the products' second workspace and scratch fail
+//   fmult_alloc_fail=N      the next N allocations of the products' second workspace and scratch fail (those of
+//                           the batched products included)
 //   batch_selinv_fused=0|1  0 forces the three-launch form of every step of the batched selected inversion
 //   rsolve_poison=0|1       1 fills the scratch of the reproducible solve with NaN before every sweep
 //   solve_sparse_poison=0|1 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
-//   fmult_poison=0|1        1 fills the scratch of the factor products with NaN before every direction
+//   fmult_poison=0|1        1 fills the scratch of the factor products (the batched ones too) with NaN before every
+//                           direction
 int spllt_hip_debug(const char* what) {
   if (!what) return -1;
   const std::string w(what);
@@ -1040,6 +1043,75 @@ int spllt_hip_solve_batch(void* fkeep, int nrhs, double* x_host, int64_t ldx, in
 
 int spllt_hip_solve_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
   return solve_batch_impl(fkeep, nrhs, x_dev, ldx, job, true, pivot_order != 0, "spllt_hip_solve_batch_dev");
+}
+
+// ---- factor products and sampling for the members of a batch (spllt_hip_batch_mult.h) -------------
+// the rungs of solve_batch_impl, in its order; -20 of the batch calls with the message of the family
+static int batch_mult_leave(Fkeep* f, const char* what, int rc, const char* failed) {
+  if (rc == SPLLT_ERROR_NOT_POSDEF) return fail(f, what, std::string(failed) + " (spllt_hip_batch_status)", rc);
+  return leave(f, rc);
+}
+
+static int factor_mult_batch_impl(void* fkeep, int nvec, double* x, int64_t ldx, int job, bool dev, bool pivot_order,
+                                  const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (int rc = enter(f, what, vectors_bad(f, nvec, x, ldx, job), SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (nvec == 0) return 0;
+  Engine& e = *f->eng;
+  return batch_mult_leave(f, what, dev ? e.factor_mult_batch_dev(x, nvec, ldx, job, pivot_order) : e.factor_mult_batch(x, nvec, ldx, job),
+                          "the vectors of the members that are not positive definite were left unchanged");
+}
+
+int spllt_hip_factor_mult_batch(void* fkeep, int nvec, double* x_host, int64_t ldx, int job) {
+  return factor_mult_batch_impl(fkeep, nvec, x_host, ldx, job, false, false, "spllt_hip_factor_mult_batch");
+}
+
+int spllt_hip_factor_mult_batch_dev(void* fkeep, int nvec, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  return factor_mult_batch_impl(fkeep, nvec, x_dev, ldx, job, true, pivot_order != 0, "spllt_hip_factor_mult_batch_dev");
+}
+
+int spllt_hip_white_noise_batch_dev(void* fkeep, int nsamp, double* z_dev, int64_t ldz, uint64_t seed,
+                                    uint64_t first_sample, uint32_t stream0, int stream_step) {
+  const char* what = "spllt_hip_white_noise_batch_dev";
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = vectors_bad(f, nsamp, z_dev, ldz, 0);
+  if (!bad && (stream_step < 0 || stream_step > 1)) bad = "stream_step is not 0 (common noise) or 1 (a stream per member)";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (nsamp == 0) return 0;
+  return batch_mult_leave(f, what, f->eng->white_noise_batch_dev(z_dev, nsamp, ldz, seed, first_sample, stream0, stream_step),
+                          "the noise of the members that are not positive definite is NaN");
+}
+
+static int sample_batch_impl(const char* what, void* fkeep, int nsamp, double* x, int64_t ldx, int kind, uint64_t seed,
+                             uint64_t first_sample, uint32_t stream0, int stream_step, const double* mean, int64_t ldmean,
+                             bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = vectors_bad(f, nsamp, x, ldx, 0);
+  if (!bad && (kind < 0 || kind > 1)) bad = "kind is not 0 (precision) or 1 (covariance)";
+  if (!bad && (stream_step < 0 || stream_step > 1)) bad = "stream_step is not 0 (common noise) or 1 (a stream per member)";
+  if (!bad && mean && ldmean != 0 && ldmean < f->S->n) bad = "ldmean is neither 0 (one mean for all members) nor >= n";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (nsamp == 0) return 0;
+  return batch_mult_leave(f, what,
+                          f->eng->sample_batch(x, nsamp, ldx, kind, seed, first_sample, stream0, stream_step, mean, ldmean, dev),
+                          "the samples of the members that are not positive definite are NaN");
+}
+
+int spllt_hip_sample_batch(void* fkeep, int nsamp, double* x_host, int64_t ldx, int kind, uint64_t seed,
+                           uint64_t first_sample, uint32_t stream0, int stream_step, const double* mean_host,
+                           int64_t ldmean) {
+  return sample_batch_impl("spllt_hip_sample_batch", fkeep, nsamp, x_host, ldx, kind, seed, first_sample, stream0,
+                           stream_step, mean_host, ldmean, false);
+}
+
+int spllt_hip_sample_batch_dev(void* fkeep, int nsamp, double* x_dev, int64_t ldx, int kind, uint64_t seed,
+                               uint64_t first_sample, uint32_t stream0, int stream_step, const double* mean_dev,
+                               int64_t ldmean) {
+  return sample_batch_impl("spllt_hip_sample_batch_dev", fkeep, nsamp, x_dev, ldx, kind, seed, first_sample, stream0,
+                           stream_step, mean_dev, ldmean, true);
 }
 
 // ---- refined solves ---------------------------------------------------------
@@ -1487,6 +1559,7 @@ int spllt_hip_release_factor_mult(void* fkeep) { return release(fkeep, &Engine::
 int spllt_hip_release_solve_sparse(void* fkeep) { return release(fkeep, &Engine::release_solve_sparse, WAIT_NOT_POSDEF); }
 int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::release_refine, WAIT_IGNORE); }
 int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::release_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse_batch(void* fkeep) { return release(fkeep, &Engine::release_inverse_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse(void* fkeep) { return release(fkeep, &Engine::release_inverse, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_adjoint(void* fkeep) { return release(fkeep, &Engine::release_factor_adjoint, WAIT_IGNORE | LENIENT); }

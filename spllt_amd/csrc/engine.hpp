@@ -174,6 +174,24 @@ class Engine {
   // when set_reproducible_solve is on, else of solve_many); mean: n doubles in user order or null; user order
   int sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, const double* mean, bool dev);
   int release_factor_mult();                                          // workspace, scratch and tables back to the pool
+  // ---- the same for every member of the last batch (batch_mult.hip): vector q of member b at x[(b nvec + q) ldx ..],
+  // the layout of solve_batch; every launch carries all members (two per direction, plus pack and unpack, per
+  // block of 32 vectors per member).  The tables are those of prepare_factor_mult, applied to the members'
+  // arenas; taken on first use: two workspaces of nbatch rb n doubles and a scratch of nbatch rb max(frows,
+  // bsize), rb = 32, or 16 when that does not fit (-1: no memory either way, nothing kept; the batch, its solve
+  // and the single factorization stay usable).  Kept until release_factor_mult_batch / release_batch, re-taken
+  // when a later batch has more members.  A member that is not positive definite: its vectors stay as they
+  // were, its noise and samples are NaN, the call returns -20.
+  int factor_mult_batch_dev(double* x_dev, int nvec, int64_t ldx, int job, bool pivot_order);
+  int factor_mult_batch(double* x_host, int nvec, int64_t ldx, int job);   // host vectors, user order
+  // z[(b nsamp + q) ldz + p] = N(0, 1) of (seed, pivot position p, stream stream0 + b stream_step, sample first + q)
+  int white_noise_batch_dev(double* z_dev, int nsamp, int64_t ldz, uint64_t seed, uint64_t first, uint32_t stream0,
+                            int stream_step);
+  // x[(b nsamp + q) ldx ..] = mean_b + P^T L_b z_bq (kind 1) or mean_b + P^T L_b^-T z_bq (kind 0: the backward sweep
+  // of solve_batch); mean: null, n doubles for all members (ldmean = 0) or member b's at mean + b ldmean
+  int sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, uint32_t stream0,
+                   int stream_step, const double* mean, int64_t ldmean, bool dev);
+  int release_factor_mult_batch();
   // ---- sparse right-hand sides and selected outputs (solve_sparse.hip, single GPU): B = k sparse columns (CSC,
   // 1-based, user order, validated by the caller: check_sparse_columns), sel = nsel wanted user variables (null:
   // all n).  Per group of 32 columns (a tail of at most 16: a block of 16) the substitution program is filtered
@@ -465,7 +483,11 @@ class Engine {
   // the last of the two is released
   hipError_t ensure_rsolve_tables();
   void drop_rsolve_tables();
-  // factor products (taken on first use, all or nothing)
+  // factor products (taken on first use, all or nothing).  The RsolveTables and the chunk list are shared by the
+  // single-handle products (fm_ready_) and the batched ones (bm_ready_) and given back with the last of the two.
+  hipError_t ensure_fmult_tables();
+  void drop_fmult_tables();
+  hipError_t fmult_take(void** p, size_t bytes);   // dalloc, unless the debug hook "fmult_alloc_fail" says no
   int prepare_factor_mult(bool host_stage);
   void enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
   bool fm_ready_ = false;
@@ -476,6 +498,21 @@ class Engine {
   double* d_fmW_ = nullptr;        // fm_rb_ * n doubles: the second workspace
   double* d_fmscratch_ = nullptr;  // fm_rb_ * rs_stride_ doubles
   double* d_fmmean_ = nullptr;     // n doubles: the mean of a host entry point
+  // batched factor products: workspaces and scratch for bm_capacity_ members
+  int prepare_factor_mult_batch();
+  void drop_factor_mult_batch();
+  BmultView bmult_view(int rb) const;
+  void enqueue_factor_mult_batch_block(double* x_dev, int64_t xstride, int64_t ldx, int nv, int rb, int job,
+                                       bool pivot_order);
+  int batch_failed() const;        // -20 when a member of the last batch is not positive definite
+  bool bm_ready_ = false;
+  int bm_rb_ = 32;                 // widest block the workspaces and the scratch hold
+  int bm_capacity_ = 0;            // members they hold
+  int bm_member_fast_ = 0;         // grid order of the product kernels (experiment knob, batch_mult.hip)
+  double* d_bmW_[2] = {nullptr, nullptr};   // bm_capacity_ * bm_rb_ * n doubles each
+  double* d_bmscratch_ = nullptr;  // bm_capacity_ * bm_rb_ * rs_stride_ doubles
+  double* d_bmmean_ = nullptr;     // the means of a host entry point
+  size_t bm_mean_elems_ = 0;
   // blocked solve (workspace allocated on first use, kept with the engine)
   int prepare_solve_many(bool host_stage);
   void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);

@@ -606,7 +606,7 @@ int Engine::prepare_solve_repro() {
     for (void* p : {(void*)d_rsscratch_, (void*)d_rsstage_})
       if (p) release_buffer(p);
     d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
-    if (!fm_ready_) drop_rsolve_tables();
+    if (!d_fmtab_) drop_rsolve_tables();   // (the tables of the products, single or batched, hold them too)
     feature_err_ = "solve_repro: not enough device memory for the tables and the scratch of 4 right-hand sides (" +
                    std::to_string(sb >> 20) + " MiB): " + hipGetErrorString(e);
     return alloc_code(e);
@@ -624,7 +624,7 @@ int Engine::release_solve_repro() {
   for (void* p : {(void*)d_rsscratch_, (void*)d_rsstage_})
     if (p) release_buffer(p);
   d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
-  if (!fm_ready_) drop_rsolve_tables();
+  if (!d_fmtab_) drop_rsolve_tables();   // (the tables of the products, single or batched, hold them too)
   rs_ready_ = false;
   return 0;
 }
@@ -707,36 +707,52 @@ static std::atomic<int> g_fmult_alloc_fail{0};
 void set_fmult_poison(bool on) { g_fmult_poison.store(on); }
 void set_fmult_alloc_fail(int n) { g_fmult_alloc_fail.store(n); }
 
-int Engine::prepare_factor_mult(bool host_stage) {
-  int rc = prepare_solve_many(host_stage);
-  if (rc) return rc;
-  if (fm_ready_) return 0;
-  const size_t n1 = (size_t)std::max(1, S_->n);
-  // the (block column, chunk of 64 pivot positions) pairs of the diagonal launches, block columns ascending
+// the tables of the products: the RsolveTables and the (block column, chunk of 64 pivot positions) pairs of the
+// diagonal launches, block columns ascending
+hipError_t Engine::ensure_fmult_tables() {
+  if (d_fmtab_) return hipSuccess;
   std::vector<UpdTile> chunks;
   for (size_t b = 0; b < sprog_.units.size(); ++b)
     for (int c = 0; c * 64 < sprog_.units[b].w; ++c) chunks.push_back(UpdTile{(int)b, (short)c, 0});
   fm_nchunks_ = (int64_t)chunks.size();
-  // (a failure here leaves the factor and every solve usable: the engine's status is not touched)
   hipError_t e = ensure_rsolve_tables();
   if (e == hipSuccess) {
     TableStager tab;
     tab.add(&d_fmchunks_, chunks);
     e = tab.commit(&d_fmtab_, [this](void** q, size_t b) { return dalloc(q, b); });
   }
+  if (e != hipSuccess) drop_fmult_tables();
+  return e;
+}
+
+// (the caller has checked that neither the single-handle products nor the batched ones are left)
+void Engine::drop_fmult_tables() {
+  if (d_fmtab_) release_buffer(d_fmtab_);
+  d_fmtab_ = nullptr; d_fmchunks_ = nullptr;
+  if (!rs_ready_) drop_rsolve_tables();
+}
+
+hipError_t Engine::fmult_take(void** p, size_t bytes) {
+  if (g_fmult_alloc_fail.load() > 0) {
+    g_fmult_alloc_fail.fetch_sub(1);
+    return hipErrorOutOfMemory;
+  }
+  return dalloc(p, bytes);
+}
+
+int Engine::prepare_factor_mult(bool host_stage) {
+  int rc = prepare_solve_many(host_stage);
+  if (rc) return rc;
+  if (fm_ready_) return 0;
+  const size_t n1 = (size_t)std::max(1, S_->n);
+  // (a failure here leaves the factor and every solve usable: the engine's status is not touched)
+  hipError_t e = ensure_fmult_tables();
   size_t want = 0;
-  auto take = [&](void** p, size_t bytes) {
-    if (g_fmult_alloc_fail.load() > 0) {
-      g_fmult_alloc_fail.fetch_sub(1);
-      return hipErrorOutOfMemory;
-    }
-    return dalloc(p, bytes);
-  };
   // blocks of 32 vectors; when that does not fit, blocks of 16 (per vector the same sums in the same order)
   for (int rb = 32; e == hipSuccess && rb >= 16; rb /= 2) {
     want = sizeof(double) * (size_t)rb * (n1 + (size_t)rs_stride_);
-    e = take((void**)&d_fmW_, sizeof(double) * (size_t)rb * n1);
-    if (e == hipSuccess) e = take((void**)&d_fmscratch_, sizeof(double) * (size_t)rb * (size_t)rs_stride_);
+    e = fmult_take((void**)&d_fmW_, sizeof(double) * (size_t)rb * n1);
+    if (e == hipSuccess) e = fmult_take((void**)&d_fmscratch_, sizeof(double) * (size_t)rb * (size_t)rs_stride_);
     fm_rb_ = rb;
     if (e == hipSuccess) break;
     (void)hipGetLastError();
@@ -747,9 +763,7 @@ int Engine::prepare_factor_mult(bool host_stage) {
   }
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    if (d_fmtab_) release_buffer(d_fmtab_);
-    d_fmtab_ = nullptr; d_fmchunks_ = nullptr;
-    if (!rs_ready_) drop_rsolve_tables();
+    if (!bm_ready_) drop_fmult_tables();
     feature_err_ = "factor_mult: not enough device memory for the tables, the second workspace and the scratch of 16 "
                    "vectors (" + std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
     return alloc_code(e);
@@ -764,11 +778,11 @@ int Engine::release_factor_mult() {
   if (!fm_ready_ && !d_fmmean_) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "factor_mult release")) return rc;
-  for (void* p : {(void*)d_fmtab_, (void*)d_fmW_, (void*)d_fmscratch_, (void*)d_fmmean_})
+  for (void* p : {(void*)d_fmW_, (void*)d_fmscratch_, (void*)d_fmmean_})
     if (p) release_buffer(p);
-  d_fmtab_ = nullptr; d_fmchunks_ = nullptr; d_fmW_ = nullptr; d_fmscratch_ = nullptr; d_fmmean_ = nullptr;
+  d_fmW_ = nullptr; d_fmscratch_ = nullptr; d_fmmean_ = nullptr;
   fm_ready_ = false;
-  if (!rs_ready_) drop_rsolve_tables();
+  if (!bm_ready_) drop_fmult_tables();
   return 0;
 }
 
@@ -904,6 +918,249 @@ int Engine::sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, u
     done += nv;
   }
   return 0;
+}
+
+// ---- the products and the samplers for every member of a batch ---------------------------------------
+void Engine::drop_factor_mult_batch() {
+  for (void* p : {(void*)d_bmW_[0], (void*)d_bmW_[1], (void*)d_bmscratch_, (void*)d_bmmean_})
+    if (p) release_buffer(p);
+  d_bmW_[0] = d_bmW_[1] = d_bmscratch_ = d_bmmean_ = nullptr;
+  bm_mean_elems_ = 0;
+  bm_capacity_ = 0;
+  const bool had = bm_ready_;
+  bm_ready_ = false;
+  if (had && !fm_ready_) drop_fmult_tables();
+}
+
+// tables (shared with the single-handle products), two workspaces and the scratch for the members of the last
+// batch; all or nothing
+int Engine::prepare_factor_mult_batch() {
+  int rc = prepare_solve();   // (the handle's solve_units / solve_tiles: they describe every member's arena)
+  if (rc) return rc;
+  const int nbatch = bt_.nbatch;
+  if (bm_ready_ && nbatch <= bm_capacity_) return 0;
+  if (bm_ready_) drop_factor_mult_batch();   // (a larger batch: everything again)
+  const size_t n1 = (size_t)std::max(1, S_->n);
+  // (a failure here leaves the batch, its solve and the single factorization usable)
+  hipError_t e = ensure_order();
+  if (e == hipSuccess) e = ensure_fmult_tables();
+  size_t want = 0;
+  for (int rb = 32; e == hipSuccess && rb >= 16; rb /= 2) {
+    const size_t wb = sizeof(double) * (size_t)nbatch * (size_t)rb * n1;
+    const size_t sb = sizeof(double) * (size_t)nbatch * (size_t)rb * (size_t)rs_stride_;
+    want = 2 * wb + sb;
+    e = fmult_take((void**)&d_bmW_[0], wb);
+    if (e == hipSuccess) e = fmult_take((void**)&d_bmW_[1], wb);
+    if (e == hipSuccess) e = fmult_take((void**)&d_bmscratch_, sb);
+    bm_rb_ = rb;
+    if (e == hipSuccess) break;
+    (void)hipGetLastError();
+    for (void* p : {(void*)d_bmW_[0], (void*)d_bmW_[1], (void*)d_bmscratch_})
+      if (p) release_buffer(p);
+    d_bmW_[0] = d_bmW_[1] = d_bmscratch_ = nullptr;
+    if (rb > 16 && alloc_code(e) == -1) e = hipSuccess;   // (out of memory: once more with half of it)
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (!fm_ready_) drop_fmult_tables();
+    feature_err_ = "factor_mult_batch: not enough device memory for the tables, two workspaces and the scratch of 16 "
+                   "vectors for each of " + std::to_string(nbatch) + " members (" + std::to_string(want >> 20) +
+                   " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  // experiment knob of scripts/factor_mult_batch_bench.py (the A/B of the two grid orders)
+  if (const char* env = std::getenv("SPLLT_BATCH_MULT_MEMBER_FAST")) bm_member_fast_ = std::atoi(env) != 0;
+  bm_capacity_ = nbatch;
+  bm_ready_ = true;
+  return 0;
+}
+
+int Engine::release_factor_mult_batch() {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!bm_ready_ && !d_bmmean_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "factor_mult_batch release")) return rc;
+  drop_factor_mult_batch();
+  return 0;
+}
+
+BmultView Engine::bmult_view(int rb) const {
+  return BmultView{bt_.L, bt_.flag, bt_.lstride, (int64_t)rb * S_->n, (int64_t)rb * rs_stride_, bt_.nbatch, bm_member_fast_};
+}
+
+int Engine::batch_failed() const {
+  for (int fl : bt_.hflag)
+    if (fl != INT_MAX) return kErrNotPosDef;
+  return 0;
+}
+
+// one block of nv <= rb vectors of every member (member b's at x_dev + b * xstride): pack, the products `job`
+// asks for, unpack (enqueue only); the workspaces play the parts of enqueue_factor_mult_block
+void Engine::enqueue_factor_mult_batch_block(double* x_dev, int64_t xstride, int64_t ldx, int nv, int rb, int job,
+                                             bool pivot_order) {
+  const int n = S_->n;
+  const int* order = pivot_order ? nullptr : d_order_;
+  const SolveTablesView tv = solve_tables();
+  const BmultView v = bmult_view(rb);
+  const FmultView fv{d_rsfslot_, d_rsbfirst_, d_rsgptr_, d_rsgsrc_, d_rsbslot_, d_bmscratch_};
+  const int64_t ntiles = (int64_t)sprog_.tiles.size();
+  auto product = [&](bool transpose, const double* X, double* Y) {
+    // debug: a slot that is read without having been written by this product shows up as NaN
+    if (g_fmult_poison.load())
+      (void)hipMemsetAsync(d_bmscratch_, 0xFF, sizeof(double) * (size_t)bm_capacity_ * (size_t)bm_rb_ * (size_t)rs_stride_,
+                           stream_);
+    launch_batch_mult(stream_, v, tv, ntiles, d_fmchunks_, fm_nchunks_, transpose, X, Y, rb, fv);
+  };
+  launch_batch_mult_pack(stream_, v, false, x_dev, xstride, ldx, order, n, nv, rb, d_bmW_[0]);
+  if (job != 1) product(true, d_bmW_[0], d_bmW_[1]);
+  if (job == 0) product(false, d_bmW_[1], d_bmW_[0]);
+  if (job == 1) product(false, d_bmW_[0], d_bmW_[1]);
+  launch_batch_mult_pack(stream_, v, true, x_dev, xstride, ldx, order, n, nv, rb, job == 0 ? d_bmW_[0] : d_bmW_[1]);
+}
+
+int Engine::factor_mult_batch_dev(double* x_dev, int nvec, int64_t ldx, int job, bool pivot_order) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!x_dev || nvec < 0 || ldx < S_->n || job < 0 || job > 2 || bt_.nbatch <= 0) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;          // (the caller waits first)
+  if (nvec == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_factor_mult_batch();
+  if (rc) return rc;
+  for (int done = 0; done < nvec;) {
+    const int left = nvec - done;
+    const int rb = left > 16 && bm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
+    enqueue_factor_mult_batch_block(x_dev + (int64_t)done * ldx, (int64_t)nvec * ldx, ldx, nv, rb, job, pivot_order);
+    done += nv;
+  }
+  HIPCHK(hipGetLastError(), "factor_mult_batch launch");
+  if ((rc = sync_stream(stream_, "factor_mult_batch sync"))) return rc;
+  return batch_failed();
+}
+
+// groups of at most 32 vectors per member through the batch's staging buffer
+int Engine::factor_mult_batch(double* x_host, int nvec, int64_t ldx, int job) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!x_host || nvec < 0 || ldx < S_->n || job < 0 || job > 2 || bt_.nbatch <= 0) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nvec == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_factor_mult_batch();
+  if (rc) return rc;
+  const int n = S_->n, nbatch = bt_.nbatch;
+  if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)std::min(nvec, 32) * (size_t)n,
+                              "the staged vectors")))
+    return rc;
+  for (int done = 0; done < nvec;) {
+    const int left = nvec - done;
+    const int rb = left > 16 && bm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
+    // (a failed member's vectors make the round trip unchanged: nothing on the device touches them)
+    for (int b = 0; b < nbatch; ++b)
+      if ((rc = copy_vectors(true, bt_.stage + (int64_t)b * nv * n, x_host + ((int64_t)b * nvec + done) * ldx, ldx, nv,
+                             "batch x H2D")))
+        return rc;
+    enqueue_factor_mult_batch_block(bt_.stage, (int64_t)nv * n, n, nv, rb, job, false);
+    HIPCHK(hipGetLastError(), "factor_mult_batch launch");
+    for (int b = 0; b < nbatch; ++b)
+      if ((rc = copy_vectors(false, bt_.stage + (int64_t)b * nv * n, x_host + ((int64_t)b * nvec + done) * ldx, ldx, nv,
+                             "batch y D2H")))
+        return rc;
+    if ((rc = sync_stream(stream_, "factor_mult_batch sync"))) return rc;
+    done += nv;
+  }
+  return batch_failed();
+}
+
+int Engine::white_noise_batch_dev(double* z_dev, int nsamp, int64_t ldz, uint64_t seed, uint64_t first, uint32_t stream0,
+                                  int stream_step) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!z_dev || nsamp < 0 || ldz < S_->n || stream_step < 0 || stream_step > 1 || bt_.nbatch <= 0) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nsamp == 0 || S_->n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  launch_batch_white_noise(stream_, bmult_view(16), z_dev, (int64_t)nsamp * ldz, ldz, nullptr, S_->n, nsamp, seed, first,
+                           stream0, stream_step);
+  HIPCHK(hipGetLastError(), "white_noise_batch launch");
+  if (int rc = sync_stream(stream_, "white_noise_batch sync")) return rc;
+  return batch_failed();
+}
+
+// As Engine::sample: the noise is written where the operation that follows expects a pivot-order vector laid out in
+// user positions, the product and the sweep then run through their own batch entry points.
+int Engine::sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, uint32_t stream0,
+                         int stream_step, const double* mean, int64_t ldmean, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n, nbatch = bt_.nbatch;
+  if (!x || nsamp < 0 || ldx < n || kind < 0 || kind > 1 || stream_step < 0 || stream_step > 1 ||
+      (mean && ldmean != 0 && ldmean < n) || nbatch <= 0)
+    return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;
+  if (nsamp == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = kind == 1 ? prepare_factor_mult_batch() : 0;
+  if (rc) return rc;
+  if (hipError_t e = ensure_order()) {
+    (void)hipGetLastError();
+    feature_err_ = std::string("sample_batch: the order table could not be uploaded: ") + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  const double* dmean = mean;
+  int64_t ldm = ldmean;
+  if (mean && !dev) {
+    const size_t nm = ldmean == 0 ? 1 : (size_t)nbatch;
+    if ((rc = grow_batch_buffer(&d_bmmean_, &bm_mean_elems_, nm * (size_t)n, "the means"))) return rc;
+    if ((rc = copy_vectors_to_device(d_bmmean_, mean, ldmean, (int64_t)nm, "mean H2D"))) return rc;
+    dmean = d_bmmean_;
+    ldm = ldmean == 0 ? 0 : n;
+  }
+  // one group of nv samples per member on device vectors (member b's at xg + b * xs, sample q at + q * ld)
+  auto group = [&](double* xg, int64_t xs, int64_t ld, int nv, uint64_t s0) -> int {
+    launch_batch_white_noise(stream_, bmult_view(16), xg, xs, ld, d_order_, n, nv, seed, s0, stream0, stream_step);
+    if (kind == 1) {
+      for (int done = 0; done < nv;) {
+        const int left = nv - done;
+        const int rb = left > 16 && bm_rb_ == 32 ? 32 : 16, cur = std::min(left, rb);
+        enqueue_factor_mult_batch_block(xg + (int64_t)done * ld, xs, ld, cur, rb, 1, false);
+        done += cur;
+      }
+    } else {
+      // (xs = nv * ld: the layout of solve_batch; its -20 is this call's own: the failed members keep their NaN)
+      const int r = solve_batch(xg, true, nv, ld, 2, false);
+      if (r && r != kErrNotPosDef) return r;
+    }
+    if (dmean) launch_batch_add_mean(stream_, bmult_view(16), xg, xs, ld, dmean, ldm, n, nv);
+    HIPCHK(hipGetLastError(), "sample_batch launch");
+    return 0;
+  };
+  if (dev) {
+    if ((rc = group(x, (int64_t)nsamp * ldx, ldx, nsamp, first))) return rc;
+    if ((rc = sync_stream(stream_, "sample_batch sync"))) return rc;
+    return batch_failed();
+  }
+  // groups of at most 32 samples per member through the batch's staging buffer, packed (vector q of member b at
+  // (b * nv + q) * n: the layout of solve_batch, which stages nothing for vectors that are on the device)
+  const int gmax = std::min(nsamp, 32);
+  if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)gmax * (size_t)n, "the staged samples")))
+    return rc;
+  for (int done = 0; done < nsamp;) {
+    const int nv = std::min(gmax, nsamp - done);
+    if ((rc = group(bt_.stage, (int64_t)nv * n, (int64_t)n, nv, first + (uint64_t)done))) return rc;
+    for (int b = 0; b < nbatch; ++b)
+      if ((rc = copy_vectors(false, bt_.stage + (int64_t)b * nv * n, x + ((int64_t)b * nsamp + done) * ldx, ldx, nv,
+                             "batch x D2H")))
+        return rc;
+    if ((rc = sync_stream(stream_, "sample_batch sync"))) return rc;
+    done += nv;
+  }
+  return batch_failed();
 }
 
 // ---- refined solves --------------------------------------------------------------------------------

@@ -280,6 +280,33 @@ void launch_white_noise(hipStream_t st, double* z, int64_t ldz, const int* order
                         uint64_t first);
 // x[q * ldx + i] += mean[i], q < nvec
 void launch_add_mean(hipStream_t st, double* x, int64_t ldx, const double* mean, int n, int nvec);
+// ---- the same for every member of a batch (batch_mult.hip) -------------------------------------------
+// Member b: arena L + b * lstride (the layout of the single arena: the tables of the handle's SolveProgram apply),
+// flag[b], workspaces X + b * wstride and Y + b * wstride (wstride = rb * n), scratch fv.scratch + b * sstride.
+// A member whose flag is set is skipped by every kernel of a product, pack and unpack included.
+// member_fast: 0 = the member is the slow grid axis (the workgroups of one member are consecutive), 1 = the
+// members of one work item are consecutive.  Every wrapper returns the number of kernel launches it made: the
+// members are split into ranges above 65535 (the y extent of a grid) and above batch_grid_limit() workgroups.
+struct BmultView {
+  const double* L;
+  const int* flag;
+  int64_t lstride, wstride, sstride;
+  int nbatch;
+  int member_fast;
+};
+// W_b[p(i) * rb + q] = q < nv ? x[b * xstride + q * ldx + i] : 0 (unpack: the other way, q < nv only)
+int launch_batch_mult_pack(hipStream_t st, const BmultView& v, bool unpack, double* x, int64_t xstride, int64_t ldx,
+                           const int* order, int n, int nv, int rb, double* W);
+// Y_b = L_b X_b (transpose: L_b^T X_b): two launches for all members, arguments as launch_factor_mult
+int launch_batch_mult(hipStream_t st, const BmultView& v, const SolveTablesView& t, int64_t ntiles, const UpdTile* chunks,
+                      int64_t nchunks, bool transpose, const double* X, double* Y, int rb, const FmultView& fv);
+// z[b * zstride + q * ldz + i] = the standard normal of (pivot position order[i] (null: i), stream stream0 +
+// b * stream_step, sample first + q, seed); NaN for a member whose flag is set
+int launch_batch_white_noise(hipStream_t st, const BmultView& v, double* z, int64_t zstride, int64_t ldz, const int* order,
+                             int n, int nsamp, uint64_t seed, uint64_t first, uint32_t stream0, int stream_step);
+// x[b * xstride + q * ldx + i] += mean[b * ldmean + i], q < nvec (ldmean = 0: one mean for all members)
+int launch_batch_add_mean(hipStream_t st, const BmultView& v, double* x, int64_t xstride, int64_t ldx, const double* mean,
+                          int64_t ldmean, int n, int nvec);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
 

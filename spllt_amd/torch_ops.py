@@ -274,6 +274,36 @@ class SparseCholesky:
         x = work.t()
         return x if mean is None else x + mean[:, None]
 
+    def sample_batch(self, vals, nsamp, seed=0, kind="precision", mean=None, common_noise=False):
+        """nsamp draws per member of N(mean_b, A(vals[b])^-1) (kind "precision") or N(mean_b, A(vals[b]))
+        ("covariance") from the cached factors of the batch (those of solve_batch / logdet_batch): a float64 device
+        tensor (nbatch, n, nsamp).  vals: (nbatch, nnz); mean: (n,) for all members or (nbatch, n).  Member b draws
+        from a noise stream of its own, common_noise=True gives every member the same noise (Factorization.sample_batch).
+        The result carries NO gradient, neither to vals nor to mean, like the draws of ``sample`` with respect to val:
+        it is computed under no_grad, mean added on the device.  reproducible=True raises NotImplementedError, like the
+        other batch operations."""
+        if self.reproducible:
+            raise NotImplementedError("sample_batch: the batch has no deterministic form (reproducible=True)")
+        self._values(vals, "vals", (None, self.nnz))
+        ldmean = 0
+        if mean is not None:
+            if isinstance(mean, torch.Tensor) and mean.dim() == 2:
+                self._tensor(mean, "mean", (vals.shape[0], self.n), vals.device)
+                ldmean = self.n
+            else:
+                self._tensor(mean, "mean", (self.n,), vals.device)
+        self._enter(vals)
+        with torch.no_grad():
+            self._ensure_batch(vals)
+            work = torch.empty((vals.shape[0], int(nsamp), self.n), dtype=torch.float64, device=self.device)
+            m = None if mean is None else mean.detach().contiguous()
+            self._sync()
+            with torch.cuda.device(self.device):
+                self.f.sample_batch_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed, kind=kind,
+                                        mean_dev_ptr=None if m is None else m.data_ptr(), ldmean=ldmean,
+                                        common_noise=common_noise)
+        return work.transpose(1, 2)
+
     # ---- operations with the factor in the graph ------------------------------------------------------
     def _factor_op_inplace(self, work, op):
         """work: (nvec, n) contiguous, overwritten with op(L) applied to every vector (user layout)"""
