@@ -1011,6 +1011,57 @@ class Factorization:
         self._call("spllt_hip_release_factor_mult_batch", self.fkeep)
         return self
 
+    # ---- blocked solve for the members of a batch (include/spllt_hip_batch_solve_many.h) -----
+    def solve_many_batch(self, X, job=0):
+        """spllt_hip_solve_many_batch on a copy of X: shape (B, n), one vector per member, or (B, nrhs, n), like
+        solve_batch, whose numbers it gives to rounding.  A member's vectors go through the fp64 matrix cores in
+        blocks of 32 (a tail of at most 16: a block of 16), its factor is read once per block: the call for many
+        right-hand sides per member.  Measured: with 8 or more right-hand sides per member
+        and 4 or more members it is 1.3 to 12 times faster than solve_batch; with ONE right-hand side per member and
+        the backward sweep alone (job 2) solve_batch is faster (this path at 0.73-0.98 of it: a block of 16 is the
+        least it runs), and so it is for a batch of one small matrix with well over 32 right-hand sides of job 2
+        (0.57 on poisson2d_128 with 128).  job 0 / 1 / 2 as solve_batch.
+        The vectors of a member that is not positive definite come back unchanged."""
+        x = np.array(X, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (2, 3):
+            raise ValueError("solve_many_batch: X must have shape (B, n) or (B, nrhs, n)")
+        nrhs = 1 if x.ndim == 2 else x.shape[1]
+        if x.shape[-1] != self.n:
+            raise ValueError(f"solve_many_batch: the vectors have length {x.shape[-1]}, n = {self.n}")
+        nb = self._batch_count()
+        if nb > 0 and x.shape[0] != nb:
+            raise ValueError(f"solve_many_batch: X holds vectors for {x.shape[0]} members, the last batch has {nb}")
+        self._call("spllt_hip_solve_many_batch", self.fkeep, nrhs, C.c_void_p(x.ctypes.data), x.shape[-1], job,
+                   ok=self._BATCH_OK)
+        return x
+
+    def solve_many_batch_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
+        """spllt_hip_solve_many_batch_dev: device vectors in place, the layout of solve_batch_dev.  Returns 0 or
+        -20."""
+        if int(nrhs) < 0:
+            raise ValueError("solve_many_batch_dev: nrhs < 0")
+        if ldx is None:
+            ldx = self.n
+        return self._call("spllt_hip_solve_many_batch_dev", self.fkeep, int(nrhs), C.c_void_p(x_dev_ptr), int(ldx), job,
+                          1 if pivot_order else 0, ok=self._BATCH_OK)
+
+    def set_batch_blocked_solve(self, on):
+        """Route the backward sweep of sample_batch(kind="precision") through the blocked path (off by default;
+        the samples agree to rounding).  Returns the previous setting."""
+        return bool(self._call("spllt_hip_set_batch_blocked_solve", self.fkeep, 1 if on else 0))
+
+    def solve_many_batch_info(self):
+        """of the blocked batch solve: block width in use (0: no storage held), blocks per member and kernel
+        launches of the last call, bytes of the workspace"""
+        out = np.zeros(4, dtype=np.int64)
+        self._call("spllt_hip_solve_many_batch_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        return dict(zip(("rb", "blocks", "launches", "workspace_bytes"), (int(v) for v in out)))
+
+    def release_solve_many_batch(self):
+        """The workspace of the blocked batch solve back to the device pool."""
+        self._call("spllt_hip_release_solve_many_batch", self.fkeep)
+        return self
+
     # ---- batched selected inversion -------------------------------------------
     def selected_inverse_batch(self):
         """spllt_hip_selected_inverse_batch: Z_b on the pattern of L for every member of the last batch.

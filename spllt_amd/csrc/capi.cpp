@@ -29,6 +29,7 @@
 #include "kernels.hpp"
 #include "spllt_hip.h"
 #include "spllt_hip_batch_mult.h"
+#include "spllt_hip_batch_solve_many.h"
 #include "symbolic.hpp"
 
 using namespace spx;
@@ -81,6 +82,7 @@ struct Fkeep {
   double* xbuf = nullptr;  // multi-GPU exchange buffer (caller-owned device memory)
   bool dead = false;       // a submission never returned: the engine belongs to the stuck helper thread
   bool repro_solve = false;   // spllt_hip_set_reproducible_solve: handed to the engine before every solve
+  bool batch_blocked = false;   // spllt_hip_set_batch_blocked_solve: handed to the engine before every sample_batch
   // what spllt_hip_program_get builds from the analysis alone, each once per pattern (and key):
   Cached<SelinvProgram> si;    // the selected-inversion program, keyed by panel width and chain block
   Cached<SelinvProgram> bsi;   // ... and the batch's (panel width 64 whatever the handle's)
@@ -717,7 +719,7 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 //   batch_grid_limit=N      the grid size from which on a batched launch is split by member range (N <= 0: the
 //                           hardware limit again)
 //   fmult_alloc_fail=N      the next N allocations of the products' second workspace and scratch fail (those of
-//                           the batched products included)
+//                           the batched products and the workspace of the batched blocked solve included)
 //   batch_selinv_fused=0|1  0 forces the three-launch form of every step of the batched selected inversion
 //   rsolve_poison=0|1       1 fills the scratch of the reproducible solve with NaN before every sweep
 //   solve_sparse_poison=0|1 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
@@ -1095,6 +1097,7 @@ static int sample_batch_impl(const char* what, void* fkeep, int nsamp, double* x
   if (!bad && mean && ldmean != 0 && ldmean < f->S->n) bad = "ldmean is neither 0 (one mean for all members) nor >= n";
   if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
   if (nsamp == 0) return 0;
+  f->eng->set_batch_blocked_solve(f->batch_blocked);
   return batch_mult_leave(f, what,
                           f->eng->sample_batch(x, nsamp, ldx, kind, seed, first_sample, stream0, stream_step, mean, ldmean, dev),
                           "the samples of the members that are not positive definite are NaN");
@@ -1112,6 +1115,45 @@ int spllt_hip_sample_batch_dev(void* fkeep, int nsamp, double* x_dev, int64_t ld
                                int64_t ldmean) {
   return sample_batch_impl("spllt_hip_sample_batch_dev", fkeep, nsamp, x_dev, ldx, kind, seed, first_sample, stream0,
                            stream_step, mean_dev, ldmean, true);
+}
+
+// ---- blocked solve for the members of a batch (spllt_hip_batch_solve_many.h) -----------------------
+// the rungs of solve_batch_impl, in its order
+static int solve_many_batch_impl(void* fkeep, int nrhs, double* x, int64_t ldx, int job, bool dev, bool pivot_order,
+                                 const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (int rc = enter(f, what, vectors_bad(f, nrhs, x, ldx, job), SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (nrhs == 0) return 0;
+  return batch_mult_leave(f, what, f->eng->solve_many_batch(x, dev, nrhs, ldx, job, pivot_order),
+                          "the vectors of the members that are not positive definite were left unchanged");
+}
+
+int spllt_hip_solve_many_batch(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
+  return solve_many_batch_impl(fkeep, nrhs, x_host, ldx, job, false, false, "spllt_hip_solve_many_batch");
+}
+
+int spllt_hip_solve_many_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  return solve_many_batch_impl(fkeep, nrhs, x_dev, ldx, job, true, pivot_order != 0, "spllt_hip_solve_many_batch_dev");
+}
+
+int spllt_hip_set_batch_blocked_solve(void* fkeep, int on) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (on && f->eo.nranks > 1) {   // (a plain setter: refused without the stderr line of the guard)
+    f->last_error = "spllt_hip_set_batch_blocked_solve: not available on a partitioned (multi-GPU) handle";
+    return SPLLT_ERROR_UNIMPLEMENTED;
+  }
+  const int before = f->batch_blocked ? 1 : 0;
+  f->batch_blocked = on != 0;
+  return before;
+}
+
+int spllt_hip_solve_many_batch_info(void* fkeep, int64_t out[4]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 4; ++i) out[i] = f->eng ? f->eng->solve_many_batch_info()[i] : 0;
+  return 0;
 }
 
 // ---- refined solves ---------------------------------------------------------
@@ -1560,6 +1602,7 @@ int spllt_hip_release_solve_sparse(void* fkeep) { return release(fkeep, &Engine:
 int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::release_refine, WAIT_IGNORE); }
 int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::release_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_solve_many_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_many_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse_batch(void* fkeep) { return release(fkeep, &Engine::release_inverse_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse(void* fkeep) { return release(fkeep, &Engine::release_inverse, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_adjoint(void* fkeep) { return release(fkeep, &Engine::release_factor_adjoint, WAIT_IGNORE | LENIENT); }

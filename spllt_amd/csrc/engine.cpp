@@ -2207,10 +2207,11 @@ int Engine::release_batch() {
   feature_err_.clear();
   if (status_) return status_;
   bt_.z_valid = false;
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bm_ready_ && !d_bmmean_) { bt_.nbatch = 0; return 0; }
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bm_ready_ && !d_bmmean_ && !bsm_ready_) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
+  drop_solve_many_batch();    // (... and that of the blocked solve)
   for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out, (void*)bt_.Y, (void*)bt_.stage,
                   (void*)bt_.Z, (void*)bt_.siscratch})
     if (p) release_buffer(p);

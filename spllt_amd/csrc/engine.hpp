@@ -192,6 +192,22 @@ class Engine {
   int sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, uint32_t stream0,
                    int stream_step, const double* mean, int64_t ldmean, bool dev);
   int release_factor_mult_batch();
+  // ---- blocked solve for every member of the last batch (batch_solve_many.hip): the kernels of solve_many with
+  // member offsets, on the batch's own solve program.  Vector q of member b at x[(b nrhs + q) ldx ..], the layout
+  // of solve_batch; job 0 / 1 / 2 as there.  Each member's vectors go in blocks of 32 (a tail of at most 16: a
+  // block of 16); per block: pack, the launches of the sweeps, unpack -- every launch carries all members.
+  // Storage on first use: nbatch 32 n doubles, or nbatch 16 n with blocks of 16 only when that does not fit (-1:
+  // no memory either way, nothing kept; the batch, solve_batch and the single factorization stay usable).  Kept
+  // until release_solve_many_batch / release_batch, re-taken when a later batch has more members.  A member that
+  // is not positive definite: its vectors stay as they were, the call returns -20.
+  int solve_many_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order);
+  // on: the backward sweep of sample_batch kind 0 runs through solve_many_batch instead of solve_batch
+  void set_batch_blocked_solve(bool on) { bsm_on_ = on; }
+  bool batch_blocked_solve() const { return bsm_on_; }
+  // block width in use (32, 16 after the fallback, 0 before the first call), blocks per member and kernel launches
+  // of the last solve_many_batch, bytes of the workspace
+  const int64_t* solve_many_batch_info() const { return bsm_info_; }
+  int release_solve_many_batch();
   // ---- sparse right-hand sides and selected outputs (solve_sparse.hip, single GPU): B = k sparse columns (CSC,
   // 1-based, user order, validated by the caller: check_sparse_columns), sel = nsel wanted user variables (null:
   // all n).  Per group of 32 columns (a tail of at most 16: a block of 16) the substitution program is filtered
@@ -513,6 +529,17 @@ class Engine {
   double* d_bmscratch_ = nullptr;  // bm_capacity_ * bm_rb_ * rs_stride_ doubles
   double* d_bmmean_ = nullptr;     // the means of a host entry point
   size_t bm_mean_elems_ = 0;
+  // batched blocked solve: the workspace for bsm_capacity_ members
+  int prepare_solve_many_batch();
+  void drop_solve_many_batch();
+  int enqueue_solve_many_batch_block(double* x_dev, int64_t xstride, int64_t ldx, int nv, int rb, int job,
+                                     bool pivot_order);   // launches made, -1: a launch overflows a grid
+  bool bsm_ready_ = false;
+  bool bsm_on_ = false;            // sample_batch kind 0 goes through the blocked path
+  int bsm_rb_ = 32;                // widest block the workspace holds
+  int bsm_capacity_ = 0;           // members it holds
+  double* d_bsmW_ = nullptr;       // bsm_capacity_ * bsm_rb_ * n doubles: W_b[p * rb + q]
+  int64_t bsm_info_[4] = {0, 0, 0, 0};
   // blocked solve (workspace allocated on first use, kept with the engine)
   int prepare_solve_many(bool host_stage);
   void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);

@@ -1133,7 +1133,7 @@ int Engine::sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t s
       }
     } else {
       // (xs = nv * ld: the layout of solve_batch; its -20 is this call's own: the failed members keep their NaN)
-      const int r = solve_batch(xg, true, nv, ld, 2, false);
+      const int r = bsm_on_ ? solve_many_batch(xg, true, nv, ld, 2, false) : solve_batch(xg, true, nv, ld, 2, false);
       if (r && r != kErrNotPosDef) return r;
     }
     if (dmean) launch_batch_add_mean(stream_, bmult_view(16), xg, xs, ld, dmean, ldm, n, nv);
@@ -1160,6 +1160,135 @@ int Engine::sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t s
     if ((rc = sync_stream(stream_, "sample_batch sync"))) return rc;
     done += nv;
   }
+  return batch_failed();
+}
+
+// ---- blocked solve for every member of a batch -------------------------------------------------------
+void Engine::drop_solve_many_batch() {
+  if (d_bsmW_) release_buffer(d_bsmW_);
+  d_bsmW_ = nullptr;
+  bsm_capacity_ = 0;
+  bsm_ready_ = false;
+  bsm_info_[0] = bsm_info_[3] = 0;
+}
+
+// the workspace for the members of the last batch: 32 vectors per member, or 16 when that does not fit
+int Engine::prepare_solve_many_batch() {
+  const int nbatch = bt_.nbatch;
+  if (bsm_ready_ && nbatch <= bsm_capacity_) return 0;
+  if (bsm_ready_) drop_solve_many_batch();   // (a larger batch: the workspace again)
+  const size_t n1 = (size_t)std::max(1, S_->n);
+  // (a failure here leaves the batch, solve_batch and the single factorization usable)
+  hipError_t e = ensure_order();
+  size_t want = 0;
+  for (int rb = 32; e == hipSuccess && rb >= 16; rb /= 2) {
+    want = sizeof(double) * (size_t)nbatch * (size_t)rb * n1;
+    e = fmult_take((void**)&d_bsmW_, want);
+    bsm_rb_ = rb;
+    if (e == hipSuccess) break;
+    (void)hipGetLastError();
+    d_bsmW_ = nullptr;
+    if (rb > 16 && alloc_code(e) == -1) e = hipSuccess;   // (out of memory: once more with half of it)
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    feature_err_ = "solve_many_batch: not enough device memory for the workspace of 16 right-hand sides for each of " +
+                   std::to_string(nbatch) + " members (" + std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  bsm_capacity_ = nbatch;
+  bsm_ready_ = true;
+  bsm_info_[0] = bsm_rb_;
+  bsm_info_[3] = (int64_t)want;
+  return 0;
+}
+
+int Engine::release_solve_many_batch() {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (!bsm_ready_) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "solve_many_batch release")) return rc;
+  drop_solve_many_batch();
+  return 0;
+}
+
+// one block of nv <= rb vectors of every member (member b's at x_dev + b * xstride): pack, the sweeps `job` asks
+// for in the order of solve_batch, unpack (enqueue only)
+int Engine::enqueue_solve_many_batch_block(double* x_dev, int64_t xstride, int64_t ldx, int nv, int rb, int job,
+                                           bool pivot_order) {
+  const int n = S_->n;
+  const int* order = pivot_order ? nullptr : d_order_;
+  const BatchView v = batch_view();
+  int nl = 0;
+  bool fits = true;
+  auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
+  count(launch_batch_solve_many_pack(stream_, v, false, x_dev, xstride, ldx, order, n, nv, rb, d_bsmW_));
+  if (!fits) return -1;   // (nothing was launched: the vectors are as they were)
+  auto run = [&](const std::vector<SolveLaunch>& ls) {
+    for (const SolveLaunch& l : ls)
+      count(launch_batch_solve_many(stream_, v, l, bt_.slist, bt_.stiles, bt_.sunits, d_rlist_, d_bsmW_, rb, n));
+  };
+  if (job == 0 || job == 1) run(bt_.sprog.fwd);
+  if (job == 0 || job == 2) run(bt_.sprog.bwd);
+  count(launch_batch_solve_many_pack(stream_, v, true, x_dev, xstride, ldx, order, n, nv, rb, d_bsmW_));
+  return fits ? nl : -1;
+}
+
+int Engine::solve_many_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n, nbatch = bt_.nbatch;
+  if (!x || nrhs < 0 || ldx < n || job < 0 || job > 2 || nbatch <= 0) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_) return -10;          // (the caller waits first)
+  if (nrhs == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = prepare_solve_many_batch();
+  if (rc) return rc;
+  if (!on_device &&
+      (rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)std::min(nrhs, 32) * (size_t)n,
+                              "the staged right-hand sides")))
+    return rc;
+  int64_t blocks = 0, launches = 0;
+  bool fits = true;
+  for (int done = 0; done < nrhs && fits;) {
+    const int left = nrhs - done;
+    const int rb = left > 16 && bsm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
+    int k;
+    if (on_device) {
+      k = enqueue_solve_many_batch_block(x + (int64_t)done * ldx, (int64_t)nrhs * ldx, ldx, nv, rb, job, pivot_order);
+    } else {
+      // the block of every member through the staging buffer, packed (a failed member's vectors make the round trip
+      // unchanged: nothing on the device touches them)
+      for (int b = 0; b < nbatch; ++b)
+        if ((rc = copy_vectors(true, bt_.stage + (int64_t)b * nv * n, x + ((int64_t)b * nrhs + done) * ldx, ldx, nv,
+                               "batch rhs H2D")))
+          return rc;
+      k = enqueue_solve_many_batch_block(bt_.stage, (int64_t)nv * n, n, nv, rb, job, false);
+      HIPCHK(hipGetLastError(), "solve_many_batch launch");
+      if (k >= 0) {
+        for (int b = 0; b < nbatch; ++b)
+          if ((rc = copy_vectors(false, bt_.stage + (int64_t)b * nv * n, x + ((int64_t)b * nrhs + done) * ldx, ldx, nv,
+                                 "batch x D2H")))
+            return rc;
+      }
+      if ((rc = sync_stream(stream_, "solve_many_batch sync"))) return rc;
+    }
+    if (k < 0) fits = false;
+    else launches += k;
+    ++blocks;
+    done += nv;
+  }
+  HIPCHK(hipGetLastError(), "solve_many_batch launch");
+  if ((rc = sync_stream(stream_, "solve_many_batch sync"))) return rc;
+  if (!fits) {
+    feature_err_ = "solve_many_batch: a launch has more work items for one member than a grid holds (the vectors are not "
+                   "all solved)";
+    return -99;
+  }
+  bsm_info_[1] = blocks;
+  bsm_info_[2] = launches;
   return batch_failed();
 }
 

@@ -192,6 +192,15 @@ int launch_batch_solve(hipStream_t st, const BatchView& v, int kind, const int* 
                        int n);
 // out[b] = 2 sum_j log L_b[diag_pos[j]] in a fixed order; NaN for a member whose flag is set
 int launch_batch_log_det(hipStream_t st, const BatchView& v, const int64_t* diag_pos, int n, double* out);
+// ---- blocked solve for the members of a batch (batch_solve_many.hip): the kernels of solve_many.hip per member ----
+// Member b's workspace: W + b * rb * n, W_b[p * rb + q] (rb = 16 or 32); arena, dinv scratch and flag as above.
+// W_b[p(i) * rb + q] = q < nv ? x[b * xstride + q * ldx + i] : 0 (unpack: the other way, q < nv only); a member
+// whose flag is set is skipped
+int launch_batch_solve_many_pack(hipStream_t st, const BatchView& v, bool unpack, double* x, int64_t xstride, int64_t ldx,
+                                 const int* order, int n, int nv, int rb, double* W);
+// one launch l of a SolveProgram built with pw = cb = 64 (list / tiles / units: its tables) for all members
+int launch_batch_solve_many(hipStream_t st, const BatchView& v, const SolveLaunch& l, const int* list,
+                            const UpdTile* tiles, const SolveUnit* units, const int* rlist, double* W, int rb, int n);
 // the limit in force (set_batch_grid_limit) and the hardware limit, for the other batched translation units
 int64_t batch_grid_limit();
 int64_t batch_grid_limit_max();

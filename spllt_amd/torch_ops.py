@@ -40,7 +40,10 @@ class SparseCholesky:
     A_or_pattern: a scipy sparse symmetric matrix (its lower triangle gives the pattern and the order of ``val``) or
     the triple (n, ptr, row) of a 1-based CSC lower triangle.  reproducible=True: the deterministic engine (flag
     4096) and the reproducible solve -- forward and backward of ``solve`` and ``logdet`` are then bit-reproducible
-    across calls; the batch has no deterministic form and raises NotImplementedError.
+    across calls; the batch has no deterministic form and raises NotImplementedError.  batch_blocked=True: the
+    forward and the backward of ``solve_batch`` and the precision kind of ``sample_batch`` run through the blocked
+    matrix-core batch solve (Factorization.solve_many_batch_dev) instead of solve_batch_dev -- the same numbers to
+    rounding, the path for many right-hand sides per member; off by default.
 
     One factorization serves every operation on the same values: the object remembers the tensor it factorized last
     (a weak reference and its ``_version``) and the library's factor serial, and factorizes again only when one of
@@ -48,12 +51,13 @@ class SparseCholesky:
     autograd's own check of saved tensors does not see it: pass a fresh tensor or call ``invalidate()`` then.
     """
 
-    def __init__(self, A_or_pattern, nb=256, reproducible=False, **analyse_kw):
+    def __init__(self, A_or_pattern, nb=256, reproducible=False, batch_blocked=False, **analyse_kw):
         if isinstance(A_or_pattern, (tuple, list)):
             n, ptr, row = A_or_pattern
         else:
             n, ptr, row, _ = csc_lower_1based(A_or_pattern)
         self.reproducible = bool(reproducible)
+        self.batch_blocked = bool(batch_blocked)
         flags = int(analyse_kw.pop("engine_flags", 0)) | (4096 if self.reproducible else 0)
         self.f = Factorization(n, ptr, row, nb=nb, engine_flags=flags, **analyse_kw)
         self.n, self.nnz = self.f.n, self.f.nnz
@@ -169,7 +173,10 @@ class SparseCholesky:
         """work: (nbatch, nrhs, n) contiguous, overwritten"""
         self._sync()
         with torch.cuda.device(self.device):
-            self.f.solve_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n)
+            if self.batch_blocked:
+                self.f.solve_many_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n)
+            else:
+                self.f.solve_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n)
         return work
 
     def _outer(self, ut, vt, alpha):
@@ -299,9 +306,13 @@ class SparseCholesky:
             m = None if mean is None else mean.detach().contiguous()
             self._sync()
             with torch.cuda.device(self.device):
-                self.f.sample_batch_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed, kind=kind,
-                                        mean_dev_ptr=None if m is None else m.data_ptr(), ldmean=ldmean,
-                                        common_noise=common_noise)
+                before = self.f.set_batch_blocked_solve(self.batch_blocked)
+                try:
+                    self.f.sample_batch_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed, kind=kind,
+                                            mean_dev_ptr=None if m is None else m.data_ptr(), ldmean=ldmean,
+                                            common_noise=common_noise)
+                finally:
+                    self.f.set_batch_blocked_solve(before)
         return work.transpose(1, 2)
 
     # ---- operations with the factor in the graph ------------------------------------------------------
