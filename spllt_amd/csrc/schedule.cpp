@@ -114,16 +114,16 @@ struct Builder {
     // longest tiles first: the K extent of a tile is its unit's source width, and a
     // launch mixes units of very different K (inter-node updates), so dispatching
     // the heavy tiles first shortens the tail of the launch
+    const int ubase = (int)P.units.size() - (int)us.size();
+    std::vector<int64_t> work(us.size());
+    for (size_t i = 0; i < us.size(); ++i) {
+      const UpdUnit& u = us[i];
+      int64_t k = 0;
+      if (u.nseg == 1) k = u.klen >= 0 ? u.klen : S.bcols[u.src_bcol0].width;
+      else for (int sg = 0; sg < u.nseg; ++sg) k += S.bcols[u.src_bcol0 + sg].width;
+      work[i] = k;
+    }
     {
-      const int ubase = (int)P.units.size() - (int)us.size();
-      std::vector<int64_t> work(us.size());
-      for (size_t i = 0; i < us.size(); ++i) {
-        const UpdUnit& u = us[i];
-        int64_t k = 0;
-        if (u.nseg == 1) k = u.klen >= 0 ? u.klen : S.bcols[u.src_bcol0].width;
-        else for (int sg = 0; sg < u.nseg; ++sg) k += S.bcols[u.src_bcol0 + sg].width;
-        work[i] = k;
-      }
       auto by_work = [&](const UpdTile& a, const UpdTile& b) { return work[a.unit - ubase] > work[b.unit - ubase]; };
       std::stable_sort(t128.begin(), t128.end(), by_work);
       std::stable_sort(t64.begin(), t64.end(), by_work);
@@ -141,10 +141,16 @@ struct Builder {
     // launch order interleaves the eight sequences -- so the workgroups resident on an XCD form
     // a compact 2-D block of ONE unit that walks K together: its A strips are shared by all
     // tile columns, its B strips by all its rows.
-    static const int64_t xcd_order_env = env_int("SPLLT_XCD_ORDER", 1);
+    // SPLLT_XCD_ORDER, read per program: 0 = the plain order, 1 = the bands below for the 128- and
+    // 64-tile launches of many rounds only, 2 (the default; the batch program keeps 1) = those, and
+    // every other update launch in the launch-sized shares of xcd_share_order further down
+    const int64_t xcd_mode = env_int("SPLLT_XCD_ORDER", opt.env_switches ? 2 : 1);
+    // workgroups of a launch resident on one XCD (32 CUs): the 32-tile kernel (k_update<32, 32, 2, 2>)
+    // has 4 waves of 56 registers and 17.5 KB of LDS per workgroup, so the 8 waves per SIMD bound it:
+    // 8 workgroups per CU, 256 per XCD (the 128- and 64-tile figures are those of round 3)
+    auto xcd_resident = [](int T) -> size_t { return T == 128 ? 64 : (T == 64 ? 160 : 256); };
     auto xcd_order = [&](std::vector<UpdTile>& tv, int T) {
-      const size_t cap = T == 128 ? 64 : (T == 64 ? 160 : 256);
-      if (!xcd_order_env || tv.size() < 8 * cap) return;
+      const size_t cap = xcd_resident(T);
       std::vector<std::vector<UpdTile>> seq(8);
       size_t band = 0, i = 0;
       while (i < tv.size()) {
@@ -186,8 +192,77 @@ struct Builder {
       }
       tv.swap(out);
     };
-    xcd_order(t128, 128);
-    xcd_order(t64, 64);
+    // XCD-aware order of every other update launch: the chain-stream launches (in-panel, c -> c+1)
+    // and the small zones have one to three rounds of tiles, so the share of an XCD follows the
+    // LAUNCH, not the residency: position p runs on XCD p % 8, XCD r owns the n / 8 positions
+    // congruent to r.  The tiles of a unit are put tile row by tile row and cut into bands of whole
+    // tile rows, about n / 8 tiles each (a longer tile row: in pieces; a smaller unit: one band, so
+    // the many small units of a level's in-panel updates stay whole).  The bands go, heaviest
+    // first, to the XCD with the least sum of K so far that still has positions left; a band that
+    // does not fit its XCD's positions continues on the next one (this is also how a launch of
+    // fewer than 8 tiles, or of a tile count that is no multiple of 8, comes out as a permutation).
+    // Every XCD's sequence is filled exactly, so tiles at positions congruent modulo 8 are the
+    // sequence of ONE XCD: an A strip is fetched by the one or two XCDs that hold its tile row, not
+    // by all eight.  Units of different K in one launch can leave the XCDs uneven in work (the
+    // sum of K: equal tile counts are not equal work); then the bands are halved, twice at most.
+    auto xcd_share_order = [&](std::vector<UpdTile>& tv) {
+      const size_t n = tv.size();
+      if (n < 2) return;
+      for (size_t i = 0; i < n;) {
+        size_t j = i;
+        while (j < n && tv[j].unit == tv[i].unit) ++j;
+        std::sort(tv.begin() + (long)i, tv.begin() + (long)j, [](const UpdTile& a, const UpdTile& b) {
+          return a.ti != b.ti ? a.ti < b.ti : a.tj < b.tj;
+        });
+        i = j;
+      }
+      size_t room[8];
+      for (size_t r = 0; r < 8; ++r) room[r] = n / 8 + (r < n % 8 ? 1 : 0);
+      std::vector<UpdTile> seq[8];
+      for (size_t m = 1; m <= 4; m *= 2) {
+        const size_t g = std::max<size_t>(1, (n + 8 * m - 1) / (8 * m));   // tiles per band
+        int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (auto& q : seq) q.clear();
+        auto deal = [&](size_t b, size_t e) {                               // the band tv[b, e)
+          const int64_t k = work[(size_t)(tv[b].unit - ubase)];
+          while (b < e) {
+            int r = -1;
+            for (int q = 0; q < 8; ++q) {
+              if (seq[q].size() >= room[q]) continue;
+              if (r < 0 || load[q] < load[r] || (load[q] == load[r] && seq[q].size() < seq[r].size())) r = q;
+            }
+            const size_t c = std::min(e - b, room[r] - seq[r].size());
+            seq[r].insert(seq[r].end(), tv.begin() + (long)b, tv.begin() + (long)(b + c));
+            load[r] += k * (int64_t)c;
+            b += c;
+          }
+        };
+        size_t b = 0;                                                       // first tile of the open band
+        for (size_t i = 0; i < n;) {
+          size_t j = i;                                                     // one tile row: tv[i, j)
+          while (j < n && tv[j].unit == tv[i].unit && tv[j].ti == tv[i].ti) ++j;
+          if (b < i && (tv[b].unit != tv[i].unit || j - b > g)) { deal(b, i); b = i; }
+          while (j - b > g) { deal(b, b + g); b += g; }
+          i = j;
+        }
+        if (b < n) deal(b, n);
+        int64_t most = 0, sum = 0;
+        for (int q = 0; q < 8; ++q) { most = std::max(most, load[q]); sum += load[q]; }
+        if (n < 64 || 8.0 * (double)most <= 1.03 * (double)sum) break;      // within 3 % of the mean
+      }
+      for (size_t p = 0; p < n; ++p) tv[p] = seq[p % 8][p / 8];
+    };
+    // (a launch is either all TRSM units, a step of the panel chain -- one tile column per unit,
+    // every tile its own A rows: nothing to share -- or has none)
+    const bool share_order = xcd_mode >= 2 && us.front().mode != MODE_TRSM;
+    auto order_tiles = [&](std::vector<UpdTile>& tv, int T) {
+      if (!xcd_mode) return;
+      if (T != 32 && tv.size() >= 8 * xcd_resident(T)) xcd_order(tv, T);   // many rounds: bands of the residency
+      else if (share_order) xcd_share_order(tv);
+    };
+    order_tiles(t128, 128);
+    order_tiles(t64, 64);
+    order_tiles(t32, 32);
     // useful flops of ONE tile of a unit, the convention of the whole program (and of the
     // reference's symbolic count): 2 K per entry the tile really computes for the destination
     // (entries above the diagonal of a unit that straddles it do not count); TRSM: the
