@@ -32,17 +32,6 @@
 
 namespace spx {
 
-// workgroup -> (member, work item); v.nbatch: the members of this launch
-__device__ __forceinline__ void bm_split(const BmultView& v, int& b, unsigned& t) {
-  if (v.member_fast) {
-    b = (int)(blockIdx.x % (unsigned)v.nbatch);
-    t = blockIdx.x / (unsigned)v.nbatch;
-  } else {
-    b = (int)blockIdx.y;
-    t = blockIdx.x;
-  }
-}
-
 template <bool T, int RB>
 __global__ __launch_bounds__(256) void k_bm_strip(const BmultView v, const UpdTile* __restrict__ tiles,
                                                   const SolveUnit* __restrict__ units, const int* __restrict__ rlist,
@@ -50,7 +39,7 @@ __global__ __launch_bounds__(256) void k_bm_strip(const BmultView v, const UpdTi
   __shared__ double Xs[T ? kSolveStripRows : 1][RB + SM_PAD];
   int b;
   unsigned t;
-  bm_split(v, b, t);
+  sm_member_split(v.member_fast, v.nbatch, b, t);
   if (v.flag[b] != INT_MAX) return;   // (before any barrier)
   fv.scratch += (int64_t)b * v.sstride;
   const UpdTile tl = tiles[t];
@@ -64,7 +53,7 @@ __global__ __launch_bounds__(256) void k_bm_diag(const BmultView v, const UpdTil
   __shared__ double Ts[T ? 1 : 64][RB + SM_PAD];
   int b;
   unsigned t;
-  bm_split(v, b, t);
+  sm_member_split(v.member_fast, v.nbatch, b, t);
   if (v.flag[b] != INT_MAX) return;
   fv.scratch += (int64_t)b * v.sstride;
   const UpdTile ch = chunks[t];
@@ -72,39 +61,15 @@ __global__ __launch_bounds__(256) void k_bm_diag(const BmultView v, const UpdTil
                       Y + (int64_t)b * v.wstride, fv, Ts);
 }
 
-// k_sm_pack of solve_many.hip for member blockIdx.y: 64 rows per workgroup, transposed through LDS; a short
-// block is zero-filled in W only
+// k_sm_pack of solve_many.hip for member blockIdx.y (sm_pack_body): 64 rows per workgroup
 template <int RB, bool UNPACK>
 __global__ __launch_bounds__(256) void k_bm_pack(const BmultView v, double* __restrict__ x, int64_t xstride, int64_t ldx,
                                                  const int* __restrict__ order, int n, int nv, double* __restrict__ W) {
   __shared__ double tile[64][RB + 1];
   const int b = blockIdx.y;
-  if (v.flag[b] != INT_MAX) return;
-  x += (int64_t)b * xstride;
-  W += (int64_t)b * v.wstride;
-  const int tid = threadIdx.x;
-  const int i0 = blockIdx.x * 64;
-  if (!UNPACK) {
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int ii = e & 63, q = e >> 6, i = i0 + ii;
-      tile[ii][q] = (i < n && q < nv) ? x[(int64_t)q * ldx + i] : 0.0;
-    }
-    __syncthreads();
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int q = e % RB, ii = e / RB, i = i0 + ii;
-      if (i < n) W[(int64_t)(order ? order[i] : i) * RB + q] = tile[ii][q];
-    }
-  } else {
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int q = e % RB, ii = e / RB, i = i0 + ii;
-      if (i < n) tile[ii][q] = W[(int64_t)(order ? order[i] : i) * RB + q];
-    }
-    __syncthreads();
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int ii = e & 63, q = e >> 6, i = i0 + ii;
-      if (i < n && q < nv) x[(int64_t)q * ldx + i] = tile[ii][q];
-    }
-  }
+  if (v.flag[b] != INT_MAX) return;   // (before any barrier)
+  sm_pack_body<RB, UNPACK>((int)blockIdx.x * 64, x + (int64_t)b * xstride, ldx, order, n, nv,
+                           W + (int64_t)b * v.wstride, tile);
 }
 
 // grid: (positions / 256, samples, members).  member0: the first member of this launch in the batch.

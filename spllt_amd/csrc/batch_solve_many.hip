@@ -30,17 +30,6 @@
 
 namespace spx {
 
-// workgroup -> (member, work item); v.nbatch: the members of this launch
-__device__ __forceinline__ void bsm_split(const BatchView& v, int& b, unsigned& t) {
-  if (v.member_fast) {
-    b = (int)(blockIdx.x % (unsigned)v.nbatch);
-    t = blockIdx.x / (unsigned)v.nbatch;
-  } else {
-    b = (int)blockIdx.y;
-    t = blockIdx.x;
-  }
-}
-
 // 64 rows of one member per workgroup (member blockIdx.y)
 template <int RB, bool UNPACK>
 __global__ __launch_bounds__(256) void k_bsm_pack(const BatchView v, double* __restrict__ x, int64_t xstride, int64_t ldx,
@@ -58,7 +47,7 @@ __global__ __launch_bounds__(256) void k_bsm_diag(const BatchView v, const int* 
   __shared__ double T[64][RB + SM_PAD];
   int b;
   unsigned t;
-  bsm_split(v, b, t);
+  sm_member_split(v.member_fast, v.nbatch, b, t);
   if (v.flag[b] != INT_MAX) return;
   sm_diag_body<BWD, RB>(units[list[t]], v.L + (int64_t)b * v.lstride, v.dinv + (int64_t)b * v.dstride,
                         W + (int64_t)b * RB * n, T);
@@ -70,7 +59,7 @@ __global__ __launch_bounds__(256) void k_bsm_strip_fwd(const BatchView v, const 
                                                        const int* __restrict__ rlist, double* W, int n) {
   int b;
   unsigned t;
-  bsm_split(v, b, t);
+  sm_member_split(v.member_fast, v.nbatch, b, t);
   if (v.flag[b] != INT_MAX) return;
   const UpdTile tl = tiles[t];
   sm_strip_fwd_body<RB>((int)tl.ti, units[tl.unit], v.L + (int64_t)b * v.lstride, rlist, W + (int64_t)b * RB * n);
@@ -83,7 +72,7 @@ __global__ __launch_bounds__(256) void k_bsm_strip_bwd(const BatchView v, const 
   __shared__ double X[kSolveStripRows][RB + SM_PAD];
   int b;
   unsigned t;
-  bsm_split(v, b, t);
+  sm_member_split(v.member_fast, v.nbatch, b, t);
   if (v.flag[b] != INT_MAX) return;
   const UpdTile tl = tiles[t];
   sm_strip_bwd_body<RB>((int)tl.ti, units[tl.unit], v.L + (int64_t)b * v.lstride, rlist, W + (int64_t)b * RB * n, X);

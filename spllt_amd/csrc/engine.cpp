@@ -2123,9 +2123,7 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   bt_.launches = nl;
   bt_.nbatch = nbatch;
   bt_.hflag = bt_.hflag_pending;
-  for (int fl : bt_.hflag)
-    if (fl != INT_MAX) return kErrNotPosDef;
-  return 0;
+  return batch_failed();
 }
 
 int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order) {
@@ -2173,9 +2171,7 @@ int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int jo
     feature_err_ = "batch solve: a launch has more work items for one member than a grid holds (the vectors are not solved)";
     return -99;
   }
-  for (int fl : bt_.hflag)
-    if (fl != INT_MAX) return kErrNotPosDef;
-  return 0;
+  return batch_failed();
 }
 
 int Engine::download_batch(int member, double* out, int64_t count) {

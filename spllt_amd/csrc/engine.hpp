@@ -7,6 +7,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -482,6 +483,38 @@ class Engine {
     return copy_vectors(true, dev, const_cast<double*>(host), ldx, nv, what, len);
   }
   std::string feature_err_;
+  // What a vector entry point does before it touches the device: feature_err_ cleared, then status_, the
+  // arguments (-10), a partitioned handle (-98), pending_ (-10), an empty call (0), hipSetDevice.  False: the
+  // caller returns *rc.
+  bool enter(bool args_ok, bool empty, int* rc);
+  // ... and a release_*: status_, nothing held (0), hipSetDevice, the stream idle (`what` names the wait)
+  bool enter_release(bool held, const char* what, int* rc);
+  // The walk of a blocked feature over the vectors of a call (engine_detail.hpp, for_each_block), on the device
+  // or through a staging buffer.  x: vector q of member b at x + (b * total + q) * ldx; members = 1: one arena.
+  struct BlockWalk {
+    const char* label;        // of the feature, for the texts of a HIP failure
+    double* x;
+    bool on_device;
+    int total;                // vectors per member
+    int64_t ldx;
+    int members;
+    double* stage;            // host x: members * min(total, 32) * n doubles on the device
+    int cap;                  // widest block (32 or 16)
+    bool pivot_order = false; // of device vectors (staged ones are in user order)
+    bool upload = true;       // false: the block is produced on the device (the samplers)
+  };
+  struct BlockTally { int64_t blocks = 0, launches = 0; };
+  // enqueue(done, xdev, xstride, ld, nv, rb, pivot_order) -> launches made, or a negative code that ends the walk.
+  // Device x: every block enqueued on x itself, ONE launch check and ONE sync behind the walk.  Host x, per block
+  // (the staging buffer is reused): H2D per member, enqueue on the packed block (member b at stage + b * nv * n,
+  // ld = n), launch check, D2H per member unless enqueue refused, sync.  Returns 0, what enqueue refused with
+  // (once the stream is idle), or kErrHip.
+  template <class Enq> int walk_blocks(const BlockWalk& w, Enq&& enqueue, BlockTally* tally = nullptr);
+  // Blocks of 32 vectors, and when that does not fit, blocks of 16: every buffer of the list through fmult_take,
+  // in order, at *rb = 32; at the first failure what was taken goes back, every pointer is null, and "out of
+  // memory" (alone) tries *rb = 16 once.  *want: the bytes of the last width tried.
+  struct BlockBuffer { void** p; size_t bytes; };   // bytes per vector of a block
+  hipError_t take_block_buffers(std::initializer_list<BlockBuffer> bufs, int* rb, size_t* want);
   // reproducible solve (tables and scratch taken on first use, all or nothing)
   int enqueue_solve_repro(double* y, int64_t ldy, int cur, int job);
   bool repro_on_ = false;
@@ -505,6 +538,7 @@ class Engine {
   void drop_fmult_tables();
   hipError_t fmult_take(void** p, size_t bytes);   // dalloc, unless the debug hook "fmult_alloc_fail" says no
   int prepare_factor_mult(bool host_stage);
+  int run_factor_mult(double* x, bool on_device, int nvec, int64_t ldx, int job, bool pivot_order);   // both entry points
   void enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
   bool fm_ready_ = false;
   int fm_rb_ = 32;                 // widest block the workspace and the scratch hold (32, or 16 when memory is short)
@@ -516,6 +550,7 @@ class Engine {
   double* d_fmmean_ = nullptr;     // n doubles: the mean of a host entry point
   // batched factor products: workspaces and scratch for bm_capacity_ members
   int prepare_factor_mult_batch();
+  int run_factor_mult_batch(double* x, bool on_device, int nvec, int64_t ldx, int job, bool pivot_order);   // both entry points
   void drop_factor_mult_batch();
   BmultView bmult_view(int rb) const;
   void enqueue_factor_mult_batch_block(double* x_dev, int64_t xstride, int64_t ldx, int nv, int rb, int job,
@@ -542,6 +577,7 @@ class Engine {
   int64_t bsm_info_[4] = {0, 0, 0, 0};
   // blocked solve (workspace allocated on first use, kept with the engine)
   int prepare_solve_many(bool host_stage);
+  int run_solve_many(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order);   // both entry points
   void enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
   double* d_smW_ = nullptr;        // n * 32 doubles: W[p * rb + q]
   double* d_smstage_ = nullptr;    // n * 32 doubles: a block of host vectors in the caller's order (solve_many)

@@ -1,5 +1,6 @@
 // What the translation units of the Engine share (engine.cpp, engine_solve.cpp): the error-check macros of
-// its member functions, the one-allocation table upload, the error code of a failed allocation, RCCL.
+// its member functions, the one-allocation table upload, the error code of a failed allocation, the two rules
+// by which a call's vectors are cut into launch sets, RCCL.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -21,6 +22,32 @@ constexpr int kErrHip = -30, kErrNotPosDef = -20;
 
 // what a feature returns when taking its device memory failed: -1 (no memory) or -30 (the runtime)
 inline int alloc_code(hipError_t e) { return e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? -1 : kErrHip; }
+
+// The vectors of a call for the blocked kernels (blocks of rb = 16 or 32; cap: the widest block the feature's
+// storage holds): blocks of 32 while more than 16 are left, the tail as ONE zero-padded block of 16 or 32.
+// f(done, nv, rb) per block of nv <= rb vectors; the walk stops at the first non-zero return of f and returns it.
+template <class F>
+int for_each_block(int total, int cap, F&& f) {
+  for (int done = 0; done < total;) {
+    const int left = total - done;
+    const int rb = (left > 16 && cap == 32) ? 32 : 16, nv = std::min(left, rb);
+    if (int rc = f(done, nv, rb)) return rc;
+    done += nv;
+  }
+  return 0;
+}
+
+// The same for the kernels that take 4, 2 or 1 vectors per sweep: f(done, cur).
+template <class F>
+int for_each_group4(int total, F&& f) {
+  for (int done = 0; done < total;) {
+    const int left = total - done;
+    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+    if (int rc = f(done, cur)) return rc;
+    done += cur;
+  }
+  return 0;
+}
 
 // Tables of an engine go to the device as ONE allocation and ONE copy: the parts are laid out in
 // a host staging buffer (256-byte aligned), the typed device pointers are set after the upload.

@@ -1,6 +1,9 @@
 // The solve family of the Engine: the substitution program on the device (solve, solve_dev), the blocked solve
-// for many right-hand sides, the reproducible solve and the refined solves.  They share one walk over the
-// program's launches, one table view, one order table and one staging helper.
+// for many right-hand sides, the reproducible solve, the factor products and samplers, their batched forms and
+// the refined solves.  They share one walk over the program's launches, one table view, one order table and one
+// staging helper; the vector entry points share one preamble (enter), the blocked features one walk over the
+// blocks of a call (walk_blocks, around each feature's enqueue_*_block) and one width fallback for their
+// storage (take_block_buffers).  The block rules themselves are in engine_detail.hpp.
 #include <atomic>
 #include <chrono>
 #include <climits>
@@ -112,6 +115,79 @@ void Engine::for_each_solve_launch(int job, int phase, F&& f) const {
   if (do_bwd && (phase == -1 || phase == 2)) run(sprog_.bwd, sv_bwd_, sprog_.bwd_ntop, sprog_.bwd.size());
 }
 
+bool Engine::enter(bool args_ok, bool empty, int* rc) {
+  feature_err_.clear();
+  // (-98: a rank of a partition holds a part of L only; pending_: the caller waits first)
+  *rc = status_ ? status_ : !args_ok ? -10 : opt_.nranks > 1 ? -98 : pending_ ? -10 : 0;
+  if (*rc || empty) return false;
+  const hipError_t e = hipSetDevice(device_);
+  if (e != hipSuccess) *rc = fail(kErrHip, "hipSetDevice", e);
+  return e == hipSuccess;
+}
+
+bool Engine::enter_release(bool held, const char* what, int* rc) {
+  feature_err_.clear();
+  *rc = status_;
+  if (*rc || !held) return false;
+  const hipError_t e = hipSetDevice(device_);
+  *rc = e != hipSuccess ? fail(kErrHip, "hipSetDevice", e) : sync_stream(stream_, what);
+  return *rc == 0;
+}
+
+template <class Enq>
+int Engine::walk_blocks(const BlockWalk& w, Enq&& enqueue, BlockTally* tally) {
+  const int n = S_->n;
+  const std::string label(w.label), launch = label + " launch", sync = label + " sync";
+  // the block at `done` of every member between the caller's host array and the staging buffer (a failed member's
+  // vectors make the round trip unchanged: nothing on the device touches them)
+  auto stage = [&](bool up, int done, int nv) -> int {
+    const std::string what = label + (up ? " H2D" : " D2H");
+    for (int b = 0; b < w.members; ++b)
+      if (int rc = copy_vectors(up, w.stage + (int64_t)b * nv * n, w.x + ((int64_t)b * w.total + done) * w.ldx, w.ldx, nv,
+                                what.c_str()))
+        return rc;
+    return 0;
+  };
+  BlockTally t;
+  const int rc = for_each_block(w.total, w.cap, [&](int done, int nv, int rb) -> int {
+    int r = 0;
+    if (!w.on_device && w.upload && (r = stage(true, done, nv))) return r;
+    const int k = w.on_device ? enqueue(done, w.x + (int64_t)done * w.ldx, (int64_t)w.total * w.ldx, w.ldx, nv, rb, w.pivot_order)
+                              : enqueue(done, w.stage, (int64_t)nv * n, (int64_t)n, nv, rb, false);
+    ++t.blocks;
+    t.launches += std::max(k, 0);
+    if (!w.on_device) {
+      HIPCHK(hipGetLastError(), launch.c_str());
+      if (k >= 0 && (r = stage(false, done, nv))) return r;
+      if ((r = sync_stream(stream_, sync.c_str()))) return r;
+    }
+    return std::min(k, 0);
+  });
+  if (w.on_device) {
+    HIPCHK(hipGetLastError(), launch.c_str());
+    if (int r = sync_stream(stream_, sync.c_str())) return r;
+  }
+  if (tally) *tally = t;
+  return rc;
+}
+
+hipError_t Engine::take_block_buffers(std::initializer_list<BlockBuffer> bufs, int* rb, size_t* want) {
+  for (*rb = 32;; *rb /= 2) {
+    hipError_t e = hipSuccess;
+    *want = 0;
+    for (const BlockBuffer& b : bufs) *want += b.bytes * (size_t)*rb;
+    for (const BlockBuffer& b : bufs)
+      if ((e = fmult_take(b.p, b.bytes * (size_t)*rb)) != hipSuccess) break;
+    if (e == hipSuccess) return e;
+    (void)hipGetLastError();
+    for (const BlockBuffer& b : bufs) {
+      if (*b.p) release_buffer(*b.p);
+      *b.p = nullptr;
+    }
+    if (*rb == 16 || alloc_code(e) != -1) return e;   // (out of memory: once more with half of it)
+  }
+}
+
 // Substitution on device vectors in pivot order (y[q * n + p], q < nrhs), in place.
 // phase -1: everything that `job` asks for; 0/1/2: the three phases of a
 // partitioned solve (schedule.hpp, SolveProgram).
@@ -124,15 +200,13 @@ int Engine::solve_dev(double* y_dev, int nrhs, int job, int phase) {
   if (rc) return rc;
   const int n = S_->n;
   const SolveTablesView tv = solve_tables();
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);   // kernel variants: 4, 2 or 1 per sweep
+  for_each_group4(nrhs, [&](int done, int cur) {
     double* y = y_dev + (int64_t)done * n;
     for_each_solve_launch(job, phase, [&](const SolveLaunch& l, const SolveLaunchInfo& li) {
       launch_solve(stream_, tv, l, li, y, cur, (int64_t)n);
     });
-    done += cur;
-  }
+    return 0;
+  });
   HIPCHK(hipGetLastError(), "solve launch");
   return sync_stream(stream_, "solve sync");
 }
@@ -148,9 +222,7 @@ int Engine::solve(double* x_host, int nrhs, int job) {
   const int n = S.n;
   // up to four right-hand sides per sweep: every entry of L is read once for all of them
   std::vector<double> yh((size_t)n * 4);
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+  return for_each_group4(nrhs, [&](int done, int cur) -> int {
     for (int q = 0; q < cur; ++q) {
       const double* xr = x_host + (int64_t)(done + q) * n;
       double* yq = yh.data() + (size_t)q * n;
@@ -181,9 +253,8 @@ int Engine::solve(double* x_host, int nrhs, int job) {
       const double* yq = yh.data() + (size_t)q * n;
       for (int i = 0; i < n; ++i) xr[i] = yq[S.order[i]];
     }
-    done += cur;
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // ---- blocked solve for many right-hand sides ---------------------------------------------------
@@ -218,51 +289,25 @@ void Engine::enqueue_solve_many_block(double* x_dev, int64_t ldx, int nv, int rb
   launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
 }
 
+// the blocked solve on device vectors, or on host vectors through the staging block (a block goes up in the caller's
+// layout, its n-vectors only: the permutation happens on the device)
+int Engine::run_solve_many(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  int rc;
+  if (!enter(job >= 0 && job <= 2 && nrhs >= 0 && x && ldx >= S_->n, nrhs == 0 || S_->n == 0, &rc)) return rc;
+  if ((rc = prepare_solve_many(!on_device))) return rc;
+  return walk_blocks({"solve_many", x, on_device, nrhs, ldx, 1, d_smstage_, 32, pivot_order},
+                     [&](int, double* xd, int64_t, int64_t ld, int nv, int rb, bool po) {
+                       enqueue_solve_many_block(xd, ld, nv, rb, job, po);
+                       return 0;
+                     });
+}
+
 int Engine::solve_many_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
-  if (pending_) return -10;          // (the caller waits first)
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_many(false);
-  if (rc) return rc;
-  // 32 per sweep while at least 32 are left; the tail as one zero-padded block of 16 or 32
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
-    enqueue_solve_many_block(x_dev + (int64_t)done * ldx, ldx, nv, rb, job, pivot_order);
-    done += nv;
-  }
-  HIPCHK(hipGetLastError(), "solve_many launch");
-  return sync_stream(stream_, "solve_many sync");
+  return run_solve_many(x_dev, true, nrhs, ldx, job, pivot_order);
 }
 
 int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_many(true);
-  if (rc) return rc;
-  const int n = S_->n;
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int rb = left > 16 ? 32 : 16, nv = std::min(left, rb);
-    double* xb = x_host + (int64_t)done * ldx;
-    // the block in the caller's layout, its n-vectors only (the permutation happens on the device)
-    if ((rc = copy_vectors(true, d_smstage_, xb, ldx, nv, "rhs H2D"))) return rc;
-    enqueue_solve_many_block(d_smstage_, n, nv, rb, job, false);
-    HIPCHK(hipGetLastError(), "solve_many launch");
-    if ((rc = copy_vectors(false, d_smstage_, xb, ldx, nv, "x D2H"))) return rc;
-    if ((rc = sync_stream(stream_, "solve_many sync"))) return rc;
-    done += nv;
-  }
-  return 0;
+  return run_solve_many(x_host, false, nrhs, ldx, job, false);
 }
 
 // ---- sparse right-hand sides and selected outputs ----------------------------------------------------
@@ -445,17 +490,14 @@ int Engine::solve_sparse(int k, const int* bptr, const int* brow, const double* 
   const auto host_t0 = std::chrono::steady_clock::now();
   std::vector<SsGroup> groups;
   size_t tab_bytes = 0;
-  for (int done = 0; done < k;) {
-    const int left = k - done;
+  for_each_block(k, 32, [&](int done, int nv, int rb) {
     SsGroup g;
-    g.c0 = done;
-    g.rb = left > 16 ? 32 : 16;
-    g.nv = std::min(left, g.rb);
+    g.c0 = done, g.nv = nv, g.rb = rb;
     ss_plan_group(g, bptr, brow, bval, all ? -1 : nsel, all ? nullptr : sel, job, nullptr);
     tab_bytes = std::max(tab_bytes, g.bytes);
-    done += g.nv;
     groups.push_back(std::move(g));
-  }
+    return 0;
+  });
   ss_host_us_ = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
   const size_t out_bytes = dev ? 0 : sizeof(double) * (size_t)nout * 32;
   hipError_t e = ss_reserve((void**)&d_sstab_, &ss_tab_cap_, tab_bytes);
@@ -503,17 +545,14 @@ int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* b
   build_solve_sparse_plan(*S_, 0, k, bptr, brow, 0, &none, 1, U);
   std::vector<SsGroup> groups;
   size_t tab_bytes = 0;
-  for (int done = 0; done < k;) {
-    const int left = k - done;
+  for_each_block(k, 32, [&](int done, int nv, int rb) {
     SsGroup g;
-    g.c0 = done;
-    g.rb = left > 16 ? 32 : 16;
-    g.nv = std::min(left, g.rb);
+    g.c0 = done, g.nv = nv, g.rb = rb;
     ss_plan_group(g, bptr, brow, bval, 0, &none, 1, &U.range);
     tab_bytes = std::max(tab_bytes, g.bytes);
-    done += g.nv;
     groups.push_back(std::move(g));
-  }
+    return 0;
+  });
   ss_host_us_ = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
   const size_t ng = groups.size(), nchunk = groups[0].chunks.size() / 2;
   const size_t wstride = (size_t)32 * (size_t)n;
@@ -551,11 +590,8 @@ int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* b
 }
 
 int Engine::release_solve_sparse() {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!d_sstab_ && !d_ssout_ && !d_ssgramW_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "solve_sparse release")) return rc;
+  int rc;
+  if (!enter_release(d_sstab_ || d_ssout_ || d_ssgramW_, "solve_sparse release", &rc)) return rc;
   for (void* p : {(void*)d_sstab_, (void*)d_ssout_, (void*)d_ssgramW_})
     if (p) release_buffer(p);
   d_sstab_ = nullptr; d_ssout_ = nullptr; d_ssgramW_ = nullptr;
@@ -616,11 +652,8 @@ int Engine::prepare_solve_repro() {
 }
 
 int Engine::release_solve_repro() {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!rs_ready_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "solve_repro release")) return rc;
+  int rc;
+  if (!enter_release(rs_ready_, "solve_repro release", &rc)) return rc;
   for (void* p : {(void*)d_rsscratch_, (void*)d_rsstage_})
     if (p) release_buffer(p);
   d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
@@ -646,47 +679,29 @@ int Engine::enqueue_solve_repro(double* y, int64_t ldy, int cur, int job) {
 }
 
 int Engine::solve_repro_dev(double* x_dev, int nrhs, int64_t ldx, int job, bool pivot_order) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (job < 0 || job > 2 || nrhs < 0 || !x_dev || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
-  if (pending_) return -10;          // (the caller waits first)
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_repro();
-  if (rc) return rc;
+  int rc;
+  if (!enter(job >= 0 && job <= 2 && nrhs >= 0 && x_dev && ldx >= S_->n, nrhs == 0 || S_->n == 0, &rc)) return rc;
+  if ((rc = prepare_solve_repro())) return rc;
   const int n = S_->n;
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+  rc = for_each_group4(nrhs, [&](int done, int cur) -> int {
     double* xg = x_dev + (int64_t)done * ldx;
-    if (pivot_order) {
-      if ((rc = enqueue_solve_repro(xg, ldx, cur, job))) return rc;
-    } else {
-      launch_permute_vectors(stream_, false, xg, ldx, d_order_, n, cur, d_y_);
-      if ((rc = enqueue_solve_repro(d_y_, (int64_t)n, cur, job))) return rc;
-      launch_permute_vectors(stream_, true, xg, ldx, d_order_, n, cur, d_y_);
-    }
-    done += cur;
-  }
+    if (pivot_order) return enqueue_solve_repro(xg, ldx, cur, job);
+    launch_permute_vectors(stream_, false, xg, ldx, d_order_, n, cur, d_y_);
+    if (int r = enqueue_solve_repro(d_y_, (int64_t)n, cur, job)) return r;
+    launch_permute_vectors(stream_, true, xg, ldx, d_order_, n, cur, d_y_);
+    return 0;
+  });
+  if (rc) return rc;
   HIPCHK(hipGetLastError(), "solve_repro launch");
   return sync_stream(stream_, "solve_repro sync");
 }
 
 int Engine::solve_repro(double* x_host, int nrhs, int64_t ldx, int job) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (job < 0 || job > 2 || nrhs < 0 || !x_host || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nrhs == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_repro();
-  if (rc) return rc;
+  int rc;
+  if (!enter(job >= 0 && job <= 2 && nrhs >= 0 && x_host && ldx >= S_->n, nrhs == 0 || S_->n == 0, &rc)) return rc;
+  if ((rc = prepare_solve_repro())) return rc;
   const int n = S_->n;
-  for (int done = 0; done < nrhs;) {
-    const int left = nrhs - done;
-    const int cur = left >= 4 ? 4 : (left >= 2 ? 2 : 1);
+  return for_each_group4(nrhs, [&](int done, int cur) -> int {
     double* xg = x_host + (int64_t)done * ldx;
     // the group in the caller's layout, its n-vectors only (the permutation happens on the device)
     if ((rc = copy_vectors(true, d_rsstage_, xg, ldx, cur, "rhs H2D"))) return rc;
@@ -695,10 +710,8 @@ int Engine::solve_repro(double* x_host, int nrhs, int64_t ldx, int job) {
     launch_permute_vectors(stream_, true, d_rsstage_, (int64_t)n, d_order_, n, cur, d_y_);
     HIPCHK(hipGetLastError(), "solve_repro launch");
     if ((rc = copy_vectors(false, d_rsstage_, xg, ldx, cur, "x D2H"))) return rc;
-    if ((rc = sync_stream(stream_, "solve_repro sync"))) return rc;
-    done += cur;
-  }
-  return 0;
+    return sync_stream(stream_, "solve_repro sync");
+  });
 }
 
 // ---- products with the factor, Gaussian sampling ---------------------------------------------------
@@ -748,19 +761,10 @@ int Engine::prepare_factor_mult(bool host_stage) {
   // (a failure here leaves the factor and every solve usable: the engine's status is not touched)
   hipError_t e = ensure_fmult_tables();
   size_t want = 0;
-  // blocks of 32 vectors; when that does not fit, blocks of 16 (per vector the same sums in the same order)
-  for (int rb = 32; e == hipSuccess && rb >= 16; rb /= 2) {
-    want = sizeof(double) * (size_t)rb * (n1 + (size_t)rs_stride_);
-    e = fmult_take((void**)&d_fmW_, sizeof(double) * (size_t)rb * n1);
-    if (e == hipSuccess) e = fmult_take((void**)&d_fmscratch_, sizeof(double) * (size_t)rb * (size_t)rs_stride_);
-    fm_rb_ = rb;
-    if (e == hipSuccess) break;
-    (void)hipGetLastError();
-    for (void* p : {(void*)d_fmW_, (void*)d_fmscratch_})
-      if (p) release_buffer(p);
-    d_fmW_ = nullptr; d_fmscratch_ = nullptr;
-    if (rb > 16 && alloc_code(e) == -1) e = hipSuccess;   // (out of memory: once more with half of it)
-  }
+  // (per vector the same sums in the same order at either width)
+  if (e == hipSuccess)
+    e = take_block_buffers({{(void**)&d_fmW_, sizeof(double) * n1}, {(void**)&d_fmscratch_, sizeof(double) * (size_t)rs_stride_}},
+                           &fm_rb_, &want);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     if (!bm_ready_) drop_fmult_tables();
@@ -773,11 +777,8 @@ int Engine::prepare_factor_mult(bool host_stage) {
 }
 
 int Engine::release_factor_mult() {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!fm_ready_ && !d_fmmean_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "factor_mult release")) return rc;
+  int rc;
+  if (!enter_release(fm_ready_ || d_fmmean_, "factor_mult release", &rc)) return rc;
   for (void* p : {(void*)d_fmW_, (void*)d_fmscratch_, (void*)d_fmmean_})
     if (p) release_buffer(p);
   d_fmW_ = nullptr; d_fmscratch_ = nullptr; d_fmmean_ = nullptr;
@@ -807,59 +808,28 @@ void Engine::enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int r
   launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, job == 0 ? d_smW_ : d_fmW_);
 }
 
+int Engine::run_factor_mult(double* x, bool on_device, int nvec, int64_t ldx, int job, bool pivot_order) {
+  int rc;
+  if (!enter(job >= 0 && job <= 2 && nvec >= 0 && x && ldx >= S_->n, nvec == 0 || S_->n == 0, &rc)) return rc;
+  if ((rc = prepare_factor_mult(!on_device))) return rc;
+  return walk_blocks({"factor_mult", x, on_device, nvec, ldx, 1, d_smstage_, fm_rb_, pivot_order},
+                     [&](int, double* xd, int64_t, int64_t ld, int nv, int rb, bool po) {
+                       enqueue_factor_mult_block(xd, ld, nv, rb, job, po);
+                       return 0;
+                     });
+}
+
 int Engine::factor_mult_dev(double* x_dev, int nvec, int64_t ldx, int job, bool pivot_order) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (job < 0 || job > 2 || nvec < 0 || !x_dev || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
-  if (pending_) return -10;          // (the caller waits first)
-  if (nvec == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_factor_mult(false);
-  if (rc) return rc;
-  for (int done = 0; done < nvec;) {
-    const int left = nvec - done;
-    const int rb = left > 16 && fm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
-    enqueue_factor_mult_block(x_dev + (int64_t)done * ldx, ldx, nv, rb, job, pivot_order);
-    done += nv;
-  }
-  HIPCHK(hipGetLastError(), "factor_mult launch");
-  return sync_stream(stream_, "factor_mult sync");
+  return run_factor_mult(x_dev, true, nvec, ldx, job, pivot_order);
 }
 
 int Engine::factor_mult(double* x_host, int nvec, int64_t ldx, int job) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (job < 0 || job > 2 || nvec < 0 || !x_host || ldx < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nvec == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_factor_mult(true);
-  if (rc) return rc;
-  const int n = S_->n;
-  for (int done = 0; done < nvec;) {
-    const int left = nvec - done;
-    const int rb = left > 16 && fm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
-    double* xb = x_host + (int64_t)done * ldx;
-    if ((rc = copy_vectors(true, d_smstage_, xb, ldx, nv, "x H2D"))) return rc;
-    enqueue_factor_mult_block(d_smstage_, n, nv, rb, job, false);
-    HIPCHK(hipGetLastError(), "factor_mult launch");
-    if ((rc = copy_vectors(false, d_smstage_, xb, ldx, nv, "y D2H"))) return rc;
-    if ((rc = sync_stream(stream_, "factor_mult sync"))) return rc;
-    done += nv;
-  }
-  return 0;
+  return run_factor_mult(x_host, false, nvec, ldx, job, false);
 }
 
 int Engine::white_noise_dev(double* z_dev, int nsamp, int64_t ldz, uint64_t seed, uint64_t first) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (nsamp < 0 || !z_dev || ldz < S_->n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nsamp == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc;
+  if (!enter(nsamp >= 0 && z_dev && ldz >= S_->n, nsamp == 0 || S_->n == 0, &rc)) return rc;
   launch_white_noise(stream_, z_dev, ldz, nullptr, S_->n, nsamp, seed, first);
   HIPCHK(hipGetLastError(), "white_noise launch");
   return sync_stream(stream_, "white_noise sync");
@@ -869,15 +839,10 @@ int Engine::white_noise_dev(double* z_dev, int nsamp, int64_t ldz, uint64_t seed
 // positions (x[i] = z[order[i]]): the product and the sweeps then run through their own entry points.
 int Engine::sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, const double* mean,
                    bool dev) {
-  feature_err_.clear();
-  if (status_) return status_;
   const int n = S_->n;
-  if (kind < 0 || kind > 1 || nsamp < 0 || !x || ldx < n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nsamp == 0 || n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = kind == 1 ? prepare_factor_mult(!dev) : (repro_on_ ? prepare_solve_repro() : 0);
+  int rc;
+  if (!enter(kind >= 0 && kind <= 1 && nsamp >= 0 && x && ldx >= n, nsamp == 0 || n == 0, &rc)) return rc;
+  rc = kind == 1 ? prepare_factor_mult(!dev) : (repro_on_ ? prepare_solve_repro() : 0);
   if (!rc) rc = prepare_solve_many(!dev);   // (the order table; the staging block of the host entry point)
   if (rc) return rc;
   const double* dmean = mean;
@@ -910,14 +875,11 @@ int Engine::sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, u
     if ((rc = group(x, ldx, nsamp, first))) return rc;
     return sync_stream(stream_, "sample sync");
   }
-  for (int done = 0; done < nsamp;) {   // the staging block holds 32 vectors
-    const int nv = std::min(32, nsamp - done);
-    if ((rc = group(d_smstage_, (int64_t)n, nv, first + (uint64_t)done))) return rc;
-    if ((rc = copy_vectors(false, d_smstage_, x + (int64_t)done * ldx, ldx, nv, "x D2H"))) return rc;
-    if ((rc = sync_stream(stream_, "sample sync"))) return rc;
-    done += nv;
-  }
-  return 0;
+  // groups of at most 32 (what the staging block holds): min(left, 32) is the block rule's nv at cap 32 for every left
+  return walk_blocks({"sample", x, false, nsamp, ldx, 1, d_smstage_, 32, false, false},
+                     [&](int done, double* xg, int64_t, int64_t ld, int nv, int, bool) {
+                       return group(xg, ld, nv, first + (uint64_t)done);
+                     });
 }
 
 // ---- the products and the samplers for every member of a batch ---------------------------------------
@@ -945,20 +907,9 @@ int Engine::prepare_factor_mult_batch() {
   hipError_t e = ensure_order();
   if (e == hipSuccess) e = ensure_fmult_tables();
   size_t want = 0;
-  for (int rb = 32; e == hipSuccess && rb >= 16; rb /= 2) {
-    const size_t wb = sizeof(double) * (size_t)nbatch * (size_t)rb * n1;
-    const size_t sb = sizeof(double) * (size_t)nbatch * (size_t)rb * (size_t)rs_stride_;
-    want = 2 * wb + sb;
-    e = fmult_take((void**)&d_bmW_[0], wb);
-    if (e == hipSuccess) e = fmult_take((void**)&d_bmW_[1], wb);
-    if (e == hipSuccess) e = fmult_take((void**)&d_bmscratch_, sb);
-    bm_rb_ = rb;
-    if (e == hipSuccess) break;
-    (void)hipGetLastError();
-    for (void* p : {(void*)d_bmW_[0], (void*)d_bmW_[1], (void*)d_bmscratch_})
-      if (p) release_buffer(p);
-    d_bmW_[0] = d_bmW_[1] = d_bmscratch_ = nullptr;
-    if (rb > 16 && alloc_code(e) == -1) e = hipSuccess;   // (out of memory: once more with half of it)
+  if (e == hipSuccess) {
+    const size_t wb = sizeof(double) * (size_t)nbatch * n1, sb = sizeof(double) * (size_t)nbatch * (size_t)rs_stride_;
+    e = take_block_buffers({{(void**)&d_bmW_[0], wb}, {(void**)&d_bmW_[1], wb}, {(void**)&d_bmscratch_, sb}}, &bm_rb_, &want);
   }
   if (e != hipSuccess) {
     (void)hipGetLastError();
@@ -976,11 +927,8 @@ int Engine::prepare_factor_mult_batch() {
 }
 
 int Engine::release_factor_mult_batch() {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!bm_ready_ && !d_bmmean_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "factor_mult_batch release")) return rc;
+  int rc;
+  if (!enter_release(bm_ready_ || d_bmmean_, "factor_mult_batch release", &rc)) return rc;
   drop_factor_mult_batch();
   return 0;
 }
@@ -1019,75 +967,42 @@ void Engine::enqueue_factor_mult_batch_block(double* x_dev, int64_t xstride, int
   launch_batch_mult_pack(stream_, v, true, x_dev, xstride, ldx, order, n, nv, rb, job == 0 ? d_bmW_[0] : d_bmW_[1]);
 }
 
-int Engine::factor_mult_batch_dev(double* x_dev, int nvec, int64_t ldx, int job, bool pivot_order) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!x_dev || nvec < 0 || ldx < S_->n || job < 0 || job > 2 || bt_.nbatch <= 0) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;          // (the caller waits first)
-  if (nvec == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_factor_mult_batch();
-  if (rc) return rc;
-  for (int done = 0; done < nvec;) {
-    const int left = nvec - done;
-    const int rb = left > 16 && bm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
-    enqueue_factor_mult_batch_block(x_dev + (int64_t)done * ldx, (int64_t)nvec * ldx, ldx, nv, rb, job, pivot_order);
-    done += nv;
-  }
-  HIPCHK(hipGetLastError(), "factor_mult_batch launch");
-  if ((rc = sync_stream(stream_, "factor_mult_batch sync"))) return rc;
-  return batch_failed();
-}
-
-// groups of at most 32 vectors per member through the batch's staging buffer
-int Engine::factor_mult_batch(double* x_host, int nvec, int64_t ldx, int job) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!x_host || nvec < 0 || ldx < S_->n || job < 0 || job > 2 || bt_.nbatch <= 0) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nvec == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_factor_mult_batch();
-  if (rc) return rc;
+// device vectors, or groups of at most 32 host vectors per member through the batch's staging buffer
+int Engine::run_factor_mult_batch(double* x, bool on_device, int nvec, int64_t ldx, int job, bool pivot_order) {
   const int n = S_->n, nbatch = bt_.nbatch;
-  if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)std::min(nvec, 32) * (size_t)n,
+  int rc;
+  if (!enter(x && nvec >= 0 && ldx >= n && job >= 0 && job <= 2 && nbatch > 0, nvec == 0 || n == 0, &rc)) return rc;
+  if ((rc = prepare_factor_mult_batch())) return rc;
+  if (!on_device &&
+      (rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)std::min(nvec, 32) * (size_t)n,
                               "the staged vectors")))
     return rc;
-  for (int done = 0; done < nvec;) {
-    const int left = nvec - done;
-    const int rb = left > 16 && bm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
-    // (a failed member's vectors make the round trip unchanged: nothing on the device touches them)
-    for (int b = 0; b < nbatch; ++b)
-      if ((rc = copy_vectors(true, bt_.stage + (int64_t)b * nv * n, x_host + ((int64_t)b * nvec + done) * ldx, ldx, nv,
-                             "batch x H2D")))
-        return rc;
-    enqueue_factor_mult_batch_block(bt_.stage, (int64_t)nv * n, n, nv, rb, job, false);
-    HIPCHK(hipGetLastError(), "factor_mult_batch launch");
-    for (int b = 0; b < nbatch; ++b)
-      if ((rc = copy_vectors(false, bt_.stage + (int64_t)b * nv * n, x_host + ((int64_t)b * nvec + done) * ldx, ldx, nv,
-                             "batch y D2H")))
-        return rc;
-    if ((rc = sync_stream(stream_, "factor_mult_batch sync"))) return rc;
-    done += nv;
-  }
-  return batch_failed();
+  rc = walk_blocks({"factor_mult_batch", x, on_device, nvec, ldx, nbatch, bt_.stage, bm_rb_, pivot_order},
+                   [&](int, double* xd, int64_t xs, int64_t ld, int nv, int rb, bool po) {
+                     enqueue_factor_mult_batch_block(xd, xs, ld, nv, rb, job, po);
+                     return 0;
+                   });
+  return rc ? rc : batch_failed();
+}
+
+int Engine::factor_mult_batch_dev(double* x_dev, int nvec, int64_t ldx, int job, bool pivot_order) {
+  return run_factor_mult_batch(x_dev, true, nvec, ldx, job, pivot_order);
+}
+
+int Engine::factor_mult_batch(double* x_host, int nvec, int64_t ldx, int job) {
+  return run_factor_mult_batch(x_host, false, nvec, ldx, job, false);
 }
 
 int Engine::white_noise_batch_dev(double* z_dev, int nsamp, int64_t ldz, uint64_t seed, uint64_t first, uint32_t stream0,
                                   int stream_step) {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!z_dev || nsamp < 0 || ldz < S_->n || stream_step < 0 || stream_step > 1 || bt_.nbatch <= 0) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nsamp == 0 || S_->n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc;
+  if (!enter(z_dev && nsamp >= 0 && ldz >= S_->n && stream_step >= 0 && stream_step <= 1 && bt_.nbatch > 0,
+             nsamp == 0 || S_->n == 0, &rc))
+    return rc;
   launch_batch_white_noise(stream_, bmult_view(16), z_dev, (int64_t)nsamp * ldz, ldz, nullptr, S_->n, nsamp, seed, first,
                            stream0, stream_step);
   HIPCHK(hipGetLastError(), "white_noise_batch launch");
-  if (int rc = sync_stream(stream_, "white_noise_batch sync")) return rc;
+  if ((rc = sync_stream(stream_, "white_noise_batch sync"))) return rc;
   return batch_failed();
 }
 
@@ -1095,18 +1010,13 @@ int Engine::white_noise_batch_dev(double* z_dev, int nsamp, int64_t ldz, uint64_
 // user positions, the product and the sweep then run through their own batch entry points.
 int Engine::sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, uint64_t first, uint32_t stream0,
                          int stream_step, const double* mean, int64_t ldmean, bool dev) {
-  feature_err_.clear();
-  if (status_) return status_;
   const int n = S_->n, nbatch = bt_.nbatch;
-  if (!x || nsamp < 0 || ldx < n || kind < 0 || kind > 1 || stream_step < 0 || stream_step > 1 ||
-      (mean && ldmean != 0 && ldmean < n) || nbatch <= 0)
-    return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;
-  if (nsamp == 0 || n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = kind == 1 ? prepare_factor_mult_batch() : 0;
-  if (rc) return rc;
+  int rc;
+  if (!enter(x && nsamp >= 0 && ldx >= n && kind >= 0 && kind <= 1 && stream_step >= 0 && stream_step <= 1 &&
+                 !(mean && ldmean != 0 && ldmean < n) && nbatch > 0,
+             nsamp == 0 || n == 0, &rc))
+    return rc;
+  if (kind == 1 && (rc = prepare_factor_mult_batch())) return rc;
   if (hipError_t e = ensure_order()) {
     (void)hipGetLastError();
     feature_err_ = std::string("sample_batch: the order table could not be uploaded: ") + hipGetErrorString(e);
@@ -1125,12 +1035,10 @@ int Engine::sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t s
   auto group = [&](double* xg, int64_t xs, int64_t ld, int nv, uint64_t s0) -> int {
     launch_batch_white_noise(stream_, bmult_view(16), xg, xs, ld, d_order_, n, nv, seed, s0, stream0, stream_step);
     if (kind == 1) {
-      for (int done = 0; done < nv;) {
-        const int left = nv - done;
-        const int rb = left > 16 && bm_rb_ == 32 ? 32 : 16, cur = std::min(left, rb);
+      for_each_block(nv, bm_rb_, [&](int done, int cur, int rb) {
         enqueue_factor_mult_batch_block(xg + (int64_t)done * ld, xs, ld, cur, rb, 1, false);
-        done += cur;
-      }
+        return 0;
+      });
     } else {
       // (xs = nv * ld: the layout of solve_batch; its -20 is this call's own: the failed members keep their NaN)
       const int r = bsm_on_ ? solve_many_batch(xg, true, nv, ld, 2, false) : solve_batch(xg, true, nv, ld, 2, false);
@@ -1147,20 +1055,15 @@ int Engine::sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t s
   }
   // groups of at most 32 samples per member through the batch's staging buffer, packed (vector q of member b at
   // (b * nv + q) * n: the layout of solve_batch, which stages nothing for vectors that are on the device)
-  const int gmax = std::min(nsamp, 32);
-  if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)gmax * (size_t)n, "the staged samples")))
+  // (min(left, 32) is the block rule's nv at cap 32 for every left)
+  if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)std::min(nsamp, 32) * (size_t)n,
+                              "the staged samples")))
     return rc;
-  for (int done = 0; done < nsamp;) {
-    const int nv = std::min(gmax, nsamp - done);
-    if ((rc = group(bt_.stage, (int64_t)nv * n, (int64_t)n, nv, first + (uint64_t)done))) return rc;
-    for (int b = 0; b < nbatch; ++b)
-      if ((rc = copy_vectors(false, bt_.stage + (int64_t)b * nv * n, x + ((int64_t)b * nsamp + done) * ldx, ldx, nv,
-                             "batch x D2H")))
-        return rc;
-    if ((rc = sync_stream(stream_, "sample_batch sync"))) return rc;
-    done += nv;
-  }
-  return batch_failed();
+  rc = walk_blocks({"sample_batch", x, false, nsamp, ldx, nbatch, bt_.stage, 32, false, false},
+                   [&](int done, double* xg, int64_t xs, int64_t ld, int nv, int, bool) {
+                     return group(xg, xs, ld, nv, first + (uint64_t)done);
+                   });
+  return rc ? rc : batch_failed();
 }
 
 // ---- blocked solve for every member of a batch -------------------------------------------------------
@@ -1181,15 +1084,7 @@ int Engine::prepare_solve_many_batch() {
   // (a failure here leaves the batch, solve_batch and the single factorization usable)
   hipError_t e = ensure_order();
   size_t want = 0;
-  for (int rb = 32; e == hipSuccess && rb >= 16; rb /= 2) {
-    want = sizeof(double) * (size_t)nbatch * (size_t)rb * n1;
-    e = fmult_take((void**)&d_bsmW_, want);
-    bsm_rb_ = rb;
-    if (e == hipSuccess) break;
-    (void)hipGetLastError();
-    d_bsmW_ = nullptr;
-    if (rb > 16 && alloc_code(e) == -1) e = hipSuccess;   // (out of memory: once more with half of it)
-  }
+  if (e == hipSuccess) e = take_block_buffers({{(void**)&d_bsmW_, sizeof(double) * (size_t)nbatch * n1}}, &bsm_rb_, &want);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     feature_err_ = "solve_many_batch: not enough device memory for the workspace of 16 right-hand sides for each of " +
@@ -1204,11 +1099,8 @@ int Engine::prepare_solve_many_batch() {
 }
 
 int Engine::release_solve_many_batch() {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!bsm_ready_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "solve_many_batch release")) return rc;
+  int rc;
+  if (!enter_release(bsm_ready_, "solve_many_batch release", &rc)) return rc;
   drop_solve_many_batch();
   return 0;
 }
@@ -1236,59 +1128,27 @@ int Engine::enqueue_solve_many_batch_block(double* x_dev, int64_t xstride, int64
 }
 
 int Engine::solve_many_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order) {
-  feature_err_.clear();
-  if (status_) return status_;
   const int n = S_->n, nbatch = bt_.nbatch;
-  if (!x || nrhs < 0 || ldx < n || job < 0 || job > 2 || nbatch <= 0) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;          // (the caller waits first)
-  if (nrhs == 0 || n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_solve_many_batch();
-  if (rc) return rc;
+  int rc;
+  if (!enter(x && nrhs >= 0 && ldx >= n && job >= 0 && job <= 2 && nbatch > 0, nrhs == 0 || n == 0, &rc)) return rc;
+  if ((rc = prepare_solve_many_batch())) return rc;
   if (!on_device &&
       (rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)std::min(nrhs, 32) * (size_t)n,
                               "the staged right-hand sides")))
     return rc;
-  int64_t blocks = 0, launches = 0;
-  bool fits = true;
-  for (int done = 0; done < nrhs && fits;) {
-    const int left = nrhs - done;
-    const int rb = left > 16 && bsm_rb_ == 32 ? 32 : 16, nv = std::min(left, rb);
-    int k;
-    if (on_device) {
-      k = enqueue_solve_many_batch_block(x + (int64_t)done * ldx, (int64_t)nrhs * ldx, ldx, nv, rb, job, pivot_order);
-    } else {
-      // the block of every member through the staging buffer, packed (a failed member's vectors make the round trip
-      // unchanged: nothing on the device touches them)
-      for (int b = 0; b < nbatch; ++b)
-        if ((rc = copy_vectors(true, bt_.stage + (int64_t)b * nv * n, x + ((int64_t)b * nrhs + done) * ldx, ldx, nv,
-                               "batch rhs H2D")))
-          return rc;
-      k = enqueue_solve_many_batch_block(bt_.stage, (int64_t)nv * n, n, nv, rb, job, false);
-      HIPCHK(hipGetLastError(), "solve_many_batch launch");
-      if (k >= 0) {
-        for (int b = 0; b < nbatch; ++b)
-          if ((rc = copy_vectors(false, bt_.stage + (int64_t)b * nv * n, x + ((int64_t)b * nrhs + done) * ldx, ldx, nv,
-                                 "batch x D2H")))
-            return rc;
-      }
-      if ((rc = sync_stream(stream_, "solve_many_batch sync"))) return rc;
-    }
-    if (k < 0) fits = false;
-    else launches += k;
-    ++blocks;
-    done += nv;
-  }
-  HIPCHK(hipGetLastError(), "solve_many_batch launch");
-  if ((rc = sync_stream(stream_, "solve_many_batch sync"))) return rc;
-  if (!fits) {
+  BlockTally t;
+  rc = walk_blocks({"solve_many_batch", x, on_device, nrhs, ldx, nbatch, bt_.stage, bsm_rb_, pivot_order},
+                   [&](int, double* xd, int64_t xs, int64_t ld, int nv, int rb, bool po) {
+                     return enqueue_solve_many_batch_block(xd, xs, ld, nv, rb, job, po);
+                   }, &t);
+  if (rc == -1) {   // (of the enqueue; the walk's own failures are kErrHip)
     feature_err_ = "solve_many_batch: a launch has more work items for one member than a grid holds (the vectors are not "
                    "all solved)";
     return -99;
   }
-  bsm_info_[1] = blocks;
-  bsm_info_[2] = launches;
+  if (rc) return rc;
+  bsm_info_[1] = t.blocks;
+  bsm_info_[2] = t.launches;
   return batch_failed();
 }
 
@@ -1352,11 +1212,8 @@ int Engine::prepare_refine(bool host_val) {
 }
 
 int Engine::release_refine() {
-  feature_err_.clear();
-  if (status_) return status_;
-  if (!refine_ready_ && !d_rfval_) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  if (int rc = sync_stream(stream_, "refine release")) return rc;
+  int rc;
+  if (!enter_release(refine_ready_ || d_rfval_, "refine release", &rc)) return rc;
   for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_, (void*)d_rfval_})
     if (p) release_buffer(p);
   d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr; d_rfval_ = nullptr;
@@ -1366,16 +1223,10 @@ int Engine::release_refine() {
 
 int Engine::matvec(const double* val, int nvec, const double* x, int64_t ldx, double* y, int64_t ldy, bool dev,
                    bool pivot_order) {
-  feature_err_.clear();
-  if (status_) return status_;
   const int n = S_->n;
-  if (!val || !x || !y || nvec < 0 || ldx < n || ldy < n) return -10;
-  if (opt_.nranks > 1) return -98;
-  if (pending_) return -10;   // (the caller waits first)
-  if (nvec == 0 || n == 0) return 0;
-  HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc = prepare_refine(!dev);
-  if (rc) return rc;
+  int rc;
+  if (!enter(val && x && y && nvec >= 0 && ldx >= n && ldy >= n, nvec == 0 || n == 0, &rc)) return rc;
+  if ((rc = prepare_refine(!dev))) return rc;
   const double* dval = val;
   if (!dev) {
     HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");

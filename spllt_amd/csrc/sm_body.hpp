@@ -1,7 +1,8 @@
 // The device bodies of the blocked substitution (solve_many.hip: one arena; batch_solve_many.hip: one arena per
 // member of a batch).  A body is a function of (unit or tile, L, dinv, W, rlist, the LDS array) alone: the
 // kernels around it only say which arena, which dinv scratch and which workspace.  Every sum runs in the order
-// it has always had in k_sm_*: fixed by the tables and by K, never by the wrapper.
+// it has always had in k_sm_*: fixed by the tables and by K, never by the wrapper.  (The pack / unpack body, which
+// the products use too, is in sm_mm.hpp.)
 //
 // Workspace layout: W[p * RB + q], pivot position p, right-hand side q < RB.  Lane l of a wavefront supplies
 // A[l&15][l>>4] and B[l>>4][l&15] and receives C[(l>>4) + 4 r][l&15] in register r.
@@ -14,37 +15,6 @@
 #include "sm_mm.hpp"
 
 namespace spx {
-
-// ---------------------------------------------------------------------------
-// pack: W[p(i) * RB + q] = q < nv ? x[q * ldx + i] : 0,  p(i) = order[i] (user order) or i (order = null)
-// unpack: x[q * ldx + i] = W[p(i) * RB + q] for q < nv only.  Rows i0 .. i0 + 63, transposed through `tile`.
-// ---------------------------------------------------------------------------
-template <int RB, bool UNPACK>
-__device__ __forceinline__ void sm_pack_body(int i0, double* __restrict__ x, int64_t ldx, const int* __restrict__ order,
-                                             int n, int nv, double* __restrict__ W, double (*tile)[RB + 1]) {
-  const int tid = threadIdx.x;
-  if (!UNPACK) {
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int ii = e & 63, q = e >> 6, i = i0 + ii;
-      tile[ii][q] = (i < n && q < nv) ? x[(int64_t)q * ldx + i] : 0.0;
-    }
-    __syncthreads();
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int q = e % RB, ii = e / RB, i = i0 + ii;
-      if (i < n) W[(int64_t)(order ? order[i] : i) * RB + q] = tile[ii][q];
-    }
-  } else {
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int q = e % RB, ii = e / RB, i = i0 + ii;
-      if (i < n) tile[ii][q] = W[(int64_t)(order ? order[i] : i) * RB + q];
-    }
-    __syncthreads();
-    for (int e = tid; e < 64 * RB; e += 256) {
-      const int ii = e & 63, q = e >> 6, i = i0 + ii;
-      if (i < n && q < nv) x[(int64_t)q * ldx + i] = tile[ii][q];
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // Diagonal tile of one block column per workgroup (4 wavefronts, wavefront v owns rows 16 v .. 16 v + 15

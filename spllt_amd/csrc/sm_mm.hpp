@@ -3,6 +3,8 @@
 // Lane l of a wavefront supplies A[l&15][l>>4] and B[l>>4][l&15] and receives C[(l>>4) + 4 r][l&15] in
 // register r.  Column q of the result depends on column q of B alone, and its sum runs over k in an order
 // that depends on K only: not on RB, and not on the column's place in the block.
+// Also what every blocked translation unit needs besides (solve_many.hip, batch_solve_many.hip, batch_mult.hip; no
+// atomic add in this header): the pack / unpack of a block of vectors, the workgroup -> (member, work item) split.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,6 +56,49 @@ __device__ __forceinline__ void sm_mm(const double* arow, int64_t sa, int K, con
 #pragma unroll
     for (int c = 0; c < NC; ++c)
       acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bp[(int64_t)kc * ldb + 16 * c + col], acc[c], 0, 0, 0);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// pack: W[p(i) * RB + q] = q < nv ? x[q * ldx + i] : 0,  p(i) = order[i] (user order) or i (order = null)
+// unpack: x[q * ldx + i] = W[p(i) * RB + q] for q < nv only.  Rows i0 .. i0 + 63, transposed through `tile`.
+// ---------------------------------------------------------------------------
+template <int RB, bool UNPACK>
+__device__ __forceinline__ void sm_pack_body(int i0, double* __restrict__ x, int64_t ldx, const int* __restrict__ order,
+                                             int n, int nv, double* __restrict__ W, double (*tile)[RB + 1]) {
+  const int tid = threadIdx.x;
+  if (!UNPACK) {
+    for (int e = tid; e < 64 * RB; e += 256) {
+      const int ii = e & 63, q = e >> 6, i = i0 + ii;
+      tile[ii][q] = (i < n && q < nv) ? x[(int64_t)q * ldx + i] : 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < 64 * RB; e += 256) {
+      const int q = e % RB, ii = e / RB, i = i0 + ii;
+      if (i < n) W[(int64_t)(order ? order[i] : i) * RB + q] = tile[ii][q];
+    }
+  } else {
+    for (int e = tid; e < 64 * RB; e += 256) {
+      const int q = e % RB, ii = e / RB, i = i0 + ii;
+      if (i < n) tile[ii][q] = W[(int64_t)(order ? order[i] : i) * RB + q];
+    }
+    __syncthreads();
+    for (int e = tid; e < 64 * RB; e += 256) {
+      const int ii = e & 63, q = e >> 6, i = i0 + ii;
+      if (i < n && q < nv) x[(int64_t)q * ldx + i] = tile[ii][q];
+    }
+  }
+}
+
+// workgroup -> (member b, work item t) of a batched launch over nbatch members: the member is the slow grid axis
+// (blockIdx.y), or with member_fast the fast index of a linear grid
+__device__ __forceinline__ void sm_member_split(int member_fast, int nbatch, int& b, unsigned& t) {
+  if (member_fast) {
+    b = (int)(blockIdx.x % (unsigned)nbatch);
+    t = blockIdx.x / (unsigned)nbatch;
+  } else {
+    b = (int)blockIdx.y;
+    t = blockIdx.x;
   }
 }
 
