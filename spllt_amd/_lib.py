@@ -191,11 +191,25 @@ _BATCH_SOLVE_MANY = {
     "spllt_hip_solve_many_batch_info": (i32, [vp, i64p]),
     "spllt_hip_release_solve_many_batch": (i32, [vp]),
 }
+# every symbol declared in include/spllt_hip_batch_adjoint.h: the factor adjoint of the members of a batch.  A table
+# of its own for the same reason.
+_BATCH_ADJOINT = {
+    "spllt_hip_factor_adjoint_seed_batch_dev": (i32, [vp, i32, vp, vp, i64, f64, i32, i32]),
+    "spllt_hip_factor_adjoint_seed_batch": (i32, [vp, i32, dp, dp, i64, f64, i32, i32]),
+    "spllt_hip_set_factor_adjoint_batch": (i32, [vp, dp, i64]),
+    "spllt_hip_get_factor_adjoint_batch": (i32, [vp, i32, dp, i64]),
+    "spllt_hip_device_factor_adjoint_batch": (vp, [vp, i64p]),
+    "spllt_hip_factor_adjoint_batch_dev": (i32, [vp, vp, i64]),
+    "spllt_hip_factor_adjoint_batch": (i32, [vp, dp, i64]),
+    "spllt_hip_batch_adjoint_launches": (i32, [vp]),
+    "spllt_hip_release_factor_adjoint_batch": (i32, [vp]),
+}
 del vp, vpp, i32, i64, u64, f64, cstr, long, ip, i64p, dp, fp, longp, ipp, dpp, opt, inf   # (names of the table only)
 IFACE_SYMBOLS = list(_IFACE)
 HIP_SYMBOLS = list(_HIP)
 BATCH_MULT_SYMBOLS = list(_BATCH_MULT)
 BATCH_SOLVE_MANY_SYMBOLS = list(_BATCH_SOLVE_MANY)
+BATCH_ADJOINT_SYMBOLS = list(_BATCH_ADJOINT)
 
 _lib = None
 
@@ -210,7 +224,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C spllt_amd/csrc`. spllt_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY):
+    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -1111,6 +1111,84 @@ class Factorization:
     def release_inverse_batch(self):
         self._call("spllt_hip_release_inverse_batch", self.fkeep)
 
+    # ---- factor adjoint of the members of a batch (include/spllt_hip_batch_adjoint.h) ----
+    def factor_adjoint_seed_batch(self, a, b, alpha=1.0, accumulate=False, a_pivot_order=False, b_pivot_order=False):
+        """spllt_hip_factor_adjoint_seed_batch on host arrays a, b of shape (B, n), one vector per member, or
+        (B, nvec, n), like solve_batch: Lbar_b (+)= alpha sum_q a_bq b_bq^T on the lower positions of L_b; a
+        vector is in the user's variable order unless its flag says pivot order"""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if a.shape != b.shape or a.ndim not in (2, 3) or a.shape[-1] != self.n:
+            raise ValueError("factor_adjoint_seed_batch: a and b must both have shape (B, n) or (B, nvec, n)")
+        nb = self._batch_count()
+        if nb > 0 and a.shape[0] != nb:
+            raise ValueError(f"factor_adjoint_seed_batch: vectors for {a.shape[0]} members, the last batch has {nb}")
+        nvec = 1 if a.ndim == 2 else a.shape[1]
+        self._call("spllt_hip_factor_adjoint_seed_batch", self.fkeep, nvec, _dp(a), _dp(b), max(self.n, 1), float(alpha),
+                   1 if accumulate else 0, self._order_flags(a_pivot_order, b_pivot_order))
+        return self
+
+    def factor_adjoint_seed_batch_dev(self, a_dev_ptr, b_dev_ptr, nvec, ld=None, alpha=1.0, accumulate=False,
+                                      a_pivot_order=False, b_pivot_order=False):
+        """spllt_hip_factor_adjoint_seed_batch_dev: the seed from device vectors, vector q of member b at
+        a[(b*nvec + q)*ld .. + n)"""
+        if ld is None:
+            ld = self.n
+        self._call("spllt_hip_factor_adjoint_seed_batch_dev", self.fkeep, int(nvec), C.c_void_p(a_dev_ptr),
+                   C.c_void_p(b_dev_ptr), int(ld), float(alpha), 1 if accumulate else 0,
+                   self._order_flags(a_pivot_order, b_pivot_order))
+        return self
+
+    def set_factor_adjoint_batch(self, arenas):
+        """spllt_hip_set_factor_adjoint_batch: an arbitrary Lbar_b for every member, shape (B, >= arena), each row
+        in the layout of get_factor_batch"""
+        arenas = np.ascontiguousarray(arenas, dtype=np.float64)
+        if arenas.ndim != 2:
+            raise ValueError("set_factor_adjoint_batch: arenas must have shape (B, arena)")
+        nb = self._batch_count()
+        if nb > 0 and arenas.shape[0] != nb:
+            raise ValueError(f"set_factor_adjoint_batch: arenas for {arenas.shape[0]} members, the last batch has {nb}")
+        self._call("spllt_hip_set_factor_adjoint_batch", self.fkeep, _dp(arenas), arenas.shape[1])
+        return self
+
+    def get_factor_adjoint_batch(self, member, out=None):
+        """one member's adjoint arena on the host: Lbar_b as seeded, or after factor_adjoint_batch() d loss /
+        d (P A_b P^T) on the stored lower positions"""
+        arena = self.sym_info()["arena"]
+        if out is None:
+            out = np.zeros(max(arena, 1), dtype=np.float64)
+        assert out.dtype == np.float64 and out.size >= arena and out.flags["C_CONTIGUOUS"]
+        self._call("spllt_hip_get_factor_adjoint_batch", self.fkeep, int(member), _dp(out), arena)
+        return out[:arena]
+
+    def device_factor_adjoint_batch_ptr(self):
+        """(device pointer of member 0's adjoint arena, member stride in doubles); (None, 0) while unseeded"""
+        stride = C.c_int64()
+        p = self.lib.spllt_hip_device_factor_adjoint_batch(self.fkeep, C.byref(stride))
+        return p, stride.value
+
+    def factor_adjoint_batch(self):
+        """spllt_hip_factor_adjoint_batch: the sweep over the seeded arenas; returns d loss / d val_b, shape
+        (nbatch, nnz); the row of a member that is not positive definite is NaN"""
+        nb = self._batch_count()
+        out = np.zeros((max(nb, 1), max(self.nnz, 1)), dtype=np.float64)
+        self._call("spllt_hip_factor_adjoint_batch", self.fkeep, _dp(out), out.shape[1], ok=self._BATCH_OK)
+        return out[:nb, :self.nnz]
+
+    def factor_adjoint_batch_dev(self, gval_dev_ptr, ldout=None):
+        """spllt_hip_factor_adjoint_batch_dev: the same sweep, gval[b*ldout + k] into device memory.  Returns 0
+        or -20."""
+        return self._call("spllt_hip_factor_adjoint_batch_dev", self.fkeep, C.c_void_p(gval_dev_ptr),
+                          int(self.nnz if ldout is None else ldout), ok=self._BATCH_OK)
+
+    def batch_adjoint_launches(self):
+        """kernel launches of the last sweep of the batch's factor adjoint, the reader included"""
+        return int(self.lib.spllt_hip_batch_adjoint_launches(self.fkeep))
+
+    def release_factor_adjoint_batch(self):
+        self._call("spllt_hip_release_factor_adjoint_batch", self.fkeep)
+        return self
+
     # ---- multi-GPU subtree partition ------------------------------------------
     def set_partition(self, rank, nranks):
         """Declare this process as `rank` of `nranks`; returns the number of

@@ -27,6 +27,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "batch_split.hpp"
 #include "kernels.hpp"
 
 namespace spx {
@@ -37,21 +38,12 @@ constexpr int BI_KC = 32;           // K rows per LDS stage of k_batch_selinv_sy
 constexpr int BI_T = kSelinvTile;   // 64
 constexpr int BI_LD = BI_T + 1;     // LDS row stride of the fused kernel's two operand buffers
 
-// workgroup -> (member, work item), as in batch.hip
-__device__ __forceinline__ void bsi_split(const BatchView& v, int64_t count, int& b, int64_t& t) {
-  const unsigned wg = blockIdx.x;
-  if (v.member_fast) {
-    b = (int)(wg % (unsigned)v.nbatch);
-    t = wg / (unsigned)v.nbatch;
-  } else {
-    b = (int)(wg / (unsigned)count);
-    t = wg % (unsigned)count;
-  }
-}
-
 // ---------------------------------------------------------------------------
-// k_selinv_symm of selinv.hip for member b (dense-path shortcut included)
+// k_selinv_symm of selinv.hip for member b (dense-path shortcut included).  kDoubleDiag: the gathered block
+// is S = tril(G_RR) + tril(G_RR)^T of the factor adjoint (batch_adjoint.hip: s.Z is then the adjoint arena), whose
+// diagonal counts twice; a diagonal entry occurs in the generic branch only.  The inversion instantiates false.
 // ---------------------------------------------------------------------------
+template <bool kDoubleDiag>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_batch_selinv_symm(BatchSelinvView s, const UpdTile* __restrict__ tiles, int64_t count,
                                                            const SelinvUnit* __restrict__ units,
                                                            const SelinvRow* __restrict__ rows,
@@ -139,6 +131,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           const int a = ri >= rk ? ri : rk, e = ri >= rk ? rk : ri;
           const int64_t qpos = d.map < 0 ? (int64_t)a : (int64_t)relpos[(int64_t)d.map + a - e];
           v = Z[d.cbase + qpos * d.ld];
+          if (kDoubleDiag && ri == rk) v += v;
         }
         ra[q] = v;
       }
@@ -452,39 +445,27 @@ __global__ __launch_bounds__(256) void k_batch_selinv_pattern(BatchSelinvView s,
 // of batch.hip, test hook included); beyond that the members are split into ranges.  Every wrapper returns
 // the number of kernel launches it made (-1, nothing launched: ONE member's work items overflow a grid).
 // ---------------------------------------------------------------------------
-namespace {
-template <class Fn>
-int bsi_member_ranges(const BatchSelinvView& s, int64_t per_member, Fn&& fn) {
-  if (per_member <= 0 || s.v.nbatch <= 0) return 0;
-  const int64_t limit = batch_grid_limit();
-  if (per_member > batch_grid_limit_max()) return -1;
-  const int step = (int)std::max<int64_t>(1, std::min<int64_t>(s.v.nbatch, limit / per_member));
-  int launches = 0;
-  for (int b0 = 0; b0 < s.v.nbatch; b0 += step) {
-    BatchSelinvView r = s;
-    r.v.nbatch = std::min(step, s.v.nbatch - b0);
-    r.v.L += (int64_t)b0 * s.v.lstride;
-    r.v.dinv += (int64_t)b0 * s.v.dstride;
-    if (r.v.flag) r.v.flag += b0;
-    r.Z += (int64_t)b0 * s.v.lstride;
-    if (r.scratch) r.scratch += (int64_t)b0 * s.sstride;
-    fn(r, b0);
-    ++launches;
-  }
-  return launches;
-}
-}  // namespace
 
 int launch_batch_selinv(hipStream_t st, const BatchSelinvView& s, const SelinvLaunch& l, const SelinvUnit* units,
                         const UpdTile* tiles, const SelinvRow* rows, const int* relpos) {
   return bsi_member_ranges(s, l.count, [&](const BatchSelinvView& r, int) {
     const dim3 grid((unsigned)(l.count * r.v.nbatch));
     if (l.kind == SI_SYMM)
-      hipLaunchKernelGGL(k_batch_selinv_symm, grid, dim3(256), 0, st, r, tiles + l.first, l.count, units, rows, relpos);
+      hipLaunchKernelGGL(k_batch_selinv_symm<false>, grid, dim3(256), 0, st, r, tiles + l.first, l.count, units, rows, relpos);
     else if (l.kind == SI_SCALE)
       hipLaunchKernelGGL(k_batch_selinv_scale, grid, dim3(256), 0, st, r, tiles + l.first, l.count, units);
     else
       hipLaunchKernelGGL(k_batch_selinv_diag, grid, dim3(1024), 0, st, r, units + l.first, l.count);
+  });
+}
+
+int launch_batch_selinv_symm_doubled(hipStream_t st, const BatchSelinvView& s, const SelinvLaunch& l,
+                                     const SelinvUnit* units, const UpdTile* tiles, const SelinvRow* rows,
+                                     const int* relpos) {
+  if (l.kind != SI_SYMM) return 0;
+  return bsi_member_ranges(s, l.count, [&](const BatchSelinvView& r, int) {
+    hipLaunchKernelGGL(k_batch_selinv_symm<true>, dim3((unsigned)(l.count * r.v.nbatch)), dim3(256), 0, st, r,
+                       tiles + l.first, l.count, units, rows, relpos);
   });
 }
 

@@ -1,0 +1,49 @@
+// What the batched translation units on a BatchSelinvView share (batch_selinv.hip, batch_adjoint.hip): the map
+// from a workgroup to (member, work item), and the split of the members of a launch into ranges.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "kernels.hpp"
+
+namespace spx {
+
+// workgroup -> (member, work item), as in batch.hip
+__device__ __forceinline__ void bsi_split(const BatchView& v, int64_t count, int& b, int64_t& t) {
+  const unsigned wg = blockIdx.x;
+  if (v.member_fast) {
+    b = (int)(wg % (unsigned)v.nbatch);
+    t = wg / (unsigned)v.nbatch;
+  } else {
+    b = (int)(wg / (unsigned)count);
+    t = wg % (unsigned)count;
+  }
+}
+
+// fn(view of the members [b0, b0 + r.v.nbatch), b0) once per range: one range as long as (work items) x (members)
+// fits a grid (the limit of batch.hip, test hook included).  Returns the number of ranges (-1, fn never called:
+// ONE member's work items overflow a grid).
+template <class Fn>
+int bsi_member_ranges(const BatchSelinvView& s, int64_t per_member, Fn&& fn) {
+  if (per_member <= 0 || s.v.nbatch <= 0) return 0;
+  const int64_t limit = batch_grid_limit();
+  if (per_member > batch_grid_limit_max()) return -1;
+  const int step = (int)std::max<int64_t>(1, std::min<int64_t>(s.v.nbatch, limit / per_member));
+  int launches = 0;
+  for (int b0 = 0; b0 < s.v.nbatch; b0 += step) {
+    BatchSelinvView r = s;
+    r.v.nbatch = std::min(step, s.v.nbatch - b0);
+    r.v.L += (int64_t)b0 * s.v.lstride;
+    r.v.dinv += (int64_t)b0 * s.v.dstride;
+    if (r.v.flag) r.v.flag += b0;
+    r.Z += (int64_t)b0 * s.v.lstride;
+    if (r.scratch) r.scratch += (int64_t)b0 * s.sstride;
+    fn(r, b0);
+    ++launches;
+  }
+  return launches;
+}
+
+}  // namespace spx

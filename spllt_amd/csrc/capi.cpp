@@ -29,6 +29,7 @@
 #include "kernels.hpp"
 #include "spllt_hip.h"
 #include "spllt_hip_batch_mult.h"
+#include "spllt_hip_batch_adjoint.h"
 #include "spllt_hip_batch_solve_many.h"
 #include "symbolic.hpp"
 
@@ -721,6 +722,7 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 //   fmult_alloc_fail=N      the next N allocations of the products' second workspace and scratch fail (those of
 //                           the batched products and the workspace of the batched blocked solve included)
 //   batch_selinv_fused=0|1  0 forces the three-launch form of every step of the batched selected inversion
+//   batch_fadj_fused=0|1    1 runs the eligible steps of the factor adjoint of a batch as one fused launch each (default 0)
 //   rsolve_poison=0|1       1 fills the scratch of the reproducible solve with NaN before every sweep
 //   solve_sparse_poison=0|1 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
 //   fmult_poison=0|1        1 fills the scratch of the factor products (the batched ones too) with NaN before every
@@ -737,7 +739,8 @@ int spllt_hip_debug(const char* what) {
   if (name == "batch_grid_limit") { set_batch_grid_limit(std::atoll(value.c_str())); return 0; }
   if (name == "fmult_alloc_fail") { set_fmult_alloc_fail(std::atoi(value.c_str())); return 0; }
   static const struct { const char* name; void (*set)(bool); } kSwitches[] = {
-      {"batch_selinv_fused", set_batch_selinv_fused}, {"rsolve_poison", set_rsolve_poison},
+      {"batch_selinv_fused", set_batch_selinv_fused}, {"batch_fadj_fused", set_batch_fadj_fused},
+      {"rsolve_poison", set_rsolve_poison},
       {"solve_sparse_poison", set_solve_sparse_poison}, {"fmult_poison", set_fmult_poison}};
   for (const auto& s : kSwitches)
     if (name == s.name && (value == "0" || value == "1")) { s.set(value == "1"); return 0; }
@@ -1580,6 +1583,87 @@ int spllt_hip_factor_adjoint(void* fkeep, double* gval_host) {
   return fadj_sweep_impl("spllt_hip_factor_adjoint", fkeep, gval_host, false);
 }
 
+// ---- reverse-mode derivative of the factors of a batch (spllt_hip_batch_adjoint.h) ------------------
+constexpr unsigned kBatchAdjoint = SINGLE | WAIT_IGNORE | BATCH;
+
+static int bfadj_seed_impl(const char* what, void* fkeep, int nvec, const double* a, const double* b, int64_t ld,
+                           double alpha, int accumulate, int order_flags, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!a || !b) bad = "a vector array is null";
+  else if (nvec < 0) bad = "nvec < 0";
+  else if (ld < f->S->n) bad = "ld < n";
+  else if (accumulate < 0 || accumulate > 1) bad = "accumulate is not 0 or 1";
+  else if (order_flags < 0 || order_flags > 3) bad = "order_flags is not 0 .. 3";
+  if (int rc = enter(f, what, bad, kBatchAdjoint)) return rc;
+  return leave(f, f->eng->fadj_seed_batch(nvec, a, b, ld, alpha, accumulate != 0, order_flags, dev));
+}
+
+int spllt_hip_factor_adjoint_seed_batch_dev(void* fkeep, int nvec, const double* a_dev, const double* b_dev, int64_t ld,
+                                            double alpha, int accumulate, int order_flags) {
+  return bfadj_seed_impl("spllt_hip_factor_adjoint_seed_batch_dev", fkeep, nvec, a_dev, b_dev, ld, alpha, accumulate,
+                         order_flags, true);
+}
+
+int spllt_hip_factor_adjoint_seed_batch(void* fkeep, int nvec, const double* a_host, const double* b_host, int64_t ld,
+                                        double alpha, int accumulate, int order_flags) {
+  return bfadj_seed_impl("spllt_hip_factor_adjoint_seed_batch", fkeep, nvec, a_host, b_host, ld, alpha, accumulate,
+                         order_flags, false);
+}
+
+int spllt_hip_set_factor_adjoint_batch(void* fkeep, const double* host_arenas, int64_t ldarena) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = !host_arenas ? "the arenas are null" : ldarena < f->S->arena ? "ldarena is smaller than the factor arena" : nullptr;
+  if (int rc = enter(f, "spllt_hip_set_factor_adjoint_batch", bad, kBatchAdjoint)) return rc;
+  return leave(f, f->eng->fadj_upload_batch(host_arenas, ldarena));
+}
+
+int spllt_hip_get_factor_adjoint_batch(void* fkeep, int member, double* out, int64_t count) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_get_factor_adjoint_batch";
+  const char* bad = !out ? "the output array is null" : count < 0 ? "count < 0" : nullptr;
+  if (int rc = enter(f, what, bad, kBatchAdjoint)) return rc;
+  if (f->eng->fadj_batch_state() == Engine::FADJ_UNSEEDED)
+    return fail(f, what, "no factor adjoint of the current batch (seed it after every spllt_hip_factor_batch)");
+  if (member < 0 || member >= f->eng->batch_count()) return fail(f, what, "member is not in [0, nbatch)");
+  return leave(f, f->eng->fadj_download_batch(member, out, count));
+}
+
+double* spllt_hip_device_factor_adjoint_batch(void* fkeep, int64_t* member_stride) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (member_stride) *member_stride = 0;
+  if (!f || !f->eng || f->dead || f->eng->pending()) return nullptr;
+  return f->eng->device_G_batch(member_stride);
+}
+
+static int bfadj_sweep_impl(const char* what, void* fkeep, double* gval, int64_t ldout, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = !gval ? "the gradient array is null" : ldout < f->S->nnzA ? "ldout < nnz" : nullptr;
+  if (int rc = enter(f, what, bad, kBatchAdjoint)) return rc;
+  const int rc = f->eng->fadj_sweep_batch(gval, ldout, dev);
+  if (rc == SPLLT_ERROR_NOT_POSDEF)   // -20 of the batch calls
+    return fail(f, what, "the members that are not positive definite were skipped (their rows are NaN), the others are "
+                         "served (spllt_hip_batch_status)", rc);
+  return leave(f, rc);
+}
+
+int spllt_hip_factor_adjoint_batch_dev(void* fkeep, double* gval_dev, int64_t ldout) {
+  return bfadj_sweep_impl("spllt_hip_factor_adjoint_batch_dev", fkeep, gval_dev, ldout, true);
+}
+
+int spllt_hip_factor_adjoint_batch(void* fkeep, double* gval_host, int64_t ldout) {
+  return bfadj_sweep_impl("spllt_hip_factor_adjoint_batch", fkeep, gval_host, ldout, false);
+}
+
+int spllt_hip_batch_adjoint_launches(void* fkeep) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f) return SPLLT_ERROR_PARAMETER;
+  return (f->eng && !f->dead) ? f->eng->batch_adjoint_launches() : 0;
+}
+
 // ---- giving a feature's device memory back ---------------------------------------------------------
 // Three shapes have grown, and they differ observably; the differences stay, as flags:
 //   WAIT_NOT_POSDEF  a pending failure other than "not positive definite" is returned, nothing released
@@ -1604,6 +1688,7 @@ int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::releas
 int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_solve_many_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_many_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse_batch(void* fkeep) { return release(fkeep, &Engine::release_inverse_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_factor_adjoint_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_adjoint_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse(void* fkeep) { return release(fkeep, &Engine::release_inverse, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_adjoint(void* fkeep) { return release(fkeep, &Engine::release_factor_adjoint, WAIT_IGNORE | LENIENT); }
 

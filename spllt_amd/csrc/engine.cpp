@@ -1504,9 +1504,9 @@ int Engine::release_inverse() {
 }
 
 // ---- reverse-mode derivative of the factor ---------------------------------------------------------
-int Engine::prepare_fadj() {
-  int rc = prepare_selinv();
-  if (rc) return rc;
+// the seed kernel's tables (block columns, (block column, strip) tiles, position -> variable): from the
+// Symbolic structure alone, shared by the single arena and the arenas of a batch
+int Engine::prepare_fadj_tables() {
   const Symbolic& S = *S_;
   if (!d_fadj_tables_) {
     std::vector<FadjCol> cols((size_t)S.nbcol());
@@ -1529,6 +1529,14 @@ int Engine::prepare_fadj() {
     }
     fa_ntiles_ = (int64_t)tiles.size();
   }
+  return 0;
+}
+
+int Engine::prepare_fadj() {
+  int rc = prepare_selinv();
+  if (rc) return rc;
+  if ((rc = prepare_fadj_tables())) return rc;
+  const Symbolic& S = *S_;
   if (!d_G_ || !d_siscratch_) {
     const size_t gb = sizeof(double) * (size_t)std::max<int64_t>(1, S.arena);
     const size_t sb = sizeof(double) * (size_t)std::max<int64_t>(1, siprog_.scratch_size);
@@ -2087,6 +2095,7 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   if ((rc = reserve_batch(nbatch))) return rc;
   bt_.nbatch = 0;                    // (no batch until this one is finished)
   bt_.z_valid = false;               // (the members' inverses belong to the factors this call replaces)
+  bt_.g_state = FADJ_UNSEEDED;       // (... and so do their adjoints)
   bt_.hflag.clear();
   const double* vd = val;
   int64_t ld = ldval;
@@ -2203,17 +2212,19 @@ int Engine::release_batch() {
   feature_err_.clear();
   if (status_) return status_;
   bt_.z_valid = false;
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bm_ready_ && !d_bmmean_ && !bsm_ready_) { bt_.nbatch = 0; return 0; }
+  bt_.g_state = FADJ_UNSEEDED;
+  bt_.fa_launches = 0;
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bt_.siscratch && !bm_ready_ && !d_bmmean_ && !bsm_ready_) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
   drop_solve_many_batch();    // (... and that of the blocked solve)
   for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out, (void*)bt_.Y, (void*)bt_.stage,
-                  (void*)bt_.Z, (void*)bt_.siscratch})
+                  (void*)bt_.Z, (void*)bt_.G, (void*)bt_.siscratch})
     if (p) release_buffer(p);
-  bt_.L = bt_.dinv = bt_.out = bt_.Y = bt_.stage = bt_.Z = bt_.siscratch = nullptr;
+  bt_.L = bt_.dinv = bt_.out = bt_.Y = bt_.stage = bt_.Z = bt_.G = bt_.siscratch = nullptr;
   bt_.flag = nullptr;
-  bt_.z_capacity = 0;
+  bt_.z_capacity = bt_.g_capacity = bt_.sc_capacity = 0;
   bt_.si_launches = 0;
   bt_.capacity = bt_.nbatch = 0;
   bt_.y_elems = bt_.stage_elems = 0;
@@ -2275,30 +2286,63 @@ int Engine::prepare_batch_selinv() {
   return 0;
 }
 
-// Z arenas and step scratch for nbatch members; all or nothing (a failure leaves the batch factor usable)
-int Engine::reserve_batch_inverse(int nbatch) {
-  if (nbatch <= bt_.z_capacity && bt_.Z && bt_.siscratch) return 0;
-  auto drop = [this]() {
-    if (bt_.Z) release_buffer(bt_.Z);
-    if (bt_.siscratch) release_buffer(bt_.siscratch);
-    bt_.Z = bt_.siscratch = nullptr;
-    bt_.z_capacity = 0;
-    bt_.z_valid = false;
-  };
-  drop();
-  const size_t zb = sizeof(double) * (size_t)bt_.lstride * (size_t)nbatch;
+// the step scratch of the batch's SelinvProgram for nbatch members: shared by the inversion and the factor
+// adjoint (a step leaves nothing in it), taken by whoever comes first
+hipError_t Engine::reserve_batch_scratch(int nbatch) {
+  if (nbatch <= bt_.sc_capacity && bt_.siscratch) return hipSuccess;
+  if (bt_.siscratch) release_buffer(bt_.siscratch);
+  bt_.siscratch = nullptr;
+  bt_.sc_capacity = 0;
+  hipError_t e = dalloc((void**)&bt_.siscratch, sizeof(double) * (size_t)bt_.sstride * (size_t)nbatch);
+  if (e != hipSuccess) {
+    bt_.siscratch = nullptr;
+    return e;
+  }
+  bt_.sc_capacity = nbatch;
+  return hipSuccess;
+}
+
+// One set of arenas of the batch (Z or G: *capacity x lstride doubles) and the step scratch for nbatch members; all or
+// nothing: a failure keeps neither the arenas nor -- unless `other`, the set that shares it, is held -- the scratch,
+// and leaves the batch factor usable.  *retaken: the arenas are new memory (what they held is gone).
+int Engine::reserve_batch_arenas(double** arena, int* capacity, const double* other, int nbatch, const char* feature,
+                                 const char* which, bool* retaken) {
+  *retaken = false;
+  if (nbatch <= *capacity && *arena && nbatch <= bt_.sc_capacity && bt_.siscratch) return 0;
+  const size_t ab = sizeof(double) * (size_t)bt_.lstride * (size_t)nbatch;
   const size_t sb = sizeof(double) * (size_t)bt_.sstride * (size_t)nbatch;
-  hipError_t e = dalloc((void**)&bt_.Z, zb);
-  if (e == hipSuccess) e = dalloc((void**)&bt_.siscratch, sb);
+  hipError_t e = hipSuccess;
+  if (nbatch > *capacity || !*arena) {
+    if (*arena) release_buffer(*arena);
+    *arena = nullptr;
+    *capacity = 0;
+    *retaken = true;
+    e = dalloc((void**)arena, ab);
+    if (e != hipSuccess) *arena = nullptr;
+  }
+  if (e == hipSuccess) e = reserve_batch_scratch(nbatch);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    drop();
-    feature_err_ = "batched selected inversion: not enough device memory for the inverse arenas of " + std::to_string(nbatch) +
-                   " members (" + std::to_string((zb + sb) >> 20) + " MiB): " + hipGetErrorString(e);
+    if (*arena) release_buffer(*arena);
+    *arena = nullptr;
+    *capacity = 0;
+    *retaken = true;
+    if (bt_.siscratch && !other) { release_buffer(bt_.siscratch); bt_.siscratch = nullptr; bt_.sc_capacity = 0; }
+    feature_err_ = std::string(feature) + ": not enough device memory for the " + which + " of " + std::to_string(nbatch) +
+                   " members (" + std::to_string((ab + sb) >> 20) + " MiB): " + hipGetErrorString(e);
     return -1;
   }
-  bt_.z_capacity = nbatch;
+  *capacity = nbatch;
   return 0;
+}
+
+// Z arenas and step scratch for nbatch members; all or nothing (a failure leaves the batch factor usable)
+int Engine::reserve_batch_inverse(int nbatch) {
+  bool retaken;
+  const int rc = reserve_batch_arenas(&bt_.Z, &bt_.z_capacity, bt_.G, nbatch, "batched selected inversion", "inverse arenas",
+                                      &retaken);
+  if (retaken) bt_.z_valid = false;
+  return rc;
 }
 
 int Engine::selected_inverse_batch() {
@@ -2414,13 +2458,203 @@ int Engine::release_inverse_batch() {
   if (status_) return status_;
   bt_.z_valid = false;
   bt_.si_launches = 0;
-  if (!bt_.Z && !bt_.siscratch) return 0;
+  if (!bt_.Z && (!bt_.siscratch || bt_.G)) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch inverse release")) return rc;
   if (bt_.Z) release_buffer(bt_.Z);
-  if (bt_.siscratch) release_buffer(bt_.siscratch);
-  bt_.Z = bt_.siscratch = nullptr;
+  bt_.Z = nullptr;
   bt_.z_capacity = 0;
+  if (bt_.siscratch && !bt_.G) {   // (the factor adjoint of the batch shares the scratch)
+    release_buffer(bt_.siscratch);
+    bt_.siscratch = nullptr;
+    bt_.sc_capacity = 0;
+  }
+  return 0;
+}
+
+// ---- reverse-mode derivative of the factors of a batch ------------------------------------------------
+// (off by default: measured, DESIGN.md section 23 -- not slower than the three-launch form from 4 members on, 0.4 %
+// slower with ONE member of a 128 x 128 Poisson problem)
+namespace {
+std::atomic<bool> g_batch_fadj_fused{false};
+}
+void set_batch_fadj_fused(bool on) { g_batch_fadj_fused.store(on); }
+bool batch_fadj_fused() { return g_batch_fadj_fused.load(); }
+
+// program tables, seed tables, the adjoint arenas and the step scratch for the current batch; all or nothing
+// (a failure keeps nothing new and leaves the batch factor, its solves and its inversion usable)
+int Engine::reserve_batch_adjoint() {
+  int rc = prepare_batch_selinv();
+  if (rc) return rc;
+  if ((rc = prepare_fadj_tables())) return rc;
+  bool retaken;
+  rc = reserve_batch_arenas(&bt_.G, &bt_.g_capacity, bt_.Z, bt_.nbatch, "batch factor adjoint", "adjoint arenas", &retaken);
+  if (retaken) bt_.g_state = FADJ_UNSEEDED;
+  return rc;
+}
+
+BatchSelinvView Engine::batch_adjoint_view() const {
+  BatchSelinvView s = batch_selinv_view();
+  s.Z = bt_.G;
+  return s;
+}
+
+int Engine::fadj_seed_batch(int nvec, const double* a, const double* b, int64_t ld, double alpha, bool accumulate,
+                            int order_flags, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (opt_.nranks > 1) return -98;
+  const int n = S_->n;
+  if (pending_ || !a || !b || nvec < 0 || ld < n || bt_.nbatch <= 0) return -10;
+  if (accumulate && bt_.g_state != FADJ_SEEDED) {
+    feature_err_ = "batch factor adjoint: accumulate = 1 needs seeded adjoint arenas of the current batch (these are " +
+                   std::string(bt_.g_state == FADJ_SWEPT ? "swept" : "unseeded or stale") + ")";
+    return -10;
+  }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = reserve_batch_adjoint();
+  if (rc) return rc;
+  const int nbatch = bt_.nbatch;
+  constexpr int kGroup = 32;   // vectors per member of one staged group of the host entry point
+  const int gmax = std::min(nvec, kGroup);
+  if (!dev && nvec > 0 && n > 0 &&
+      (rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, 2 * (size_t)nbatch * (size_t)gmax * (size_t)n, "the staged seed vectors")))
+    return rc;
+  if (!accumulate) bt_.g_state = FADJ_UNSEEDED;
+  const BatchSelinvView s = batch_adjoint_view();
+  bool fits = true;
+  auto seed = [&](int nv, const double* ad, const double* bd, int64_t ldd, bool acc) {
+    if (launch_batch_fadj_seed(stream_, s, d_fatiles_, fa_ntiles_, d_facols_, d_rlist_, d_faporder_, nv, ad, bd, ldd, alpha,
+                               acc, order_flags) < 0)
+      fits = false;
+  };
+  if (dev || nvec == 0 || n == 0) {
+    seed(nvec, a, b, ld, accumulate);
+  } else {
+    // (one stage for all groups: the copies of a group are ordered on the stream behind the launch that read the last)
+    for (int q0 = 0; q0 < nvec && fits; q0 += kGroup) {
+      const int nv = std::min(kGroup, nvec - q0);
+      double* sa = bt_.stage;
+      double* sb = bt_.stage + (int64_t)nbatch * nv * n;
+      for (int m = 0; m < nbatch; ++m) {
+        const int64_t src = ((int64_t)m * nvec + q0) * ld, dst = (int64_t)m * nv * n;
+        if ((rc = copy_vectors_to_device(sa + dst, a + src, ld, nv, "batch seed H2D"))) return rc;
+        if ((rc = copy_vectors_to_device(sb + dst, b + src, ld, nv, "batch seed H2D"))) return rc;
+      }
+      seed(nv, sa, sb, n, accumulate || q0 > 0);
+    }
+  }
+  HIPCHK(hipGetLastError(), "batch factor adjoint seed launch");
+  if ((rc = sync_stream(stream_, "batch factor adjoint seed sync"))) return rc;
+  if (!fits) {
+    feature_err_ = "batch factor adjoint: the seed has more work items for ONE member than a grid holds";
+    return -99;
+  }
+  bt_.g_state = FADJ_SEEDED;
+  return 0;
+}
+
+int Engine::fadj_upload_batch(const double* host_arenas, int64_t ldarena) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (opt_.nranks > 1) return -98;
+  if (pending_ || !host_arenas || ldarena < S_->arena || bt_.nbatch <= 0) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = reserve_batch_adjoint();
+  if (rc) return rc;
+  bt_.g_state = FADJ_UNSEEDED;
+  if (S_->arena > 0)
+    for (int m = 0; m < bt_.nbatch; ++m)
+      HIPCHK(hipMemcpyAsync(bt_.G + (int64_t)m * bt_.lstride, host_arenas + (int64_t)m * ldarena,
+                            sizeof(double) * (size_t)S_->arena, hipMemcpyHostToDevice, stream_), "batch adjoint H2D");
+  if ((rc = sync_stream(stream_, "batch factor adjoint upload sync"))) return rc;
+  bt_.g_state = FADJ_SEEDED;
+  return 0;
+}
+
+int Engine::fadj_download_batch(int member, double* out, int64_t count) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (bt_.g_state == FADJ_UNSEEDED || !out || member < 0 || member >= bt_.nbatch || count < 0) return -10;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  return staged_d2h(out, bt_.G + (int64_t)member * bt_.lstride, sizeof(double) * (size_t)std::min<int64_t>(count, S_->arena));
+}
+
+double* Engine::device_G_batch(int64_t* member_stride) {
+  const bool ok = bt_.g_state != FADJ_UNSEEDED && bt_.nbatch > 0 && bt_.G;
+  if (member_stride) *member_stride = ok ? bt_.lstride : 0;
+  return ok ? bt_.G : nullptr;
+}
+
+int Engine::fadj_sweep_batch(double* gval, int64_t ldout, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (opt_.nranks > 1) return -98;
+  const int64_t nnz = S_->nnzA;
+  if (pending_ || !gval || ldout < nnz || bt_.nbatch <= 0) return -10;
+  if (bt_.g_state != FADJ_SEEDED) {
+    feature_err_ = "batch factor adjoint: the sweep needs freshly seeded adjoint arenas of the current batch (these are " +
+                   std::string(bt_.g_state == FADJ_SWEPT ? "already swept" : "unseeded or stale") + ")";
+    return -10;
+  }
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc = reserve_batch_adjoint();   // (seeded: everything is held; the scratch may have gone with the inversion)
+  if (rc) return rc;
+  if (!dev && nnz > 0 &&
+      (rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)bt_.nbatch * (size_t)nnz, "the gathered gradients")))
+    return rc;
+  bt_.g_state = FADJ_UNSEEDED;   // (a sweep that fails half way leaves nothing to read)
+  const BatchSelinvView s = batch_adjoint_view();
+  const SelinvProgram& P = bt_.siprog;
+  const bool fused = batch_fadj_fused();
+  bool fits = true;
+  int nl = 0;
+  auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
+  for (size_t i = 0; i < P.launches.size() && fits;) {
+    size_t j = i;
+    while (P.launches[j].kind != SI_DIAG) ++j;     // (every step ends with its DIAG launch)
+    const SelinvLaunch& d = P.launches[j];
+    if (fused && bt_.si_fusable[j]) {
+      count(launch_batch_fadj_fused(stream_, s, bt_.siunits + d.first, d.count, bt_.sirows, bt_.sirelpos));
+    } else {
+      for (size_t k = i; k <= j && fits; ++k)
+        count(launch_batch_fadj(stream_, s, P.launches[k], bt_.siunits, bt_.sitiles, bt_.sirows, bt_.sirelpos));
+    }
+    i = j + 1;
+  }
+  if (fits && nnz > 0)
+    count(launch_batch_selinv_pattern(stream_, s, d_map_dst_, d_map_src_, nmap_, dev ? gval : bt_.stage, dev ? ldout : nnz));
+  HIPCHK(hipGetLastError(), "batch factor adjoint launch");
+  if (fits && !dev && nnz > 0 &&
+      (rc = copy_vectors(false, bt_.stage, gval, ldout, bt_.nbatch, "batch factor adjoint D2H", nnz)))
+    return rc;
+  if ((rc = sync_stream(stream_, "batch factor adjoint sync"))) return rc;
+  if (!fits) {
+    feature_err_ = "batch factor adjoint: a launch of the program has more work items for ONE member than a grid holds";
+    return -99;
+  }
+  bt_.fa_launches = nl;
+  bt_.g_state = FADJ_SWEPT;
+  return batch_failed();
+}
+
+// the adjoint arenas back to the pool, the step scratch too unless the inversion holds it
+int Engine::release_factor_adjoint_batch() {
+  feature_err_.clear();
+  if (status_) return status_;
+  bt_.g_state = FADJ_UNSEEDED;
+  bt_.fa_launches = 0;
+  if (!bt_.G) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (int rc = sync_stream(stream_, "batch factor adjoint release")) return rc;
+  release_buffer(bt_.G);
+  bt_.G = nullptr;
+  bt_.g_capacity = 0;
+  if (bt_.siscratch && !bt_.Z) {
+    release_buffer(bt_.siscratch);
+    bt_.siscratch = nullptr;
+    bt_.sc_capacity = 0;
+  }
   return 0;
 }
 

@@ -55,6 +55,10 @@ struct EngineOptions {
 // debug hook (spllt_hip_debug "batch_selinv_fused=0|1"): 0 forces the three-launch form of every step of the
 // batched selected inversion; process-wide, read when an inversion is enqueued
 void set_batch_selinv_fused(bool on);
+// switch (spllt_hip_debug "batch_fadj_fused=0|1"): 1 runs every eligible step of the factor adjoint of a batch as
+// ONE fused launch, 0 (the default: DESIGN.md section 23) all steps in their three-launch form; process-wide, read
+// when a sweep is enqueued
+void set_batch_fadj_fused(bool on);
 // debug: the scratch of the reproducible solve is filled with NaN before every sweep
 void set_rsolve_poison(bool on);
 // debug: the scratch of the factor products is filled with NaN before every direction
@@ -64,6 +68,7 @@ void set_fmult_alloc_fail(int n);
 // debug: the workspace of a sparse solve is filled with NaN before its touched rows are zeroed
 void set_solve_sparse_poison(bool on);
 bool batch_selinv_fused();
+bool batch_fadj_fused();
 
 struct FactorStats {
   double submit_ms = 0;   // host time spent in factor_async
@@ -325,6 +330,27 @@ class Engine {
   int batch_selinv_launches() const { return bt_.si_launches; }
   int release_inverse_batch();
   const SelinvProgram& batch_selinv_program() const { return bt_.siprog; }
+  // ---- reverse-mode derivative of the factors of a batch (batch_adjoint.hip): G_b, one more arena per member
+  // (capacity x lstride), from d loss / d L_b (seeded or uploaded) to d loss / d (P A_b P^T) on every stored
+  // lower position, by the batch's SelinvProgram: tables and step scratch are shared with the batched
+  // inversion (whoever comes first takes them, the last release returns the scratch), Z and G are separate.
+  // The states are those of the single arena, for the whole batch: accumulate needs a seeded arena, the sweep
+  // a freshly seeded one, download a seeded or swept one; factor_batch makes it stale.  Every check happens
+  // before anything is enqueued; every call returns with the stream drained.  The single arena and its state
+  // are not touched.
+  int fadj_batch_state() const { return bt_.g_state; }
+  // vector q of member b at a + (b * nvec + q) * ld (the layout of solve_batch); the host entry stages groups
+  // of at most 32 vectors per member
+  int fadj_seed_batch(int nvec, const double* a, const double* b, int64_t ld, double alpha, bool accumulate,
+                      int order_flags, bool dev);
+  int fadj_upload_batch(const double* host_arenas, int64_t ldarena);   // member b at host_arenas + b * ldarena
+  int fadj_download_batch(int member, double* out, int64_t count);
+  double* device_G_batch(int64_t* member_stride);
+  // gval[b * ldout + k]: nnz doubles per member in the order of val, NaN for a member that is not positive
+  // definite (-20 then, the others are served)
+  int fadj_sweep_batch(double* gval, int64_t ldout, bool dev);
+  int batch_adjoint_launches() const { return bt_.fa_launches; }   // of the last sweep, reader included
+  int release_factor_adjoint_batch();
   double* device_L() { return d_L_; }
   hipStream_t stream() { return stream_; }
   // the stream the pending exchange is packed / unpacked on (its collective belongs there); the chain stream when none is pending
@@ -653,6 +679,7 @@ class Engine {
   int gather_inverse_on_pattern(double* out_dev, double* arena = nullptr);   // arena: null = d_Z_
   // factor adjoint: the arena, the (block column, strip) tiles of the seed kernel and the position -> variable table
   int prepare_fadj();
+  int prepare_fadj_tables();
   int fadj_state_ = FADJ_UNSEEDED;
   double* d_G_ = nullptr;
   double* d_gpat_ = nullptr;       // nnz doubles: the gradient on the analysed pattern (host entry point)
@@ -716,6 +743,12 @@ class Engine {
     int64_t sstride = 0;
     bool z_valid = false;
     int si_launches = 0;
+    int sc_capacity = 0;             // members the step scratch holds (shared: inversion and factor adjoint)
+    // factor adjoint of the batch: the arenas and their state (FadjState, for the whole batch)
+    double* G = nullptr;             // g_capacity x lstride
+    int g_capacity = 0;
+    int g_state = 0;
+    int fa_launches = 0;
   } bt_;
   int prepare_batch();
   int reserve_batch(int nbatch);
@@ -724,6 +757,11 @@ class Engine {
   int prepare_batch_selinv();
   int reserve_batch_inverse(int nbatch);
   BatchSelinvView batch_selinv_view() const;
+  hipError_t reserve_batch_scratch(int nbatch);
+  int reserve_batch_arenas(double** arena, int* capacity, const double* other, int nbatch, const char* feature,
+                           const char* which, bool* retaken);
+  int reserve_batch_adjoint();
+  BatchSelinvView batch_adjoint_view() const;
 };
 
 // The batch program of a pattern: build_program with fixed options (single stream, no fused panels, no

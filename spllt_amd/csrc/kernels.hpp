@@ -227,6 +227,24 @@ int launch_batch_selinv_diag_gather(hipStream_t st, const BatchSelinvView& s, co
 // out[b * ldout + map_src[e]] = Z_b[map_dst[e]]  (A_b^-1 at the entries of the analysed pattern, in the order of val)
 int launch_batch_selinv_pattern(hipStream_t st, const BatchSelinvView& s, const int64_t* map_dst, const int64_t* map_src,
                                 int64_t nmap, double* out, int64_t ldout);
+// the SI_SYMM launch for all members with the diagonal of the gathered symmetric block doubled (the factor
+// adjoint of the batch: s.Z is the adjoint arena)
+int launch_batch_selinv_symm_doubled(hipStream_t st, const BatchSelinvView& s, const SelinvLaunch& l,
+                                     const SelinvUnit* units, const UpdTile* tiles, const SelinvRow* rows,
+                                     const int* relpos);
+// ---- reverse-mode derivative of the factors of a batch (batch_adjoint.hip) ----------------------------
+// The BatchSelinvView with the adjoint arenas in the place of Z: member b's G + b * v.lstride.  Tables, flags
+// and return values as above.
+// launch_fadj_seed for every member: vector q of member b at a[(b * nvec + q) * ld ..], b likewise
+int launch_batch_fadj_seed(hipStream_t st, const BatchSelinvView& s, const UpdTile* tiles, int64_t ntiles,
+                           const FadjCol* cols, const int* rlist, const int* porder, int nvec, const double* a,
+                           const double* b, int64_t ld, double alpha, bool accumulate, int order_flags);
+// one launch of the program (SI_SYMM / SI_SCALE / SI_DIAG) on the adjoint arenas of all members
+int launch_batch_fadj(hipStream_t st, const BatchSelinvView& s, const SelinvLaunch& l, const SelinvUnit* units,
+                      const UpdTile* tiles, const SelinvRow* rows, const int* relpos);
+// one whole adjoint step of units[0 .. count), each with nR <= 64 and nsplit <= 1, in one launch
+int launch_batch_fadj_fused(hipStream_t st, const BatchSelinvView& s, const SelinvUnit* units, int64_t count,
+                            const SelinvRow* rows, const int* relpos);
 // ---- sampled outer product on the analysed pattern (pattern_outer.hip) ---------------------------------
 // out[b * ldout + k] = alpha * sum_q ( u_q[i] v_q[j] + [i != j] u_q[j] v_q[i] ) for entry k = (prow[k], pcol[k]) =
 // (i, j) of the pattern (0-based user variables) and member b, whose vector q is at u + (b * nvec + q) * ldu;

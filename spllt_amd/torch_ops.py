@@ -18,8 +18,11 @@ The factor itself is differentiated by one sweep (spllt_hip_factor_adjoint): wit
 
 restricted to the pattern of L, any number of columns in ONE sweep (the map Lbar -> d loss / d val is linear).
 
-Out of scope: CPU tensors, float32, partitioned handles, sparse right-hand sides, second derivatives, gradients
-through the batch's factors; ``sample`` stays without a gradient to the matrix values (``rsample`` has it).
+The factors of a batch are differentiated the same way, all members in one sweep (spllt_hip_factor_adjoint_batch):
+``factor_apply_batch`` and ``rsample_batch``.
+
+Out of scope: CPU tensors, float32, partitioned handles, sparse right-hand sides, second derivatives; ``sample`` and
+``sample_batch`` stay without a gradient to the matrix values (``rsample`` and ``rsample_batch`` have it).
 """
 import weakref
 
@@ -287,8 +290,8 @@ class SparseCholesky:
         tensor (nbatch, n, nsamp).  vals: (nbatch, nnz); mean: (n,) for all members or (nbatch, n).  Member b draws
         from a noise stream of its own, common_noise=True gives every member the same noise (Factorization.sample_batch).
         The result carries NO gradient, neither to vals nor to mean, like the draws of ``sample`` with respect to val:
-        it is computed under no_grad, mean added on the device.  reproducible=True raises NotImplementedError, like the
-        other batch operations."""
+        it is computed under no_grad, mean added on the device (``rsample_batch`` draws the same bits with the
+        pathwise gradient).  reproducible=True raises NotImplementedError, like the other batch operations."""
         if self.reproducible:
             raise NotImplementedError("sample_batch: the batch has no deterministic form (reproducible=True)")
         self._values(vals, "vals", (None, self.nnz))
@@ -369,6 +372,75 @@ class SparseCholesky:
         self._enter(val)
         x = _RSample.apply(self, val, int(nsamp), int(seed), kind)
         return x if mean is None else x + mean[:, None]
+
+    # ---- the same with the factors of a batch in the graph ---------------------------------------------
+    def _factor_op_batch_inplace(self, work, op):
+        """work: (nbatch, nvec, n) contiguous, overwritten with op(L_b) applied to every vector of member b"""
+        self._sync()
+        with torch.cuda.device(self.device):
+            job = 1 if op in ("L", "Linv") else 2
+            if op in ("L", "Lt"):
+                self.f.factor_mult_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n, job=job)
+            elif self.batch_blocked:
+                self.f.solve_many_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n, job=job)
+            else:
+                self.f.solve_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n, job=job)
+        return work
+
+    def _factor_adjoint_batch(self, a, b, alpha, b_pivot_order=False):
+        """a, b: (nbatch, nvec, n) contiguous -> d/dvals of the seeds alpha sum_q a_bq b_bq^T, (nbatch, nnz): seed
+        passes of 32 vectors per member, ONE sweep for all members, the reader"""
+        nbatch, nvec, step = a.shape[0], a.shape[1], 32
+        if nvec == 0:
+            return torch.zeros((nbatch, self.nnz), dtype=torch.float64, device=self.device)
+        out = torch.empty((nbatch, self.nnz), dtype=torch.float64, device=self.device)
+        keep = []                     # (the passes' copies live until the library has read them)
+        self._sync()
+        with torch.cuda.device(self.device):
+            for q in range(0, nvec, step):
+                aq, bq = a, b
+                if nvec > step:
+                    aq, bq = a[:, q:q + step].contiguous(), b[:, q:q + step].contiguous()
+                    keep.append((aq, bq))
+                    self._sync()
+                self.f.factor_adjoint_seed_batch_dev(aq.data_ptr(), bq.data_ptr(), aq.shape[1], ld=self.n, alpha=alpha,
+                                                     accumulate=q > 0, b_pivot_order=b_pivot_order)
+            self.f.factor_adjoint_batch_dev(out.data_ptr(), ldout=self.nnz)
+        return out
+
+    def factor_apply_batch(self, vals, X, op):
+        """Y_b = op(L_b) X[b] for the Cholesky factors P A(vals[b]) P^T = L_b L_b^T; op: "L", "Lt", "Linv",
+        "Ltinv".  vals: (nbatch, nnz), X: (nbatch, n, nvec), the vectors in the layout of ``factor_apply``.
+        Differentiable in vals and X; the backward pass is one library call for the gradient of X, then seed passes
+        of 32 vectors per member, ONE sweep of the batch's factor adjoint and its reader for vals."""
+        if self.reproducible:
+            raise NotImplementedError("factor_apply_batch: the batch has no deterministic form (reproducible=True)")
+        if op not in self._FACTOR_OPS:
+            raise ValueError(f"op: expected one of {self._FACTOR_OPS}, got {op!r}")
+        self._values(vals, "vals", (None, self.nnz))
+        self._tensor(X, "X", (vals.shape[0], self.n, None), vals.device)
+        self._enter(vals)
+        return _FactorApplyBatch.apply(self, vals, X, op)
+
+    def rsample_batch(self, vals, nsamp, seed=0, kind="precision", mean=None, common_noise=False):
+        """``sample_batch`` with the pathwise gradient: the same bits forward, differentiable in vals and mean
+        ((n,) or (nbatch, n); added outside the Function, its gradient is autograd's).  The noise is not kept: the
+        backward pass draws it again (covariance) or does not need it (precision)."""
+        if self.reproducible:
+            raise NotImplementedError("rsample_batch: the batch has no deterministic form (reproducible=True)")
+        self._values(vals, "vals", (None, self.nnz))
+        if mean is not None:
+            if isinstance(mean, torch.Tensor) and mean.dim() == 2:
+                self._tensor(mean, "mean", (vals.shape[0], self.n), vals.device)
+            else:
+                self._tensor(mean, "mean", (self.n,), vals.device)
+        if kind not in ("precision", "covariance"):
+            raise ValueError(f"kind: expected 'precision' or 'covariance', got {kind!r}")
+        self._enter(vals)
+        x = _RSampleBatch.apply(self, vals, int(nsamp), int(seed), kind, bool(common_noise))
+        if mean is None:
+            return x
+        return x + (mean[:, :, None] if mean.dim() == 2 else mean[None, :, None])
 
     def close(self):
         self.f.close()
@@ -479,6 +551,89 @@ class _RSample(torch.autograd.Function):
                 chol.f.white_noise_dev(z.data_ptr(), ctx.nsamp, ldz=chol.n, seed=ctx.seed)
             gval = chol._factor_adjoint(gt, z[:ctx.nsamp], 1.0, b_pivot_order=True)
         return None, gval, None, None, None
+
+
+def _to_batch_vectors(B):
+    """(nbatch, n, nvec) -> a fresh contiguous (nbatch, nvec, n) work tensor"""
+    return B.detach().transpose(1, 2).clone(memory_format=torch.contiguous_format)
+
+
+class _FactorApplyBatch(torch.autograd.Function):
+    """Y_b = op(L_b) X_b; the table of the module docstring per member"""
+
+    @staticmethod
+    def forward(ctx, chol, vals, X, op):
+        ctx.chol, ctx.op = chol, op
+        ctx.serial = chol._ensure_batch(vals)
+        work = chol._factor_op_batch_inplace(_to_batch_vectors(X), op)
+        # the products need their input, the solves their output
+        ctx.save_for_backward(vals, _to_batch_vectors(X) if op in ("L", "Lt") else work)
+        return work.transpose(1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol, op = ctx.chol, ctx.op
+        vals, kept = ctx.saved_tensors
+        if chol.f.factor_serial(1) != ctx.serial:       # another batch was factorized in between
+            chol._ensure_batch(vals)
+        gt = _to_batch_vectors(grad)
+        xbar = chol._factor_op_batch_inplace(gt.clone(), _FactorApply._ADJOINT[op])
+        gvals = None
+        if ctx.needs_input_grad[1]:
+            if op == "L":
+                gvals = chol._factor_adjoint_batch(gt, kept, 1.0)
+            elif op == "Lt":
+                gvals = chol._factor_adjoint_batch(kept, gt, 1.0)
+            elif op == "Linv":
+                gvals = chol._factor_adjoint_batch(xbar, kept, -1.0)
+            else:
+                gvals = chol._factor_adjoint_batch(kept, xbar, -1.0)
+        return None, gvals, xbar.transpose(1, 2), None
+
+
+class _RSampleBatch(torch.autograd.Function):
+    """x_b = P^T L_b^-T z_b (precision) or P^T L_b z_b (covariance), z_b the white noise of (seed, member's stream,
+    sample); the mean is added outside (its gradient is autograd's)"""
+
+    @staticmethod
+    def forward(ctx, chol, vals, nsamp, seed, kind, common_noise):
+        ctx.chol, ctx.nsamp, ctx.seed, ctx.kind, ctx.common = chol, nsamp, seed, kind, common_noise
+        ctx.serial = chol._ensure_batch(vals)
+        work = torch.empty((vals.shape[0], nsamp, chol.n), dtype=torch.float64, device=chol.device)
+        chol._sync()
+        with torch.cuda.device(chol.device):
+            before = chol.f.set_batch_blocked_solve(chol.batch_blocked)
+            try:
+                chol.f.sample_batch_dev(work.data_ptr(), nsamp, ldx=chol.n, seed=seed, kind=kind, common_noise=common_noise)
+            finally:
+                chol.f.set_batch_blocked_solve(before)
+        if kind == "precision":
+            ctx.save_for_backward(vals, work)
+        else:
+            ctx.save_for_backward(vals)
+        return work.transpose(1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        chol = ctx.chol
+        vals = ctx.saved_tensors[0]
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        if chol.f.factor_serial(1) != ctx.serial:
+            chol._ensure_batch(vals)
+        gt = _to_batch_vectors(grad)
+        if ctx.kind == "precision":      # y = L^-T z: Lbar = -y (L^-1 ybar)^T
+            u = chol._factor_op_batch_inplace(gt, "Linv")
+            gvals = chol._factor_adjoint_batch(ctx.saved_tensors[1], u, -1.0)
+        else:                            # y = L z: Lbar = ybar z^T, z in pivot order as white_noise_batch_dev writes it
+            z = torch.empty((vals.shape[0], max(ctx.nsamp, 1), chol.n), dtype=torch.float64, device=chol.device)
+            chol._sync()
+            with torch.cuda.device(chol.device):
+                chol.f.white_noise_batch_dev(z.data_ptr(), ctx.nsamp, ldz=chol.n, seed=ctx.seed, common_noise=ctx.common)
+            gvals = chol._factor_adjoint_batch(gt, z if ctx.nsamp > 0 else z[:, :0], 1.0, b_pivot_order=True)
+        return None, gvals, None, None, None, None
 
 
 class _LogDet(torch.autograd.Function):
