@@ -204,12 +204,23 @@ _BATCH_ADJOINT = {
     "spllt_hip_batch_adjoint_launches": (i32, [vp]),
     "spllt_hip_release_factor_adjoint_batch": (i32, [vp]),
 }
+# every symbol declared in include/spllt_hip_batch_refine.h: the product A_b x and the refined solves of the members
+# of a batch.  A table of its own for the same reason.
+_BATCH_REFINE = {
+    "spllt_hip_matvec_batch": (i32, [vp, i32, i32, dp, i64, i32, dp, i64, dp, i64]),
+    "spllt_hip_matvec_batch_dev": (i32, [vp, i32, i32, vp, i64, i32, vp, i64, vp, i64, i32]),
+    "spllt_hip_solve_refined_batch": (i32, [vp, i32, dp, i64, i32, dp, i64, i32, f64, i32, ip, dp]),
+    "spllt_hip_solve_refined_batch_dev": (i32, [vp, i32, vp, i64, i32, vp, i64, i32, f64, i32, ip, dp]),
+    "spllt_hip_solve_refined_batch_info": (i32, [vp, i64p]),
+    "spllt_hip_release_refine_batch": (i32, [vp]),
+}
 del vp, vpp, i32, i64, u64, f64, cstr, long, ip, i64p, dp, fp, longp, ipp, dpp, opt, inf   # (names of the table only)
 IFACE_SYMBOLS = list(_IFACE)
 HIP_SYMBOLS = list(_HIP)
 BATCH_MULT_SYMBOLS = list(_BATCH_MULT)
 BATCH_SOLVE_MANY_SYMBOLS = list(_BATCH_SOLVE_MANY)
 BATCH_ADJOINT_SYMBOLS = list(_BATCH_ADJOINT)
+BATCH_REFINE_SYMBOLS = list(_BATCH_REFINE)
 
 _lib = None
 
@@ -224,7 +235,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C spllt_amd/csrc`. spllt_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT):
+    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -1062,6 +1062,105 @@ class Factorization:
         self._call("spllt_hip_release_solve_many_batch", self.fkeep)
         return self
 
+    # ---- the product and the refined solves for the members of a batch (include/spllt_hip_batch_refine.h) -----
+    def _batch_values(self, vals, where):
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if vals.ndim != 2 or vals.shape[1] != self.nnz:
+            raise ValueError(f"{where}: vals must have shape (B, nnz) = (B, {self.nnz}), not {vals.shape}")
+        return vals
+
+    def _batch_vectors(self, X, nb, where):
+        """a C-ordered copy of X, shape (B, n) or (B, nvec, n) with B = nb, and nvec"""
+        x = np.array(X, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (2, 3):
+            raise ValueError(f"{where}: the vectors must have shape (B, n) or (B, nvec, n)")
+        if x.shape[-1] != self.n:
+            raise ValueError(f"{where}: the vectors have length {x.shape[-1]}, n = {self.n}")
+        if x.shape[0] != nb:
+            raise ValueError(f"{where}: vectors for {x.shape[0]} members, values for {nb}")
+        return x, (1 if x.ndim == 2 else x.shape[1])
+
+    def matvec_batch(self, vals, X):
+        """spllt_hip_matvec_batch: y_b = A_b x_b on the device with A_b = (the analysed pattern, vals[b]); vals of
+        shape (B, nnz), X of shape (B, n) or (B, nvec, n), like solve_batch.  Member b's product is bit-identical
+        to matvec(vals[b], ...), and two calls return bit-identical results.  Needs neither a factor nor a batch."""
+        vals = self._batch_values(vals, "matvec_batch")
+        x, nvec = self._batch_vectors(X, vals.shape[0], "matvec_batch")
+        y = np.empty_like(x)
+        ld = max(1, self.n)
+        self._call("spllt_hip_matvec_batch", self.fkeep, vals.shape[0], self.nnz, _dp(vals), max(1, self.nnz), nvec,
+                   _dp(x), ld, _dp(y), ld)
+        return y
+
+    def matvec_batch_dev(self, val_dev_ptr, nbatch, x_dev_ptr, y_dev_ptr, nvec, ldval=None, ldx=None, ldy=None,
+                         pivot_order=False):
+        """spllt_hip_matvec_batch_dev: the product on device arrays (member b's values at val + b*ldval, vector q
+        of member b at x[(b*nvec + q)*ldx .. + n), y alike; pivot_order as solve_many_dev; x and y must not
+        overlap)."""
+        self._call("spllt_hip_matvec_batch_dev", self.fkeep, int(nbatch), self.nnz, C.c_void_p(val_dev_ptr),
+                   int(self.nnz if ldval is None else ldval), int(nvec), C.c_void_p(x_dev_ptr),
+                   int(self.n if ldx is None else ldx), C.c_void_p(y_dev_ptr), int(self.n if ldy is None else ldy),
+                   1 if pivot_order else 0)
+        return self
+
+    def solve_refined_batch(self, vals, B, method="pcg", tol=1e-14, max_iter=50):
+        """spllt_hip_solve_refined_batch on a copy of B (shape (B, n) or (B, nrhs, n), like solve_batch): solve
+        A_b x = b for A_b = (pattern, vals[b]) with the factor of member b of the last factor_batch as
+        preconditioner, to the backward error tol, all members in one set of launches.  method "ir" or "pcg".
+        Returns (x, iterations, error) of shapes (B, nrhs, n), (B, nrhs) and (B, nrhs): as solve_refined per pair.
+        A member that is not positive definite keeps its vectors, with iterations 0 and error NaN.
+        self.refine_status keeps the call's return value (0: every pair reached tol, 1: at least one did not,
+        -20: a member is not positive definite -- the others were served; other negative flags raise)."""
+        if method not in self._METHODS:
+            raise SplltError("spllt_hip_solve_refined_batch", -10, "method is not 'ir' or 'pcg'")
+        vals = self._batch_values(vals, "solve_refined_batch")
+        nb = self._batch_count()
+        if nb > 0 and vals.shape[0] != nb:
+            raise ValueError(f"solve_refined_batch: values for {vals.shape[0]} members, the last batch has {nb}")
+        x, nrhs = self._batch_vectors(B, vals.shape[0], "solve_refined_batch")
+        x = x.reshape(vals.shape[0], nrhs, self.n)
+        it = np.zeros(max(1, x.shape[0] * nrhs), dtype=np.int32)
+        err = np.zeros(max(1, x.shape[0] * nrhs), dtype=np.float64)
+        rc = self.lib.spllt_hip_solve_refined_batch(self.fkeep, self.nnz, _dp(vals), max(1, self.nnz), nrhs, _dp(x),
+                                                    max(1, self.n), self._METHODS[method], float(tol), int(max_iter),
+                                                    _ip(it), _dp(err))
+        self.refine_status = rc
+        if rc < 0 and rc not in self._BATCH_OK:
+            raise SplltError("spllt_hip_solve_refined_batch", rc, self.last_error())
+        shape = (x.shape[0], nrhs)
+        return x, it[:x.shape[0] * nrhs].reshape(shape), err[:x.shape[0] * nrhs].reshape(shape)
+
+    def solve_refined_batch_dev(self, val_dev_ptr, x_dev_ptr, nrhs, ldval=None, ldx=None, method="pcg", tol=1e-14,
+                                max_iter=50):
+        """spllt_hip_solve_refined_batch_dev: values and vectors on the device (user order, in place), the layout
+        of solve_batch_dev.  Returns (status, iterations, error) with arrays of shape (B, nrhs); status 0: every
+        pair reached tol, 1: at least one did not, -20: a member is not positive definite."""
+        if method not in self._METHODS:
+            raise SplltError("spllt_hip_solve_refined_batch_dev", -10, "method is not 'ir' or 'pcg'")
+        if int(nrhs) < 0:
+            raise ValueError("solve_refined_batch_dev: nrhs < 0")
+        nb = max(self._batch_count(), 0)
+        it = np.zeros(max(1, nb * nrhs), dtype=np.int32)
+        err = np.zeros(max(1, nb * nrhs), dtype=np.float64)
+        rc = self._call("spllt_hip_solve_refined_batch_dev", self.fkeep, self.nnz, C.c_void_p(val_dev_ptr),
+                        int(self.nnz if ldval is None else ldval), int(nrhs), C.c_void_p(x_dev_ptr),
+                        int(self.n if ldx is None else ldx), self._METHODS[method], float(tol), int(max_iter),
+                        _ip(it), _dp(err), ok=self._BATCH_OK)
+        self.refine_status = rc
+        return rc, it[:nb * nrhs].reshape(nb, nrhs), err[:nb * nrhs].reshape(nb, nrhs)
+
+    def solve_refined_batch_info(self):
+        """of the refined batch solve: pass width the storage holds (0: none held), passes and kernel launches of
+        the last call (this family's and the sweeps'), bytes of the storage"""
+        out = np.zeros(4, dtype=np.int64)
+        self._call("spllt_hip_solve_refined_batch_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        return dict(zip(("width", "passes", "launches", "workspace_bytes"), (int(v) for v in out)))
+
+    def release_refine_batch(self):
+        """The work arrays of the refined batch solve back to the device pool."""
+        self._call("spllt_hip_release_refine_batch", self.fkeep)
+        return self
+
     # ---- batched selected inversion -------------------------------------------
     def selected_inverse_batch(self):
         """spllt_hip_selected_inverse_batch: Z_b on the pattern of L for every member of the last batch.

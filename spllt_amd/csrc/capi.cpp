@@ -31,6 +31,7 @@
 #include "spllt_hip_batch_mult.h"
 #include "spllt_hip_batch_adjoint.h"
 #include "spllt_hip_batch_solve_many.h"
+#include "spllt_hip_batch_refine.h"
 #include "symbolic.hpp"
 
 using namespace spx;
@@ -1218,6 +1219,85 @@ int spllt_hip_solve_refined_dev(void* fkeep, int nnz, const double* val_dev, int
                             "spllt_hip_solve_refined_dev");
 }
 
+// ---- the product and the refined solves for the members of a batch (spllt_hip_batch_refine.h) --------
+// what is wrong with the values of a batch call, or null
+static const char* batch_values_bad(const Fkeep* f, int nnz, const double* val, int64_t ldval) {
+  if (!val) return "the array of values is null";
+  if ((int64_t)nnz != f->S->nnzA) return "nnz does not match the analysed pattern";
+  if (ldval < nnz) return "ldval < nnz";
+  return nullptr;
+}
+
+static int matvec_batch_impl(void* fkeep, int nbatch, int nnz, const double* val, int64_t ldval, int nvec, const double* x,
+                             int64_t ldx, double* y, int64_t ldy, bool dev, bool pivot_order, const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!val) bad = "the array of values is null";
+  else if (!x || !y) bad = "a vector array is null";
+  else if (nbatch < 0) bad = "nbatch < 0";
+  else if (nvec < 0) bad = "nvec < 0";
+  else if ((bad = batch_values_bad(f, nnz, val, ldval))) {}
+  else if (ldx < f->S->n) bad = "ldx < n";
+  else if (ldy < f->S->n) bad = "ldy < n";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | ENGINE | (nvec == 0 || nbatch == 0 ? EMPTY : 0))) return done(rc);
+  return leave(f, f->eng->matvec_batch(val, ldval, nbatch, nvec, x, ldx, y, ldy, dev, pivot_order));
+}
+
+int spllt_hip_matvec_batch(void* fkeep, int nbatch, int nnz, const double* val_host, int64_t ldval, int nvec,
+                           const double* x_host, int64_t ldx, double* y_host, int64_t ldy) {
+  return matvec_batch_impl(fkeep, nbatch, nnz, val_host, ldval, nvec, x_host, ldx, y_host, ldy, false, false,
+                           "spllt_hip_matvec_batch");
+}
+
+int spllt_hip_matvec_batch_dev(void* fkeep, int nbatch, int nnz, const double* val_dev, int64_t ldval, int nvec,
+                               const double* x_dev, int64_t ldx, double* y_dev, int64_t ldy, int pivot_order) {
+  return matvec_batch_impl(fkeep, nbatch, nnz, val_dev, ldval, nvec, x_dev, ldx, y_dev, ldy, true, pivot_order != 0,
+                           "spllt_hip_matvec_batch_dev");
+}
+
+// the rungs of solve_batch_impl and of solve_refined_impl
+static int solve_refined_batch_impl(void* fkeep, int nnz, const double* val, int64_t ldval, int nrhs, double* x, int64_t ldx,
+                                    int method, double tol, int max_iter, int* iterations, double* error, bool dev,
+                                    const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (!val) bad = "the array of values is null";
+  else if (!x) bad = "the array of right-hand sides is null";
+  else if (nrhs < 0) bad = "nrhs < 0";
+  else if ((bad = batch_values_bad(f, nnz, val, ldval))) {}
+  else if (ldx < f->S->n) bad = "ldx < n";
+  else if (method != 0 && method != 1) bad = "method is not 0 (refinement) or 1 (PCG)";
+  else if (!(tol > 0.0)) bad = "tol is not positive";
+  else if (max_iter < 0) bad = "max_iter < 0";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (nrhs == 0) return 0;
+  int rc = f->eng->solve_refined_batch(val, ldval, nrhs, x, ldx, dev, method, tol, max_iter, iterations, error);
+  if (rc == 1)   // rc 1 of the refined solve: not an error, the vectors hold their best iterates
+    return fail(f, what, "at least one vector did not reach tol (error[] says which)", 1);
+  return batch_mult_leave(f, what, rc, "the vectors of the members that are not positive definite were left unchanged");
+}
+
+int spllt_hip_solve_refined_batch(void* fkeep, int nnz, const double* val_host, int64_t ldval, int nrhs, double* x_host,
+                                  int64_t ldx, int method, double tol, int max_iter, int* iterations, double* error) {
+  return solve_refined_batch_impl(fkeep, nnz, val_host, ldval, nrhs, x_host, ldx, method, tol, max_iter, iterations, error,
+                                  false, "spllt_hip_solve_refined_batch");
+}
+
+int spllt_hip_solve_refined_batch_dev(void* fkeep, int nnz, const double* val_dev, int64_t ldval, int nrhs, double* x_dev,
+                                      int64_t ldx, int method, double tol, int max_iter, int* iterations, double* error) {
+  return solve_refined_batch_impl(fkeep, nnz, val_dev, ldval, nrhs, x_dev, ldx, method, tol, max_iter, iterations, error,
+                                  true, "spllt_hip_solve_refined_batch_dev");
+}
+
+int spllt_hip_solve_refined_batch_info(void* fkeep, int64_t out[4]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 4; ++i) out[i] = f->eng ? f->eng->solve_refined_batch_info()[i] : 0;
+  return 0;
+}
+
 // ---- low-rank update / downdate of the factor ------------------------------------------------------
 int64_t spllt_hip_updown_plan(void* fkeep, int k, const int* wptr, const int* wrow, int32_t* bcols, int64_t capacity) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
@@ -1687,6 +1767,7 @@ int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::relea
 int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::release_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_solve_many_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_many_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_refine_batch(void* fkeep) { return release(fkeep, &Engine::release_refine_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse_batch(void* fkeep) { return release(fkeep, &Engine::release_inverse_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_adjoint_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_adjoint_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse(void* fkeep) { return release(fkeep, &Engine::release_inverse, WAIT_IGNORE | LENIENT); }

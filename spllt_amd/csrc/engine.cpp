@@ -2158,20 +2158,24 @@ int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int jo
   const int* order = pivot_order ? nullptr : d_order_;
   // (a launch whose work items for one member overflow a grid: every launch has at most as many work items as
   // the pack, which is checked first -- n / 256 blocks against the block columns and strips of n rows)
-  if (launch_batch_pack(stream_, v, false, xd, ld, nrhs, order, n, bt_.Y) < 0) {
+  int nl = launch_batch_pack(stream_, v, false, xd, ld, nrhs, order, n, bt_.Y);
+  if (nl < 0) {
     feature_err_ = "batch solve: nrhs vectors of one member are more work items than a grid holds";
     return -99;
   }
   bool fits = true;
   auto run = [&](const std::vector<SolveLaunch>& ls) {
-    for (const SolveLaunch& l : ls)
-      if (launch_batch_solve(stream_, v, l.kind, bt_.slist, bt_.stiles, l.first, l.count, bt_.sunits, d_rlist_, bt_.Y,
-                             nrhs, n) < 0)
-        fits = false;
+    for (const SolveLaunch& l : ls) {
+      const int k = launch_batch_solve(stream_, v, l.kind, bt_.slist, bt_.stiles, l.first, l.count, bt_.sunits, d_rlist_,
+                                       bt_.Y, nrhs, n);
+      if (k < 0) fits = false;
+      else nl += k;
+    }
   };
   if (job == 0 || job == 1) run(bt_.sprog.fwd);
   if (job == 0 || job == 2) run(bt_.sprog.bwd);
-  launch_batch_pack(stream_, v, true, xd, ld, nrhs, order, n, bt_.Y);
+  nl += std::max(0, launch_batch_pack(stream_, v, true, xd, ld, nrhs, order, n, bt_.Y));
+  bt_.solve_launches = nl;   // (read by the refined solve of the batch)
   HIPCHK(hipGetLastError(), "batch solve launch");
   // (the vectors of a failed member come back as they went: nothing on the device touched them)
   if (!on_device && (rc = copy_vectors(false, bt_.stage, x, ldx, (int64_t)nvec, "batch x D2H"))) return rc;
@@ -2214,11 +2218,12 @@ int Engine::release_batch() {
   bt_.z_valid = false;
   bt_.g_state = FADJ_UNSEEDED;
   bt_.fa_launches = 0;
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bt_.siscratch && !bm_ready_ && !d_bmmean_ && !bsm_ready_) { bt_.nbatch = 0; return 0; }
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bt_.siscratch && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brf_ready_ && !d_brfval_) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
   drop_solve_many_batch();    // (... and that of the blocked solve)
+  drop_refine_batch();        // (... and those of the refined solves)
   for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out, (void*)bt_.Y, (void*)bt_.stage,
                   (void*)bt_.Z, (void*)bt_.G, (void*)bt_.siscratch})
     if (p) release_buffer(p);

@@ -246,6 +246,22 @@ class Engine {
   int solve_refined(const double* val, int nrhs, double* x, int64_t ldx, bool dev, int method, double tol,
                     int max_iter, int* iterations, double* error);
   int release_refine();     // operator tables and work vectors back to the pool
+  // ---- the same for the members of a batch (batch_refine.hip).  Vector q of member b at (b * nvec + q) * ld, the
+  // layout of solve_batch; member b's values at val + b * ldval.  The product takes nbatch from the caller and
+  // needs neither a factor nor a batch; the refined solve serves the members of the LAST batch with their
+  // factors as M^-1 (solve_batch below BRF_BLOCKED_MIN vectors per member in a pass, solve_many_batch from there
+  // on: measured, from 1).  Passes of at most 32 vectors per member (16 / 8 when the six work arrays do not fit; else -1 with
+  // nothing kept).  iterations / error: nbatch * nrhs entries in the order of the vectors, either may be null.
+  // A member without a factor: nothing of it is read or written, iterations 0, error NaN, -20 after the others
+  // were served.  Else 0: every pair reached tol, 1: at least one did not.
+  int matvec_batch(const double* val, int64_t ldval, int nbatch, int nvec, const double* x, int64_t ldx, double* y,
+                   int64_t ldy, bool dev, bool pivot_order);
+  int solve_refined_batch(const double* val, int64_t ldval, int nrhs, double* x, int64_t ldx, bool dev, int method,
+                          double tol, int max_iter, int* iterations, double* error);
+  // pass width the workspace holds (0: none held), passes and kernel launches of the last solve_refined_batch (its
+  // own kernels and those of the sweeps, whichever route M^-1 took), bytes of the workspace
+  const int64_t* solve_refined_batch_info() const { return brf_info_; }
+  int release_refine_batch();
   bool factored() const { return factored_ && !ud_invalid_; }
   // ---- low-rank update / downdate (updown.hip, single GPU): the factor of P (A + sign W W^T) P^T in place of
   // the current one, same layout, the dinv slots of the visited block columns rebuilt -- every solve then works
@@ -641,6 +657,30 @@ class Engine {
   int refine_readback(int nv, std::vector<double>& out);
   int refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol, int max_iter,
                    int* iterations, double* error);
+  // the operator tables: shared by the single handle (refine_ready_) and the batch (brf_ready_), given back with
+  // the last of the two
+  hipError_t ensure_refine_tables();
+  void drop_refine_tables();
+  bool rf_tables_ = false;
+  // refined solves of a batch: six work arrays, partials, scalars and states for brf_capacity_ members
+  int prepare_refine_batch(int members);
+  void drop_refine_batch();
+  int refine_batch_apply_factor(double* v, int nv, int64_t* launches);
+  int refine_batch_pass(const double* dval, int64_t ldval, int nv, double* x, int64_t xstride, int64_t ldx, bool dev,
+                        int done, int nrhs, int method, double tol, int max_iter, int* iterations, double* error,
+                        int64_t* launches, int* worst);
+  bool brf_ready_ = false;
+  int brf_rb_ = 0;                 // pass width the work arrays hold (32, 16 or 8)
+  int brf_capacity_ = 0;           // members they hold
+  double* d_brfwork_ = nullptr;    // 6 x capacity x brf_rb_ x n: b, x, r, p, q, best x
+  double* d_brfpart_ = nullptr;
+  double* d_brfds_ = nullptr;      // amax[capacity], sigma[capacity], then the scalars of a pass (refine.hpp)
+  int* d_brfis_ = nullptr;
+  double* d_brfval_ = nullptr;     // the values of a host entry point
+  size_t brf_val_elems_ = 0;
+  double* d_brfmv_ = nullptr;      // the product's own workspace: three arrays of members x min(nvec, 32) x n
+  size_t brf_mv_elems_ = 0;
+  int64_t brf_info_[4] = {0, 0, 0, 0};
   bool factored_ = false;          // a factorization has been enqueued on this engine
   bool refine_ready_ = false;
   char* d_rftab_ = nullptr;        // one allocation behind the four tables below
@@ -727,6 +767,7 @@ class Engine {
     std::vector<int> hflag_pending;  // destination of the flags' D2H copy (outlives a wait that fails)
     bool own_init = false;           // init_* are the batch's own upload (else the engine's d_init_* tables)
     int launches = 0;
+    int solve_launches = 0;          // kernel launches of the last solve_batch
     int member_fast = 0;
     // batched selected inversion: program and tables (once per engine), Z arenas and scratch (per batch)
     bool si_ready = false;

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <climits>
 #include <cstdlib>
+#include <limits>
 
 #include "engine.hpp"
 #include "engine_detail.hpp"
@@ -1155,35 +1156,55 @@ int Engine::solve_many_batch(double* x, bool on_device, int nrhs, int64_t ldx, i
 // ---- refined solves --------------------------------------------------------------------------------
 // Operator tables (once per engine) and the work vectors of one group, all or nothing: a failed allocation
 // gives back what it got and leaves the factor and every other solve usable.
+hipError_t Engine::ensure_refine_tables() {
+  if (rf_tables_) return hipSuccess;
+  const Symbolic& S = *S_;
+  std::vector<int64_t> rowptr;
+  std::vector<int> col, src, rows;
+  build_matvec_tables(S, rowptr, col, src);
+  // rows by length: at most 16 entries -> 4 lanes per row, at most 128 -> 16 lanes, longer -> a wavefront
+  rows.reserve((size_t)S.n);
+  for (int c = 0; c < 3; ++c) {
+    rf_nrows_[c] = 0;
+    for (int p = 0; p < S.n; ++p) {
+      const int64_t len = rowptr[(size_t)p + 1] - rowptr[(size_t)p];
+      const int cls = len <= 16 ? 0 : (len <= 128 ? 1 : 2);
+      if (cls == c) { rows.push_back(p); ++rf_nrows_[c]; }
+    }
+  }
+  TableStager tab;
+  tab.add(&d_rfrowptr_, rowptr);
+  tab.add(&d_rfcol_, col);
+  tab.add(&d_rfsrc_, src);
+  tab.add(&d_rfrows_, rows);
+  hipError_t e = tab.commit(&d_rftab_, [this](void** q, size_t b) { return dalloc(q, b); });
+  if (e == hipSuccess) e = ensure_order();
+  if (e != hipSuccess) {
+    if (d_rftab_) release_buffer(d_rftab_);
+    d_rftab_ = nullptr;
+    return e;
+  }
+  rf_tables_ = true;
+  return hipSuccess;
+}
+
+void Engine::drop_refine_tables() {
+  if (refine_ready_ || brf_ready_) return;   // (the other of the two still works on them)
+  if (d_rftab_) release_buffer(d_rftab_);
+  d_rftab_ = nullptr;
+  rf_tables_ = false;
+}
+
 int Engine::prepare_refine(bool host_val) {
   const Symbolic& S = *S_;
   const size_t n1 = (size_t)std::max(1, S.n);
   hipError_t e = hipSuccess;
   size_t want = 0;
   if (!refine_ready_) {
-    std::vector<int64_t> rowptr;
-    std::vector<int> col, src, rows;
-    build_matvec_tables(S, rowptr, col, src);
-    // rows by length: at most 16 entries -> 4 lanes per row, at most 128 -> 16 lanes, longer -> a wavefront
-    rows.reserve((size_t)S.n);
-    for (int c = 0; c < 3; ++c) {
-      rf_nrows_[c] = 0;
-      for (int p = 0; p < S.n; ++p) {
-        const int64_t len = rowptr[(size_t)p + 1] - rowptr[(size_t)p];
-        const int cls = len <= 16 ? 0 : (len <= 128 ? 1 : 2);
-        if (cls == c) { rows.push_back(p); ++rf_nrows_[c]; }
-      }
-    }
+    e = ensure_refine_tables();
     RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
     const size_t slots = (size_t)std::max(std::max(spmv_slots(op), vec_slots(S.n)), RF_AMAX_WG);
-    TableStager tab;
-    tab.add(&d_rfrowptr_, rowptr);
-    tab.add(&d_rfcol_, col);
-    tab.add(&d_rfsrc_, src);
-    tab.add(&d_rfrows_, rows);
-    e = tab.commit(&d_rftab_, [this](void** q, size_t b) { return dalloc(q, b); });
     want = sizeof(double) * 6 * RF_G * n1;
-    if (e == hipSuccess) e = ensure_order();
     if (e == hipSuccess) e = dalloc((void**)&d_rfwork_, want);
     if (e == hipSuccess) e = dalloc((void**)&d_rfpart_, sizeof(double) * 2 * RF_G * slots);
     if (e == hipSuccess) e = dalloc((void**)&d_rfds_, sizeof(double) * RF_DS);
@@ -1199,9 +1220,10 @@ int Engine::prepare_refine(bool host_val) {
   if (e != hipSuccess) {
     (void)hipGetLastError();
     if (!refine_ready_) {
-      for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_})
+      for (void* p : {(void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_})
         if (p) release_buffer(p);
-      d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr;
+      d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr;
+      drop_refine_tables();
     }
     feature_err_ = "refined solve: not enough device memory for the operator and the work vectors (" +
                    std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
@@ -1214,10 +1236,11 @@ int Engine::prepare_refine(bool host_val) {
 int Engine::release_refine() {
   int rc;
   if (!enter_release(refine_ready_ || d_rfval_, "refine release", &rc)) return rc;
-  for (void* p : {(void*)d_rftab_, (void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_, (void*)d_rfval_})
+  for (void* p : {(void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_, (void*)d_rfval_})
     if (p) release_buffer(p);
-  d_rftab_ = nullptr; d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr; d_rfval_ = nullptr;
+  d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr; d_rfval_ = nullptr;
   refine_ready_ = false;
+  drop_refine_tables();
   return 0;
 }
 
@@ -1399,6 +1422,336 @@ int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, b
     done += nv;
   }
   return worst;
+}
+
+// ---- refined solves for the members of a batch ---------------------------------------------------------
+void Engine::drop_refine_batch() {
+  for (void* p : {(void*)d_brfwork_, (void*)d_brfpart_, (void*)d_brfds_, (void*)d_brfis_, (void*)d_brfval_, (void*)d_brfmv_})
+    if (p) release_buffer(p);
+  d_brfwork_ = d_brfpart_ = d_brfds_ = d_brfval_ = d_brfmv_ = nullptr;
+  d_brfis_ = nullptr;
+  brf_val_elems_ = brf_mv_elems_ = 0;
+  brf_capacity_ = 0;
+  brf_rb_ = 0;
+  const bool had = brf_ready_;
+  brf_ready_ = false;
+  brf_info_[0] = brf_info_[3] = 0;
+  (void)had;
+  drop_refine_tables();   // (also those a product alone uploaded; kept while the single handle's refined solve is ready)
+}
+
+// the operator tables (those of the single handle) and the storage of a pass for `members` members: six work
+// arrays, the partial sums, the scalars and the states, all or nothing; 32 vectors per member, else 16, else 8
+int Engine::prepare_refine_batch(int members) {
+  if (brf_ready_ && members <= brf_capacity_) return 0;
+  if (brf_ready_) drop_refine_batch();   // (a larger batch: everything again)
+  const size_t n1 = (size_t)std::max(1, S_->n), nb = (size_t)members;
+  // (a failure here leaves the batch, its solves and the single factorization usable)
+  hipError_t e = ensure_refine_tables();
+  size_t want = 0;
+  if (e == hipSuccess) {
+    const RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+    const size_t slots = (size_t)std::max(spmv_slots(op), vec_slots(S_->n));
+    for (int rb = RF_G; rb >= 8; rb /= 2) {
+      const size_t np = nb * (size_t)rb;
+      const size_t wb = sizeof(double) * 6 * np * n1;
+      const size_t pb = sizeof(double) * std::max(2 * slots * np, nb * (size_t)RF_AMAX_WG);
+      const size_t db = sizeof(double) * (2 * nb + BRF_DS * np), ib = sizeof(int) * (RF_IS / RF_G) * np;
+      want = wb + pb + db + ib;
+      e = fmult_take((void**)&d_brfwork_, wb);
+      if (e == hipSuccess) e = dalloc((void**)&d_brfpart_, pb);
+      if (e == hipSuccess) e = dalloc((void**)&d_brfds_, db);
+      if (e == hipSuccess) e = dalloc((void**)&d_brfis_, ib);
+      if (e == hipSuccess) e = hipMemsetAsync(d_brfds_, 0, db, stream_);
+      if (e == hipSuccess) e = hipMemsetAsync(d_brfis_, 0, ib, stream_);
+      if (e == hipSuccess) { brf_rb_ = rb; break; }
+      (void)hipGetLastError();
+      for (void* p : {(void*)d_brfwork_, (void*)d_brfpart_, (void*)d_brfds_, (void*)d_brfis_})
+        if (p) release_buffer(p);
+      d_brfwork_ = d_brfpart_ = d_brfds_ = nullptr;
+      d_brfis_ = nullptr;
+      if (alloc_code(e) != -1) break;   // (out of memory: once more with half of it)
+    }
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    drop_refine_tables();
+    feature_err_ = "solve_refined_batch: not enough device memory for the operator and six work arrays of 8 vectors for "
+                   "each of " + std::to_string(members) + " members (" + std::to_string(want >> 20) + " MiB): " +
+                   hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  brf_capacity_ = members;
+  brf_ready_ = true;
+  brf_info_[0] = brf_rb_;
+  brf_info_[3] = (int64_t)want;
+  return 0;
+}
+
+int Engine::release_refine_batch() {
+  int rc;
+  // (rf_tables_ without a ready user: the tables of a product that needed no workspace)
+  if (!enter_release(brf_ready_ || d_brfval_ || d_brfmv_ || (rf_tables_ && !refine_ready_), "refine_batch release", &rc)) return rc;
+  drop_refine_batch();
+  return 0;
+}
+
+namespace {
+// from this many vectors per member in a pass on, M^-1 is the blocked solve (experiment knob of
+// scripts/refine_batch_bench.py: SPLLT_BRF_BLOCKED_MIN)
+int brf_blocked_min() {
+  if (const char* env = std::getenv("SPLLT_BRF_BLOCKED_MIN")) return std::max(1, std::atoi(env));
+  return BRF_BLOCKED_MIN;
+}
+}  // namespace
+
+int Engine::matvec_batch(const double* val, int64_t ldval, int nbatch, int nvec, const double* x, int64_t ldx, double* y,
+                         int64_t ldy, bool dev, bool pivot_order) {
+  const int n = S_->n;
+  const int64_t nnz = S_->nnzA;
+  int rc;
+  if (!enter(val && x && y && nbatch >= 0 && nvec >= 0 && ldval >= nnz && ldx >= n && ldy >= n,
+             nbatch == 0 || nvec == 0 || n == 0, &rc))
+    return rc;
+  // device vectors in pivot order need the tables only; else a workspace of the product's own (permuted x, y, and
+  // the staged vectors of a host call), one pass of at most 32 vectors per member -- not the solver's six arrays
+  const bool direct = dev && pivot_order;
+  const int cap = RF_G;
+  if (hipError_t e = ensure_refine_tables()) {
+    (void)hipGetLastError();
+    feature_err_ = std::string("matvec_batch: the operator tables could not be uploaded: ") + hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  const size_t gcap = (size_t)nbatch * (size_t)std::min(cap, nvec) * (size_t)n;
+  if (!direct && (rc = grow_batch_buffer(&d_brfmv_, &brf_mv_elems_, (dev ? 2 : 3) * gcap, "the workspace of the product"))) {
+    drop_refine_tables();
+    return rc;
+  }
+  const double* dval = val;
+  int64_t ldv = ldval;
+  if (!dev) {
+    if ((rc = grow_batch_buffer(&d_brfval_, &brf_val_elems_, (size_t)nbatch * (size_t)std::max<int64_t>(nnz, 1), "the staged values")))
+      return rc;
+    if (nnz > 0 && (rc = copy_vectors_to_device(d_brfval_, val, ldval, nbatch, "matvec_batch val H2D", nnz))) return rc;
+    dval = d_brfval_;
+    ldv = nnz;
+  }
+  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  BrfTally t;
+  for (int done = 0; done < nvec && t.fits;) {
+    const int nv = std::min(cap, nvec - done);
+    const BrfView v{nullptr, nbatch, nv, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t gn = (size_t)nbatch * (size_t)nv * (size_t)n;
+    double *wb = d_brfmv_, *wr = wb ? wb + gn : nullptr, *wq = wb && !dev ? wb + 2 * gn : nullptr;
+    const double* xg = x + (int64_t)done * ldx;
+    double* yg = y + (int64_t)done * ldy;
+    if (direct) {
+      t.add(launch_bspmv(stream_, op, v, dval, ldv, xg, (int64_t)nvec * ldx, ldx, nullptr, yg, (int64_t)nvec * ldy, ldy,
+                         nullptr, 0, false));
+    } else {
+      if (!dev)
+        for (int b = 0; b < nbatch; ++b)
+          if ((rc = copy_vectors_to_device(wq + (size_t)b * nv * n, xg + (int64_t)b * nvec * ldx, ldx, nv, "matvec_batch x H2D")))
+            return rc;
+      // (the permutation reads its source only)
+      t.add(dev ? launch_brf_permute(stream_, v, false, const_cast<double*>(xg), (int64_t)nvec * ldx, ldx, d_order_, n, wb)
+                : launch_brf_permute(stream_, v, false, wq, (int64_t)nv * n, n, d_order_, n, wb));
+      t.add(launch_bspmv(stream_, op, v, dval, ldv, wb, (int64_t)nv * n, n, nullptr, wr, (int64_t)nv * n, n, nullptr, 0, false));
+      t.add(dev ? launch_brf_permute(stream_, v, true, yg, (int64_t)nvec * ldy, ldy, d_order_, n, wr)
+                : launch_brf_permute(stream_, v, true, wq, (int64_t)nv * n, n, d_order_, n, wr));
+      HIPCHK(hipGetLastError(), "matvec_batch launch");
+      if (!dev && t.fits) {
+        for (int b = 0; b < nbatch; ++b)
+          if ((rc = copy_vectors(false, wq + (size_t)b * nv * n, yg + (int64_t)b * nvec * ldy, ldy, nv, "matvec_batch y D2H")))
+            return rc;
+        if ((rc = sync_stream(stream_, "matvec_batch sync"))) return rc;
+      }
+    }
+    done += nv;
+  }
+  HIPCHK(hipGetLastError(), "matvec_batch launch");
+  if ((rc = sync_stream(stream_, "matvec_batch sync"))) return rc;
+  if (!t.fits) {
+    feature_err_ = "matvec_batch: a launch has more work items for one member than a grid holds (the product is not complete)";
+    return -99;
+  }
+  return 0;
+}
+
+// both sweeps with the members' factors on nv work vectors per member (pivot order, ld = n), through the batch's
+// own paths; -20 is not this call's (the members without a factor are skipped by every kernel here as well).
+// The sweeps know no member mask: a member whose vectors are all frozen rides along with zero columns.
+int Engine::refine_batch_apply_factor(double* v, int nv, int64_t* launches) {
+  int rc;
+  if (nv < brf_blocked_min()) {
+    rc = solve_batch(v, true, nv, (int64_t)S_->n, 0, true);
+    if (rc == 0 || rc == kErrNotPosDef) *launches += bt_.solve_launches;
+  } else {
+    rc = solve_many_batch(v, true, nv, (int64_t)S_->n, 0, true);
+    *launches += bsm_info_[2];
+  }
+  return rc == kErrNotPosDef ? 0 : rc;
+}
+
+// one pass: nv <= brf_rb_ vectors of every member, the loop of refine_group for all (member, vector) pairs at once
+int Engine::refine_batch_pass(const double* dval, int64_t ldval, int nv, double* x, int64_t xstride, int64_t ldx, bool dev,
+                              int done, int nrhs, int method, double tol, int max_iter, int* iterations, double* error,
+                              int64_t* launches, int* worst) {
+  const int n = S_->n, nbatch = bt_.nbatch;
+  const size_t np = (size_t)nbatch * (size_t)nv, gn = np * (size_t)n;
+  double *B = d_brfwork_, *X = B + gn, *R = X + gn, *P = R + gn, *Q = P + gn, *XB = Q + gn;
+  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  const int sslots = spmv_slots(op), vslots = vec_slots(n);
+  const BrfView v{bt_.flag, nbatch, nv, d_brfds_, d_brfds_ + brf_capacity_, d_brfds_ + 2 * brf_capacity_, d_brfis_, d_brfpart_};
+  const int *st = v.st(), *decl = v.decl(), *improve = v.improve();
+  const int64_t ws = (int64_t)nv * n;   // a member's stride in the work arrays
+  BrfTally t;
+  int rc = 0;
+  auto ok = [&](int64_t i) { return bt_.hflag[(size_t)i] == INT_MAX; };
+  // (x + done * ldx: vector `done` of member 0; a member without a factor is neither copied nor permuted)
+  double* xg = x + (int64_t)done * ldx;
+  if (dev) {
+    t.add(launch_brf_permute(stream_, v, false, xg, xstride, ldx, d_order_, n, B));
+  } else {
+    for (int b = 0; b < nbatch; ++b)
+      if (ok(b) && (rc = copy_vectors(true, Q + (int64_t)b * ws, xg + (int64_t)b * xstride, ldx, nv, "refine_batch rhs H2D")))
+        return rc;
+    t.add(launch_brf_permute(stream_, v, false, Q, ws, n, d_order_, n, B));
+  }
+  t.add(launch_brf_dot(stream_, v, n, B, B, nullptr, 0, true));
+  t.add(launch_brf_finalize(stream_, v, RFS_BNORM, vslots, tol, 0));
+  // x = M^-1 b, r = b - A x, the error of the first iterate
+  t.add(launch_brf_copy(stream_, v, n, X, B, nullptr, 0));
+  if (!t.fits) return -99;
+  if ((rc = refine_batch_apply_factor(X, nv, launches))) return rc;
+  auto true_residual = [&](const int* sel, int want, int flag) {
+    t.add(launch_bspmv(stream_, op, v, dval, ldval, X, ws, n, B, R, ws, n, sel, want, true));
+    t.add(launch_brf_finalize(stream_, v, RFS_TRUE, sslots, tol, flag));
+    t.add(launch_brf_copy(stream_, v, n, XB, X, improve, 1));   // the best confirmed iterate
+  };
+  true_residual(st, 0, 0);
+  // the one array that crosses the bus per iteration: out[g] = best confirmed error, out[np + g] = state
+  std::vector<double> out(2 * np, 0.0);
+  auto readback = [&]() -> int {
+    HIPCHK(hipGetLastError(), "refine_batch launch");
+    HIPCHK(hipMemcpyAsync(out.data(), v.out(), sizeof(double) * 2 * np, hipMemcpyDeviceToHost, stream_), "refine_batch state D2H");
+    return sync_stream(stream_, "refine_batch sync");
+  };
+  if ((rc = readback())) return rc;
+  auto active = [&]() {
+    for (size_t g = 0; g < np; ++g)
+      if (out[np + g] == 0.0) return true;
+    return false;
+  };
+  std::vector<int> its(np, 0);
+  for (int it = 0; it < max_iter && active() && t.fits;) {
+    ++it;
+    for (size_t g = 0; g < np; ++g)
+      if (out[np + g] == 0.0) its[g] = it;
+    if (method == 0) {
+      // x += M^-1 r ; r = b - A x
+      t.add(launch_brf_copy(stream_, v, n, P, R, st, 0, true));   // (frozen pairs: a zero column for the sweep)
+      if ((rc = refine_batch_apply_factor(P, nv, launches))) return rc;
+      t.add(launch_brf_axpy(stream_, v, n, nullptr, X, P, nullptr, nullptr, st, 0, false));
+      true_residual(st, 0, 0);
+    } else {
+      // z = M^-1 r (in q) ; beta = r.z / (r.z)_old, 0 after a restart ; p = z + beta p
+      t.add(launch_brf_copy(stream_, v, n, Q, R, st, 0, true));   // (frozen pairs: a zero column for the sweep)
+      if ((rc = refine_batch_apply_factor(Q, nv, launches))) return rc;
+      t.add(launch_brf_dot(stream_, v, n, R, Q, st, 0, false));
+      t.add(launch_brf_finalize(stream_, v, RFS_BETA, vslots, tol, 0));
+      t.add(launch_brf_pupdate(stream_, v, n, v.beta(), P, Q, st, 0));
+      // q = A p with the partials of p.q ; alpha = r.z / p.q ; x += alpha p, r -= alpha q
+      t.add(launch_bspmv(stream_, op, v, dval, ldval, P, ws, n, nullptr, Q, ws, n, st, 0, true));
+      t.add(launch_brf_finalize(stream_, v, RFS_ALPHA, sslots, tol, 0));
+      t.add(launch_brf_axpy(stream_, v, n, v.alpha(), X, P, R, Q, st, 0, true));
+      t.add(launch_brf_finalize(stream_, v, RFS_REC, vslots, tol, 0));
+      // what the recurrence declares converged is confirmed with a true residual (no work if nothing is declared)
+      true_residual(decl, 1, 1);
+    }
+    if ((rc = readback())) return rc;
+  }
+  if (method == 1 && active() && t.fits) {
+    // out of iterations: the error reported is that of a true residual
+    t.add(launch_brf_finalize(stream_, v, RFS_FINAL, 0, tol, 0));
+    true_residual(decl, 1, 1);
+    if ((rc = readback())) return rc;
+  }
+  if (dev) {
+    t.add(launch_brf_permute(stream_, v, true, xg, xstride, ldx, d_order_, n, XB));
+  } else {
+    t.add(launch_brf_permute(stream_, v, true, Q, ws, n, d_order_, n, XB));
+    HIPCHK(hipGetLastError(), "refine_batch launch");
+    for (int b = 0; b < nbatch; ++b)
+      if (ok(b) && (rc = copy_vectors(false, Q + (int64_t)b * ws, xg + (int64_t)b * xstride, ldx, nv, "refine_batch x D2H")))
+        return rc;
+  }
+  HIPCHK(hipGetLastError(), "refine_batch launch");
+  if ((rc = sync_stream(stream_, "refine_batch sync"))) return rc;
+  *launches += t.n;
+  if (!t.fits) return -99;
+  for (int b = 0; b < nbatch; ++b)
+    for (int q = 0; q < nv; ++q) {
+      const size_t g = (size_t)b * nv + q, o = (size_t)b * nrhs + done + q;
+      if (iterations) iterations[o] = ok(b) ? its[g] : 0;
+      if (error) error[o] = ok(b) ? out[g] : std::numeric_limits<double>::quiet_NaN();
+      if (ok(b) && out[np + g] != 1.0) *worst = 1;
+    }
+  return 0;
+}
+
+int Engine::solve_refined_batch(const double* val, int64_t ldval, int nrhs, double* x, int64_t ldx, bool dev, int method,
+                                double tol, int max_iter, int* iterations, double* error) {
+  const int n = S_->n, nbatch = bt_.nbatch;
+  const int64_t nnz = S_->nnzA;
+  int rc;
+  if (!enter(val && x && nrhs >= 0 && ldval >= nnz && ldx >= n && method >= 0 && method <= 1 && tol > 0.0 && max_iter >= 0 &&
+                 nbatch > 0,
+             nrhs == 0, &rc))
+    return rc;
+  brf_info_[1] = brf_info_[2] = 0;
+  if (n == 0) {
+    for (int64_t o = 0; o < (int64_t)nbatch * nrhs; ++o) {
+      if (iterations) iterations[o] = 0;
+      if (error) error[o] = 0.0;
+    }
+    return 0;
+  }
+  if ((rc = prepare_refine_batch(nbatch))) return rc;
+  const double* dval = val;
+  int64_t ldv = ldval;
+  if (!dev) {
+    if ((rc = grow_batch_buffer(&d_brfval_, &brf_val_elems_, (size_t)nbatch * (size_t)std::max<int64_t>(nnz, 1), "the staged values")))
+      return rc;
+    for (int b = 0; b < nbatch; ++b)   // (a member without a factor: its values are not read)
+      if (bt_.hflag[(size_t)b] == INT_MAX &&
+          (rc = copy_vectors_to_device(d_brfval_ + (int64_t)b * nnz, val + (int64_t)b * ldval, nnz, 1, "refine_batch val H2D", nnz)))
+        return rc;
+    dval = d_brfval_;
+    ldv = nnz;
+  }
+  int64_t launches = 0;
+  {
+    const BrfView v{bt_.flag, nbatch, 1, d_brfds_, d_brfds_ + brf_capacity_, d_brfds_ + 2 * brf_capacity_, d_brfis_, d_brfpart_};
+    const int k = launch_brf_absmax(stream_, v, dval, ldv, nnz);
+    if (k < 0) return -99;
+    launches += k;
+  }
+  int worst = 0, passes = 0;
+  for (int done = 0; done < nrhs;) {
+    const int nv = std::min(brf_rb_, nrhs - done);
+    rc = refine_batch_pass(dval, ldv, nv, x, (int64_t)nrhs * ldx, ldx, dev, done, nrhs, method, tol, max_iter, iterations,
+                           error, &launches, &worst);
+    if (rc == -99 && feature_err_.empty())
+      feature_err_ = "solve_refined_batch: a launch has more work items for one member than a grid holds";
+    if (rc) return rc;
+    ++passes;
+    done += nv;
+  }
+  brf_info_[1] = passes;
+  brf_info_[2] = launches;
+  const int failed = batch_failed();
+  return failed ? failed : worst;
 }
 
 }  // namespace spx

@@ -17,36 +17,15 @@
 #include <cstdint>
 
 #include "refine.hpp"
+#include "rf_body.hpp"
 
 namespace spx {
 
-__device__ __forceinline__ bool rf_selected(const int* sel, int want, int q) { return !sel || sel[q] == want; }
-
-// sum over the wavefront (butterfly: every lane ends with the same bits)
-__device__ __forceinline__ double rf_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// the workgroup's sums of a and b to part[(slot * 2 + 0 / 1) * G + q]; every thread of the 256 calls it
-__device__ __forceinline__ void rf_block_sum2(double a, double b, double* part, int slot, int q) {
-  __shared__ double red[2][4];
-  a = rf_wave_sum(a);
-  b = rf_wave_sum(b);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { red[0][wave] = a; red[1][wave] = b; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const int w = threadIdx.x;
-    part[((int64_t)slot * 2 + w) * RF_G + q] = ((red[w][0] + red[w][1]) + red[w][2]) + red[w][3];
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------
 // rows[first .. first + nrows) of one length class; workgroup = 4 wavefronts x (64 / LPR) rows, grid.y =
-// chunk of RF_NV vectors.  Lane `sub` of a row's LPR lanes takes entries sub, sub + LPR, ... in order, the
-// LPR sums meet in a butterfly.
+// chunk of RF_NV vectors (the row body: rf_body.hpp).  The kernels of this file pass the literal 1.0 for the
+// bodies' scale `sc`: after inlining the products with it fold away (x * 1.0 is x for every x, NaN and signed zero
+// included), so the arithmetic is what it was before the bodies were shared; tests/test_refine_gpu.py pins it.
 // ---------------------------------------------------------------------------------------------------
 template <int LPR, bool RES>
 __global__ __launch_bounds__(256) void k_spmv(const int* __restrict__ rows, int nrows, const int64_t* __restrict__ rowptr,
@@ -55,7 +34,6 @@ __global__ __launch_bounds__(256) void k_spmv(const int* __restrict__ rows, int 
                                               const double* __restrict__ b, double* __restrict__ y, int64_t ldy, int nvec,
                                               const int* __restrict__ sel, int want, double* __restrict__ part,
                                               int slot0) {
-  constexpr int RPW = 64 / LPR, RPB = 4 * RPW;
   __shared__ double red[4][2 * RF_NV];
   const int q0 = blockIdx.y * RF_NV;
   const int nq = min(RF_NV, nvec - q0);
@@ -63,53 +41,8 @@ __global__ __launch_bounds__(256) void k_spmv(const int* __restrict__ rows, int 
   for (int j = 0; j < nq; ++j)
     if (rf_selected(sel, want, q0 + j)) act |= 1u << j;
   if (!act) return;   // (the same for every thread of the workgroup)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane % LPR;
-  const int ri = blockIdx.x * RPB + wave * RPW + lane / LPR;
-  const bool has = ri < nrows;
-  const int row = has ? rows[ri] : 0;
-  const int64_t k0 = has ? rowptr[row] : 0, k1 = has ? rowptr[row + 1] : 0;
-  double acc[RF_NV];
-#pragma unroll
-  for (int j = 0; j < RF_NV; ++j) acc[j] = 0.0;
-  for (int64_t k = k0 + sub; k < k1; k += LPR) {
-    const int c = col[k];
-    const double a = val[src[k]];
-#pragma unroll
-    for (int j = 0; j < RF_NV; ++j)
-      if (j < nq) acc[j] = fma(a, x[(int64_t)(q0 + j) * ldx + c], acc[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < RF_NV; ++j)
-#pragma unroll
-    for (int off = LPR / 2; off >= 1; off >>= 1) acc[j] += __shfl_xor(acc[j], off, 64);
-  const bool lead = has && sub == 0;
-  double p0[RF_NV], p1[RF_NV];
-#pragma unroll
-  for (int j = 0; j < RF_NV; ++j) {
-    p0[j] = 0.0;
-    p1[j] = 0.0;
-    if (lead && ((act >> j) & 1u)) {
-      const double xr = x[(int64_t)(q0 + j) * ldx + row];
-      const double out = RES ? b[(int64_t)(q0 + j) * ldy + row] - acc[j] : acc[j];
-      y[(int64_t)(q0 + j) * ldy + row] = out;
-      p0[j] = RES ? out * out : xr * out;
-      p1[j] = RES ? xr * xr : 0.0;
-    }
-  }
-  if (!part) return;
-#pragma unroll
-  for (int j = 0; j < RF_NV; ++j) {
-    p0[j] = rf_wave_sum(p0[j]);
-    p1[j] = rf_wave_sum(p1[j]);
-    if (lane == 0) { red[wave][2 * j] = p0[j]; red[wave][2 * j + 1] = p1[j]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 * RF_NV) {
-    const int j = threadIdx.x >> 1, w = threadIdx.x & 1;
-    if (j < nq)
-      part[((int64_t)(slot0 + blockIdx.x) * 2 + w) * RF_G + q0 + j] =
-          ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-  }
+  rf_spmv_body<LPR, RES>((int)blockIdx.x, q0, nq, act, rows, nrows, rowptr, col, src, val, x, ldx, b, y, ldy,
+                         part ? part + ((int64_t)(slot0 + blockIdx.x) * 2) * RF_G : nullptr, RF_G, 1.0, red);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -123,22 +56,9 @@ __global__ __launch_bounds__(256) void k_rf_axpy(int n, const double* __restrict
   if (!rf_selected(sel, want, q)) return;
   const double a = alpha ? alpha[q] : 1.0;
   const int64_t base = (int64_t)q * n;
-  double rr = 0.0, xx = 0.0;
-#pragma unroll
-  for (int k = 0; k < RF_VROWS / 256; ++k) {
-    const int i = blockIdx.x * RF_VROWS + k * 256 + threadIdx.x;
-    if (i < n) {
-      const double xv = fma(a, p[base + i], x[base + i]);
-      x[base + i] = xv;
-      xx = fma(xv, xv, xx);
-      if (qv) {
-        const double rv = fma(-a, qv[base + i], r[base + i]);
-        r[base + i] = rv;
-        rr = fma(rv, rv, rr);
-      }
-    }
-  }
-  if (part) rf_block_sum2(rr, xx, part, blockIdx.x, q);
+  double rr, xx;
+  rf_axpy_body(n, (int)blockIdx.x, a, x + base, p + base, r ? r + base : nullptr, qv ? qv + base : nullptr, 1.0, rr, xx);
+  if (part) rf_block_sum2(rr, xx, part + ((int64_t)blockIdx.x * 2) * RF_G + q, RF_G);
 }
 
 __global__ __launch_bounds__(256) void k_rf_pupdate(int n, const double* __restrict__ beta, double* __restrict__ p,
@@ -146,13 +66,8 @@ __global__ __launch_bounds__(256) void k_rf_pupdate(int n, const double* __restr
                                                     int want) {
   const int q = blockIdx.y;
   if (!rf_selected(sel, want, q)) return;
-  const double bt = beta[q];
   const int64_t base = (int64_t)q * n;
-#pragma unroll
-  for (int k = 0; k < RF_VROWS / 256; ++k) {
-    const int i = blockIdx.x * RF_VROWS + k * 256 + threadIdx.x;
-    if (i < n) p[base + i] = bt == 0.0 ? z[base + i] : fma(bt, p[base + i], z[base + i]);
-  }
+  rf_pupdate_body(n, (int)blockIdx.x, beta[q], p + base, z + base);
 }
 
 __global__ __launch_bounds__(256) void k_rf_dot(int n, const double* __restrict__ a, const double* __restrict__ b,
@@ -160,13 +75,8 @@ __global__ __launch_bounds__(256) void k_rf_dot(int n, const double* __restrict_
   const int q = blockIdx.y;
   if (!rf_selected(sel, want, q)) return;
   const int64_t base = (int64_t)q * n;
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < RF_VROWS / 256; ++k) {
-    const int i = blockIdx.x * RF_VROWS + k * 256 + threadIdx.x;
-    if (i < n) s = fma(a[base + i], b[base + i], s);
-  }
-  rf_block_sum2(s, 0.0, part, blockIdx.x, q);
+  const double s = rf_dot_body(n, (int)blockIdx.x, a + base, b + base, 1.0);
+  rf_block_sum2(s, 0.0, part + ((int64_t)blockIdx.x * 2) * RF_G + q, RF_G);
 }
 
 __global__ __launch_bounds__(256) void k_rf_copy(int n, double* __restrict__ dst, const double* __restrict__ src,
@@ -175,123 +85,36 @@ __global__ __launch_bounds__(256) void k_rf_copy(int n, double* __restrict__ dst
   const bool mine = rf_selected(sel, want, q);
   if (!mine && !zero_others) return;
   const int64_t base = (int64_t)q * n;
-#pragma unroll
-  for (int k = 0; k < RF_VROWS / 256; ++k) {
-    const int i = blockIdx.x * RF_VROWS + k * 256 + threadIdx.x;
-    if (i < n) dst[base + i] = mine ? src[base + i] : 0.0;
-  }
+  rf_copy_body(n, (int)blockIdx.x, mine, dst + base, src + base);
 }
-
-// max that a NaN wins: once m is a NaN no comparison replaces it
-__device__ __forceinline__ double rf_nanmax(double m, double a) { return (a > m || a != a) ? a : m; }
 
 __global__ __launch_bounds__(256) void k_rf_absmax(const double* __restrict__ val, int64_t nnz, double* __restrict__ part) {
   __shared__ double red[4];
-  double m = 0.0;
-  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < nnz; k += (int64_t)gridDim.x * 256)
-    m = rf_nanmax(m, fabs(val[k]));
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = rf_nanmax(m, __shfl_xor(m, off, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = rf_nanmax(rf_nanmax(rf_nanmax(red[0], red[1]), red[2]), red[3]);
+  rf_absmax_body(val, nnz, (int)blockIdx.x, (int)gridDim.x, part + blockIdx.x, red);
 }
 
 // ---------------------------------------------------------------------------------------------------
-// One workgroup of 256: thread t adds the partials of vector t & 31 in slots (t >> 5), (t >> 5) + 8, ... ;
-// the eight slices of a vector are then added in order by thread q, which also does the scalar step.
+// One workgroup of 256: the second stage of a reduction (rf_second_stage), then thread q does the scalar step
+// of vector q.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool rf_finite(double v) { return v == v && fabs(v) <= 1.79769313486231570e308; }
-
 __global__ __launch_bounds__(256) void k_rf_finalize(int stage, const double* __restrict__ part, int nslots, int nvec,
                                                      double tol, int flag, double* __restrict__ ds, int* __restrict__ is) {
   __shared__ double red[2][8][RF_G];
   __shared__ double mred[256];
   const int t = threadIdx.x;
   if (stage == RFS_AMAX) {
-    double m = 0.0;
-    for (int s = t; s < nslots; s += 256) m = rf_nanmax(m, part[s]);
-    mred[t] = m;
-    __syncthreads();
-    if (t == 0) {
-      for (int s = 1; s < 256; ++s) m = rf_nanmax(m, mred[s]);
-      ds[RFD_AMAX] = m;
-    }
+    const double m = rf_absmax_final(part, nslots, mred);
+    if (t == 0) ds[RFD_AMAX] = m;
     return;
   }
-  const int q = t & (RF_G - 1), sl = t >> 5;
-  double s0 = 0.0, s1 = 0.0;
-  if (stage != RFS_FINAL)
-    for (int s = sl; s < nslots; s += 8) {
-      s0 += part[((int64_t)s * 2) * RF_G + q];
-      s1 += part[((int64_t)s * 2 + 1) * RF_G + q];
-    }
-  red[0][sl][q] = s0;
-  red[1][sl][q] = s1;
-  __syncthreads();
+  double s0, s1;
+  rf_second_stage(stage != RFS_FINAL, part, RF_G, nslots, true, red, s0, s1);
   if (t >= RF_G || t >= nvec) return;
-  s0 = red[0][0][q];
-  s1 = red[1][0][q];
-  for (int s = 1; s < 8; ++s) { s0 += red[0][s][q]; s1 += red[1][s][q]; }
-  int st = is[RFI_ST + q];
-  switch (stage) {
-    case RFS_BNORM:   // s0 = |b|^2: the start of a group
-      ds[RFD_BNORM + q] = sqrt(s0);
-      ds[RFD_EBEST + q] = -1.0;
-      ds[RFD_RZ + q] = 0.0;
-      ds[RFD_ALPHA + q] = 0.0;
-      ds[RFD_BETA + q] = 0.0;
-      st = 0;
-      is[RFI_DECL + q] = 0;
-      is[RFI_RESTART + q] = 1;
-      is[RFI_IMPROVE + q] = 0;
-      break;
-    case RFS_TRUE: {  // s0 = |b - A x|^2, s1 = |x|^2 of the vectors with st == 0 (flag = 0) / decl == 1 (flag = 1)
-      const bool mine = flag ? is[RFI_DECL + q] == 1 : st == 0;
-      int improve = 0;
-      if (mine) {
-        const double e = s0 == 0.0 ? 0.0 : sqrt(s0) / (ds[RFD_BNORM + q] + ds[RFD_AMAX] * sqrt(s1));
-        const double eb = ds[RFD_EBEST + q];
-        if (eb < 0.0 || e < eb) { improve = 1; ds[RFD_EBEST + q] = e; }
-        if (!rf_finite(e)) st = 2;
-        else if (e <= tol) st = 1;
-        else is[RFI_RESTART + q] = 1;   // (PCG: go on from the true residual with a fresh direction)
-        is[RFI_DECL + q] = 0;
-      }
-      is[RFI_IMPROVE + q] = improve;
-      break;
-    }
-    case RFS_ALPHA:   // s0 = p.q
-      if (st == 0) {
-        const double a = ds[RFD_RZ + q] / s0;
-        if (!rf_finite(a)) st = 2;
-        ds[RFD_ALPHA + q] = rf_finite(a) ? a : 0.0;
-      }
-      break;
-    case RFS_REC:     // s0 = |r|^2 of the recurrence, s1 = |x|^2
-      if (st == 0) {
-        const double e = s0 == 0.0 ? 0.0 : sqrt(s0) / (ds[RFD_BNORM + q] + ds[RFD_AMAX] * sqrt(s1));
-        if (!rf_finite(e)) st = 2;
-        else if (e <= tol) is[RFI_DECL + q] = 1;
-      }
-      break;
-    case RFS_BETA:    // s0 = r.z
-      if (st == 0) {
-        const double bt = is[RFI_RESTART + q] ? 0.0 : s0 / ds[RFD_RZ + q];
-        if (!rf_finite(bt) || !rf_finite(s0)) st = 2;
-        ds[RFD_BETA + q] = rf_finite(bt) ? bt : 0.0;
-        ds[RFD_RZ + q] = s0;
-        is[RFI_RESTART + q] = 0;
-      }
-      break;
-    case RFS_FINAL:   // what still iterates gets one true residual before the call returns
-      is[RFI_DECL + q] = st == 0 ? 1 : 0;
-      break;
-    default: break;
-  }
-  is[RFI_ST + q] = st;
-  ds[RFD_OUT + q] = ds[RFD_EBEST + q];
-  ds[RFD_OUT + RF_G + q] = (double)st;
+  const int q = t;
+  const RfScalars v{ds + RFD_ALPHA + q, ds + RFD_BETA + q,  ds + RFD_RZ + q,          ds + RFD_BNORM + q,
+                    ds + RFD_EBEST + q, ds + RFD_OUT + q,   ds + RFD_OUT + RF_G + q,  is + RFI_ST + q,
+                    is + RFI_DECL + q,  is + RFI_RESTART + q, is + RFI_IMPROVE + q};
+  rf_scalar_step(stage, s0, s1, tol, flag, ds[RFD_AMAX], v);
 }
 
 // ---------------------------------------------------------------------------------------------------
