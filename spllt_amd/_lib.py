@@ -214,6 +214,21 @@ _BATCH_REFINE = {
     "spllt_hip_solve_refined_batch_info": (i32, [vp, i64p]),
     "spllt_hip_release_refine_batch": (i32, [vp]),
 }
+# every symbol declared in include/spllt_hip_constrain.h: hard linear constraints C x = e on the current factor.  A
+# table of its own for the same reason.
+_CONSTRAIN = {
+    "spllt_hip_set_constraints": (i32, [vp, i32, dp, i64]),
+    "spllt_hip_set_constraints_dev": (i32, [vp, i32, vp, i64]),
+    "spllt_hip_constrain": (i32, [vp, i32, dp, i64, dp, i64, dp, i64]),
+    "spllt_hip_constrain_dev": (i32, [vp, i32, vp, i64, vp, i64, vp, i64]),
+    "spllt_hip_solve_constrained": (i32, [vp, i32, dp, i64, dp, i64, dp, i64]),
+    "spllt_hip_solve_constrained_dev": (i32, [vp, i32, vp, i64, vp, i64, vp, i64]),
+    "spllt_hip_sample_constrained": (i32, [vp, i32, dp, i64, u64, u64, dp, dp]),
+    "spllt_hip_sample_constrained_dev": (i32, [vp, i32, vp, i64, u64, u64, vp, vp]),
+    "spllt_hip_inverse_diag_constrained": (i32, [vp, dp, i32]),
+    "spllt_hip_constraints_info": (i32, [vp, i64p, dp]),
+    "spllt_hip_release_constraints": (i32, [vp]),
+}
 del vp, vpp, i32, i64, u64, f64, cstr, long, ip, i64p, dp, fp, longp, ipp, dpp, opt, inf   # (names of the table only)
 IFACE_SYMBOLS = list(_IFACE)
 HIP_SYMBOLS = list(_HIP)
@@ -221,6 +236,7 @@ BATCH_MULT_SYMBOLS = list(_BATCH_MULT)
 BATCH_SOLVE_MANY_SYMBOLS = list(_BATCH_SOLVE_MANY)
 BATCH_ADJOINT_SYMBOLS = list(_BATCH_ADJOINT)
 BATCH_REFINE_SYMBOLS = list(_BATCH_REFINE)
+CONSTRAIN_SYMBOLS = list(_CONSTRAIN)
 
 _lib = None
 
@@ -235,7 +251,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C spllt_amd/csrc`. spllt_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE):
+    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE, _CONSTRAIN):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

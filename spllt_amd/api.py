@@ -473,6 +473,111 @@ class Factorization:
         self._call("spllt_hip_release_solve_repro", self.fkeep)
         return self
 
+    # ---- hard linear constraints C x = e (include/spllt_hip_constrain.h) -----------
+    def set_constraints(self, C_rows):
+        """spllt_hip_set_constraints: store the k <= 64 dense rows of C (k x n, or n for one row) and build
+        W = A^-1 C^T, S = C W = G G^T and U = W G^-T for the current factor; a later factorization or update is
+        picked up by the next call that needs them.  None or zero rows clear the constraints.  Dependent rows
+        raise SplltError with flag -20 and leave the handle without constraints."""
+        if C_rows is None:
+            self._call("spllt_hip_set_constraints", self.fkeep, 0, None, max(self.n, 1))
+            return self
+        c = np.ascontiguousarray(np.atleast_2d(np.asarray(C_rows, dtype=np.float64)))
+        if c.ndim != 2 or c.shape[1] != self.n:
+            raise ValueError(f"C must be (k, {self.n}), got {c.shape}")
+        self._call("spllt_hip_set_constraints", self.fkeep, c.shape[0], _dp(c) if c.shape[0] else None, max(self.n, 1))
+        return self
+
+    def set_constraints_dev(self, c_dev_ptr, k, ldc=None):
+        """spllt_hip_set_constraints_dev: row i of C at c[i*ldc .. i*ldc + n) in device memory"""
+        self._call("spllt_hip_set_constraints_dev", self.fkeep, int(k), C.c_void_p(c_dev_ptr),
+                   int(self.n if ldc is None else ldc))
+        return self
+
+    def _constrain_call(self, name, X, e, multipliers):
+        x = np.array(X, dtype=np.float64, order="F", copy=True)
+        if x.shape[0] != self.n or x.ndim > 2:
+            raise ValueError(f"the vectors must be ({self.n},) or ({self.n}, nvec), got {x.shape}")
+        nvec = 1 if x.ndim == 1 else x.shape[1]
+        k = self.constraints_info()["k"]
+        ev, lde = None, 0
+        if e is not None:
+            ev = np.array(e, dtype=np.float64, order="F", copy=True)
+            if ev.shape not in ((k,), (k, nvec)):
+                raise ValueError(f"e must be ({k},) or ({k}, {nvec}), got {ev.shape}")
+            lde = k if ev.ndim == 2 else 0     # (one column per vector, else one shared column)
+        lam = np.zeros((max(k, 1), nvec), dtype=np.float64, order="F") if multipliers else None
+        self._call(name, self.fkeep, nvec, _dp(x), max(self.n, 1), None if ev is None else _dp(ev), lde,
+                   None if lam is None else _dp(lam), max(k, 1))
+        if not multipliers:
+            return x
+        lam = lam[:k]
+        return x, (lam[:, 0] if x.ndim == 1 else lam)
+
+    def constrain(self, X, e=None, multipliers=False):
+        """spllt_hip_constrain on a copy of X (n or n x nvec): x* = x - U G^-1 (C x - e), so that C x* = e.  e: None
+        (zeros), k targets shared by all vectors, or (k, nvec).  multipliers=True also returns lambda = S^-1 (C x - e)
+        (k or k x nvec).  Bit-reproducible: the same vector gives the same bits whatever nvec and its place."""
+        return self._constrain_call("spllt_hip_constrain", X, e, multipliers)
+
+    def solve_constrained(self, b, e=None, multipliers=False):
+        """spllt_hip_solve_constrained on a copy of b: constrain(solve_many(b), e) in one call; with
+        multipliers=True, (x*, lambda) solves the KKT system A x + C^T lambda = b, C x = e."""
+        return self._constrain_call("spllt_hip_solve_constrained", b, e, multipliers)
+
+    def sample_constrained(self, nsamp, seed=0, mean=None, e=None, first_sample=0):
+        """spllt_hip_sample_constrained: nsamp draws of N(mean, A^-1) | C x = e as an F-ordered (n, nsamp) array:
+        the kind "precision" sample of (seed, first_sample + q), corrected (conditioning by kriging).  e: None or
+        k shared targets."""
+        x = np.zeros((self.n, nsamp), dtype=np.float64, order="F")
+        m = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        if m is not None and m.shape != (self.n,):
+            raise ValueError(f"mean must be ({self.n},)")
+        ev = None if e is None else np.ascontiguousarray(e, dtype=np.float64)
+        if ev is not None and ev.shape != (self.constraints_info()["k"],):
+            raise ValueError("e must hold one target per constraint")
+        self._call("spllt_hip_sample_constrained", self.fkeep, nsamp, _dp(x), max(self.n, 1), int(seed), int(first_sample),
+                   None if m is None else _dp(m), None if ev is None else _dp(ev))
+        return x
+
+    def constrain_dev(self, x_dev_ptr, nvec, ldx=None, e_dev_ptr=None, lde=0, lambda_dev_ptr=None, ldl=0,
+                      entry="constrain"):
+        """spllt_hip_constrain_dev / spllt_hip_solve_constrained_dev (entry="solve_constrained") on device vectors,
+        in place (layout of solve_many_dev); e and lambda: device pointers or None"""
+        self._call(f"spllt_hip_{entry}_dev", self.fkeep, int(nvec), C.c_void_p(x_dev_ptr), int(self.n if ldx is None else ldx),
+                   None if e_dev_ptr is None else C.c_void_p(e_dev_ptr), int(lde),
+                   None if lambda_dev_ptr is None else C.c_void_p(lambda_dev_ptr), int(ldl))
+        return self
+
+    def sample_constrained_dev(self, x_dev_ptr, nsamp, ldx=None, seed=0, mean_dev_ptr=None, e_dev_ptr=None, first_sample=0):
+        """spllt_hip_sample_constrained_dev: the constrained samples into device memory (layout of sample_dev)"""
+        self._call("spllt_hip_sample_constrained_dev", self.fkeep, int(nsamp), C.c_void_p(x_dev_ptr),
+                   int(self.n if ldx is None else ldx), int(seed), int(first_sample),
+                   None if mean_dev_ptr is None else C.c_void_p(mean_dev_ptr),
+                   None if e_dev_ptr is None else C.c_void_p(e_dev_ptr))
+        return self
+
+    def inverse_diag_constrained(self):
+        """Var(x_i | C x = e) = (A^-1)_ii - sum_j U[i, j]^2 in the user's variable order; needs selected_inverse()
+        of the current factor, like inverse_diag"""
+        out = np.zeros(max(self.n, 1), dtype=np.float64)
+        self._call("spllt_hip_inverse_diag_constrained", self.fkeep, _dp(out), self.n)
+        return out[:self.n]
+
+    def constraints_info(self):
+        """k, rebuilds of U so far, device bytes held, kernel launches of the last call, log det S and the smallest
+        relative pivot of S = G G^T"""
+        out = np.zeros(4, dtype=np.int64)
+        stat = np.zeros(2, dtype=np.float64)
+        self._call("spllt_hip_constraints_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)), _dp(stat))
+        return {"k": int(out[0]), "rebuilds": int(out[1]), "device_bytes": int(out[2]), "launches": int(out[3]),
+                "log_det_s": float(stat[0]), "min_relative_pivot": float(stat[1])}
+
+    def release_constraints(self):
+        """C, U and the work arrays of the constraints back to the device pool; C is forgotten."""
+        self._call("spllt_hip_release_constraints", self.fkeep)
+        return self
+
     # ---- products with the factor, Gaussian sampling ------------------------------
     def factor_mult(self, x, job=0):
         """spllt_hip_factor_mult on a copy of x (n or n x nvec): job 0 P^T L L^T P x, 1 P^T L x, 2 L^T P x -- the

@@ -32,6 +32,7 @@
 #include "spllt_hip_batch_adjoint.h"
 #include "spllt_hip_batch_solve_many.h"
 #include "spllt_hip_batch_refine.h"
+#include "spllt_hip_constrain.h"
 #include "symbolic.hpp"
 
 using namespace spx;
@@ -980,6 +981,101 @@ int spllt_hip_white_noise_dev(void* fkeep, int nsamp, double* z_dev, int64_t ldz
   return leave(f, f->eng->white_noise_dev(z_dev, nsamp, ldz, seed, first_sample));
 }
 
+// ---- hard linear constraints C x = e (spllt_hip_constrain.h) ----------------------------------------
+static int set_constraints_impl(const char* what, void* fkeep, int k, const double* c, int64_t ldc, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (k != 0 && !c) bad = "the array of constraint rows is null";
+  else if (k < 0) bad = "k < 0";
+  else if (k > 64) bad = "k > 64";
+  else if (k > 0 && ldc < f->S->n) bad = "ldc < n";
+  // (FACTORED, as the refined solves: on an engine that has never factorized, W would be numbers of an empty arena)
+  if (int rc = enter(f, what, bad, SINGLE | WAIT | FACTORED)) return rc;
+  f->eng->set_reproducible_solve(f->repro_solve);
+  return leave(f, f->eng->set_constraints(k, c, ldc, dev, f->serial[0]));
+}
+
+int spllt_hip_set_constraints(void* fkeep, int k, const double* c_host, int64_t ldc) {
+  return set_constraints_impl("spllt_hip_set_constraints", fkeep, k, c_host, ldc, false);
+}
+
+int spllt_hip_set_constraints_dev(void* fkeep, int k, const double* c_dev, int64_t ldc) {
+  return set_constraints_impl("spllt_hip_set_constraints_dev", fkeep, k, c_dev, ldc, true);
+}
+
+// the correction behind nothing (op 0), the blocked solve (1) or the kind-0 sample (2): Engine::CnOp
+static int constrain_impl(const char* what, int op, void* fkeep, int nvec, double* x, int64_t ldx, const double* e,
+                          int64_t lde, double* lambda, int64_t ldl, bool dev, uint64_t seed, uint64_t first,
+                          const double* mean) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = vectors_bad(f, nvec, x, ldx, 0);
+  const int k = f->eng ? f->eng->constraints_k() : 0;   // (0: refused below, once the ladder is through)
+  if (!bad && k > 0 && e && lde != 0 && lde < k) bad = "lde is neither 0 nor >= k";
+  if (!bad && k > 0 && lambda && ldl < k) bad = "ldl < k";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT | FACTORED)) return rc;
+  if (f->eng->constraints_k() <= 0) return fail(f, what, "no constraints are set on this handle (spllt_hip_set_constraints)");
+  f->eng->set_reproducible_solve(f->repro_solve);
+  return leave(f, f->eng->constrain(op, nvec, x, ldx, e, e ? lde : 0, lambda, ldl, dev, f->serial[0], seed, first, mean));
+}
+
+int spllt_hip_constrain(void* fkeep, int nvec, double* x_host, int64_t ldx, const double* e_host, int64_t lde,
+                        double* lambda_host, int64_t ldl) {
+  return constrain_impl("spllt_hip_constrain", Engine::CN_CORRECT, fkeep, nvec, x_host, ldx, e_host, lde, lambda_host, ldl,
+                        false, 0, 0, nullptr);
+}
+
+int spllt_hip_constrain_dev(void* fkeep, int nvec, double* x_dev, int64_t ldx, const double* e_dev, int64_t lde,
+                            double* lambda_dev, int64_t ldl) {
+  return constrain_impl("spllt_hip_constrain_dev", Engine::CN_CORRECT, fkeep, nvec, x_dev, ldx, e_dev, lde, lambda_dev, ldl,
+                        true, 0, 0, nullptr);
+}
+
+int spllt_hip_solve_constrained(void* fkeep, int nrhs, double* x_host, int64_t ldx, const double* e_host, int64_t lde,
+                                double* lambda_host, int64_t ldl) {
+  return constrain_impl("spllt_hip_solve_constrained", Engine::CN_SOLVE, fkeep, nrhs, x_host, ldx, e_host, lde, lambda_host,
+                        ldl, false, 0, 0, nullptr);
+}
+
+int spllt_hip_solve_constrained_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, const double* e_dev, int64_t lde,
+                                    double* lambda_dev, int64_t ldl) {
+  return constrain_impl("spllt_hip_solve_constrained_dev", Engine::CN_SOLVE, fkeep, nrhs, x_dev, ldx, e_dev, lde, lambda_dev,
+                        ldl, true, 0, 0, nullptr);
+}
+
+int spllt_hip_sample_constrained(void* fkeep, int nsamp, double* x_host, int64_t ldx, uint64_t seed, uint64_t first_sample,
+                                 const double* mean_host, const double* e_host) {
+  return constrain_impl("spllt_hip_sample_constrained", Engine::CN_SAMPLE, fkeep, nsamp, x_host, ldx, e_host, 0, nullptr, 0,
+                        false, seed, first_sample, mean_host);
+}
+
+int spllt_hip_sample_constrained_dev(void* fkeep, int nsamp, double* x_dev, int64_t ldx, uint64_t seed,
+                                     uint64_t first_sample, const double* mean_dev, const double* e_dev) {
+  return constrain_impl("spllt_hip_sample_constrained_dev", Engine::CN_SAMPLE, fkeep, nsamp, x_dev, ldx, e_dev, 0, nullptr, 0,
+                        true, seed, first_sample, mean_dev);
+}
+
+int spllt_hip_inverse_diag_constrained(void* fkeep, double* out, int n) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  const char* what = "spllt_hip_inverse_diag_constrained";
+  if (int rc = enter(f, what, out ? nullptr : "", SINGLE_F | WAIT | FACTOR | INVERSE)) return rc;
+  if (n != f->S->n)
+    return fail(f, what, "n = " + std::to_string(n) + " does not match the analysed order " + std::to_string(f->S->n));
+  if (f->eng->constraints_k() <= 0) return fail(f, what, "no constraints are set on this handle (spllt_hip_set_constraints)");
+  f->eng->set_reproducible_solve(f->repro_solve);
+  return leave(f, f->eng->inverse_diag_constrained(out, n, f->serial[0]));
+}
+
+int spllt_hip_constraints_info(void* fkeep, int64_t out[4], double stat[2]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out || !stat) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  stat[0] = stat[1] = 0.0;
+  if (f->eng && !f->dead) f->eng->constraints_info(out, stat);
+  return 0;
+}
+
 // ---- batched factorization --------------------------------------------------
 static int factor_batch_impl(void* akeep, void* fkeep, int nbatch, int nnz, const double* val, int64_t ldval, bool dev,
                              const char* what) {
@@ -1761,6 +1857,7 @@ static int release(void* fkeep, int (Engine::*fn)(), unsigned need) {
 }
 
 int spllt_hip_release_solve_repro(void* fkeep) { return release(fkeep, &Engine::release_solve_repro, WAIT_NOT_POSDEF); }
+int spllt_hip_release_constraints(void* fkeep) { return release(fkeep, &Engine::release_constraints, WAIT_NOT_POSDEF); }
 int spllt_hip_release_factor_mult(void* fkeep) { return release(fkeep, &Engine::release_factor_mult, WAIT_NOT_POSDEF); }
 int spllt_hip_release_solve_sparse(void* fkeep) { return release(fkeep, &Engine::release_solve_sparse, WAIT_NOT_POSDEF); }
 int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::release_refine, WAIT_IGNORE); }

@@ -262,6 +262,28 @@ class Engine {
   // own kernels and those of the sweeps, whichever route M^-1 took), bytes of the workspace
   const int64_t* solve_refined_batch_info() const { return brf_info_; }
   int release_refine_batch();
+  // ---- hard linear constraints C x = e (constrain.hip, single GPU; include/spllt_hip_constrain.h has the
+  // mathematics).  set_constraints stores C (k rows of n at c + i * ldc, user order; dev: a device pointer) and builds
+  // W = A^-1 C^T (solve_repro_dev when set_reproducible_solve is on, else solve_many_dev), S = C W, S = G G^T, U = W G^-T
+  // for the factor `serial` names (the caller's count of changes of the factor); k = 0 releases.  Every later call
+  // passes the current serial: when it differs, U, G and the scalars are rebuilt from the stored C first.  Dependent
+  // rows: -20, feature_error() names the row, nothing of the feature stays allocated.  Storage, all or nothing (-1: no
+  // memory, nothing kept): C and U (k n doubles each), G, the partials of cn_nchunks(n) chunks, t, and the staged e /
+  // lambda of a host entry point.
+  int set_constraints(int k, const double* c, int64_t ldc, bool dev, int64_t serial);
+  int constraints_k() const { return cn_.k; }
+  // op 0: the correction of the nvec vectors in x (layout of solve_many); 1: solve_many_dev job 0 first; 2: x = the
+  // kind-0 sample of (seed, first + q) + mean first (e then k shared targets: lde = 0).  Passes of at most 32 vectors
+  // (for_each_block); host vectors go through the staging block of solve_many.  e: null, shared (lde = 0) or per
+  // vector; lambda: null or k per vector.
+  enum CnOp : int { CN_CORRECT = 0, CN_SOLVE = 1, CN_SAMPLE = 2 };
+  int constrain(int op, int nvec, double* x, int64_t ldx, const double* e, int64_t lde, double* lambda, int64_t ldl,
+                bool dev, int64_t serial, uint64_t seed = 0, uint64_t first = 0, const double* mean = nullptr);
+  int inverse_diag_constrained(double* out, int n, int64_t serial);   // host, user order; needs inverse_valid()
+  // out: k, rebuilds of U, device bytes held, kernel launches of this family in the last call; stat: log det S, the
+  // smallest pivot_j / S_jj
+  void constraints_info(int64_t out[4], double stat[2]) const;
+  int release_constraints();
   bool factored() const { return factored_ && !ud_invalid_; }
   // ---- low-rank update / downdate (updown.hip, single GPU): the factor of P (A + sign W W^T) P^T in place of
   // the current one, same layout, the dinv slots of the visited block columns rebuilt -- every solve then works
@@ -694,6 +716,22 @@ class Engine {
   double* d_rfds_ = nullptr;       // device scalars (refine.hpp)
   int* d_rfis_ = nullptr;
   double* d_rfval_ = nullptr;      // nnz doubles: the values of a host entry point
+  // hard linear constraints: C, U, G, the partials and t (taken by set_constraints, all or nothing)
+  struct CnState {
+    int k = 0;                     // rows of C held (0: none)
+    int64_t serial = -1;           // the factor U, G and the scalars belong to
+    int64_t rebuilds = 0, launches = 0;
+    size_t bytes = 0;
+    double* C = nullptr;           // k x n, row i at C + i * n
+    double* U = nullptr;           // k x n, column j of U at U + j * n
+    double* G = nullptr;           // kCnMaxRows^2, then stat[4]
+    double* part = nullptr;        // cn_nchunks(n) * kCnMaxRows^2
+    double* T = nullptr;           // kCnPass * kCnMaxRows, then the staged e and lambda (as much each)
+    double logdet = 0.0, minrel = 0.0;
+  } cn_;
+  void drop_constraints();
+  int build_constraints(int64_t serial);   // U, G and the scalars from C and the current factor
+  int cn_pass(double* xd, int64_t ld, int nv, const double* e, int64_t lde, double* lambda, int64_t ldl);   // enqueue only
   // update / downdate: work array and coefficient scratch (taken on first use, both or neither)
   bool ud_invalid_ = false;
   int64_t ud_info_[4] = {0, 0, 0, 0};

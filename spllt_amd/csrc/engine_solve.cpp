@@ -1754,4 +1754,204 @@ int Engine::solve_refined_batch(const double* val, int64_t ldval, int nrhs, doub
   return failed ? failed : worst;
 }
 
+// ---- hard linear constraints C x = e ----------------------------------------------------------------------
+void Engine::drop_constraints() {
+  for (void* p : {(void*)cn_.C, (void*)cn_.U, (void*)cn_.G, (void*)cn_.part, (void*)cn_.T})
+    if (p) release_buffer(p);
+  const int64_t rebuilds = cn_.rebuilds;
+  cn_ = CnState{};
+  cn_.rebuilds = rebuilds;
+}
+
+int Engine::release_constraints() {
+  int rc;
+  if (!enter_release(cn_.k > 0, "constraints release", &rc)) return rc;
+  drop_constraints();
+  return 0;
+}
+
+void Engine::constraints_info(int64_t out[4], double stat[2]) const {
+  out[0] = cn_.k;
+  out[1] = cn_.rebuilds;
+  out[2] = (int64_t)cn_.bytes;
+  out[3] = cn_.launches;
+  stat[0] = cn_.logdet;
+  stat[1] = cn_.minrel;
+}
+
+// U, G, log det S and the smallest relative pivot from the stored C and the current factor
+int Engine::build_constraints(int64_t serial) {
+  const int n = S_->n, k = cn_.k;
+  int rc = prepare_solve_many(false);
+  if (!rc && repro_on_) rc = prepare_solve_repro();
+  if (rc) return rc;
+  cn_.serial = -1;
+  HIPCHK(hipMemcpyAsync(cn_.U, cn_.C, sizeof(double) * (size_t)k * (size_t)n, hipMemcpyDeviceToDevice, stream_), "constraints W");
+  if ((rc = repro_on_ ? solve_repro_dev(cn_.U, k, (int64_t)n, 0, false) : solve_many_dev(cn_.U, k, (int64_t)n, 0, false)))
+    return rc;
+  double* dstat = cn_.G + kCnMaxRows * kCnMaxRows;
+  launch_cn_dot(stream_, cn_.C, (int64_t)n, k, cn_.U, (int64_t)n, k, n, cn_.part, kCnMaxRows, true);
+  launch_cn_chol(stream_, cn_.part, cn_nchunks(n), k, cn_.G, dstat);
+  cn_.launches += 2;
+  HIPCHK(hipGetLastError(), "constraints launch");
+  double stat[3] = {0.0, 0.0, 0.0};
+  HIPCHK(hipMemcpyAsync(stat, dstat, sizeof stat, hipMemcpyDeviceToHost, stream_), "constraints D2H");
+  if ((rc = sync_stream(stream_, "constraints sync"))) return rc;
+  if (stat[2] != 0.0) {
+    feature_err_ = "set_constraints: row " + std::to_string((int)stat[2]) + " of C depends on the rows before it (its pivot of "
+                   "S = C A^-1 C^T is <= 2^-26 S_jj or not finite): the handle holds no constraints";
+    return kErrNotPosDef;
+  }
+  launch_cn_scale(stream_, cn_.U, (int64_t)n, n, k, cn_.G);
+  ++cn_.launches;
+  HIPCHK(hipGetLastError(), "constraints launch");
+  if ((rc = sync_stream(stream_, "constraints sync"))) return rc;
+  cn_.logdet = stat[0];
+  cn_.minrel = stat[1];
+  cn_.serial = serial;
+  ++cn_.rebuilds;
+  return 0;
+}
+
+int Engine::set_constraints(int k, const double* c, int64_t ldc, bool dev, int64_t serial) {
+  if (k == 0) return release_constraints();
+  const int n = S_->n;
+  int rc;
+  if (!enter(k > 0 && k <= kCnMaxRows && c && ldc >= n && n > 0, false, &rc)) return rc;
+  if ((rc = prepare_solve_many(false))) return rc;
+  if (cn_.k != k) {
+    // (a failure here leaves the factor and every solve usable: the engine's status is not touched)
+    drop_constraints();
+    const size_t kn = sizeof(double) * (size_t)k * (size_t)n, gb = sizeof(double) * (kCnMaxRows * kCnMaxRows + 8),
+                 pb = sizeof(double) * (size_t)cn_nchunks(n) * kCnMaxRows * kCnMaxRows,
+                 tb = sizeof(double) * 3 * kCnPass * kCnMaxRows;
+    hipError_t e = hipSuccess;
+    const std::pair<double**, size_t> want[] = {{&cn_.C, kn}, {&cn_.U, kn}, {&cn_.G, gb}, {&cn_.part, pb}, {&cn_.T, tb}};
+    for (const auto& w : want)
+      if ((e = fmult_take((void**)w.first, w.second)) != hipSuccess) break;
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      drop_constraints();
+      feature_err_ = "set_constraints: not enough device memory for C, U and the partial sums (" +
+                     std::to_string((2 * kn + gb + pb + tb) >> 20) + " MiB): " + hipGetErrorString(e);
+      return alloc_code(e);
+    }
+    cn_.bytes = 2 * kn + gb + pb + tb;
+    cn_.k = k;
+  }
+  cn_.launches = 0;
+  const hipError_t e = hipMemcpy2DAsync(cn_.C, sizeof(double) * (size_t)n, c, sizeof(double) * (size_t)ldc, sizeof(double) * (size_t)n,
+                                        (size_t)k, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_);
+  if (e != hipSuccess) {
+    drop_constraints();
+    return fail(kErrHip, "constraints C copy", e);
+  }
+  if ((rc = build_constraints(serial))) {
+    const std::string why = feature_err_;
+    if (!poisoned_) drop_constraints();
+    feature_err_ = why;
+  }
+  return rc;
+}
+
+// one pass of nv <= kCnPass device vectors: r = C x - e, t = G^-1 r (and lambda), x -= U t (enqueue only)
+int Engine::cn_pass(double* xd, int64_t ld, int nv, const double* e, int64_t lde, double* lambda, int64_t ldl) {
+  const int n = S_->n, k = cn_.k;
+  launch_cn_dot(stream_, cn_.C, (int64_t)n, k, xd, ld, nv, n, cn_.part, kCnPass, false);
+  launch_cn_small(stream_, cn_.part, cn_nchunks(n), k, nv, cn_.G, e, lde, cn_.T, lambda, ldl);
+  launch_cn_apply(stream_, xd, ld, nv, n, cn_.U, (int64_t)n, k, cn_.T);
+  cn_.launches += 3;
+  return 0;
+}
+
+int Engine::constrain(int op, int nvec, double* x, int64_t ldx, const double* e, int64_t lde, double* lambda, int64_t ldl,
+                      bool dev, int64_t serial, uint64_t seed, uint64_t first, const double* mean) {
+  const int n = S_->n, k = cn_.k;
+  int rc;
+  if (!enter(op >= CN_CORRECT && op <= CN_SAMPLE && nvec >= 0 && x && ldx >= n && k > 0 && (lde == 0 || lde >= k) &&
+                 (!lambda || ldl >= k),
+             nvec == 0 || n == 0, &rc))
+    return rc;
+  cn_.launches = 0;
+  if (cn_.serial != serial && (rc = build_constraints(serial))) {
+    const std::string why = feature_err_;
+    if (!poisoned_) drop_constraints();
+    feature_err_ = why;
+    return rc;
+  }
+  if ((rc = prepare_solve_many(!dev))) return rc;
+  if (op == CN_SAMPLE && repro_on_ && (rc = prepare_solve_repro())) return rc;
+  double* estage = cn_.T + kCnPass * kCnMaxRows;
+  double* lstage = estage + kCnPass * kCnMaxRows;
+  const double* dmean = mean;
+  if (mean && !dev) {
+    if (!d_fmmean_) {
+      hipError_t me = dalloc((void**)&d_fmmean_, sizeof(double) * (size_t)n);
+      if (me != hipSuccess) {
+        (void)hipGetLastError();
+        d_fmmean_ = nullptr;
+        feature_err_ = std::string("sample_constrained: not enough device memory for the mean: ") + hipGetErrorString(me);
+        return alloc_code(me);
+      }
+    }
+    HIPCHK(hipMemcpyAsync(d_fmmean_, mean, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream_), "mean H2D");
+    dmean = d_fmmean_;
+  }
+  if (e && !dev && lde == 0 && (rc = copy_vectors_to_device(estage, e, (int64_t)k, 1, "constrain e H2D", (int64_t)k))) return rc;
+  rc = for_each_block(nvec, kCnPass, [&](int done, int nv, int) -> int {
+    int r = 0;
+    double* xd = dev ? x + (int64_t)done * ldx : d_smstage_;
+    const int64_t ld = dev ? ldx : (int64_t)n;
+    if (!dev && op != CN_SAMPLE && (r = copy_vectors(true, d_smstage_, x + (int64_t)done * ldx, ldx, nv, "constrain H2D"))) return r;
+    if (op == CN_SOLVE) {
+      if ((r = solve_many_dev(xd, nv, ld, 0, false))) return r;
+    } else if (op == CN_SAMPLE) {
+      launch_white_noise(stream_, xd, ld, d_order_, n, nv, seed, first + (uint64_t)done);
+      if ((r = repro_on_ ? solve_repro_dev(xd, nv, ld, 2, false) : solve_many_dev(xd, nv, ld, 2, false))) return r;
+      if (dmean) launch_add_mean(stream_, xd, ld, dmean, n, nv);
+    }
+    const double* ep = e;
+    int64_t le = lde;
+    if (e && dev) {
+      ep = e + (int64_t)done * lde;
+    } else if (e) {
+      if (lde != 0 && (r = copy_vectors_to_device(estage, e + (int64_t)done * lde, lde, nv, "constrain e H2D", (int64_t)k)))
+        return r;
+      ep = estage;
+      le = lde ? (int64_t)k : 0;
+    }
+    double* lp = !lambda ? nullptr : dev ? lambda + (int64_t)done * ldl : lstage;
+    cn_pass(xd, ld, nv, ep, le, lp, dev ? ldl : (int64_t)k);
+    if (!dev) {
+      HIPCHK(hipGetLastError(), "constrain launch");
+      if ((r = copy_vectors(false, d_smstage_, x + (int64_t)done * ldx, ldx, nv, "constrain D2H"))) return r;
+      if (lambda && (r = copy_vectors(false, lstage, lambda + (int64_t)done * ldl, ldl, nv, "constrain lambda D2H", (int64_t)k)))
+        return r;
+      if ((r = sync_stream(stream_, "constrain sync"))) return r;
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  HIPCHK(hipGetLastError(), "constrain launch");
+  return sync_stream(stream_, "constrain sync");
+}
+
+int Engine::inverse_diag_constrained(double* out, int n, int64_t serial) {
+  int rc;
+  if (!enter(z_valid_ && out && n == S_->n && cn_.k > 0, false, &rc)) return rc;
+  cn_.launches = 0;
+  if (cn_.serial != serial && (rc = build_constraints(serial))) {
+    const std::string why = feature_err_;
+    if (!poisoned_) drop_constraints();
+    feature_err_ = why;
+    return rc;
+  }
+  launch_selinv_diag_gather(stream_, d_Z_, d_sidiag_, d_order_, n, d_siout_);
+  launch_cn_var(stream_, d_siout_, cn_.U, (int64_t)n, n, cn_.k, d_siout_);
+  ++cn_.launches;
+  HIPCHK(hipGetLastError(), "constrained diag launch");
+  HIPCHK(hipMemcpyAsync(out, d_siout_, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, stream_), "constrained diag D2H");
+  return sync_stream(stream_, "constrained diag sync");
+}
+
 }  // namespace spx

@@ -336,5 +336,30 @@ int launch_batch_add_mean(hipStream_t st, const BmultView& v, double* x, int64_t
                           int64_t ldmean, int n, int nvec);
 void launch_expand_buffer(hipStream_t st, double* a, int blkn, const int* row_list, int rls,
                           const int* col_list, int cls, int ndiag, const double* buffer);
+// ---- hard linear constraints C x = e (constrain.hip; user order throughout, no atomic add) ---------------------
+// C: k <= kCnMaxRows rows of n at C + i * ldc; vectors as solve_many (vector q at X + q * ldx); U as the vectors (column j
+// at U + j * ldu); G: the lower Cholesky factor of S = C W, G[i * kCnMaxRows + j], zero above the diagonal and behind k.
+// The n positions are cut into chunks of cn_chunk(n) (a multiple of 64; at most 256 chunks): a product's partial
+// of chunk c is part[(c * kCnMaxRows + i) * ldp + q], ldp = kCnPass for a pass of vectors and kCnMaxRows for S.
+constexpr int kCnMaxRows = 64, kCnPass = 32;
+int cn_chunk(int n);
+inline int cn_nchunks(int n) { return n > 0 ? (n + cn_chunk(n) - 1) / cn_chunk(n) : 0; }
+// part = C X^T per chunk for nv <= ldp vectors; lower: only the 16 x 16 tiles on and below the diagonal (S = C W)
+void launch_cn_dot(hipStream_t st, const double* C, int64_t ldc, int k, const double* X, int64_t ldx, int nv, int n,
+                   double* part, int ldp, bool lower);
+// S = the sum of the partials in chunk order (lower triangle, mirrored), S = G G^T in one workgroup.  stat[0] = log det S,
+// stat[1] = min_j pivot_j / S_jj, stat[2] = 0 or the 1-based row j whose pivot is <= 2^-26 S_jj or not finite
+void launch_cn_chol(hipStream_t st, const double* part, int nchunks, int k, double* G, double* stat);
+// U <- U G^-T in place (on entry U = W): every position an independent forward substitution over k
+void launch_cn_scale(hipStream_t st, double* U, int64_t ldu, int n, int k, const double* G);
+// r = (the sum of the partials in chunk order) - e, t = G^-1 r into T[q * kCnMaxRows + j] (zero behind k and nv), and
+// lambda[q * ldl + j] = (G^-T t)_j when lambda is given.  e: null (zeros), lde = 0 (shared) or per vector.
+void launch_cn_small(hipStream_t st, const double* part, int nchunks, int k, int nv, const double* G, const double* e,
+                     int64_t lde, double* T, double* lambda, int64_t ldl);
+// X[q * ldx + p] -= sum_j U[j * ldu + p] T[q * kCnMaxRows + j], q < nv <= kCnPass: one read and one write of X
+void launch_cn_apply(hipStream_t st, double* X, int64_t ldx, int nv, int n, const double* U, int64_t ldu, int k,
+                     const double* T);
+// out[i] = zdiag[i] - sum_j U[j * ldu + i]^2, j ascending (out may be zdiag)
+void launch_cn_var(hipStream_t st, const double* zdiag, const double* U, int64_t ldu, int n, int k, double* out);
 
 }  // namespace spx

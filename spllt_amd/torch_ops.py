@@ -67,6 +67,7 @@ class SparseCholesky:
         self.device = None            # the device of the first tensor; the engine is created there
         self._stream = None
         self._weight = None           # 2 - delta_ij per entry of val
+        self._C = None                # set_constraints: (the rows, whether the handle has them)
         self.invalidate()
 
     # ---- checks: before any library call ----------------------------------------------------------
@@ -261,16 +262,96 @@ class SparseCholesky:
             vt = V.reshape(self.n, -1).t().contiguous()
             return self._outer(ut, vt, float(alpha))
 
-    def sample(self, val, nsamp, seed=0, kind="precision", mean=None):
+    def set_constraints(self, C):
+        """Hard linear constraints C x = e for ``solve_constrained`` and ``sample(..., constrained=True)``.  C: a
+        float64 device tensor (k, n), k <= 64, or None to clear them.  The rows are copied to the handle with the
+        next constrained operation (which has the factor they need); a later factorization is picked up by the
+        library.  WITHOUT GRADIENTS: nothing that passes through the constraints carries a gradient, neither to
+        val, nor to C, nor to B, mean or e."""
+        if C is None:
+            self._C = None
+            if self.device is not None:
+                with torch.cuda.device(self.device):
+                    self.f.release_constraints()
+            return self
+        self._tensor(C, "C", (None, self.n))
+        if not 1 <= C.shape[0] <= 64:
+            raise ValueError(f"C: expected 1 to 64 rows, got {C.shape[0]}")
+        self._C = (C.detach().contiguous().clone(), False)    # (rows, already on the handle)
+        return self
+
+    def _ensure_constraints(self):
+        """the stored rows on the handle (the current factor is on the device); returns k"""
+        if self._C is None:
+            raise RuntimeError("SparseCholesky: no constraints (call set_constraints first)")
+        rows, on_handle = self._C
+        if not on_handle:
+            self._sync()
+            with torch.cuda.device(self.device):
+                before = self.f.set_reproducible_solve(self.reproducible)
+                try:
+                    self.f.set_constraints_dev(rows.data_ptr(), rows.shape[0], ldc=self.n)
+                finally:
+                    self.f.set_reproducible_solve(before)
+            self._C = (rows, True)
+        return rows.shape[0]
+
+    def solve_constrained(self, val, B, e=None):
+        """x* = argmin 1/2 x^T A(val) x - B^T x subject to C x = e, for every column of B: the blocked solve, then
+        the correction, on device tensors in one library call.  B: (n,) or (n, nrhs); e: None (zeros) or (k,).
+        Returns (x*, lambda), lambda (k,) or (k, nrhs) the Lagrange multipliers.  WITHOUT GRADIENTS (see
+        set_constraints)."""
+        self._values(val, "val", (self.nnz,))
+        self._rhs(B, "B", val.device)
+        self._enter(val)
+        with torch.no_grad():
+            self._ensure_factor(val)
+            k = self._ensure_constraints()
+            if e is not None:
+                e = self._tensor(e, "e", (k,)).contiguous()
+            work = B.detach().reshape(self.n, -1).t().contiguous().clone()
+            lam = torch.empty((work.shape[0], k), dtype=torch.float64, device=self.device)
+            self._sync()
+            with torch.cuda.device(self.device):
+                self.f.constrain_dev(work.data_ptr(), work.shape[0], ldx=self.n, e_dev_ptr=None if e is None else e.data_ptr(),
+                                     lde=0, lambda_dev_ptr=lam.data_ptr(), ldl=k, entry="solve_constrained")
+        x, lam = work.t(), lam.t()
+        return (x[:, 0], lam[:, 0]) if B.dim() == 1 else (x, lam)
+
+    def sample(self, val, nsamp, seed=0, kind="precision", mean=None, constrained=False, e=None):
         """nsamp draws of N(mean, A(val)^-1) (kind "precision") or N(mean, A(val)) ("covariance") from the cached
         factor of val: a float64 device tensor (n, nsamp); sample q is a function of (seed, q) alone
         (Factorization.sample).  The result carries NO gradient to val -- pathwise derivatives through L are out of
         scope -- but it does carry the gradient to mean (the identity).  reproducible=True: the precision kind
-        goes through the reproducible solve and repeats bit for bit, like the covariance kind always does."""
+        goes through the reproducible solve and repeats bit for bit, like the covariance kind always does.
+        constrained=True (kind "precision" only): draws of N(mean, A(val)^-1) | C x = e for the rows of
+        set_constraints, e None (zeros) or (k,); WITHOUT GRADIENTS, to mean as well."""
         self._values(val, "val", (self.nnz,))
         if mean is not None:
             self._tensor(mean, "mean", (self.n,), val.device)
         self._enter(val)
+        if constrained:
+            if kind != "precision":
+                raise ValueError("sample: constrained=True needs kind='precision'")
+            with torch.no_grad():
+                self._ensure_factor(val)
+                k = self._ensure_constraints()
+                if e is not None:
+                    e = self._tensor(e, "e", (k,)).contiguous()
+                m = None if mean is None else mean.detach().contiguous()
+                work = torch.empty((int(nsamp), self.n), dtype=torch.float64, device=self.device)
+                self._sync()
+                with torch.cuda.device(self.device):
+                    before = self.f.set_reproducible_solve(self.reproducible)
+                    try:
+                        self.f.sample_constrained_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed,
+                                                      mean_dev_ptr=None if m is None else m.data_ptr(),
+                                                      e_dev_ptr=None if e is None else e.data_ptr())
+                    finally:
+                        self.f.set_reproducible_solve(before)
+            return work.t()
+        if e is not None:
+            raise ValueError("sample: e needs constrained=True")
         with torch.no_grad():
             self._ensure_factor(val)
             work = torch.empty((int(nsamp), self.n), dtype=torch.float64, device=self.device)
