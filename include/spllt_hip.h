@@ -330,7 +330,10 @@ int spllt_hip_release_solve_repro(void *fkeep);   /* tables and scratch back to 
  * partitioned handle -> SPLLT_ERROR_UNIMPLEMENTED; no device memory for blocks of 16 either ->
  * SPLLT_ERROR_ALLOCATION (nothing is kept half-allocated, the factor and every solve stay usable).
  * Debug: spllt_hip_debug("fmult_poison=1") fills the scratch with NaN before every direction ("=0": off);
- * "fmult_alloc_fail=N" makes the next N allocations of the second workspace and the scratch fail. */
+ * "fmult_alloc_fail=N" makes the next N allocations of the second workspace and the scratch fail;
+ * "alloc_fail_at=K" makes the K-th allocation of any optional feature's device memory from now on fail once
+ * (0: off; "alloc_fail_armed" returns 1 while it still waits).  spllt_hip_program_get "owned" returns two
+ * int64: the device buffers the handle's engine holds and their bytes. */
 int spllt_hip_factor_mult(void *fkeep, int nvec, double *x_host, int64_t ldx, int job);      /* host, user order */
 int spllt_hip_factor_mult_dev(void *fkeep, int nvec, double *x_dev, int64_t ldx, int job,
                               int pivot_order);   /* device; 0 = user order, 1 = pivot order */

@@ -164,6 +164,8 @@ class Factorization:
         raw = raw[:nbytes]
         if name == "solve_sparse_host_us":
             return int(raw.view(np.int64)[0])
+        if name == "owned":              # entries of the engine's ledger of device buffers, their bytes
+            return raw.view(np.int64)
         if name == "matvec_rowptr":      # the operator of the refined solves
             return raw.view(np.int64)
         if name in ("matvec_col", "matvec_src"):

@@ -723,6 +723,8 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 //                           hardware limit again)
 //   fmult_alloc_fail=N      the next N allocations of the products' second workspace and scratch fail (those of
 //                           the batched products and the workspace of the batched blocked solve included)
+//   alloc_fail_at=K         the K-th allocation of feature memory from now on fails once with "out of memory" and the
+//                           hook disarms itself (0 disarms it); "alloc_fail_armed" reads whether it still waits
 //   batch_selinv_fused=0|1  0 forces the three-launch form of every step of the batched selected inversion
 //   batch_fadj_fused=0|1    1 runs the eligible steps of the factor adjoint of a batch as one fused launch each (default 0)
 //   rsolve_poison=0|1       1 fills the scratch of the reproducible solve with NaN before every sweep
@@ -735,11 +737,13 @@ int spllt_hip_debug(const char* what) {
   if (w == "wedge") { mark_runtime_wedged(); return 0; }
   if (w == "wedged") return runtime_wedged() ? 1 : 0;
   if (w == "teardown") { run_pools_teardown_for_test(); return 0; }
+  if (w == "alloc_fail_armed") return alloc_fail_armed() ? 1 : 0;
   const size_t eq = w.find('=');
   if (eq == std::string::npos) return -1;
   const std::string name = w.substr(0, eq), value = w.substr(eq + 1);
   if (name == "batch_grid_limit") { set_batch_grid_limit(std::atoll(value.c_str())); return 0; }
   if (name == "fmult_alloc_fail") { set_fmult_alloc_fail(std::atoi(value.c_str())); return 0; }
+  if (name == "alloc_fail_at") { set_alloc_fail_at(std::atoi(value.c_str())); return 0; }
   static const struct { const char* name; void (*set)(bool); } kSwitches[] = {
       {"batch_selinv_fused", set_batch_selinv_fused}, {"batch_fadj_fused", set_batch_fadj_fused},
       {"rsolve_poison", set_rsolve_poison},
@@ -2025,6 +2029,11 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
     return Out{cap >= (int64_t)sizeof v ? buf : nullptr, cap}.bytes(&v, sizeof v);
   }
   const Out o{buf, cap};
+  if (k == "owned") {   // (entries of the engine's ledger of device buffers and their bytes: host state only)
+    int64_t v[2] = {0, 0};
+    if (f->eng) f->eng->owned_info(v);
+    return o.bytes(v, sizeof v);
+  }
   if (is("pattern_")) return get_pattern(f, k, o);
   if (is("matvec_")) return get_matvec(f, k, o);
   // The program can be inspected without a GPU: build it on demand.

@@ -289,10 +289,7 @@ hipError_t Engine::ensure_order() {
   std::vector<int> order(S_->order.begin(), S_->order.end());
   if (order.empty()) order.push_back(0);
   hipError_t e = dev_upload(&d_order_, order);
-  if (e != hipSuccess) {
-    release_buffer(d_order_);
-    d_order_ = nullptr;
-  }
+  if (e != hipSuccess) give_back(d_order_);
   return e;
 }
 
@@ -1402,18 +1399,24 @@ int Engine::prepare_selinv() {
   tab.add(&d_sirelpos_, siprog_.relpos);
   tab.add(&d_sidiag_, siprog_.diag_pos);
   // (a failure here leaves the factor and the solve usable: the engine's status is not touched)
-  hipError_t e = tab.commit(&d_selinv_tables_, [this](void** q, size_t b) { return dalloc(q, b); });
-  if (e == hipSuccess) e = ensure_order();
-  if (e == hipSuccess) e = dalloc((void**)&d_siout_, sizeof(double) * ((size_t)S.n + 1));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (d_selinv_tables_) { release_buffer(d_selinv_tables_); d_selinv_tables_ = nullptr; }
+  auto t = take();
+  t.tables(tab, &d_selinv_tables_);
+  if (t.ok()) t.check(ensure_order());
+  t(&d_siout_, sizeof(double) * ((size_t)S.n + 1));
+  if (!t.ok()) {
     feature_err_ = std::string("selected inversion: not enough device memory for the program tables (") +
-                   hipGetErrorString(e) + ")";
-    return alloc_code(e);
+                   hipGetErrorString(t.error()) + ")";
+    return alloc_code(t.error());
   }
+  t.commit();
   selinv_ready_ = true;
   return 0;
+}
+
+void Engine::owned_info(int64_t out[2]) const {
+  out[0] = (int64_t)owned_.size();
+  out[1] = 0;
+  for (const auto& b : owned_) out[1] += (int64_t)b.second;
 }
 
 void Engine::release_buffer(void* p) {
@@ -1432,19 +1435,20 @@ int Engine::selected_inverse() {
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   int rc = prepare_selinv();
   if (rc) return rc;
-  if (!d_Z_ || !d_siscratch_) {
+  if (!d_Z_) {
     // the Z arena (L's size) and the scratch: a failure here leaves the factor usable
     const size_t zb = sizeof(double) * (size_t)std::max<int64_t>(1, S_->arena);
     const size_t sb = sizeof(double) * (size_t)std::max<int64_t>(1, siprog_.scratch_size);
-    hipError_t e = d_Z_ ? hipSuccess : dalloc((void**)&d_Z_, zb);
-    if (e == hipSuccess && !d_siscratch_) e = dalloc((void**)&d_siscratch_, sb);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      if (d_Z_) { release_buffer(d_Z_); d_Z_ = nullptr; }
+    auto t = take();
+    t(&d_Z_, zb);
+    if (!d_siscratch_) t(&d_siscratch_, sb);
+    if (!t.ok()) {
       feature_err_ = "selected inversion: not enough device memory for the inverse arena (" + std::to_string(zb >> 20) +
                      " MiB) and its scratch (" + std::to_string(sb >> 20) + " MiB)";
       return -1;
     }
+    t.commit();
+    si_users_.hold();
   }
   z_valid_ = false;
   for (const SelinvLaunch& l : siprog_.launches)
@@ -1494,11 +1498,8 @@ int Engine::release_inverse() {
   if (d_Z_) {
     HIPCHK(hipSetDevice(device_), "hipSetDevice");
     if (int rc = sync_stream(stream_, "selinv release")) return rc;
-    release_buffer(d_Z_);
-    if (!d_G_) release_buffer(d_siscratch_);   // (the factor adjoint shares the scratch)
-    if (d_sipat_) release_buffer(d_sipat_);
-    d_Z_ = d_sipat_ = nullptr;
-    if (!d_G_) d_siscratch_ = nullptr;
+    give_back(d_Z_, d_sipat_);
+    si_users_.drop([this] { give_back(d_siscratch_); });
   }
   return 0;
 }
@@ -1520,13 +1521,13 @@ int Engine::prepare_fadj_tables() {
     tab.add(&d_facols_, cols);
     tab.add(&d_fatiles_, tiles);
     tab.add(&d_faporder_, S.porder);
-    hipError_t e = tab.commit(&d_fadj_tables_, [this](void** q, size_t b) { return dalloc(q, b); });
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      if (d_fadj_tables_) { release_buffer(d_fadj_tables_); d_fadj_tables_ = nullptr; }
-      feature_err_ = std::string("factor adjoint: not enough device memory for the seed tables (") + hipGetErrorString(e) + ")";
-      return alloc_code(e);
+    auto t = take();
+    t.tables(tab, &d_fadj_tables_);
+    if (!t.ok()) {
+      feature_err_ = std::string("factor adjoint: not enough device memory for the seed tables (") + hipGetErrorString(t.error()) + ")";
+      return alloc_code(t.error());
     }
+    t.commit();
     fa_ntiles_ = (int64_t)tiles.size();
   }
   return 0;
@@ -1537,19 +1538,19 @@ int Engine::prepare_fadj() {
   if (rc) return rc;
   if ((rc = prepare_fadj_tables())) return rc;
   const Symbolic& S = *S_;
-  if (!d_G_ || !d_siscratch_) {
+  if (!d_G_) {   // (hence unseeded)
     const size_t gb = sizeof(double) * (size_t)std::max<int64_t>(1, S.arena);
     const size_t sb = sizeof(double) * (size_t)std::max<int64_t>(1, siprog_.scratch_size);
-    const bool had_g = d_G_ != nullptr;
-    hipError_t e = d_G_ ? hipSuccess : dalloc((void**)&d_G_, gb);
-    if (e == hipSuccess && !d_siscratch_) e = dalloc((void**)&d_siscratch_, sb);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      if (d_G_ && !had_g) { release_buffer(d_G_); d_G_ = nullptr; fadj_state_ = FADJ_UNSEEDED; }
+    auto t = take();
+    t(&d_G_, gb);
+    if (!d_siscratch_) t(&d_siscratch_, sb);
+    if (!t.ok()) {
       feature_err_ = "factor adjoint: not enough device memory for the adjoint arena (" + std::to_string(gb >> 20) +
                      " MiB) and the scratch (" + std::to_string(sb >> 20) + " MiB)";
       return -1;
     }
+    t.commit();
+    si_users_.hold();
   }
   return 0;
 }
@@ -1572,12 +1573,13 @@ int Engine::fadj_seed(int nvec, const double* a, const double* b, int64_t ld, do
   const double *ad = a, *bd = b;
   int64_t ldd = ld;
   if (!dev && nvec > 0 && n > 0) {
-    hipError_t e = dalloc((void**)&stage, sizeof(double) * 2 * (size_t)nvec * (size_t)n);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      feature_err_ = std::string("factor adjoint: not enough device memory to stage the seed vectors (") + hipGetErrorString(e) + ")";
-      return alloc_code(e);
+    auto t = take();
+    t(&stage, sizeof(double) * 2 * (size_t)nvec * (size_t)n);
+    if (!t.ok()) {
+      feature_err_ = std::string("factor adjoint: not enough device memory to stage the seed vectors (") + hipGetErrorString(t.error()) + ")";
+      return alloc_code(t.error());
     }
+    t.commit();   // (returned below, once the stream has drained)
     if ((rc = copy_vectors(true, stage, const_cast<double*>(a), ld, nvec, "seed H2D"))) return rc;
     if ((rc = copy_vectors(true, stage + (int64_t)nvec * n, const_cast<double*>(b), ld, nvec, "seed H2D"))) return rc;
     ad = stage;
@@ -1589,7 +1591,7 @@ int Engine::fadj_seed(int nvec, const double* a, const double* b, int64_t ld, do
                    accumulate, order_flags);
   HIPCHK(hipGetLastError(), "factor adjoint seed launch");
   rc = sync_stream(stream_, "factor adjoint seed sync");
-  if (stage && !rc) release_buffer(stage);
+  if (!rc) give_back(stage);
   if (rc) return rc;
   fadj_state_ = FADJ_SEEDED;
   return 0;
@@ -1632,13 +1634,13 @@ int Engine::fadj_sweep(double* gval, bool dev) {
   if (rc) return rc;
   const int64_t nnz = S_->nnzA;
   if (!dev && !d_gpat_ && nnz > 0) {
-    hipError_t e = dalloc((void**)&d_gpat_, sizeof(double) * (size_t)nnz);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      d_gpat_ = nullptr;
-      feature_err_ = std::string("factor adjoint: not enough device memory for the gathered gradient (") + hipGetErrorString(e) + ")";
-      return alloc_code(e);
+    auto t = take();
+    t(&d_gpat_, sizeof(double) * (size_t)nnz);
+    if (!t.ok()) {
+      feature_err_ = std::string("factor adjoint: not enough device memory for the gathered gradient (") + hipGetErrorString(t.error()) + ")";
+      return alloc_code(t.error());
     }
+    t.commit();
   }
   fadj_state_ = FADJ_UNSEEDED;   // (a sweep that fails half way leaves nothing to read)
   for (const SelinvLaunch& l : siprog_.launches)
@@ -1661,10 +1663,8 @@ int Engine::release_factor_adjoint() {
   if (d_G_) {
     HIPCHK(hipSetDevice(device_), "hipSetDevice");
     if (int rc = sync_stream(stream_, "factor adjoint release")) return rc;
-    release_buffer(d_G_);
-    d_G_ = nullptr;
-    if (d_gpat_) { release_buffer(d_gpat_); d_gpat_ = nullptr; }
-    if (!d_Z_ && d_siscratch_) { release_buffer(d_siscratch_); d_siscratch_ = nullptr; }
+    give_back(d_G_, d_gpat_);
+    si_users_.drop([this] { give_back(d_siscratch_); });
   }
   return 0;
 }
@@ -1691,13 +1691,13 @@ int Engine::inverse_on_pattern(double* out) {
   if (nnz == 0) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (!d_sipat_) {
-    hipError_t e = dalloc((void**)&d_sipat_, sizeof(double) * (size_t)nnz);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      d_sipat_ = nullptr;
-      feature_err_ = std::string("inverse on pattern: not enough device memory for the gathered entries (") + hipGetErrorString(e) + ")";
+    auto t = take();
+    t(&d_sipat_, sizeof(double) * (size_t)nnz);
+    if (!t.ok()) {
+      feature_err_ = std::string("inverse on pattern: not enough device memory for the gathered entries (") + hipGetErrorString(t.error()) + ")";
       return -1;
     }
+    t.commit();
   }
   if (int rc = gather_inverse_on_pattern(d_sipat_)) return rc;
   return staged_d2h(out, d_sipat_, sizeof(double) * (size_t)nnz);
@@ -1730,15 +1730,14 @@ int Engine::pattern_outer(int nbatch, int nvec, const double* u, int64_t ldu, co
     TableStager tab;
     tab.add(&d_porow_, row);
     tab.add(&d_pocol_, col);
-    hipError_t e = tab.commit(&d_potab_, [this](void** q, size_t b) { return dalloc(q, b); });
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      if (d_potab_) release_buffer(d_potab_);
-      d_potab_ = nullptr;
+    auto t = take();
+    t.tables(tab, &d_potab_);
+    if (!t.ok()) {
       feature_err_ = std::string("pattern outer product: not enough device memory for the tables of the pattern (") +
-                     hipGetErrorString(e) + ")";
-      return alloc_code(e);
+                     hipGetErrorString(t.error()) + ")";
+      return alloc_code(t.error());
     }
+    t.commit();
   }
   const int64_t nv = (int64_t)nbatch * nvec;
   const double *du = u, *dv = v;
@@ -1748,21 +1747,13 @@ int Engine::pattern_outer(int nbatch, int nvec, const double* u, int64_t ldu, co
     // the caller's arrays packed: 2 nv vectors of n doubles, then nbatch rows of nnz doubles
     const size_t need = 2 * (size_t)nv * (size_t)n + (size_t)nbatch * (size_t)nnz;
     if (need > po_stage_elems_ || !d_postage_) {
-      if (d_postage_) {
+      if (d_postage_)
         if (int rc = sync_stream(stream_, "pattern outer product staging")) return rc;
-        release_buffer(d_postage_);
-      }
-      d_postage_ = nullptr;
-      po_stage_elems_ = 0;
-      hipError_t e = dalloc((void**)&d_postage_, sizeof(double) * need);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        d_postage_ = nullptr;
+      if (const hipError_t e = grow(&d_postage_, &po_stage_elems_, need)) {
         feature_err_ = "pattern outer product: not enough device memory to stage the vectors (" +
                        std::to_string((sizeof(double) * need) >> 20) + " MiB): " + hipGetErrorString(e);
         return alloc_code(e);
       }
-      po_stage_elems_ = need;
     }
     double* su = d_postage_;
     double* sv = su + (size_t)nv * (size_t)n;
@@ -1837,31 +1828,24 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   double* d_val = nullptr;
   {
     // a failure leaves the factor and every solve usable, and nothing of this call allocated
-    const bool had = d_udW_ != nullptr;
-    hipError_t e = hipSuccess;
-    if (!had) {
-      e = dalloc((void**)&d_udW_, wb);
-      if (e == hipSuccess) e = dalloc((void**)&d_udcoef_, cb);
-      if (e == hipSuccess) e = hipMemsetAsync(d_udW_, 0, wb, stream_);
+    auto t = take();
+    if (!d_udW_) {
+      t(&d_udW_, wb);
+      t(&d_udcoef_, cb);
+      if (t.ok()) t.check(hipMemsetAsync(d_udW_, 0, wb, stream_));
     }
-    if (e == hipSuccess) e = dalloc((void**)&d_pos, pb);
-    if (e == hipSuccess) e = dalloc((void**)&d_val, vb);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pos, pos.data(), pb, hipMemcpyHostToDevice, stream_);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_val, val.data(), vb, hipMemcpyHostToDevice, stream_);
-    if (e != hipSuccess) {
+    t(&d_pos, pb);
+    t(&d_val, vb);
+    if (t.ok()) t.check(hipMemcpyAsync(d_pos, pos.data(), pb, hipMemcpyHostToDevice, stream_));
+    if (t.ok()) t.check(hipMemcpyAsync(d_val, val.data(), vb, hipMemcpyHostToDevice, stream_));
+    if (!t.ok()) {
       (void)hipGetLastError();
-      (void)sync_stream(stream_, "update staging");
-      if (d_val) release_buffer(d_val);
-      if (d_pos) release_buffer(d_pos);
-      if (!had) {
-        if (d_udcoef_) release_buffer(d_udcoef_);
-        if (d_udW_) release_buffer(d_udW_);
-        d_udW_ = d_udcoef_ = nullptr;
-      }
+      (void)sync_stream(stream_, "update staging");   // (before the roll-back returns what a copy may still write)
       feature_err_ = "update: not enough device memory for the work array (" + std::to_string(wb >> 10) +
-                     " KiB), the coefficient scratch and the entries of W: " + hipGetErrorString(e);
-      return alloc_code(e);
+                     " KiB), the coefficient scratch and the entries of W: " + hipGetErrorString(t.error());
+      return alloc_code(t.error());
     }
+    t.commit();
   }
   int* d_flag = reinterpret_cast<int*>(d_udcoef_ + (size_t)maxw * kUpdownVec * 3);
   int64_t launches = 0;
@@ -1891,16 +1875,13 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   if (le == hipSuccess) le = hipEventRecord(ev1_, stream_);
   if (le == hipSuccess) le = hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, stream_);
   rc = sync_stream(stream_, "update sync");
-  release_buffer(d_val);
-  release_buffer(d_pos);
+  give_back(d_val, d_pos);
   z_valid_ = false;
   fadj_state_ = FADJ_UNSEEDED;
   if (le != hipSuccess || rc) {
     // the sweep did not finish: the arena is half modified and the work array may not be zero
     ud_invalid_ = true;
-    if (d_udW_) release_buffer(d_udW_);
-    if (d_udcoef_) release_buffer(d_udcoef_);
-    d_udW_ = d_udcoef_ = nullptr;
+    give_back(d_udW_, d_udcoef_);
     return le != hipSuccess ? fail(kErrHip, "update launch", le) : rc;
   }
   float ms = 0;
@@ -2013,14 +1994,14 @@ int Engine::prepare_batch() {
   tab.add(&bt_.slist, bt_.sprog.diag_list);
   tab.add(&bt_.stiles, bt_.sprog.tiles);
   // (a failure here leaves the single factorization usable: the engine's status is not touched)
-  hipError_t e = tab.commit(&bt_.d_tab, [this](void** q, size_t b) { return dalloc(q, b); });
-  if (e == hipSuccess) e = ensure_order();
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (bt_.d_tab) { release_buffer(bt_.d_tab); bt_.d_tab = nullptr; }
-    feature_err_ = std::string("batched factorization: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
-    return alloc_code(e);
+  auto t = take();
+  t.tables(tab, &bt_.d_tab);
+  if (t.ok()) t.check(ensure_order());
+  if (!t.ok()) {
+    feature_err_ = std::string("batched factorization: the program tables could not be uploaded (") + hipGetErrorString(t.error()) + ")";
+    return alloc_code(t.error());
   }
+  t.commit();
   if (!bt_.own_init) {
     bt_.init_cptr = d_init_cptr_;
     bt_.init_loc = d_init_loc_;
@@ -2035,49 +2016,35 @@ int Engine::prepare_batch() {
 // arenas, dinv scratch, flags and log-det slots for nbatch members; all or nothing
 int Engine::reserve_batch(int nbatch) {
   if (nbatch <= bt_.capacity) return 0;
-  auto drop = [this]() {
-    for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out})
-      if (p) release_buffer(p);
-    bt_.L = bt_.dinv = bt_.out = nullptr;
-    bt_.flag = nullptr;
-    bt_.capacity = bt_.nbatch = 0;
-    bt_.hflag.clear();
-  };
-  drop();
+  give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out);   // (a larger batch: everything again)
+  bt_.capacity = bt_.nbatch = 0;
+  bt_.hflag.clear();
   // member strides: multiples of 32 doubles, so that every member starts 256-byte aligned
   bt_.lstride = std::max<int64_t>(32, (S_->arena + 31) / 32 * 32);
   bt_.dstride = std::max<int64_t>(32, (bt_.prog.dinv_size + 31) / 32 * 32);
   const size_t lb = sizeof(double) * (size_t)bt_.lstride * (size_t)nbatch;
   const size_t db = sizeof(double) * (size_t)bt_.dstride * (size_t)nbatch;
-  hipError_t e = dalloc((void**)&bt_.L, lb);
-  if (e == hipSuccess) e = dalloc((void**)&bt_.dinv, db);
-  if (e == hipSuccess) e = dalloc((void**)&bt_.flag, sizeof(int) * (size_t)nbatch);
-  if (e == hipSuccess) e = dalloc((void**)&bt_.out, sizeof(double) * (size_t)nbatch);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    drop();
+  auto t = take();
+  t(&bt_.L, lb);
+  t(&bt_.dinv, db);
+  t(&bt_.flag, sizeof(int) * (size_t)nbatch);
+  t(&bt_.out, sizeof(double) * (size_t)nbatch);
+  if (!t.ok()) {
     feature_err_ = "batched factorization: not enough device memory for " + std::to_string(nbatch) + " members (" +
-                   std::to_string((lb + db) >> 20) + " MiB): " + hipGetErrorString(e);
-    return alloc_code(e);
+                   std::to_string((lb + db) >> 20) + " MiB): " + hipGetErrorString(t.error());
+    return alloc_code(t.error());
   }
+  t.commit();
   bt_.capacity = nbatch;
   return 0;
 }
 
 int Engine::grow_batch_buffer(double** p, size_t* have, size_t need, const char* what) {
-  if (need <= *have && *p) return 0;
-  if (*p) release_buffer(*p);
-  *p = nullptr;
-  *have = 0;
-  hipError_t e = dalloc((void**)p, sizeof(double) * std::max<size_t>(need, 1));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
+  if (const hipError_t e = grow(p, have, need)) {
     feature_err_ = std::string("batch: not enough device memory for ") + what + " (" +
                    std::to_string((sizeof(double) * need) >> 20) + " MiB): " + hipGetErrorString(e);
     return alloc_code(e);
   }
-  *have = need;
   return 0;
 }
 
@@ -2218,17 +2185,15 @@ int Engine::release_batch() {
   bt_.z_valid = false;
   bt_.g_state = FADJ_UNSEEDED;
   bt_.fa_launches = 0;
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bt_.siscratch && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brf_ready_ && !d_brfval_) { bt_.nbatch = 0; return 0; }
+  // (the batch's own storage, and what its features say of theirs)
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brf_held()) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
   drop_solve_many_batch();    // (... and that of the blocked solve)
   drop_refine_batch();        // (... and those of the refined solves)
-  for (void* p : {(void*)bt_.L, (void*)bt_.dinv, (void*)bt_.flag, (void*)bt_.out, (void*)bt_.Y, (void*)bt_.stage,
-                  (void*)bt_.Z, (void*)bt_.G, (void*)bt_.siscratch})
-    if (p) release_buffer(p);
-  bt_.L = bt_.dinv = bt_.out = bt_.Y = bt_.stage = bt_.Z = bt_.G = bt_.siscratch = nullptr;
-  bt_.flag = nullptr;
+  give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, bt_.Y, bt_.stage, bt_.Z, bt_.G, bt_.siscratch);
+  bt_.sc_users = Shared{};
   bt_.z_capacity = bt_.g_capacity = bt_.sc_capacity = 0;
   bt_.si_launches = 0;
   bt_.capacity = bt_.nbatch = 0;
@@ -2279,72 +2244,55 @@ int Engine::prepare_batch_selinv() {
   tab.add(&bt_.sitiles, P.tiles);
   tab.add(&bt_.sirows, P.rows);
   tab.add(&bt_.sirelpos, P.relpos);
-  hipError_t e = tab.commit(&bt_.d_sitab, [this](void** q, size_t b) { return dalloc(q, b); });
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (bt_.d_sitab) { release_buffer(bt_.d_sitab); bt_.d_sitab = nullptr; }
-    feature_err_ = std::string("batched selected inversion: the program tables could not be uploaded (") + hipGetErrorString(e) + ")";
-    return alloc_code(e);
+  auto t = take();
+  t.tables(tab, &bt_.d_sitab);
+  if (!t.ok()) {
+    feature_err_ = std::string("batched selected inversion: the program tables could not be uploaded (") + hipGetErrorString(t.error()) + ")";
+    return alloc_code(t.error());
   }
+  t.commit();
   bt_.sstride = std::max<int64_t>(32, (P.scratch_size + 31) / 32 * 32);
   bt_.si_ready = true;
   return 0;
 }
 
-// the step scratch of the batch's SelinvProgram for nbatch members: shared by the inversion and the factor
-// adjoint (a step leaves nothing in it), taken by whoever comes first
-hipError_t Engine::reserve_batch_scratch(int nbatch) {
-  if (nbatch <= bt_.sc_capacity && bt_.siscratch) return hipSuccess;
-  if (bt_.siscratch) release_buffer(bt_.siscratch);
-  bt_.siscratch = nullptr;
-  bt_.sc_capacity = 0;
-  hipError_t e = dalloc((void**)&bt_.siscratch, sizeof(double) * (size_t)bt_.sstride * (size_t)nbatch);
-  if (e != hipSuccess) {
-    bt_.siscratch = nullptr;
-    return e;
-  }
-  bt_.sc_capacity = nbatch;
-  return hipSuccess;
-}
-
-// One set of arenas of the batch (Z or G: *capacity x lstride doubles) and the step scratch for nbatch members; all or
-// nothing: a failure keeps neither the arenas nor -- unless `other`, the set that shares it, is held -- the scratch,
-// and leaves the batch factor usable.  *retaken: the arenas are new memory (what they held is gone).
-int Engine::reserve_batch_arenas(double** arena, int* capacity, const double* other, int nbatch, const char* feature,
-                                 const char* which, bool* retaken) {
+// One set of arenas of the batch (Z or G: *capacity x lstride doubles) and the step scratch for nbatch members.  The
+// scratch is shared by the inversion and the factor adjoint (a step leaves nothing in it): each set of arenas is a
+// user of it while it is held.  All or nothing: a failure keeps neither the arenas nor this set's hold of the
+// scratch, and leaves the batch factor usable.  *retaken: the arenas are new memory (what they held is gone).
+int Engine::reserve_batch_arenas(double** arena, int* capacity, int nbatch, const char* feature, const char* which,
+                                 bool* retaken) {
   *retaken = false;
   if (nbatch <= *capacity && *arena && nbatch <= bt_.sc_capacity && bt_.siscratch) return 0;
-  const size_t ab = sizeof(double) * (size_t)bt_.lstride * (size_t)nbatch;
-  const size_t sb = sizeof(double) * (size_t)bt_.sstride * (size_t)nbatch;
+  const size_t an = (size_t)bt_.lstride * (size_t)nbatch, sn = (size_t)bt_.sstride * (size_t)nbatch;
+  const bool held = *arena != nullptr;   // (this set is a user of the scratch already)
+  size_t have = (size_t)bt_.lstride * (size_t)*capacity, sc_have = (size_t)bt_.sstride * (size_t)bt_.sc_capacity;
   hipError_t e = hipSuccess;
   if (nbatch > *capacity || !*arena) {
-    if (*arena) release_buffer(*arena);
-    *arena = nullptr;
-    *capacity = 0;
     *retaken = true;
-    e = dalloc((void**)arena, ab);
-    if (e != hipSuccess) *arena = nullptr;
+    e = grow(arena, &have, an);
   }
-  if (e == hipSuccess) e = reserve_batch_scratch(nbatch);
+  if (e == hipSuccess) e = grow(&bt_.siscratch, &sc_have, sn);
+  if (!bt_.siscratch) bt_.sc_capacity = 0;
   if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (*arena) release_buffer(*arena);
-    *arena = nullptr;
+    give_back(*arena);
     *capacity = 0;
     *retaken = true;
-    if (bt_.siscratch && !other) { release_buffer(bt_.siscratch); bt_.siscratch = nullptr; bt_.sc_capacity = 0; }
+    if (held) bt_.sc_users.drop([this] { give_back(bt_.siscratch); bt_.sc_capacity = 0; });
     feature_err_ = std::string(feature) + ": not enough device memory for the " + which + " of " + std::to_string(nbatch) +
-                   " members (" + std::to_string((ab + sb) >> 20) + " MiB): " + hipGetErrorString(e);
+                   " members (" + std::to_string((sizeof(double) * (an + sn)) >> 20) + " MiB): " + hipGetErrorString(e);
     return -1;
   }
+  if (!held) bt_.sc_users.hold();
   *capacity = nbatch;
+  bt_.sc_capacity = std::max(bt_.sc_capacity, nbatch);
   return 0;
 }
 
 // Z arenas and step scratch for nbatch members; all or nothing (a failure leaves the batch factor usable)
 int Engine::reserve_batch_inverse(int nbatch) {
   bool retaken;
-  const int rc = reserve_batch_arenas(&bt_.Z, &bt_.z_capacity, bt_.G, nbatch, "batched selected inversion", "inverse arenas",
+  const int rc = reserve_batch_arenas(&bt_.Z, &bt_.z_capacity, nbatch, "batched selected inversion", "inverse arenas",
                                       &retaken);
   if (retaken) bt_.z_valid = false;
   return rc;
@@ -2463,17 +2411,12 @@ int Engine::release_inverse_batch() {
   if (status_) return status_;
   bt_.z_valid = false;
   bt_.si_launches = 0;
-  if (!bt_.Z && (!bt_.siscratch || bt_.G)) return 0;
+  if (!bt_.Z) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch inverse release")) return rc;
-  if (bt_.Z) release_buffer(bt_.Z);
-  bt_.Z = nullptr;
+  give_back(bt_.Z);
   bt_.z_capacity = 0;
-  if (bt_.siscratch && !bt_.G) {   // (the factor adjoint of the batch shares the scratch)
-    release_buffer(bt_.siscratch);
-    bt_.siscratch = nullptr;
-    bt_.sc_capacity = 0;
-  }
+  bt_.sc_users.drop([this] { give_back(bt_.siscratch); bt_.sc_capacity = 0; });
   return 0;
 }
 
@@ -2493,7 +2436,7 @@ int Engine::reserve_batch_adjoint() {
   if (rc) return rc;
   if ((rc = prepare_fadj_tables())) return rc;
   bool retaken;
-  rc = reserve_batch_arenas(&bt_.G, &bt_.g_capacity, bt_.Z, bt_.nbatch, "batch factor adjoint", "adjoint arenas", &retaken);
+  rc = reserve_batch_arenas(&bt_.G, &bt_.g_capacity, bt_.nbatch, "batch factor adjoint", "adjoint arenas", &retaken);
   if (retaken) bt_.g_state = FADJ_UNSEEDED;
   return rc;
 }
@@ -2652,14 +2595,9 @@ int Engine::release_factor_adjoint_batch() {
   if (!bt_.G) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch factor adjoint release")) return rc;
-  release_buffer(bt_.G);
-  bt_.G = nullptr;
+  give_back(bt_.G);
   bt_.g_capacity = 0;
-  if (bt_.siscratch && !bt_.Z) {
-    release_buffer(bt_.siscratch);
-    bt_.siscratch = nullptr;
-    bt_.sc_capacity = 0;
-  }
+  bt_.sc_users.drop([this] { give_back(bt_.siscratch); bt_.sc_capacity = 0; });
   return 0;
 }
 

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "engine_detail.hpp"
 #include "kernels.hpp"
 #include "schedule.hpp"
 #include "symbolic.hpp"
@@ -65,6 +66,10 @@ void set_rsolve_poison(bool on);
 void set_fmult_poison(bool on);
 // debug: the next n allocations of the factor products' workspace and scratch fail (the fall-back to blocks of 16)
 void set_fmult_alloc_fail(int n);
+// debug: the k-th allocation of feature memory from now on (a Take or a grow; 1: the next) fails once with "out of
+// memory", then the hook is disarmed; 0 disarms it
+void set_alloc_fail_at(int k);
+bool alloc_fail_armed();
 // debug: the workspace of a sparse solve is filled with NaN before its touched rows are zeroed
 void set_solve_sparse_poison(bool on);
 bool batch_selinv_fused();
@@ -87,6 +92,12 @@ int resolve_graph_mode(const Symbolic& S, const EngineOptions& opt);
 // the top-tree block columns; fills the partition fields of so (the vectors must outlive it).
 void partition_options(const Symbolic& S, const EngineOptions& opt, std::vector<int>& owner,
                        std::vector<int>& top_owner, ScheduleOptions& so);
+
+// the two callables through which a Take, a grow and a give_back work on an engine's ledger of device buffers
+class Engine;
+struct EngineAlloc { Engine* eng; inline hipError_t operator()(void** p, size_t bytes) const; };
+struct EngineRelease { Engine* eng; inline void operator()(void* p) const; };
+using FeatureTake = Take<EngineAlloc, EngineRelease>;
 
 class Engine {
  public:
@@ -371,7 +382,7 @@ class Engine {
   // ---- reverse-mode derivative of the factors of a batch (batch_adjoint.hip): G_b, one more arena per member
   // (capacity x lstride), from d loss / d L_b (seeded or uploaded) to d loss / d (P A_b P^T) on every stored
   // lower position, by the batch's SelinvProgram: tables and step scratch are shared with the batched
-  // inversion (whoever comes first takes them, the last release returns the scratch), Z and G are separate.
+  // inversion (whoever comes first takes them; the scratch counts its users), Z and G are separate.
   // The states are those of the single arena, for the whole batch: accumulate needs a seeded arena, the sweep
   // a freshly seeded one, download a seeded or swept one; factor_batch makes it stale.  Every check happens
   // before anything is enqueued; every call returns with the stream drained.  The single arena and its state
@@ -391,6 +402,8 @@ class Engine {
   int release_factor_adjoint_batch();
   double* device_L() { return d_L_; }
   hipStream_t stream() { return stream_; }
+  // entries of the ledger of device buffers and their bytes (host state only)
+  void owned_info(int64_t out[2]) const;
   // the stream the pending exchange is packed / unpacked on (its collective belongs there); the chain stream when none is pending
   hipStream_t pending_exchange_stream() const { return awaiting_exchange_ ? exchange_stream(prog_.launches[cur_x_]) : stream_; }
   const Program& program() const { return prog_; }
@@ -438,6 +451,16 @@ class Engine {
   // device buffers of this engine (pointer, bytes): taken from / returned to the process-wide cache
   std::vector<std::pair<void*, size_t>> owned_;
   hipError_t dalloc(void** p, size_t bytes);
+  // The memory of the optional features (engine_detail.hpp): one transaction per prepare_* / reserve_*, on its
+  // stack (auto t = take()); buffers that grow with the calls; what a release_* returns.  All of them work on
+  // owned_ through dalloc / release_buffer.
+  friend struct EngineAlloc;
+  friend struct EngineRelease;
+  FeatureTake take() { return FeatureTake(EngineAlloc{this}, EngineRelease{this}); }
+  template <class Tp> hipError_t grow(Tp** p, size_t* have, size_t need) {
+    return spx::grow(EngineAlloc{this}, EngineRelease{this}, p, have, need);
+  }
+  template <class... Tp> void give_back(Tp*&... p) { spx::give_back(EngineRelease{this}, p...); }
   template <class Tp> hipError_t dev_upload(Tp** dptr, const std::vector<Tp>& v);
   // host-to-device copy of val through two pinned staging buffers (spllt_factor's val is pageable
   // user memory: handing it to hipMemcpyAsync makes the "asynchronous" copy a blocking one inside
@@ -574,9 +597,9 @@ class Engine {
   // ld = n), launch check, D2H per member unless enqueue refused, sync.  Returns 0, what enqueue refused with
   // (once the stream is idle), or kErrHip.
   template <class Enq> int walk_blocks(const BlockWalk& w, Enq&& enqueue, BlockTally* tally = nullptr);
-  // Blocks of 32 vectors, and when that does not fit, blocks of 16: every buffer of the list through fmult_take,
-  // in order, at *rb = 32; at the first failure what was taken goes back, every pointer is null, and "out of
-  // memory" (alone) tries *rb = 16 once.  *want: the bytes of the last width tried.
+  // Blocks of 32 vectors, and when that does not fit, blocks of 16: one Take per width, every buffer of the list
+  // through its block(), in order, at *rb = 32; a failure rolls that width back, and "out of memory" (alone) tries
+  // *rb = 16 once.  *want: the bytes of the last width tried.
   struct BlockBuffer { void** p; size_t bytes; };   // bytes per vector of a block
   hipError_t take_block_buffers(std::initializer_list<BlockBuffer> bufs, int* rb, size_t* want);
   // reproducible solve (tables and scratch taken on first use, all or nothing)
@@ -592,15 +615,18 @@ class Engine {
   double* d_rsscratch_ = nullptr;  // 4 x rs_stride_ doubles
   double* d_rsstage_ = nullptr;    // 4 n doubles: host vectors in the caller's order
   int64_t rs_stride_ = 0;
-  // the RsolveTables on the device: shared by the reproducible solve and the factor products, given back when
-  // the last of the two is released
-  hipError_t ensure_rsolve_tables();
-  void drop_rsolve_tables();
-  // factor products (taken on first use, all or nothing).  The RsolveTables and the chunk list are shared by the
-  // single-handle products (fm_ready_) and the batched ones (bm_ready_) and given back with the last of the two.
-  hipError_t ensure_fmult_tables();
-  void drop_fmult_tables();
-  hipError_t fmult_take(void** p, size_t bytes);   // dalloc, unless the debug hook "fmult_alloc_fail" says no
+  // the RsolveTables on the device, uploaded within the caller's transaction when absent.  Users (rs_users_): the
+  // reproducible solve (rs_ready_) and the tables of the factor products (while d_fmtab_ is held).
+  void ensure_rsolve_tables(FeatureTake& t);
+  void unhold_rsolve_tables();
+  Shared rs_users_;
+  // factor products (taken on first use, all or nothing).  The chunk list, uploaded within the caller's
+  // transaction when absent.  Users (fm_users_): the single-handle products (fm_ready_) and the batched ones
+  // (bm_ready_); the first hold takes the RsolveTables along, the last drop lets them go.
+  void ensure_fmult_tables(FeatureTake& t);
+  void hold_fmult_tables();
+  void unhold_fmult_tables();
+  Shared fm_users_;
   int prepare_factor_mult(bool host_stage);
   int run_factor_mult(double* x, bool on_device, int nvec, int64_t ldx, int job, bool pivot_order);   // both entry points
   void enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order);
@@ -664,7 +690,6 @@ class Engine {
                      int job, const std::vector<int>* zero_ranges);
   int ss_upload(const SsGroup& g, SsTables& t);
   int ss_enqueue(const SsGroup& g, const SsTables& t, int job, double* W);
-  hipError_t ss_reserve(void** p, size_t* cap, size_t bytes);
   int ss_fail_alloc(const char* what, size_t bytes, hipError_t e);
   char* d_sstab_ = nullptr;        // staged tables of one group (grows, stays)
   double* d_ssout_ = nullptr;      // gathered entries / G of a host entry point, the partial products of gram
@@ -679,11 +704,11 @@ class Engine {
   int refine_readback(int nv, std::vector<double>& out);
   int refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol, int max_iter,
                    int* iterations, double* error);
-  // the operator tables: shared by the single handle (refine_ready_) and the batch (brf_ready_), given back with
-  // the last of the two
-  hipError_t ensure_refine_tables();
-  void drop_refine_tables();
-  bool rf_tables_ = false;
+  // the operator tables, uploaded within the caller's transaction when absent.  Users (rf_users_): the single
+  // handle's refined solve (refine_ready_), the batch's (brf_ready_) and the product of a batch (brf_mv_held_).
+  void ensure_refine_tables(FeatureTake& t);
+  void unhold_refine_tables();
+  Shared rf_users_;
   // refined solves of a batch: six work arrays, partials, scalars and states for brf_capacity_ members
   int prepare_refine_batch(int members);
   void drop_refine_batch();
@@ -692,6 +717,8 @@ class Engine {
                         int done, int nrhs, int method, double tol, int max_iter, int* iterations, double* error,
                         int64_t* launches, int* worst);
   bool brf_ready_ = false;
+  bool brf_mv_held_ = false;       // matvec_batch has uploaded or found the operator tables and keeps them
+  bool brf_held() const { return brf_ready_ || brf_mv_held_ || d_brfval_ || d_brfmv_; }
   int brf_rb_ = 0;                 // pass width the work arrays hold (32, 16 or 8)
   int brf_capacity_ = 0;           // members they hold
   double* d_brfwork_ = nullptr;    // 6 x capacity x brf_rb_ x n: b, x, r, p, q, best x
@@ -751,7 +778,8 @@ class Engine {
   int* d_sirelpos_ = nullptr;
   int64_t* d_sidiag_ = nullptr;
   double* d_Z_ = nullptr;
-  double* d_siscratch_ = nullptr;
+  double* d_siscratch_ = nullptr;  // users (si_users_): the inverse arena d_Z_ and the adjoint arena d_G_
+  Shared si_users_;
   double* d_siout_ = nullptr;      // n + 1 doubles: diag(A^-1), log det
   double* d_sipat_ = nullptr;      // nnz doubles: A^-1 on the analysed pattern (inverse_on_pattern)
   int gather_inverse_on_pattern(double* out_dev, double* arena = nullptr);   // arena: null = d_Z_
@@ -822,7 +850,8 @@ class Engine {
     int64_t sstride = 0;
     bool z_valid = false;
     int si_launches = 0;
-    int sc_capacity = 0;             // members the step scratch holds (shared: inversion and factor adjoint)
+    int sc_capacity = 0;             // members the step scratch holds
+    Shared sc_users;                 // of the step scratch: the inverse arenas Z and the adjoint arenas G
     // factor adjoint of the batch: the arenas and their state (FadjState, for the whole batch)
     double* G = nullptr;             // g_capacity x lstride
     int g_capacity = 0;
@@ -831,17 +860,19 @@ class Engine {
   } bt_;
   int prepare_batch();
   int reserve_batch(int nbatch);
-  int grow_batch_buffer(double** p, size_t* have, size_t need, const char* what);
+  int grow_batch_buffer(double** p, size_t* have, size_t need, const char* what);   // grow + the batch's message
   BatchView batch_view() const;
   int prepare_batch_selinv();
   int reserve_batch_inverse(int nbatch);
   BatchSelinvView batch_selinv_view() const;
-  hipError_t reserve_batch_scratch(int nbatch);
-  int reserve_batch_arenas(double** arena, int* capacity, const double* other, int nbatch, const char* feature,
-                           const char* which, bool* retaken);
+  int reserve_batch_arenas(double** arena, int* capacity, int nbatch, const char* feature, const char* which,
+                           bool* retaken);
   int reserve_batch_adjoint();
   BatchSelinvView batch_adjoint_view() const;
 };
+
+inline hipError_t EngineAlloc::operator()(void** p, size_t bytes) const { return eng->dalloc(p, bytes); }
+inline void EngineRelease::operator()(void* p) const { eng->release_buffer(p); }
 
 // The batch program of a pattern: build_program with fixed options (single stream, no fused panels, no
 // chain blocks, no subtree tasks, atomics, pw = tile = 64, no partition), whatever the handle's engine

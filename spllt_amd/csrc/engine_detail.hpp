@@ -5,9 +5,11 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace spx {
@@ -75,6 +77,118 @@ struct TableStager {
     if (e != hipSuccess) return e;
     for (const Slot& sl : slots) *sl.dptr = *blob + sl.off;
     return hipSuccess;
+  }
+};
+
+// ---- the device memory of the optional features -------------------------------------------------------------
+// Every feature takes its buffers on first use, all or nothing, through ONE allocation path (feature_alloc) and
+// the three helpers below; what several features use is counted (Shared).  None of this owns memory beyond a
+// call: the engine's ledger does, and a Take lives on the stack of the prepare_* / reserve_* that made it.
+//
+// The two debug hooks of that path (spllt_hip_debug): simulated return codes, nothing is asked of the device.
+inline std::atomic<int>& fmult_alloc_fail_left() { static std::atomic<int> v{0}; return v; }   // "fmult_alloc_fail=n"
+inline std::atomic<int>& alloc_fail_countdown() { static std::atomic<int> v{0}; return v; }    // "alloc_fail_at=k"
+
+// block: an allocation the hook "fmult_alloc_fail" may refuse (the width-dependent buffers of the blocked paths,
+// the buffers of the constraints); every call counts for "alloc_fail_at", which disarms itself when it fires
+template <class Alloc>
+hipError_t feature_alloc(Alloc& alloc, void** p, size_t bytes, bool block) {
+  if (block && fmult_alloc_fail_left().load() > 0) {
+    fmult_alloc_fail_left().fetch_sub(1);
+    return hipErrorOutOfMemory;
+  }
+  if (alloc_fail_countdown().load() > 0 && alloc_fail_countdown().fetch_sub(1) == 1) return hipErrorOutOfMemory;
+  return alloc(p, bytes);
+}
+
+// releases every non-null argument and nulls it, whatever its pointee type
+template <class Release, class... Tp>
+void give_back(Release&& release, Tp*&... p) {
+  auto one = [&](auto*& q) {
+    if (q) release((void*)q);
+    q = nullptr;
+  };
+  (one(p), ...);
+}
+
+// One all-or-nothing take.  Every request after the first failure is a no-op; leaving the scope without commit()
+// releases what THIS transaction took, last first, nulls the pointers it set (and no other) and clears the
+// sticky HIP error.  alloc(void**, size_t) -> hipError_t, release(void*).
+template <class Alloc, class Release>
+class Take {
+ public:
+  Take(Alloc alloc, Release release) : alloc_(std::move(alloc)), release_(std::move(release)) {}
+  Take(const Take&) = delete;
+  Take& operator=(const Take&) = delete;
+  ~Take() {
+    if (committed_) return;
+    for (size_t i = set_.size(); i-- > 0;) {
+      if (set_[i].owns) release_(*set_[i].p);
+      *set_[i].p = nullptr;
+    }
+    if (e_ != hipSuccess) (void)hipGetLastError();
+  }
+  template <class Tp> void operator()(Tp** p, size_t bytes) { take((void**)p, bytes, false); }
+  template <class Tp> void block(Tp** p, size_t bytes) { take((void**)p, bytes, true); }   // through "fmult_alloc_fail"
+  // the one allocation and the one copy of a TableStager; the typed pointers of its slots are rolled back too
+  void tables(TableStager& tab, char** blob) {
+    bytes_ += std::max<size_t>(tab.host.size(), 8);
+    if (e_ != hipSuccess) return;
+    e_ = tab.commit(blob, [this](void** q, size_t b) {
+      const hipError_t e = feature_alloc(alloc_, q, b, false);
+      if (e == hipSuccess) set_.push_back({q, true});
+      return e;
+    });
+    if (e_ == hipSuccess)
+      for (const TableStager::Slot& sl : tab.slots) set_.push_back({sl.dptr, false});
+  }
+  void check(hipError_t e) { if (e_ == hipSuccess) e_ = e; }   // any other step joins the same outcome
+  bool ok() const { return e_ == hipSuccess; }
+  hipError_t error() const { return e_; }
+  size_t bytes() const { return bytes_; }   // of every request, made or skipped
+  void commit() { committed_ = e_ == hipSuccess; }
+
+ private:
+  struct Entry { void** p; bool owns; };
+  void take(void** p, size_t bytes, bool block) {
+    bytes_ += bytes;
+    if (e_ != hipSuccess) return;
+    e_ = feature_alloc(alloc_, p, bytes, block);
+    if (e_ == hipSuccess) set_.push_back({p, true});
+  }
+  Alloc alloc_;
+  Release release_;
+  std::vector<Entry> set_;
+  hipError_t e_ = hipSuccess;
+  size_t bytes_ = 0;
+  bool committed_ = false;
+};
+
+// A buffer that grows with the calls: kept while it holds `need` elements, else released and taken again.  A
+// failure leaves *p null and *have 0; the caller writes its own message.
+template <class Alloc, class Release, class Tp>
+hipError_t grow(Alloc&& alloc, Release&& release, Tp** p, size_t* have, size_t need) {
+  if (*p && *have >= need) return hipSuccess;
+  give_back(release, *p);
+  *have = 0;
+  const hipError_t e = feature_alloc(alloc, (void**)p, sizeof(Tp) * std::max<size_t>(need, 1), false);
+  if (e == hipSuccess) {
+    *have = need;
+  } else {
+    (void)hipGetLastError();
+    *p = nullptr;
+  }
+  return e;
+}
+
+// What more than one feature uses: every user holds it once (on its own not-ready -> ready edge) and drops it
+// once; the drop of the last user runs `last`, which returns the memory.
+struct Shared {
+  int users = 0;
+  void hold() { ++users; }
+  template <class F>
+  void drop(F&& last) {
+    if (users > 0 && --users == 0) last();
   }
 };
 

@@ -174,18 +174,11 @@ int Engine::walk_blocks(const BlockWalk& w, Enq&& enqueue, BlockTally* tally) {
 
 hipError_t Engine::take_block_buffers(std::initializer_list<BlockBuffer> bufs, int* rb, size_t* want) {
   for (*rb = 32;; *rb /= 2) {
-    hipError_t e = hipSuccess;
-    *want = 0;
-    for (const BlockBuffer& b : bufs) *want += b.bytes * (size_t)*rb;
-    for (const BlockBuffer& b : bufs)
-      if ((e = fmult_take(b.p, b.bytes * (size_t)*rb)) != hipSuccess) break;
-    if (e == hipSuccess) return e;
-    (void)hipGetLastError();
-    for (const BlockBuffer& b : bufs) {
-      if (*b.p) release_buffer(*b.p);
-      *b.p = nullptr;
-    }
-    if (*rb == 16 || alloc_code(e) != -1) return e;   // (out of memory: once more with half of it)
+    auto t = take();
+    for (const BlockBuffer& b : bufs) t.block(b.p, b.bytes * (size_t)*rb);
+    *want = t.bytes();
+    t.commit();
+    if (t.ok() || *rb == 16 || alloc_code(t.error()) != -1) return t.error();   // (out of memory: once more with half of it)
   }
 }
 
@@ -265,16 +258,16 @@ int Engine::prepare_solve_many(bool host_stage) {
   const Symbolic& S = *S_;
   const size_t wb = sizeof(double) * 32 * (size_t)std::max(1, S.n);
   // (a failure here leaves the factor and the existing solve usable: the engine's status is not touched)
-  hipError_t e = hipSuccess;
-  if (!d_smW_) e = dalloc((void**)&d_smW_, wb);
-  if (e == hipSuccess) e = ensure_order();
-  if (e == hipSuccess && host_stage && !d_smstage_) e = dalloc((void**)&d_smstage_, wb);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
+  auto t = take();
+  if (!d_smW_) t(&d_smW_, wb);
+  if (t.ok()) t.check(ensure_order());
+  if (host_stage && !d_smstage_) t(&d_smstage_, wb);
+  if (!t.ok()) {
     feature_err_ = "solve_many: not enough device memory for the workspace of 32 right-hand sides (" +
-                   std::to_string(wb >> 20) + " MiB): " + hipGetErrorString(e);
-    return alloc_code(e);
+                   std::to_string(wb >> 20) + " MiB): " + hipGetErrorString(t.error());
+    return alloc_code(t.error());
   }
+  t.commit();
   return 0;
 }
 
@@ -414,21 +407,9 @@ int Engine::ss_filterable() {
   return -99;
 }
 
-hipError_t Engine::ss_reserve(void** p, size_t* cap, size_t bytes) {
-  if (*p && *cap >= bytes) return hipSuccess;
-  if (*p) release_buffer(*p);
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = dalloc(p, std::max<size_t>(bytes, 8));
-  if (e == hipSuccess) *cap = bytes; else *p = nullptr;
-  return e;
-}
-
+// (the capacities are in elements: bytes of the tables, doubles of the other two)
 int Engine::ss_fail_alloc(const char* what, size_t bytes, hipError_t e) {
-  (void)hipGetLastError();
-  for (void* p : {(void*)d_sstab_, (void*)d_ssout_, (void*)d_ssgramW_})
-    if (p) release_buffer(p);
-  d_sstab_ = nullptr; d_ssout_ = nullptr; d_ssgramW_ = nullptr;
+  give_back(d_sstab_, d_ssout_, d_ssgramW_);
   ss_tab_cap_ = ss_out_cap_ = ss_gram_cap_ = 0;
   feature_err_ = std::string(what) + ": not enough device memory (" + std::to_string(bytes >> 20) + " MiB): " +
                  hipGetErrorString(e);
@@ -501,8 +482,8 @@ int Engine::solve_sparse(int k, const int* bptr, const int* brow, const double* 
   });
   ss_host_us_ = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
   const size_t out_bytes = dev ? 0 : sizeof(double) * (size_t)nout * 32;
-  hipError_t e = ss_reserve((void**)&d_sstab_, &ss_tab_cap_, tab_bytes);
-  if (e == hipSuccess && !dev) e = ss_reserve((void**)&d_ssout_, &ss_out_cap_, out_bytes);
+  hipError_t e = grow(&d_sstab_, &ss_tab_cap_, tab_bytes);
+  if (e == hipSuccess && !dev) e = grow(&d_ssout_, &ss_out_cap_, out_bytes / sizeof(double));
   if (e != hipSuccess) return ss_fail_alloc("solve_sparse", tab_bytes + out_bytes, e);
   for (int64_t& v : ss_info_) v = 0;
   for (const SsGroup& g : groups) {
@@ -559,9 +540,9 @@ int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* b
   const size_t wstride = (size_t)32 * (size_t)n;
   const size_t gram_bytes = sizeof(double) * wstride * (ng - 1);
   const size_t out_bytes = sizeof(double) * ((size_t)k * (size_t)k + nchunk * 1024);
-  hipError_t e = ss_reserve((void**)&d_sstab_, &ss_tab_cap_, tab_bytes);
-  if (e == hipSuccess) e = ss_reserve((void**)&d_ssout_, &ss_out_cap_, out_bytes);
-  if (e == hipSuccess && ng > 1) e = ss_reserve((void**)&d_ssgramW_, &ss_gram_cap_, gram_bytes);
+  hipError_t e = grow(&d_sstab_, &ss_tab_cap_, tab_bytes);
+  if (e == hipSuccess) e = grow(&d_ssout_, &ss_out_cap_, out_bytes / sizeof(double));
+  if (e == hipSuccess && ng > 1) e = grow(&d_ssgramW_, &ss_gram_cap_, gram_bytes / sizeof(double));
   if (e != hipSuccess) return ss_fail_alloc("gram_sparse", tab_bytes + out_bytes + gram_bytes, e);
   for (int64_t& v : ss_info_) v = 0;
   auto workspace = [&](size_t gi) { return gi == 0 ? d_smW_ : d_ssgramW_ + (gi - 1) * wstride; };
@@ -593,9 +574,7 @@ int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* b
 int Engine::release_solve_sparse() {
   int rc;
   if (!enter_release(d_sstab_ || d_ssout_ || d_ssgramW_, "solve_sparse release", &rc)) return rc;
-  for (void* p : {(void*)d_sstab_, (void*)d_ssout_, (void*)d_ssgramW_})
-    if (p) release_buffer(p);
-  d_sstab_ = nullptr; d_ssout_ = nullptr; d_ssgramW_ = nullptr;
+  give_back(d_sstab_, d_ssout_, d_ssgramW_);
   ss_tab_cap_ = ss_out_cap_ = ss_gram_cap_ = 0;
   return 0;
 }
@@ -605,8 +584,8 @@ static std::atomic<bool> g_rsolve_poison{false};
 void set_rsolve_poison(bool on) { g_rsolve_poison.store(on); }
 
 // the RsolveTables of the substitution program, uploaded once; rs_stride_ = max(frows, bsize)
-hipError_t Engine::ensure_rsolve_tables() {
-  if (d_rstab_) return hipSuccess;
+void Engine::ensure_rsolve_tables(FeatureTake& t) {
+  if (d_rstab_) return;
   RsolveTables R;
   build_rsolve_tables(*S_, sprog_, R);
   rs_stride_ = std::max<int64_t>(1, std::max(R.frows, R.bsize));
@@ -616,15 +595,11 @@ hipError_t Engine::ensure_rsolve_tables() {
   tab.add(&d_rsgptr_, R.gptr);
   tab.add(&d_rsgsrc_, R.gsrc);
   tab.add(&d_rsbslot_, R.bslot);
-  hipError_t e = tab.commit(&d_rstab_, [this](void** q, size_t b) { return dalloc(q, b); });
-  if (e != hipSuccess) drop_rsolve_tables();
-  return e;
+  t.tables(tab, &d_rstab_);
 }
 
-// (the caller has checked that neither user is left)
-void Engine::drop_rsolve_tables() {
-  if (d_rstab_) release_buffer(d_rstab_);
-  d_rstab_ = nullptr;
+void Engine::unhold_rsolve_tables() {
+  rs_users_.drop([this] { give_back(d_rstab_); });
 }
 
 int Engine::prepare_solve_repro() {
@@ -633,21 +608,19 @@ int Engine::prepare_solve_repro() {
   if (rs_ready_) return 0;
   const Symbolic& S = *S_;
   // (a failure here leaves the factor and the other solves usable: the engine's status is not touched)
-  hipError_t e = ensure_rsolve_tables();
+  auto t = take();
+  ensure_rsolve_tables(t);
   const size_t sb = sizeof(double) * 4 * (size_t)rs_stride_;
-  if (e == hipSuccess) e = ensure_order();
-  if (e == hipSuccess) e = dalloc((void**)&d_rsscratch_, sb);
-  if (e == hipSuccess) e = dalloc((void**)&d_rsstage_, sizeof(double) * 4 * (size_t)std::max(1, S.n));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    for (void* p : {(void*)d_rsscratch_, (void*)d_rsstage_})
-      if (p) release_buffer(p);
-    d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
-    if (!d_fmtab_) drop_rsolve_tables();   // (the tables of the products, single or batched, hold them too)
+  if (t.ok()) t.check(ensure_order());
+  t(&d_rsscratch_, sb);
+  t(&d_rsstage_, sizeof(double) * 4 * (size_t)std::max(1, S.n));
+  if (!t.ok()) {
     feature_err_ = "solve_repro: not enough device memory for the tables and the scratch of 4 right-hand sides (" +
-                   std::to_string(sb >> 20) + " MiB): " + hipGetErrorString(e);
-    return alloc_code(e);
+                   std::to_string(sb >> 20) + " MiB): " + hipGetErrorString(t.error());
+    return alloc_code(t.error());
   }
+  t.commit();
+  rs_users_.hold();
   rs_ready_ = true;
   return 0;
 }
@@ -655,11 +628,9 @@ int Engine::prepare_solve_repro() {
 int Engine::release_solve_repro() {
   int rc;
   if (!enter_release(rs_ready_, "solve_repro release", &rc)) return rc;
-  for (void* p : {(void*)d_rsscratch_, (void*)d_rsstage_})
-    if (p) release_buffer(p);
-  d_rsscratch_ = nullptr; d_rsstage_ = nullptr;
-  if (!d_fmtab_) drop_rsolve_tables();   // (the tables of the products, single or batched, hold them too)
+  give_back(d_rsscratch_, d_rsstage_);
   rs_ready_ = false;
+  unhold_rsolve_tables();
   return 0;
 }
 
@@ -717,41 +688,37 @@ int Engine::solve_repro(double* x_host, int nrhs, int64_t ldx, int job) {
 
 // ---- products with the factor, Gaussian sampling ---------------------------------------------------
 static std::atomic<bool> g_fmult_poison{false};
-static std::atomic<int> g_fmult_alloc_fail{0};
 void set_fmult_poison(bool on) { g_fmult_poison.store(on); }
-void set_fmult_alloc_fail(int n) { g_fmult_alloc_fail.store(n); }
+void set_fmult_alloc_fail(int n) { fmult_alloc_fail_left().store(n); }
+void set_alloc_fail_at(int k) { alloc_fail_countdown().store(std::max(k, 0)); }
+bool alloc_fail_armed() { return alloc_fail_countdown().load() > 0; }
 
 // the tables of the products: the RsolveTables and the (block column, chunk of 64 pivot positions) pairs of the
 // diagonal launches, block columns ascending
-hipError_t Engine::ensure_fmult_tables() {
-  if (d_fmtab_) return hipSuccess;
+void Engine::ensure_fmult_tables(FeatureTake& t) {
+  if (d_fmtab_) return;
   std::vector<UpdTile> chunks;
   for (size_t b = 0; b < sprog_.units.size(); ++b)
     for (int c = 0; c * 64 < sprog_.units[b].w; ++c) chunks.push_back(UpdTile{(int)b, (short)c, 0});
   fm_nchunks_ = (int64_t)chunks.size();
-  hipError_t e = ensure_rsolve_tables();
-  if (e == hipSuccess) {
-    TableStager tab;
-    tab.add(&d_fmchunks_, chunks);
-    e = tab.commit(&d_fmtab_, [this](void** q, size_t b) { return dalloc(q, b); });
-  }
-  if (e != hipSuccess) drop_fmult_tables();
-  return e;
+  ensure_rsolve_tables(t);
+  TableStager tab;
+  tab.add(&d_fmchunks_, chunks);
+  t.tables(tab, &d_fmtab_);
 }
 
-// (the caller has checked that neither the single-handle products nor the batched ones are left)
-void Engine::drop_fmult_tables() {
-  if (d_fmtab_) release_buffer(d_fmtab_);
-  d_fmtab_ = nullptr; d_fmchunks_ = nullptr;
-  if (!rs_ready_) drop_rsolve_tables();
+// (after the commit of the transaction that ensured them)
+void Engine::hold_fmult_tables() {
+  if (fm_users_.users == 0) rs_users_.hold();
+  fm_users_.hold();
 }
 
-hipError_t Engine::fmult_take(void** p, size_t bytes) {
-  if (g_fmult_alloc_fail.load() > 0) {
-    g_fmult_alloc_fail.fetch_sub(1);
-    return hipErrorOutOfMemory;
-  }
-  return dalloc(p, bytes);
+void Engine::unhold_fmult_tables() {
+  fm_users_.drop([this] {
+    give_back(d_fmtab_);
+    d_fmchunks_ = nullptr;
+    unhold_rsolve_tables();
+  });
 }
 
 int Engine::prepare_factor_mult(bool host_stage) {
@@ -760,19 +727,20 @@ int Engine::prepare_factor_mult(bool host_stage) {
   if (fm_ready_) return 0;
   const size_t n1 = (size_t)std::max(1, S_->n);
   // (a failure here leaves the factor and every solve usable: the engine's status is not touched)
-  hipError_t e = ensure_fmult_tables();
+  auto t = take();
+  ensure_fmult_tables(t);
   size_t want = 0;
   // (per vector the same sums in the same order at either width)
-  if (e == hipSuccess)
-    e = take_block_buffers({{(void**)&d_fmW_, sizeof(double) * n1}, {(void**)&d_fmscratch_, sizeof(double) * (size_t)rs_stride_}},
-                           &fm_rb_, &want);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (!bm_ready_) drop_fmult_tables();
+  if (t.ok())
+    t.check(take_block_buffers({{(void**)&d_fmW_, sizeof(double) * n1}, {(void**)&d_fmscratch_, sizeof(double) * (size_t)rs_stride_}},
+                               &fm_rb_, &want));
+  if (const hipError_t e = t.error()) {
     feature_err_ = "factor_mult: not enough device memory for the tables, the second workspace and the scratch of 16 "
                    "vectors (" + std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
     return alloc_code(e);
   }
+  t.commit();
+  hold_fmult_tables();
   fm_ready_ = true;
   return 0;
 }
@@ -780,11 +748,9 @@ int Engine::prepare_factor_mult(bool host_stage) {
 int Engine::release_factor_mult() {
   int rc;
   if (!enter_release(fm_ready_ || d_fmmean_, "factor_mult release", &rc)) return rc;
-  for (void* p : {(void*)d_fmW_, (void*)d_fmscratch_, (void*)d_fmmean_})
-    if (p) release_buffer(p);
-  d_fmW_ = nullptr; d_fmscratch_ = nullptr; d_fmmean_ = nullptr;
+  give_back(d_fmW_, d_fmscratch_, d_fmmean_);
+  if (fm_ready_) unhold_fmult_tables();
   fm_ready_ = false;
-  if (!bm_ready_) drop_fmult_tables();
   return 0;
 }
 
@@ -849,13 +815,13 @@ int Engine::sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, u
   const double* dmean = mean;
   if (mean && !dev) {
     if (!d_fmmean_) {
-      hipError_t e = dalloc((void**)&d_fmmean_, sizeof(double) * (size_t)n);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        d_fmmean_ = nullptr;
-        feature_err_ = std::string("sample: not enough device memory for the mean: ") + hipGetErrorString(e);
-        return alloc_code(e);
+      auto t = take();
+      t(&d_fmmean_, sizeof(double) * (size_t)n);
+      if (!t.ok()) {
+        feature_err_ = std::string("sample: not enough device memory for the mean: ") + hipGetErrorString(t.error());
+        return alloc_code(t.error());
       }
+      t.commit();
     }
     HIPCHK(hipMemcpyAsync(d_fmmean_, mean, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream_), "mean H2D");
     dmean = d_fmmean_;
@@ -885,14 +851,11 @@ int Engine::sample(double* x, int nsamp, int64_t ldx, int kind, uint64_t seed, u
 
 // ---- the products and the samplers for every member of a batch ---------------------------------------
 void Engine::drop_factor_mult_batch() {
-  for (void* p : {(void*)d_bmW_[0], (void*)d_bmW_[1], (void*)d_bmscratch_, (void*)d_bmmean_})
-    if (p) release_buffer(p);
-  d_bmW_[0] = d_bmW_[1] = d_bmscratch_ = d_bmmean_ = nullptr;
+  give_back(d_bmW_[0], d_bmW_[1], d_bmscratch_, d_bmmean_);
   bm_mean_elems_ = 0;
   bm_capacity_ = 0;
-  const bool had = bm_ready_;
+  if (bm_ready_) unhold_fmult_tables();
   bm_ready_ = false;
-  if (had && !fm_ready_) drop_fmult_tables();
 }
 
 // tables (shared with the single-handle products), two workspaces and the scratch for the members of the last
@@ -905,16 +868,15 @@ int Engine::prepare_factor_mult_batch() {
   if (bm_ready_) drop_factor_mult_batch();   // (a larger batch: everything again)
   const size_t n1 = (size_t)std::max(1, S_->n);
   // (a failure here leaves the batch, its solve and the single factorization usable)
-  hipError_t e = ensure_order();
-  if (e == hipSuccess) e = ensure_fmult_tables();
+  auto t = take();
+  t.check(ensure_order());
+  ensure_fmult_tables(t);
   size_t want = 0;
-  if (e == hipSuccess) {
+  if (t.ok()) {
     const size_t wb = sizeof(double) * (size_t)nbatch * n1, sb = sizeof(double) * (size_t)nbatch * (size_t)rs_stride_;
-    e = take_block_buffers({{(void**)&d_bmW_[0], wb}, {(void**)&d_bmW_[1], wb}, {(void**)&d_bmscratch_, sb}}, &bm_rb_, &want);
+    t.check(take_block_buffers({{(void**)&d_bmW_[0], wb}, {(void**)&d_bmW_[1], wb}, {(void**)&d_bmscratch_, sb}}, &bm_rb_, &want));
   }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (!fm_ready_) drop_fmult_tables();
+  if (const hipError_t e = t.error()) {
     feature_err_ = "factor_mult_batch: not enough device memory for the tables, two workspaces and the scratch of 16 "
                    "vectors for each of " + std::to_string(nbatch) + " members (" + std::to_string(want >> 20) +
                    " MiB): " + hipGetErrorString(e);
@@ -922,6 +884,8 @@ int Engine::prepare_factor_mult_batch() {
   }
   // experiment knob of scripts/factor_mult_batch_bench.py (the A/B of the two grid orders)
   if (const char* env = std::getenv("SPLLT_BATCH_MULT_MEMBER_FAST")) bm_member_fast_ = std::atoi(env) != 0;
+  t.commit();
+  hold_fmult_tables();
   bm_capacity_ = nbatch;
   bm_ready_ = true;
   return 0;
@@ -1069,8 +1033,7 @@ int Engine::sample_batch(double* x, int nsamp, int64_t ldx, int kind, uint64_t s
 
 // ---- blocked solve for every member of a batch -------------------------------------------------------
 void Engine::drop_solve_many_batch() {
-  if (d_bsmW_) release_buffer(d_bsmW_);
-  d_bsmW_ = nullptr;
+  give_back(d_bsmW_);
   bsm_capacity_ = 0;
   bsm_ready_ = false;
   bsm_info_[0] = bsm_info_[3] = 0;
@@ -1156,8 +1119,8 @@ int Engine::solve_many_batch(double* x, bool on_device, int nrhs, int64_t ldx, i
 // ---- refined solves --------------------------------------------------------------------------------
 // Operator tables (once per engine) and the work vectors of one group, all or nothing: a failed allocation
 // gives back what it got and leaves the factor and every other solve usable.
-hipError_t Engine::ensure_refine_tables() {
-  if (rf_tables_) return hipSuccess;
+void Engine::ensure_refine_tables(FeatureTake& t) {
+  if (d_rftab_) return;
   const Symbolic& S = *S_;
   std::vector<int64_t> rowptr;
   std::vector<int> col, src, rows;
@@ -1177,58 +1140,42 @@ hipError_t Engine::ensure_refine_tables() {
   tab.add(&d_rfcol_, col);
   tab.add(&d_rfsrc_, src);
   tab.add(&d_rfrows_, rows);
-  hipError_t e = tab.commit(&d_rftab_, [this](void** q, size_t b) { return dalloc(q, b); });
-  if (e == hipSuccess) e = ensure_order();
-  if (e != hipSuccess) {
-    if (d_rftab_) release_buffer(d_rftab_);
-    d_rftab_ = nullptr;
-    return e;
-  }
-  rf_tables_ = true;
-  return hipSuccess;
+  t.tables(tab, &d_rftab_);
+  if (t.ok()) t.check(ensure_order());
 }
 
-void Engine::drop_refine_tables() {
-  if (refine_ready_ || brf_ready_) return;   // (the other of the two still works on them)
-  if (d_rftab_) release_buffer(d_rftab_);
-  d_rftab_ = nullptr;
-  rf_tables_ = false;
+void Engine::unhold_refine_tables() {
+  rf_users_.drop([this] { give_back(d_rftab_); });
 }
 
 int Engine::prepare_refine(bool host_val) {
   const Symbolic& S = *S_;
   const size_t n1 = (size_t)std::max(1, S.n);
-  hipError_t e = hipSuccess;
+  auto t = take();
   size_t want = 0;
   if (!refine_ready_) {
-    e = ensure_refine_tables();
+    ensure_refine_tables(t);
     RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
     const size_t slots = (size_t)std::max(std::max(spmv_slots(op), vec_slots(S.n)), RF_AMAX_WG);
     want = sizeof(double) * 6 * RF_G * n1;
-    if (e == hipSuccess) e = dalloc((void**)&d_rfwork_, want);
-    if (e == hipSuccess) e = dalloc((void**)&d_rfpart_, sizeof(double) * 2 * RF_G * slots);
-    if (e == hipSuccess) e = dalloc((void**)&d_rfds_, sizeof(double) * RF_DS);
-    if (e == hipSuccess) e = dalloc((void**)&d_rfis_, sizeof(int) * RF_IS);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rfis_, 0, sizeof(int) * RF_IS, stream_);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rfds_, 0, sizeof(double) * RF_DS, stream_);
+    t(&d_rfwork_, want);
+    t(&d_rfpart_, sizeof(double) * 2 * RF_G * slots);
+    t(&d_rfds_, sizeof(double) * RF_DS);
+    t(&d_rfis_, sizeof(int) * RF_IS);
+    if (t.ok()) t.check(hipMemsetAsync(d_rfis_, 0, sizeof(int) * RF_IS, stream_));
+    if (t.ok()) t.check(hipMemsetAsync(d_rfds_, 0, sizeof(double) * RF_DS, stream_));
   }
-  if (e == hipSuccess && host_val && !d_rfval_) {
+  if (t.ok() && host_val && !d_rfval_) {
     want = sizeof(double) * (size_t)std::max<int64_t>(1, S.nnzA);
-    e = dalloc((void**)&d_rfval_, want);
-    if (e != hipSuccess) d_rfval_ = nullptr;
+    t(&d_rfval_, want);
   }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (!refine_ready_) {
-      for (void* p : {(void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_})
-        if (p) release_buffer(p);
-      d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr;
-      drop_refine_tables();
-    }
+  if (!t.ok()) {
     feature_err_ = "refined solve: not enough device memory for the operator and the work vectors (" +
-                   std::to_string(want >> 20) + " MiB): " + hipGetErrorString(e);
-    return alloc_code(e);
+                   std::to_string(want >> 20) + " MiB): " + hipGetErrorString(t.error());
+    return alloc_code(t.error());
   }
+  t.commit();
+  if (!refine_ready_) rf_users_.hold();
   refine_ready_ = true;
   return 0;
 }
@@ -1236,11 +1183,9 @@ int Engine::prepare_refine(bool host_val) {
 int Engine::release_refine() {
   int rc;
   if (!enter_release(refine_ready_ || d_rfval_, "refine release", &rc)) return rc;
-  for (void* p : {(void*)d_rfwork_, (void*)d_rfpart_, (void*)d_rfds_, (void*)d_rfis_, (void*)d_rfval_})
-    if (p) release_buffer(p);
-  d_rfwork_ = nullptr; d_rfpart_ = nullptr; d_rfds_ = nullptr; d_rfis_ = nullptr; d_rfval_ = nullptr;
+  give_back(d_rfwork_, d_rfpart_, d_rfds_, d_rfis_, d_rfval_);
+  if (refine_ready_) unhold_refine_tables();
   refine_ready_ = false;
-  drop_refine_tables();
   return 0;
 }
 
@@ -1426,18 +1371,14 @@ int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, b
 
 // ---- refined solves for the members of a batch ---------------------------------------------------------
 void Engine::drop_refine_batch() {
-  for (void* p : {(void*)d_brfwork_, (void*)d_brfpart_, (void*)d_brfds_, (void*)d_brfis_, (void*)d_brfval_, (void*)d_brfmv_})
-    if (p) release_buffer(p);
-  d_brfwork_ = d_brfpart_ = d_brfds_ = d_brfval_ = d_brfmv_ = nullptr;
-  d_brfis_ = nullptr;
+  give_back(d_brfwork_, d_brfpart_, d_brfds_, d_brfis_, d_brfval_, d_brfmv_);
   brf_val_elems_ = brf_mv_elems_ = 0;
   brf_capacity_ = 0;
   brf_rb_ = 0;
-  const bool had = brf_ready_;
-  brf_ready_ = false;
   brf_info_[0] = brf_info_[3] = 0;
-  (void)had;
-  drop_refine_tables();   // (also those a product alone uploaded; kept while the single handle's refined solve is ready)
+  if (brf_ready_) unhold_refine_tables();
+  if (brf_mv_held_) unhold_refine_tables();   // (the hold of the products)
+  brf_ready_ = brf_mv_held_ = false;
 }
 
 // the operator tables (those of the single handle) and the storage of a pass for `members` members: six work
@@ -1447,40 +1388,40 @@ int Engine::prepare_refine_batch(int members) {
   if (brf_ready_) drop_refine_batch();   // (a larger batch: everything again)
   const size_t n1 = (size_t)std::max(1, S_->n), nb = (size_t)members;
   // (a failure here leaves the batch, its solves and the single factorization usable)
-  hipError_t e = ensure_refine_tables();
+  auto tables = take();
+  ensure_refine_tables(tables);
+  hipError_t e = tables.error();
   size_t want = 0;
   if (e == hipSuccess) {
     const RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
     const size_t slots = (size_t)std::max(spmv_slots(op), vec_slots(S_->n));
-    for (int rb = RF_G; rb >= 8; rb /= 2) {
+    for (int rb = RF_G; rb >= 8; rb /= 2) {   // (one transaction per width)
       const size_t np = nb * (size_t)rb;
       const size_t wb = sizeof(double) * 6 * np * n1;
       const size_t pb = sizeof(double) * std::max(2 * slots * np, nb * (size_t)RF_AMAX_WG);
       const size_t db = sizeof(double) * (2 * nb + BRF_DS * np), ib = sizeof(int) * (RF_IS / RF_G) * np;
       want = wb + pb + db + ib;
-      e = fmult_take((void**)&d_brfwork_, wb);
-      if (e == hipSuccess) e = dalloc((void**)&d_brfpart_, pb);
-      if (e == hipSuccess) e = dalloc((void**)&d_brfds_, db);
-      if (e == hipSuccess) e = dalloc((void**)&d_brfis_, ib);
-      if (e == hipSuccess) e = hipMemsetAsync(d_brfds_, 0, db, stream_);
-      if (e == hipSuccess) e = hipMemsetAsync(d_brfis_, 0, ib, stream_);
-      if (e == hipSuccess) { brf_rb_ = rb; break; }
-      (void)hipGetLastError();
-      for (void* p : {(void*)d_brfwork_, (void*)d_brfpart_, (void*)d_brfds_, (void*)d_brfis_})
-        if (p) release_buffer(p);
-      d_brfwork_ = d_brfpart_ = d_brfds_ = nullptr;
-      d_brfis_ = nullptr;
-      if (alloc_code(e) != -1) break;   // (out of memory: once more with half of it)
+      auto t = take();
+      t.block(&d_brfwork_, wb);
+      t(&d_brfpart_, pb);
+      t(&d_brfds_, db);
+      t(&d_brfis_, ib);
+      if (t.ok()) t.check(hipMemsetAsync(d_brfds_, 0, db, stream_));
+      if (t.ok()) t.check(hipMemsetAsync(d_brfis_, 0, ib, stream_));
+      t.commit();
+      e = t.error();
+      if (e == hipSuccess) brf_rb_ = rb;
+      if (e == hipSuccess || alloc_code(e) != -1) break;   // (out of memory: once more with half of it)
     }
   }
   if (e != hipSuccess) {
-    (void)hipGetLastError();
-    drop_refine_tables();
     feature_err_ = "solve_refined_batch: not enough device memory for the operator and six work arrays of 8 vectors for "
                    "each of " + std::to_string(members) + " members (" + std::to_string(want >> 20) + " MiB): " +
                    hipGetErrorString(e);
     return alloc_code(e);
   }
+  tables.commit();
+  rf_users_.hold();
   brf_capacity_ = members;
   brf_ready_ = true;
   brf_info_[0] = brf_rb_;
@@ -1490,8 +1431,7 @@ int Engine::prepare_refine_batch(int members) {
 
 int Engine::release_refine_batch() {
   int rc;
-  // (rf_tables_ without a ready user: the tables of a product that needed no workspace)
-  if (!enter_release(brf_ready_ || d_brfval_ || d_brfmv_ || (rf_tables_ && !refine_ready_), "refine_batch release", &rc)) return rc;
+  if (!enter_release(brf_held(), "refine_batch release", &rc)) return rc;
   drop_refine_batch();
   return 0;
 }
@@ -1517,14 +1457,24 @@ int Engine::matvec_batch(const double* val, int64_t ldval, int nbatch, int nvec,
   // the staged vectors of a host call), one pass of at most 32 vectors per member -- not the solver's six arrays
   const bool direct = dev && pivot_order;
   const int cap = RF_G;
-  if (hipError_t e = ensure_refine_tables()) {
-    (void)hipGetLastError();
-    feature_err_ = std::string("matvec_batch: the operator tables could not be uploaded: ") + hipGetErrorString(e);
-    return alloc_code(e);
+  const bool first = !brf_mv_held_;
+  if (first) {
+    auto t = take();
+    ensure_refine_tables(t);
+    if (!t.ok()) {
+      feature_err_ = std::string("matvec_batch: the operator tables could not be uploaded: ") + hipGetErrorString(t.error());
+      return alloc_code(t.error());
+    }
+    t.commit();
+    rf_users_.hold();
+    brf_mv_held_ = true;
   }
   const size_t gcap = (size_t)nbatch * (size_t)std::min(cap, nvec) * (size_t)n;
   if (!direct && (rc = grow_batch_buffer(&d_brfmv_, &brf_mv_elems_, (dev ? 2 : 3) * gcap, "the workspace of the product"))) {
-    drop_refine_tables();
+    if (first) {   // (what this call held)
+      brf_mv_held_ = false;
+      unhold_refine_tables();
+    }
     return rc;
   }
   const double* dval = val;
@@ -1756,8 +1706,7 @@ int Engine::solve_refined_batch(const double* val, int64_t ldval, int nrhs, doub
 
 // ---- hard linear constraints C x = e ----------------------------------------------------------------------
 void Engine::drop_constraints() {
-  for (void* p : {(void*)cn_.C, (void*)cn_.U, (void*)cn_.G, (void*)cn_.part, (void*)cn_.T})
-    if (p) release_buffer(p);
+  give_back(cn_.C, cn_.U, cn_.G, cn_.part, cn_.T);
   const int64_t rebuilds = cn_.rebuilds;
   cn_ = CnState{};
   cn_.rebuilds = rebuilds;
@@ -1825,18 +1774,19 @@ int Engine::set_constraints(int k, const double* c, int64_t ldc, bool dev, int64
     const size_t kn = sizeof(double) * (size_t)k * (size_t)n, gb = sizeof(double) * (kCnMaxRows * kCnMaxRows + 8),
                  pb = sizeof(double) * (size_t)cn_nchunks(n) * kCnMaxRows * kCnMaxRows,
                  tb = sizeof(double) * 3 * kCnPass * kCnMaxRows;
-    hipError_t e = hipSuccess;
-    const std::pair<double**, size_t> want[] = {{&cn_.C, kn}, {&cn_.U, kn}, {&cn_.G, gb}, {&cn_.part, pb}, {&cn_.T, tb}};
-    for (const auto& w : want)
-      if ((e = fmult_take((void**)w.first, w.second)) != hipSuccess) break;
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      drop_constraints();
+    auto t = take();
+    t.block(&cn_.C, kn);
+    t.block(&cn_.U, kn);
+    t.block(&cn_.G, gb);
+    t.block(&cn_.part, pb);
+    t.block(&cn_.T, tb);
+    if (!t.ok()) {
       feature_err_ = "set_constraints: not enough device memory for C, U and the partial sums (" +
-                     std::to_string((2 * kn + gb + pb + tb) >> 20) + " MiB): " + hipGetErrorString(e);
-      return alloc_code(e);
+                     std::to_string(t.bytes() >> 20) + " MiB): " + hipGetErrorString(t.error());
+      return alloc_code(t.error());
     }
-    cn_.bytes = 2 * kn + gb + pb + tb;
+    t.commit();
+    cn_.bytes = t.bytes();
     cn_.k = k;
   }
   cn_.launches = 0;
@@ -1886,13 +1836,13 @@ int Engine::constrain(int op, int nvec, double* x, int64_t ldx, const double* e,
   const double* dmean = mean;
   if (mean && !dev) {
     if (!d_fmmean_) {
-      hipError_t me = dalloc((void**)&d_fmmean_, sizeof(double) * (size_t)n);
-      if (me != hipSuccess) {
-        (void)hipGetLastError();
-        d_fmmean_ = nullptr;
-        feature_err_ = std::string("sample_constrained: not enough device memory for the mean: ") + hipGetErrorString(me);
-        return alloc_code(me);
+      auto t = take();
+      t(&d_fmmean_, sizeof(double) * (size_t)n);
+      if (!t.ok()) {
+        feature_err_ = std::string("sample_constrained: not enough device memory for the mean: ") + hipGetErrorString(t.error());
+        return alloc_code(t.error());
       }
+      t.commit();
     }
     HIPCHK(hipMemcpyAsync(d_fmmean_, mean, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream_), "mean H2D");
     dmean = d_fmmean_;
