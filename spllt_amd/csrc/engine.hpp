@@ -19,6 +19,9 @@
 
 namespace spx {
 
+struct RfOperator;   // (refine.hpp)
+struct BrfView;
+
 // deadline of every blocking wait, seconds (SPLLT_HIP_TIMEOUT_S, default 180; 0: none)
 double hip_deadline_s();
 // runs fn on the process's submission thread and waits for it with that deadline; a job that
@@ -701,9 +704,10 @@ class Engine {
   // refined solves: operator tables and work vectors (taken on first use, all or nothing)
   int prepare_refine(bool host_val);
   int refine_apply_factor(double* v, int nv);
-  int refine_readback(int nv, std::vector<double>& out);
-  int refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol, int max_iter,
-                   int* iterations, double* error);
+  // the two backends of refine_iterate (refine_driver.hpp): one group of the handle, one pass of the batch
+  struct RefineBackend;
+  struct RefineBatchBackend;
+  RfOperator refine_operator() const;
   // the operator tables, uploaded within the caller's transaction when absent.  Users (rf_users_): the single
   // handle's refined solve (refine_ready_), the batch's (brf_ready_) and the product of a batch (brf_mv_held_).
   void ensure_refine_tables(FeatureTake& t);
@@ -713,9 +717,7 @@ class Engine {
   int prepare_refine_batch(int members);
   void drop_refine_batch();
   int refine_batch_apply_factor(double* v, int nv, int64_t* launches);
-  int refine_batch_pass(const double* dval, int64_t ldval, int nv, double* x, int64_t xstride, int64_t ldx, bool dev,
-                        int done, int nrhs, int method, double tol, int max_iter, int* iterations, double* error,
-                        int64_t* launches, int* worst);
+  BrfView brf_view(int nv) const;   // nv vectors of every member of the batch on the scalars of a pass
   bool brf_ready_ = false;
   bool brf_mv_held_ = false;       // matvec_batch has uploaded or found the operator tables and keeps them
   bool brf_held() const { return brf_ready_ || brf_mv_held_ || d_brfval_ || d_brfmv_; }

@@ -51,6 +51,17 @@ int for_each_group4(int total, F&& f) {
   return 0;
 }
 
+// The products of one block of the factor products on two workspaces, the packed vectors in w0: job 0 is L^T X into
+// w1 and L of that back into w0, job 1 is L X and job 2 L^T X into w1.  product(transpose, from, to); returns the
+// workspace that holds the result.
+template <class P>
+double* factor_mult_sequence(int job, double* w0, double* w1, P&& product) {
+  if (job != 1) product(true, w0, w1);
+  if (job == 0) product(false, w1, w0);
+  if (job == 1) product(false, w0, w1);
+  return job == 0 ? w0 : w1;
+}
+
 // Tables of an engine go to the device as ONE allocation and ONE copy: the parts are laid out in
 // a host staging buffer (256-byte aligned), the typed device pointers are set after the upload.
 // (Two dozen allocations, synchronous copies and frees per engine were two dozen chances per

@@ -13,6 +13,7 @@
 #include "engine.hpp"
 #include "engine_detail.hpp"
 #include "refine.hpp"
+#include "refine_driver.hpp"
 
 namespace spx {
 
@@ -754,8 +755,7 @@ int Engine::release_factor_mult() {
   return 0;
 }
 
-// one block of nv <= rb vectors: pack, the products `job` asks for, unpack (enqueue only).  Job 0 is L^T X into
-// the second workspace and L of that back into the first; job 1 / 2 end in the second one.
+// one block of nv <= rb vectors: pack, the products `job` asks for (factor_mult_sequence), unpack (enqueue only)
 void Engine::enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int rb, int job, bool pivot_order) {
   const int n = S_->n;
   const int* order = pivot_order ? nullptr : d_order_;
@@ -769,10 +769,7 @@ void Engine::enqueue_factor_mult_block(double* x_dev, int64_t ldx, int nv, int r
     launch_factor_mult(stream_, tv, ntiles, d_fmchunks_, fm_nchunks_, transpose, X, Y, rb, fv);
   };
   launch_solve_many_pack(stream_, x_dev, ldx, order, n, nv, rb, d_smW_);
-  if (job != 1) product(true, d_smW_, d_fmW_);
-  if (job == 0) product(false, d_fmW_, d_smW_);
-  if (job == 1) product(false, d_smW_, d_fmW_);
-  launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, job == 0 ? d_smW_ : d_fmW_);
+  launch_solve_many_unpack(stream_, x_dev, ldx, order, n, nv, rb, factor_mult_sequence(job, d_smW_, d_fmW_, product));
 }
 
 int Engine::run_factor_mult(double* x, bool on_device, int nvec, int64_t ldx, int job, bool pivot_order) {
@@ -926,10 +923,8 @@ void Engine::enqueue_factor_mult_batch_block(double* x_dev, int64_t xstride, int
     launch_batch_mult(stream_, v, tv, ntiles, d_fmchunks_, fm_nchunks_, transpose, X, Y, rb, fv);
   };
   launch_batch_mult_pack(stream_, v, false, x_dev, xstride, ldx, order, n, nv, rb, d_bmW_[0]);
-  if (job != 1) product(true, d_bmW_[0], d_bmW_[1]);
-  if (job == 0) product(false, d_bmW_[1], d_bmW_[0]);
-  if (job == 1) product(false, d_bmW_[0], d_bmW_[1]);
-  launch_batch_mult_pack(stream_, v, true, x_dev, xstride, ldx, order, n, nv, rb, job == 0 ? d_bmW_[0] : d_bmW_[1]);
+  launch_batch_mult_pack(stream_, v, true, x_dev, xstride, ldx, order, n, nv, rb,
+                         factor_mult_sequence(job, d_bmW_[0], d_bmW_[1], product));
 }
 
 // device vectors, or groups of at most 32 host vectors per member through the batch's staging buffer
@@ -1144,6 +1139,10 @@ void Engine::ensure_refine_tables(FeatureTake& t) {
   if (t.ok()) t.check(ensure_order());
 }
 
+RfOperator Engine::refine_operator() const {
+  return RfOperator{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+}
+
 void Engine::unhold_refine_tables() {
   rf_users_.drop([this] { give_back(d_rftab_); });
 }
@@ -1155,7 +1154,7 @@ int Engine::prepare_refine(bool host_val) {
   size_t want = 0;
   if (!refine_ready_) {
     ensure_refine_tables(t);
-    RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+    const RfOperator op = refine_operator();
     const size_t slots = (size_t)std::max(std::max(spmv_slots(op), vec_slots(S.n)), RF_AMAX_WG);
     want = sizeof(double) * 6 * RF_G * n1;
     t(&d_rfwork_, want);
@@ -1200,7 +1199,7 @@ int Engine::matvec(const double* val, int nvec, const double* x, int64_t ldx, do
     HIPCHK(hipMemcpyAsync(d_rfval_, val, sizeof(double) * (size_t)S_->nnzA, hipMemcpyHostToDevice, stream_), "val H2D");
     dval = d_rfval_;
   }
-  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  const RfOperator op = refine_operator();
   const size_t gn = (size_t)RF_G * (size_t)n;
   double *wb = d_rfwork_, *wr = d_rfwork_ + 2 * gn, *wq = d_rfwork_ + 4 * gn;
   for (int done = 0; done < nvec;) {
@@ -1236,100 +1235,79 @@ int Engine::refine_apply_factor(double* v, int nv) {
   return nv <= 4 ? solve_dev(v, nv, 0, -1) : solve_many_dev(v, nv, (int64_t)S_->n, 0, true);
 }
 
-// the one array that crosses the bus per iteration: out[q] = best confirmed error, out[32 + q] = state
-int Engine::refine_readback(int nv, std::vector<double>& out) {
-  (void)nv;
-  HIPCHK(hipGetLastError(), "refine launch");
-  HIPCHK(hipMemcpyAsync(out.data(), d_rfds_ + RFD_OUT, sizeof(double) * 2 * RF_G, hipMemcpyDeviceToHost, stream_),
-         "refine state D2H");
-  return sync_stream(stream_, "refine sync");
-}
+// refine_iterate on one group of nv <= RF_G vectors of the handle: work arrays of RF_G vectors each, the scalars at
+// their RFD_* / RFI_* offsets, out[q] = best confirmed error, out[RF_G + q] = state
+struct Engine::RefineBackend {
+  Engine& e;
+  const double* dval;
+  int nv;
+  double* x;   // the caller's vectors of this group
+  int64_t ldx;
+  bool dev;
+  double tol;
+  const int n = e.S_->n;
+  const RfOperator op = e.refine_operator();
+  const hipStream_t s = e.stream_;
 
-int Engine::refine_group(const double* dval, int nv, double* x, int64_t ldx, bool dev, int method, double tol,
-                         int max_iter, int* iterations, double* error) {
-  const int n = S_->n;
-  const size_t gn = (size_t)RF_G * (size_t)n;
-  double *B = d_rfwork_, *X = B + gn, *R = X + gn, *P = R + gn, *Q = P + gn, *XB = Q + gn;
-  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
-  const int sslots = spmv_slots(op), vslots = vec_slots(n);
-  const int* st = d_rfis_ + RFI_ST;
-  const int* decl = d_rfis_ + RFI_DECL;
-  const int* improve = d_rfis_ + RFI_IMPROVE;
-  int rc = 0;
-  if (dev) {
-    launch_permute_vectors(stream_, false, x, ldx, d_order_, n, nv, B);
-  } else {
-    if ((rc = copy_vectors(true, Q, x, ldx, nv, "rhs H2D"))) return rc;
-    launch_permute_vectors(stream_, false, Q, n, d_order_, n, nv, B);
+  int fail(int code, const char* what, hipError_t err) { return e.fail(code, what, err); }
+  double* w(RfVec k) const { return k == RFV_NONE ? nullptr : e.d_rfwork_ + (size_t)k * RF_G * (size_t)n; }
+  const int* sel(RfSel k) const {
+    constexpr int off[] = {0, RFI_ST, RFI_DECL, RFI_IMPROVE};
+    return k == RFSEL_ALL ? nullptr : e.d_rfis_ + off[k];
   }
-  launch_rf_dot(stream_, n, nv, B, B, nullptr, 0, d_rfpart_);
-  launch_rf_finalize(stream_, RFS_BNORM, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
-  // x = M^-1 b, r = b - A x, the error of the first iterate
-  launch_rf_copy(stream_, n, nv, X, B, nullptr, 0);
-  if ((rc = refine_apply_factor(X, nv))) return rc;
-  auto true_residual = [&](const int* sel, int want, int flag) {
-    launch_spmv(stream_, op, dval, X, n, B, R, n, nv, sel, want, d_rfpart_);
-    launch_rf_finalize(stream_, RFS_TRUE, d_rfpart_, sslots, nv, tol, flag, d_rfds_, d_rfis_);
-    launch_rf_copy(stream_, n, nv, XB, X, improve, 1);   // the best confirmed iterate
-  };
-  true_residual(st, 0, 0);
-  std::vector<double> out(2 * RF_G, 0.0);
-  if ((rc = refine_readback(nv, out))) return rc;
-  auto active = [&]() {
-    for (int q = 0; q < nv; ++q)
-      if (out[(size_t)RF_G + q] == 0.0) return true;
-    return false;
-  };
-  std::vector<int> its((size_t)nv, 0);
-  for (int it = 0; it < max_iter && active();) {
-    ++it;
-    for (int q = 0; q < nv; ++q)
-      if (out[(size_t)RF_G + q] == 0.0) its[(size_t)q] = it;
-    if (method == 0) {
-      // x += M^-1 r ; r = b - A x
-      launch_rf_copy(stream_, n, nv, P, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
-      if ((rc = refine_apply_factor(P, nv))) return rc;
-      launch_rf_axpy(stream_, n, nv, nullptr, X, P, nullptr, nullptr, st, 0, nullptr);
-      true_residual(st, 0, 0);
-    } else {
-      // z = M^-1 r (in q) ; beta = r.z / (r.z)_old, 0 after a restart ; p = z + beta p
-      launch_rf_copy(stream_, n, nv, Q, R, st, 0, true);   // (frozen vectors: a zero column for the sweep)
-      if ((rc = refine_apply_factor(Q, nv))) return rc;
-      launch_rf_dot(stream_, n, nv, R, Q, st, 0, d_rfpart_);
-      launch_rf_finalize(stream_, RFS_BETA, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
-      launch_rf_pupdate(stream_, n, nv, d_rfds_ + RFD_BETA, P, Q, st, 0);
-      // q = A p with the partials of p.q ; alpha = r.z / p.q ; x += alpha p, r -= alpha q
-      launch_spmv(stream_, op, dval, P, n, nullptr, Q, n, nv, st, 0, d_rfpart_);
-      launch_rf_finalize(stream_, RFS_ALPHA, d_rfpart_, sslots, nv, tol, 0, d_rfds_, d_rfis_);
-      launch_rf_axpy(stream_, n, nv, d_rfds_ + RFD_ALPHA, X, P, R, Q, st, 0, d_rfpart_);
-      launch_rf_finalize(stream_, RFS_REC, d_rfpart_, vslots, nv, tol, 0, d_rfds_, d_rfis_);
-      // what the recurrence declares converged is confirmed with a true residual (no work if nothing is declared)
-      true_residual(decl, 1, 1);
+  double* part(bool partials) const { return partials ? e.d_rfpart_ : nullptr; }
+
+  int pairs() const { return nv; }
+  int stride() const { return RF_G; }
+  int vslots() const { return vec_slots(n); }
+  int sslots() const { return spmv_slots(op); }
+  bool fits() const { return true; }
+  int permute_in() {
+    if (dev) {
+      launch_permute_vectors(s, false, x, ldx, e.d_order_, n, nv, w(RFV_B));
+      return 0;
     }
-    if ((rc = refine_readback(nv, out))) return rc;
+    if (int rc = e.copy_vectors(true, w(RFV_Q), x, ldx, nv, "rhs H2D")) return rc;
+    launch_permute_vectors(s, false, w(RFV_Q), n, e.d_order_, n, nv, w(RFV_B));
+    return 0;
   }
-  if (method == 1 && active()) {
-    // out of iterations: the error reported is that of a true residual
-    launch_rf_finalize(stream_, RFS_FINAL, d_rfpart_, 0, nv, tol, 0, d_rfds_, d_rfis_);
-    true_residual(decl, 1, 1);
-    if ((rc = refine_readback(nv, out))) return rc;
+  void dot(RfVec a, RfVec b, RfSel k, int want, bool) { launch_rf_dot(s, n, nv, w(a), w(b), sel(k), want, e.d_rfpart_); }
+  void finalize(int stage, int nslots, int flag) {
+    launch_rf_finalize(s, stage, e.d_rfpart_, nslots, nv, tol, flag, e.d_rfds_, e.d_rfis_);
   }
-  if (dev) {
-    launch_permute_vectors(stream_, true, x, ldx, d_order_, n, nv, XB);
-  } else {
-    launch_permute_vectors(stream_, true, Q, n, d_order_, n, nv, XB);
-    if ((rc = copy_vectors(false, Q, x, ldx, nv, "x D2H"))) return rc;
+  void copy(RfVec dst, RfVec src, RfSel k, int want, bool zero_others) {
+    launch_rf_copy(s, n, nv, w(dst), w(src), sel(k), want, zero_others);
   }
-  HIPCHK(hipGetLastError(), "refine launch");
-  if ((rc = sync_stream(stream_, "refine sync"))) return rc;
-  int worst = 0;
-  for (int q = 0; q < nv; ++q) {
-    if (iterations) iterations[q] = its[(size_t)q];
-    if (error) error[q] = out[(size_t)q];
-    if (out[(size_t)RF_G + q] != 1.0) worst = 1;
+  int apply_factor(RfVec v) { return e.refine_apply_factor(w(v), nv); }
+  void spmv(RfVec xv, RfVec b, RfVec y, RfSel k, int want, bool partials) {
+    launch_spmv(s, op, dval, w(xv), n, w(b), w(y), n, nv, sel(k), want, part(partials));
   }
-  return worst;
-}
+  void axpy(bool alpha, RfVec xv, RfVec p, RfVec r, RfVec q, RfSel k, int want, bool partials) {
+    launch_rf_axpy(s, n, nv, alpha ? e.d_rfds_ + RFD_ALPHA : nullptr, w(xv), w(p), w(r), w(q), sel(k), want, part(partials));
+  }
+  void pupdate(RfVec p, RfVec z, RfSel k, int want) {
+    launch_rf_pupdate(s, n, nv, e.d_rfds_ + RFD_BETA, w(p), w(z), sel(k), want);
+  }
+  // the one array that crosses the bus per iteration
+  int readback(std::vector<double>& out) {
+    HIPCHK(hipGetLastError(), "refine launch");
+    HIPCHK(hipMemcpyAsync(out.data(), e.d_rfds_ + RFD_OUT, sizeof(double) * 2 * RF_G, hipMemcpyDeviceToHost, s),
+           "refine state D2H");
+    return e.sync_stream(s, "refine sync");
+  }
+  int permute_out(RfVec src) {
+    if (dev) {
+      launch_permute_vectors(s, true, x, ldx, e.d_order_, n, nv, w(src));
+      return 0;
+    }
+    launch_permute_vectors(s, true, w(RFV_Q), n, e.d_order_, n, nv, w(src));
+    return e.copy_vectors(false, w(RFV_Q), x, ldx, nv, "x D2H");
+  }
+  int finish() {
+    HIPCHK(hipGetLastError(), "refine launch");
+    return e.sync_stream(s, "refine sync");
+  }
+};
 
 int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, bool dev, int method, double tol,
                           int max_iter, int* iterations, double* error) {
@@ -1358,12 +1336,17 @@ int Engine::solve_refined(const double* val, int nrhs, double* x, int64_t ldx, b
   launch_rf_absmax(stream_, dval, S_->nnzA, d_rfpart_);
   launch_rf_finalize(stream_, RFS_AMAX, d_rfpart_, RF_AMAX_WG, 0, tol, 0, d_rfds_, d_rfis_);
   int worst = 0;
+  std::vector<int> its;
+  std::vector<double> out;
   for (int done = 0; done < nrhs;) {
     const int nv = std::min(RF_G, nrhs - done);
-    rc = refine_group(dval, nv, x + (int64_t)done * ldx, ldx, dev, method, tol, max_iter,
-                      iterations ? iterations + done : nullptr, error ? error + done : nullptr);
-    if (rc < 0) return rc;
-    worst |= rc;
+    RefineBackend be{*this, dval, nv, x + (int64_t)done * ldx, ldx, dev, tol};
+    if ((rc = refine_iterate(be, method, max_iter, its, out))) return rc;
+    for (int q = 0; q < nv; ++q) {
+      if (iterations) iterations[done + q] = its[(size_t)q];
+      if (error) error[done + q] = out[(size_t)q];
+      if (out[(size_t)RF_G + q] != 1.0) worst = 1;
+    }
     done += nv;
   }
   return worst;
@@ -1393,7 +1376,7 @@ int Engine::prepare_refine_batch(int members) {
   hipError_t e = tables.error();
   size_t want = 0;
   if (e == hipSuccess) {
-    const RfOperator op{nullptr, nullptr, nullptr, nullptr, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+    const RfOperator op = refine_operator();
     const size_t slots = (size_t)std::max(spmv_slots(op), vec_slots(S_->n));
     for (int rb = RF_G; rb >= 8; rb /= 2) {   // (one transaction per width)
       const size_t np = nb * (size_t)rb;
@@ -1486,7 +1469,7 @@ int Engine::matvec_batch(const double* val, int64_t ldval, int nbatch, int nvec,
     dval = d_brfval_;
     ldv = nnz;
   }
-  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
+  const RfOperator op = refine_operator();
   BrfTally t;
   for (int done = 0; done < nvec && t.fits;) {
     const int nv = std::min(cap, nvec - done);
@@ -1543,112 +1526,96 @@ int Engine::refine_batch_apply_factor(double* v, int nv, int64_t* launches) {
   return rc == kErrNotPosDef ? 0 : rc;
 }
 
-// one pass: nv <= brf_rb_ vectors of every member, the loop of refine_group for all (member, vector) pairs at once
-int Engine::refine_batch_pass(const double* dval, int64_t ldval, int nv, double* x, int64_t xstride, int64_t ldx, bool dev,
-                              int done, int nrhs, int method, double tol, int max_iter, int* iterations, double* error,
-                              int64_t* launches, int* worst) {
-  const int n = S_->n, nbatch = bt_.nbatch;
-  const size_t np = (size_t)nbatch * (size_t)nv, gn = np * (size_t)n;
-  double *B = d_brfwork_, *X = B + gn, *R = X + gn, *P = R + gn, *Q = P + gn, *XB = Q + gn;
-  const RfOperator op{d_rfrowptr_, d_rfcol_, d_rfsrc_, d_rfrows_, {rf_nrows_[0], rf_nrows_[1], rf_nrows_[2]}};
-  const int sslots = spmv_slots(op), vslots = vec_slots(n);
-  const BrfView v{bt_.flag, nbatch, nv, d_brfds_, d_brfds_ + brf_capacity_, d_brfds_ + 2 * brf_capacity_, d_brfis_, d_brfpart_};
-  const int *st = v.st(), *decl = v.decl(), *improve = v.improve();
+BrfView Engine::brf_view(int nv) const {
+  return BrfView{bt_.flag, bt_.nbatch, nv, d_brfds_, d_brfds_ + brf_capacity_, d_brfds_ + 2 * brf_capacity_, d_brfis_, d_brfpart_};
+}
+
+// refine_iterate on one pass: nv <= brf_rb_ vectors of every member, np = nbatch * nv pairs.  A member without a
+// factor is neither copied nor permuted.  The launches of the pass and of its sweeps are added to brf_info_[2]; a
+// launch that does not fit a grid makes the pass end with -99.
+struct Engine::RefineBatchBackend {
+  Engine& e;
+  const double* dval;
+  int64_t ldval;
+  int nv;
+  double* x;   // vector 0 of this pass of member 0
+  int64_t xstride, ldx;
+  bool dev;
+  double tol;
+  const int n = e.S_->n, nbatch = e.bt_.nbatch;
+  const RfOperator op = e.refine_operator();
+  const BrfView v = e.brf_view(nv);
+  const hipStream_t s = e.stream_;
   const int64_t ws = (int64_t)nv * n;   // a member's stride in the work arrays
   BrfTally t;
-  int rc = 0;
-  auto ok = [&](int64_t i) { return bt_.hflag[(size_t)i] == INT_MAX; };
-  // (x + done * ldx: vector `done` of member 0; a member without a factor is neither copied nor permuted)
-  double* xg = x + (int64_t)done * ldx;
-  if (dev) {
-    t.add(launch_brf_permute(stream_, v, false, xg, xstride, ldx, d_order_, n, B));
-  } else {
-    for (int b = 0; b < nbatch; ++b)
-      if (ok(b) && (rc = copy_vectors(true, Q + (int64_t)b * ws, xg + (int64_t)b * xstride, ldx, nv, "refine_batch rhs H2D")))
-        return rc;
-    t.add(launch_brf_permute(stream_, v, false, Q, ws, n, d_order_, n, B));
+
+  int fail(int code, const char* what, hipError_t err) { return e.fail(code, what, err); }
+  bool ok(int b) const { return e.bt_.hflag[(size_t)b] == INT_MAX; }
+  double* w(RfVec k) const { return k == RFV_NONE ? nullptr : e.d_brfwork_ + (int64_t)k * nbatch * ws; }
+  const int* sel(RfSel k) const {
+    return k == RFSEL_ALL ? nullptr : (k == RFSEL_ST ? v.st() : (k == RFSEL_DECL ? v.decl() : v.improve()));
   }
-  t.add(launch_brf_dot(stream_, v, n, B, B, nullptr, 0, true));
-  t.add(launch_brf_finalize(stream_, v, RFS_BNORM, vslots, tol, 0));
-  // x = M^-1 b, r = b - A x, the error of the first iterate
-  t.add(launch_brf_copy(stream_, v, n, X, B, nullptr, 0));
-  if (!t.fits) return -99;
-  if ((rc = refine_batch_apply_factor(X, nv, launches))) return rc;
-  auto true_residual = [&](const int* sel, int want, int flag) {
-    t.add(launch_bspmv(stream_, op, v, dval, ldval, X, ws, n, B, R, ws, n, sel, want, true));
-    t.add(launch_brf_finalize(stream_, v, RFS_TRUE, sslots, tol, flag));
-    t.add(launch_brf_copy(stream_, v, n, XB, X, improve, 1));   // the best confirmed iterate
-  };
-  true_residual(st, 0, 0);
-  // the one array that crosses the bus per iteration: out[g] = best confirmed error, out[np + g] = state
-  std::vector<double> out(2 * np, 0.0);
-  auto readback = [&]() -> int {
-    HIPCHK(hipGetLastError(), "refine_batch launch");
-    HIPCHK(hipMemcpyAsync(out.data(), v.out(), sizeof(double) * 2 * np, hipMemcpyDeviceToHost, stream_), "refine_batch state D2H");
-    return sync_stream(stream_, "refine_batch sync");
-  };
-  if ((rc = readback())) return rc;
-  auto active = [&]() {
-    for (size_t g = 0; g < np; ++g)
-      if (out[np + g] == 0.0) return true;
-    return false;
-  };
-  std::vector<int> its(np, 0);
-  for (int it = 0; it < max_iter && active() && t.fits;) {
-    ++it;
-    for (size_t g = 0; g < np; ++g)
-      if (out[np + g] == 0.0) its[g] = it;
-    if (method == 0) {
-      // x += M^-1 r ; r = b - A x
-      t.add(launch_brf_copy(stream_, v, n, P, R, st, 0, true));   // (frozen pairs: a zero column for the sweep)
-      if ((rc = refine_batch_apply_factor(P, nv, launches))) return rc;
-      t.add(launch_brf_axpy(stream_, v, n, nullptr, X, P, nullptr, nullptr, st, 0, false));
-      true_residual(st, 0, 0);
-    } else {
-      // z = M^-1 r (in q) ; beta = r.z / (r.z)_old, 0 after a restart ; p = z + beta p
-      t.add(launch_brf_copy(stream_, v, n, Q, R, st, 0, true));   // (frozen pairs: a zero column for the sweep)
-      if ((rc = refine_batch_apply_factor(Q, nv, launches))) return rc;
-      t.add(launch_brf_dot(stream_, v, n, R, Q, st, 0, false));
-      t.add(launch_brf_finalize(stream_, v, RFS_BETA, vslots, tol, 0));
-      t.add(launch_brf_pupdate(stream_, v, n, v.beta(), P, Q, st, 0));
-      // q = A p with the partials of p.q ; alpha = r.z / p.q ; x += alpha p, r -= alpha q
-      t.add(launch_bspmv(stream_, op, v, dval, ldval, P, ws, n, nullptr, Q, ws, n, st, 0, true));
-      t.add(launch_brf_finalize(stream_, v, RFS_ALPHA, sslots, tol, 0));
-      t.add(launch_brf_axpy(stream_, v, n, v.alpha(), X, P, R, Q, st, 0, true));
-      t.add(launch_brf_finalize(stream_, v, RFS_REC, vslots, tol, 0));
-      // what the recurrence declares converged is confirmed with a true residual (no work if nothing is declared)
-      true_residual(decl, 1, 1);
+
+  int pairs() const { return v.np(); }
+  int stride() const { return v.np(); }
+  int vslots() const { return vec_slots(n); }
+  int sslots() const { return spmv_slots(op); }
+  bool fits() const { return t.fits; }
+  int permute_in() {
+    if (dev) {
+      t.add(launch_brf_permute(s, v, false, x, xstride, ldx, e.d_order_, n, w(RFV_B)));
+      return 0;
     }
-    if ((rc = readback())) return rc;
+    for (int b = 0; b < nbatch; ++b)
+      if (int rc = ok(b) ? e.copy_vectors(true, w(RFV_Q) + b * ws, x + b * xstride, ldx, nv, "refine_batch rhs H2D") : 0)
+        return rc;
+    t.add(launch_brf_permute(s, v, false, w(RFV_Q), ws, n, e.d_order_, n, w(RFV_B)));
+    return 0;
   }
-  if (method == 1 && active() && t.fits) {
-    // out of iterations: the error reported is that of a true residual
-    t.add(launch_brf_finalize(stream_, v, RFS_FINAL, 0, tol, 0));
-    true_residual(decl, 1, 1);
-    if ((rc = readback())) return rc;
+  void dot(RfVec a, RfVec b, RfSel k, int want, bool residual_like) {
+    t.add(launch_brf_dot(s, v, n, w(a), w(b), sel(k), want, residual_like));
   }
-  if (dev) {
-    t.add(launch_brf_permute(stream_, v, true, xg, xstride, ldx, d_order_, n, XB));
-  } else {
-    t.add(launch_brf_permute(stream_, v, true, Q, ws, n, d_order_, n, XB));
+  void finalize(int stage, int nslots, int flag) { t.add(launch_brf_finalize(s, v, stage, nslots, tol, flag)); }
+  void copy(RfVec dst, RfVec src, RfSel k, int want, bool zero_others) {
+    t.add(launch_brf_copy(s, v, n, w(dst), w(src), sel(k), want, zero_others));
+  }
+  int apply_factor(RfVec k) { return e.refine_batch_apply_factor(w(k), nv, &e.brf_info_[2]); }
+  void spmv(RfVec xv, RfVec b, RfVec y, RfSel k, int want, bool partials) {
+    t.add(launch_bspmv(s, op, v, dval, ldval, w(xv), ws, n, w(b), w(y), ws, n, sel(k), want, partials));
+  }
+  void axpy(bool alpha, RfVec xv, RfVec p, RfVec r, RfVec q, RfSel k, int want, bool partials) {
+    t.add(launch_brf_axpy(s, v, n, alpha ? v.alpha() : nullptr, w(xv), w(p), w(r), w(q), sel(k), want, partials));
+  }
+  void pupdate(RfVec p, RfVec z, RfSel k, int want) { t.add(launch_brf_pupdate(s, v, n, v.beta(), w(p), w(z), sel(k), want)); }
+  // the one array that crosses the bus per iteration
+  int readback(std::vector<double>& out) {
+    HIPCHK(hipGetLastError(), "refine_batch launch");
+    HIPCHK(hipMemcpyAsync(out.data(), v.out(), sizeof(double) * 2 * (size_t)v.np(), hipMemcpyDeviceToHost, s),
+           "refine_batch state D2H");
+    return e.sync_stream(s, "refine_batch sync");
+  }
+  int permute_out(RfVec src) {
+    if (dev) {
+      t.add(launch_brf_permute(s, v, true, x, xstride, ldx, e.d_order_, n, w(src)));
+      return 0;
+    }
+    t.add(launch_brf_permute(s, v, true, w(RFV_Q), ws, n, e.d_order_, n, w(src)));
     HIPCHK(hipGetLastError(), "refine_batch launch");
     for (int b = 0; b < nbatch; ++b)
-      if (ok(b) && (rc = copy_vectors(false, Q + (int64_t)b * ws, xg + (int64_t)b * xstride, ldx, nv, "refine_batch x D2H")))
+      if (int rc = ok(b) ? e.copy_vectors(false, w(RFV_Q) + b * ws, x + b * xstride, ldx, nv, "refine_batch x D2H") : 0)
         return rc;
+    return 0;
   }
-  HIPCHK(hipGetLastError(), "refine_batch launch");
-  if ((rc = sync_stream(stream_, "refine_batch sync"))) return rc;
-  *launches += t.n;
-  if (!t.fits) return -99;
-  for (int b = 0; b < nbatch; ++b)
-    for (int q = 0; q < nv; ++q) {
-      const size_t g = (size_t)b * nv + q, o = (size_t)b * nrhs + done + q;
-      if (iterations) iterations[o] = ok(b) ? its[g] : 0;
-      if (error) error[o] = ok(b) ? out[g] : std::numeric_limits<double>::quiet_NaN();
-      if (ok(b) && out[np + g] != 1.0) *worst = 1;
-    }
-  return 0;
-}
+  int finish() {
+    HIPCHK(hipGetLastError(), "refine_batch launch");
+    if (int rc = e.sync_stream(s, "refine_batch sync")) return rc;
+    e.brf_info_[2] += t.n;
+    if (t.fits) return 0;
+    if (e.feature_err_.empty())
+      e.feature_err_ = "solve_refined_batch: a launch has more work items for one member than a grid holds";
+    return -99;
+  }
+};
 
 int Engine::solve_refined_batch(const double* val, int64_t ldval, int nrhs, double* x, int64_t ldx, bool dev, int method,
                                 double tol, int max_iter, int* iterations, double* error) {
@@ -1680,26 +1647,34 @@ int Engine::solve_refined_batch(const double* val, int64_t ldval, int nrhs, doub
     dval = d_brfval_;
     ldv = nnz;
   }
-  int64_t launches = 0;
   {
-    const BrfView v{bt_.flag, nbatch, 1, d_brfds_, d_brfds_ + brf_capacity_, d_brfds_ + 2 * brf_capacity_, d_brfis_, d_brfpart_};
-    const int k = launch_brf_absmax(stream_, v, dval, ldv, nnz);
+    const int k = launch_brf_absmax(stream_, brf_view(1), dval, ldv, nnz);
     if (k < 0) return -99;
-    launches += k;
+    brf_info_[2] = k;
   }
   int worst = 0, passes = 0;
+  std::vector<int> its;
+  std::vector<double> out;
   for (int done = 0; done < nrhs;) {
     const int nv = std::min(brf_rb_, nrhs - done);
-    rc = refine_batch_pass(dval, ldv, nv, x, (int64_t)nrhs * ldx, ldx, dev, done, nrhs, method, tol, max_iter, iterations,
-                           error, &launches, &worst);
-    if (rc == -99 && feature_err_.empty())
-      feature_err_ = "solve_refined_batch: a launch has more work items for one member than a grid holds";
-    if (rc) return rc;
+    RefineBatchBackend be{*this, dval, ldv, nv, x + (int64_t)done * ldx, (int64_t)nrhs * ldx, ldx, dev, tol};
+    if ((rc = refine_iterate(be, method, max_iter, its, out))) {
+      brf_info_[2] = 0;   // (the counts of a call that went through)
+      return rc;
+    }
+    const size_t np = (size_t)nbatch * (size_t)nv;
+    for (int b = 0; b < nbatch; ++b)
+      for (int q = 0; q < nv; ++q) {
+        const size_t g = (size_t)b * nv + q, o = (size_t)b * nrhs + done + q;
+        const bool ok = bt_.hflag[(size_t)b] == INT_MAX;   // (else: a member without a factor)
+        if (iterations) iterations[o] = ok ? its[g] : 0;
+        if (error) error[o] = ok ? out[g] : std::numeric_limits<double>::quiet_NaN();
+        if (ok && out[np + g] != 1.0) worst = 1;
+      }
     ++passes;
     done += nv;
   }
   brf_info_[1] = passes;
-  brf_info_[2] = launches;
   const int failed = batch_failed();
   return failed ? failed : worst;
 }
