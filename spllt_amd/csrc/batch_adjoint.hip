@@ -15,7 +15,8 @@
 //                 workgroup: six 64 x 64 products, no scratch traffic
 //
 // The bodies of seed, scale and diag are those of the single handle (fa_body.hpp): per member the same sums in
-// the same order.  Every product runs on v_mfma_f64_16x16x4_f64 with LDS operands in the layout of
+// the same order; the SYMM body and the gather of the fused kernel's first product are those of the selected
+// inversion (si_body.hpp: si_symm_body<true>, si_small_gather_body<true, ..>).  Every product runs on v_mfma_f64_16x16x4_f64 with LDS operands in the layout of
 // factor_adjoint.hip (FA_LDA = 66 for the A operand, FA_LDB = 80 for the B operand: its header has the bank
 // argument).  No atomics, no waiting between workgroups, no loop bound or branch that depends on data: two
 // sweeps over the same L_b and G_b bits give the same bits, whatever the other members hold.
@@ -27,6 +28,7 @@
 #include "batch_split.hpp"
 #include "fa_body.hpp"
 #include "kernels.hpp"
+#include "si_body.hpp"
 
 namespace spx {
 
@@ -126,29 +128,10 @@ __global__ __launch_bounds__(256) void k_bfa_fused(BatchSelinvView s, const Seli
   d4 acc[4];
   bfa_zero(acc);
   if (nR > 0) {   // (the same for every thread of the workgroup)
-    const SelinvRow* nrows = rows + u.row_off + u.rbase;
-    if (tid < nR) Ri[tid] = nrows[tid];
-    __syncthreads();
-    const double* Lrj = L + u.off + (int64_t)(u.c0 + pn) * u.ld + u.c0;
     double* Grj = G + u.off + (int64_t)(u.c0 + pn) * u.ld + u.c0;
     double lreg[16];
-    // 1: the lower half of G_RR through the descriptor of the column's row (the K row fastest across the
-    // threads), mirrored into the upper half, the diagonal doubled; L_RJ
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int i = ti0 + 4 * q, k = tj;
-      double v = 0.0;
-      if (i < nR && k <= i) {
-        const SelinvRow d = Ri[k];
-        const int64_t qpos = d.map < 0 ? (int64_t)(u.rbase + i) : (int64_t)relpos[(int64_t)d.map + i - k];
-        v = G[d.cbase + qpos * d.ld];
-        if (k == i) v += v;
-      }
-      if (k <= i || i >= nR || k >= nR) At[i][k] = v;
-      if (k < i && i < nR) At[k][i] = v;
-      lreg[q] = (i < nR && tj < pn) ? Lrj[(int64_t)i * u.ld + tj] : 0.0;
-      Bt[i][tj] = lreg[q];
-    }
+    // 1: S (tril(G_RR) mirrored, the diagonal doubled) and L_RJ
+    si_small_gather_body<true, FA_LDA, FA_LDB>(u, rows, relpos, L, G, At, Bt, Ri, lreg);
     __syncthreads();
     fadj_mm4(At, 16 * wv, Bt, (nR + 3) >> 2, ncb, lane, acc);   // Y = S L_RJ
     __syncthreads();

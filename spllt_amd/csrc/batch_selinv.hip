@@ -5,10 +5,10 @@
 // scratch + b sstride, and every table is read shared.  A member whose not-positive-definite flag is set
 // is skipped by every workgroup: nothing of it is read or written.
 //
-//   k_batch_selinv_symm / _scale / _diag   the three step kernels of selinv.hip with the member dimension:
-//                         the same recurrences, the same fixed summation order
+//   k_batch_selinv_symm / _scale / _diag   the three step kernels: si_symm_body, si_scale_body and si_diag_body
+//                         of si_body.hpp (its header describes the steps) on the arenas of member b
 //   k_batch_selinv_fused  a whole step (SYMM + SCALE + DIAG) of one unit with nR <= 64 and one K slice in
-//                         one workgroup: Z_RR gathered into LDS, the four products on
+//                         one workgroup: Z_RR gathered into LDS (si_small_gather_body), the four products on
 //                         v_mfma_f64_16x16x4_f64, no scratch traffic
 //   k_batch_selinv_diag_gather   (A_b^-1)_ii in the user's variable order, NaN for a failed member
 //   k_batch_selinv_pattern       (A_b^-1) at the entries of the caller's CSC-lower pattern, in the order of
@@ -18,7 +18,7 @@
 // bit-identical Z for every member.  Nothing is read or written outside the rows and columns a table
 // entry names, so a member never touches its neighbour's arena.
 //
-// MFMA lane map (header of kernels.hip): lane l supplies A[l&15][l>>4] and B[l>>4][l&15] and receives
+// MFMA lane map (header of si_body.hpp): lane l supplies A[l&15][l>>4] and B[l>>4][l&15] and receives
 // C[(l>>4) + 4 r][l&15] in register r.
 #include <hip/hip_runtime.h>
 
@@ -29,254 +29,56 @@
 
 #include "batch_split.hpp"
 #include "kernels.hpp"
+#include "si_body.hpp"
 
 namespace spx {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr int BI_KC = 32;           // K rows per LDS stage of k_batch_selinv_symm
-constexpr int BI_T = kSelinvTile;   // 64
-constexpr int BI_LD = BI_T + 1;     // LDS row stride of the fused kernel's two operand buffers
+constexpr int BI_LD = SI_T + 1;     // LDS row stride of the fused kernel's two operand buffers
 
 // ---------------------------------------------------------------------------
-// k_selinv_symm of selinv.hip for member b (dense-path shortcut included).  kDoubleDiag: the gathered block
-// is S = tril(G_RR) + tril(G_RR)^T of the factor adjoint (batch_adjoint.hip: s.Z is then the adjoint arena), whose
-// diagonal counts twice; a diagonal entry occurs in the generic branch only.  The inversion instantiates false.
+// The step kernels: workgroup -> (member b, work item), the member's flag before any barrier, the member's
+// arenas, the body.  kDoubleDiag = true is the SYMM step of the factor adjoint (batch_adjoint.hip: s.Z is then
+// the adjoint arena).
 // ---------------------------------------------------------------------------
 template <bool kDoubleDiag>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_batch_selinv_symm(BatchSelinvView s, const UpdTile* __restrict__ tiles, int64_t count,
                                                            const SelinvUnit* __restrict__ units,
                                                            const SelinvRow* __restrict__ rows,
                                                            const int* __restrict__ relpos) {
-  __shared__ double As[BI_T][BI_KC + 1];
-  __shared__ double Bs[BI_KC][BI_T + 1];
-  __shared__ SelinvRow Ri[BI_T];
+  __shared__ double As[SI_T][SI_KC + 1];
+  __shared__ double Bs[SI_KC][SI_T + 1];
+  __shared__ SelinvRow Ri[SI_T];
   int b;
   int64_t wi;
   bsi_split(s.v, count, b, wi);
   if (s.v.flag[b] != INT_MAX) return;
-  const double* __restrict__ L = s.v.L + (int64_t)b * s.v.lstride;
-  const double* __restrict__ Z = s.Z + (int64_t)b * s.v.lstride;
-  double* __restrict__ scratch = s.scratch + (int64_t)b * s.sstride;
   const UpdTile t = tiles[wi];
-  const SelinvUnit u = units[t.unit];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int nR = u.nR, pn = u.pn;
-  const int i0 = t.ti * BI_T;
-  const int k0 = t.tj * u.kslice;
-  const int k1 = min(nR, k0 + u.kslice);
-  const SelinvRow* nrows = rows + u.row_off;
-  if (tid < BI_T && i0 + tid < nR) Ri[tid] = nrows[u.rbase + i0 + tid];
-  __syncthreads();
-  const int ak = tid % BI_KC, ai0 = tid / BI_KC;
-  const int bj = tid & 63, bk0 = tid >> 6;
-  const double* Lrj = L + u.off + (int64_t)(u.c0 + pn) * u.ld + u.c0;
-  double ra[8], rb[8];
-  auto upper = [&](int kb) { return i0 + BI_T <= kb; };
-  auto lower = [&](int kb) { return kb + BI_KC <= i0; };
-  auto own_block = [&](int first, int last) {   // R-local rows [first, last]
-    const int a = u.rbase + first, e = u.rbase + last;
-    return e < u.ncol && a / u.nb == e / u.nb;
-  };
-  const bool tile_dense = own_block(i0, min(nR, i0 + BI_T) - 1);
-  const SelinvRow dI0 = Ri[0];
-  auto load = [&](int kb) {
-    const int klast = min(k1, kb + BI_KC) - 1;
-    if (upper(kb) && tile_dense) {
-      const int il = tid & 63;
-      const bool iin = i0 + il < nR;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int kk = kb + (tid >> 6) + 4 * q;
-        ra[q] = (iin && kk < k1) ? Z[dI0.cbase + il + (int64_t)(u.rbase + kk) * dI0.ld] : 0.0;
-      }
-    } else if (lower(kb) && own_block(kb, klast)) {
-      const SelinvRow dK0 = nrows[u.rbase + kb];
-      const bool kin = kb + ak < k1;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int ii = i0 + ai0 + 8 * q;
-        ra[q] = (kin && ii < nR) ? Z[dK0.cbase + ak + (int64_t)(u.rbase + ii) * dK0.ld] : 0.0;
-      }
-    } else if (upper(kb)) {
-      const int il = tid & 63, ii = i0 + il;
-      const bool iin = ii < nR;
-      const SelinvRow d = iin ? Ri[il] : SelinvRow{0, 0, -1};
-      const int ri = u.rbase + ii;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int kk = kb + (tid >> 6) + 4 * q;
-        double v = 0.0;
-        if (iin && kk < k1) {
-          const int rk = u.rbase + kk;
-          const int64_t qpos = d.map < 0 ? (int64_t)rk : (int64_t)relpos[(int64_t)d.map + rk - ri];
-          v = Z[d.cbase + qpos * d.ld];
-        }
-        ra[q] = v;
-      }
-    } else {
-      const int kk = kb + ak;
-      const bool kin = kk < k1;
-      const int rk = u.rbase + kk;
-      SelinvRow dk{0, 0, -1};
-      if (kin) dk = nrows[rk];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int ii = i0 + ai0 + 8 * q;
-        double v = 0.0;
-        if (kin && ii < nR) {
-          const int ri = u.rbase + ii;
-          // lower half (r_i >= r_k) through row k's descriptor, upper half transposed through row i's
-          const SelinvRow d = ri >= rk ? dk : Ri[ai0 + 8 * q];
-          const int a = ri >= rk ? ri : rk, e = ri >= rk ? rk : ri;
-          const int64_t qpos = d.map < 0 ? (int64_t)a : (int64_t)relpos[(int64_t)d.map + a - e];
-          v = Z[d.cbase + qpos * d.ld];
-          if (kDoubleDiag && ri == rk) v += v;
-        }
-        ra[q] = v;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int kr = kb + bk0 + 4 * q;
-      rb[q] = (kr < k1 && bj < pn) ? Lrj[(int64_t)kr * u.ld + bj] : 0.0;
-    }
-  };
-  d4 acc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
-  const int ncb = (pn + 15) >> 4;
-  load(k0);
-  for (int kb = k0; kb < k1; kb += BI_KC) {
-    __syncthreads();
-    if (upper(kb)) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) As[tid & 63][(tid >> 6) + 4 * q] = ra[q];
-    } else {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) As[ai0 + 8 * q][ak] = ra[q];
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) Bs[bk0 + 4 * q][bj] = rb[q];
-    __syncthreads();
-    if (kb + BI_KC < k1) load(kb + BI_KC);   // in flight during the products
-#pragma unroll
-    for (int st = 0; st < BI_KC / 4; ++st) {
-      const double a = As[16 * wv + (lane & 15)][4 * st + (lane >> 4)];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < ncb) acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[4 * st + (lane >> 4)][16 * c + (lane & 15)], acc[c], 0, 0, 0);
-    }
-  }
-  double* Y = scratch + u.y_off + (int64_t)t.tj * nR * pn;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = i0 + 16 * wv + (lane >> 4) + 4 * r, col = 16 * c + (lane & 15);
-      if (row < nR && col < pn) Y[(int64_t)row * pn + col] = acc[c][r];
-    }
+  si_symm_body<kDoubleDiag>(t, units[t.unit], rows, relpos, s.v.L + (int64_t)b * s.v.lstride,
+                            s.Z + (int64_t)b * s.v.lstride, s.scratch + (int64_t)b * s.sstride, As, Bs, Ri);
 }
 
-// ---------------------------------------------------------------------------
-// k_selinv_scale of selinv.hip for member b
-// ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_batch_selinv_scale(BatchSelinvView s, const UpdTile* __restrict__ tiles, int64_t count,
                                                             const SelinvUnit* __restrict__ units) {
-  __shared__ double Ys[BI_T][BI_T + 1];
-  __shared__ double Ms[BI_T][BI_T + 1];   // inv(L_JJ), then the tile's rows of L_RJ
+  __shared__ double Ys[SI_T][SI_T + 1];
+  __shared__ double Ms[SI_T][SI_T + 1];
   int b;
   int64_t wi;
   bsi_split(s.v, count, b, wi);
   if (s.v.flag[b] != INT_MAX) return;
-  const double* __restrict__ L = s.v.L + (int64_t)b * s.v.lstride;
-  const double* __restrict__ dinv = s.v.dinv + (int64_t)b * s.v.dstride;
-  double* __restrict__ Z = s.Z + (int64_t)b * s.v.lstride;
-  double* __restrict__ scratch = s.scratch + (int64_t)b * s.sstride;
   const UpdTile t = tiles[wi];
-  const SelinvUnit u = units[t.unit];
-  const int tid = threadIdx.x, j = tid & 63, i0w = tid >> 6;
-  const int nR = u.nR, pn = u.pn;
-  const int i0 = t.ti * BI_T;
-  const int nr = min(BI_T, nR - i0);
-  for (int q = 0; q < 16; ++q) {
-    const int i = i0w + 4 * q;
-    double y = 0.0, d = 0.0;
-    if (j < pn) {
-      if (i < nr)
-        for (int sl = 0; sl < u.nsplit; ++sl) y += scratch[u.y_off + ((int64_t)sl * nR + i0 + i) * pn + j];
-      if (i < pn && j <= i) d = dinv[u.dinv_off + (int64_t)i * u.dinv_ld + j];
-    }
-    Ys[i][j] = y;
-    Ms[i][j] = d;
-  }
-  __syncthreads();
-  double z[16];
-  for (int q = 0; q < 16; ++q) {
-    const int i = i0w + 4 * q;
-    double sum = 0.0;
-    for (int c = j; c < pn; ++c) sum += Ys[i][c] * Ms[c][j];
-    z[q] = -sum;
-  }
-  __syncthreads();
-  double* Zrj = Z + u.off + (int64_t)(u.c0 + pn + i0) * u.ld + u.c0;
-  const double* Lrj = L + u.off + (int64_t)(u.c0 + pn + i0) * u.ld + u.c0;
-  for (int q = 0; q < 16; ++q) {
-    const int i = i0w + 4 * q;
-    const bool in = i < nr && j < pn;
-    if (in) Zrj[(int64_t)i * u.ld + j] = z[q];
-    Ys[i][j] = in ? z[q] : 0.0;
-    Ms[i][j] = in ? Lrj[(int64_t)i * u.ld + j] : 0.0;
-  }
-  __syncthreads();
-  double* P = scratch + u.p_off + (int64_t)t.ti * pn * pn;
-  for (int q = 0; q < 16; ++q) {
-    const int a = i0w + 4 * q;
-    if (a >= pn || j >= pn) continue;
-    double sum = 0.0;
-    for (int i = 0; i < nr; ++i) sum += Ms[i][a] * Ys[i][j];
-    P[a * pn + j] = sum;
-  }
+  si_scale_body(t, units[t.unit], s.v.L + (int64_t)b * s.v.lstride, s.v.dinv + (int64_t)b * s.v.dstride,
+                s.Z + (int64_t)b * s.v.lstride, s.scratch + (int64_t)b * s.sstride, Ys, Ms);
 }
 
-// ---------------------------------------------------------------------------
-// k_selinv_diag of selinv.hip for member b
-// ---------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_batch_selinv_diag(BatchSelinvView s, const SelinvUnit* __restrict__ units, int64_t count) {
-  __shared__ double Ds[BI_T][BI_T + 1];
-  __shared__ double Ts[BI_T][BI_T + 1];
+  __shared__ double Ds[SI_T][SI_T + 1];
+  __shared__ double Ts[SI_T][SI_T + 1];
   int b;
   int64_t wi;
   bsi_split(s.v, count, b, wi);
   if (s.v.flag[b] != INT_MAX) return;
-  const double* __restrict__ dinv = s.v.dinv + (int64_t)b * s.v.dstride;
-  double* __restrict__ Z = s.Z + (int64_t)b * s.v.lstride;
-  const double* __restrict__ scratch = s.scratch + (int64_t)b * s.sstride;
-  const SelinvUnit u = units[wi];
-  const int tid = threadIdx.x, e = tid & 63, a0 = tid >> 6;   // (1024 threads: 16 row groups)
-  const int pn = u.pn;
-  for (int q = 0; q < 4; ++q) {
-    const int a = a0 + 16 * q;
-    double d = 0.0, tt = 0.0;
-    if (a < pn && e < pn) {
-      if (e <= a) d = dinv[u.dinv_off + (int64_t)a * u.dinv_ld + e];
-      tt = d;
-      const double* p = scratch + u.p_off + (int64_t)a * pn + e;
-#pragma unroll 8
-      for (int ti = 0; ti < u.ntile; ++ti) tt -= p[(int64_t)ti * pn * pn];
-    }
-    Ds[a][e] = d;
-    Ts[a][e] = tt;
-  }
-  __syncthreads();
-  double* Zjj = Z + u.off + (int64_t)u.c0 * u.ld + u.c0;
-  for (int q = 0; q < 4; ++q) {
-    const int a = a0 + 16 * q;
-    if (a >= pn || e > a) continue;
-    double sum = 0.0;
-    for (int c = a; c < pn; ++c) sum += Ds[c][a] * Ts[c][e];
-    Zjj[(int64_t)a * u.ld + e] = sum;
-  }
+  si_diag_body(units[wi], s.v.dinv + (int64_t)b * s.v.dstride, s.Z + (int64_t)b * s.v.lstride,
+               s.scratch + (int64_t)b * s.sstride, Ds, Ts);
 }
 
 // ---------------------------------------------------------------------------
@@ -308,9 +110,9 @@ __device__ __forceinline__ void bsi_mm(const double (*A)[BI_LD], const double (*
 __global__ __launch_bounds__(256) void k_batch_selinv_fused(BatchSelinvView s, const SelinvUnit* __restrict__ units, int64_t count,
                                                             const SelinvRow* __restrict__ rows,
                                                             const int* __restrict__ relpos) {
-  __shared__ double Ab[BI_T][BI_LD];
-  __shared__ double Bb[BI_T][BI_LD];
-  __shared__ SelinvRow Ri[BI_T];
+  __shared__ double Ab[SI_T][BI_LD];
+  __shared__ double Bb[SI_T][BI_LD];
+  __shared__ SelinvRow Ri[SI_T];
   int b;
   int64_t wi;
   bsi_split(s.v, count, b, wi);
@@ -333,27 +135,9 @@ __global__ __launch_bounds__(256) void k_batch_selinv_fused(BatchSelinvView s, c
   }
   d4 acc[4];
   if (nR > 0) {   // (the same for every thread of the workgroup)
-    const SelinvRow* nrows = rows + u.row_off + u.rbase;
-    if (tid < nR) Ri[tid] = nrows[tid];
-    __syncthreads();
-    const double* Lrj = L + u.off + (int64_t)(u.c0 + pn) * u.ld + u.c0;
     double lreg[16];
-    // 1: Z_RR, its lower half through the descriptor of the column's row (the K row fastest across the
-    // threads: coalesced), mirrored into the upper half; L_RJ
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int i = ti0 + 4 * q, k = tj;
-      double v = 0.0;
-      if (i < nR && k <= i) {
-        const SelinvRow d = Ri[k];
-        const int64_t qpos = d.map < 0 ? (int64_t)(u.rbase + i) : (int64_t)relpos[(int64_t)d.map + i - k];
-        v = Z[d.cbase + qpos * d.ld];
-      }
-      if (k <= i || i >= nR || k >= nR) Ab[i][k] = v;
-      if (k < i && i < nR) Ab[k][i] = v;
-      lreg[q] = (i < nR && tj < pn) ? Lrj[(int64_t)i * u.ld + tj] : 0.0;
-      Bb[i][tj] = lreg[q];
-    }
+    // 1: Z_RR (symmetric) and L_RJ
+    si_small_gather_body<false, BI_LD, BI_LD>(u, rows, relpos, L, Z, Ab, Bb, Ri, lreg);
     __syncthreads();
     bsi_mm<false>(Ab, Bb, nR, ncb, wv, g, col, acc);
     __syncthreads();

@@ -2298,6 +2298,24 @@ int Engine::reserve_batch_inverse(int nbatch) {
   return rc;
 }
 
+template <class Fused, class One>
+int Engine::walk_batch_steps(bool fused, Fused&& fused_step, One&& one_launch) {
+  const SelinvProgram& P = bt_.siprog;
+  int nl = 0;
+  for (size_t i = 0; i < P.launches.size();) {
+    size_t j = i;
+    while (P.launches[j].kind != SI_DIAG) ++j;     // (every step ends with its DIAG launch)
+    const bool whole = fused && bt_.si_fusable[j];
+    for (size_t k = whole ? j : i; k <= j; ++k) {
+      const int made = whole ? fused_step(P.launches[k]) : one_launch(P.launches[k]);
+      if (made < 0) return -1;
+      nl += made;
+    }
+    i = j + 1;
+  }
+  return nl;
+}
+
 int Engine::selected_inverse_batch() {
   feature_err_.clear();
   if (status_) return status_;
@@ -2309,26 +2327,13 @@ int Engine::selected_inverse_batch() {
   if ((rc = reserve_batch_inverse(bt_.nbatch))) return rc;
   bt_.z_valid = false;
   const BatchSelinvView s = batch_selinv_view();
-  const SelinvProgram& P = bt_.siprog;
-  const bool fused = batch_selinv_fused();
-  bool fits = true;
-  int nl = 0;
-  auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
-  for (size_t i = 0; i < P.launches.size() && fits;) {
-    size_t j = i;
-    while (P.launches[j].kind != SI_DIAG) ++j;     // (every step ends with its DIAG launch)
-    const SelinvLaunch& d = P.launches[j];
-    if (fused && bt_.si_fusable[j]) {
-      count(launch_batch_selinv_fused(stream_, s, bt_.siunits + d.first, d.count, bt_.sirows, bt_.sirelpos));
-    } else {
-      for (size_t k = i; k <= j && fits; ++k)
-        count(launch_batch_selinv(stream_, s, P.launches[k], bt_.siunits, bt_.sitiles, bt_.sirows, bt_.sirelpos));
-    }
-    i = j + 1;
-  }
+  const int nl = walk_batch_steps(
+      batch_selinv_fused(),
+      [&](const SelinvLaunch& d) { return launch_batch_selinv_fused(stream_, s, bt_.siunits + d.first, d.count, bt_.sirows, bt_.sirelpos); },
+      [&](const SelinvLaunch& l) { return launch_batch_selinv(stream_, s, l, bt_.siunits, bt_.sitiles, bt_.sirows, bt_.sirelpos); });
   HIPCHK(hipGetLastError(), "batch selinv launch");
   if ((rc = sync_stream(stream_, "batch selinv sync"))) return rc;
-  if (!fits) {
+  if (nl < 0) {
     feature_err_ = "batched selected inversion: a launch of the program has more work items for ONE member than a grid holds";
     return -99;
   }
@@ -2553,25 +2558,15 @@ int Engine::fadj_sweep_batch(double* gval, int64_t ldout, bool dev) {
     return rc;
   bt_.g_state = FADJ_UNSEEDED;   // (a sweep that fails half way leaves nothing to read)
   const BatchSelinvView s = batch_adjoint_view();
-  const SelinvProgram& P = bt_.siprog;
-  const bool fused = batch_fadj_fused();
-  bool fits = true;
-  int nl = 0;
-  auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
-  for (size_t i = 0; i < P.launches.size() && fits;) {
-    size_t j = i;
-    while (P.launches[j].kind != SI_DIAG) ++j;     // (every step ends with its DIAG launch)
-    const SelinvLaunch& d = P.launches[j];
-    if (fused && bt_.si_fusable[j]) {
-      count(launch_batch_fadj_fused(stream_, s, bt_.siunits + d.first, d.count, bt_.sirows, bt_.sirelpos));
-    } else {
-      for (size_t k = i; k <= j && fits; ++k)
-        count(launch_batch_fadj(stream_, s, P.launches[k], bt_.siunits, bt_.sitiles, bt_.sirows, bt_.sirelpos));
-    }
-    i = j + 1;
+  int nl = walk_batch_steps(
+      batch_fadj_fused(),
+      [&](const SelinvLaunch& d) { return launch_batch_fadj_fused(stream_, s, bt_.siunits + d.first, d.count, bt_.sirows, bt_.sirelpos); },
+      [&](const SelinvLaunch& l) { return launch_batch_fadj(stream_, s, l, bt_.siunits, bt_.sitiles, bt_.sirows, bt_.sirelpos); });
+  if (nl >= 0 && nnz > 0) {
+    const int k = launch_batch_selinv_pattern(stream_, s, d_map_dst_, d_map_src_, nmap_, dev ? gval : bt_.stage, dev ? ldout : nnz);
+    nl = k < 0 ? -1 : nl + k;
   }
-  if (fits && nnz > 0)
-    count(launch_batch_selinv_pattern(stream_, s, d_map_dst_, d_map_src_, nmap_, dev ? gval : bt_.stage, dev ? ldout : nnz));
+  const bool fits = nl >= 0;
   HIPCHK(hipGetLastError(), "batch factor adjoint launch");
   if (fits && !dev && nnz > 0 &&
       (rc = copy_vectors(false, bt_.stage, gval, ldout, bt_.nbatch, "batch factor adjoint D2H", nnz)))

@@ -866,6 +866,10 @@ class Engine {
   BatchView batch_view() const;
   int prepare_batch_selinv();
   int reserve_batch_inverse(int nbatch);
+  // The steps [SYMM] [SCALE] DIAG of bt_.siprog in order: fused_step(DIAG launch of the step) where fused and the
+  // step is fusable, else one_launch(launch) for each of its launches; both return launches made, or -1.  Returns
+  // the sum, or -1 when a grid overflowed (the walk ends there).
+  template <class Fused, class One> int walk_batch_steps(bool fused, Fused&& fused_step, One&& one_launch);
   BatchSelinvView batch_selinv_view() const;
   int reserve_batch_arenas(double** arena, int* capacity, int nbatch, const char* feature, const char* which,
                            bool* retaken);

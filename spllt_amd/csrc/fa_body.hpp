@@ -8,10 +8,9 @@
 #include <cstdint>
 
 #include "kernels.hpp"
+#include "si_body.hpp"   // d4; the SYMM step of the adjoint is si_symm_body<true>
 
 namespace spx {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int FA_T = kSelinvTile;   // 64
 constexpr int FA_LDA = 66;
