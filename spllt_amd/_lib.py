@@ -229,6 +229,23 @@ _CONSTRAIN = {
     "spllt_hip_constraints_info": (i32, [vp, i64p, dp]),
     "spllt_hip_release_constraints": (i32, [vp]),
 }
+# every symbol declared in include/spllt_hip_constrain_batch.h: hard linear constraints for the members of a batch.  A
+# table of its own for the same reason.
+u32 = C.c_uint32
+_CONSTRAIN_BATCH = {
+    "spllt_hip_set_constraints_batch": (i32, [vp, i32, dp, i64]),
+    "spllt_hip_set_constraints_batch_dev": (i32, [vp, i32, vp, i64]),
+    "spllt_hip_constrain_batch": (i32, [vp, i32, vp, i64, vp, i64, vp, i64]),
+    "spllt_hip_constrain_batch_dev": (i32, [vp, i32, vp, i64, vp, i64, vp, i64]),
+    "spllt_hip_solve_constrained_batch": (i32, [vp, i32, vp, i64, vp, i64, vp, i64]),
+    "spllt_hip_solve_constrained_batch_dev": (i32, [vp, i32, vp, i64, vp, i64, vp, i64]),
+    "spllt_hip_sample_constrained_batch": (i32, [vp, i32, vp, i64, u64, u64, u32, i32, vp, i64, vp]),
+    "spllt_hip_sample_constrained_batch_dev": (i32, [vp, i32, vp, i64, u64, u64, u32, i32, vp, i64, vp]),
+    "spllt_hip_inverse_diag_constrained_batch": (i32, [vp, dp, i64]),
+    "spllt_hip_constraints_batch_info": (i32, [vp, i64p, dp, i64]),
+    "spllt_hip_release_constraints_batch": (i32, [vp]),
+}
+del u32
 del vp, vpp, i32, i64, u64, f64, cstr, long, ip, i64p, dp, fp, longp, ipp, dpp, opt, inf   # (names of the table only)
 IFACE_SYMBOLS = list(_IFACE)
 HIP_SYMBOLS = list(_HIP)
@@ -237,6 +254,7 @@ BATCH_SOLVE_MANY_SYMBOLS = list(_BATCH_SOLVE_MANY)
 BATCH_ADJOINT_SYMBOLS = list(_BATCH_ADJOINT)
 BATCH_REFINE_SYMBOLS = list(_BATCH_REFINE)
 CONSTRAIN_SYMBOLS = list(_CONSTRAIN)
+CONSTRAIN_BATCH_SYMBOLS = list(_CONSTRAIN_BATCH)
 
 _lib = None
 
@@ -251,7 +269,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C spllt_amd/csrc`. spllt_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE, _CONSTRAIN):
+    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE, _CONSTRAIN, _CONSTRAIN_BATCH):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

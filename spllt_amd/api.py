@@ -1317,6 +1317,142 @@ class Factorization:
     def release_inverse_batch(self):
         self._call("spllt_hip_release_inverse_batch", self.fkeep)
 
+    # ---- hard linear constraints for the members of a batch (include/spllt_hip_constrain_batch.h) -----
+    def set_constraints_batch(self, C_rows):
+        """spllt_hip_set_constraints_batch: store the k <= 64 dense rows of ONE C (k x n, or n for one row) for all
+        members of the last batch and build U_b, G_b per member.  They stay with the handle across batches: a later
+        factor_batch is picked up by the next call that needs them.  None or zero rows clear the constraints.
+        Dependent rows in any factorized member raise SplltError with flag -20 (the message names the member and the
+        row) and leave the batch without constraints.  A member that is not positive definite holds none; the
+        others do (self.constrain_batch_status keeps the call's 0 or -20)."""
+        if C_rows is None:
+            self._call("spllt_hip_set_constraints_batch", self.fkeep, 0, None, max(self.n, 1))
+            return self
+        c = np.ascontiguousarray(np.atleast_2d(np.asarray(C_rows, dtype=np.float64)))
+        if c.ndim != 2 or (c.shape[0] and c.shape[1] != self.n):
+            raise ValueError(f"set_constraints_batch: C must be (k, {self.n}), got {c.shape}")
+        rc = self._call("spllt_hip_set_constraints_batch", self.fkeep, c.shape[0], _dp(c) if c.shape[0] else None,
+                        max(self.n, 1), ok=self._BATCH_OK)
+        if rc == -20 and c.shape[0] and self.constraints_batch_info()["k"] == 0:
+            raise SplltError("spllt_hip_set_constraints_batch", rc, self.last_error())
+        self.constrain_batch_status = rc
+        return self
+
+    def set_constraints_batch_dev(self, c_dev_ptr, k, ldc=None):
+        """spllt_hip_set_constraints_batch_dev: row i of C at c[i*ldc .. i*ldc + n) in device memory.  Returns 0 or
+        -20 (see constraints_batch_info()["k"]: 0 after dependent rows)."""
+        return self._call("spllt_hip_set_constraints_batch_dev", self.fkeep, int(k), C.c_void_p(c_dev_ptr),
+                          int(self.n if ldc is None else ldc), ok=self._BATCH_OK)
+
+    def _constrain_batch_call(self, name, X, e, multipliers):
+        where = name[len("spllt_hip_"):]
+        nb = self._batch_count()
+        x = np.array(X, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (2, 3):
+            raise ValueError(f"{where}: the vectors must have shape (B, n) or (B, nvec, n)")
+        if x.shape[-1] != self.n:
+            raise ValueError(f"{where}: the vectors have length {x.shape[-1]}, n = {self.n}")
+        if nb > 0 and x.shape[0] != nb:
+            raise ValueError(f"{where}: vectors for {x.shape[0]} members, the last batch has {nb}")
+        nvec = 1 if x.ndim == 2 else x.shape[1]
+        k = self.constraints_batch_info()["k"]
+        ev, lde = None, 0
+        if e is not None:
+            ev = np.ascontiguousarray(e, dtype=np.float64)
+            if ev.shape not in ((k,), (x.shape[0], nvec, k)):
+                raise ValueError(f"{where}: e must be ({k},) or ({x.shape[0]}, {nvec}, {k}), got {ev.shape}")
+            lde = k if ev.ndim == 3 else 0     # (one column per vector, else one shared column)
+        lam = np.zeros((x.shape[0], nvec, max(k, 1)), dtype=np.float64) if multipliers else None
+        self.constrain_batch_status = self._call(
+            name, self.fkeep, nvec, C.c_void_p(x.ctypes.data), max(self.n, 1),
+            None if ev is None else C.c_void_p(ev.ctypes.data), lde,
+            None if lam is None else C.c_void_p(lam.ctypes.data), max(k, 1), ok=self._BATCH_OK)
+        if not multipliers:
+            return x
+        lam = lam[..., :k]
+        return x, (lam[:, 0] if x.ndim == 2 else lam)
+
+    def constrain_batch(self, X, e=None, multipliers=False):
+        """spllt_hip_constrain_batch on a copy of X ((B, n) or (B, nvec, n), like solve_many_batch): per member
+        x* = x - U_b G_b^-1 (C x - e), so that C x* = e.  e: None (zeros), (k,) shared by every vector of every member,
+        or (B, nvec, k).  multipliers=True also returns lambda = S_b^-1 (C x - e), shape (B, k) or (B, nvec, k).  The
+        vectors of a member that is not positive definite come back unchanged, its multipliers NaN."""
+        return self._constrain_batch_call("spllt_hip_constrain_batch", X, e, multipliers)
+
+    def solve_constrained_batch(self, B, e=None, multipliers=False):
+        """spllt_hip_solve_constrained_batch on a copy of B: constrain_batch(solve_many_batch(B), e) in one call; with
+        multipliers=True (x, lambda) solves A_b x + C^T lambda = b, C x = e for every member."""
+        return self._constrain_batch_call("spllt_hip_solve_constrained_batch", B, e, multipliers)
+
+    def _constrain_batch_targets(self, e, where):
+        if e is None:
+            return None
+        ev = np.ascontiguousarray(e, dtype=np.float64)
+        if ev.shape != (self.constraints_batch_info()["k"],):
+            raise ValueError(f"{where}: e must hold one target per constraint")
+        return ev
+
+    def sample_constrained_batch(self, nsamp, seed=0, mean=None, e=None, first_sample=0, stream0=0, common_noise=False):
+        """spllt_hip_sample_constrained_batch: nsamp draws per member of N(mean_b, A_b^-1) | C x = e as a (B, nsamp, n)
+        array: the samples of sample_batch(kind="precision") with the same arguments, corrected.  e: None or (k,).
+        The samples of a member that is not positive definite are NaN."""
+        if int(nsamp) < 0:
+            raise ValueError("sample_constrained_batch: nsamp < 0")
+        m, ldm = self._batch_mean(mean, "sample_constrained_batch")
+        ev = self._constrain_batch_targets(e, "sample_constrained_batch")
+        x = np.zeros((max(self._batch_count(), 0), int(nsamp), self.n), dtype=np.float64)
+        self.constrain_batch_status = self._call(
+            "spllt_hip_sample_constrained_batch", self.fkeep, int(nsamp), C.c_void_p(x.ctypes.data), max(self.n, 1),
+            int(seed), int(first_sample), int(stream0), 0 if common_noise else 1,
+            None if m is None else C.c_void_p(m.ctypes.data), ldm, None if ev is None else C.c_void_p(ev.ctypes.data),
+            ok=self._BATCH_OK)
+        return x
+
+    def constrain_batch_dev(self, x_dev_ptr, nvec, ldx=None, e_dev_ptr=None, lde=0, lambda_dev_ptr=None, ldl=0,
+                            entry="constrain"):
+        """spllt_hip_constrain_batch_dev / spllt_hip_solve_constrained_batch_dev (entry="solve_constrained") on device
+        vectors, in place: vector q of member b at x[(b*nvec + q)*ldx .. + n), e and lambda alike.  Returns 0 or
+        -20."""
+        return self._call(f"spllt_hip_{entry}_batch_dev", self.fkeep, int(nvec), C.c_void_p(x_dev_ptr),
+                          int(self.n if ldx is None else ldx), None if e_dev_ptr is None else C.c_void_p(e_dev_ptr),
+                          int(lde), None if lambda_dev_ptr is None else C.c_void_p(lambda_dev_ptr), int(ldl),
+                          ok=self._BATCH_OK)
+
+    def sample_constrained_batch_dev(self, x_dev_ptr, nsamp, ldx=None, seed=0, mean_dev_ptr=None, ldmean=0, e_dev_ptr=None,
+                                     first_sample=0, stream0=0, common_noise=False):
+        """spllt_hip_sample_constrained_batch_dev: the constrained samples into device memory (layout of
+        sample_batch_dev).  Returns 0 or -20."""
+        return self._call("spllt_hip_sample_constrained_batch_dev", self.fkeep, int(nsamp), C.c_void_p(x_dev_ptr),
+                          int(max(self.n, 1) if ldx is None else ldx), int(seed), int(first_sample), int(stream0),
+                          0 if common_noise else 1, None if mean_dev_ptr is None else C.c_void_p(mean_dev_ptr),
+                          int(ldmean), None if e_dev_ptr is None else C.c_void_p(e_dev_ptr), ok=self._BATCH_OK)
+
+    def inverse_diag_constrained_batch(self):
+        """Var(x_i | C x = e) = (A_b^-1)_ii - sum_j U_b[i, j]^2 per member, shape (nbatch, n), user order; needs
+        selected_inverse_batch() of the current batch.  NaN rows for members that are not positive definite."""
+        nb = self._batch_count()
+        out = np.zeros((max(nb, 1), max(self.n, 1)), dtype=np.float64)
+        self.constrain_batch_status = self._call("spllt_hip_inverse_diag_constrained_batch", self.fkeep, _dp(out),
+                                                 out.shape[1], ok=self._BATCH_OK)
+        return out[:nb, :self.n]
+
+    def constraints_batch_info(self):
+        """k (0: none set), rebuilds of the U_b, device bytes, kernel launches of the family in the last call, and per
+        member of the last batch log det S_b and the smallest relative pivot of S_b (NaN for a member that is not
+        positive definite, or until the first call after a new batch has rebuilt them; empty without constraints)."""
+        out = np.zeros(4, dtype=np.int64)
+        nb = max(self._batch_count(), 0)
+        stat = np.zeros((max(nb, 1), 2), dtype=np.float64)
+        self._call("spllt_hip_constraints_batch_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)), _dp(stat), 2)
+        have = nb if out[0] > 0 else 0
+        return {"k": int(out[0]), "rebuilds": int(out[1]), "device_bytes": int(out[2]), "launches": int(out[3]),
+                "log_det_s": stat[:have, 0].copy(), "min_relative_pivot": stat[:have, 1].copy()}
+
+    def release_constraints_batch(self):
+        """C, the U_b and the work arrays of the batch's constraints back to the device pool; C is forgotten."""
+        self._call("spllt_hip_release_constraints_batch", self.fkeep)
+        return self
+
     # ---- factor adjoint of the members of a batch (include/spllt_hip_batch_adjoint.h) ----
     def factor_adjoint_seed_batch(self, a, b, alpha=1.0, accumulate=False, a_pivot_order=False, b_pivot_order=False):
         """spllt_hip_factor_adjoint_seed_batch on host arrays a, b of shape (B, n), one vector per member, or

@@ -33,6 +33,7 @@
 #include "spllt_hip_batch_solve_many.h"
 #include "spllt_hip_batch_refine.h"
 #include "spllt_hip_constrain.h"
+#include "spllt_hip_constrain_batch.h"
 #include "symbolic.hpp"
 
 using namespace spx;
@@ -1398,6 +1399,123 @@ int spllt_hip_solve_refined_batch_info(void* fkeep, int64_t out[4]) {
   return 0;
 }
 
+// ---- hard linear constraints for the members of a batch (spllt_hip_constrain_batch.h) ---------------
+// the argument rungs of set_constraints_impl, then the handle rungs of solve_many_batch_impl
+static int set_constraints_batch_impl(const char* what, void* fkeep, int k, const double* c, int64_t ldc, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = nullptr;
+  if (k != 0 && !c) bad = "the array of constraint rows is null";
+  else if (k < 0) bad = "k < 0";
+  else if (k > 64) bad = "k > 64";
+  else if (k > 0 && ldc < f->S->n) bad = "ldc < n";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  const int rc = f->eng->set_constraints_batch(k, c, ldc, dev);
+  // (-20 with the constraints still held: a member is not positive definite; without: a dependent row, the engine's
+  // message names it)
+  if (rc == SPLLT_ERROR_NOT_POSDEF && f->eng->constraints_batch_k() > 0)
+    return batch_mult_leave(f, what, rc, "the members that are not positive definite hold no constraints, the others do");
+  return leave(f, rc);
+}
+
+int spllt_hip_set_constraints_batch(void* fkeep, int k, const double* c_host, int64_t ldc) {
+  return set_constraints_batch_impl("spllt_hip_set_constraints_batch", fkeep, k, c_host, ldc, false);
+}
+
+int spllt_hip_set_constraints_batch_dev(void* fkeep, int k, const double* c_dev, int64_t ldc) {
+  return set_constraints_batch_impl("spllt_hip_set_constraints_batch_dev", fkeep, k, c_dev, ldc, true);
+}
+
+static const char* const kNoBatchConstraints = "no constraints are set on this batch (spllt_hip_set_constraints_batch)";
+
+// the rungs of constrain_impl for the arguments, of solve_many_batch_impl / sample_batch_impl for the handle
+static int constrain_batch_impl(const char* what, int op, void* fkeep, int nvec, double* x, int64_t ldx, const double* e,
+                                int64_t lde, double* lambda, int64_t ldl, bool dev, uint64_t seed, uint64_t first,
+                                uint32_t stream0, int stream_step, const double* mean, int64_t ldmean) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = vectors_bad(f, nvec, x, ldx, 0);
+  const int k = f->eng ? f->eng->constraints_batch_k() : 0;   // (0: refused below, once the ladder is through)
+  if (!bad && k > 0 && e && lde != 0 && lde < k) bad = "lde is neither 0 nor >= k";
+  if (!bad && k > 0 && lambda && ldl < k) bad = "ldl < k";
+  if (!bad && (stream_step < 0 || stream_step > 1)) bad = "stream_step is not 0 (common noise) or 1 (a stream per member)";
+  if (!bad && mean && ldmean != 0 && ldmean < f->S->n) bad = "ldmean is neither 0 (one mean for all members) nor >= n";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (nvec == 0) return 0;
+  if (f->eng->constraints_batch_k() <= 0) return fail(f, what, kNoBatchConstraints);
+  f->eng->set_batch_blocked_solve(f->batch_blocked);
+  const int rc = f->eng->constrain_batch(op, nvec, x, ldx, e, e ? lde : 0, lambda, ldl, dev, seed, first, stream0, stream_step,
+                                         mean, ldmean);
+  // (-20 with the constraints gone: the rebuild for a later batch met a dependent row, the engine's message names it)
+  if (rc == SPLLT_ERROR_NOT_POSDEF && f->eng->constraints_batch_k() <= 0) return leave(f, rc);
+  return batch_mult_leave(f, what, rc,
+                          op == Engine::CN_SAMPLE ? "the samples of the members that are not positive definite are NaN"
+                                                  : "the vectors of the members that are not positive definite were left "
+                                                    "unchanged");
+}
+
+int spllt_hip_constrain_batch(void* fkeep, int nvec, double* x_host, int64_t ldx, const double* e_host, int64_t lde,
+                              double* lambda_host, int64_t ldl) {
+  return constrain_batch_impl("spllt_hip_constrain_batch", Engine::CN_CORRECT, fkeep, nvec, x_host, ldx, e_host, lde,
+                              lambda_host, ldl, false, 0, 0, 0, 1, nullptr, 0);
+}
+
+int spllt_hip_constrain_batch_dev(void* fkeep, int nvec, double* x_dev, int64_t ldx, const double* e_dev, int64_t lde,
+                                  double* lambda_dev, int64_t ldl) {
+  return constrain_batch_impl("spllt_hip_constrain_batch_dev", Engine::CN_CORRECT, fkeep, nvec, x_dev, ldx, e_dev, lde,
+                              lambda_dev, ldl, true, 0, 0, 0, 1, nullptr, 0);
+}
+
+int spllt_hip_solve_constrained_batch(void* fkeep, int nrhs, double* x_host, int64_t ldx, const double* e_host, int64_t lde,
+                                      double* lambda_host, int64_t ldl) {
+  return constrain_batch_impl("spllt_hip_solve_constrained_batch", Engine::CN_SOLVE, fkeep, nrhs, x_host, ldx, e_host, lde,
+                              lambda_host, ldl, false, 0, 0, 0, 1, nullptr, 0);
+}
+
+int spllt_hip_solve_constrained_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, const double* e_dev,
+                                          int64_t lde, double* lambda_dev, int64_t ldl) {
+  return constrain_batch_impl("spllt_hip_solve_constrained_batch_dev", Engine::CN_SOLVE, fkeep, nrhs, x_dev, ldx, e_dev, lde,
+                              lambda_dev, ldl, true, 0, 0, 0, 1, nullptr, 0);
+}
+
+int spllt_hip_sample_constrained_batch(void* fkeep, int nsamp, double* x_host, int64_t ldx, uint64_t seed,
+                                       uint64_t first_sample, uint32_t stream0, int stream_step, const double* mean_host,
+                                       int64_t ldmean, const double* e_host) {
+  return constrain_batch_impl("spllt_hip_sample_constrained_batch", Engine::CN_SAMPLE, fkeep, nsamp, x_host, ldx, e_host, 0,
+                              nullptr, 0, false, seed, first_sample, stream0, stream_step, mean_host, ldmean);
+}
+
+int spllt_hip_sample_constrained_batch_dev(void* fkeep, int nsamp, double* x_dev, int64_t ldx, uint64_t seed,
+                                           uint64_t first_sample, uint32_t stream0, int stream_step, const double* mean_dev,
+                                           int64_t ldmean, const double* e_dev) {
+  return constrain_batch_impl("spllt_hip_sample_constrained_batch_dev", Engine::CN_SAMPLE, fkeep, nsamp, x_dev, ldx, e_dev,
+                              0, nullptr, 0, true, seed, first_sample, stream0, stream_step, mean_dev, ldmean);
+}
+
+// the rungs of spllt_hip_inverse_diag_batch, then "no constraints"
+int spllt_hip_inverse_diag_constrained_batch(void* fkeep, double* out, int64_t ldout) {
+  const char* what = "spllt_hip_inverse_diag_constrained_batch";
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  const char* bad = !out ? "the output array is null" : ldout < f->S->n ? "ldout < n" : nullptr;
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH | BATCH_INVERSE)) return rc;
+  if (f->eng->constraints_batch_k() <= 0) return fail(f, what, kNoBatchConstraints);
+  const int rc = f->eng->inverse_diag_constrained_batch(out, ldout);
+  if (rc == SPLLT_ERROR_NOT_POSDEF && f->eng->constraints_batch_k() <= 0) return leave(f, rc);
+  return batch_mult_leave(f, what, rc, "the rows of the members that are not positive definite are NaN");
+}
+
+int spllt_hip_constraints_batch_info(void* fkeep, int64_t out[4], double* stat, int64_t ldstat) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out || (stat && ldstat < 2)) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  if (!f->eng || f->dead) return 0;
+  if (stat)
+    for (int b = 0; b < f->eng->batch_count(); ++b) stat[(int64_t)b * ldstat] = stat[(int64_t)b * ldstat + 1] = 0.0;
+  f->eng->constraints_batch_info(out, stat, ldstat);
+  return 0;
+}
+
 // ---- low-rank update / downdate of the factor ------------------------------------------------------
 int64_t spllt_hip_updown_plan(void* fkeep, int k, const int* wptr, const int* wrow, int32_t* bcols, int64_t capacity) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
@@ -1869,6 +1987,7 @@ int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::releas
 int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_solve_many_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_many_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_refine_batch(void* fkeep) { return release(fkeep, &Engine::release_refine_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_constraints_batch(void* fkeep) { return release(fkeep, &Engine::release_constraints_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse_batch(void* fkeep) { return release(fkeep, &Engine::release_inverse_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_adjoint_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_adjoint_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse(void* fkeep) { return release(fkeep, &Engine::release_inverse, WAIT_IGNORE | LENIENT); }

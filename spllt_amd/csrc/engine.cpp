@@ -2063,6 +2063,7 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   bt_.nbatch = 0;                    // (no batch until this one is finished)
   bt_.z_valid = false;               // (the members' inverses belong to the factors this call replaces)
   bt_.g_state = FADJ_UNSEEDED;       // (... and so do their adjoints)
+  ++bt_.generation;                 // (... and what the constraints of the batch built from them)
   bt_.hflag.clear();
   const double* vd = val;
   int64_t ld = ldval;
@@ -2186,12 +2187,13 @@ int Engine::release_batch() {
   bt_.g_state = FADJ_UNSEEDED;
   bt_.fa_launches = 0;
   // (the batch's own storage, and what its features say of theirs)
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brf_held()) { bt_.nbatch = 0; return 0; }
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brf_held() && !bcn_.C) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
   drop_solve_many_batch();    // (... and that of the blocked solve)
   drop_refine_batch();        // (... and those of the refined solves)
+  drop_constraints_batch();   // (... and the constraints of the batch, C included)
   give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, bt_.Y, bt_.stage, bt_.Z, bt_.G, bt_.siscratch);
   bt_.sc_users = Shared{};
   bt_.z_capacity = bt_.g_capacity = bt_.sc_capacity = 0;

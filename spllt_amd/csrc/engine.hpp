@@ -298,6 +298,27 @@ class Engine {
   // smallest pivot_j / S_jj
   void constraints_info(int64_t out[4], double stat[2]) const;
   int release_constraints();
+  // ---- the same for the members of the LAST batch (constrain_batch.hip; include/spllt_hip_constrain_batch.h has the
+  // mathematics, the layout of e and lambda and the storage formula).  ONE C for all members; U_b, G_b and the scalars
+  // belong to the batch generation they were built for (bt_.generation, bumped by every factor_batch): every call
+  // compares and rebuilds from the stored C first, taking the storage again when the batch has grown.  Independent
+  // of cn_: neither family reads or touches the other's state.  A member that is not positive definite is skipped
+  // by every kernel; the calls return -20 after serving the others.  Dependent rows in ANY factorized member: -20,
+  // feature_error() names the member and the row, nothing of the feature stays allocated.  W_b always by
+  // solve_many_batch; host vectors through the batch's staging buffer.
+  int set_constraints_batch(int k, const double* c, int64_t ldc, bool dev);
+  int constraints_batch_k() const { return bcn_.k; }
+  // op as CnOp: 0 the correction of the nvec vectors per member in x (layout of solve_batch), 1 solve_many_batch job 0
+  // first, 2 the kind-0 samples of sample_batch first (e then k shared targets: lde = 0).  Passes of at most 32
+  // vectors per member (for_each_block), three launches each whatever nbatch.
+  int constrain_batch(int op, int nvec, double* x, int64_t ldx, const double* e, int64_t lde, double* lambda, int64_t ldl,
+                      bool dev, uint64_t seed = 0, uint64_t first = 0, uint32_t stream0 = 0, int stream_step = 1,
+                      const double* mean = nullptr, int64_t ldmean = 0);
+  int inverse_diag_constrained_batch(double* out, int64_t ldout);   // host, out[b * ldout + i]; needs batch_inverse_valid()
+  // out: k, rebuilds, device bytes held, kernel launches of this family in the last call; stat (may be null): log det
+  // S_b and the smallest relative pivot of member b at stat + b * ldstat, NaN for a failed member or a stale build
+  void constraints_batch_info(int64_t out[4], double* stat, int64_t ldstat) const;
+  int release_constraints_batch();
   bool factored() const { return factored_ && !ud_invalid_; }
   // ---- low-rank update / downdate (updown.hip, single GPU): the factor of P (A + sign W W^T) P^T in place of
   // the current one, same layout, the dinv slots of the visited block columns rebuilt -- every solve then works
@@ -761,6 +782,29 @@ class Engine {
   void drop_constraints();
   int build_constraints(int64_t serial);   // U, G and the scalars from C and the current factor
   int cn_pass(double* xd, int64_t ld, int nv, const double* e, int64_t lde, double* lambda, int64_t ldl);   // enqueue only
+  // ... for the members of a batch: C once, everything else per member (taken in one transaction for `capacity`
+  // members)
+  struct BcnState {
+    int k = 0;                     // rows of C held (0: none)
+    int capacity = 0;              // members the storage holds
+    int64_t generation = -1;       // the batch U_b, G_b and the scalars belong to (-1: none)
+    int64_t rebuilds = 0, launches = 0;
+    size_t bytes = 0;
+    double* C = nullptr;           // k x n
+    double* U = nullptr;           // capacity x k x n
+    double* G = nullptr;           // capacity x kCnMaxRows^2, then capacity x kBcnStat scalars
+    double* part = nullptr;        // capacity x cn_nchunks(n) x kCnMaxRows^2
+    double* T = nullptr;           // capacity x kCnPass x kCnMaxRows, then the staged e and lambda (as much each)
+    std::vector<double> stat;      // nbatch x 2 of the last build: log det S_b, min pivot_j / S_jj
+  } bcn_;
+  void drop_constraints_batch();
+  int take_constraints_batch(int k, int members, bool keep_c);   // the storage, all or nothing
+  int build_constraints_batch();           // U_b, G_b and the scalars from C and the current batch
+  int refresh_constraints_batch();         // the build when the batch is newer than the numbers held
+  BcnView bcn_view() const;
+  // one pass of nv <= kCnPass vectors per member (member b's at xd + b * xs): enqueue only; launches made or -1
+  int bcn_pass(double* xd, int64_t xs, int64_t ld, int nv, const double* e, int64_t es, int64_t lde, double* lambda,
+               int64_t ls, int64_t ldl);
   // update / downdate: work array and coefficient scratch (taken on first use, both or neither)
   bool ud_invalid_ = false;
   int64_t ud_info_[4] = {0, 0, 0, 0};
@@ -859,6 +903,7 @@ class Engine {
     int g_capacity = 0;
     int g_state = 0;
     int fa_launches = 0;
+    int64_t generation = 0;          // counts the factor_batch calls that replaced the members' factors
   } bt_;
   int prepare_batch();
   int reserve_batch(int nbatch);

@@ -1879,4 +1879,311 @@ int Engine::inverse_diag_constrained(double* out, int n, int64_t serial) {
   return sync_stream(stream_, "constrained diag sync");
 }
 
+// ---- hard linear constraints C x = e for the members of a batch ---------------------------------------------
+namespace {
+// build_constraints_batch to its callers: a dependent row (reported as -20 once the constraints are dropped), as
+// opposed to the -20 of a member that is not positive definite (the constraints stay)
+constexpr int kErrDependent = -2000;
+}  // namespace
+
+BcnView Engine::bcn_view() const {
+  return BcnView{bt_.flag, bt_.nbatch, S_->n, bcn_.k, bcn_.C, bcn_.U, bcn_.G,
+                 bcn_.G + (size_t)bcn_.capacity * kCnMaxRows * kCnMaxRows, bcn_.part, bcn_.T,
+                 (int64_t)cn_nchunks(S_->n) * kCnMaxRows * kCnMaxRows};
+}
+
+void Engine::drop_constraints_batch() {
+  give_back(bcn_.C, bcn_.U, bcn_.G, bcn_.part, bcn_.T);
+  const int64_t rebuilds = bcn_.rebuilds;
+  bcn_ = BcnState{};
+  bcn_.rebuilds = rebuilds;
+}
+
+int Engine::release_constraints_batch() {
+  int rc;
+  if (!enter_release(bcn_.C != nullptr, "constraints_batch release", &rc)) return rc;
+  drop_constraints_batch();
+  return 0;
+}
+
+void Engine::constraints_batch_info(int64_t out[4], double* stat, int64_t ldstat) const {
+  out[0] = bcn_.k;
+  out[1] = bcn_.rebuilds;
+  out[2] = (int64_t)bcn_.bytes;
+  out[3] = bcn_.launches;
+  if (!stat || bcn_.k <= 0) return;
+  // (numbers of an old batch are never returned: NaN until the first call that rebuilds)
+  const bool current = bcn_.generation == bt_.generation && bcn_.stat.size() == 2 * (size_t)bt_.nbatch;
+  for (int b = 0; b < bt_.nbatch; ++b)
+    for (int i = 0; i < 2; ++i)
+      stat[(int64_t)b * ldstat + i] = current ? bcn_.stat[2 * (size_t)b + i] : std::numeric_limits<double>::quiet_NaN();
+}
+
+// C (kept from the storage held when keep_c), U, G and the scalars, the partials and T for `members` members: one
+// transaction; a failure keeps what was held before
+int Engine::take_constraints_batch(int k, int members, bool keep_c) {
+  const size_t n = (size_t)S_->n, m = (size_t)members;
+  const size_t kn = sizeof(double) * (size_t)k * n;
+  BcnState fresh;
+  {
+    auto t = take();
+    t.block(&fresh.C, kn);
+    t.block(&fresh.U, kn * m);
+    t.block(&fresh.G, sizeof(double) * m * (kCnMaxRows * kCnMaxRows + kBcnStat));
+    t.block(&fresh.part, sizeof(double) * m * (size_t)cn_nchunks(S_->n) * kCnMaxRows * kCnMaxRows);
+    t.block(&fresh.T, sizeof(double) * m * 3 * kCnPass * kCnMaxRows);
+    if (t.ok() && keep_c) {
+      t.check(hipMemcpyAsync(fresh.C, bcn_.C, kn, hipMemcpyDeviceToDevice, stream_));
+      if (t.ok()) t.check(hipStreamSynchronize(stream_));
+    }
+    if (!t.ok()) {
+      feature_err_ = "set_constraints_batch: not enough device memory for C, U and the partial sums of " +
+                     std::to_string(members) + " members (" + std::to_string(t.bytes() >> 20) +
+                     " MiB): " + hipGetErrorString(t.error());
+      return alloc_code(t.error());
+    }
+    t.commit();
+    fresh.bytes = t.bytes();
+  }
+  fresh.rebuilds = bcn_.rebuilds;
+  fresh.launches = bcn_.launches;
+  drop_constraints_batch();
+  bcn_ = fresh;
+  bcn_.k = k;
+  bcn_.capacity = members;
+  return 0;
+}
+
+// U_b, G_b, log det S_b and the smallest relative pivot of every factorized member from the stored C: the copy of C
+// into every member's slot, the blocked batch solve, three launches.  0, -20 with the constraints still held (a
+// member is not positive definite: the others are built), or an error after which the caller drops the constraints.
+int Engine::build_constraints_batch() {
+  const int n = S_->n, k = bcn_.k, nbatch = bt_.nbatch;
+  bcn_.generation = -1;
+  const BcnView v = bcn_view();
+  bool fits = launch_bcn_bcast(stream_, v) >= 0;
+  HIPCHK(hipGetLastError(), "constraints_batch launch");
+  int rc = fits ? solve_many_batch(bcn_.U, true, k, (int64_t)n, 0, false) : 0;
+  if (rc && rc != kErrNotPosDef) return rc;
+  int nl = 0;
+  auto count = [&](int l) { if (l < 0) fits = false; else nl += l; };
+  if (fits) count(launch_bcn_dot(stream_, v, bcn_.U, (int64_t)k * n, (int64_t)n, k, kCnMaxRows, true));
+  if (fits) count(launch_bcn_chol(stream_, v));
+  if (fits) count(launch_bcn_scale(stream_, v));
+  bcn_.launches += nl;
+  HIPCHK(hipGetLastError(), "constraints_batch launch");
+  std::vector<double> stat((size_t)nbatch * kBcnStat, 0.0);
+  HIPCHK(hipMemcpyAsync(stat.data(), v.stat, sizeof(double) * stat.size(), hipMemcpyDeviceToHost, stream_),
+         "constraints_batch D2H");
+  if ((rc = sync_stream(stream_, "constraints_batch sync"))) return rc;
+  if (!fits) {
+    feature_err_ = "set_constraints_batch: the batch has more members than a grid dimension holds";
+    return -99;
+  }
+  // (U_b of a member with a dependent row was scaled by a G_b that is not a factor: the caller drops everything)
+  bcn_.stat.assign(2 * (size_t)nbatch, std::numeric_limits<double>::quiet_NaN());
+  for (int b = 0; b < nbatch; ++b) {
+    if (bt_.hflag[(size_t)b] != INT_MAX) continue;   // (nothing of it was written: the scalars are not read)
+    const double* sb = &stat[(size_t)b * kBcnStat];
+    if (sb[2] != 0.0) {
+      feature_err_ = "set_constraints_batch: member " + std::to_string(b) + ", row " + std::to_string((int)sb[2]) +
+                     " of C depends on the rows before it (its pivot of S_b = C A_b^-1 C^T is <= 2^-26 S_jj or not "
+                     "finite): the batch holds no constraints";
+      return kErrDependent;
+    }
+    bcn_.stat[2 * (size_t)b] = sb[0];
+    bcn_.stat[2 * (size_t)b + 1] = sb[1];
+  }
+  bcn_.generation = bt_.generation;
+  ++bcn_.rebuilds;
+  return batch_failed();
+}
+
+// before a call that needs U_b: the storage for the members of the current batch and their numbers
+int Engine::refresh_constraints_batch() {
+  if (bcn_.generation == bt_.generation && bt_.nbatch <= bcn_.capacity) return 0;
+  int rc = 0;
+  if (bt_.nbatch > bcn_.capacity) rc = take_constraints_batch(bcn_.k, bt_.nbatch, true);
+  if (!rc) rc = build_constraints_batch();
+  if (rc == kErrDependent || (rc && rc != kErrNotPosDef)) {
+    const std::string why = feature_err_;
+    if (!poisoned_) drop_constraints_batch();
+    feature_err_ = why;
+    return rc == kErrDependent ? kErrNotPosDef : rc;
+  }
+  return 0;   // (-20 of a member that is not positive definite: the caller reports it after serving the others)
+}
+
+int Engine::set_constraints_batch(int k, const double* c, int64_t ldc, bool dev) {
+  if (k == 0) return release_constraints_batch();
+  const int n = S_->n, nbatch = bt_.nbatch;
+  int rc;
+  if (!enter(k > 0 && k <= kCnMaxRows && c && ldc >= n && n > 0 && nbatch > 0, false, &rc)) return rc;
+  // (a failure here leaves the batch and every other call usable: the engine's status is not touched)
+  if ((bcn_.k != k || nbatch > bcn_.capacity) && (rc = take_constraints_batch(k, nbatch, false))) {
+    const std::string why = feature_err_;
+    drop_constraints_batch();
+    feature_err_ = why;
+    return rc;
+  }
+  bcn_.launches = 0;
+  const hipError_t e = hipMemcpy2DAsync(bcn_.C, sizeof(double) * (size_t)n, c, sizeof(double) * (size_t)ldc,
+                                        sizeof(double) * (size_t)n, (size_t)k,
+                                        dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_);
+  if (e != hipSuccess) {
+    drop_constraints_batch();
+    return fail(kErrHip, "constraints_batch C copy", e);
+  }
+  rc = build_constraints_batch();
+  if (rc && rc != kErrNotPosDef) {
+    const std::string why = feature_err_;
+    if (!poisoned_) drop_constraints_batch();
+    feature_err_ = why;
+    return rc == kErrDependent ? kErrNotPosDef : rc;
+  }
+  return rc;
+}
+
+int Engine::bcn_pass(double* xd, int64_t xs, int64_t ld, int nv, const double* e, int64_t es, int64_t lde, double* lambda,
+                     int64_t ls, int64_t ldl) {
+  const BcnView v = bcn_view();
+  int nl = 0;
+  for (int l : {launch_bcn_dot(stream_, v, xd, xs, ld, nv, kCnPass, false),
+                launch_bcn_small(stream_, v, nv, e, es, lde, lambda, ls, ldl), launch_bcn_apply(stream_, v, xd, xs, ld, nv)}) {
+    if (l < 0) return -1;
+    nl += l;
+  }
+  return nl;
+}
+
+int Engine::constrain_batch(int op, int nvec, double* x, int64_t ldx, const double* e, int64_t lde, double* lambda,
+                            int64_t ldl, bool dev, uint64_t seed, uint64_t first, uint32_t stream0, int stream_step,
+                            const double* mean, int64_t ldmean) {
+  const int n = S_->n, k = bcn_.k, nbatch = bt_.nbatch;
+  int rc;
+  if (!enter(op >= CN_CORRECT && op <= CN_SAMPLE && nvec >= 0 && x && ldx >= n && k > 0 && nbatch > 0 &&
+                 (lde == 0 || lde >= k) && (!lambda || ldl >= k) && stream_step >= 0 && stream_step <= 1 &&
+                 !(mean && ldmean != 0 && ldmean < n),
+             nvec == 0 || n == 0, &rc))
+    return rc;
+  bcn_.launches = 0;
+  if ((rc = refresh_constraints_batch())) return rc;
+  if (op == CN_SOLVE && (rc = prepare_solve_many_batch())) return rc;
+  const int cap = std::min(nvec, kCnPass);
+  if (!dev && (rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)cap * (size_t)n,
+                                      "the staged vectors")))
+    return rc;
+  // the mean of a host entry point, as sample_batch keeps it
+  const double* dmean = mean;
+  int64_t ldm = ldmean;
+  if (op == CN_SAMPLE && mean && !dev) {
+    const size_t nm = ldmean == 0 ? 1 : (size_t)nbatch;
+    if ((rc = grow_batch_buffer(&d_bmmean_, &bm_mean_elems_, nm * (size_t)n, "the means"))) return rc;
+    if ((rc = copy_vectors_to_device(d_bmmean_, mean, ldmean, (int64_t)nm, "mean H2D"))) return rc;
+    dmean = d_bmmean_;
+    ldm = ldmean == 0 ? 0 : n;
+  }
+  // device vectors: the samples of the whole call first (sample_batch lays member b's at x + b nsamp ldx)
+  if (op == CN_SAMPLE && dev) {
+    rc = sample_batch(x, nvec, ldx, 0, seed, first, stream0, stream_step, dmean, ldm, true);
+    if (rc && rc != kErrNotPosDef) return rc;
+  }
+  double* estage = bcn_.T + (size_t)bcn_.capacity * kCnPass * kCnMaxRows;
+  double* lstage = estage + (size_t)bcn_.capacity * kCnPass * kCnMaxRows;
+  if (e && !dev && lde == 0 && (rc = copy_vectors_to_device(estage, e, (int64_t)k, 1, "constrain_batch e H2D", (int64_t)k)))
+    return rc;
+  bool fits = true;
+  rc = walk_blocks({"constrain_batch", x, dev, nvec, ldx, nbatch, bt_.stage, kCnPass, false, op != CN_SAMPLE},
+                   [&](int done, double* xd, int64_t xs, int64_t ld, int nv, int, bool) -> int {
+                     int r = 0;
+                     if (op == CN_SOLVE) {
+                       // (blocks of the width the workspace of the blocked solve holds)
+                       r = for_each_block(nv, bsm_rb_, [&](int at, int cur, int rb) {
+                         return std::min(enqueue_solve_many_batch_block(xd + (int64_t)at * ld, xs, ld, cur, rb, 0, false), 0);
+                       });
+                       if (r) { fits = false; return -1; }
+                     } else if (op == CN_SAMPLE && !dev) {
+                       r = sample_batch(xd, nv, ld, 0, seed, first + (uint64_t)done, stream0, stream_step, dmean, ldm, true);
+                       if (r && r != kErrNotPosDef) return r;
+                     }
+                     const double* ep = e;
+                     int64_t es = lde == 0 ? 0 : (int64_t)nvec * lde, le = lde;
+                     double* lp = lambda;
+                     int64_t ls = (int64_t)nvec * ldl, ll = ldl;
+                     if (dev) {
+                       if (e) ep = e + (int64_t)done * lde;
+                       if (lambda) lp = lambda + (int64_t)done * ldl;
+                     } else {
+                       if (e && lde != 0) {
+                         for (int b = 0; b < nbatch; ++b)
+                           if ((r = copy_vectors_to_device(estage + (int64_t)b * nv * k, e + ((int64_t)b * nvec + done) * lde, lde,
+                                                           nv, "constrain_batch e H2D", (int64_t)k)))
+                             return r;
+                         es = (int64_t)nv * k;
+                         le = k;
+                       }
+                       if (e) ep = estage;
+                       if (lambda) {
+                         lp = lstage;
+                         ls = (int64_t)nv * k;
+                         ll = k;
+                       }
+                     }
+                     const int nl = bcn_pass(xd, xs, ld, nv, ep, es, le, lp, ls, ll);
+                     if (nl < 0) { fits = false; return -1; }
+                     bcn_.launches += nl;
+                     if (!dev && lambda)
+                       for (int b = 0; b < nbatch; ++b) {
+                         if (bt_.hflag[(size_t)b] != INT_MAX) continue;   // (NaN below: nothing was written for it)
+                         if ((r = copy_vectors(false, lstage + (int64_t)b * nv * k, lambda + ((int64_t)b * nvec + done) * ldl, ldl,
+                                               nv, "constrain_batch lambda D2H", (int64_t)k)))
+                           return r;
+                       }
+                     return 0;
+                   });
+  if (!fits) {
+    feature_err_ = "constrain_batch: a launch has more work items for one member than a grid holds (the vectors are not "
+                   "all served)";
+    return -99;
+  }
+  if (rc) return rc;
+  // a member that is not positive definite: its multipliers are NaN (its vectors stay as they were; its samples are
+  // the NaN of sample_batch)
+  if (lambda) {
+    for (int b = 0; b < nbatch; ++b) {
+      if (bt_.hflag[(size_t)b] == INT_MAX) continue;
+      if (!dev) {
+        for (int q = 0; q < nvec; ++q)
+          std::fill_n(lambda + ((int64_t)b * nvec + q) * ldl, k, std::numeric_limits<double>::quiet_NaN());
+      } else {
+        const std::vector<double> nan((size_t)k * (size_t)nvec, std::numeric_limits<double>::quiet_NaN());
+        HIPCHK(hipMemcpy2D(lambda + (int64_t)b * nvec * ldl, sizeof(double) * (size_t)ldl, nan.data(),
+                           sizeof(double) * (size_t)k, sizeof(double) * (size_t)k, (size_t)nvec, hipMemcpyHostToDevice),
+               "constrain_batch lambda NaN");
+      }
+    }
+  }
+  return batch_failed();
+}
+
+int Engine::inverse_diag_constrained_batch(double* out, int64_t ldout) {
+  const int n = S_->n, nbatch = bt_.nbatch;
+  int rc;
+  if (!enter(bt_.z_valid && out && ldout >= n && nbatch > 0 && bcn_.k > 0, n == 0, &rc)) return rc;
+  bcn_.launches = 0;
+  if ((rc = refresh_constraints_batch())) return rc;
+  if ((rc = grow_batch_buffer(&bt_.stage, &bt_.stage_elems, (size_t)nbatch * (size_t)n, "the gathered diagonals"))) return rc;
+  // (the gather leaves NaN in the row of a member that is not positive definite; the kernel below skips that row)
+  if (launch_batch_selinv_diag_gather(stream_, batch_selinv_view(), bt_.diag, d_order_, n, bt_.stage, n) < 0 ||
+      launch_bcn_var(stream_, bcn_view(), bt_.stage, (int64_t)n, bt_.stage) < 0) {
+    feature_err_ = "constrained batch diagonal: one member's entries are more work items than a grid holds";
+    return -99;
+  }
+  ++bcn_.launches;
+  HIPCHK(hipGetLastError(), "constrained batch diag launch");
+  if ((rc = copy_vectors(false, bt_.stage, out, ldout, nbatch, "constrained batch diag D2H"))) return rc;
+  if ((rc = sync_stream(stream_, "constrained batch diag sync"))) return rc;
+  return batch_failed();
+}
+
 }  // namespace spx

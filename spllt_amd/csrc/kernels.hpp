@@ -361,5 +361,33 @@ void launch_cn_apply(hipStream_t st, double* X, int64_t ldx, int nv, int n, cons
                      const double* T);
 // out[i] = zdiag[i] - sum_j U[j * ldu + i]^2, j ascending (out may be zdiag)
 void launch_cn_var(hipStream_t st, const double* zdiag, const double* U, int64_t ldu, int n, int k, double* out);
+// ---- the same for the members of a batch (constrain_batch.hip): the bodies of the kernels above (cn_body.hpp) on the
+// arrays of member b, the member from the last grid dimension; a member whose flag is not INT_MAX is neither read nor
+// written.  C is shared; everything else has a fixed stride per member.  Every launcher returns the launches made (0:
+// nothing to do) or -1 when the members do not fit a grid dimension (nothing launched).
+constexpr int kBcnStat = 4;   // doubles of scalars per member: log det S_b, min pivot_j / S_jj, the failed row, unused
+struct BcnView {
+  const int* flag;   // the batch's flags
+  int nbatch, n, k;
+  const double* C;   // k x n, row i at C + i * n
+  double* U;         // member b at U + b * k * n, column j of U_b at + j * n
+  double* G;         // member b at G + b * kCnMaxRows^2
+  double* stat;      // member b at stat + b * kBcnStat
+  double* part;      // member b at part + b * pstride, laid out as the single handle's
+  double* T;         // member b at T + b * kCnPass * kCnMaxRows
+  int64_t pstride;   // cn_nchunks(n) * kCnMaxRows^2
+};
+int launch_bcn_bcast(hipStream_t st, const BcnView& v);   // U_b = C (that is W_b = C^T before the solve) for every member
+// member b's vectors at X + b * xstride, vector q at + q * ldx
+int launch_bcn_dot(hipStream_t st, const BcnView& v, const double* X, int64_t xstride, int64_t ldx, int nv, int ldp,
+                   bool lower);
+int launch_bcn_chol(hipStream_t st, const BcnView& v);
+int launch_bcn_scale(hipStream_t st, const BcnView& v);
+// e: null, or member b's at e + b * estride, vector q's at + q * lde (lde = 0: one column); lambda alike, or null
+int launch_bcn_small(hipStream_t st, const BcnView& v, int nv, const double* e, int64_t estride, int64_t lde,
+                     double* lambda, int64_t lstride, int64_t ldl);
+int launch_bcn_apply(hipStream_t st, const BcnView& v, double* X, int64_t xstride, int64_t ldx, int nv);
+// member b's row at zdiag + b * ld and out + b * ld (out may be zdiag)
+int launch_bcn_var(hipStream_t st, const BcnView& v, const double* zdiag, int64_t ld, double* out);
 
 }  // namespace spx

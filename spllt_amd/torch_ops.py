@@ -68,6 +68,7 @@ class SparseCholesky:
         self._stream = None
         self._weight = None           # 2 - delta_ij per entry of val
         self._C = None                # set_constraints: (the rows, whether the handle has them)
+        self._C_on_batch = False      # ... and whether the handle's batch has them
         self.invalidate()
 
     # ---- checks: before any library call ----------------------------------------------------------
@@ -263,16 +264,19 @@ class SparseCholesky:
             return self._outer(ut, vt, float(alpha))
 
     def set_constraints(self, C):
-        """Hard linear constraints C x = e for ``solve_constrained`` and ``sample(..., constrained=True)``.  C: a
+        """Hard linear constraints C x = e for ``solve_constrained`` and ``sample(..., constrained=True)``, and for
+        their batch forms ``solve_constrained_batch`` and ``sample_batch(..., constrained=True)``.  C: a
         float64 device tensor (k, n), k <= 64, or None to clear them.  The rows are copied to the handle with the
         next constrained operation (which has the factor they need); a later factorization is picked up by the
         library.  WITHOUT GRADIENTS: nothing that passes through the constraints carries a gradient, neither to
         val, nor to C, nor to B, mean or e."""
+        self._C_on_batch = False
         if C is None:
             self._C = None
             if self.device is not None:
                 with torch.cuda.device(self.device):
                     self.f.release_constraints()
+                    self.f.release_constraints_batch()
             return self
         self._tensor(C, "C", (None, self.n))
         if not 1 <= C.shape[0] <= 64:
@@ -295,6 +299,43 @@ class SparseCholesky:
                     self.f.set_reproducible_solve(before)
             self._C = (rows, True)
         return rows.shape[0]
+
+    def _ensure_constraints_batch(self):
+        """the stored rows on the handle's batch (the current batch is on the device); returns k"""
+        if self._C is None:
+            raise RuntimeError("SparseCholesky: no constraints (call set_constraints first)")
+        rows = self._C[0]
+        if not self._C_on_batch:
+            self._sync()
+            with torch.cuda.device(self.device):
+                if self.f.set_constraints_batch_dev(rows.data_ptr(), rows.shape[0], ldc=self.n) < 0:
+                    raise SplltError("spllt_hip_set_constraints_batch_dev", _NOT_POSDEF, self.f.last_error())
+            self._C_on_batch = True
+        return rows.shape[0]
+
+    def solve_constrained_batch(self, vals, B, e=None):
+        """x*_b = argmin 1/2 x^T A(vals[b]) x - B[b]^T x subject to C x = e, for every column of B[b] and every member
+        in the same launches: the blocked batch solve, then the correction, in one library call.  vals: (nbatch,
+        nnz), B: (nbatch, n, nrhs); e: None (zeros) or (k,).  Returns (x*, lambda) of shapes (nbatch, n, nrhs) and
+        (nbatch, k, nrhs).  WITHOUT GRADIENTS (see set_constraints)."""
+        if self.reproducible:
+            raise NotImplementedError("solve_constrained_batch: the batch has no deterministic form (reproducible=True)")
+        self._values(vals, "vals", (None, self.nnz))
+        self._tensor(B, "B", (vals.shape[0], self.n, None), vals.device)
+        self._enter(vals)
+        with torch.no_grad():
+            self._ensure_batch(vals)
+            k = self._ensure_constraints_batch()
+            if e is not None:
+                e = self._tensor(e, "e", (k,)).contiguous()
+            work = B.detach().transpose(1, 2).contiguous().clone()
+            lam = torch.empty((work.shape[0], work.shape[1], k), dtype=torch.float64, device=self.device)
+            self._sync()
+            with torch.cuda.device(self.device):
+                self.f.constrain_batch_dev(work.data_ptr(), work.shape[1], ldx=self.n,
+                                           e_dev_ptr=None if e is None else e.data_ptr(), lde=0,
+                                           lambda_dev_ptr=lam.data_ptr(), ldl=k, entry="solve_constrained")
+        return work.transpose(1, 2), lam.transpose(1, 2)
 
     def solve_constrained(self, val, B, e=None):
         """x* = argmin 1/2 x^T A(val) x - B^T x subject to C x = e, for every column of B: the blocked solve, then
@@ -365,16 +406,23 @@ class SparseCholesky:
         x = work.t()
         return x if mean is None else x + mean[:, None]
 
-    def sample_batch(self, vals, nsamp, seed=0, kind="precision", mean=None, common_noise=False):
+    def sample_batch(self, vals, nsamp, seed=0, kind="precision", mean=None, common_noise=False, constrained=False,
+                     e=None):
         """nsamp draws per member of N(mean_b, A(vals[b])^-1) (kind "precision") or N(mean_b, A(vals[b]))
         ("covariance") from the cached factors of the batch (those of solve_batch / logdet_batch): a float64 device
         tensor (nbatch, n, nsamp).  vals: (nbatch, nnz); mean: (n,) for all members or (nbatch, n).  Member b draws
         from a noise stream of its own, common_noise=True gives every member the same noise (Factorization.sample_batch).
         The result carries NO gradient, neither to vals nor to mean, like the draws of ``sample`` with respect to val:
         it is computed under no_grad, mean added on the device (``rsample_batch`` draws the same bits with the
-        pathwise gradient).  reproducible=True raises NotImplementedError, like the other batch operations."""
+        pathwise gradient).  reproducible=True raises NotImplementedError, like the other batch operations.
+        constrained=True (kind "precision" only): draws of N(mean_b, A(vals[b])^-1) | C x = e for the rows of
+        set_constraints, e None (zeros) or (k,)."""
         if self.reproducible:
             raise NotImplementedError("sample_batch: the batch has no deterministic form (reproducible=True)")
+        if constrained and kind != "precision":
+            raise ValueError("sample_batch: constrained=True needs kind='precision'")
+        if e is not None and not constrained:
+            raise ValueError("sample_batch: e needs constrained=True")
         self._values(vals, "vals", (None, self.nnz))
         ldmean = 0
         if mean is not None:
@@ -388,13 +436,23 @@ class SparseCholesky:
             self._ensure_batch(vals)
             work = torch.empty((vals.shape[0], int(nsamp), self.n), dtype=torch.float64, device=self.device)
             m = None if mean is None else mean.detach().contiguous()
+            if constrained:
+                k = self._ensure_constraints_batch()
+                if e is not None:
+                    e = self._tensor(e, "e", (k,)).contiguous()
             self._sync()
             with torch.cuda.device(self.device):
                 before = self.f.set_batch_blocked_solve(self.batch_blocked)
                 try:
-                    self.f.sample_batch_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed, kind=kind,
-                                            mean_dev_ptr=None if m is None else m.data_ptr(), ldmean=ldmean,
-                                            common_noise=common_noise)
+                    if constrained:
+                        self.f.sample_constrained_batch_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed,
+                                                            mean_dev_ptr=None if m is None else m.data_ptr(),
+                                                            ldmean=ldmean, e_dev_ptr=None if e is None else e.data_ptr(),
+                                                            common_noise=common_noise)
+                    else:
+                        self.f.sample_batch_dev(work.data_ptr(), int(nsamp), ldx=self.n, seed=seed, kind=kind,
+                                                mean_dev_ptr=None if m is None else m.data_ptr(), ldmean=ldmean,
+                                                common_noise=common_noise)
                 finally:
                     self.f.set_batch_blocked_solve(before)
         return work.transpose(1, 2)
