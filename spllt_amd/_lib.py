@@ -245,6 +245,15 @@ _CONSTRAIN_BATCH = {
     "spllt_hip_constraints_batch_info": (i32, [vp, i64p, dp, i64]),
     "spllt_hip_release_constraints_batch": (i32, [vp]),
 }
+# every symbol declared in include/spllt_hip_batch_repro.h: the bit-reproducible batch.  A table of its own for the
+# same reason.
+_BATCH_REPRO = {
+    "spllt_hip_set_batch_reproducible": (i32, [vp, i32]),
+    "spllt_hip_solve_repro_batch": (i32, [vp, i32, vp, i64, i32]),
+    "spllt_hip_solve_repro_batch_dev": (i32, [vp, i32, vp, i64, i32, i32]),
+    "spllt_hip_batch_repro_info": (i32, [vp, i64p]),
+    "spllt_hip_release_batch_repro": (i32, [vp]),
+}
 del u32
 del vp, vpp, i32, i64, u64, f64, cstr, long, ip, i64p, dp, fp, longp, ipp, dpp, opt, inf   # (names of the table only)
 IFACE_SYMBOLS = list(_IFACE)
@@ -255,6 +264,7 @@ BATCH_ADJOINT_SYMBOLS = list(_BATCH_ADJOINT)
 BATCH_REFINE_SYMBOLS = list(_BATCH_REFINE)
 CONSTRAIN_SYMBOLS = list(_CONSTRAIN)
 CONSTRAIN_BATCH_SYMBOLS = list(_CONSTRAIN_BATCH)
+BATCH_REPRO_SYMBOLS = list(_BATCH_REPRO)
 
 _lib = None
 
@@ -269,7 +279,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C spllt_amd/csrc`. spllt_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE, _CONSTRAIN, _CONSTRAIN_BATCH):
+    for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE, _CONSTRAIN, _CONSTRAIN_BATCH,
+                  _BATCH_REPRO):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

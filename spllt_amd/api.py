@@ -172,6 +172,8 @@ class Factorization:
             return raw.view(np.int32)
         if name.startswith("batch_"):    # the batch program: the layouts of the unprefixed names
             name = name[len("batch_"):]
+            if name.startswith("det_"):  # ... and those of its deterministic form
+                name = name[len("det_"):]
         if name == "launches":
             return raw.view(np.int64).reshape(-1, len(LAUNCH_COLS))
         if name == "units":
@@ -1167,6 +1169,56 @@ class Factorization:
     def release_solve_many_batch(self):
         """The workspace of the blocked batch solve back to the device pool."""
         self._call("spllt_hip_release_solve_many_batch", self.fkeep)
+        return self
+
+    # ---- the bit-reproducible batch (include/spllt_hip_batch_repro.h) -----
+    def set_batch_reproducible(self, on):
+        """on: factor_batch runs the deterministic batch program and EVERY sweep over the members of a batch
+        (solve_batch, solve_many_batch, the constrained family, sample_batch(kind="precision"), the preconditioner of
+        solve_refined_batch) runs the reproducible blocked kernels: a member's bits depend on its values and vectors
+        alone, not on the run, on B, on its place in the batch or on the other vectors.  Off
+        by default; flipping it keeps an existing batch.  Returns the previous setting."""
+        return bool(self._call("spllt_hip_set_batch_reproducible", self.fkeep, 1 if on else 0))
+
+    def solve_reproducible_batch(self, X, job=0):
+        """spllt_hip_solve_repro_batch on a copy of X, shapes and jobs as solve_many_batch: the reproducible sweep
+        whatever set_batch_reproducible says.  The vectors of a member that is not positive definite come back
+        unchanged."""
+        x = np.array(X, dtype=np.float64, order="C", copy=True)
+        if x.ndim not in (2, 3):
+            raise ValueError("solve_reproducible_batch: X must have shape (B, n) or (B, nrhs, n)")
+        nrhs = 1 if x.ndim == 2 else x.shape[1]
+        if x.shape[-1] != self.n:
+            raise ValueError(f"solve_reproducible_batch: the vectors have length {x.shape[-1]}, n = {self.n}")
+        nb = self._batch_count()
+        if nb > 0 and x.shape[0] != nb:
+            raise ValueError(f"solve_reproducible_batch: X holds vectors for {x.shape[0]} members, the last batch has {nb}")
+        self._call("spllt_hip_solve_repro_batch", self.fkeep, nrhs, C.c_void_p(x.ctypes.data), x.shape[-1], job,
+                   ok=self._BATCH_OK)
+        return x
+
+    def solve_reproducible_batch_dev(self, x_dev_ptr, nrhs, ldx=None, job=0, pivot_order=False):
+        """spllt_hip_solve_repro_batch_dev: device vectors in place, the layout of solve_batch_dev.  Returns 0 or
+        -20."""
+        if int(nrhs) < 0:
+            raise ValueError("solve_reproducible_batch_dev: nrhs < 0")
+        if ldx is None:
+            ldx = self.n
+        return self._call("spllt_hip_solve_repro_batch_dev", self.fkeep, int(nrhs), C.c_void_p(x_dev_ptr), int(ldx), job,
+                          1 if pivot_order else 0, ok=self._BATCH_OK)
+
+    def batch_repro_info(self):
+        """the switch, whether the last batch was factorized by the deterministic program, the kernel launches of that
+        factorization, the width of the last block of the last reproducible sweep, bytes of the factor scratch and of
+        the sweep scratch"""
+        out = np.zeros(6, dtype=np.int64)
+        self._call("spllt_hip_batch_repro_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        return dict(zip(("on", "deterministic_factor", "factor_launches", "sweep_rb", "factor_scratch_bytes",
+                         "sweep_scratch_bytes"), (int(v) for v in out)))
+
+    def release_batch_repro(self):
+        """The scratch and the tables of the reproducible sweep back to the device pool."""
+        self._call("spllt_hip_release_batch_repro", self.fkeep)
         return self
 
     # ---- the product and the refined solves for the members of a batch (include/spllt_hip_batch_refine.h) -----

@@ -32,6 +32,7 @@
 #include "spllt_hip_batch_adjoint.h"
 #include "spllt_hip_batch_solve_many.h"
 #include "spllt_hip_batch_refine.h"
+#include "spllt_hip_batch_repro.h"
 #include "spllt_hip_constrain.h"
 #include "spllt_hip_constrain_batch.h"
 #include "symbolic.hpp"
@@ -87,10 +88,13 @@ struct Fkeep {
   bool dead = false;       // a submission never returned: the engine belongs to the stuck helper thread
   bool repro_solve = false;   // spllt_hip_set_reproducible_solve: handed to the engine before every solve
   bool batch_blocked = false;   // spllt_hip_set_batch_blocked_solve: handed to the engine before every sample_batch
+  bool batch_repro = false;     // spllt_hip_set_batch_reproducible: handed to the engine by the setter and at its creation
   // what spllt_hip_program_get builds from the analysis alone, each once per pattern (and key):
   Cached<SelinvProgram> si;    // the selected-inversion program, keyed by panel width and chain block
   Cached<SelinvProgram> bsi;   // ... and the batch's (panel width 64 whatever the handle's)
   Cached<Program> bt;          // the batch program
+  Cached<Program> btd;         // ... and its deterministic form ("batch_det_*")
+  Cached<RsolveTables> brs;    // the tables of the batch's reproducible sweep ("batch_rsolve_*")
   Cached<MatvecTables> mv;     // the operator tables ("matvec_*")
   Cached<PatternTables> po;    // the (row, column) tables ("pattern_row" / "pattern_col")
   // spllt_hip_factor_serial: successful changes of the single factor [0] and of the batch [1]
@@ -169,6 +173,7 @@ int ensure_engine(Fkeep* f, bool message = true) {
     f->eng.reset(new (std::nothrow) Engine(f->S, f->eo));
     if (!f->eng) return SPLLT_ERROR_ALLOCATION;
     f->eng->set_exchange_buffer(f->xbuf);
+    f->eng->set_batch_reproducible(f->batch_repro);   // (an engine that exists hears of the switch from its setter)
   }
   if (message && f->eng->status()) f->last_error = f->eng->error();
   return f->eng->status();
@@ -729,6 +734,8 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 //   batch_selinv_fused=0|1  0 forces the three-launch form of every step of the batched selected inversion
 //   batch_fadj_fused=0|1    1 runs the eligible steps of the factor adjoint of a batch as one fused launch each (default 0)
 //   rsolve_poison=0|1       1 fills the scratch of the reproducible solve with NaN before every sweep
+//   batch_repro_poison=0|1  1 fills the scratch of the deterministic batch factorization and that of the reproducible
+//                           batch sweep with NaN before every factorization and every sweep
 //   solve_sparse_poison=0|1 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
 //   fmult_poison=0|1        1 fills the scratch of the factor products (the batched ones too) with NaN before every
 //                           direction
@@ -747,7 +754,7 @@ int spllt_hip_debug(const char* what) {
   if (name == "alloc_fail_at") { set_alloc_fail_at(std::atoi(value.c_str())); return 0; }
   static const struct { const char* name; void (*set)(bool); } kSwitches[] = {
       {"batch_selinv_fused", set_batch_selinv_fused}, {"batch_fadj_fused", set_batch_fadj_fused},
-      {"rsolve_poison", set_rsolve_poison},
+      {"rsolve_poison", set_rsolve_poison}, {"batch_repro_poison", set_batch_repro_poison},
       {"solve_sparse_poison", set_solve_sparse_poison}, {"fmult_poison", set_fmult_poison}};
   for (const auto& s : kSwitches)
     if (name == s.name && (value == "0" || value == "1")) { s.set(value == "1"); return 0; }
@@ -1258,6 +1265,48 @@ int spllt_hip_solve_many_batch_info(void* fkeep, int64_t out[4]) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
   for (int i = 0; i < 4; ++i) out[i] = f->eng ? f->eng->solve_many_batch_info()[i] : 0;
+  return 0;
+}
+
+// ---- the bit-reproducible batch (spllt_hip_batch_repro.h) -------------------------------------------
+int spllt_hip_set_batch_reproducible(void* fkeep, int on) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S) return SPLLT_ERROR_PARAMETER;
+  if (on && f->eo.nranks > 1) {   // (a plain setter: refused without the stderr line of the guard)
+    f->last_error = "spllt_hip_set_batch_reproducible: not available on a partitioned (multi-GPU) handle";
+    return SPLLT_ERROR_UNIMPLEMENTED;
+  }
+  const int before = f->batch_repro ? 1 : 0;
+  f->batch_repro = on != 0;
+  if (f->eng && !f->dead) f->eng->set_batch_reproducible(f->batch_repro);
+  return before;
+}
+
+// the rungs of solve_many_batch_impl, in its order
+static int solve_repro_batch_impl(void* fkeep, int nrhs, double* x, int64_t ldx, int job, bool dev, bool pivot_order,
+                                  const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  if (int rc = enter(f, what, vectors_bad(f, nrhs, x, ldx, job), SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (nrhs == 0) return 0;
+  return batch_mult_leave(f, what, f->eng->solve_repro_batch(x, dev, nrhs, ldx, job, pivot_order),
+                          "the vectors of the members that are not positive definite were left unchanged");
+}
+
+int spllt_hip_solve_repro_batch(void* fkeep, int nrhs, double* x_host, int64_t ldx, int job) {
+  return solve_repro_batch_impl(fkeep, nrhs, x_host, ldx, job, false, false, "spllt_hip_solve_repro_batch");
+}
+
+int spllt_hip_solve_repro_batch_dev(void* fkeep, int nrhs, double* x_dev, int64_t ldx, int job, int pivot_order) {
+  return solve_repro_batch_impl(fkeep, nrhs, x_dev, ldx, job, true, pivot_order != 0, "spllt_hip_solve_repro_batch_dev");
+}
+
+int spllt_hip_batch_repro_info(void* fkeep, int64_t out[6]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  if (f->eng && !f->dead) f->eng->batch_repro_info(out);
+  out[0] = f->batch_repro ? 1 : 0;
   return 0;
 }
 
@@ -1986,6 +2035,7 @@ int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::relea
 int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::release_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_solve_many_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_many_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_batch_repro(void* fkeep) { return release(fkeep, &Engine::release_batch_repro, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_refine_batch(void* fkeep) { return release(fkeep, &Engine::release_refine_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_constraints_batch(void* fkeep) { return release(fkeep, &Engine::release_constraints_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_inverse_batch(void* fkeep) { return release(fkeep, &Engine::release_inverse_batch, WAIT_IGNORE | LENIENT); }
@@ -2138,6 +2188,36 @@ static int64_t get_batch(Fkeep* f, const std::string& q, const Out& o) {   // q:
   return -1;
 }
 
+// "batch_det_*": the deterministic program of the batched factorization (batch_repro.hip), the same fixed options
+static int64_t get_batch_det(Fkeep* f, const std::string& q, const Out& o) {
+  const Program* P = f->btd.get(f->S, 1, 0, [&](Program& v) { return build_batch_program(*f->S, v, &f->last_error, true); });
+  if (!P) return -1;
+  static const char* const kNames[] = {"launches", "units", "tiles", "chains", "relpos", "dinv_size", "potrf", "scratch_size",
+                                       "gather_tiles", "gather_items"};
+  for (const char* n : kNames)
+    if (q == n) return get_plain(P, q, o);
+  return -1;
+}
+
+// "batch_rsolve_*": the tables of the reproducible sweep of the batch, from the batch's own solve program (pw = cb = 64)
+static int64_t get_batch_rsolve(Fkeep* f, const std::string& q, const Out& o) {
+  const RsolveTables* R = f->brs.get(f->S, 64, 64, [&](RsolveTables& v) {
+    SolveProgram sp;
+    build_solve_program(*f->S, 64, 64, sp);
+    v = RsolveTables();
+    build_rsolve_tables(*f->S, sp, v);
+    return 0;
+  });
+  if (q == "fslot") return o.bytes(R->fslot);
+  if (q == "bfirst") return o.bytes(R->bfirst);
+  if (q == "gptr") return o.bytes(R->gptr);
+  if (q == "gsrc") return o.bytes(R->gsrc);
+  if (q == "bslot") return o.bytes(R->bslot);
+  if (q == "frows") return o.bytes(&R->frows, sizeof(int64_t));
+  if (q == "bsize") return o.bytes(&R->bsize, sizeof(int64_t));
+  return -1;
+}
+
 int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t cap) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
   if (!f || !f->S || !name) return -1;
@@ -2167,6 +2247,8 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
   if (is("batch_selinv_"))   // panels of 64 columns whatever the handle's, from the symbolic structure alone
     return get_selinv(f->bsi.get(f->S, 64, 64, [&](SelinvProgram& v) { return build_selinv_program(*f->S, 64, 64, v); }),
                       k.substr(6), o);
+  if (is("batch_det_")) return get_batch_det(f, k.substr(10), o);
+  if (is("batch_rsolve_")) return get_batch_rsolve(f, k.substr(13), o);
   if (is("batch_")) return get_batch(f, k.substr(6), o);
   if (is("selinv_"))         // (single GPU; built from the symbolic structure alone)
     return get_selinv(f->si.get(f->S, P->pw, P->cb, [&](SelinvProgram& v) { return build_selinv_program(*f->S, P->pw, P->cb, v); }),

@@ -1901,7 +1901,7 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
 }
 
 // ---- batched factorization ------------------------------------------------------------------------
-int build_batch_program(const Symbolic& S, Program& P, std::string* why) {
+int build_batch_program(const Symbolic& S, Program& P, std::string* why, bool deterministic) {
   ScheduleOptions so;
   so.pw = 64;
   so.tile = 64;
@@ -1911,18 +1911,37 @@ int build_batch_program(const Symbolic& S, Program& P, std::string* why) {
   so.fused_panel = false;
   so.subtrees = false;
   so.env_switches = false;      // (SPLLT_CHAIN4=1 / SPLLT_SUBTREES=1 are experiments of the single-handle engine)
-  so.deterministic = false;
+  so.deterministic = deterministic;   // (batch_repro.hip: MODE_BUFFER units + one L_GATHER launch per level)
   P = Program();
   build_program(S, so, P);
   auto bad = [&](const std::string& what) {
     if (why) *why = "batched factorization: the batch program holds " + what + ", which the batch kernels do not implement";
     return -99;
   };
+  const int scatter_mode = deterministic ? MODE_BUFFER : MODE_SCATTER;   // how this program subtracts between nodes
   if (P.pw != 64 || !P.exchanges.empty()) return bad("a panel width other than 64 or an exchange");
   for (size_t i = 0; i < P.launches.size(); ++i) {
     const Launch& l = P.launches[i];
-    if (l.kind != L_CHAIN && l.kind != L_GEMM) return bad("launch kind " + std::to_string(l.kind));
+    if (l.kind != L_CHAIN && l.kind != L_GEMM && !(deterministic && l.kind == L_GATHER))
+      return bad("launch kind " + std::to_string(l.kind));
     if (l.count <= 0) continue;
+    if (l.kind == L_GATHER) {
+      // a tile is at most 64 x 64 (the LDS tile of the gather kernel) and its items lie inside the scratch
+      if (l.first < 0 || l.first + l.count > (int64_t)P.gather_tiles.size()) return bad("a gather launch outside its table");
+      for (int64_t q = l.first; q < l.first + l.count; ++q) {
+        const GatherTile& t = P.gather_tiles[(size_t)q];
+        if (t.rows < 1 || t.rows > 64 || t.cols < 1 || t.cols > 64 || t.first < 0 || t.count < 0 ||
+            (size_t)t.first + (size_t)t.count > P.gather_items.size())
+          return bad("a gather tile larger than 64 x 64");
+        for (int e = t.first; e < t.first + t.count; ++e) {
+          const GatherItem& g = P.gather_items[(size_t)e];
+          if (g.i0 < 0 || g.i1 < g.i0 || g.j0 < 0 || g.j1 < g.j0 || g.j1 > g.ld || g.buf_off < 0 ||
+              g.buf_off + (int64_t)g.i1 * g.ld > P.scratch_size)
+            return bad("a gather item outside the scratch");
+        }
+      }
+      continue;
+    }
     if (l.kind == L_CHAIN) {
       for (int64_t q = l.first; q < l.first + l.count; ++q) {
         const ChainUnit& u = P.chain_units[(size_t)q];
@@ -1933,7 +1952,9 @@ int build_batch_program(const Symbolic& S, Program& P, std::string* why) {
     if (l.tile != 32 && l.tile != 64) return bad("tile edge " + std::to_string(l.tile));
     for (int64_t q = l.first; q < l.first + l.count; ++q) {
       const UpdUnit& u = P.units[(size_t)P.tiles[(size_t)q].unit];
-      if (u.mode != MODE_DIRECT && u.mode != MODE_SCATTER && u.mode != MODE_TRSM) return bad("unit mode " + std::to_string(u.mode));
+      if (u.mode != MODE_DIRECT && u.mode != scatter_mode && u.mode != MODE_TRSM) return bad("unit mode " + std::to_string(u.mode));
+      if (u.mode == MODE_BUFFER && (u.d_ld != u.N || u.d_off < 0 || u.d_off + (int64_t)u.M * u.N > P.scratch_size))
+        return bad("a BUFFER unit outside the scratch");
       if (u.mode == MODE_DIRECT && u.atomic) return bad("a DIRECT unit that subtracts with atomics");
       // a TRSM tile overwrites its own operand rows: it must cover all the unit's columns, and the K
       // window must be the inverted panel's
@@ -2014,10 +2035,29 @@ int Engine::prepare_batch() {
 }
 
 // arenas, dinv scratch, flags and log-det slots for nbatch members; all or nothing
-int Engine::reserve_batch(int nbatch) {
-  if (nbatch <= bt_.capacity) return 0;
-  give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out);   // (a larger batch: everything again)
+int Engine::reserve_batch(int nbatch, bool deterministic) {
+  const bool want_f = deterministic && brp_.prog.scratch_size > 0;
+  if (nbatch <= bt_.capacity) {
+    if (!want_f || (brp_.fscratch && brp_.f_capacity >= bt_.capacity)) return 0;
+    // the batch stands and the switch came later: the factor scratch alone, for the members the batch holds
+    give_back(brp_.fscratch);
+    brp_.f_capacity = 0;
+    auto t = take();
+    t(&brp_.fscratch, sizeof(double) * (size_t)brp_.fstride * (size_t)bt_.capacity);
+    if (!t.ok()) {
+      feature_err_ = "batched factorization: not enough device memory for the scratch of the deterministic program (" +
+                     std::to_string((sizeof(double) * (size_t)brp_.fstride * (size_t)bt_.capacity) >> 20) + " MiB): " +
+                     hipGetErrorString(t.error());
+      return alloc_code(t.error());
+    }
+    t.commit();
+    brp_.f_capacity = bt_.capacity;
+    return 0;
+  }
+  const bool take_f = want_f || brp_.fscratch;      // (a scratch that is held grows with the batch)
+  give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, brp_.fscratch);   // (a larger batch: everything again)
   bt_.capacity = bt_.nbatch = 0;
+  brp_.f_capacity = 0;
   bt_.hflag.clear();
   // member strides: multiples of 32 doubles, so that every member starts 256-byte aligned
   bt_.lstride = std::max<int64_t>(32, (S_->arena + 31) / 32 * 32);
@@ -2029,14 +2069,56 @@ int Engine::reserve_batch(int nbatch) {
   t(&bt_.dinv, db);
   t(&bt_.flag, sizeof(int) * (size_t)nbatch);
   t(&bt_.out, sizeof(double) * (size_t)nbatch);
+  const size_t fb = take_f ? sizeof(double) * (size_t)brp_.fstride * (size_t)nbatch : 0;
+  if (take_f) t(&brp_.fscratch, fb);
   if (!t.ok()) {
     feature_err_ = "batched factorization: not enough device memory for " + std::to_string(nbatch) + " members (" +
-                   std::to_string((lb + db) >> 20) + " MiB): " + hipGetErrorString(t.error());
+                   std::to_string((lb + db + fb) >> 20) + " MiB): " + hipGetErrorString(t.error());
     return alloc_code(t.error());
   }
   t.commit();
   bt_.capacity = nbatch;
+  if (take_f) brp_.f_capacity = nbatch;
   return 0;
+}
+
+// ---- bit-reproducible batch: the deterministic program and its tables, built and uploaded once per engine
+int Engine::prepare_batch_repro() {
+  if (brp_.ready) return 0;
+  int rc = build_batch_program(*S_, brp_.prog, &feature_err_, true);
+  if (rc) return rc;
+  if (brp_.prog.dinv_size != bt_.prog.dinv_size) {   // (both follow from the block columns and pw = cb = 64 alone)
+    feature_err_ = "batched factorization: the deterministic program lays the dinv scratch out differently";
+    return -99;
+  }
+  TableStager tab;
+  tab.add(&brp_.units, brp_.prog.units);
+  tab.add(&brp_.tiles, brp_.prog.tiles);
+  tab.add(&brp_.chain, brp_.prog.chain_units);
+  tab.add(&brp_.relpos, brp_.prog.relpos);
+  tab.add(&brp_.gtiles, brp_.prog.gather_tiles);
+  tab.add(&brp_.gitems, brp_.prog.gather_items);
+  auto t = take();
+  t.tables(tab, &brp_.d_tab);
+  if (!t.ok()) {
+    feature_err_ = std::string("batched factorization: the tables of the deterministic program could not be uploaded (") +
+                   hipGetErrorString(t.error()) + ")";
+    return alloc_code(t.error());
+  }
+  t.commit();
+  // member stride: a multiple of 32 doubles, as the arena's
+  brp_.fstride = std::max<int64_t>(32, (brp_.prog.scratch_size + 31) / 32 * 32);
+  brp_.ready = true;
+  return 0;
+}
+
+BatchReproView Engine::brepro_factor_view(int nbatch) const {
+  BatchReproView s;
+  s.v = batch_view();
+  s.v.nbatch = nbatch;
+  s.scratch = brp_.fscratch;
+  s.sstride = brp_.fstride;
+  return s;
 }
 
 int Engine::grow_batch_buffer(double** p, size_t* have, size_t need, const char* what) {
@@ -2059,7 +2141,9 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   int rc = prepare_batch();
   if (rc) return rc;
-  if ((rc = reserve_batch(nbatch))) return rc;
+  const bool det = brp_on_;          // (the deterministic program: batch_repro.hip)
+  if (det && (rc = prepare_batch_repro())) return rc;
+  if ((rc = reserve_batch(nbatch, det))) return rc;
   bt_.nbatch = 0;                    // (no batch until this one is finished)
   bt_.z_valid = false;               // (the members' inverses belong to the factors this call replaces)
   bt_.g_state = FADJ_UNSEEDED;       // (... and so do their adjoints)
@@ -2080,13 +2164,29 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   int nl = 0;
   auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
   count(launch_batch_init(stream_, v, S_->arena, vd, ld, bt_.init_cptr, bt_.init_loc, bt_.init_src));
-  for (const Launch& l : bt_.prog.launches) {
-    if (l.count <= 0 || !fits) continue;
-    if (l.kind == L_CHAIN)
-      count(launch_batch_chain(stream_, v, bt_.chain + l.first, l.count));
-    else
-      count(launch_batch_update(stream_, v, l.tile, bt_.tiles + l.first, l.count, bt_.units, d_bc_off_, d_bc_w_,
-                                bt_.relpos, d_rlist_));
+  if (det) {
+    const BatchReproView s = brepro_factor_view(nbatch);
+    // debug: a buffered entry that is gathered without having been stored by this factorization shows up as NaN
+    if (batch_repro_poison() && brp_.fscratch)
+      (void)hipMemsetAsync(brp_.fscratch, 0xFF, sizeof(double) * (size_t)brp_.fstride * (size_t)brp_.f_capacity, stream_);
+    for (const Launch& l : brp_.prog.launches) {
+      if (l.count <= 0 || !fits) continue;
+      if (l.kind == L_CHAIN)
+        count(launch_batch_chain(stream_, v, brp_.chain + l.first, l.count));
+      else if (l.kind == L_GATHER)
+        count(launch_bdet_gather(stream_, s, brp_.gtiles + l.first, l.count, brp_.gitems, brp_.relpos, d_rlist_));
+      else
+        count(launch_bdet_update(stream_, s, l.tile, brp_.tiles + l.first, l.count, brp_.units, d_bc_off_, d_bc_w_));
+    }
+  } else {
+    for (const Launch& l : bt_.prog.launches) {
+      if (l.count <= 0 || !fits) continue;
+      if (l.kind == L_CHAIN)
+        count(launch_batch_chain(stream_, v, bt_.chain + l.first, l.count));
+      else
+        count(launch_batch_update(stream_, v, l.tile, bt_.tiles + l.first, l.count, bt_.units, d_bc_off_, d_bc_w_,
+                                  bt_.relpos, d_rlist_));
+    }
   }
   HIPCHK(hipGetLastError(), "batch factor launch");
   // (the destination of the copy lives in bt_: a wait that runs into its deadline leaves it in flight)
@@ -2100,6 +2200,7 @@ int Engine::factor_batch(const double* val, bool on_device, int nbatch, int64_t 
   bt_.launches = nl;
   bt_.nbatch = nbatch;
   bt_.hflag = bt_.hflag_pending;
+  brp_.last_det = det;
   return batch_failed();
 }
 
@@ -2109,6 +2210,11 @@ int Engine::solve_batch(double* x, bool on_device, int nrhs, int64_t ldx, int jo
   const int n = S_->n;
   if (!x || nrhs < 0 || ldx < n || job < 0 || job > 2 || bt_.nbatch <= 0) return -10;
   if (nrhs == 0 || n == 0) return 0;
+  if (brp_on_) {   // the reproducible batch: every sweep goes through the dispatch point of the blocked solve
+    const int rc = solve_many_batch(x, on_device, nrhs, ldx, job, pivot_order);
+    bt_.solve_launches = (int)bsm_info_[2];
+    return rc;
+  }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   const size_t nvec = (size_t)bt_.nbatch * (size_t)nrhs;
   int rc = grow_batch_buffer(&bt_.Y, &bt_.y_elems, nvec * (size_t)n, "the solve workspace");
@@ -2187,14 +2293,17 @@ int Engine::release_batch() {
   bt_.g_state = FADJ_UNSEEDED;
   bt_.fa_launches = 0;
   // (the batch's own storage, and what its features say of theirs)
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brf_held() && !bcn_.C) { bt_.nbatch = 0; return 0; }
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brp_.swscratch && !brf_held() && !bcn_.C) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
   drop_solve_many_batch();    // (... and that of the blocked solve)
+  drop_solve_repro_batch();   // (... and the scratch of its reproducible form)
   drop_refine_batch();        // (... and those of the refined solves)
   drop_constraints_batch();   // (... and the constraints of the batch, C included)
-  give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, bt_.Y, bt_.stage, bt_.Z, bt_.G, bt_.siscratch);
+  give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, bt_.Y, bt_.stage, bt_.Z, bt_.G, bt_.siscratch, brp_.fscratch);
+  brp_.f_capacity = 0;
+  brp_.last_det = false;
   bt_.sc_users = Shared{};
   bt_.z_capacity = bt_.g_capacity = bt_.sc_capacity = 0;
   bt_.si_launches = 0;

@@ -65,6 +65,10 @@ void set_batch_selinv_fused(bool on);
 void set_batch_fadj_fused(bool on);
 // debug: the scratch of the reproducible solve is filled with NaN before every sweep
 void set_rsolve_poison(bool on);
+// debug hook (spllt_hip_debug "batch_repro_poison=0|1"): 1 fills the scratch of the deterministic batch
+// factorization and that of the reproducible batch sweep with NaN before every factorization and every sweep
+void set_batch_repro_poison(bool on);
+bool batch_repro_poison();
 // debug: the scratch of the factor products is filled with NaN before every direction
 void set_fmult_poison(bool on);
 // debug: the next n allocations of the factor products' workspace and scratch fail (the fall-back to blocks of 16)
@@ -228,6 +232,22 @@ class Engine {
   // of the last solve_many_batch, bytes of the workspace
   const int64_t* solve_many_batch_info() const { return bsm_info_; }
   int release_solve_many_batch();
+  // ---- bit-reproducible batch (batch_repro.hip; include/spllt_hip_batch_repro.h).  on: factor_batch runs the
+  // deterministic batch program (MODE_BUFFER units + ordered gathers) and EVERY blocked sweep of the batch -- the
+  // dispatch point enqueue_solve_many_batch_block, to which solve_batch is routed as well -- runs the kernels that
+  // store the strip products and subtract them in table order.  The factor scratch (scratch_size doubles per member)
+  // is taken with the batch; the sweep's tables and scratch (rb max(frows, bsize) doubles per member) on the first
+  // reproducible sweep, all or nothing (-1: nothing kept, the batch and every other solve stay usable).  Flipping the
+  // switch keeps the batch.
+  void set_batch_reproducible(bool on) { brp_on_ = on; }
+  bool batch_reproducible() const { return brp_on_; }
+  // solve_many_batch through the reproducible kernels whatever the switch says
+  int solve_repro_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order);
+  // the switch, whether the LAST batch was factorized by the deterministic program, the kernel launches of that
+  // factorization, the block width of the last reproducible sweep's last block, bytes of the factor scratch, bytes
+  // of the sweep scratch
+  void batch_repro_info(int64_t out[6]) const;
+  int release_batch_repro();   // the sweep's scratch and tables (the factor scratch goes with the batch)
   // ---- sparse right-hand sides and selected outputs (solve_sparse.hip, single GPU): B = k sparse columns (CSC,
   // 1-based, user order, validated by the caller: check_sparse_columns), sel = nsel wanted user variables (null:
   // all n).  Per group of 32 columns (a tail of at most 16: a block of 16) the substitution program is filtered
@@ -689,6 +709,40 @@ class Engine {
   int bsm_capacity_ = 0;           // members it holds
   double* d_bsmW_ = nullptr;       // bsm_capacity_ * bsm_rb_ * n doubles: W_b[p * rb + q]
   int64_t bsm_info_[4] = {0, 0, 0, 0};
+  // bit-reproducible batch: the deterministic program and its tables (once per engine), the factor scratch (with
+  // the batch), the tables and the scratch of the sweep (first reproducible sweep, for sw_capacity members)
+  struct BreproState {
+    bool ready = false;              // the deterministic program is built and its tables are on the device
+    Program prog;
+    char* d_tab = nullptr;
+    UpdUnit* units = nullptr;
+    UpdTile* tiles = nullptr;
+    ChainUnit* chain = nullptr;
+    int* relpos = nullptr;
+    GatherTile* gtiles = nullptr;
+    GatherItem* gitems = nullptr;
+    double* fscratch = nullptr;      // f_capacity x fstride
+    int f_capacity = 0;
+    int64_t fstride = 0;
+    bool last_det = false;           // the last batch was factorized by the deterministic program
+    char* d_swtab = nullptr;
+    int64_t* fslot = nullptr;
+    int64_t* bfirst = nullptr;
+    int64_t* gptr = nullptr;
+    int64_t* gsrc = nullptr;
+    int64_t* bslot = nullptr;
+    int64_t slots = 0;               // max(frows, bsize, 1): scratch slots per right-hand side
+    double* swscratch = nullptr;     // sw_capacity x sw_rb x slots
+    int sw_rb = 0, sw_capacity = 0;
+    int last_rb = 0;
+  } brp_;
+  bool brp_on_ = false;
+  bool brp_force_ = false;           // solve_repro_batch is running
+  bool brp_sweep() const { return brp_on_ || brp_force_; }
+  int prepare_batch_repro();         // program + tables
+  int prepare_solve_repro_batch();   // the sweep's tables and scratch for the members of the last batch
+  void drop_solve_repro_batch();
+  BatchReproView brepro_factor_view(int nbatch) const;
   // blocked solve (workspace allocated on first use, kept with the engine)
   int prepare_solve_many(bool host_stage);
   int run_solve_many(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order);   // both entry points
@@ -906,7 +960,7 @@ class Engine {
     int64_t generation = 0;          // counts the factor_batch calls that replaced the members' factors
   } bt_;
   int prepare_batch();
-  int reserve_batch(int nbatch);
+  int reserve_batch(int nbatch, bool deterministic);   // (deterministic: the factor scratch too, one transaction)
   int grow_batch_buffer(double** p, size_t* have, size_t need, const char* what);   // grow + the batch's message
   BatchView batch_view() const;
   int prepare_batch_selinv();
@@ -930,7 +984,9 @@ inline void EngineRelease::operator()(void* p) const { eng->release_buffer(p); }
 // flags say.  0, or -99 with *why when the program holds anything batch.hip does not implement (launch
 // kinds other than L_CHAIN / L_GEMM, tile edges other than 32 / 64, unit modes other than DIRECT /
 // SCATTER / TRSM, an atomic DIRECT unit): nothing is skipped silently.
-int build_batch_program(const Symbolic& S, Program& P, std::string* why);
+// deterministic: the same options with ScheduleOptions::deterministic (batch_repro.hip) -- MODE_BUFFER units in
+// the place of the SCATTER ones and L_GATHER launches are accepted besides, and nothing else.
+int build_batch_program(const Symbolic& S, Program& P, std::string* why, bool deterministic = false);
 // arena offset of the diagonal entry of every pivot position (from the Symbolic structure alone)
 void batch_diag_positions(const Symbolic& S, std::vector<int64_t>& pos);
 

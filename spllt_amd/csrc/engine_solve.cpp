@@ -1037,7 +1037,15 @@ void Engine::drop_solve_many_batch() {
 // the workspace for the members of the last batch: 32 vectors per member, or 16 when that does not fit
 int Engine::prepare_solve_many_batch() {
   const int nbatch = bt_.nbatch;
-  if (bsm_ready_ && nbatch <= bsm_capacity_) return 0;
+  // the reproducible form needs its tables and its scratch besides; a scratch that only fits blocks of 16 narrows
+  // the blocks of the walk (the workspace holds them either way)
+  auto repro = [&]() -> int {
+    if (!brp_sweep()) return 0;
+    if (int rc = prepare_solve_repro_batch()) return rc;
+    if (brp_.sw_rb < bsm_rb_) bsm_info_[0] = bsm_rb_ = brp_.sw_rb;
+    return 0;
+  };
+  if (bsm_ready_ && nbatch <= bsm_capacity_) return repro();
   if (bsm_ready_) drop_solve_many_batch();   // (a larger batch: the workspace again)
   const size_t n1 = (size_t)std::max(1, S_->n);
   // (a failure here leaves the batch, solve_batch and the single factorization usable)
@@ -1054,7 +1062,76 @@ int Engine::prepare_solve_many_batch() {
   bsm_ready_ = true;
   bsm_info_[0] = bsm_rb_;
   bsm_info_[3] = (int64_t)want;
+  return repro();
+}
+
+// ---- the reproducible form of the blocked sweep (batch_repro.hip) ----------------------------------------
+static std::atomic<bool> g_batch_repro_poison{false};
+void set_batch_repro_poison(bool on) { g_batch_repro_poison.store(on); }
+bool batch_repro_poison() { return g_batch_repro_poison.load(); }
+
+void Engine::drop_solve_repro_batch() {
+  give_back(brp_.swscratch, brp_.d_swtab);
+  brp_.fslot = brp_.bfirst = brp_.gptr = brp_.gsrc = brp_.bslot = nullptr;
+  brp_.sw_rb = brp_.sw_capacity = brp_.last_rb = 0;
+}
+
+// the tables of the batch's own solve program and rb max(frows, bsize) doubles per member of the last batch, one
+// transaction (taken again together when a later batch has more members): rb = 32, or 16 when that does not fit
+int Engine::prepare_solve_repro_batch() {
+  const int nbatch = bt_.nbatch;
+  if (brp_.swscratch && nbatch <= brp_.sw_capacity) return 0;
+  drop_solve_repro_batch();   // (a larger batch: the scratch again)
+  RsolveTables R;
+  build_rsolve_tables(*S_, bt_.sprog, R);
+  brp_.slots = std::max<int64_t>(1, std::max(R.frows, R.bsize));
+  TableStager tab;
+  tab.add(&brp_.fslot, R.fslot);
+  tab.add(&brp_.bfirst, R.bfirst);
+  tab.add(&brp_.gptr, R.gptr);
+  tab.add(&brp_.gsrc, R.gsrc);
+  tab.add(&brp_.bslot, R.bslot);
+  // (a failure here leaves the batch, every other solve and the single factorization usable)
+  auto t = take();
+  t.tables(tab, &brp_.d_swtab);
+  size_t want = 0;
+  int rb = 32;
+  if (t.ok())
+    t.check(take_block_buffers({{(void**)&brp_.swscratch, sizeof(double) * (size_t)nbatch * (size_t)brp_.slots}}, &rb, &want));
+  if (const hipError_t e = t.error()) {
+    give_back(brp_.swscratch);
+    feature_err_ = "reproducible batch sweep: not enough device memory for the tables and the scratch of 16 right-hand "
+                   "sides for each of " + std::to_string(nbatch) + " members (" + std::to_string(want >> 20) + " MiB): " +
+                   hipGetErrorString(e);
+    return alloc_code(e);
+  }
+  t.commit();
+  brp_.sw_rb = rb;
+  brp_.sw_capacity = nbatch;
   return 0;
+}
+
+int Engine::release_batch_repro() {
+  int rc;
+  if (!enter_release(brp_.swscratch || brp_.d_swtab, "batch_repro release", &rc)) return rc;
+  drop_solve_repro_batch();
+  return 0;
+}
+
+void Engine::batch_repro_info(int64_t out[6]) const {
+  out[0] = brp_on_ ? 1 : 0;
+  out[1] = bt_.nbatch > 0 && brp_.last_det ? 1 : 0;
+  out[2] = out[1] ? bt_.launches : 0;
+  out[3] = brp_.last_rb;
+  out[4] = (int64_t)sizeof(double) * brp_.fstride * brp_.f_capacity;
+  out[5] = (int64_t)sizeof(double) * brp_.slots * brp_.sw_rb * brp_.sw_capacity;
+}
+
+int Engine::solve_repro_batch(double* x, bool on_device, int nrhs, int64_t ldx, int job, bool pivot_order) {
+  brp_force_ = true;
+  const int rc = solve_many_batch(x, on_device, nrhs, ldx, job, pivot_order);
+  brp_force_ = false;
+  return rc;
 }
 
 int Engine::release_solve_many_batch() {
@@ -1074,11 +1151,22 @@ int Engine::enqueue_solve_many_batch_block(double* x_dev, int64_t xstride, int64
   int nl = 0;
   bool fits = true;
   auto count = [&](int k) { if (k < 0) fits = false; else nl += k; };
+  // the reproducible batch: the same launches in the same order by the kernels of batch_repro.hip (the caller's
+  // prepare_solve_many_batch has taken their tables and scratch; without them nothing is launched)
+  const bool repro = brp_sweep();
+  if (repro && !(brp_.swscratch && rb <= brp_.sw_rb)) return -1;
   count(launch_batch_solve_many_pack(stream_, v, false, x_dev, xstride, ldx, order, n, nv, rb, d_bsmW_));
   if (!fits) return -1;   // (nothing was launched: the vectors are as they were)
+  const BatchReproView rs{v, brp_.swscratch, (int64_t)brp_.sw_rb * brp_.slots};
+  const RsmTables tb{brp_.fslot, brp_.bfirst, brp_.gptr, brp_.gsrc, brp_.bslot};
+  if (repro) brp_.last_rb = rb;
   auto run = [&](const std::vector<SolveLaunch>& ls) {
+    // debug: a slot that is read without having been written in this sweep shows up as NaN
+    if (repro && batch_repro_poison())
+      (void)hipMemsetAsync(brp_.swscratch, 0xFF, sizeof(double) * (size_t)rs.sstride * (size_t)brp_.sw_capacity, stream_);
     for (const SolveLaunch& l : ls)
-      count(launch_batch_solve_many(stream_, v, l, bt_.slist, bt_.stiles, bt_.sunits, d_rlist_, d_bsmW_, rb, n));
+      count(repro ? launch_batch_solve_repro(stream_, rs, l, bt_.slist, bt_.stiles, bt_.sunits, d_rlist_, tb, d_bsmW_, rb, n)
+                  : launch_batch_solve_many(stream_, v, l, bt_.slist, bt_.stiles, bt_.sunits, d_rlist_, d_bsmW_, rb, n));
   };
   if (job == 0 || job == 1) run(bt_.sprog.fwd);
   if (job == 0 || job == 2) run(bt_.sprog.bwd);

@@ -204,6 +204,35 @@ int launch_batch_solve_many(hipStream_t st, const BatchView& v, const SolveLaunc
 // the limit in force (set_batch_grid_limit) and the hardware limit, for the other batched translation units
 int64_t batch_grid_limit();
 int64_t batch_grid_limit_max();
+// ---- bit-reproducible batch (batch_repro.hip): no atomic add anywhere ----------------------------------
+// The batch's view plus member b's scratch at scratch + b * sstride: the MODE_BUFFER products of the deterministic
+// batch program (factorization), or the stored strip products of a sweep.  When the members of a launch are split
+// into ranges the scratch pointer moves with the first member, as L, dinv and flag do.  A member whose flag is set
+// is skipped by every kernel before any barrier.  Return values as above.
+struct BatchReproView {
+  BatchView v;
+  double* scratch;
+  int64_t sstride;
+};
+// k_batch_update with the epilogues TRSM, DIRECT and BUFFER (the product stored at scratch_b[u.d_off + i N + j])
+int launch_bdet_update(hipStream_t st, const BatchReproView& s, int tile, const UpdTile* tiles, int64_t count,
+                       const UpdUnit* units, const int64_t* bc_off, const int* bc_w);
+// k_gather for (gather tile, member): the buffered blocks subtracted from their destination tiles, items in table order
+int launch_bdet_gather(hipStream_t st, const BatchReproView& s, const GatherTile* tiles, int64_t count,
+                       const GatherItem* items, const int* relpos, const int* rlist);
+// the tables of build_rsolve_tables for the batch's solve program on the device (shared by all members)
+struct RsmTables {
+  const int64_t* fslot;    // per block column
+  const int64_t* bfirst;   // per block column (-1: no rows below)
+  const int64_t* gptr;     // n + 1
+  const int64_t* gsrc;     // frows
+  const int64_t* bslot;    // per tile of the SolveProgram
+};
+// launch_batch_solve_many without atomics: a strip stores into member b's scratch (rb * max(frows, bsize) doubles),
+// the diagonal launch subtracts the stored products in table order first (rsm_body.hpp)
+int launch_batch_solve_repro(hipStream_t st, const BatchReproView& s, const SolveLaunch& l, const int* list,
+                             const UpdTile* tiles, const SolveUnit* units, const int* rlist, const RsmTables& tb,
+                             double* W, int rb, int n);
 // ---- batched selected inversion (batch_selinv.hip): Z_b on the pattern of L for every member ----------
 // The batch's view plus member b's inverse arena Z + b * v.lstride (L's layout) and step scratch
 // scratch + b * sstride.  The tables are those of a SelinvProgram built with pw = cb = 64 and are shared.

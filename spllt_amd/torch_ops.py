@@ -35,6 +35,9 @@ from .api import Factorization, SplltError, csc_lower_1based
 __all__ = ["SparseCholesky"]
 
 _NOT_POSDEF = -20
+# what a batch operation says under reproducible=True alone (the single handle's switch does not reach the batch)
+_NO_DET_BATCH = (": the batch has no deterministic form under reproducible=True; pass batch_reproducible=True for the "
+                 "bit-reproducible batch")
 
 
 class SparseCholesky:
@@ -43,7 +46,12 @@ class SparseCholesky:
     A_or_pattern: a scipy sparse symmetric matrix (its lower triangle gives the pattern and the order of ``val``) or
     the triple (n, ptr, row) of a 1-based CSC lower triangle.  reproducible=True: the deterministic engine (flag
     4096) and the reproducible solve -- forward and backward of ``solve`` and ``logdet`` are then bit-reproducible
-    across calls; the batch has no deterministic form and raises NotImplementedError.  batch_blocked=True: the
+    across calls; it does not reach the batch, whose operations then raise NotImplementedError unless
+    batch_reproducible=True is given too.  batch_reproducible=True: Factorization.set_batch_reproducible for the
+    handle -- the deterministic batch factorization and the reproducible blocked sweep under every batch operation:
+    ``solve_batch``, ``logdet_batch``, ``sample_batch`` (both kinds), ``solve_constrained_batch``,
+    ``factor_apply_batch`` and ``rsample_batch`` and the backward passes of the differentiable ones repeat bit for
+    bit, whatever the batch size and a member's place in it.  batch_blocked=True: the
     forward and the backward of ``solve_batch`` and the precision kind of ``sample_batch`` run through the blocked
     matrix-core batch solve (Factorization.solve_many_batch_dev) instead of solve_batch_dev -- the same numbers to
     rounding, the path for many right-hand sides per member; off by default.
@@ -54,7 +62,8 @@ class SparseCholesky:
     autograd's own check of saved tensors does not see it: pass a fresh tensor or call ``invalidate()`` then.
     """
 
-    def __init__(self, A_or_pattern, nb=256, reproducible=False, batch_blocked=False, **analyse_kw):
+    def __init__(self, A_or_pattern, nb=256, reproducible=False, batch_blocked=False, batch_reproducible=False,
+                 **analyse_kw):
         if isinstance(A_or_pattern, (tuple, list)):
             n, ptr, row = A_or_pattern
         else:
@@ -64,7 +73,10 @@ class SparseCholesky:
         flags = int(analyse_kw.pop("engine_flags", 0)) | (4096 if self.reproducible else 0)
         self.f = Factorization(n, ptr, row, nb=nb, engine_flags=flags, **analyse_kw)
         self.n, self.nnz = self.f.n, self.f.nnz
-        self.device = None            # the device of the first tensor; the engine is created there
+        self.batch_reproducible = bool(batch_reproducible)
+        if self.batch_reproducible:   # (off: the handle never hears of the switch)
+            self.f.set_batch_reproducible(True)
+        self.device = None           # the device of the first tensor; the engine is created there
         self._stream = None
         self._weight = None           # 2 - delta_ij per entry of val
         self._C = None                # set_constraints: (the rows, whether the handle has them)
@@ -237,8 +249,8 @@ class SparseCholesky:
 
     def solve_batch(self, vals, B):
         """X_b = A(vals[b])^-1 B[b].  vals: (nbatch, nnz), B: (nbatch, n, nrhs); differentiable in both"""
-        if self.reproducible:
-            raise NotImplementedError("solve_batch: the batch has no deterministic form (reproducible=True)")
+        if self.reproducible and not self.batch_reproducible:
+            raise NotImplementedError("solve_batch" + _NO_DET_BATCH)
         self._values(vals, "vals", (None, self.nnz))
         self._tensor(B, "B", (vals.shape[0], self.n, None), vals.device)
         self._enter(vals)
@@ -246,8 +258,8 @@ class SparseCholesky:
 
     def logdet_batch(self, vals):
         """log det A(vals[b]), shape (nbatch,); differentiable in vals"""
-        if self.reproducible:
-            raise NotImplementedError("logdet_batch: the batch has no deterministic form (reproducible=True)")
+        if self.reproducible and not self.batch_reproducible:
+            raise NotImplementedError("logdet_batch" + _NO_DET_BATCH)
         self._values(vals, "vals", (None, self.nnz))
         self._enter(vals)
         return _LogDetBatch.apply(self, vals)
@@ -318,8 +330,8 @@ class SparseCholesky:
         in the same launches: the blocked batch solve, then the correction, in one library call.  vals: (nbatch,
         nnz), B: (nbatch, n, nrhs); e: None (zeros) or (k,).  Returns (x*, lambda) of shapes (nbatch, n, nrhs) and
         (nbatch, k, nrhs).  WITHOUT GRADIENTS (see set_constraints)."""
-        if self.reproducible:
-            raise NotImplementedError("solve_constrained_batch: the batch has no deterministic form (reproducible=True)")
+        if self.reproducible and not self.batch_reproducible:
+            raise NotImplementedError("solve_constrained_batch" + _NO_DET_BATCH)
         self._values(vals, "vals", (None, self.nnz))
         self._tensor(B, "B", (vals.shape[0], self.n, None), vals.device)
         self._enter(vals)
@@ -417,8 +429,8 @@ class SparseCholesky:
         pathwise gradient).  reproducible=True raises NotImplementedError, like the other batch operations.
         constrained=True (kind "precision" only): draws of N(mean_b, A(vals[b])^-1) | C x = e for the rows of
         set_constraints, e None (zeros) or (k,)."""
-        if self.reproducible:
-            raise NotImplementedError("sample_batch: the batch has no deterministic form (reproducible=True)")
+        if self.reproducible and not self.batch_reproducible:
+            raise NotImplementedError("sample_batch" + _NO_DET_BATCH)
         if constrained and kind != "precision":
             raise ValueError("sample_batch: constrained=True needs kind='precision'")
         if e is not None and not constrained:
@@ -552,8 +564,8 @@ class SparseCholesky:
         "Ltinv".  vals: (nbatch, nnz), X: (nbatch, n, nvec), the vectors in the layout of ``factor_apply``.
         Differentiable in vals and X; the backward pass is one library call for the gradient of X, then seed passes
         of 32 vectors per member, ONE sweep of the batch's factor adjoint and its reader for vals."""
-        if self.reproducible:
-            raise NotImplementedError("factor_apply_batch: the batch has no deterministic form (reproducible=True)")
+        if self.reproducible and not self.batch_reproducible:
+            raise NotImplementedError("factor_apply_batch" + _NO_DET_BATCH)
         if op not in self._FACTOR_OPS:
             raise ValueError(f"op: expected one of {self._FACTOR_OPS}, got {op!r}")
         self._values(vals, "vals", (None, self.nnz))
@@ -565,8 +577,8 @@ class SparseCholesky:
         """``sample_batch`` with the pathwise gradient: the same bits forward, differentiable in vals and mean
         ((n,) or (nbatch, n); added outside the Function, its gradient is autograd's).  The noise is not kept: the
         backward pass draws it again (covariance) or does not need it (precision)."""
-        if self.reproducible:
-            raise NotImplementedError("rsample_batch: the batch has no deterministic form (reproducible=True)")
+        if self.reproducible and not self.batch_reproducible:
+            raise NotImplementedError("rsample_batch" + _NO_DET_BATCH)
         self._values(vals, "vals", (None, self.nnz))
         if mean is not None:
             if isinstance(mean, torch.Tensor) and mean.dim() == 2:
