@@ -1221,6 +1221,72 @@ class Factorization:
         self._call("spllt_hip_release_batch_repro", self.fkeep)
         return self
 
+    # ---- update / downdate of the factors of a batch (include/spllt_hip_updown_batch.h) -----
+    def _updown_batch_pattern(self, W, where):
+        """W (scipy sparse n x k) as the 1-based CSC arrays of the C interface and its values, in canonical CSC order
+        (rows ascending within a column, duplicates summed); stored zeros stay: W gives the PATTERN"""
+        import scipy.sparse as sp
+        if not sp.issparse(W):
+            raise ValueError(f"{where}: W must be a scipy sparse n x k matrix (it gives the pattern)")
+        if W.shape[0] != self.n:
+            raise ValueError(f"{where}: W has {W.shape[0]} rows, n = {self.n}")
+        W = sp.csc_matrix(W, dtype=np.float64, copy=True)
+        W.sum_duplicates()
+        W.sort_indices()
+        return (W.shape[1], np.ascontiguousarray(W.indptr + 1, dtype=np.int32),
+                np.ascontiguousarray(np.append(W.indices + 1, 0), dtype=np.int32),
+                np.ascontiguousarray(W.data, dtype=np.float64))
+
+    def update_batch(self, W, vals=None, downdate=False):
+        """spllt_hip_updown_batch: the factors of A_b + W_b W_b^T (downdate: A_b - W_b W_b^T) in place of those of the
+        last batch.  W (scipy sparse, n x k) gives the ONE pattern; vals of shape (B, nnz(W)) holds member b's values
+        in W's CSC order (rows ascending within a column); vals=None: W's own values for every member.  The pattern
+        of every column must be a clique of the analysed matrix (include/spllt_hip.h, spllt_hip_updown).  Returns 0,
+        or -20 when a member is not positive definite (batch_status() tells which; the others are served)."""
+        where = "update_batch"
+        k, ptr, row, wdata = self._updown_batch_pattern(W, where)
+        nent = int(wdata.size)
+        nb = self._batch_count()
+        if vals is None:
+            vals = np.tile(wdata, (max(nb, 1), 1))
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if vals.ndim != 2 or vals.shape[1] != nent:
+            raise ValueError(f"{where}: vals must have shape (B, nnz(W)) = (B, {nent}), not {vals.shape}")
+        if nb > 0 and vals.shape[0] != nb:
+            raise ValueError(f"{where}: vals holds values for {vals.shape[0]} members, the last batch has {nb}")
+        if nent == 0:
+            vals = np.zeros((vals.shape[0], 1))
+        return self._call("spllt_hip_updown_batch", self.fkeep, k, _ip(ptr), _ip(row), C.c_void_p(vals.ctypes.data),
+                          int(vals.shape[1]), -1 if downdate else 1, ok=self._BATCH_OK)
+
+    def update_batch_dev(self, W, vals_ptr, ldw, downdate=False):
+        """spllt_hip_updown_batch_dev: the same with the values in HBM (integer device pointer; member b's value of
+        CSC position e at ptr + (b * ldw + e) doubles, ldw >= nnz(W)).  The library reads the values of EVERY member of
+        the last batch.  Returns 0 or -20."""
+        k, ptr, row, wdata = self._updown_batch_pattern(W, "update_batch_dev")
+        if int(ldw) < int(wdata.size):
+            raise ValueError(f"update_batch_dev: ldw = {ldw} < nnz(W) = {wdata.size}")
+        return self._call("spllt_hip_updown_batch_dev", self.fkeep, k, _ip(ptr), _ip(row), C.c_void_p(vals_ptr), int(ldw),
+                          -1 if downdate else 1, ok=self._BATCH_OK)
+
+    def updown_batch_info(self):
+        """of the last update_batch(): block columns visited, entries of L in them per member, kernel launches, passes,
+        members served, members that failed in that call"""
+        out = np.zeros(6, dtype=np.int64)
+        self._call("spllt_hip_updown_batch_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        return dict(zip(("bcols", "entries", "launches", "passes", "served", "failed"), (int(v) for v in out)))
+
+    def updown_batch_device_ms(self):
+        """spllt_hip_updown_batch_time: device time of the last update_batch(), first scatter to last kernel"""
+        v = C.c_double()
+        self._call("spllt_hip_updown_batch_time", self.fkeep, C.byref(v))
+        return v.value
+
+    def release_updown_batch(self):
+        """The work arrays of update_batch back to the device pool."""
+        self._call("spllt_hip_release_updown_batch", self.fkeep)
+        return self
+
     # ---- the product and the refined solves for the members of a batch (include/spllt_hip_batch_refine.h) -----
     def _batch_values(self, vals, where):
         vals = np.ascontiguousarray(vals, dtype=np.float64)

@@ -35,6 +35,7 @@
 #include "spllt_hip_batch_repro.h"
 #include "spllt_hip_constrain.h"
 #include "spllt_hip_constrain_batch.h"
+#include "spllt_hip_updown_batch.h"
 #include "symbolic.hpp"
 
 using namespace spx;
@@ -1611,6 +1612,62 @@ int spllt_hip_updown_info(void* fkeep, int64_t out[4]) {
   return 0;
 }
 
+// ---- low-rank update / downdate of the factors of a batch (spllt_hip_updown_batch.h) ----------------
+static int updown_batch_impl(void* fkeep, int k, const int* wptr, const int* wrow, const double* wval, int64_t ldw,
+                             int sign, bool dev, const char* what) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  std::vector<int> plan, first;
+  std::string why;
+  const char* bad = nullptr;
+  // (the argument checks of spllt_hip_updown, in its order, then the member stride)
+  if (sign != 1 && sign != -1) bad = "sign is not +1 or -1";
+  else if (k > 0 && !wval) bad = "the array of values is null";
+  else if (build_updown_plan(*f->S, k, wptr, wrow, plan, &first, &why)) bad = why.c_str();
+  else if (k > 0 && ldw < (int64_t)wptr[k] - 1) bad = "ldw < wptr[k] - 1";
+  const int nb = (f->eng && !f->dead) ? f->eng->batch_count() : 0;
+  for (int b = 0; !bad && !dev && k > 0 && b < nb; ++b)
+    for (int e = wptr[0] - 1; !bad && e < wptr[k] - 1; ++e)
+      if (!std::isfinite(wval[(int64_t)b * ldw + e])) bad = "a value of W is not finite";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  const int rc = f->eng->updown_batch(k, wptr, wrow, wval, ldw, dev, sign, plan, first);
+  if (!plan.empty() && rc != SPLLT_ERROR_ALLOCATION && rc != SPLLT_ERROR_PARAMETER && rc != SPLLT_ERROR_UNIMPLEMENTED)
+    ++f->serial[1];   // (the call reached the device: the members' factors have changed, a failed one included)
+  if (rc == SPLLT_ERROR_NOT_POSDEF) {   // -20 of the batch calls
+    const bool fresh = f->eng->updown_batch_info()[5] > 0;   // (a downdate of THIS call failed: said aloud, as spllt_hip_updown does)
+    fail(f, what, fresh ? f->eng->feature_error()
+                        : std::string("the members that are not positive definite were skipped, the others are "
+                                      "modified (spllt_hip_batch_status)"), rc);
+    if (fresh) std::fprintf(stderr, "spllt-hip: %s\n", f->last_error.c_str());
+    return rc;
+  }
+  return leave(f, rc);
+}
+
+int spllt_hip_updown_batch(void* fkeep, int k, const int* wptr, const int* wrow, const double* wval_host, int64_t ldw,
+                           int sign) {
+  return updown_batch_impl(fkeep, k, wptr, wrow, wval_host, ldw, sign, false, "spllt_hip_updown_batch");
+}
+
+int spllt_hip_updown_batch_dev(void* fkeep, int k, const int* wptr, const int* wrow, const double* wval_dev, int64_t ldw,
+                               int sign) {
+  return updown_batch_impl(fkeep, k, wptr, wrow, wval_dev, ldw, sign, true, "spllt_hip_updown_batch_dev");
+}
+
+int spllt_hip_updown_batch_info(void* fkeep, int64_t out[6]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 6; ++i) out[i] = (f->eng && !f->dead) ? f->eng->updown_batch_info()[i] : 0;
+  return 0;
+}
+
+int spllt_hip_updown_batch_time(void* fkeep, double* device_ms) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !device_ms) return SPLLT_ERROR_PARAMETER;
+  *device_ms = (f->eng && !f->dead) ? f->eng->updown_batch_device_ms() : 0.0;
+  return 0;
+}
+
 // ---- sparse right-hand sides and selected outputs --------------------------------------------------
 // the ladder of the sparse solves; out: the output array, ld against the number of wanted entries (gram: against k)
 static int solve_sparse_enter(Fkeep* f, const char* what, int k, const int* bptr, const int* brow, const double* bval,
@@ -2035,6 +2092,7 @@ int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::relea
 int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::release_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_solve_many_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_many_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_updown_batch(void* fkeep) { return release(fkeep, &Engine::release_updown_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_batch_repro(void* fkeep) { return release(fkeep, &Engine::release_batch_repro, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_refine_batch(void* fkeep) { return release(fkeep, &Engine::release_refine_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_constraints_batch(void* fkeep) { return release(fkeep, &Engine::release_constraints_batch, WAIT_IGNORE | LENIENT); }

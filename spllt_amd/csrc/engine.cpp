@@ -18,6 +18,7 @@
 
 #include "engine_detail.hpp"
 #include "kernels.hpp"
+#include "updown_stage.hpp"
 
 namespace spx {
 
@@ -1900,6 +1901,167 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   return 0;
 }
 
+// ---- low-rank update / downdate of the factors of a batch ---------------------------------------------
+// The launches of Engine::updown with every launch carrying all members (batch_updown.hip).  The units are the
+// batch's own (bt_.sprog, pw = cb = 64): slot p of a block column at dinv_off + 4096 p with row stride = the
+// panel's width, which is what k_batch_chain writes (ldw = ce - cs = pn, panels of 64) and what ud_gen_block
+// advances by (pn x pn per panel, every panel but the last 64 wide).
+void Engine::drop_updown_batch() {
+  give_back(bud_.W, bud_.coef, bud_.flag);
+  bud_.capacity = 0;
+  for (int64_t& v : bud_.info) v = 0;
+  bud_.device_ms = 0.0;
+}
+
+int Engine::release_updown_batch() {
+  int rc;
+  if (!enter_release(bud_.W || bud_.coef || bud_.flag, "batch update release", &rc)) return rc;
+  drop_updown_batch();
+  return 0;
+}
+
+int Engine::updown_batch(int k, const int* wptr, const int* wrow, const double* wval, int64_t ldw, bool dev, int sign,
+                         const std::vector<int>& all, const std::vector<int>& first) {
+  feature_err_.clear();
+  if (status_) return status_;
+  if (opt_.nranks > 1) return -98;
+  if (k < 0 || (k > 0 && (!wptr || !wrow || !wval)) || (sign != 1 && sign != -1) || (int)first.size() != k) return -10;
+  if (pending_ || bt_.nbatch <= 0) return -10;
+  if (k > 0 && ldw < (int64_t)wptr[k] - 1) return -10;
+  const Symbolic& S = *S_;
+  const int nbatch = bt_.nbatch;
+  for (int64_t& v : bud_.info) v = 0;
+  bud_.device_ms = 0.0;
+  if (all.empty()) return 0;         // k = 0, or every column empty
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  UpdownStage st;
+  stage_updown(k, wptr, wrow, S.order.data(), first.data(), kUpdownVec,
+               [&](const int* pf, int nc, std::vector<int>& plan) { updown_paths(S, pf, nc, plan); }, st);
+  int maxw = 1;
+  for (const BlockCol& B : S.bcols) maxw = std::max(maxw, B.width);
+  const int64_t wstride = (int64_t)kUpdownVec * std::max(1, S.n), cstride = (int64_t)maxw * kUpdownVec * 3;
+  const int64_t nent = (int64_t)wptr[k] - 1;   // (the members' values packed: row b of the staged copy)
+  const size_t pb = sizeof(int64_t) * st.pos.size(), eb = sizeof(int) * st.ent.size();
+  const size_t vb = dev ? 0 : sizeof(double) * (size_t)nbatch * (size_t)nent;
+  int64_t* d_pos = nullptr;
+  int* d_ent = nullptr;
+  double* d_val = nullptr;
+  {
+    // a failure leaves the batch and the single factor usable, and nothing of this call allocated; a larger batch
+    // takes the three per-member arrays again, together
+    auto t = take();
+    if (bud_.W && nbatch > bud_.capacity) drop_updown_batch();
+    const bool fresh = !bud_.W;
+    const size_t wbytes = sizeof(double) * (size_t)wstride * (size_t)nbatch;
+    if (fresh) {
+      t(&bud_.W, wbytes);
+      t(&bud_.coef, sizeof(double) * (size_t)cstride * (size_t)nbatch);
+      t(&bud_.flag, sizeof(int) * (size_t)nbatch);
+      if (t.ok()) t.check(hipMemsetAsync(bud_.W, 0, wbytes, stream_));
+    }
+    t(&d_pos, pb);
+    t(&d_ent, eb);
+    if (!dev) t(&d_val, vb);
+    if (t.ok()) t.check(hipMemcpyAsync(d_pos, st.pos.data(), pb, hipMemcpyHostToDevice, stream_));
+    if (t.ok()) t.check(hipMemcpyAsync(d_ent, st.ent.data(), eb, hipMemcpyHostToDevice, stream_));
+    if (!t.ok()) {
+      (void)hipGetLastError();
+      (void)sync_stream(stream_, "batch update staging");   // (before the roll-back returns what a copy may still write)
+      feature_err_ = "batch update: not enough device memory for the work arrays of " + std::to_string(nbatch) +
+                     " members (" + std::to_string(wbytes >> 10) + " KiB), the coefficient scratch and the entries of W: " +
+                     hipGetErrorString(t.error());
+      return alloc_code(t.error());
+    }
+    t.commit();
+    if (fresh) {
+      bud_.capacity = nbatch;
+      bud_.wstride = wstride;
+      bud_.cstride = cstride;
+    }
+  }
+  const double* vd = wval;
+  int64_t ldv = ldw;
+  if (!dev) {
+    if (int rc = copy_vectors_to_device(d_val, wval, ldw, nbatch, "batch update values H2D", nent)) {
+      give_back(d_val, d_ent, d_pos);
+      return rc;
+    }
+    vd = d_val;
+    ldv = nent;
+  }
+  BupdownView s;
+  s.v = batch_view();
+  s.Wd = bud_.W;
+  s.coef = bud_.coef;
+  s.udflag = bud_.flag;
+  s.wstride = bud_.wstride;
+  s.cstride = bud_.cstride;
+  int64_t launches = 0;
+  bool fits = true;
+  auto count = [&](int made) { if (made < 0) fits = false; else launches += made; };
+  for (int p = 0; p < st.npass && fits; ++p) {
+    const int nc = st.pass_nc[(size_t)p];
+    if (p == 0) (void)hipEventRecord(ev0_, stream_);
+    count(launch_bupdown_scatter(stream_, s, d_pos + st.pass_ptr[(size_t)p], d_ent + st.pass_ptr[(size_t)p],
+                                 st.pass_ptr[(size_t)p + 1] - st.pass_ptr[(size_t)p], vd, ldv, p == 0));
+    for (int64_t i = st.plan_ptr[(size_t)p]; i < st.plan_ptr[(size_t)p + 1] && fits; ++i) {
+      const SolveUnit& u = bt_.sprog.units[(size_t)st.plan[(size_t)i]];
+      count(launch_bupdown_gen(stream_, s, u, sign, nc));
+      count(launch_bupdown_apply(stream_, s, u, d_rlist_, sign, nc));
+    }
+  }
+  hipError_t le = hipGetLastError();
+  if (le == hipSuccess) le = hipEventRecord(ev1_, stream_);
+  bud_.hflag_pending.assign((size_t)nbatch, INT_MAX);
+  if (le == hipSuccess)
+    le = hipMemcpyAsync(bud_.hflag_pending.data(), bud_.flag, sizeof(int) * (size_t)nbatch, hipMemcpyDeviceToHost, stream_);
+  int rc = sync_stream(stream_, "batch update sync");
+  give_back(d_val, d_ent, d_pos);
+  bt_.z_valid = false;
+  bt_.g_state = FADJ_UNSEEDED;
+  ++bt_.generation;
+  if (le != hipSuccess || rc || !fits) {
+    // the sweep did not finish: the arenas are half modified and the work arrays may not be zero
+    bt_.nbatch = 0;
+    bt_.hflag.clear();
+    drop_updown_batch();
+    if (le != hipSuccess) return fail(kErrHip, "batch update launch", le);
+    if (rc) return rc;
+    feature_err_ = "batch update: a block column has more strips for ONE member than a grid holds; the batch is left "
+                   "without members";
+    return -99;
+  }
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, ev0_, ev1_) == hipSuccess) bud_.device_ms = ms;
+  // the words of this call into the batch's flags, on the host and on the device (the scatter of a later pass has
+  // merged what failed before it; what failed in the last pass has not been merged yet)
+  int64_t served = 0, failed = 0;
+  for (int b = 0; b < nbatch; ++b) {
+    if (bt_.hflag[(size_t)b] != INT_MAX) continue;
+    ++served;
+    if (bud_.hflag_pending[(size_t)b] != INT_MAX) {
+      bt_.hflag[(size_t)b] = bud_.hflag_pending[(size_t)b];
+      ++failed;
+    }
+  }
+  if (failed) {
+    HIPCHK(hipMemcpyAsync(bt_.flag, bt_.hflag.data(), sizeof(int) * (size_t)nbatch, hipMemcpyHostToDevice, stream_),
+           "batch update flags H2D");
+    if ((rc = sync_stream(stream_, "batch update flags sync"))) return rc;
+  }
+  bud_.info[0] = (int64_t)all.size();
+  for (int b : all) bud_.info[1] += (int64_t)S.bcols[(size_t)b].nrow * S.bcols[(size_t)b].width;
+  bud_.info[2] = launches;
+  bud_.info[3] = st.npass;
+  bud_.info[4] = served;
+  bud_.info[5] = failed;
+  if (failed)
+    feature_err_ = "batch downdate: " + std::to_string(failed) + " of " + std::to_string(nbatch) +
+                   " members are not positive definite after the modification; they are skipped until the next "
+                   "factor_batch (spllt_hip_batch_status)";
+  return batch_failed();
+}
+
 // ---- batched factorization ------------------------------------------------------------------------
 int build_batch_program(const Symbolic& S, Program& P, std::string* why, bool deterministic) {
   ScheduleOptions so;
@@ -2293,7 +2455,7 @@ int Engine::release_batch() {
   bt_.g_state = FADJ_UNSEEDED;
   bt_.fa_launches = 0;
   // (the batch's own storage, and what its features say of theirs)
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brp_.swscratch && !brf_held() && !bcn_.C) { bt_.nbatch = 0; return 0; }
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brp_.swscratch && !brf_held() && !bcn_.C && !bud_.W) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
@@ -2301,6 +2463,7 @@ int Engine::release_batch() {
   drop_solve_repro_batch();   // (... and the scratch of its reproducible form)
   drop_refine_batch();        // (... and those of the refined solves)
   drop_constraints_batch();   // (... and the constraints of the batch, C included)
+  drop_updown_batch();        // (... and the work arrays of its update / downdate)
   give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, bt_.Y, bt_.stage, bt_.Z, bt_.G, bt_.siscratch, brp_.fscratch);
   brp_.f_capacity = 0;
   brp_.last_det = false;

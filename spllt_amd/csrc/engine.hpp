@@ -444,6 +444,25 @@ class Engine {
   int fadj_sweep_batch(double* gval, int64_t ldout, bool dev);
   int batch_adjoint_launches() const { return bt_.fa_launches; }   // of the last sweep, reader included
   int release_factor_adjoint_batch();
+  // ---- low-rank update / downdate of the factors of the LAST batch (batch_updown.hip; include/
+  // spllt_hip_updown_batch.h): the members' arenas afterwards hold the factors of P (A_b + sign W_b W_b^T) P^T, in
+  // place, their dinv slots rebuilt -- every sweep over the batch then works on the modified factors.  ONE pattern
+  // (wptr / wrow, host, validated by the caller: build_updown_plan gives all / first), member b's values at wval + b *
+  // ldw (dev: a device pointer, read in place; else staged).  Per pass of up to kUpdownVec columns one scatter launch,
+  // then per block column of the pass's plan a generate launch of one workgroup per member and, where it has rows
+  // below, an apply launch of (strips x members) workgroups: the launch count does not depend on nbatch.  A member
+  // whose downdate meets a non-positive pivot is flagged in the batch's own flags (batch_flags()) and skipped by every
+  // batch consumer until the next factor_batch; the call serves the others and returns -20.  A call that reached the
+  // device marks the members' inverses stale, their adjoints unseeded and bumps the batch generation.  Storage (work
+  // arrays, coefficient scratch, one word per member): ONE transaction on first use, kept until release_batch /
+  // release_updown_batch.  A launch or wait that fails mid-sweep leaves the batch without members.
+  int updown_batch(int k, const int* wptr, const int* wrow, const double* wval, int64_t ldw, bool dev, int sign,
+                   const std::vector<int>& all, const std::vector<int>& first);
+  // of the last updown_batch(): block columns visited, entries of L in them per member, kernel launches, passes,
+  // members served, members that failed in that call
+  const int64_t* updown_batch_info() const { return bud_.info; }
+  double updown_batch_device_ms() const { return bud_.device_ms; }
+  int release_updown_batch();
   double* device_L() { return d_L_; }
   hipStream_t stream() { return stream_; }
   // entries of the ledger of device buffers and their bytes (host state only)
@@ -865,6 +884,19 @@ class Engine {
   double ud_device_ms_ = 0.0;
   double* d_udW_ = nullptr;        // n x kUpdownVec doubles, zero between calls
   double* d_udcoef_ = nullptr;     // (widest block column) x kUpdownVec x 3 doubles + the flag word
+  // ... of the batch: per member a work array (wstride = kUpdownVec n doubles, zero between calls), a coefficient
+  // scratch (cstride doubles) and a word; all three or none
+  struct BudState {
+    double* W = nullptr;
+    double* coef = nullptr;
+    int* flag = nullptr;
+    int capacity = 0;                // members the storage holds
+    int64_t wstride = 0, cstride = 0;
+    int64_t info[6] = {0, 0, 0, 0, 0, 0};
+    double device_ms = 0.0;
+    std::vector<int> hflag_pending;  // destination of the words' D2H copy (outlives a wait that fails)
+  } bud_;
+  void drop_updown_batch();
   // selected inversion (tables uploaded once per pattern, on first use)
   int prepare_selinv();
   void release_buffer(void* p);

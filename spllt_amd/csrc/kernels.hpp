@@ -300,6 +300,33 @@ void launch_updown_gen(hipStream_t st, const SolveUnit& u, double* L, double* di
 // the rows below the square (nothing is launched when there are none)
 void launch_updown_apply(hipStream_t st, const SolveUnit& u, double* L, const int* rlist, double* Wd, const double* coef,
                          int sign, int nv);
+// ---- the same for the members of a batch (batch_updown.hip; the bodies of updown.hip per member: ud_body.hpp) ----
+// The batch's view (arenas, dinv scratch, the batch's OWN flags) plus member b's work array Wd + b * wstride
+// (kUpdownVec n doubles, zero between calls), coefficient scratch coef + b * cstride ((widest block column) x
+// kUpdownVec x 3 doubles) and word udflag[b]: INT_MAX, or the smallest pivot position + 1 at which a downdate of this
+// call failed.  v.flag[b] is merged from udflag[b] by the scatter launch of the NEXT pass (and by the host after
+// the last one): it does not change while the block columns of a pass run, so the two exits below are uniform
+// per (pass, member).  A generate workgroup leaves at once, before it reads L, when its member's v.flag is set, or
+// when all kUpdownVec slots of its Wd at the block column's own columns compare equal to zero (the block column is
+// an identity for that member); it then stores kBupdownSkip in coef[b * cstride], which the apply workgroups of
+// that (block column, member) read.  Every wrapper returns the launches made (the members split into ranges as in
+// batch_split.hpp), -1 when one member's work items overflow a grid.
+struct BupdownView {
+  BatchView v;
+  double* Wd;
+  double* coef;
+  int* udflag;
+  int64_t wstride, cstride;
+};
+constexpr double kBupdownSkip = -1.0;   // (c = r / d of a rotation is positive)
+// Wd[b * wstride + pos[i]] = wval[b * ldw + ent[i]], i < count, for every member whose flags are clear; member b's
+// thread 0 first merges udflag[b] into v.flag[b] (reset: sets udflag[b] = INT_MAX instead -- the first pass)
+int launch_bupdown_scatter(hipStream_t st, const BupdownView& s, const int64_t* pos, const int* ent, int64_t count,
+                           const double* wval, int64_t ldw, bool reset);
+// one workgroup per member: the diagonal square of block column u (a SolveUnit of the batch's solve program, pw = 64)
+int launch_bupdown_gen(hipStream_t st, const BupdownView& s, const SolveUnit& u, int sign, int nv);
+// (strips x members) workgroups: the rows below the square; 0 when there are none
+int launch_bupdown_apply(hipStream_t st, const BupdownView& s, const SolveUnit& u, const int* rlist, int sign, int nv);
 // ---- reproducible substitution (solve_repro.hip): launch_solve without atomic adds ------------------
 // The RsolveTables (schedule.hpp) on the device and the scratch: vector q of a sweep uses scratch + q * stride,
 // stride >= max(frows, bsize).
