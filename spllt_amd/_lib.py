@@ -263,6 +263,16 @@ _BATCH_UPDOWN = {
     "spllt_hip_updown_batch_time": (i32, [vp, dp]),
     "spllt_hip_release_updown_batch": (i32, [vp]),
 }
+# every symbol declared in include/spllt_hip_solve_sparse_batch.h: sparse right-hand sides, selected outputs and
+# B^T A_b^-1 B for the members of a batch.  A table of its own for the same reason.
+_SOLVE_SPARSE_BATCH = {
+    "spllt_hip_solve_sparse_batch": (i32, [vp, i32, ip, ip, dp, i64, i32, ip, dp, i64, i32]),
+    "spllt_hip_solve_sparse_batch_dev": (i32, [vp, i32, ip, ip, dp, i64, i32, ip, vp, i64, i32]),
+    "spllt_hip_gram_sparse_batch": (i32, [vp, i32, ip, ip, dp, i64, dp, i64]),
+    "spllt_hip_gram_sparse_batch_dev": (i32, [vp, i32, ip, ip, dp, i64, vp, i64]),
+    "spllt_hip_solve_sparse_batch_info": (i32, [vp, i64p]),
+    "spllt_hip_release_solve_sparse_batch": (i32, [vp]),
+}
 del u32
 del vp, vpp, i32, i64, u64, f64, cstr, long, ip, i64p, dp, fp, longp, ipp, dpp, opt, inf   # (names of the table only)
 IFACE_SYMBOLS = list(_IFACE)
@@ -275,6 +285,7 @@ CONSTRAIN_SYMBOLS = list(_CONSTRAIN)
 CONSTRAIN_BATCH_SYMBOLS = list(_CONSTRAIN_BATCH)
 BATCH_REPRO_SYMBOLS = list(_BATCH_REPRO)
 BATCH_UPDOWN_SYMBOLS = list(_BATCH_UPDOWN)
+SOLVE_SPARSE_BATCH_SYMBOLS = list(_SOLVE_SPARSE_BATCH)
 
 _lib = None
 
@@ -290,7 +301,7 @@ def load():
             "g.build()'` or `make -C spllt_amd/csrc`. spllt_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for table in (PROTOTYPES, _BATCH_MULT, _BATCH_SOLVE_MANY, _BATCH_ADJOINT, _BATCH_REFINE, _CONSTRAIN, _CONSTRAIN_BATCH,
-                  _BATCH_REPRO, _BATCH_UPDOWN):
+                  _BATCH_REPRO, _BATCH_UPDOWN, _SOLVE_SPARSE_BATCH):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

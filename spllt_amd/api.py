@@ -162,7 +162,7 @@ class Factorization:
         raw = np.zeros(max(nbytes, 1), dtype=np.uint8)
         self.lib.spllt_hip_program_get(self.fkeep, name.encode(), raw.ctypes.data, nbytes)
         raw = raw[:nbytes]
-        if name == "solve_sparse_host_us":
+        if name in ("solve_sparse_host_us", "solve_sparse_batch_host_us"):
             return int(raw.view(np.int64)[0])
         if name == "owned":              # entries of the engine's ledger of device buffers, their bytes
             return raw.view(np.int64)
@@ -170,6 +170,8 @@ class Factorization:
             return raw.view(np.int64)
         if name in ("matvec_col", "matvec_src"):
             return raw.view(np.int32)
+        if name.startswith("bsolve_"):   # the batch's substitution program: the layouts of "solve_*"
+            name = name[1:]
         if name.startswith("batch_"):    # the batch program: the layouts of the unprefixed names
             name = name[len("batch_"):]
             if name.startswith("det_"):  # ... and those of its deterministic form
@@ -1285,6 +1287,121 @@ class Factorization:
     def release_updown_batch(self):
         """The work arrays of update_batch back to the device pool."""
         self._call("spllt_hip_release_updown_batch", self.fkeep)
+        return self
+
+    # ---- sparse right-hand sides for the members of a batch (include/spllt_hip_solve_sparse_batch.h) -----
+    solve_sparse_batch_status = None     # return value (0 or -20) of the last host call of this family
+
+    def _sparse_batch_columns(self, B, vals, where):
+        """B (scipy sparse n x k) as the 1-based CSC arrays of the C interface, in canonical CSC order (rows ascending
+        within a column, duplicates summed; stored zeros stay: B gives the PATTERN), and (values, ldb): B's own for
+        every member (ldb 0) or vals of shape (nbatch, nnz(B)) in that order.  Refuses before any library call."""
+        import scipy.sparse as sp
+        if not sp.issparse(B):
+            raise ValueError(f"{where}: B must be a scipy sparse n x k matrix (it gives the pattern)")
+        if B.shape[0] != self.n:
+            raise ValueError(f"{where}: B has {B.shape[0]} rows, n = {self.n}")
+        B = sp.csc_matrix(B, dtype=np.float64, copy=True)
+        B.sum_duplicates()
+        B.sort_indices()
+        nent = int(B.data.size)
+        ptr = np.ascontiguousarray(B.indptr + 1, dtype=np.int32)
+        row = np.ascontiguousarray(np.append(B.indices + 1, 0), dtype=np.int32)
+        if vals is None:
+            return B.shape[1], ptr, row, np.ascontiguousarray(np.append(B.data, 0.0), dtype=np.float64), 0
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        if vals.ndim != 2 or vals.shape[1] != nent:
+            raise ValueError(f"{where}: vals must have shape (B, nnz(B)) = (B, {nent}), not {vals.shape}")
+        nb = self._batch_count()
+        if nb > 0 and vals.shape[0] != nb:
+            raise ValueError(f"{where}: vals holds values for {vals.shape[0]} members, the last batch has {nb}")
+        if nent == 0:
+            vals = np.zeros((vals.shape[0], 1))
+        return B.shape[1], ptr, row, vals, int(vals.shape[1])
+
+    def _wanted_checked(self, rows, where):
+        if rows is not None:
+            r = np.asarray(rows)
+            if r.ndim > 1 or (r.size and not np.issubdtype(r.dtype, np.integer)):
+                raise ValueError(f"{where}: rows must be a one-dimensional list of 0-based variables")
+            if r.size and (int(r.min()) < 0 or int(r.max()) >= self.n):
+                raise ValueError(f"{where}: a wanted row is outside [0, n)")
+        return self._wanted(rows)
+
+    def solve_sparse_batch(self, B, rows=None, job=0, vals=None):
+        """spllt_hip_solve_sparse_batch: A_b^-1 B_b (job 1: L_b^-1 P B_b, job 2: the backward sweep) for every member of
+        the last batch, at the 0-based variables `rows` (None: all n).  B (scipy sparse, n x k) gives the ONE pattern;
+        vals of shape (nbatch, nnz(B)) holds member b's values in B's CSC order, None: B's own for every member.
+        Returns (nbatch, len(rows) or n, k), a view whose columns are contiguous; a member that is not positive
+        definite is NaN (solve_sparse_batch_status is then -20)."""
+        where = "solve_sparse_batch"
+        if job not in (0, 1, 2):
+            raise ValueError(f"{where}: job must be 0, 1 or 2")
+        k, ptr, row, v, ldb = self._sparse_batch_columns(B, vals, where)
+        nsel, sel = self._wanted_checked(rows, where)
+        m = self.n if sel is None else nsel
+        nb = self._batch_count()
+        x = np.zeros((max(nb, 1), max(k, 1), max(m, 1)), dtype=np.float64)
+        self.solve_sparse_batch_status = self._call(
+            "spllt_hip_solve_sparse_batch", self.fkeep, k, _ip(ptr), _ip(row), _dp(v), ldb, nsel,
+            None if sel is None else _ip(sel), _dp(x), x.shape[2], job, ok=self._BATCH_OK)
+        # (a view: member b's column q is the contiguous x[b, q]; no second pass over nbatch * k * nout doubles)
+        return x[:nb, :k, :m].transpose(0, 2, 1)
+
+    def solve_sparse_batch_dev(self, B, x_dev_ptr, ldx, rows=None, job=0, vals=None):
+        """spllt_hip_solve_sparse_batch_dev: the same into device memory, column q of member b at
+        x[(b*k + q)*ldx .. + (len(rows) or n)); nothing else is written.  Returns 0 or -20."""
+        where = "solve_sparse_batch_dev"
+        k, ptr, row, v, ldb = self._sparse_batch_columns(B, vals, where)
+        nsel, sel = self._wanted_checked(rows, where)
+        if int(ldx) < (self.n if sel is None else nsel):
+            raise ValueError(f"{where}: ldx = {ldx} is smaller than the number of wanted entries")
+        return self._call("spllt_hip_solve_sparse_batch_dev", self.fkeep, k, _ip(ptr), _ip(row), _dp(v), ldb, nsel,
+                          None if sel is None else _ip(sel), C.c_void_p(x_dev_ptr), int(ldx), job, ok=self._BATCH_OK)
+
+    def gram_batch(self, B, vals=None):
+        """spllt_hip_gram_sparse_batch: B_b^T A_b^-1 B_b for every member, (nbatch, k, k), each exactly symmetric;
+        B and vals as in solve_sparse_batch."""
+        where = "gram_batch"
+        k, ptr, row, v, ldb = self._sparse_batch_columns(B, vals, where)
+        nb = self._batch_count()
+        G = np.zeros((max(nb, 1), max(k, 1), max(k, 1)), dtype=np.float64)
+        self.solve_sparse_batch_status = self._call("spllt_hip_gram_sparse_batch", self.fkeep, k, _ip(ptr), _ip(row), _dp(v),
+                                                    ldb, _dp(G), G.shape[2], ok=self._BATCH_OK)
+        # (member b's column j is row j of G[b]; the matrices are symmetric)
+        return np.ascontiguousarray(G[:nb, :k, :k].transpose(0, 2, 1))
+
+    def gram_batch_dev(self, B, g_dev_ptr, ldg, vals=None):
+        """spllt_hip_gram_sparse_batch_dev: G_b column-major at g + b*k*ldg doubles.  Returns 0 or -20."""
+        where = "gram_batch_dev"
+        k, ptr, row, v, ldb = self._sparse_batch_columns(B, vals, where)
+        if int(ldg) < k:
+            raise ValueError(f"{where}: ldg = {ldg} < k = {k}")
+        return self._call("spllt_hip_gram_sparse_batch_dev", self.fkeep, k, _ip(ptr), _ip(row), _dp(v), ldb,
+                          C.c_void_p(g_dev_ptr), int(ldg), ok=self._BATCH_OK)
+
+    def inverse_block_batch(self, i, j):
+        """A_b^-1[i][:, j] for every member and any 0-based index sets i, j, inside the pattern of L or not: sparse
+        solves with the unit columns e_j and the wanted rows i; (nbatch, len(i), len(j))."""
+        import scipy.sparse as sp
+        i = np.asarray(i, dtype=np.int64).ravel()
+        j = np.asarray(j, dtype=np.int64).ravel()
+        if ((i < 0) | (i >= self.n)).any() or ((j < 0) | (j >= self.n)).any():
+            raise ValueError("inverse_block_batch: index out of range")
+        E = sp.csc_matrix((np.ones(len(j)), (j, np.arange(len(j)))), shape=(self.n, len(j)))
+        return self.solve_sparse_batch(E, rows=i)
+
+    def solve_sparse_batch_info(self):
+        """of the last solve_sparse_batch / gram_batch: the fields of solve_sparse_info (block columns and doubles of
+        L per member, kernel launches, workgroups of the sweeps summed over the members), members served and flagged"""
+        out = np.zeros(8, dtype=np.int64)
+        self._call("spllt_hip_solve_sparse_batch_info", self.fkeep, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        return dict(zip(("fwd_bcols", "bwd_bcols", "fwd_entries", "bwd_entries", "launches", "workgroups", "served",
+                         "flagged"), (int(v) for v in out)))
+
+    def release_solve_sparse_batch(self):
+        """The staged tables, the output buffer and the gram workspaces of the batch back to the device pool."""
+        self._call("spllt_hip_release_solve_sparse_batch", self.fkeep)
         return self
 
     # ---- the product and the refined solves for the members of a batch (include/spllt_hip_batch_refine.h) -----

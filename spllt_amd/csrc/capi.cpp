@@ -35,6 +35,7 @@
 #include "spllt_hip_batch_repro.h"
 #include "spllt_hip_constrain.h"
 #include "spllt_hip_constrain_batch.h"
+#include "spllt_hip_solve_sparse_batch.h"
 #include "spllt_hip_updown_batch.h"
 #include "symbolic.hpp"
 
@@ -738,6 +739,8 @@ int spllt_hip_set_engine(void* fkeep, int panel_width, int tile, int flags) {
 //   batch_repro_poison=0|1  1 fills the scratch of the deterministic batch factorization and that of the reproducible
 //                           batch sweep with NaN before every factorization and every sweep
 //   solve_sparse_poison=0|1 1 fills the workspace of a sparse solve with NaN before its touched rows are zeroed
+//   solve_sparse_batch_poison=0|1 1 fills the whole workspace of the batch with NaN before a sparse solve of the batch
+//                           zeroes its touched rows
 //   fmult_poison=0|1        1 fills the scratch of the factor products (the batched ones too) with NaN before every
 //                           direction
 int spllt_hip_debug(const char* what) {
@@ -756,7 +759,8 @@ int spllt_hip_debug(const char* what) {
   static const struct { const char* name; void (*set)(bool); } kSwitches[] = {
       {"batch_selinv_fused", set_batch_selinv_fused}, {"batch_fadj_fused", set_batch_fadj_fused},
       {"rsolve_poison", set_rsolve_poison}, {"batch_repro_poison", set_batch_repro_poison},
-      {"solve_sparse_poison", set_solve_sparse_poison}, {"fmult_poison", set_fmult_poison}};
+      {"solve_sparse_poison", set_solve_sparse_poison}, {"fmult_poison", set_fmult_poison},
+      {"solve_sparse_batch_poison", set_solve_sparse_batch_poison}};
   for (const auto& s : kSwitches)
     if (name == s.name && (value == "0" || value == "1")) { s.set(value == "1"); return 0; }
   return -1;
@@ -1736,6 +1740,76 @@ int spllt_hip_solve_sparse_info(void* fkeep, int64_t out[6]) {
   return 0;
 }
 
+// ---- sparse right-hand sides for the members of a batch (spllt_hip_solve_sparse_batch.h) ------------
+// the argument rungs of solve_sparse_enter, then the member stride; the handle rungs of solve_many_batch_impl, then
+// the reproducible switch
+static int solve_sparse_batch_enter(Fkeep* f, const char* what, int k, const int* bptr, const int* brow,
+                                    const double* bval, int64_t ldb, int nsel, const int* sel, const void* out, int64_t ld,
+                                    int64_t ld_min, int job) {
+  if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
+  std::string why;
+  const char* bad = nullptr;
+  if (!out) bad = "the output array is null";
+  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
+  else if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) bad = why.c_str();
+  else if (k > 0 && bptr[k] > bptr[0] && !bval) bad = "the array of values is null";
+  else if (ld < ld_min) bad = "the leading dimension of the output is too small";
+  else if (k > 0 && ldb != 0 && ldb < (int64_t)bptr[k] - 1) bad = "ldb is neither 0 (one set of values for all members) nor >= bptr[k] - 1";
+  if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
+  if (f->eng->batch_reproducible())
+    return fail(f, what, "not available while the reproducible batch is switched on (spllt_hip_set_batch_reproducible): "
+                         "the filtered sweeps run the kernels that add with atomics", SPLLT_ERROR_UNIMPLEMENTED);
+  return 0;
+}
+
+static int solve_sparse_batch_impl(const char* what, void* fkeep, int k, const int* bptr, const int* brow,
+                                   const double* bval, int64_t ldb, int nsel, const int* sel, double* x, int64_t ldx, int job,
+                                   bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!sel || nsel < 0) { sel = nullptr; nsel = -1; }
+  const int64_t nout = !analysed(f) ? 0 : (sel ? nsel : f->S->n);
+  if (int rc = solve_sparse_batch_enter(f, what, k, bptr, brow, bval, ldb, nsel, sel, x, ldx, nout, job)) return rc;
+  return batch_mult_leave(f, what, f->eng->solve_sparse_batch(k, bptr, brow, bval, ldb, nsel, sel, x, ldx, job, dev),
+                          "the outputs of the members that are not positive definite are NaN");
+}
+
+int spllt_hip_solve_sparse_batch(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, int64_t ldb,
+                                 int nsel, const int* sel, double* x_host, int64_t ldx, int job) {
+  return solve_sparse_batch_impl("spllt_hip_solve_sparse_batch", fkeep, k, bptr, brow, bval, ldb, nsel, sel, x_host, ldx,
+                                 job, false);
+}
+
+int spllt_hip_solve_sparse_batch_dev(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, int64_t ldb,
+                                     int nsel, const int* sel, double* x_dev, int64_t ldx, int job) {
+  return solve_sparse_batch_impl("spllt_hip_solve_sparse_batch_dev", fkeep, k, bptr, brow, bval, ldb, nsel, sel, x_dev, ldx,
+                                 job, true);
+}
+
+static int gram_sparse_batch_impl(const char* what, void* fkeep, int k, const int* bptr, const int* brow, const double* bval,
+                                  int64_t ldb, double* g, int64_t ldg, bool dev) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (int rc = solve_sparse_batch_enter(f, what, k, bptr, brow, bval, ldb, -1, nullptr, g, ldg, k, 0)) return rc;
+  return batch_mult_leave(f, what, f->eng->gram_sparse_batch(k, bptr, brow, bval, ldb, g, ldg, dev),
+                          "the outputs of the members that are not positive definite are NaN");
+}
+
+int spllt_hip_gram_sparse_batch(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, int64_t ldb,
+                                double* g_host, int64_t ldg) {
+  return gram_sparse_batch_impl("spllt_hip_gram_sparse_batch", fkeep, k, bptr, brow, bval, ldb, g_host, ldg, false);
+}
+
+int spllt_hip_gram_sparse_batch_dev(void* fkeep, int k, const int* bptr, const int* brow, const double* bval, int64_t ldb,
+                                    double* g_dev, int64_t ldg) {
+  return gram_sparse_batch_impl("spllt_hip_gram_sparse_batch_dev", fkeep, k, bptr, brow, bval, ldb, g_dev, ldg, true);
+}
+
+int spllt_hip_solve_sparse_batch_info(void* fkeep, int64_t out[8]) {
+  Fkeep* f = static_cast<Fkeep*>(fkeep);
+  if (!f || !f->S || !out) return SPLLT_ERROR_PARAMETER;
+  for (int i = 0; i < 8; ++i) out[i] = (f->eng && !f->dead) ? f->eng->solve_sparse_batch_info()[i] : 0;
+  return 0;
+}
+
 // ---- readers of the batch ------------------------------------------------------
 int spllt_hip_get_factor_batch(void* fkeep, int member, double* out, int64_t count) {
   Fkeep* f = static_cast<Fkeep*>(fkeep);
@@ -2092,6 +2166,7 @@ int spllt_hip_release_refine(void* fkeep) { return release(fkeep, &Engine::relea
 int spllt_hip_release_batch(void* fkeep) { return release(fkeep, &Engine::release_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_factor_mult_batch(void* fkeep) { return release(fkeep, &Engine::release_factor_mult_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_solve_many_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_many_batch, WAIT_IGNORE | LENIENT); }
+int spllt_hip_release_solve_sparse_batch(void* fkeep) { return release(fkeep, &Engine::release_solve_sparse_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_updown_batch(void* fkeep) { return release(fkeep, &Engine::release_updown_batch, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_batch_repro(void* fkeep) { return release(fkeep, &Engine::release_batch_repro, WAIT_IGNORE | LENIENT); }
 int spllt_hip_release_refine_batch(void* fkeep) { return release(fkeep, &Engine::release_refine_batch, WAIT_IGNORE | LENIENT); }
@@ -2157,14 +2232,8 @@ static int64_t get_selinv(const SelinvProgram* sp, const std::string& q, const O
   return -1;
 }
 
-// "solve_*" and "rsolve_*": the substitution program (partition-aware like the factor program) and the tables of
-// the reproducible solve, which follow from it and the symbolic structure alone
-static int64_t get_solve(Fkeep* f, int cb, const std::string& k, const Out& o) {
-  SolveProgram sp;
-  std::vector<int> owner;
-  if (f->eo.nranks > 1) assign_owners(*f->S, f->eo.nranks, owner);
-  build_solve_program(*f->S, f->eo.pw > 0 ? f->eo.pw : kPanelMax, cb, sp, f->eo.nranks > 1 ? owner.data() : nullptr,
-                      f->eo.rank);
+// the tables of a substitution program under their "solve_*" names; -1: not one of them
+static int64_t get_solve_tables(const SolveProgram& sp, const std::string& k, const Out& o) {
   if (k == "solve_units") return o.bytes(sp.units);
   if (k == "solve_list") return o.bytes(sp.diag_list);
   if (k == "solve_tiles") return o.bytes(sp.tiles);
@@ -2174,6 +2243,19 @@ static int64_t get_solve(Fkeep* f, int cb, const std::string& k, const Out& o) {
       put(v, {(int64_t)l.kind, (int64_t)l.level, (int64_t)l.first, (int64_t)l.count});
     return o.bytes(v);
   }
+  return -1;
+}
+
+// "solve_*" and "rsolve_*": the substitution program (partition-aware like the factor program) and the tables of
+// the reproducible solve, which follow from it and the symbolic structure alone
+static int64_t get_solve(Fkeep* f, int cb, const std::string& k, const Out& o) {
+  SolveProgram sp;
+  std::vector<int> owner;
+  if (f->eo.nranks > 1) assign_owners(*f->S, f->eo.nranks, owner);
+  build_solve_program(*f->S, f->eo.pw > 0 ? f->eo.pw : kPanelMax, cb, sp, f->eo.nranks > 1 ? owner.data() : nullptr,
+                      f->eo.rank);
+  const int64_t got = get_solve_tables(sp, k, o);
+  if (got != -1) return got;
   if (k == "solve_split") {
     int64_t v[2] = {(int64_t)sp.fwd_nsub, (int64_t)sp.bwd_ntop};
     return o.bytes(v, sizeof v);
@@ -2285,6 +2367,10 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
     const int64_t v = f->eng ? f->eng->solve_sparse_host_us() : 0;
     return Out{cap >= (int64_t)sizeof v ? buf : nullptr, cap}.bytes(&v, sizeof v);
   }
+  if (k == "solve_sparse_batch_host_us") {   // (... of the last sparse solve or gram of the batch)
+    const int64_t v = (f->eng && !f->dead) ? f->eng->solve_sparse_batch_host_us() : 0;
+    return Out{cap >= (int64_t)sizeof v ? buf : nullptr, cap}.bytes(&v, sizeof v);
+  }
   const Out o{buf, cap};
   if (k == "owned") {   // (entries of the engine's ledger of device buffers and their bytes: host state only)
     int64_t v[2] = {0, 0};
@@ -2307,6 +2393,11 @@ int64_t spllt_hip_program_get(void* fkeep, const char* name, void* buf, int64_t 
                       k.substr(6), o);
   if (is("batch_det_")) return get_batch_det(f, k.substr(10), o);
   if (is("batch_rsolve_")) return get_batch_rsolve(f, k.substr(13), o);
+  if (is("bsolve_")) {   // "bsolve_*": the "solve_*" tables of the batch's own substitution program (pw = cb = 64, no partition)
+    SolveProgram sp;
+    build_solve_program(*f->S, 64, 64, sp);
+    return get_solve_tables(sp, k.substr(1), o);
+  }
   if (is("batch_")) return get_batch(f, k.substr(6), o);
   if (is("selinv_"))         // (single GPU; built from the symbolic structure alone)
     return get_selinv(f->si.get(f->S, P->pw, P->cb, [&](SelinvProgram& v) { return build_selinv_program(*f->S, P->pw, P->cb, v); }),

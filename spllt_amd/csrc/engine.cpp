@@ -2455,7 +2455,7 @@ int Engine::release_batch() {
   bt_.g_state = FADJ_UNSEEDED;
   bt_.fa_launches = 0;
   // (the batch's own storage, and what its features say of theirs)
-  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brp_.swscratch && !brf_held() && !bcn_.C && !bud_.W) { bt_.nbatch = 0; return 0; }
+  if (!bt_.L && !bt_.Y && !bt_.stage && !bt_.Z && !bt_.G && !bm_ready_ && !d_bmmean_ && !bsm_ready_ && !brp_.swscratch && !brf_held() && !bcn_.C && !bud_.W && !bss_.tab) { bt_.nbatch = 0; return 0; }
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   if (int rc = sync_stream(stream_, "batch release")) return rc;
   drop_factor_mult_batch();   // (the workspaces of the batched products belong to the batch)
@@ -2464,6 +2464,7 @@ int Engine::release_batch() {
   drop_refine_batch();        // (... and those of the refined solves)
   drop_constraints_batch();   // (... and the constraints of the batch, C included)
   drop_updown_batch();        // (... and the work arrays of its update / downdate)
+  drop_solve_sparse_batch();  // (... and the tables, outputs and workspaces of its sparse solves)
   give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, bt_.Y, bt_.stage, bt_.Z, bt_.G, bt_.siscratch, brp_.fscratch);
   brp_.f_capacity = 0;
   brp_.last_det = false;

@@ -15,6 +15,7 @@
 #include "engine_detail.hpp"
 #include "kernels.hpp"
 #include "schedule.hpp"
+#include "ss_filter.hpp"
 #include "symbolic.hpp"
 
 namespace spx {
@@ -79,6 +80,8 @@ void set_alloc_fail_at(int k);
 bool alloc_fail_armed();
 // debug: the workspace of a sparse solve is filled with NaN before its touched rows are zeroed
 void set_solve_sparse_poison(bool on);
+// ... and the whole workspace of the batch before a sparse solve of the batch clears its touched rows
+void set_solve_sparse_batch_poison(bool on);
 bool batch_selinv_fused();
 bool batch_fadj_fused();
 
@@ -463,6 +466,22 @@ class Engine {
   const int64_t* updown_batch_info() const { return bud_.info; }
   double updown_batch_device_ms() const { return bud_.device_ms; }
   int release_updown_batch();
+  // ---- sparse right-hand sides and B^T A_b^-1 B for every member of the last batch (batch_solve_sparse.hip,
+  // spllt_hip_solve_sparse_batch.h): solve_sparse / gram_sparse with every launch carrying
+  // all members.  B's pattern is shared (one plan, one filtered program -- the batch's own, bt_.sprog -- and one
+  // upload per group); bval: host values, one set (ldb = 0) or member b's at bval + b * ldb.  x: column q of member
+  // b at x[(b * k + q) * ldx + t]; g: G_b at g + b * k * ldg.  A flagged member's outputs are NaN (-20 once the
+  // others are served).  -98 while the reproducible batch is on.  All device memory is taken before anything runs
+  // (-1: nothing of the feature stays allocated, the batch and everything else stay usable).
+  int solve_sparse_batch(int k, const int* bptr, const int* brow, const double* bval, int64_t ldb, int nsel,
+                         const int* sel, double* x, int64_t ldx, int job, bool dev);
+  int gram_sparse_batch(int k, const int* bptr, const int* brow, const double* bval, int64_t ldb, double* g,
+                        int64_t ldg, bool dev);
+  // of the last call: the six fields of solve_sparse_info (block columns and entries per member, launches, sweep
+  // workgroups summed over members), members served, members flagged
+  const int64_t* solve_sparse_batch_info() const { return bss_.info; }
+  int64_t solve_sparse_batch_host_us() const { return bss_.host_us; }
+  int release_solve_sparse_batch();
   double* device_L() { return d_L_; }
   hipStream_t stream() { return stream_; }
   // entries of the ledger of device buffers and their bytes (host state only)
@@ -610,15 +629,9 @@ class Engine {
   SolveTablesView solve_tables() const { return {d_slist_, d_stiles_, d_sunits_, d_L_, d_dinv_, d_rlist_}; }
   // the rule of prepare_solve for one launch over the lists it indexes (the program's, or filtered ones)
   SolveLaunchInfo solve_launch_info(const SolveLaunch& l, const int* list, const UpdTile* tiles) const;
-  // where block column b sits in the program (prepare_solve): its launches of fwd / bwd (-1: no strips), its
-  // entry of diag_list and its tiles -- what filtering the program to a set of block columns walks
-  struct SolveBcolSlot {
-    int fdiag = -1, fstrip = -1, bdiag = -1, bstrip = -1;
-    int64_t dpos = 0, t0 = 0, tn = 0;
-  };
-  std::vector<SolveBcolSlot> sv_slot_;
-  int64_t sv_entries_ = 0, sv_bwd_wgs_ = 0;   // doubles of L in all block columns; workgroups of the whole backward sweep
-  bool sv_slot_ok_ = true;   // the program has the shape the slots assume (checked while they are built)
+  // where every block column sits in sprog_ (prepare_solve; ss_filter.hpp) -- what filtering the program to a set
+  // of block columns walks
+  SolveSlots sv_slots_;
   // f(launch, info) for the launches `job` and `phase` ask for, in program order (engine_solve.cpp)
   template <class F> void for_each_solve_launch(int job, int phase, F&& f) const;
   // user variable -> pivot position, for every permutation on the device: uploaded on first use, kept
@@ -777,14 +790,17 @@ class Engine {
     std::vector<int> list, chunks, selpos;        // compacted diag list; (first, length) chunks; wanted positions
     std::vector<UpdTile> tiles;
     std::vector<int64_t> pos;                     // scatter: pivot position * rb + column
-    std::vector<double> val;
+    std::vector<double> val;                      // single handle: the values of pos
+    std::vector<int> ent;                         // batch: the 0-based CSC entry each of pos comes from
     int64_t info[6] = {0, 0, 0, 0, 0, 0};
     size_t bytes = 0;                             // of the staged tables
   };
   struct SsTables { int* list; UpdTile* tiles; int* chunks; int* selpos; int64_t* pos; double* val; };
-  void ss_filter(bool bwd, const std::vector<int>& set, SsGroup& g) const;
-  void ss_plan_group(SsGroup& g, const int* bptr, const int* brow, const double* bval, int nsel, const int* sel,
-                     int job, const std::vector<int>* zero_ranges);
+  // (on a program and its slots: the handle's sprog_ / sv_slots_, or the batch's bt_.sprog / bss_.slots)
+  static void ss_filter(const SolveProgram& P, const SolveSlots& sl, bool bwd, const std::vector<int>& set, SsGroup& g);
+  void ss_plan_group(const SolveProgram& P, const SolveSlots& sl, bool launch_info, SsGroup& g, const int* bptr,
+                     const int* brow, const double* bval, int nsel, const int* sel, int job,
+                     const std::vector<int>* zero_ranges);
   int ss_upload(const SsGroup& g, SsTables& t);
   int ss_enqueue(const SsGroup& g, const SsTables& t, int job, double* W);
   int ss_fail_alloc(const char* what, size_t bytes, hipError_t e);
@@ -795,6 +811,27 @@ class Engine {
   int64_t ss_info_[6] = {0, 0, 0, 0, 0, 0};
   int64_t ss_host_us_ = 0;
   int ss_filterable();
+  // ... for the members of a batch (batch_solve_sparse.hip): the slots of bt_.sprog (once per engine), and the
+  // storage of a call -- staged tables and values of one group, the gathered entries / G / partial products, the
+  // workspaces of gram's groups after the first -- taken together in ONE transaction, kept while it is large enough
+  struct BssState {
+    bool slots_ready = false;
+    SolveSlots slots;
+    char* tab = nullptr;
+    double* out = nullptr;
+    double* gramW = nullptr;
+    size_t tab_cap = 0, out_cap = 0, gram_cap = 0;   // bytes, doubles, doubles
+    int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t host_us = 0;
+  } bss_;
+  int bss_enter(int* rb);                          // the batch's program is filterable, the workspace is there
+  int bss_take(size_t tab_bytes, size_t out_elems, size_t gram_elems, const char* what);
+  // tables and values of a group into bss_.tab (the stream is idle); ldv: 0 or the group's entries
+  int bss_upload(const SsGroup& g, const double* bval, int64_t ldb, SsTables& t, int64_t* ldv);
+  // poison (debug), zero, scatter and the filtered sweeps `job` asks for on the workspaces W (enqueue only);
+  // launches made, -1: a launch overflows a grid
+  int bss_enqueue(const SsGroup& g, const SsTables& t, int64_t ldv, int job, double* W);
+  void drop_solve_sparse_batch();
   // refined solves: operator tables and work vectors (taken on first use, all or nothing)
   int prepare_refine(bool host_val);
   int refine_apply_factor(double* v, int nv);

@@ -36,48 +36,14 @@ int Engine::prepare_solve() {
     const char* e = std::getenv("SPLLT_SOLVE_DIAG4");
     solve_four_ = prog_.pw == 64 && prog_.cb == 64 && !(e && std::atoi(e) == 0);
   }
-  // per launch, once (solve_launch_info), and per block column where it sits in the launches (sv_slot_)
+  // per launch, once (solve_launch_info), and per block column where it sits in the launches (sv_slots_)
   auto info = [&](const std::vector<SolveLaunch>& ls, std::vector<SolveLaunchInfo>& out) {
     out.assign(ls.size(), SolveLaunchInfo{false, nullptr});
     for (size_t i = 0; i < ls.size(); ++i) out[i] = solve_launch_info(ls[i], sprog_.diag_list.data(), sprog_.tiles.data());
   };
   info(sprog_.fwd, sv_fwd_);
   info(sprog_.bwd, sv_bwd_);
-  sv_slot_.assign(sprog_.units.size(), SolveBcolSlot{});
-  sv_slot_ok_ = true;
-  sv_entries_ = 0;
-  sv_bwd_wgs_ = 0;
-  for (const SolveUnit& u : sprog_.units) sv_entries_ += (int64_t)u.nrow * u.w;
-  for (const SolveLaunch& l : sprog_.bwd) sv_bwd_wgs_ += l.count;
-  for (int sweep = 0; sweep < 2; ++sweep) {
-    const std::vector<SolveLaunch>& ls = sweep ? sprog_.bwd : sprog_.fwd;
-    for (size_t i = 0; i < ls.size(); ++i) {
-      const bool diag = ls[i].kind == SV_DIAG_FWD || ls[i].kind == SV_DIAG_BWD;
-      for (int64_t q = ls[i].first; q < ls[i].first + ls[i].count; ++q) {
-        SolveBcolSlot& sl = sv_slot_[(size_t)(diag ? sprog_.diag_list[(size_t)q] : sprog_.tiles[(size_t)q].unit)];
-        // what the filter relies on: per sweep a block column sits in ONE diagonal launch, and its strips are one
-        // run of consecutive tiles (strip 0, 1, ...) of ONE strip launch, the same run in both sweeps
-        if (diag) {
-          int& at = sweep ? sl.bdiag : sl.fdiag;
-          if (at >= 0 || (sweep && sl.dpos != q)) sv_slot_ok_ = false;
-          at = (int)i;
-          sl.dpos = q;
-        } else {
-          int& at = sweep ? sl.bstrip : sl.fstrip;
-          if (at >= 0 && at != (int)i) sv_slot_ok_ = false;
-          at = (int)i;
-          const int64_t ti = sprog_.tiles[(size_t)q].ti;
-          if (!sweep) {   // (the backward launches index the same tiles)
-            if (sl.tn == 0) sl.t0 = q;
-            if (q != sl.t0 + sl.tn || ti != sl.tn) sv_slot_ok_ = false;
-            ++sl.tn;
-          } else if (q < sl.t0 || q >= sl.t0 + sl.tn || ti != q - sl.t0) {
-            sv_slot_ok_ = false;
-          }
-        }
-      }
-    }
-  }
+  sv_slots_ = build_solve_slots(sprog_);
   solve_ready_ = true;
   return 0;
 }
@@ -309,66 +275,36 @@ int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
 static std::atomic<bool> g_ss_poison{false};
 void set_solve_sparse_poison(bool on) { g_ss_poison.store(on); }
 
-// the launches of one sweep that hold a block column of `set` (ascending), with their entries compacted into
-// g.list / g.tiles in program order; a launch left empty is dropped.  Work: the set and its tiles, sorted.
-void Engine::ss_filter(bool bwd, const std::vector<int>& set, SsGroup& g) const {
-  struct Item { int launch; int64_t key; int b; };
-  std::vector<Item> items;
-  items.reserve(2 * set.size());
-  for (int b : set) {
-    const SolveBcolSlot& sl = sv_slot_[(size_t)b];
-    const int ld = bwd ? sl.bdiag : sl.fdiag, ls = bwd ? sl.bstrip : sl.fstrip;
-    if (ld >= 0) items.push_back({ld, sl.dpos, b});
-    if (ls >= 0) items.push_back({ls, sl.t0, b});
-  }
-  std::sort(items.begin(), items.end(),
-            [](const Item& a, const Item& b) { return a.launch != b.launch ? a.launch < b.launch : a.key < b.key; });
-  const std::vector<SolveLaunch>& prog = bwd ? sprog_.bwd : sprog_.fwd;
-  std::vector<SolveLaunch>& out = bwd ? g.bwd : g.fwd;
-  for (size_t i = 0; i < items.size();) {
-    const SolveLaunch& src = prog[(size_t)items[i].launch];
-    const bool diag = src.kind == SV_DIAG_FWD || src.kind == SV_DIAG_BWD;
-    SolveLaunch l{src.kind, src.level, (int64_t)(diag ? g.list.size() : g.tiles.size()), 0};
-    size_t j = i;
-    for (; j < items.size() && items[j].launch == items[i].launch; ++j) {
-      const SolveBcolSlot& sl = sv_slot_[(size_t)items[j].b];
-      if (diag) {
-        g.list.push_back(items[j].b);
-        ++l.count;
-        g.info[bwd ? 1 : 0] += 1;
-        g.info[bwd ? 3 : 2] += (int64_t)sprog_.units[(size_t)items[j].b].nrow * sprog_.units[(size_t)items[j].b].w;
-      } else {
-        g.tiles.insert(g.tiles.end(), sprog_.tiles.begin() + sl.t0, sprog_.tiles.begin() + sl.t0 + sl.tn);
-        l.count += sl.tn;
-      }
-    }
-    out.push_back(l);
-    g.info[5] += l.count;
-    i = j;
-  }
+// the launches of one sweep of P that hold a block column of `set`, compacted into g (ss_filter.hpp)
+void Engine::ss_filter(const SolveProgram& P, const SolveSlots& sl, bool bwd, const std::vector<int>& set, SsGroup& g) {
+  filter_solve_program(P, sl.slot, bwd, set, bwd ? g.bwd : g.fwd, g.list, g.tiles, g.info);
 }
 
-// plan, filter and stage one group (host only).  zero_ranges: the rows to clear when they are not the group's own
-// touched rows (gram: those of the whole call)
-void Engine::ss_plan_group(SsGroup& g, const int* bptr, const int* brow, const double* bval, int nsel, const int* sel,
-                           int job, const std::vector<int>* zero_ranges) {
+// plan, filter and stage one group (host only) on program P with its slots: the handle's own (sprog_) or the
+// batch's (bt_.sprog; launch_info false: the batch kernels take no SolveLaunchInfo).  zero_ranges: the rows to clear
+// when they are not the group's own touched rows (gram: those of the whole call)
+void Engine::ss_plan_group(const SolveProgram& prog, const SolveSlots& sl, bool launch_info, SsGroup& g, const int* bptr,
+                           const int* brow, const double* bval, int nsel, const int* sel, int job,
+                           const std::vector<int>* zero_ranges) {
   const Symbolic& S = *S_;
   SolveSparsePlan P;
   build_solve_sparse_plan(S, g.c0, g.c0 + g.nv, bptr, brow, nsel, sel, job, P);
-  ss_filter(false, P.fwd, g);
-  if (!P.bwd.empty() && P.bwd.size() == sprog_.units.size()) {
+  ss_filter(prog, sl, false, P.fwd, g);
+  if (!P.bwd.empty() && P.bwd.size() == prog.units.size()) {
     // every block column: the backward sweep is the program's own, on the tables that are resident already
     g.bwd_full = true;
-    g.info[1] += (int64_t)sprog_.units.size();
-    g.info[3] += sv_entries_;
-    g.info[5] += sv_bwd_wgs_;
+    g.info[1] += (int64_t)prog.units.size();
+    g.info[3] += sl.entries;
+    g.info[5] += sl.bwd_wgs;
   } else {
-    ss_filter(true, P.bwd, g);
+    ss_filter(prog, sl, true, P.bwd, g);
   }
-  g.fwd_i.resize(g.fwd.size());
-  g.bwd_i.resize(g.bwd.size());
-  for (size_t i = 0; i < g.fwd.size(); ++i) g.fwd_i[i] = solve_launch_info(g.fwd[i], g.list.data(), g.tiles.data());
-  for (size_t i = 0; i < g.bwd.size(); ++i) g.bwd_i[i] = solve_launch_info(g.bwd[i], g.list.data(), g.tiles.data());
+  if (launch_info) {
+    g.fwd_i.resize(g.fwd.size());
+    g.bwd_i.resize(g.bwd.size());
+    for (size_t i = 0; i < g.fwd.size(); ++i) g.fwd_i[i] = solve_launch_info(g.fwd[i], g.list.data(), g.tiles.data());
+    for (size_t i = 0; i < g.bwd.size(); ++i) g.bwd_i[i] = solve_launch_info(g.bwd[i], g.list.data(), g.tiles.data());
+  }
   const std::vector<int>& rg = zero_ranges ? *zero_ranges : P.range;
   for (size_t r = 0; r + 1 < rg.size(); r += 2)
     for (int o = 0; o < rg[r + 1]; o += kSsChunkRows) {
@@ -389,7 +325,8 @@ void Engine::ss_plan_group(SsGroup& g, const int* bptr, const int* brow, const d
       const int p = S.order[(size_t)brow[e] - 1];
       if (job == 2 && !touched(p)) continue;
       g.pos.push_back((int64_t)p * g.rb + q);
-      g.val.push_back(bval[e]);
+      if (launch_info) g.val.push_back(bval[e]);
+      else g.ent.push_back(e);   // (the batch packs the members' values of these entries itself)
     }
   if (sel && nsel >= 0)
     for (int t = 0; t < nsel; ++t) g.selpos.push_back(S.order[(size_t)sel[t] - 1]);
@@ -400,11 +337,12 @@ void Engine::ss_plan_group(SsGroup& g, const int* bptr, const int* brow, const d
     g.bytes = (g.bytes + 255) / 256 * 256 + std::max<size_t>(b, 8);
 }
 
-// 0, or -99 when the substitution program does not have the shape the filter relies on (prepare_solve)
+// 0, or -99 when a substitution program does not have the shape the filter relies on (build_solve_slots)
+static const char* const kSsShape = ": the substitution program holds a block column in more than one diagonal launch or "
+                                    "with strips that are not one run of one launch; filtering it is not implemented";
 int Engine::ss_filterable() {
-  if (sv_slot_ok_) return 0;
-  feature_err_ = "solve_sparse: the substitution program holds a block column in more than one diagonal launch or "
-                 "with strips that are not one run of one launch; filtering it is not implemented";
+  if (sv_slots_.ok) return 0;
+  feature_err_ = std::string("solve_sparse") + kSsShape;
   return -99;
 }
 
@@ -476,7 +414,7 @@ int Engine::solve_sparse(int k, const int* bptr, const int* brow, const double* 
   for_each_block(k, 32, [&](int done, int nv, int rb) {
     SsGroup g;
     g.c0 = done, g.nv = nv, g.rb = rb;
-    ss_plan_group(g, bptr, brow, bval, all ? -1 : nsel, all ? nullptr : sel, job, nullptr);
+    ss_plan_group(sprog_, sv_slots_, true, g, bptr, brow, bval, all ? -1 : nsel, all ? nullptr : sel, job, nullptr);
     tab_bytes = std::max(tab_bytes, g.bytes);
     groups.push_back(std::move(g));
     return 0;
@@ -531,7 +469,7 @@ int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* b
   for_each_block(k, 32, [&](int done, int nv, int rb) {
     SsGroup g;
     g.c0 = done, g.nv = nv, g.rb = rb;
-    ss_plan_group(g, bptr, brow, bval, 0, &none, 1, &U.range);
+    ss_plan_group(sprog_, sv_slots_, true, g, bptr, brow, bval, 0, &none, 1, &U.range);
     tab_bytes = std::max(tab_bytes, g.bytes);
     groups.push_back(std::move(g));
     return 0;
@@ -578,6 +516,287 @@ int Engine::release_solve_sparse() {
   give_back(d_sstab_, d_ssout_, d_ssgramW_);
   ss_tab_cap_ = ss_out_cap_ = ss_gram_cap_ = 0;
   return 0;
+}
+
+// ---- sparse right-hand sides for the members of a batch (batch_solve_sparse.hip) ---------------------
+static std::atomic<bool> g_bss_poison{false};
+void set_solve_sparse_batch_poison(bool on) { g_bss_poison.store(on); }
+
+void Engine::drop_solve_sparse_batch() {
+  give_back(bss_.tab, bss_.out, bss_.gramW);
+  bss_.tab_cap = bss_.out_cap = bss_.gram_cap = 0;
+}
+
+int Engine::release_solve_sparse_batch() {
+  int rc;
+  if (!enter_release(bss_.tab || bss_.out || bss_.gramW, "solve_sparse_batch release", &rc)) return rc;
+  drop_solve_sparse_batch();
+  return 0;
+}
+
+// the slots of the batch's own program (once), the workspace of the blocked batch solve and the order table
+int Engine::bss_enter(int* rb) {
+  if (!bss_.slots_ready) {
+    bss_.slots = build_solve_slots(bt_.sprog);
+    bss_.slots_ready = true;
+  }
+  if (!bss_.slots.ok) {
+    feature_err_ = std::string("solve_sparse_batch") + kSsShape;
+    return -99;
+  }
+  if (int rc = prepare_solve_many_batch()) return rc;
+  *rb = bsm_rb_;
+  return 0;
+}
+
+// the three buffers of a call, kept while each is large enough; else all three again in ONE transaction (a
+// failure leaves none of them)
+int Engine::bss_take(size_t tab_bytes, size_t out_elems, size_t gram_elems, const char* what) {
+  if (bss_.tab && bss_.tab_cap >= tab_bytes && bss_.out_cap >= out_elems && bss_.gram_cap >= gram_elems) return 0;
+  tab_bytes = std::max(tab_bytes, bss_.tab_cap);
+  out_elems = std::max(out_elems, bss_.out_cap);
+  gram_elems = std::max(gram_elems, bss_.gram_cap);
+  drop_solve_sparse_batch();
+  auto t = take();
+  t(&bss_.tab, std::max<size_t>(tab_bytes, 8));
+  if (out_elems) t(&bss_.out, sizeof(double) * out_elems);
+  if (gram_elems) t(&bss_.gramW, sizeof(double) * gram_elems);
+  if (!t.ok()) {
+    feature_err_ = std::string(what) + ": not enough device memory for the tables, the outputs and the workspaces of " +
+                   std::to_string(bt_.nbatch) + " members (" + std::to_string(t.bytes() >> 20) + " MiB): " +
+                   hipGetErrorString(t.error());
+    return alloc_code(t.error());
+  }
+  t.commit();
+  bss_.tab_cap = tab_bytes;
+  bss_.out_cap = out_elems;
+  bss_.gram_cap = gram_elems;
+  return 0;
+}
+
+// (the bytes bss_upload lays a group out in: the six lists of ss_plan_group with the values of all members last)
+static size_t bss_group_bytes(size_t list_bytes, size_t nvalues) {
+  return (list_bytes + 255) / 256 * 256 + std::max<size_t>(nvalues * sizeof(double), 8);
+}
+
+int Engine::bss_upload(const SsGroup& g, const double* bval, int64_t ldb, SsTables& t, int64_t* ldv) {
+  const size_t count = g.pos.size(), copies = ldb ? (size_t)bt_.nbatch : 1;
+  std::vector<double> vals(copies * count);
+  for (size_t b = 0; b < copies; ++b)
+    for (size_t i = 0; i < count; ++i) vals[b * count + i] = bval[(int64_t)b * ldb + g.ent[i]];
+  *ldv = ldb ? (int64_t)count : 0;
+  TableStager tab;
+  tab.add(&t.list, g.list);
+  tab.add(&t.tiles, g.tiles);
+  tab.add(&t.chunks, g.chunks);
+  tab.add(&t.selpos, g.selpos);
+  tab.add(&t.pos, g.pos);
+  tab.add(&t.val, vals);
+  char* blob = nullptr;
+  HIPCHK(tab.commit(&blob, [this](void** q, size_t b) {
+    *q = bss_.tab;
+    return b <= bss_.tab_cap ? hipSuccess : hipErrorOutOfMemory;
+  }), "upload the tables of a sparse solve of the batch");
+  return 0;
+}
+
+int Engine::bss_enqueue(const SsGroup& g, const SsTables& t, int64_t ldv, int job, double* W) {
+  const int n = S_->n, nbatch = bt_.nbatch;
+  const BatchView v = batch_view();
+  const BssView s{bt_.flag, nbatch};
+  const int64_t ws = (int64_t)g.rb * n;
+  if (g_bss_poison.load()) {
+    const size_t elems = W == d_bsmW_ ? (size_t)bsm_capacity_ * (size_t)bsm_rb_ * (size_t)n : (size_t)nbatch * 32 * (size_t)n;
+    (void)hipMemsetAsync(W, 0xFF, sizeof(double) * elems, stream_);
+  }
+  int nl = 0;
+  bool fits = true;
+  auto count = [&](int made) { if (made < 0) fits = false; else nl += made; };
+  count(launch_bss_zero(stream_, s, t.chunks, (int)(g.chunks.size() / 2), g.rb, W, ws));
+  count(launch_bss_scatter(stream_, s, t.pos, t.val, ldv, (int64_t)g.pos.size(), W, ws));
+  if (job != 2)
+    for (const SolveLaunch& l : g.fwd)
+      count(launch_batch_solve_many(stream_, v, l, t.list, t.tiles, bt_.sunits, d_rlist_, W, g.rb, n));
+  if (job != 1) {
+    // (all entries wanted: the program's own backward launches on the resident tables of the batch)
+    const std::vector<SolveLaunch>& bwd = g.bwd_full ? bt_.sprog.bwd : g.bwd;
+    for (const SolveLaunch& l : bwd)
+      count(launch_batch_solve_many(stream_, v, l, g.bwd_full ? bt_.slist : t.list, g.bwd_full ? bt_.stiles : t.tiles,
+                                    bt_.sunits, d_rlist_, W, g.rb, n));
+  }
+  return fits ? nl : -1;
+}
+
+static const char* const kBssRepro =
+    "not available while the reproducible batch is switched on (spllt_hip_set_batch_reproducible): the filtered sweeps "
+    "run the kernels that add with atomics";
+static const char* const kBssGrid = ": a launch has more work items for one member than a grid holds (the outputs are "
+                                    "not all written)";
+
+int Engine::solve_sparse_batch(int k, const int* bptr, const int* brow, const double* bval, int64_t ldb, int nsel,
+                               const int* sel, double* x, int64_t ldx, int job, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n, nbatch = bt_.nbatch;
+  const bool all = !sel || nsel < 0;
+  const int64_t nout = all ? n : nsel;
+  if (job < 0 || job > 2 || k < 0 || !bptr || !x || ldx < nout) return -10;
+  if (k > 0 && ((bptr[k] > bptr[0] && !bval) || (ldb != 0 && ldb < (int64_t)bptr[k] - 1))) return -10;
+  if (opt_.nranks > 1) return -98;   // a rank of a partition holds a part of L only
+  if (pending_ || nbatch <= 0) return -10;
+  if (brp_on_) {
+    feature_err_ = std::string("solve_sparse_batch: ") + kBssRepro;
+    return -98;
+  }
+  for (int64_t& v : bss_.info) v = 0;
+  if (k == 0 || nout == 0 || n == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  int rc, cap = 32;
+  if ((rc = bss_enter(&cap))) return rc;
+  // every group planned, filtered and staged on the host, and all device memory taken, before anything runs
+  const auto host_t0 = std::chrono::steady_clock::now();
+  std::vector<SsGroup> groups;
+  size_t tab_bytes = 0;
+  for_each_block(k, cap, [&](int done, int nv, int rb) {
+    SsGroup g;
+    g.c0 = done, g.nv = nv, g.rb = rb;
+    ss_plan_group(bt_.sprog, bss_.slots, false, g, bptr, brow, nullptr, all ? -1 : nsel, all ? nullptr : sel, job, nullptr);
+    tab_bytes = std::max(tab_bytes, bss_group_bytes(g.bytes, (ldb ? (size_t)nbatch : 1) * g.pos.size()));
+    groups.push_back(std::move(g));
+    return 0;
+  });
+  bss_.host_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
+  const size_t out_elems = dev ? 0 : (size_t)nbatch * 32 * (size_t)nout;
+  if ((rc = bss_take(tab_bytes, out_elems, 0, "solve_sparse_batch"))) return rc;
+  const BssView s{bt_.flag, nbatch};
+  int64_t info[6] = {0, 0, 0, 0, 0, 0};
+  bool fits = true;
+  for (const SsGroup& g : groups) {
+    SsTables t{};
+    int64_t ldv = 0;
+    if ((rc = bss_upload(g, bval, ldb, t, &ldv))) return rc;
+    const int made = bss_enqueue(g, t, ldv, job, d_bsmW_);
+    // member b's column q of the group: on the device at x + (b k + c0 + q) ldx, else packed in the output buffer
+    double* xg = dev ? x + (int64_t)g.c0 * ldx : bss_.out;
+    const int64_t ldo = dev ? ldx : nout, xs = dev ? (int64_t)k * ldx : (int64_t)g.nv * nout;
+    // (all entries: the order table is the list of wanted positions)
+    const int out = made < 0 ? -1
+                             : launch_bss_gather(stream_, s, xg, xs, ldo, all ? d_order_ : t.selpos, nout, g.nv, g.rb,
+                                                 d_bsmW_, (int64_t)g.rb * n);
+    HIPCHK(hipGetLastError(), "solve_sparse_batch launch");
+    if (made < 0 || out < 0) fits = false;
+    for (int b = 0; fits && !dev && b < nbatch; ++b)
+      if ((rc = copy_vectors(false, bss_.out + (int64_t)b * xs, x + ((int64_t)b * k + g.c0) * ldx, ldx, g.nv, "x D2H", nout)))
+        return rc;
+    if ((rc = sync_stream(stream_, "solve_sparse_batch sync"))) return rc;   // (the next group reuses the tables)
+    if (!fits) {
+      feature_err_ = std::string("solve_sparse_batch") + kBssGrid;
+      return -99;
+    }
+    info[4] += made + out;
+    for (int i = 0; i < 6; ++i)
+      if (i != 4) info[i] += g.info[i];
+  }
+  for (int i = 0; i < 6; ++i) bss_.info[i] = info[i];
+  bss_.info[5] *= nbatch;
+  for (int fl : bt_.hflag) ++bss_.info[fl == INT_MAX ? 6 : 7];
+  return batch_failed();
+}
+
+int Engine::gram_sparse_batch(int k, const int* bptr, const int* brow, const double* bval, int64_t ldb, double* gout,
+                              int64_t ldg, bool dev) {
+  feature_err_.clear();
+  if (status_) return status_;
+  const int n = S_->n, nbatch = bt_.nbatch;
+  if (k < 0 || !bptr || !gout || ldg < k) return -10;
+  if (k > 0 && ((bptr[k] > bptr[0] && !bval) || (ldb != 0 && ldb < (int64_t)bptr[k] - 1))) return -10;
+  if (opt_.nranks > 1) return -98;
+  if (pending_ || nbatch <= 0) return -10;
+  if (brp_on_) {
+    feature_err_ = std::string("gram_sparse_batch: ") + kBssRepro;
+    return -98;
+  }
+  for (int64_t& v : bss_.info) v = 0;
+  if (k == 0) return 0;
+  HIPCHK(hipSetDevice(device_), "hipSetDevice");
+  if (n == 0) {   // (no member can be flagged)
+    if (dev) {
+      for (int64_t c = 0; c < (int64_t)nbatch * k; ++c)
+        HIPCHK(hipMemsetAsync(gout + c * ldg, 0, sizeof(double) * (size_t)k, stream_), "gram_sparse_batch clear");
+      return sync_stream(stream_, "gram_sparse_batch sync");
+    }
+    for (int64_t c = 0; c < (int64_t)nbatch * k; ++c)
+      for (int i = 0; i < k; ++i) gout[c * ldg + i] = 0.0;
+    return 0;
+  }
+  int rc, cap = 32;
+  if ((rc = bss_enter(&cap))) return rc;
+  // the rows the products run over: those any column of the call touches, cleared in every group's workspace
+  static const int none = 0;
+  const auto host_t0 = std::chrono::steady_clock::now();
+  SolveSparsePlan U;
+  build_solve_sparse_plan(*S_, 0, k, bptr, brow, 0, &none, 1, U);
+  std::vector<SsGroup> groups;
+  size_t tab_bytes = 0;
+  for_each_block(k, cap, [&](int done, int nv, int rb) {
+    SsGroup g;
+    g.c0 = done, g.nv = nv, g.rb = rb;
+    ss_plan_group(bt_.sprog, bss_.slots, false, g, bptr, brow, nullptr, 0, &none, 1, &U.range);
+    tab_bytes = std::max(tab_bytes, bss_group_bytes(g.bytes, (ldb ? (size_t)nbatch : 1) * g.pos.size()));
+    groups.push_back(std::move(g));
+    return 0;
+  });
+  bss_.host_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
+  const size_t ng = groups.size(), nchunk = groups[0].chunks.size() / 2;
+  // one workspace per group and member: the first group's is the batch's own, the others' are taken here
+  const size_t gstride_w = (size_t)nbatch * 32 * (size_t)n;
+  const size_t g_elems = dev ? 0 : (size_t)nbatch * (size_t)k * (size_t)k;
+  if ((rc = bss_take(tab_bytes, g_elems + (size_t)nbatch * nchunk * 1024, gstride_w * (ng - 1), "gram_sparse_batch")))
+    return rc;
+  auto workspace = [&](size_t gi) { return gi == 0 ? d_bsmW_ : bss_.gramW + (gi - 1) * gstride_w; };
+  const BssView s{bt_.flag, nbatch};
+  int64_t info[6] = {0, 0, 0, 0, 0, 0};
+  auto overflow = [&]() {
+    feature_err_ = std::string("gram_sparse_batch") + kBssGrid;
+    return -99;
+  };
+  SsTables t{};
+  for (size_t gi = 0; gi < ng; ++gi) {
+    const SsGroup& g = groups[gi];
+    int64_t ldv = 0;
+    if ((rc = bss_upload(g, bval, ldb, t, &ldv))) return rc;
+    const int made = bss_enqueue(g, t, ldv, 1, workspace(gi));
+    HIPCHK(hipGetLastError(), "gram_sparse_batch launch");
+    if ((rc = sync_stream(stream_, "gram_sparse_batch sync"))) return rc;   // (the next group reuses the tables)
+    if (made < 0) return overflow();
+    info[4] += made;
+    for (int i = 0; i < 6; ++i)
+      if (i != 4) info[i] += g.info[i];
+  }
+  // (the chunk list of the last group, the same in every group, is still in the tables)
+  double* dG = dev ? gout : bss_.out;
+  const int64_t ldo = dev ? ldg : (int64_t)k;
+  double* part = bss_.out + g_elems;
+  bool fits = true;
+  for (size_t I = 0; I < ng && fits; ++I)
+    for (size_t J = 0; J <= I && fits; ++J) {
+      const int a = launch_bss_gram(stream_, s, t.chunks, (int)nchunk, workspace(I), (int64_t)groups[I].rb * n, groups[I].rb,
+                                    workspace(J), (int64_t)groups[J].rb * n, groups[J].rb, part);
+      const int b = a < 0 ? -1
+                          : launch_bss_gram_reduce(stream_, s, part, (int)nchunk, groups[I].nv, groups[J].nv, I == J,
+                                                   dG + (int64_t)groups[J].c0 * ldo + groups[I].c0,
+                                                   dG + (int64_t)groups[I].c0 * ldo + groups[J].c0, (int64_t)k * ldo, ldo);
+      if (a < 0 || b < 0) fits = false;
+      else info[4] += a + b;
+    }
+  HIPCHK(hipGetLastError(), "gram_sparse_batch launch");
+  if (fits && !dev && (rc = copy_vectors(false, dG, gout, ldg, (int64_t)nbatch * k, "G D2H", k))) return rc;
+  if ((rc = sync_stream(stream_, "gram_sparse_batch sync"))) return rc;
+  if (!fits) return overflow();
+  for (int i = 0; i < 6; ++i) bss_.info[i] = info[i];
+  bss_.info[5] *= nbatch;
+  for (int fl : bt_.hflag) ++bss_.info[fl == INT_MAX ? 6 : 7];
+  return batch_failed();
 }
 
 // ---- reproducible solve ----------------------------------------------------------------------------

@@ -327,6 +327,29 @@ int launch_bupdown_scatter(hipStream_t st, const BupdownView& s, const int64_t* 
 int launch_bupdown_gen(hipStream_t st, const BupdownView& s, const SolveUnit& u, int sign, int nv);
 // (strips x members) workgroups: the rows below the square; 0 when there are none
 int launch_bupdown_apply(hipStream_t st, const BupdownView& s, const SolveUnit& u, const int* rlist, int sign, int nv);
+// ---- sparse right-hand sides for the members of a batch (batch_solve_sparse.hip; the bodies of solve_sparse.hip
+// per member: ss_body.hpp) ----
+// The batch's flags and member count; member b's workspace at W + b * wstride.  The lists (chunks, pos) are shared
+// by all members.  A flagged member's workspace is never touched; its outputs (gather, gram_reduce) are NaN.  Every
+// wrapper returns the launches made (the members split into ranges as in batch_split.hpp), -1 when one member's
+// work items overflow a grid.
+struct BssView {
+  const int* flag;
+  int nbatch;
+};
+int launch_bss_zero(hipStream_t st, const BssView& s, const int* chunks, int nchunk, int rb, double* W, int64_t wstride);
+// W_b[pos[i]] = val[b * ldv + i], i < count (ldv = 0: one set of values)
+int launch_bss_scatter(hipStream_t st, const BssView& s, const int64_t* pos, const double* val, int64_t ldv,
+                       int64_t count, double* W, int64_t wstride);
+// x[b * xstride + q * ldx + t] = W_b[pos[t] * rb + q] for t < nsel, q < nv
+int launch_bss_gather(hipStream_t st, const BssView& s, double* x, int64_t xstride, int64_t ldx, const int* pos,
+                      int64_t nsel, int nv, int rb, const double* W, int64_t wstride);
+// part[(b * nchunk + c) * 1024 + i * 32 + j] = the product of chunk c's rows of member b's two workspaces
+int launch_bss_gram(hipStream_t st, const BssView& s, const int* chunks, int nchunk, const double* WI, int64_t wsI, int rbI,
+                    const double* WJ, int64_t wsJ, int rbJ, double* part);
+// launch_ss_gram_reduce for every member: G_b at Gij / Gji + b * gstride
+int launch_bss_gram_reduce(hipStream_t st, const BssView& s, const double* part, int nchunk, int nvI, int nvJ, bool diag,
+                           double* Gij, double* Gji, int64_t gstride, int64_t ldg);
 // ---- reproducible substitution (solve_repro.hip): launch_solve without atomic adds ------------------
 // The RsolveTables (schedule.hpp) on the device and the scratch: vector q of a sweep uses scratch + q * stride,
 // stride >= max(frows, bsize).
