@@ -1673,17 +1673,23 @@ int spllt_hip_updown_batch_time(void* fkeep, double* device_ms) {
 }
 
 // ---- sparse right-hand sides and selected outputs --------------------------------------------------
-// the ladder of the sparse solves; out: the output array, ld against the number of wanted entries (gram: against k)
+// the argument rungs of the sparse solves of handle and batch: the first that fails (*why holds its text when it is
+// check_sparse_columns'), or null.  out: the output array, ld against the number of wanted entries (gram: against k)
+static const char* sparse_args_bad(const Fkeep* f, int k, const int* bptr, const int* brow, const double* bval, int nsel,
+                                   const int* sel, const void* out, int64_t ld, int64_t ld_min, int job, std::string* why) {
+  if (!out) return "the output array is null";
+  if (job < 0 || job > 2) return "job is not 0, 1 or 2";
+  if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, why)) return why->c_str();
+  if (k > 0 && bptr[k] > bptr[0] && !bval) return "the array of values is null";
+  if (ld < ld_min) return "the leading dimension of the output is too small";
+  return nullptr;
+}
+
 static int solve_sparse_enter(Fkeep* f, const char* what, int k, const int* bptr, const int* brow, const double* bval,
                               int nsel, const int* sel, const void* out, int64_t ld, int64_t ld_min, int job) {
   if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
   std::string why;
-  const char* bad = nullptr;
-  if (!out) bad = "the output array is null";
-  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
-  else if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) bad = why.c_str();
-  else if (k > 0 && bptr[k] > bptr[0] && !bval) bad = "the array of values is null";
-  else if (ld < ld_min) bad = "the leading dimension of the output is too small";
+  const char* bad = sparse_args_bad(f, k, bptr, brow, bval, nsel, sel, out, ld, ld_min, job, &why);
   // (without a factorization the engine is created only to tell "no device" from "nothing factorized")
   return enter(f, what, bad, SINGLE | WAIT | ENGINE | FACTORED);
 }
@@ -1741,20 +1747,16 @@ int spllt_hip_solve_sparse_info(void* fkeep, int64_t out[6]) {
 }
 
 // ---- sparse right-hand sides for the members of a batch (spllt_hip_solve_sparse_batch.h) ------------
-// the argument rungs of solve_sparse_enter, then the member stride; the handle rungs of solve_many_batch_impl, then
+// the argument rungs of sparse_args_bad, then the member stride; the handle rungs of solve_many_batch_impl, then
 // the reproducible switch
 static int solve_sparse_batch_enter(Fkeep* f, const char* what, int k, const int* bptr, const int* brow,
                                     const double* bval, int64_t ldb, int nsel, const int* sel, const void* out, int64_t ld,
                                     int64_t ld_min, int job) {
   if (!analysed(f)) return SPLLT_ERROR_PARAMETER;
   std::string why;
-  const char* bad = nullptr;
-  if (!out) bad = "the output array is null";
-  else if (job < 0 || job > 2) bad = "job is not 0, 1 or 2";
-  else if (check_sparse_columns(*f->S, k, bptr, brow, nsel, sel, &why)) bad = why.c_str();
-  else if (k > 0 && bptr[k] > bptr[0] && !bval) bad = "the array of values is null";
-  else if (ld < ld_min) bad = "the leading dimension of the output is too small";
-  else if (k > 0 && ldb != 0 && ldb < (int64_t)bptr[k] - 1) bad = "ldb is neither 0 (one set of values for all members) nor >= bptr[k] - 1";
+  const char* bad = sparse_args_bad(f, k, bptr, brow, bval, nsel, sel, out, ld, ld_min, job, &why);
+  if (!bad && k > 0 && ldb != 0 && ldb < (int64_t)bptr[k] - 1)
+    bad = "ldb is neither 0 (one set of values for all members) nor >= bptr[k] - 1";
   if (int rc = enter(f, what, bad, SINGLE | WAIT_IGNORE | BATCH)) return rc;
   if (f->eng->batch_reproducible())
     return fail(f, what, "not available while the reproducible batch is switched on (spllt_hip_set_batch_reproducible): "

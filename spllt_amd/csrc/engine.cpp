@@ -1803,28 +1803,18 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
   int rc = prepare_solve();
   if (rc) return rc;
-  // the non-empty columns in passes of kUpdownVec; per pass the (position in the work array, value) pairs
-  std::vector<int> cols;
-  for (int v = 0; v < k; ++v)
-    if (first[(size_t)v] >= 0) cols.push_back(v);
-  const int npass = ((int)cols.size() + kUpdownVec - 1) / kUpdownVec;
-  std::vector<int64_t> pos, pass_ptr(1, 0);
-  std::vector<double> val;
-  for (int p = 0; p < npass; ++p) {
-    for (int q = 0; q < kUpdownVec && p * kUpdownVec + q < (int)cols.size(); ++q) {
-      const int v = cols[(size_t)(p * kUpdownVec + q)];
-      for (int e = wptr[v] - 1; e < wptr[v + 1] - 1; ++e) {
-        pos.push_back((int64_t)S.order[(size_t)wrow[e] - 1] * kUpdownVec + q);
-        val.push_back(wval[e]);
-      }
-    }
-    pass_ptr.push_back((int64_t)pos.size());
-  }
+  // the passes, the positions of their entries in the work array and their plans (updown_stage.hpp); the values
+  // of the entries, in that order
+  UpdownStage st;
+  stage_updown(k, wptr, wrow, S.order.data(), first.data(), kUpdownVec,
+               [&](const int* pf, int nc, std::vector<int>& plan) { updown_paths(S, pf, nc, plan); }, st);
+  std::vector<double> val(st.ent.size());
+  for (size_t i = 0; i < val.size(); ++i) val[i] = wval[st.ent[i]];
   int maxw = 1;
   for (const BlockCol& B : S.bcols) maxw = std::max(maxw, B.width);
   const size_t wb = sizeof(double) * kUpdownVec * (size_t)std::max(1, S.n);
   const size_t cb = sizeof(double) * ((size_t)maxw * kUpdownVec * 3 + 2);
-  const size_t pb = sizeof(int64_t) * pos.size(), vb = sizeof(double) * val.size();
+  const size_t pb = sizeof(int64_t) * st.pos.size(), vb = sizeof(double) * val.size();
   int64_t* d_pos = nullptr;
   double* d_val = nullptr;
   {
@@ -1837,7 +1827,7 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
     }
     t(&d_pos, pb);
     t(&d_val, vb);
-    if (t.ok()) t.check(hipMemcpyAsync(d_pos, pos.data(), pb, hipMemcpyHostToDevice, stream_));
+    if (t.ok()) t.check(hipMemcpyAsync(d_pos, st.pos.data(), pb, hipMemcpyHostToDevice, stream_));
     if (t.ok()) t.check(hipMemcpyAsync(d_val, val.data(), vb, hipMemcpyHostToDevice, stream_));
     if (!t.ok()) {
       (void)hipGetLastError();
@@ -1850,19 +1840,14 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   }
   int* d_flag = reinterpret_cast<int*>(d_udcoef_ + (size_t)maxw * kUpdownVec * 3);
   int64_t launches = 0;
-  std::vector<int> plan;
-  for (int p = 0; p < npass; ++p) {
-    const int c0 = p * kUpdownVec, nc = std::min(kUpdownVec, (int)cols.size() - c0);
-    // the plan of this pass's columns (a subset of `all`)
-    std::vector<int> pf;
-    for (int q = 0; q < nc; ++q) pf.push_back(first[(size_t)cols[(size_t)(c0 + q)]]);
-    updown_paths(S, pf.data(), nc, plan);
+  for (int p = 0; p < st.npass; ++p) {
+    const int nc = st.pass_nc[(size_t)p];
+    const int64_t e0 = st.pass_ptr[(size_t)p];
     if (p == 0) (void)hipEventRecord(ev0_, stream_);
-    launch_updown_scatter(stream_, d_pos + pass_ptr[(size_t)p], d_val + pass_ptr[(size_t)p],
-                          pass_ptr[(size_t)p + 1] - pass_ptr[(size_t)p], d_udW_, d_flag, p == 0);
+    launch_updown_scatter(stream_, d_pos + e0, d_val + e0, st.pass_ptr[(size_t)p + 1] - e0, d_udW_, d_flag, p == 0);
     ++launches;
-    for (int b : plan) {
-      const SolveUnit& u = sprog_.units[(size_t)b];
+    for (int64_t i = st.plan_ptr[(size_t)p]; i < st.plan_ptr[(size_t)p + 1]; ++i) {
+      const SolveUnit& u = sprog_.units[(size_t)st.plan[(size_t)i]];
       launch_updown_gen(stream_, u, d_L_, d_dinv_, d_udW_, d_udcoef_, d_flag, sign, nc);
       ++launches;
       if (u.nrow > u.w) {
@@ -1890,7 +1875,7 @@ int Engine::updown(int k, const int* wptr, const int* wrow, const double* wval, 
   ud_info_[0] = (int64_t)all.size();
   for (int b : all) ud_info_[1] += (int64_t)S.bcols[(size_t)b].nrow * S.bcols[(size_t)b].width;
   ud_info_[2] = launches;
-  ud_info_[3] = npass;
+  ud_info_[3] = st.npass;
   if (flag != INT_MAX) {
     npd_col_ = flag - 1;
     ud_invalid_ = true;
@@ -2464,7 +2449,7 @@ int Engine::release_batch() {
   drop_refine_batch();        // (... and those of the refined solves)
   drop_constraints_batch();   // (... and the constraints of the batch, C included)
   drop_updown_batch();        // (... and the work arrays of its update / downdate)
-  drop_solve_sparse_batch();  // (... and the tables, outputs and workspaces of its sparse solves)
+  ss_drop(bss_);              // (... and the tables, outputs and workspaces of its sparse solves)
   give_back(bt_.L, bt_.dinv, bt_.flag, bt_.out, bt_.Y, bt_.stage, bt_.Z, bt_.G, bt_.siscratch, brp_.fscratch);
   brp_.f_capacity = 0;
   brp_.last_det = false;

@@ -15,6 +15,7 @@
 #include "engine_detail.hpp"
 #include "kernels.hpp"
 #include "schedule.hpp"
+#include "ss_driver.hpp"
 #include "ss_filter.hpp"
 #include "symbolic.hpp"
 
@@ -264,10 +265,10 @@ class Engine {
   int gram_sparse(int k, const int* bptr, const int* brow, const double* bval, double* g_host, int64_t ldg);
   // of the last solve_sparse / gram_sparse: block columns of the forward / backward sweeps, doubles of L in
   // them, kernel launches, workgroups of the sweeps -- summed over the groups, from the uploaded lists
-  const int64_t* solve_sparse_info() const { return ss_info_; }
+  const int64_t* solve_sparse_info() const { return ss_.info; }
   // host microseconds the last solve_sparse / gram_sparse of this engine spent, before its first device call, on
   // the plans of its groups, the filtered launches and the arrays to be uploaded (not the upload itself)
-  int64_t solve_sparse_host_us() const { return ss_host_us_; }
+  int64_t solve_sparse_host_us() const { return ss_.host_us; }
   int release_solve_sparse();
   // on: solve(), solve_dev(phase -1) and the preconditioner of solve_refined go through the path above
   void set_reproducible_solve(bool on) { repro_on_ = on; }
@@ -790,48 +791,35 @@ class Engine {
     std::vector<int> list, chunks, selpos;        // compacted diag list; (first, length) chunks; wanted positions
     std::vector<UpdTile> tiles;
     std::vector<int64_t> pos;                     // scatter: pivot position * rb + column
-    std::vector<double> val;                      // single handle: the values of pos
-    std::vector<int> ent;                         // batch: the 0-based CSC entry each of pos comes from
+    std::vector<int> ent;                         // the 0-based CSC entry each of pos comes from
     int64_t info[6] = {0, 0, 0, 0, 0, 0};
-    size_t bytes = 0;                             // of the staged tables
+    size_t bytes = 0;                             // of the staged tables with their values (ss_table_bytes)
   };
   struct SsTables { int* list; UpdTile* tiles; int* chunks; int* selpos; int64_t* pos; double* val; };
-  // (on a program and its slots: the handle's sprog_ / sv_slots_, or the batch's bt_.sprog / bss_.slots)
+  // the sequence of a call is ss_driver.hpp's; its two backends: the handle on sprog_ / sv_slots_ / d_smW_ with three
+  // buffers that grow, the batch on bt_.sprog / bss_.slots / d_bsmW_ with one transaction for the three
+  struct SsBackend;
+  struct SsHandleBackend;
+  struct SsBatchBackend;
   static void ss_filter(const SolveProgram& P, const SolveSlots& sl, bool bwd, const std::vector<int>& set, SsGroup& g);
+  // launch_info: a SolveLaunchInfo per filtered launch (what the handle's kernels take)
   void ss_plan_group(const SolveProgram& P, const SolveSlots& sl, bool launch_info, SsGroup& g, const int* bptr,
-                     const int* brow, const double* bval, int nsel, const int* sel, int job,
-                     const std::vector<int>* zero_ranges);
-  int ss_upload(const SsGroup& g, SsTables& t);
-  int ss_enqueue(const SsGroup& g, const SsTables& t, int job, double* W);
-  int ss_fail_alloc(const char* what, size_t bytes, hipError_t e);
-  char* d_sstab_ = nullptr;        // staged tables of one group (grows, stays)
-  double* d_ssout_ = nullptr;      // gathered entries / G of a host entry point, the partial products of gram
-  double* d_ssgramW_ = nullptr;    // gram: the workspaces of the groups after the first
-  size_t ss_tab_cap_ = 0, ss_out_cap_ = 0, ss_gram_cap_ = 0;
-  int64_t ss_info_[6] = {0, 0, 0, 0, 0, 0};
-  int64_t ss_host_us_ = 0;
+                     const int* brow, int nsel, const int* sel, int job, const std::vector<int>* zero_ranges);
+  static size_t ss_table_bytes(const SsGroup& g, size_t copies);
+  // tables of a group and `copies` sets of its values (set b: bval + b * ldb) into s.tab (the stream is idle)
+  int ss_upload(const SsState& s, const SsGroup& g, const double* bval, int64_t ldb, size_t copies, SsTables& t);
+  void ss_drop(SsState& s);
+  int ss_release(SsState& s, const char* what);
   int ss_filterable();
-  // ... for the members of a batch (batch_solve_sparse.hip): the slots of bt_.sprog (once per engine), and the
-  // storage of a call -- staged tables and values of one group, the gathered entries / G / partial products, the
-  // workspaces of gram's groups after the first -- taken together in ONE transaction, kept while it is large enough
-  struct BssState {
+  SsState ss_;
+  // ... for the members of a batch (batch_solve_sparse.hip): the slots of bt_.sprog (once per engine); the storage
+  // of a call is taken together in ONE transaction, kept while it is large enough
+  struct BssState : SsState {
     bool slots_ready = false;
     SolveSlots slots;
-    char* tab = nullptr;
-    double* out = nullptr;
-    double* gramW = nullptr;
-    size_t tab_cap = 0, out_cap = 0, gram_cap = 0;   // bytes, doubles, doubles
-    int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t host_us = 0;
   } bss_;
-  int bss_enter(int* rb);                          // the batch's program is filterable, the workspace is there
+  int bss_enter();                                 // the batch's program is filterable, the workspace is there
   int bss_take(size_t tab_bytes, size_t out_elems, size_t gram_elems, const char* what);
-  // tables and values of a group into bss_.tab (the stream is idle); ldv: 0 or the group's entries
-  int bss_upload(const SsGroup& g, const double* bval, int64_t ldb, SsTables& t, int64_t* ldv);
-  // poison (debug), zero, scatter and the filtered sweeps `job` asks for on the workspaces W (enqueue only);
-  // launches made, -1: a launch overflows a grid
-  int bss_enqueue(const SsGroup& g, const SsTables& t, int64_t ldv, int job, double* W);
-  void drop_solve_sparse_batch();
   // refined solves: operator tables and work vectors (taken on first use, all or nothing)
   int prepare_refine(bool host_val);
   int refine_apply_factor(double* v, int nv);

@@ -271,21 +271,23 @@ int Engine::solve_many(double* x_host, int nrhs, int64_t ldx, int job) {
   return run_solve_many(x_host, false, nrhs, ldx, job, false);
 }
 
-// ---- sparse right-hand sides and selected outputs ----------------------------------------------------
+// ---- sparse right-hand sides and selected outputs, of the handle and of the members of a batch -------
+// The sequence of a call is ss_driver.hpp's; here are what it runs on: the planning and the upload of a group, the
+// storage, and the two backends (solve_sparse.hip, batch_solve_sparse.hip).
 static std::atomic<bool> g_ss_poison{false};
 void set_solve_sparse_poison(bool on) { g_ss_poison.store(on); }
+static std::atomic<bool> g_bss_poison{false};
+void set_solve_sparse_batch_poison(bool on) { g_bss_poison.store(on); }
 
 // the launches of one sweep of P that hold a block column of `set`, compacted into g (ss_filter.hpp)
 void Engine::ss_filter(const SolveProgram& P, const SolveSlots& sl, bool bwd, const std::vector<int>& set, SsGroup& g) {
   filter_solve_program(P, sl.slot, bwd, set, bwd ? g.bwd : g.fwd, g.list, g.tiles, g.info);
 }
 
-// plan, filter and stage one group (host only) on program P with its slots: the handle's own (sprog_) or the
-// batch's (bt_.sprog; launch_info false: the batch kernels take no SolveLaunchInfo).  zero_ranges: the rows to clear
-// when they are not the group's own touched rows (gram: those of the whole call)
+// plan, filter and stage one group (host only) on program P with its slots.  zero_ranges: the rows to clear when
+// they are not the group's own touched rows (gram: those of the whole call)
 void Engine::ss_plan_group(const SolveProgram& prog, const SolveSlots& sl, bool launch_info, SsGroup& g, const int* bptr,
-                           const int* brow, const double* bval, int nsel, const int* sel, int job,
-                           const std::vector<int>* zero_ranges) {
+                           const int* brow, int nsel, const int* sel, int job, const std::vector<int>* zero_ranges) {
   const Symbolic& S = *S_;
   SolveSparsePlan P;
   build_solve_sparse_plan(S, g.c0, g.c0 + g.nv, bptr, brow, nsel, sel, job, P);
@@ -325,16 +327,39 @@ void Engine::ss_plan_group(const SolveProgram& prog, const SolveSlots& sl, bool 
       const int p = S.order[(size_t)brow[e] - 1];
       if (job == 2 && !touched(p)) continue;
       g.pos.push_back((int64_t)p * g.rb + q);
-      if (launch_info) g.val.push_back(bval[e]);
-      else g.ent.push_back(e);   // (the batch packs the members' values of these entries itself)
+      g.ent.push_back(e);   // (the upload packs the values of these entries)
     }
   if (sel && nsel >= 0)
     for (int t = 0; t < nsel; ++t) g.selpos.push_back(S.order[(size_t)sel[t] - 1]);
-  // (the size TableStager will lay these six arrays out in: 256-byte aligned slots of at least 8 bytes)
-  g.bytes = 0;
+}
+
+// the size ss_upload lays a group out in: 256-byte aligned slots of at least 8 bytes (TableStager), the values last
+size_t Engine::ss_table_bytes(const SsGroup& g, size_t copies) {
+  size_t bytes = 0;
   for (size_t b : {g.list.size() * sizeof(int), g.tiles.size() * sizeof(UpdTile), g.chunks.size() * sizeof(int),
-                   g.selpos.size() * sizeof(int), g.pos.size() * sizeof(int64_t), g.val.size() * sizeof(double)})
-    g.bytes = (g.bytes + 255) / 256 * 256 + std::max<size_t>(b, 8);
+                   g.selpos.size() * sizeof(int), g.pos.size() * sizeof(int64_t), copies * g.ent.size() * sizeof(double)})
+    bytes = (bytes + 255) / 256 * 256 + std::max<size_t>(b, 8);
+  return bytes;
+}
+
+int Engine::ss_upload(const SsState& s, const SsGroup& g, const double* bval, int64_t ldb, size_t copies, SsTables& t) {
+  const size_t count = g.ent.size();
+  std::vector<double> vals(copies * count);
+  for (size_t b = 0; b < copies; ++b)
+    for (size_t i = 0; i < count; ++i) vals[b * count + i] = bval[(int64_t)b * ldb + g.ent[i]];
+  TableStager tab;
+  tab.add(&t.list, g.list);
+  tab.add(&t.tiles, g.tiles);
+  tab.add(&t.chunks, g.chunks);
+  tab.add(&t.selpos, g.selpos);
+  tab.add(&t.pos, g.pos);
+  tab.add(&t.val, vals);
+  char* blob = nullptr;
+  HIPCHK(tab.commit(&blob, [&s](void** q, size_t b) {
+    *q = s.tab;
+    return b <= s.tab_cap ? hipSuccess : hipErrorOutOfMemory;
+  }), "upload the tables of a sparse solve");
+  return 0;
 }
 
 // 0, or -99 when a substitution program does not have the shape the filter relies on (build_solve_slots)
@@ -346,52 +371,242 @@ int Engine::ss_filterable() {
   return -99;
 }
 
-// (the capacities are in elements: bytes of the tables, doubles of the other two)
-int Engine::ss_fail_alloc(const char* what, size_t bytes, hipError_t e) {
-  give_back(d_sstab_, d_ssout_, d_ssgramW_);
-  ss_tab_cap_ = ss_out_cap_ = ss_gram_cap_ = 0;
-  feature_err_ = std::string(what) + ": not enough device memory (" + std::to_string(bytes >> 20) + " MiB): " +
-                 hipGetErrorString(e);
-  return alloc_code(e);
+void Engine::ss_drop(SsState& s) {
+  give_back(s.tab, s.out, s.gramW);
+  s.tab_cap = s.out_cap = s.gram_cap = 0;
 }
 
-// the tables of a group into the pool buffer (reserved by the caller; the stream is idle)
-int Engine::ss_upload(const SsGroup& g, SsTables& t) {
-  TableStager tab;
-  tab.add(&t.list, g.list);
-  tab.add(&t.tiles, g.tiles);
-  tab.add(&t.chunks, g.chunks);
-  tab.add(&t.selpos, g.selpos);
-  tab.add(&t.pos, g.pos);
-  tab.add(&t.val, g.val);
-  char* blob = nullptr;
-  HIPCHK(tab.commit(&blob, [this](void** q, size_t b) {
-    *q = d_sstab_;
-    return b <= ss_tab_cap_ ? hipSuccess : hipErrorOutOfMemory;
-  }), "upload the tables of a sparse solve");
+int Engine::ss_release(SsState& s, const char* what) {
+  int rc;
+  if (!enter_release(s.tab || s.out || s.gramW, what, &rc)) return rc;
+  ss_drop(s);
   return 0;
 }
 
-// zero the touched rows of W, scatter the group's entries, the filtered sweeps `job` asks for (enqueue only);
-// returns the number of kernel launches
-int Engine::ss_enqueue(const SsGroup& g, const SsTables& t, int job, double* W) {
-  if (g_ss_poison.load())
-    (void)hipMemsetAsync(W, 0xFF, sizeof(double) * (size_t)g.rb * (size_t)S_->n, stream_);
-  launch_ss_zero(stream_, t.chunks, (int)(g.chunks.size() / 2), g.rb, W);
-  launch_ss_scatter(stream_, t.pos, t.val, (int64_t)g.pos.size(), W);
-  SolveTablesView tv = solve_tables();
-  tv.list = t.list;
-  tv.tiles = t.tiles;
-  if (job != 2)
-    for (size_t i = 0; i < g.fwd.size(); ++i) launch_solve_many(stream_, tv, g.fwd[i], g.fwd_i[i], W, g.rb);
-  const std::vector<SolveLaunch>& bwd = g.bwd_full ? sprog_.bwd : g.bwd;
-  const std::vector<SolveLaunchInfo>& bwd_i = g.bwd_full ? sv_bwd_ : g.bwd_i;
-  const SolveTablesView tb = g.bwd_full ? solve_tables() : tv;
-  if (job != 1)
-    for (size_t i = 0; i < bwd.size(); ++i) launch_solve_many(stream_, tb, bwd[i], bwd_i[i], W, g.rb);
-  return (g.chunks.empty() ? 0 : 1) + (g.pos.empty() ? 0 : 1) + (int)(job != 2 ? g.fwd.size() : 0) +
-         (int)(job != 1 ? bwd.size() : 0);
+int Engine::release_solve_sparse() { return ss_release(ss_, "solve_sparse release"); }
+int Engine::release_solve_sparse_batch() { return ss_release(bss_, "solve_sparse_batch release"); }
+
+// the slots of the batch's own program (once), the workspace of the blocked batch solve and the order table
+int Engine::bss_enter() {
+  if (!bss_.slots_ready) {
+    bss_.slots = build_solve_slots(bt_.sprog);
+    bss_.slots_ready = true;
+  }
+  if (!bss_.slots.ok) {
+    feature_err_ = std::string("solve_sparse_batch") + kSsShape;
+    return -99;
+  }
+  return prepare_solve_many_batch();
 }
+
+// the three buffers of a call, kept while each is large enough; else all three again in ONE transaction (a
+// failure leaves none of them)
+int Engine::bss_take(size_t tab_bytes, size_t out_elems, size_t gram_elems, const char* what) {
+  if (bss_.tab && bss_.tab_cap >= tab_bytes && bss_.out_cap >= out_elems && bss_.gram_cap >= gram_elems) return 0;
+  tab_bytes = std::max(tab_bytes, bss_.tab_cap);
+  out_elems = std::max(out_elems, bss_.out_cap);
+  gram_elems = std::max(gram_elems, bss_.gram_cap);
+  ss_drop(bss_);
+  auto t = take();
+  t(&bss_.tab, std::max<size_t>(tab_bytes, 8));
+  if (out_elems) t(&bss_.out, sizeof(double) * out_elems);
+  if (gram_elems) t(&bss_.gramW, sizeof(double) * gram_elems);
+  if (!t.ok()) {
+    feature_err_ = std::string(what) + ": not enough device memory for the tables, the outputs and the workspaces of " +
+                   std::to_string(bt_.nbatch) + " members (" + std::to_string(t.bytes() >> 20) + " MiB): " +
+                   hipGetErrorString(t.error());
+    return alloc_code(t.error());
+  }
+  t.commit();
+  bss_.tab_cap = tab_bytes;
+  bss_.out_cap = out_elems;
+  bss_.gram_cap = gram_elems;
+  return 0;
+}
+
+// What the two backends of the sequence share: the columns of the call, planning and upload of a group on the
+// backend's program, the copies to a host caller (member b's column q of a group: on the device at
+// x + (b k + c0 + q) ldx, else packed in the output buffer), the checks.
+struct Engine::SsBackend {
+  using Group = SsGroup;
+  Engine& e;
+  const std::string what;
+  const SolveProgram& prog;
+  const SolveSlots& slots;
+  const bool launch_info;   // the kernels take a SolveLaunchInfo per filtered launch
+  SsState& st;
+  double* const W0;
+  const int cap, members;
+  const int *bptr, *brow;
+  const double* bval;
+  const int64_t ldb;        // between the members' sets of values; 0: one set
+  const int nsel;
+  const int* sel;
+  const int n = e.S_->n;
+  const hipStream_t s = e.stream_;
+  const size_t copies = ldb ? (size_t)members : 1;
+  SolveSparsePlan rows;     // gram: of the whole call
+  SsTables t{};             // of the group uploaded last
+
+  int fail(int code, const char* w, hipError_t err) { return e.fail(code, w, err); }
+  void plan_rows(int k) {
+    static const int none = 0;
+    build_solve_sparse_plan(*e.S_, 0, k, bptr, brow, 0, &none, 1, rows);
+  }
+  SsGroup plan(int c0, int nv, int rb, int job, bool gram) {
+    static const int none = 0;
+    SsGroup g;
+    g.c0 = c0, g.nv = nv, g.rb = rb;
+    if (gram) e.ss_plan_group(prog, slots, launch_info, g, bptr, brow, 0, &none, 1, &rows.range);
+    else e.ss_plan_group(prog, slots, launch_info, g, bptr, brow, nsel, sel, job, nullptr);
+    g.bytes = ss_table_bytes(g, copies);
+    return g;
+  }
+  int upload(const SsGroup& g) { return e.ss_upload(st, g, bval, ldb, copies, t); }
+  int launch_check() {
+    HIPCHK(hipGetLastError(), (what + " launch").c_str());
+    return 0;
+  }
+  int sync() { return e.sync_stream(s, (what + " sync").c_str()); }
+  int copy_out(const SsGroup& g, const SsSolveCall& c) {
+    for (int b = 0; b < members; ++b)
+      if (int rc = e.copy_vectors(false, st.out + (int64_t)b * g.nv * c.nout, c.x + ((int64_t)b * c.k + g.c0) * c.ldx, c.ldx,
+                                  g.nv, "x D2H", c.nout))
+        return rc;
+    return 0;
+  }
+  int copy_gram(double* G, double* gout, int64_t ldg, int k) {
+    return e.copy_vectors(false, G, gout, ldg, (int64_t)members * k, "G D2H", k);
+  }
+  int overflow() {
+    e.feature_err_ = what + ": a launch has more work items for one member than a grid holds (the outputs are not all "
+                            "written)";
+    return -99;
+  }
+};
+
+// The single handle: its own program and launch infos, the workspace of solve_many, three buffers that grow.
+struct Engine::SsHandleBackend : Engine::SsBackend {
+  SsHandleBackend(Engine& e, const char* what, const int* bptr, const int* brow, const double* bval, int nsel,
+                  const int* sel)
+      : SsBackend{e, what, e.sprog_, e.sv_slots_, true, e.ss_, e.d_smW_, 32, 1, bptr, brow, bval, 0, nsel, sel} {}
+
+  // (the capacities are in elements: bytes of the tables, doubles of the other two)
+  int take(size_t tab_bytes, size_t out_elems, size_t gram_elems) {
+    hipError_t err = e.grow(&st.tab, &st.tab_cap, tab_bytes);
+    if (err == hipSuccess && out_elems) err = e.grow(&st.out, &st.out_cap, out_elems);
+    if (err == hipSuccess && gram_elems) err = e.grow(&st.gramW, &st.gram_cap, gram_elems);
+    if (err != hipSuccess) {
+      e.ss_drop(st);
+      e.feature_err_ = what + ": not enough device memory (" +
+                       std::to_string((tab_bytes + sizeof(double) * (out_elems + gram_elems)) >> 20) + " MiB): " +
+                       hipGetErrorString(err);
+      return alloc_code(err);
+    }
+    for (int64_t& v : st.info) v = 0;
+    return 0;
+  }
+  // zero the touched rows of W, scatter the group's entries, the filtered sweeps `job` asks for (enqueue only)
+  int enqueue(const SsGroup& g, int job, double* W) {
+    if (g_ss_poison.load()) (void)hipMemsetAsync(W, 0xFF, sizeof(double) * (size_t)g.rb * (size_t)n, s);
+    launch_ss_zero(s, t.chunks, (int)(g.chunks.size() / 2), g.rb, W);
+    launch_ss_scatter(s, t.pos, t.val, (int64_t)g.pos.size(), W);
+    SolveTablesView tv = e.solve_tables();
+    tv.list = t.list;
+    tv.tiles = t.tiles;
+    if (job != 2)
+      for (size_t i = 0; i < g.fwd.size(); ++i) launch_solve_many(s, tv, g.fwd[i], g.fwd_i[i], W, g.rb);
+    const std::vector<SolveLaunch>& bwd = g.bwd_full ? prog.bwd : g.bwd;
+    const std::vector<SolveLaunchInfo>& bwd_i = g.bwd_full ? e.sv_bwd_ : g.bwd_i;
+    const SolveTablesView tb = g.bwd_full ? e.solve_tables() : tv;
+    if (job != 1)
+      for (size_t i = 0; i < bwd.size(); ++i) launch_solve_many(s, tb, bwd[i], bwd_i[i], W, g.rb);
+    return (g.chunks.empty() ? 0 : 1) + (g.pos.empty() ? 0 : 1) + (int)(job != 2 ? g.fwd.size() : 0) +
+           (int)(job != 1 ? bwd.size() : 0);
+  }
+  int gather(const SsGroup& g, const SsSolveCall& c) {
+    double* xg = c.dev ? c.x + (int64_t)g.c0 * c.ldx : st.out;
+    const int64_t ldo = c.dev ? c.ldx : c.nout;
+    if (c.all) launch_solve_many_unpack(s, xg, ldo, e.d_order_, n, g.nv, g.rb, W0);
+    else launch_ss_gather(s, xg, ldo, t.selpos, nsel, g.nv, g.rb, W0);
+    return 1;
+  }
+  int pair(const SsGroup& gi, const SsGroup& gj, double* WI, double* WJ, int nchunk, double* part, bool diag, double* Gij,
+           double* Gji, int64_t ld) {
+    launch_ss_gram(s, t.chunks, nchunk, WI, gi.rb, WJ, gj.rb, part);
+    launch_ss_gram_reduce(s, part, nchunk, gi.nv, gj.nv, diag, Gij, Gji, ld);
+    return nchunk ? 2 : 1;
+  }
+  // (a failed call leaves the sums of the groups it completed)
+  void progress(const int64_t info[6]) { std::copy(info, info + 6, st.info); }
+  int finish(const int64_t*) { return 0; }
+};
+
+// The members of a batch: the batch's program on the workspaces of its blocked solve, every launch carrying all
+// members and able to overflow a grid, one transaction for the three buffers.
+struct Engine::SsBatchBackend : Engine::SsBackend {
+  const int k;
+  const BatchView v = e.batch_view();
+  const BssView bs{e.bt_.flag, members};
+
+  SsBatchBackend(Engine& e, const char* what, int k, const int* bptr, const int* brow, const double* bval, int64_t ldb,
+                 int nsel, const int* sel)
+      : SsBackend{e,    what, e.bt_.sprog, e.bss_.slots, false, e.bss_, e.d_bsmW_, e.bsm_rb_, e.bt_.nbatch,
+                  bptr, brow, bval,        ldb,          nsel,  sel},
+        k(k) {}
+
+  // (one aligned slot more than the tables take, as this path has requested from its first version: the ledger
+  // of a call is part of what the tests record)
+  int take(size_t tab_bytes, size_t out_elems, size_t gram_elems) {
+    return e.bss_take(tab_bytes + 256, out_elems, gram_elems, what.c_str());
+  }
+  // poison (debug), zero, scatter and the filtered sweeps `job` asks for on the workspaces W (enqueue only);
+  // launches made, -1: a launch overflows a grid
+  int enqueue(const SsGroup& g, int job, double* W) {
+    const int64_t ws = (int64_t)g.rb * n, ldv = ldb ? (int64_t)g.pos.size() : 0;
+    if (g_bss_poison.load()) {
+      const size_t elems =
+          W == W0 ? (size_t)e.bsm_capacity_ * (size_t)e.bsm_rb_ * (size_t)n : (size_t)members * 32 * (size_t)n;
+      (void)hipMemsetAsync(W, 0xFF, sizeof(double) * elems, s);
+    }
+    int nl = 0;
+    bool fits = true;
+    auto count = [&](int made) { if (made < 0) fits = false; else nl += made; };
+    count(launch_bss_zero(s, bs, t.chunks, (int)(g.chunks.size() / 2), g.rb, W, ws));
+    count(launch_bss_scatter(s, bs, t.pos, t.val, ldv, (int64_t)g.pos.size(), W, ws));
+    if (job != 2)
+      for (const SolveLaunch& l : g.fwd)
+        count(launch_batch_solve_many(s, v, l, t.list, t.tiles, e.bt_.sunits, e.d_rlist_, W, g.rb, n));
+    if (job != 1) {
+      // (all entries wanted: the program's own backward launches on the resident tables of the batch)
+      const std::vector<SolveLaunch>& bwd = g.bwd_full ? prog.bwd : g.bwd;
+      for (const SolveLaunch& l : bwd)
+        count(launch_batch_solve_many(s, v, l, g.bwd_full ? e.bt_.slist : t.list, g.bwd_full ? e.bt_.stiles : t.tiles,
+                                      e.bt_.sunits, e.d_rlist_, W, g.rb, n));
+    }
+    return fits ? nl : -1;
+  }
+  // (all entries: the order table is the list of wanted positions)
+  int gather(const SsGroup& g, const SsSolveCall& c) {
+    double* xg = c.dev ? c.x + (int64_t)g.c0 * c.ldx : st.out;
+    const int64_t ldo = c.dev ? c.ldx : c.nout, xs = c.dev ? (int64_t)k * c.ldx : (int64_t)g.nv * c.nout;
+    return launch_bss_gather(s, bs, xg, xs, ldo, c.all ? e.d_order_ : t.selpos, c.nout, g.nv, g.rb, W0, (int64_t)g.rb * n);
+  }
+  int pair(const SsGroup& gi, const SsGroup& gj, double* WI, double* WJ, int nchunk, double* part, bool diag, double* Gij,
+           double* Gji, int64_t ld) {
+    const int a = launch_bss_gram(s, bs, t.chunks, nchunk, WI, (int64_t)gi.rb * n, gi.rb, WJ, (int64_t)gj.rb * n, gj.rb, part);
+    if (a < 0) return -1;
+    const int b = launch_bss_gram_reduce(s, bs, part, nchunk, gi.nv, gj.nv, diag, Gij, Gji, (int64_t)k * ld, ld);
+    return b < 0 ? -1 : a + b;
+  }
+  void progress(const int64_t*) {}   // (a failed call leaves zeros)
+  int finish(const int64_t info[6]) {
+    std::copy(info, info + 6, st.info);
+    st.info[5] *= members;
+    for (int fl : e.bt_.hflag) ++st.info[fl == INT_MAX ? 6 : 7];
+    return e.batch_failed();
+  }
+};
 
 int Engine::solve_sparse(int k, const int* bptr, const int* brow, const double* bval, int nsel, const int* sel,
                          double* x, int64_t ldx, int job, bool dev) {
@@ -407,40 +622,8 @@ int Engine::solve_sparse(int k, const int* bptr, const int* brow, const double* 
   int rc = prepare_solve_many(false);
   if (rc) return rc;
   if ((rc = ss_filterable())) return rc;
-  // every group planned, filtered and staged on the host, and all device memory taken, before anything runs
-  const auto host_t0 = std::chrono::steady_clock::now();
-  std::vector<SsGroup> groups;
-  size_t tab_bytes = 0;
-  for_each_block(k, 32, [&](int done, int nv, int rb) {
-    SsGroup g;
-    g.c0 = done, g.nv = nv, g.rb = rb;
-    ss_plan_group(sprog_, sv_slots_, true, g, bptr, brow, bval, all ? -1 : nsel, all ? nullptr : sel, job, nullptr);
-    tab_bytes = std::max(tab_bytes, g.bytes);
-    groups.push_back(std::move(g));
-    return 0;
-  });
-  ss_host_us_ = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
-  const size_t out_bytes = dev ? 0 : sizeof(double) * (size_t)nout * 32;
-  hipError_t e = grow(&d_sstab_, &ss_tab_cap_, tab_bytes);
-  if (e == hipSuccess && !dev) e = grow(&d_ssout_, &ss_out_cap_, out_bytes / sizeof(double));
-  if (e != hipSuccess) return ss_fail_alloc("solve_sparse", tab_bytes + out_bytes, e);
-  for (int64_t& v : ss_info_) v = 0;
-  for (const SsGroup& g : groups) {
-    SsTables t{};
-    if ((rc = ss_upload(g, t))) return rc;
-    ss_info_[4] += 1 + ss_enqueue(g, t, job, d_smW_);   // (+ the gather)
-    double* xg = dev ? x + (int64_t)g.c0 * ldx : d_ssout_;
-    const int64_t ldg = dev ? ldx : nout;
-    if (all)
-      launch_solve_many_unpack(stream_, xg, ldg, d_order_, n, g.nv, g.rb, d_smW_);
-    else
-      launch_ss_gather(stream_, xg, ldg, t.selpos, nsel, g.nv, g.rb, d_smW_);
-    HIPCHK(hipGetLastError(), "solve_sparse launch");
-    if (!dev && (rc = copy_vectors(false, d_ssout_, x + (int64_t)g.c0 * ldx, ldx, g.nv, "x D2H", nout))) return rc;
-    if ((rc = sync_stream(stream_, "solve_sparse sync"))) return rc;   // (the next group reuses the tables)
-    for (int i = 0; i < 6; ++i) ss_info_[i] += g.info[i];
-  }
-  return 0;
+  SsHandleBackend be(*this, "solve_sparse", bptr, brow, bval, all ? -1 : nsel, all ? nullptr : sel);
+  return ss_solve_sequence(be, SsSolveCall{k, job, all, dev, x, ldx, nout});
 }
 
 int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* bval, double* g_host, int64_t ldg) {
@@ -459,179 +642,13 @@ int Engine::gram_sparse(int k, const int* bptr, const int* brow, const double* b
   int rc = prepare_solve_many(false);
   if (rc) return rc;
   if ((rc = ss_filterable())) return rc;
-  // the rows the products run over: those any column of the call touches, cleared in every group's workspace
-  static const int none = 0;
-  const auto host_t0 = std::chrono::steady_clock::now();
-  SolveSparsePlan U;
-  build_solve_sparse_plan(*S_, 0, k, bptr, brow, 0, &none, 1, U);
-  std::vector<SsGroup> groups;
-  size_t tab_bytes = 0;
-  for_each_block(k, 32, [&](int done, int nv, int rb) {
-    SsGroup g;
-    g.c0 = done, g.nv = nv, g.rb = rb;
-    ss_plan_group(sprog_, sv_slots_, true, g, bptr, brow, bval, 0, &none, 1, &U.range);
-    tab_bytes = std::max(tab_bytes, g.bytes);
-    groups.push_back(std::move(g));
-    return 0;
-  });
-  ss_host_us_ = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
-  const size_t ng = groups.size(), nchunk = groups[0].chunks.size() / 2;
-  const size_t wstride = (size_t)32 * (size_t)n;
-  const size_t gram_bytes = sizeof(double) * wstride * (ng - 1);
-  const size_t out_bytes = sizeof(double) * ((size_t)k * (size_t)k + nchunk * 1024);
-  hipError_t e = grow(&d_sstab_, &ss_tab_cap_, tab_bytes);
-  if (e == hipSuccess) e = grow(&d_ssout_, &ss_out_cap_, out_bytes / sizeof(double));
-  if (e == hipSuccess && ng > 1) e = grow(&d_ssgramW_, &ss_gram_cap_, gram_bytes / sizeof(double));
-  if (e != hipSuccess) return ss_fail_alloc("gram_sparse", tab_bytes + out_bytes + gram_bytes, e);
-  for (int64_t& v : ss_info_) v = 0;
-  auto workspace = [&](size_t gi) { return gi == 0 ? d_smW_ : d_ssgramW_ + (gi - 1) * wstride; };
-  SsTables t{};
-  for (size_t gi = 0; gi < ng; ++gi) {
-    const SsGroup& g = groups[gi];
-    if ((rc = ss_upload(g, t))) return rc;
-    ss_info_[4] += ss_enqueue(g, t, 1, workspace(gi));
-    HIPCHK(hipGetLastError(), "gram_sparse launch");
-    if ((rc = sync_stream(stream_, "gram_sparse sync"))) return rc;   // (the next group reuses the tables)
-    for (int i = 0; i < 6; ++i) ss_info_[i] += g.info[i];
-  }
-  // (the chunk list of the last group, the same in every group, is still in the tables)
-  double* dG = d_ssout_;
-  double* part = d_ssout_ + (size_t)k * (size_t)k;
-  for (size_t I = 0; I < ng; ++I)
-    for (size_t J = 0; J <= I; ++J) {
-      launch_ss_gram(stream_, t.chunks, (int)nchunk, workspace(I), groups[I].rb, workspace(J), groups[J].rb, part);
-      launch_ss_gram_reduce(stream_, part, (int)nchunk, groups[I].nv, groups[J].nv, I == J,
-                            dG + (size_t)groups[J].c0 * (size_t)k + groups[I].c0,
-                            dG + (size_t)groups[I].c0 * (size_t)k + groups[J].c0, (int64_t)k);
-      ss_info_[4] += nchunk ? 2 : 1;
-    }
-  HIPCHK(hipGetLastError(), "gram_sparse launch");
-  if ((rc = copy_vectors(false, dG, g_host, ldg, k, "G D2H", k))) return rc;
-  return sync_stream(stream_, "gram_sparse sync");
-}
-
-int Engine::release_solve_sparse() {
-  int rc;
-  if (!enter_release(d_sstab_ || d_ssout_ || d_ssgramW_, "solve_sparse release", &rc)) return rc;
-  give_back(d_sstab_, d_ssout_, d_ssgramW_);
-  ss_tab_cap_ = ss_out_cap_ = ss_gram_cap_ = 0;
-  return 0;
-}
-
-// ---- sparse right-hand sides for the members of a batch (batch_solve_sparse.hip) ---------------------
-static std::atomic<bool> g_bss_poison{false};
-void set_solve_sparse_batch_poison(bool on) { g_bss_poison.store(on); }
-
-void Engine::drop_solve_sparse_batch() {
-  give_back(bss_.tab, bss_.out, bss_.gramW);
-  bss_.tab_cap = bss_.out_cap = bss_.gram_cap = 0;
-}
-
-int Engine::release_solve_sparse_batch() {
-  int rc;
-  if (!enter_release(bss_.tab || bss_.out || bss_.gramW, "solve_sparse_batch release", &rc)) return rc;
-  drop_solve_sparse_batch();
-  return 0;
-}
-
-// the slots of the batch's own program (once), the workspace of the blocked batch solve and the order table
-int Engine::bss_enter(int* rb) {
-  if (!bss_.slots_ready) {
-    bss_.slots = build_solve_slots(bt_.sprog);
-    bss_.slots_ready = true;
-  }
-  if (!bss_.slots.ok) {
-    feature_err_ = std::string("solve_sparse_batch") + kSsShape;
-    return -99;
-  }
-  if (int rc = prepare_solve_many_batch()) return rc;
-  *rb = bsm_rb_;
-  return 0;
-}
-
-// the three buffers of a call, kept while each is large enough; else all three again in ONE transaction (a
-// failure leaves none of them)
-int Engine::bss_take(size_t tab_bytes, size_t out_elems, size_t gram_elems, const char* what) {
-  if (bss_.tab && bss_.tab_cap >= tab_bytes && bss_.out_cap >= out_elems && bss_.gram_cap >= gram_elems) return 0;
-  tab_bytes = std::max(tab_bytes, bss_.tab_cap);
-  out_elems = std::max(out_elems, bss_.out_cap);
-  gram_elems = std::max(gram_elems, bss_.gram_cap);
-  drop_solve_sparse_batch();
-  auto t = take();
-  t(&bss_.tab, std::max<size_t>(tab_bytes, 8));
-  if (out_elems) t(&bss_.out, sizeof(double) * out_elems);
-  if (gram_elems) t(&bss_.gramW, sizeof(double) * gram_elems);
-  if (!t.ok()) {
-    feature_err_ = std::string(what) + ": not enough device memory for the tables, the outputs and the workspaces of " +
-                   std::to_string(bt_.nbatch) + " members (" + std::to_string(t.bytes() >> 20) + " MiB): " +
-                   hipGetErrorString(t.error());
-    return alloc_code(t.error());
-  }
-  t.commit();
-  bss_.tab_cap = tab_bytes;
-  bss_.out_cap = out_elems;
-  bss_.gram_cap = gram_elems;
-  return 0;
-}
-
-// (the bytes bss_upload lays a group out in: the six lists of ss_plan_group with the values of all members last)
-static size_t bss_group_bytes(size_t list_bytes, size_t nvalues) {
-  return (list_bytes + 255) / 256 * 256 + std::max<size_t>(nvalues * sizeof(double), 8);
-}
-
-int Engine::bss_upload(const SsGroup& g, const double* bval, int64_t ldb, SsTables& t, int64_t* ldv) {
-  const size_t count = g.pos.size(), copies = ldb ? (size_t)bt_.nbatch : 1;
-  std::vector<double> vals(copies * count);
-  for (size_t b = 0; b < copies; ++b)
-    for (size_t i = 0; i < count; ++i) vals[b * count + i] = bval[(int64_t)b * ldb + g.ent[i]];
-  *ldv = ldb ? (int64_t)count : 0;
-  TableStager tab;
-  tab.add(&t.list, g.list);
-  tab.add(&t.tiles, g.tiles);
-  tab.add(&t.chunks, g.chunks);
-  tab.add(&t.selpos, g.selpos);
-  tab.add(&t.pos, g.pos);
-  tab.add(&t.val, vals);
-  char* blob = nullptr;
-  HIPCHK(tab.commit(&blob, [this](void** q, size_t b) {
-    *q = bss_.tab;
-    return b <= bss_.tab_cap ? hipSuccess : hipErrorOutOfMemory;
-  }), "upload the tables of a sparse solve of the batch");
-  return 0;
-}
-
-int Engine::bss_enqueue(const SsGroup& g, const SsTables& t, int64_t ldv, int job, double* W) {
-  const int n = S_->n, nbatch = bt_.nbatch;
-  const BatchView v = batch_view();
-  const BssView s{bt_.flag, nbatch};
-  const int64_t ws = (int64_t)g.rb * n;
-  if (g_bss_poison.load()) {
-    const size_t elems = W == d_bsmW_ ? (size_t)bsm_capacity_ * (size_t)bsm_rb_ * (size_t)n : (size_t)nbatch * 32 * (size_t)n;
-    (void)hipMemsetAsync(W, 0xFF, sizeof(double) * elems, stream_);
-  }
-  int nl = 0;
-  bool fits = true;
-  auto count = [&](int made) { if (made < 0) fits = false; else nl += made; };
-  count(launch_bss_zero(stream_, s, t.chunks, (int)(g.chunks.size() / 2), g.rb, W, ws));
-  count(launch_bss_scatter(stream_, s, t.pos, t.val, ldv, (int64_t)g.pos.size(), W, ws));
-  if (job != 2)
-    for (const SolveLaunch& l : g.fwd)
-      count(launch_batch_solve_many(stream_, v, l, t.list, t.tiles, bt_.sunits, d_rlist_, W, g.rb, n));
-  if (job != 1) {
-    // (all entries wanted: the program's own backward launches on the resident tables of the batch)
-    const std::vector<SolveLaunch>& bwd = g.bwd_full ? bt_.sprog.bwd : g.bwd;
-    for (const SolveLaunch& l : bwd)
-      count(launch_batch_solve_many(stream_, v, l, g.bwd_full ? bt_.slist : t.list, g.bwd_full ? bt_.stiles : t.tiles,
-                                    bt_.sunits, d_rlist_, W, g.rb, n));
-  }
-  return fits ? nl : -1;
+  SsHandleBackend be(*this, "gram_sparse", bptr, brow, bval, -1, nullptr);
+  return ss_gram_sequence(be, k, false, g_host, ldg);
 }
 
 static const char* const kBssRepro =
     "not available while the reproducible batch is switched on (spllt_hip_set_batch_reproducible): the filtered sweeps "
     "run the kernels that add with atomics";
-static const char* const kBssGrid = ": a launch has more work items for one member than a grid holds (the outputs are "
-                                    "not all written)";
 
 int Engine::solve_sparse_batch(int k, const int* bptr, const int* brow, const double* bval, int64_t ldb, int nsel,
                                const int* sel, double* x, int64_t ldx, int job, bool dev) {
@@ -651,56 +668,9 @@ int Engine::solve_sparse_batch(int k, const int* bptr, const int* brow, const do
   for (int64_t& v : bss_.info) v = 0;
   if (k == 0 || nout == 0 || n == 0) return 0;
   HIPCHK(hipSetDevice(device_), "hipSetDevice");
-  int rc, cap = 32;
-  if ((rc = bss_enter(&cap))) return rc;
-  // every group planned, filtered and staged on the host, and all device memory taken, before anything runs
-  const auto host_t0 = std::chrono::steady_clock::now();
-  std::vector<SsGroup> groups;
-  size_t tab_bytes = 0;
-  for_each_block(k, cap, [&](int done, int nv, int rb) {
-    SsGroup g;
-    g.c0 = done, g.nv = nv, g.rb = rb;
-    ss_plan_group(bt_.sprog, bss_.slots, false, g, bptr, brow, nullptr, all ? -1 : nsel, all ? nullptr : sel, job, nullptr);
-    tab_bytes = std::max(tab_bytes, bss_group_bytes(g.bytes, (ldb ? (size_t)nbatch : 1) * g.pos.size()));
-    groups.push_back(std::move(g));
-    return 0;
-  });
-  bss_.host_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
-  const size_t out_elems = dev ? 0 : (size_t)nbatch * 32 * (size_t)nout;
-  if ((rc = bss_take(tab_bytes, out_elems, 0, "solve_sparse_batch"))) return rc;
-  const BssView s{bt_.flag, nbatch};
-  int64_t info[6] = {0, 0, 0, 0, 0, 0};
-  bool fits = true;
-  for (const SsGroup& g : groups) {
-    SsTables t{};
-    int64_t ldv = 0;
-    if ((rc = bss_upload(g, bval, ldb, t, &ldv))) return rc;
-    const int made = bss_enqueue(g, t, ldv, job, d_bsmW_);
-    // member b's column q of the group: on the device at x + (b k + c0 + q) ldx, else packed in the output buffer
-    double* xg = dev ? x + (int64_t)g.c0 * ldx : bss_.out;
-    const int64_t ldo = dev ? ldx : nout, xs = dev ? (int64_t)k * ldx : (int64_t)g.nv * nout;
-    // (all entries: the order table is the list of wanted positions)
-    const int out = made < 0 ? -1
-                             : launch_bss_gather(stream_, s, xg, xs, ldo, all ? d_order_ : t.selpos, nout, g.nv, g.rb,
-                                                 d_bsmW_, (int64_t)g.rb * n);
-    HIPCHK(hipGetLastError(), "solve_sparse_batch launch");
-    if (made < 0 || out < 0) fits = false;
-    for (int b = 0; fits && !dev && b < nbatch; ++b)
-      if ((rc = copy_vectors(false, bss_.out + (int64_t)b * xs, x + ((int64_t)b * k + g.c0) * ldx, ldx, g.nv, "x D2H", nout)))
-        return rc;
-    if ((rc = sync_stream(stream_, "solve_sparse_batch sync"))) return rc;   // (the next group reuses the tables)
-    if (!fits) {
-      feature_err_ = std::string("solve_sparse_batch") + kBssGrid;
-      return -99;
-    }
-    info[4] += made + out;
-    for (int i = 0; i < 6; ++i)
-      if (i != 4) info[i] += g.info[i];
-  }
-  for (int i = 0; i < 6; ++i) bss_.info[i] = info[i];
-  bss_.info[5] *= nbatch;
-  for (int fl : bt_.hflag) ++bss_.info[fl == INT_MAX ? 6 : 7];
-  return batch_failed();
+  if (int rc = bss_enter()) return rc;
+  SsBatchBackend be(*this, "solve_sparse_batch", k, bptr, brow, bval, ldb, all ? -1 : nsel, all ? nullptr : sel);
+  return ss_solve_sequence(be, SsSolveCall{k, job, all, dev, x, ldx, nout});
 }
 
 int Engine::gram_sparse_batch(int k, const int* bptr, const int* brow, const double* bval, int64_t ldb, double* gout,
@@ -729,74 +699,9 @@ int Engine::gram_sparse_batch(int k, const int* bptr, const int* brow, const dou
       for (int i = 0; i < k; ++i) gout[c * ldg + i] = 0.0;
     return 0;
   }
-  int rc, cap = 32;
-  if ((rc = bss_enter(&cap))) return rc;
-  // the rows the products run over: those any column of the call touches, cleared in every group's workspace
-  static const int none = 0;
-  const auto host_t0 = std::chrono::steady_clock::now();
-  SolveSparsePlan U;
-  build_solve_sparse_plan(*S_, 0, k, bptr, brow, 0, &none, 1, U);
-  std::vector<SsGroup> groups;
-  size_t tab_bytes = 0;
-  for_each_block(k, cap, [&](int done, int nv, int rb) {
-    SsGroup g;
-    g.c0 = done, g.nv = nv, g.rb = rb;
-    ss_plan_group(bt_.sprog, bss_.slots, false, g, bptr, brow, nullptr, 0, &none, 1, &U.range);
-    tab_bytes = std::max(tab_bytes, bss_group_bytes(g.bytes, (ldb ? (size_t)nbatch : 1) * g.pos.size()));
-    groups.push_back(std::move(g));
-    return 0;
-  });
-  bss_.host_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count();
-  const size_t ng = groups.size(), nchunk = groups[0].chunks.size() / 2;
-  // one workspace per group and member: the first group's is the batch's own, the others' are taken here
-  const size_t gstride_w = (size_t)nbatch * 32 * (size_t)n;
-  const size_t g_elems = dev ? 0 : (size_t)nbatch * (size_t)k * (size_t)k;
-  if ((rc = bss_take(tab_bytes, g_elems + (size_t)nbatch * nchunk * 1024, gstride_w * (ng - 1), "gram_sparse_batch")))
-    return rc;
-  auto workspace = [&](size_t gi) { return gi == 0 ? d_bsmW_ : bss_.gramW + (gi - 1) * gstride_w; };
-  const BssView s{bt_.flag, nbatch};
-  int64_t info[6] = {0, 0, 0, 0, 0, 0};
-  auto overflow = [&]() {
-    feature_err_ = std::string("gram_sparse_batch") + kBssGrid;
-    return -99;
-  };
-  SsTables t{};
-  for (size_t gi = 0; gi < ng; ++gi) {
-    const SsGroup& g = groups[gi];
-    int64_t ldv = 0;
-    if ((rc = bss_upload(g, bval, ldb, t, &ldv))) return rc;
-    const int made = bss_enqueue(g, t, ldv, 1, workspace(gi));
-    HIPCHK(hipGetLastError(), "gram_sparse_batch launch");
-    if ((rc = sync_stream(stream_, "gram_sparse_batch sync"))) return rc;   // (the next group reuses the tables)
-    if (made < 0) return overflow();
-    info[4] += made;
-    for (int i = 0; i < 6; ++i)
-      if (i != 4) info[i] += g.info[i];
-  }
-  // (the chunk list of the last group, the same in every group, is still in the tables)
-  double* dG = dev ? gout : bss_.out;
-  const int64_t ldo = dev ? ldg : (int64_t)k;
-  double* part = bss_.out + g_elems;
-  bool fits = true;
-  for (size_t I = 0; I < ng && fits; ++I)
-    for (size_t J = 0; J <= I && fits; ++J) {
-      const int a = launch_bss_gram(stream_, s, t.chunks, (int)nchunk, workspace(I), (int64_t)groups[I].rb * n, groups[I].rb,
-                                    workspace(J), (int64_t)groups[J].rb * n, groups[J].rb, part);
-      const int b = a < 0 ? -1
-                          : launch_bss_gram_reduce(stream_, s, part, (int)nchunk, groups[I].nv, groups[J].nv, I == J,
-                                                   dG + (int64_t)groups[J].c0 * ldo + groups[I].c0,
-                                                   dG + (int64_t)groups[I].c0 * ldo + groups[J].c0, (int64_t)k * ldo, ldo);
-      if (a < 0 || b < 0) fits = false;
-      else info[4] += a + b;
-    }
-  HIPCHK(hipGetLastError(), "gram_sparse_batch launch");
-  if (fits && !dev && (rc = copy_vectors(false, dG, gout, ldg, (int64_t)nbatch * k, "G D2H", k))) return rc;
-  if ((rc = sync_stream(stream_, "gram_sparse_batch sync"))) return rc;
-  if (!fits) return overflow();
-  for (int i = 0; i < 6; ++i) bss_.info[i] = info[i];
-  bss_.info[5] *= nbatch;
-  for (int fl : bt_.hflag) ++bss_.info[fl == INT_MAX ? 6 : 7];
-  return batch_failed();
+  if (int rc = bss_enter()) return rc;
+  SsBatchBackend be(*this, "gram_sparse_batch", k, bptr, brow, bval, ldb, -1, nullptr);
+  return ss_gram_sequence(be, k, dev, gout, ldg);
 }
 
 // ---- reproducible solve ----------------------------------------------------------------------------
